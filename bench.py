@@ -13,6 +13,13 @@ For N > 1 the same problem is column-sharded over the ranks (strong scaling), on
 per sweep.  Launched as one rank per GPU by torch.distributed.run - or, when called without a
 rank environment, by bench.py itself, which then starts that command as a child process.  Rank 0
 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, W warm-up sweeps, K timed sweeps (no
+instrumentation inside them), the result line.  `--full` adds the secondary measurements as
+before: wall-clock-to-eps (Init breakdown, sweeps to OPTIMAL), HIP-event kernel timers in the
+timed region with the roofline and its measured HBM ceilings, and the CPU baselines.
+`--dump-outputs DIR` writes what the last timed sweep left (the iterates a caller of
+Solver.result() receives, and the residuals of the status) as DIR/<name>.npy in float64.
 """
 
 import argparse
@@ -41,11 +48,15 @@ def parse():
     p.add_argument("--m", "--rows", dest="m", type=int, default=10000)
     p.add_argument("--n", "--cols", dest="n", type=int, default=50000)
     p.add_argument("--dtype", default="f32", choices=["f32", "f64"])
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-time-to-eps", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also measure time-to-eps, the per-kernel timers / roofline and the CPU baselines")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the iterates and residuals of the last timed sweep to DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    p.add_argument("--no-time-to-eps", action="store_true", help="with --full: skip wall-clock-to-eps")
     p.add_argument("--no-profile", action="store_true",
-                   help="diagnostic: no HIP-event kernel timers in the timed region (no roofline)")
-    p.add_argument("--profile-all", action="store_true", help="time every tagged kernel")
+                   help="with --full, diagnostic: no HIP-event kernel timers in the timed region (no roofline)")
+    p.add_argument("--profile-all", action="store_true", help="with --full: time every tagged kernel")
     p.add_argument("--comm", default="rccl", choices=["rccl", "host"],
                    help="host: rehearsal of the N > 1 path on fewer GPUs than ranks (gloo + "
                         "host-callback collectives, ranks share devices) - not a judged configuration")
@@ -248,6 +259,35 @@ def cpu_baseline(At, b, lam, iters_to_eps=None, budget_s=10.0):
     return one, allc
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, status_bytes, xs):
+    """The solver's result as DIR/<name>.npy, float64: every variable (name = its id with
+    characters other than [A-Za-z0-9_.-] replaced by '_') and, where the status carries them,
+    `residuals` = [r_norm, s_norm, epsilon_primal, epsilon_dual].  Over 64 MB in all, every
+    variable is cut to the same fixed, seeded, sorted sample of its indices (saved as
+    `sample_index`)."""
+    from epsilon_amd import wire
+    r = wire.SolverStatus.FromString(status_bytes).residuals
+    arrays = {}
+    if r is not None:
+        arrays["residuals"] = np.array([r.r_norm, r.s_norm, r.epsilon_primal, r.epsilon_dual], dtype=np.float64)
+    for k in sorted(xs):
+        name = "".join(ch if ch.isalnum() or ch in "_.-" else "_" for ch in k)
+        arrays[name] = np.frombuffer(xs[k], dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        n_min = min(a.size for k, a in arrays.items() if k != "residuals")
+        keep = max(1, (DUMP_LIMIT_BYTES // 2) // (8 * len(xs)))
+        idx = np.sort(np.random.RandomState(0).choice(n_min, size=min(keep, n_min), replace=False))
+        arrays = {k: (a if k == "residuals" else a[idx]) for k, a in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     args = parse()
     # `python bench.py --gpus N` without a rank environment: start the N ranks as a child
@@ -383,7 +423,7 @@ def main():
         out["peer_window_validation"] = ("31 sweeps each way on this problem: residuals within 1e-3, iterates "
                                          "within 1e-3 of the largest entry" if peer_on else "failed - " + (why_not or "on a peer rank"))
     # ---- wall-clock-to-eps at the reference defaults (benchmark.py:130-136: max_iterations 50000)
-    if not args.no_time_to_eps and args.rehearse_ranks <= 1:
+    if args.full and not args.no_time_to_eps and args.rehearse_ranks <= 1:
         s = new_solver(wire.SolverParams(max_iterations=50000))
         # two HIP-event brackets inside Init: the Gram SYRK (the MFMA contraction of the
         # least-squares prox) and the explicit inverse
@@ -445,15 +485,17 @@ def main():
     params = wire.SolverParams(max_iterations=10 ** 9, ignore_stopping_criteria=True)
     s = new_solver(params)
     s.init()
-    # live HIP-event timers only around the dominant kernel (each bracket costs ~1 us of stream
-    # time; timing every small kernel would tax the sweep being measured by ~7 %)
+    # --full: live HIP-event timers only around the dominant kernel (each bracket costs ~1 us of
+    # stream time; timing every small kernel would tax the sweep being measured by ~7 %).  A plain
+    # run times the sweeps without them.
+    profile = args.full and not args.no_profile
     _solve.set_option("profile_filter",
                       "" if args.profile_all else "lasso_fused,gemv_n:%dx%d" % (m, At.shape[0]))
     # With the peer window the sweeps between residual checks are replayed from hipGraphs, which
     # carry no events: the timed region then runs un-instrumented and the kernel durations come
     # from a second, eager region of the same K sweeps.
     graph_mode = sharded and peer_on and os.environ.get("EPSILON_HIP_GRAPH", "") != "0"
-    _solve.profile_enable(not args.no_profile and not graph_mode)
+    _solve.profile_enable(profile and not graph_mode)
     s.run(args.warmup)
     _solve.profile_reset()
     barrier()
@@ -462,7 +504,9 @@ def main():
     barrier()
     dt = time.time() - t0
     assert done == args.steps, (done, args.steps)
-    if graph_mode and not args.no_profile:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *s.result())
+    if graph_mode and profile:
         _solve.set_option("profile_filter", "lasso_fused,peer_,symv")
         _solve.profile_enable(True)
         _solve.profile_reset()
@@ -563,15 +607,16 @@ def main():
         "config": {"workload": "lasso m=%d n=%d dense %s, PROX_ADMM, x0 density 0.01" % (m, n, args.dtype),
                    "parallelism": "1 GPU" if world == 1 else "column-sharded x%d, 1 all-reduce/sweep" % world,
                    **({"comm": comm_used} if sharded else {})},
-        "roofline": roofline,
         "sweep": {"moved_bytes_per_sweep_per_gpu": moved_sweep,
                   "moved_GBs": moved_sweep / (ms_per_step * 1e-3) / 1e9,
                   "frac_on_moved_bytes": moved_sweep / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
                   "two_pass_algorithmic_bytes_per_sweep_per_gpu": sweep_bytes,
                   "two_pass_equivalent_GBs": sweep_bytes / (ms_per_step * 1e-3) / 1e9},
-        "kernels": {k: {"launches": c, "avg_ms": t / c} for k, (c, t) in prof.items() if c},
     })
-    if world == 1 and not args.no_cpu_baseline and not args.force_sharded:
+    if args.full:
+        out["roofline"] = roofline
+        out["kernels"] = {k: {"launches": c, "avg_ms": t / c} for k, (c, t) in prof.items() if c}
+    if args.full and world == 1 and not args.no_cpu_baseline and not args.force_sharded:
         one, allc = cpu_baseline(At, b, lam, iters_to_eps=out.get("iters_to_eps"))
         out["cpu_baseline"] = one
         out["cpu_baseline_all_cores"] = allc

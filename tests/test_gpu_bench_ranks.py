@@ -30,7 +30,8 @@ def _free_port():
 
 
 def _bench(ranks, self_launch=False):
-    common = ["--no-cpu-baseline", "--steps", "20", "--warmup", "5"]
+    # --full: iters_to_eps / state_at_eps come from the wall-clock-to-eps leg
+    common = ["--full", "--no-cpu-baseline", "--steps", "20", "--warmup", "5"]
     if ranks == 1:
         cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + common
     elif self_launch:

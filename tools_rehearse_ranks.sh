@@ -5,6 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
 tag=$1; shift
 ranks=$1; shift
+set -- --full "$@"  # the summary at the end reads time-to-eps, a --full measurement
 port=$((29600 + RANDOM % 300))
 if [ "$ranks" = 1 ]; then
   timeout -k 10 300 python bench.py --no-cpu-baseline --steps 50 --warmup 5 "$@" > gpurun_out/reh_$tag.json 2> gpurun_out/reh_$tag.err
