@@ -1,0 +1,110 @@
+"""Batched solves on one data matrix (eps_solve_batch): a lambda path of K lasso instances on the
+config-2 data (problems.regression_data(10000, 50000), fp32, 1 GPU).
+
+One JSON line per K in --ks:
+  ms_per_batched_sweep      loop time of a fixed number of batched sweeps / sweeps
+  instance_sweeps_per_s     K * sweeps / loop time (single path: sweeps / loop time of one solve)
+  passes_per_sweep          launches of the batched pass per sweep (profile tags, short run)
+  init_s                    Init of all K instances in the batch (one Gram product + inverse)
+  wall_to_optimal_s         solve_batch to OPTIMAL, whole call
+  single_*                  the same K instances by K _solve.solve calls
+
+    python bench_batch.py [--ks 1,2,4,8] [--steps 100] [--warmup 10] [--m 10000 --n 50000]
+"""
+
+import argparse
+import json
+import math
+import time
+
+import numpy as np
+
+from epsilon_amd import _solve, ir, problems, wire
+
+FRACS = (0.5, 0.35, 0.25, 0.18, 0.13, 0.09, 0.065, 0.045)  # lambda / lambda_max of the path
+
+
+def parse():
+    p = argparse.ArgumentParser()
+    p.add_argument("--ks", default="1,2,4,8")
+    p.add_argument("--steps", type=int, default=100)
+    p.add_argument("--warmup", type=int, default=10)
+    p.add_argument("--m", type=int, default=10000)
+    p.add_argument("--n", type=int, default=50000)
+    return p.parse_args()
+
+
+def status(st):
+    return wire.SolverStatus.FromString(st)
+
+
+def main():
+    a = parse()
+    _solve.set_option("dtype", "f32")
+    A, b = problems.regression_data(a.m, a.n, seed=0)
+    lmax = float(np.abs(A.T.dot(b)).max())
+    Aexpr, bexpr = ir.dense_matrix(A), ir.constant(b)
+    probs = [problems.lasso_ir(Aexpr, bexpr, f * lmax, a.n) for f in FRACS]
+    data = {}
+    for p in probs:
+        data.update(p.expression_data())
+    del A
+    pbs = [p.SerializeToString() for p in probs]
+    fixed = wire.SolverParams(max_iterations=a.steps, ignore_stopping_criteria=True).SerializeToString()
+    to_opt = wire.SolverParams().SerializeToString()
+    if a.warmup > 0:
+        _solve.solve_batch(pbs[:2], None, wire.SolverParams(max_iterations=a.warmup).SerializeToString(), data)
+    for K in [int(k) for k in a.ks.split(",")]:
+        sub = pbs[:K]
+        # fixed sweeps: batched loop time and Init
+        res = _solve.solve_batch(sub, None, fixed, data)
+        sts = [status(st) for st, _ in res]
+        loop = sts[0].timing.total_time - sts[0].timing.init_time
+        init = sum(s.timing.init_time for s in sts)
+        # passes per sweep from the profile tags of a short run
+        _solve.profile_reset()
+        _solve.profile_enable(True)
+        short = 10
+        _solve.solve_batch(sub, None, wire.SolverParams(max_iterations=short, ignore_stopping_criteria=True)
+                           .SerializeToString(), data)
+        tags = _solve.profile_dump()
+        _solve.profile_enable(False)
+        passes = sum(c for t, (c, _) in tags.items() if t.split(":")[0] == "batch_fused_pass") / short
+        # to OPTIMAL
+        t0 = time.perf_counter()
+        res_opt = _solve.solve_batch(sub, None, to_opt, data)
+        wall = time.perf_counter() - t0
+        # the same instances one by one
+        single_loop, single_init, single_sweeps = 0.0, 0.0, 0
+        for pb in sub:
+            s = status(_solve.solve(pb, [], fixed, data)[0])
+            single_loop += s.timing.total_time - s.timing.init_time
+            single_init += s.timing.init_time
+            single_sweeps += a.steps
+        t0 = time.perf_counter()
+        res_single = [_solve.solve(pb, [], to_opt, data) for pb in sub]
+        single_wall = time.perf_counter() - t0
+        out = dict(
+            bench="batch_lambda_path", m=a.m, n=a.n, dtype="f32", gpus=1, K=K,
+            lambda_over_lambda_max=list(FRACS[:K]), lambda_max=lmax, sweeps=a.steps,
+            ms_per_batched_sweep=1e3 * loop / a.steps,
+            instance_sweeps_per_s=K * a.steps / loop,
+            passes_per_sweep=passes,
+            instances_per_pass=(K if passes <= 1 else int(math.ceil(K / passes))) if passes else 0,
+            init_s=init,
+            wall_to_optimal_s=wall,
+            iterations=[status(st).num_iterations for st, _ in res_opt],
+            states=[status(st).state for st, _ in res_opt],
+            single_ms_per_sweep=1e3 * single_loop / single_sweeps,
+            single_instance_sweeps_per_s=single_sweeps / single_loop,
+            single_init_s=single_init,
+            single_wall_to_optimal_s=single_wall,
+            same_iterations=[status(st).num_iterations for st, _ in res_single] ==
+                            [status(st).num_iterations for st, _ in res_opt],
+        )
+        out["speedup_instance_sweeps"] = out["instance_sweeps_per_s"] / out["single_instance_sweeps_per_s"]
+        print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()

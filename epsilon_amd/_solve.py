@@ -172,6 +172,51 @@ def solve(problem_bytes, parameters, solver_params_bytes, data):
     return _take_result(res)
 
 
+def solve_batch(problems, parameters, solver_params_bytes, data):
+    """K solves sharing `data` and the solver parameters (include/epsilon_hip.h eps_solve_batch):
+    problems[k] with parameters[k] (a list of (id, constant_bytes) per instance, or None for
+    none at all).  Returns [(status_bytes, {var_id: bytes})] in input order, each what `solve`
+    returns for that instance alone."""
+    L = lib()
+    problems = list(problems)
+    count = len(problems)
+    if parameters is None:
+        parameters = [[] for _ in problems]
+    parameters = list(parameters)
+    if len(parameters) != count:
+        raise error("solve_batch: %d problems but %d parameter lists" % (count, len(parameters)))
+    keep = []
+    blobs, nb = _blobs(data, keep)
+    n = max(count, 1)
+    pbufs = (ctypes.c_void_p * n)()
+    plens = (ctypes.c_size_t * n)()
+    parr = (ctypes.c_void_p * n)()
+    nparr = (ctypes.c_size_t * n)()
+    for k, (pbytes, plist) in enumerate(zip(problems, parameters)):
+        buf = ctypes.create_string_buffer(pbytes, len(pbytes))
+        keep.append(buf)
+        pbufs[k] = ctypes.cast(buf, ctypes.c_void_p)
+        plens[k] = len(pbytes)
+        arr, cnt = _params(plist, keep)
+        keep.append(arr)
+        parr[k] = ctypes.cast(arr, ctypes.c_void_p)
+        nparr[k] = cnt
+    res = (ctypes.c_void_p * n)()
+    _check(L.eps_solve_batch(pbufs, plens, ctypes.c_size_t(count), solver_params_bytes,
+                             ctypes.c_size_t(len(solver_params_bytes)), blobs, ctypes.c_size_t(nb),
+                             parr, nparr, res))
+    out = []
+    try:
+        for k in range(count):
+            out.append(_take_result(ctypes.c_void_p(res[k])))
+            res[k] = None
+    finally:
+        for k in range(count):
+            if res[k]:
+                L.eps_result_free(ctypes.c_void_p(res[k]))
+    return out
+
+
 def eval_prox(f_expr_bytes, lam, data, v):
     """reference `_solve.eval_prox` (solvemodule.cc:189-242)."""
     L = lib()

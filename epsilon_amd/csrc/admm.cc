@@ -5,6 +5,8 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <map>
 
 #include "comm.h"
 #include "kernels.h"
@@ -393,7 +395,7 @@ class ProxADMMSolver final : public Solver {
     SetCurrentDType(data_->dtype());
     const double t0 = Now();
     if (op_cache_.size() > 64) op_cache_.Clear();
-    OpCacheScope cache_scope(&op_cache_);
+    OpCacheScope cache_scope(InitCache());
     static const bool trace = std::getenv("EPSILON_HIP_INIT_TRACE") != nullptr;
     auto mark = [&](const char* what) {  // host wall clock + device drain, debugging aid only
       if (!trace) return;
@@ -434,6 +436,80 @@ class ProxADMMSolver final : public Solver {
     BlockVector r;
     for (int i = 0; i < N_; ++i) r += x_[i];
     return r;
+  }
+
+  // ---- batched solves (RunFusedBatches) -------------------------------------------------------
+  // A fresh fused solve whose pass the batched one mirrors: its instance for the batched kernels
+  // and the key of the group it can join (same data matrix, inverse, dtype and shape).
+  bool BatchView(k::LassoBatchMember* mem, std::vector<uint64_t>* key) const {
+    if (!initialized_ || finished_ || iter_ != 0 || !fused_ || fs_.use_peer || ShardSpec::Get().active()) return false;
+    const FusedState& f = fs_;
+    const DenseMatrixImpl& L = *f.ls.L_arg_var;
+    const DenseMatrixImpl& D = *f.ls.Dinv_arg;
+    const DType dt = data_->dtype();
+    if (L.dtype() != dt || k::LassoBatchWidth(f.m, f.n, dt) == 0) return false;
+    mem->w = f.w;
+    mem->tpart = f.tpart;
+    mem->u = f.u;
+    mem->x0 = f.x0;
+    mem->x1 = f.x1;
+    mem->y0 = f.y0;
+    mem->y1 = f.y1;
+    mem->y1prev = f.y1prev;
+    mem->alpha_vec = f.sz.alpha_vec;
+    mem->beta_vec = f.sz.beta_vec;
+    mem->p = f.p;
+    mem->rhs = f.ls.rhs_arg;
+    mem->kappa = -L.scale();
+    mem->Bs = f.sz.Bs;
+    mem->Cs = f.sz.Cs;
+    mem->a1 = f.a1;
+    mem->lam = f.sz.lam;
+    mem->alpha = f.sz.alpha;
+    mem->beta = f.sz.beta;
+    mem->M = f.sz.M;
+    auto bits = [](double v) {
+      uint64_t b;
+      std::memcpy(&b, &v, 8);
+      return b;
+    };
+    *key = {reinterpret_cast<uintptr_t>(L.data().data()), static_cast<uint64_t>(L.rows()),
+            static_cast<uint64_t>(f.m), static_cast<uint64_t>(f.n), static_cast<uint64_t>(dt),
+            bits(L.scale()), reinterpret_cast<uintptr_t>(D.data().data()), bits(D.scale()),
+            reinterpret_cast<uintptr_t>(f.symv_packed.data()), f.symv_work.n > 0 ? 1u : 0u,
+            static_cast<uint64_t>(params_.max_iterations), static_cast<uint64_t>(params_.epoch_iterations)};
+    return true;
+  }
+  const DVec& batch_packed_inverse() const { return fs_.symv_packed; }
+  double batch_inverse_scale() const { return fs_.ls.Dinv_arg->scale(); }
+  int batch_grid() const { return fs_.grid; }
+  const DVec& batch_matrix(int64_t* lda) const {
+    *lda = fs_.ls.L_arg_var->rows();
+    return fs_.ls.L_arg_var->data();
+  }
+  void BatchApplyInverse() { ApplyInverseFixed(); }
+  // the residual check at sweep `iter`: its scalars into the next slots, then (after the fetch)
+  // the status; true if the instance stops here
+  void BatchLaunchNorms(int iter) {
+    iter_ = iter;
+    LaunchFusedNorms();
+  }
+  bool BatchFinishCheck() {
+    FinishFusedCheck();
+    finished_ = status_.state == pb::SolverStatus::OPTIMAL;
+    return finished_;
+  }
+  // what Run() does when the sweeps run out
+  void BatchFinishMaxIterations(int iter) {
+    iter_ = iter;
+    ComputeResiduals();
+    status_.state = pb::SolverStatus::MAX_ITERATIONS_REACHED;
+    finished_ = true;
+  }
+  void BatchSetLoopTime(double seconds) {
+    loop_seconds_ += seconds;
+    status_.init_time = init_seconds_;
+    status_.total_time = init_seconds_ + loop_seconds_;
   }
 
  protected:
@@ -593,7 +669,7 @@ class ProxADMMSolver final : public Solver {
           const char* e = std::getenv("EPSILON_HIP_SYMV_PACKED");
           return !(e && e[0] == '0');
         }();
-        if (packed) f.symv_packed = k::SymvPack(f.m, D.data(), f.m);
+        if (packed) f.symv_packed = PackInverse(D, f.m);
       }
     }
     ResetGraph();
@@ -613,6 +689,19 @@ class ProxADMMSolver final : public Solver {
     y_prev_[1].Set(ck, fs_.y1prev);
     fused_ = true;
     FusedForward(/*from_state=*/true);
+  }
+
+  // The tile-packed copy of the cached inverse; instances of a batch (shared cache) that share
+  // the inverse share one copy.
+  DVec PackInverse(const DenseMatrixImpl& D, int64_t m) {
+    uint64_t key = 0;
+    if (shared_cache_ != nullptr) {
+      key = HashCombine(HashCombine(reinterpret_cast<uintptr_t>(D.data().data()), 0x9ac4ed), m);
+      if (auto hit = shared_cache_->Find(key)) return hit->data();
+    }
+    DVec P = k::SymvPack(m, D.data(), m);
+    if (key) shared_cache_->Put(key, std::make_shared<DenseMatrixImpl>(P, P.n, 1, false, 1.0, key));
+    return P;
   }
 
   // p = rhs_arg - L(arg,var) v0 (all-reduced when sharded), w = Dinv_arg p.
@@ -835,8 +924,14 @@ class ProxADMMSolver final : public Solver {
   }
   void BeginResiduals() override {
     Runtime& rt = Runtime::Get();
-    FusedState& f = fs_;
     rt.ResetSlots();
+    LaunchFusedNorms();
+    rt.FetchSlotsAsync();
+  }
+  // the check's six scalars into the next six slots
+  void LaunchFusedNorms() {
+    Runtime& rt = Runtime::Get();
+    FusedState& f = fs_;
     norm_slot_ = rt.NewSlot();
     for (int k = 1; k < 6; ++k) rt.NewSlot();
     const ShardSpec& sh = ShardSpec::Get();
@@ -844,11 +939,14 @@ class ProxADMMSolver final : public Solver {
     k::LassoFusedNorms(f.u, f.y0, f.y1, f.y1prev,
                        sharded ? rt.ShardSlotPtr(norm_slot_) : rt.SlotPtr(norm_slot_), f.norm_work,
                        f.use_peer ? rt.peer()->device_error_word() : nullptr);
-    rt.FetchSlotsAsync();
   }
   void EndResiduals() override {
+    Runtime::Get().WaitSlots();
+    FinishFusedCheck();
+  }
+  // the residuals and the state of the check from its fetched scalars
+  void FinishFusedCheck() {
     Runtime& rt = Runtime::Get();
-    rt.WaitSlots();
     // a timed-out exchange on ANY rank shows in the all-reduced sixth value: every rank raises at
     // the same check, none is left waiting in a collective the others never enter
     if (rt.SlotValue(norm_slot_ + 5) > 0) {
@@ -972,7 +1070,7 @@ class ProxADMMTwoBlockSolver final : public Solver {
     SetCurrentDType(data_->dtype());
     const double t0 = Now();
     if (op_cache_.size() > 64) op_cache_.Clear();
-    OpCacheScope cache_scope(&op_cache_);
+    OpCacheScope cache_scope(InitCache());
     const double sqrt_rho = std::sqrt(params_.rho);
     const DType dt = data_->dtype();
     AffineOperator H, A;
@@ -1218,6 +1316,112 @@ class ProxADMMTwoBlockSolver final : public Solver {
   bool capture_safe_ = false;
   int eager_sweeps_ = 0;
 };
+
+// ---------------------------------------------------------------------------------------------------
+// Batched solves: one group of fused instances sharing A and the cached inverse
+// ---------------------------------------------------------------------------------------------------
+namespace {
+
+void RunFusedGroup(const std::vector<ProxADMMSolver*>& g, const std::vector<k::LassoBatchMember>& mem) {
+  const double t0 = Now();
+  Runtime& rt = Runtime::Get();
+  ProxADMMSolver& lead = *g[0];
+  const DType dt = lead.data()->dtype();
+  SetCurrentDType(dt);
+  int64_t lda = 0;
+  const DVec& A = lead.batch_matrix(&lda);
+  const int64_t m = mem[0].p.n, n = mem[0].u.n;
+  const int width = k::LassoBatchWidth(m, n, dt);
+  const int grid = lead.batch_grid();
+  const DVec& P = lead.batch_packed_inverse();
+  const double dscale = lead.batch_inverse_scale();
+  const pb::SolverParams& params = lead.params();
+  const int epoch = params.epoch_iterations > 0 ? params.epoch_iterations : 1;
+  const int max_it = params.max_iterations;
+  bool rhs_aligned = true;
+  for (const auto& mb : mem)
+    if (mb.rhs.n > 0) rhs_aligned = rhs_aligned && reinterpret_cast<uintptr_t>(mb.rhs.data()) % 16 == 0;
+  const int K = static_cast<int>(g.size());
+  DVec symv_work = P.n > 0 ? DVec::Empty(K * k::SymvWorkspace(m), dt) : DVec();
+
+  std::vector<int> active(K);
+  for (int i = 0; i < K; ++i) active[i] = i;
+  DVec table;
+  auto upload = [&] {
+    std::vector<const k::LassoBatchMember*> v;
+    for (int i : active) v.push_back(&mem[i]);
+    k::LassoBatchUpload(v, dt, &table);
+  };
+  upload();
+  auto sweep = [&] {
+    const int na = static_cast<int>(active.size());
+    for (int first = 0; first < na; first += width)
+      k::LassoBatchPass(m, n, lda, A, table, first, std::min(width, na - first));
+    k::ReducePartialsBatch(m, grid, table, na, dt, rhs_aligned);
+    if (P.n > 0) {
+      k::SymvPackedBatch(m, dscale, P, table, na, symv_work);
+    } else {
+      for (int i : active) g[i]->BatchApplyInverse();  // D.Apply / Symv: per instance
+    }
+  };
+  // Run()'s iteration schedule without the pipelining: sweeps up to the next multiple of the
+  // epoch, then one residual check of every active instance with ONE fetch of their scalars
+  int iter = 0;
+  while (!active.empty() && iter < max_it) {
+    int batch = 1;
+    while ((iter + batch - 1) % epoch != 0) ++batch;
+    if (batch > max_it - iter) batch = max_it - iter;
+    for (int s = 0; s < batch; ++s) sweep();
+    iter += batch - 1;
+    if (iter % epoch == 0) {
+      rt.ResetSlots();
+      for (int i : active) g[i]->BatchLaunchNorms(iter);
+      rt.FetchSlots();
+      std::vector<int> still;
+      for (int i : active)
+        if (!g[i]->BatchFinishCheck()) still.push_back(i);
+      if (still.size() != active.size()) {  // the stopped ones are frozen: drop their descriptors
+        active.swap(still);
+        if (!active.empty()) upload();
+      }
+    }
+    ++iter;
+  }
+  for (int i : active) g[i]->BatchFinishMaxIterations(iter);
+  rt.Sync();
+  const double loop = Now() - t0;
+  for (ProxADMMSolver* s : g) s->BatchSetLoopTime(loop);
+}
+
+}  // namespace
+
+std::vector<bool> RunFusedBatches(const std::vector<Solver*>& solvers) {
+  std::vector<bool> ran(solvers.size(), false);
+  std::map<std::vector<uint64_t>, std::vector<size_t>> groups;
+  std::vector<k::LassoBatchMember> mem(solvers.size());
+  std::vector<std::vector<uint64_t>> order;  // groups in order of their first instance
+  for (size_t i = 0; i < solvers.size(); ++i) {
+    auto* s = dynamic_cast<ProxADMMSolver*>(solvers[i]);
+    std::vector<uint64_t> key;
+    if (s == nullptr || !s->BatchView(&mem[i], &key)) continue;
+    auto& members = groups[key];
+    if (members.empty()) order.push_back(key);
+    members.push_back(i);
+  }
+  for (const auto& key : order) {
+    const std::vector<size_t>& idx = groups[key];
+    if (idx.size() < 2) continue;  // alone: the single path is the same solve, with pipelined checks
+    std::vector<ProxADMMSolver*> g;
+    std::vector<k::LassoBatchMember> gm;
+    for (size_t i : idx) {
+      g.push_back(static_cast<ProxADMMSolver*>(solvers[i]));
+      gm.push_back(mem[i]);
+    }
+    RunFusedGroup(g, gm);
+    for (size_t i : idx) ran[i] = true;
+  }
+  return ran;
+}
 
 std::unique_ptr<Solver> CreateSolver(pb::Problem problem, std::shared_ptr<DataMap> data,
                                      pb::SolverParams params) {  // solvemodule.cc:74-87

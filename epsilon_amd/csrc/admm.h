@@ -44,6 +44,9 @@ class Solver {
   double init_seconds() const { return init_seconds_; }
   double loop_seconds() const { return loop_seconds_; }
   void set_log(std::function<void(const std::string&)> log) { log_ = std::move(log); }
+  // Batched solves: Init memoises its Gram products, inverses and packed inverse copies in `c`
+  // instead of this solver's own cache, so instances that share the data matrix share them.
+  void set_shared_cache(OpCache* c) { shared_cache_ = c; }
 
  protected:
   virtual void Sweep() = 0;
@@ -78,10 +81,22 @@ class Solver {
   std::function<void(const std::string&)> log_;
   // Gram products / inverses of previous Inits of this solver, by content id (warm start).
   OpCache op_cache_;
+  OpCache* shared_cache_ = nullptr;  // set_shared_cache
+  OpCache* InitCache() { return shared_cache_ ? shared_cache_ : &op_cache_; }
 };
 
 std::unique_ptr<Solver> CreateSolver(pb::Problem problem, std::shared_ptr<DataMap> data,
                                      pb::SolverParams params);
+
+// Batched solves (eps_solve_batch).  Of the initialised, not yet run `solvers`, those whose sweep
+// is the multi-block driver's fused pass in a form the batched pass mirrors
+// (k::LassoBatchWidth) are grouped by shared data matrix and cached inverse; every group of two
+// or more runs its sweeps together (kernels_fused_batch.hip: one pass over A for up to KB
+// instances, one reduction and one inverse apply for all), with each instance's residual check
+// every epoch_iterations sweeps and each frozen at the check that stops it.  Every solver run
+// here ends with exactly the status and iterates its own Run(-1) would give.  Returns, per
+// solver, whether it was run; the others are untouched.
+std::vector<bool> RunFusedBatches(const std::vector<Solver*>& solvers);
 
 // One prox evaluation (reference python/epopt/solvemodule.cc:189-242).
 BlockVector EvalProx(const pb::Expression& f_expr, double lambda, DataMap* data,

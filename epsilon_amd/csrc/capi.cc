@@ -173,6 +173,81 @@ int eps_solve(const void* problem, size_t problem_len, const void* solver_params
   });
 }
 
+int eps_solve_batch(const void* const* problems, const size_t* problem_lens, size_t count,
+                    const void* solver_params, size_t solver_params_len, const eps_blob* data,
+                    size_t ndata, const eps_param* const* params, const size_t* nparams,
+                    eps_result** out) {
+  if (out != nullptr && problems != nullptr)
+    for (size_t k = 0; k < count; ++k) out[k] = nullptr;
+  return Guard([&] {
+    EPS_CHECK_MSG(count > 0, "eps_solve_batch: count is 0");
+    EPS_CHECK_MSG(problems != nullptr && problem_lens != nullptr && out != nullptr,
+                  "eps_solve_batch: null problems / problem_lens / out");
+    EPS_CHECK_MSG(nparams == nullptr || params != nullptr, "eps_solve_batch: nparams without params");
+    const DType dt = ConfiguredDType();
+    SetCurrentDType(dt);
+    pb::SolverParams sp = pb::ParseSolverParams(solver_params, solver_params_len);
+    // every instance parsed before any work starts
+    std::vector<pb::Problem> probs(count);
+    std::vector<std::vector<std::pair<std::string, pb::Constant>>> binds(count);
+    for (size_t k = 0; k < count; ++k) {
+      try {
+        EPS_CHECK_MSG(problems[k] != nullptr, "null problem");
+        probs[k] = pb::ParseProblem(problems[k], problem_lens[k]);
+        const size_t np = nparams ? nparams[k] : 0;
+        EPS_CHECK_MSG(np == 0 || params[k] != nullptr, "nparams " << np << " with a null parameter array");
+        for (size_t i = 0; i < np; ++i) {
+          EPS_CHECK_MSG(params[k][i].id != nullptr, "parameter " << i << " without an id");
+          binds[k].emplace_back(params[k][i].id,
+                                pb::ParseConstant(params[k][i].constant_proto, params[k][i].len));
+        }
+      } catch (const std::exception& e) {
+        EPS_FATAL("eps_solve_batch: instance " << k << ": " << e.what());
+      }
+    }
+    // one data map (one upload of each constant) and one memo of Gram products / inverses for all
+    auto dm = MakeDataMap(data, ndata, dt);
+    OpCache shared;
+    std::vector<std::unique_ptr<Solver>> solvers(count);
+    std::vector<std::unique_ptr<eps_result>> results(count);
+    std::vector<Solver*> pending;
+    std::vector<size_t> pending_index;
+    for (size_t k = 0; k < count; ++k) {
+      try {
+        dm->ClearParameters();
+        for (const auto& b : binds[k]) dm->SetParameter(b.first, b.second);
+        solvers[k] = CreateSolver(std::move(probs[k]), dm, sp);
+        solvers[k]->set_log(LogToStdout);
+        solvers[k]->set_shared_cache(&shared);
+        solvers[k]->Init();
+        pending.push_back(solvers[k].get());
+        pending_index.push_back(k);
+      } catch (const std::exception& e) {
+        EPS_FATAL("eps_solve_batch: instance " << k << ": " << e.what());
+      }
+    }
+    // fused instances that share A and the inverse run together; every other one alone, with
+    // its own parameters bound again (its operators may read them on first use)
+    const std::vector<bool> ran = RunFusedBatches(pending);
+    for (size_t i = 0; i < pending.size(); ++i) {
+      const size_t k = pending_index[i];
+      try {
+        if (!ran[i]) {
+          dm->ClearParameters();
+          for (const auto& b : binds[k]) dm->SetParameter(b.first, b.second);
+          solvers[k]->Run(-1);
+        }
+        results[k].reset(new eps_result);
+        FillResult(solvers[k].get(), results[k].get());
+        solvers[k].reset();
+      } catch (const std::exception& e) {
+        EPS_FATAL("eps_solve_batch: instance " << k << ": " << e.what());
+      }
+    }
+    for (size_t k = 0; k < count; ++k) out[k] = results[k].release();
+  });
+}
+
 int eps_eval_prox(const void* f_expr, size_t f_expr_len, double lambda, const eps_blob* data,
                   size_t ndata, const eps_blob* v, size_t nv, eps_result** out) {
   return Guard([&] {

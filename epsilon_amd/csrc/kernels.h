@@ -78,12 +78,55 @@ struct LassoFusedArgs {
 };
 bool LassoFusedSupported(int64_t m, int64_t n, const DVec& A, int64_t lda);
 int LassoFusedGrid(int64_t m, int64_t n, DType dt = F32);
+int LassoFusedBlock(int64_t m, int64_t n, DType dt);  // threads per workgroup of the pass
 void LassoFusedPass(const LassoFusedArgs& args);
 // out6 = {||y0||^2, ||y1||^2, ||y0 + y1||^2, ||y1 - y1prev||^2, ||u||^2, peer_err ? 1 : 0} (device
 // doubles), one launch; `work`: 64 * 5 + 1 doubles, zero-initialised once (the last double is a
 // ticket counter); `peer_err` (optional): the device-side error word of the peer exchange.
 void LassoFusedNorms(const DVec& u, const DVec& y0, const DVec& y1, const DVec& y1prev, double* out6,
                      const DVec& work, const unsigned* peer_err = nullptr);
+
+// ---- batched fused pass: instances sharing one data matrix (kernels_fused_batch.hip) ---------
+// One instance of a batched sweep as the kernels read it (device array, compute type T): the
+// multi-block driver's fused state plus its forward vectors.  Every instance's arithmetic is
+// the single pass's (LassoFusedPass, ReducePartials, SymvPacked), so its iterates are
+// bit-identical to its own solve.
+template <class T> struct LassoBatchInst {
+  const T* w;        // m: the inverse apply's output, read by the pass
+  T* tpart;          // grid * m: per-workgroup partials of A v0'
+  T* u; T* x0; T* x1; T* y0; T* y1; T* y1prev;  // n each, in place
+  const T* alpha_v;  // per-column alpha / beta of the scaled zone (nullptr: uniform)
+  const T* beta_v;
+  T* p;              // m: the reduced partials (+ rhs), input of the inverse apply
+  const T* rhs;      // m: constant part of the rhs (nullptr: none)
+  T kappa, Bs, Cs, a1, lam, alpha, beta, M;
+};
+// Host view of one instance (scalars as double, narrowed per dtype on upload).
+struct LassoBatchMember {
+  DVec w, tpart, u, x0, x1, y0, y1, y1prev, alpha_vec, beta_vec, p, rhs;
+  double kappa = 0, Bs = 0, Cs = 0, a1 = 0, lam = 0, alpha = 1, beta = 1, M = 0;
+};
+// Instances one launch of the batched pass carries for (m, dtype) - set by the register budget
+// of its instantiation - or 0 where the single pass would take a form the batched one does not
+// mirror (512-thread workgroups, the pair kernel): such instances are solved one by one.
+int LassoBatchWidth(int64_t m, int64_t n, DType dt);
+// The descriptors of `members` in order into `table` (device; grown as needed): the active set
+// of a batch is this array, so an instance that stops is dropped by uploading the shorter list.
+void LassoBatchUpload(const std::vector<const LassoBatchMember*>& members, DType dt, DVec* table);
+// The fused pass of instances [first, first + count) of `table`, count <= LassoBatchWidth: each
+// loaded column of A feeds every instance's dot product, chain and forward update.
+void LassoBatchPass(int64_t m, int64_t n, int64_t lda, const DVec& A, const DVec& table, int first,
+                    int count);
+// p = kappa * sum(tpart) (+ rhs) of `count` instances in one launch, each in the summation order
+// of ReducePartials(m, nparts, tpart, kappa, 0, p, rhs).  `rhs_aligned`: every rhs present is
+// 16-byte aligned (picks the same kernel form as the single call).
+void ReducePartialsBatch(int64_t m, int nparts, const DVec& table, int count, DType dt,
+                         bool rhs_aligned);
+// w = alpha * P p for `count` instances (P: SymvPack of a symmetric m x m matrix): every packed
+// tile is read once for all of them; each result in SymvPacked's arithmetic order.  `work`:
+// count * SymvWorkspace(m) values.
+void SymvPackedBatch(int64_t m, double alpha, const DVec& P, const DVec& table, int count,
+                     const DVec& work);
 
 // ---- one-shot peer-write exchange (kernels_peer.hip; PeerView in comm.h) ----------------------
 void PeerBumpEpoch(const PeerView& pv);

@@ -1,0 +1,261 @@
+// Batched fused sweep: K instances of the "least squares + separable threshold" structure that
+// share the data matrix A (a regularisation path, cross-validation folds, several right-hand
+// sides) in ONE pass over A per sweep instead of K.
+//
+// Same geometry as LassoFusedStreamKernel (kernels_fused.hip) with 256 threads: thread t owns
+// rows R(t + 256q), q < NR, of every column (R = 4 in f32, 2 in f64: one 16-byte load); the
+// workgroups take the same columns in the same order (LassoFusedGrid), the next column's loads
+// are in flight while the current one is reduced.  Each loaded column feeds KB instances: their
+// dot products with their own w, one LDS round trip and ONE barrier for all KB block
+// reductions, their elementwise chains and their forward updates into their own partial t'.
+// w and t' of every instance stay in registers (2 NR 16-byte values per instance per thread),
+// which is what bounds KB (LassoBatchWidth; DESIGN.md lists the registers of each form).
+//
+// Per instance the arithmetic is exactly the single pass's: the same chunk order in the dot
+// product, the same shuffle tree and LDS sum, the same chain (kernels_fused_chain.h), the same
+// order of forward updates, and this file is compiled with -ffp-contract=off as kernels_fused.hip
+// is - so every instance's iterates are bit-identical to its own solve.
+#include <hip/hip_runtime.h>
+
+#include <cstdlib>
+#include <vector>
+
+#include "kernels.h"
+#include "kernels_fused_chain.h"
+
+namespace eps {
+namespace k {
+
+namespace {
+
+constexpr int kBlock = 256;
+
+template <class T> struct Chunk;  // one 16-byte load: R rows
+template <> struct Chunk<float> {
+  static constexpr int R = 4;
+  typedef float V __attribute__((ext_vector_type(4)));
+};
+template <> struct Chunk<double> {
+  static constexpr int R = 2;
+  typedef double V __attribute__((ext_vector_type(2)));
+};
+
+template <class T, int NR, int KB>
+__global__ __launch_bounds__(kBlock) void LassoBatchStreamKernel(int64_t m, int64_t n, const T* __restrict__ A,
+                                                                 int64_t lda,
+                                                                 const LassoBatchInst<T>* __restrict__ tab,
+                                                                 int nk) {
+  typedef typename Chunk<T>::V V;
+  constexpr int R = Chunk<T>::R;
+  __shared__ T red[2][KB][kBlock / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  V zero;
+#pragma unroll
+  for (int r = 0; r < R; ++r) zero[r] = T(0);
+  V wv[KB][NR], tp[KB][NR];
+  int64_t row[NR];
+#pragma unroll
+  for (int q = 0; q < NR; ++q) row[q] = (static_cast<int64_t>(q) * kBlock + tid) * R;
+#pragma unroll
+  for (int i = 0; i < KB; ++i) {
+#pragma unroll
+    for (int q = 0; q < NR; ++q) {
+      wv[i][q] = (i < nk && row[q] < m) ? *reinterpret_cast<const V*>(tab[i].w + row[q]) : zero;
+      tp[i][q] = zero;
+    }
+  }
+  // this workgroup's columns: exactly those of LassoFusedStreamKernel, in its order
+  const int64_t npairs = (n + 1) / 2;
+  auto column = [&](int64_t step) -> int64_t {
+    const int64_t jp = blockIdx.x + (step >> 1) * gridDim.x;
+    const int64_t j = 2 * jp + (step & 1);
+    return (jp < npairs && j < n) ? j : -1;
+  };
+  auto load = [&](V (&a)[NR], int64_t j) {
+    const T* cp = A + j * lda;
+#pragma unroll
+    for (int q = 0; q < NR; ++q)
+      a[q] = row[q] < m ? __builtin_nontemporal_load(reinterpret_cast<const V*>(cp + row[q])) : zero;
+  };
+  V cur[NR], nxt[NR];
+  int64_t step = 0;
+  int64_t j = column(0);
+  if (j >= 0) load(cur, j);
+  int par = 0;
+  while (j >= 0) {
+    int64_t jn = column(step + 1);
+    if (jn < 0 && ((step + 1) & 1)) jn = column(step + 2);
+    const int64_t step_n = (jn >= 0 && column(step + 1) < 0) ? step + 2 : step + 1;
+    if (jn >= 0) load(nxt, jn);
+    // every instance's column state is read before the barrier: thread 0 overwrites it after
+    T uj[KB], y0j[KB], y1j[KB];
+#pragma unroll
+    for (int i = 0; i < KB; ++i) {
+      if (i >= nk) continue;
+      uj[i] = tab[i].u[j];
+      y0j[i] = tab[i].y0[j];
+      y1j[i] = tab[i].y1[j];
+      T d = T(0);
+#pragma unroll
+      for (int q = 0; q < NR; ++q)
+#pragma unroll
+        for (int r = 0; r < R; ++r) d += cur[q][r] * wv[i][q][r];
+      d = WaveSumT<T>(d);
+      if (lane == 0) red[par][i][wave] = d;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < KB; ++i) {
+      if (i >= nk) continue;
+      const LassoBatchInst<T>& I = tab[i];
+      T d = red[par][i][0];
+#pragma unroll
+      for (int w2 = 1; w2 < kBlock / 64; ++w2) d += red[par][i][w2];
+      FusedScalarsT<T> c;
+      c.kappa = I.kappa;
+      c.Bs = I.Bs;
+      c.Cs = I.Cs;
+      c.a1 = I.a1;
+      c.lam = I.lam;
+      c.alpha = I.alpha_v != nullptr ? I.alpha_v[j] : I.alpha;
+      c.beta = I.beta_v != nullptr ? I.beta_v[j] : I.beta;
+      c.M = I.M;
+      T nx0, nx1, ny0, ny1, nu;
+      const T v0n = ChainOneT<T>(d, c, uj[i], y0j[i], y1j[i], &nx0, &nx1, &ny0, &ny1, &nu);
+      if (tid == 0) {
+        I.y1prev[j] = y1j[i];
+        I.x0[j] = nx0;
+        I.x1[j] = nx1;
+        I.y0[j] = ny0;
+        I.y1[j] = ny1;
+        I.u[j] = nu;
+      }
+#pragma unroll
+      for (int q = 0; q < NR; ++q)
+#pragma unroll
+        for (int r = 0; r < R; ++r) tp[i][q][r] += cur[q][r] * v0n;
+    }
+    par ^= 1;
+#pragma unroll
+    for (int q = 0; q < NR; ++q) cur[q] = nxt[q];
+    j = jn;
+    step = step_n;
+  }
+#pragma unroll
+  for (int i = 0; i < KB; ++i) {
+    if (i >= nk) continue;
+    T* out = tab[i].tpart + static_cast<int64_t>(blockIdx.x) * m;
+#pragma unroll
+    for (int q = 0; q < NR; ++q)
+      if (row[q] < m) *reinterpret_cast<V*>(out + row[q]) = tp[i][q];
+  }
+}
+
+// 16-byte row chunks per thread of the single pass with 256 threads, rounded up to its ladder
+int ChunksPerThread(int64_t m, DType dt) {
+  const int64_t rows = dt == F32 ? 4 : 2;
+  const int64_t need = (m + rows * kBlock - 1) / (rows * kBlock);
+  return need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : need <= 8 ? 8 : 10;
+}
+
+// Instances per launch for NR chunks per thread: w and t' take 8 NR registers per instance in
+// either type, the column and the next one in flight 8 NR more.  Chosen so that no
+// instantiation spills to scratch (hipcc -Rpass-analysis=kernel-resource-usage).
+constexpr int WidthFor(int nr) { return nr <= 2 ? 8 : nr <= 4 ? 6 : nr <= 8 ? 5 : 4; }
+
+template <class T, int NR>
+void LaunchBatch(int grid, int64_t m, int64_t n, const T* A, int64_t lda, const LassoBatchInst<T>* tab, int nk) {
+  hipLaunchKernelGGL((LassoBatchStreamKernel<T, NR, WidthFor(NR)>), dim3(grid), dim3(kBlock), 0,
+                     Runtime::Get().stream(), m, n, A, lda, tab, nk);
+}
+
+template <class T>
+void LaunchBatchT(int nr, int grid, int64_t m, int64_t n, const T* A, int64_t lda, const LassoBatchInst<T>* tab,
+                  int nk) {
+  switch (nr) {
+    case 1: LaunchBatch<T, 1>(grid, m, n, A, lda, tab, nk); break;
+    case 2: LaunchBatch<T, 2>(grid, m, n, A, lda, tab, nk); break;
+    case 4: LaunchBatch<T, 4>(grid, m, n, A, lda, tab, nk); break;
+    case 8: LaunchBatch<T, 8>(grid, m, n, A, lda, tab, nk); break;
+    default: LaunchBatch<T, 10>(grid, m, n, A, lda, tab, nk); break;
+  }
+}
+
+template <class T>
+LassoBatchInst<T> Narrow(const LassoBatchMember& s) {
+  LassoBatchInst<T> d;
+  d.w = s.w.as<T>();
+  d.tpart = s.tpart.as<T>();
+  d.u = s.u.as<T>();
+  d.x0 = s.x0.as<T>();
+  d.x1 = s.x1.as<T>();
+  d.y0 = s.y0.as<T>();
+  d.y1 = s.y1.as<T>();
+  d.y1prev = s.y1prev.as<T>();
+  d.alpha_v = s.alpha_vec.n > 0 ? s.alpha_vec.as<T>() : nullptr;
+  d.beta_v = s.beta_vec.n > 0 ? s.beta_vec.as<T>() : nullptr;
+  d.p = s.p.as<T>();
+  d.rhs = s.rhs.n > 0 ? s.rhs.as<T>() : nullptr;
+  d.kappa = static_cast<T>(s.kappa);
+  d.Bs = static_cast<T>(s.Bs);
+  d.Cs = static_cast<T>(s.Cs);
+  d.a1 = static_cast<T>(s.a1);
+  d.lam = static_cast<T>(s.lam);
+  d.alpha = static_cast<T>(s.alpha);
+  d.beta = static_cast<T>(s.beta);
+  d.M = static_cast<T>(s.M);
+  return d;
+}
+
+template <class T>
+void UploadT(const std::vector<const LassoBatchMember*>& members, DVec* table) {
+  std::vector<LassoBatchInst<T>> host;
+  host.reserve(members.size());
+  for (const LassoBatchMember* s : members) host.push_back(Narrow<T>(*s));
+  const size_t bytes = host.size() * sizeof(LassoBatchInst<T>);
+  const int64_t words = static_cast<int64_t>((bytes + 7) / 8);
+  if (table->n < words || table->dt != F64) *table = DVec::Empty(words < 1 ? 1 : words, F64);
+  if (bytes == 0) return;
+  Runtime& rt = Runtime::Get();
+  EPS_HIP(hipMemcpyAsync(table->data(), host.data(), bytes, hipMemcpyHostToDevice, rt.stream()));
+  rt.Sync();  // `host` goes out of scope
+}
+
+}  // namespace
+
+int LassoBatchWidth(int64_t m, int64_t n, DType dt) {
+  if (LassoFusedBlock(m, n, dt) != kBlock) return 0;
+  // the single f32 pass may be switched to its two-column form, which the batch does not mirror
+  static const char* env = std::getenv("EPSILON_HIP_FUSED_KERNEL");
+  if (dt == F32 && env && env[0] == 'p') return 0;
+  return WidthFor(ChunksPerThread(m, dt));
+}
+
+void LassoBatchUpload(const std::vector<const LassoBatchMember*>& members, DType dt, DVec* table) {
+  for (const LassoBatchMember* s : members)
+    for (const DVec* v : {&s->w, &s->tpart, &s->u, &s->x0, &s->x1, &s->y0, &s->y1, &s->y1prev, &s->p})
+      EPS_CHECK(v->dt == dt && v->n > 0);
+  if (dt == F32) UploadT<float>(members, table);
+  else UploadT<double>(members, table);
+}
+
+void LassoBatchPass(int64_t m, int64_t n, int64_t lda, const DVec& A, const DVec& table, int first, int count) {
+  const DType dt = A.dt;
+  EPS_CHECK(LassoFusedSupported(m, n, A, lda));
+  const int width = LassoBatchWidth(m, n, dt);
+  EPS_CHECK_MSG(width > 0 && count >= 1 && count <= width,
+                "batched fused pass: " << count << " instances, width " << width);
+  const int grid = LassoFusedGrid(m, n, dt);
+  const int nr = ChunksPerThread(m, dt);
+  ProfScope prof("batch_fused_pass", m, n);
+  if (dt == F32)
+    LaunchBatchT<float>(nr, grid, m, n, A.as<float>(), lda,
+                        reinterpret_cast<const LassoBatchInst<float>*>(table.as<char>()) + first, count);
+  else
+    LaunchBatchT<double>(nr, grid, m, n, A.as<double>(), lda,
+                         reinterpret_cast<const LassoBatchInst<double>*>(table.as<char>()) + first, count);
+  EPS_HIP(hipGetLastError());
+}
+
+}  // namespace k
+}  // namespace eps

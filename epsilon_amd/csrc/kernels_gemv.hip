@@ -138,14 +138,13 @@ __global__ __launch_bounds__(kBlock) void GemvNKernel(int64_t rows, int64_t cols
 // y[r] = alpha * sum_k partial[k][r] + beta*y[r].  64 rows per workgroup, the splits are dealt
 // to the 4 wavefronts and summed in a FIXED order (k ascending inside a wave, then wave 0..3),
 // so the result is deterministic; loads are independent and unrolled so that many are in flight.
+// (the body takes the workgroup's row block, so that ReducePartialsBatch runs it per instance)
 template <class T>
-__global__ __launch_bounds__(kBlock) void GemvNReduceKernel(int64_t rows, int nsplit,
-                                                            const T* __restrict__ partial,
-                                                            T alpha, T beta, T* y,
-                                                            const T* __restrict__ add) {
+__device__ inline void GemvNReduceBody(int64_t rows, int nsplit, const T* __restrict__ partial, T alpha,
+                                       T beta, T* y, const T* __restrict__ add, int64_t blk) {
   __shared__ T part[kBlock / 64][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t r = static_cast<int64_t>(blockIdx.x) * 64 + lane;
+  const int64_t r = blk * 64 + lane;
   T s = T(0);
   if (r < rows) {
     const int per = (nsplit + 3) / 4;
@@ -171,6 +170,14 @@ __global__ __launch_bounds__(kBlock) void GemvNReduceKernel(int64_t rows, int ns
     if (add) out += add[r];
     y[r] = out;
   }
+}
+
+template <class T>
+__global__ __launch_bounds__(kBlock) void GemvNReduceKernel(int64_t rows, int nsplit,
+                                                            const T* __restrict__ partial,
+                                                            T alpha, T beta, T* y,
+                                                            const T* __restrict__ add) {
+  GemvNReduceBody<T>(rows, nsplit, partial, alpha, beta, y, add, blockIdx.x);
 }
 
 template <class T>
@@ -500,12 +507,9 @@ __global__ __launch_bounds__(kBlock) void SymvTileKernel(int64_t n, const T* __r
 // half-workgroups (even / odd position in the list), loaded eight at a time, and the two halves
 // are added in a fixed order.
 template <class T>
-__global__ __launch_bounds__(kBlock) void SymvReduceKernel(int64_t n, int64_t nb,
-                                                           const T* __restrict__ prow,
-                                                           const T* __restrict__ pcol, T alpha,
-                                                           T beta, T* y) {
+__device__ inline void SymvReduceBody(int64_t n, int64_t nb, const T* __restrict__ prow,
+                                      const T* __restrict__ pcol, T alpha, T beta, T* y, int64_t I) {
   __shared__ T half[kSB];
-  const int64_t I = blockIdx.x;
   const int off = threadIdx.x & (kSB - 1), grp = threadIdx.x >> 7;  // kSB == 128
   const int64_t base = I * (I + 1) / 2;
   auto part = [&](int64_t p) -> const T* {  // p-th partial vector of this block, p < nb
@@ -528,6 +532,14 @@ __global__ __launch_bounds__(kBlock) void SymvReduceKernel(int64_t n, int64_t nb
     const T tot = s + half[off];
     y[r] = (beta == T(0)) ? alpha * tot : alpha * tot + beta * y[r];
   }
+}
+
+template <class T>
+__global__ __launch_bounds__(kBlock) void SymvReduceKernel(int64_t n, int64_t nb,
+                                                           const T* __restrict__ prow,
+                                                           const T* __restrict__ pcol, T alpha,
+                                                           T beta, T* y) {
+  SymvReduceBody<T>(n, nb, prow, pcol, alpha, beta, y, blockIdx.x);
 }
 
 // tile-packed copy of the lower tiles of a symmetric matrix (see SymvTileKernel<T, true>)
@@ -627,13 +639,12 @@ namespace {
 // wave and the 4 waves in order - a fixed summation order.
 constexpr int kRQ4 = 8, kPL4 = kBlock / kRQ4;
 
-__global__ __launch_bounds__(kBlock) void ReducePartials4Kernel(int64_t rows, int nparts,
-                                                                const float* __restrict__ partial,
-                                                                float alpha, float beta, float* y,
-                                                                const float* __restrict__ add) {
+__device__ inline void ReducePartials4Body(int64_t rows, int nparts, const float* __restrict__ partial,
+                                           float alpha, float beta, float* y, const float* __restrict__ add,
+                                           int64_t blk) {
   __shared__ float4 part[kBlock / 64][kRQ4];
   const int t = threadIdx.x, rq = t & (kRQ4 - 1), pl = t >> 3, wave = t >> 6;
-  const int64_t r0 = (static_cast<int64_t>(blockIdx.x) * kRQ4 + rq) * 4;
+  const int64_t r0 = (blk * kRQ4 + rq) * 4;
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
   if (r0 < rows) {
     const float* p = partial + r0;
@@ -688,6 +699,29 @@ __global__ __launch_bounds__(kBlock) void ReducePartials4Kernel(int64_t rows, in
   }
   *reinterpret_cast<float4*>(y + r0) = make_float4(o[0], o[1], o[2], o[3]);
 }
+
+__global__ __launch_bounds__(kBlock) void ReducePartials4Kernel(int64_t rows, int nparts,
+                                                                const float* __restrict__ partial,
+                                                                float alpha, float beta, float* y,
+                                                                const float* __restrict__ add) {
+  ReducePartials4Body(rows, nparts, partial, alpha, beta, y, add, blockIdx.x);
+}
+
+// ---- the same reductions for the instances of a batched fused sweep (kernels_fused_batch.hip):
+// workgroup row (blockIdx.y) b runs instance b's single reduction, p_b = kappa_b sum(tpart_b) + rhs_b
+template <class T>
+__global__ __launch_bounds__(kBlock) void ReducePartialsBatchKernel(int64_t rows, int nparts,
+                                                                    const LassoBatchInst<T>* __restrict__ tab,
+                                                                    bool four) {
+  const LassoBatchInst<T>& I = tab[blockIdx.y];
+  if constexpr (sizeof(T) == 4) {
+    if (four) {
+      ReducePartials4Body(rows, nparts, I.tpart, I.kappa, 0.f, I.p, I.rhs, blockIdx.x);
+      return;
+    }
+  }
+  GemvNReduceBody<T>(rows, nparts, I.tpart, I.kappa, T(0), I.p, I.rhs, blockIdx.x);
+}
 }  // namespace
 
 void ReducePartials(int64_t rows, int nparts, const DVec& partial, double alpha, double beta,
@@ -738,6 +772,145 @@ void Gemv(bool trans, int64_t rows, int64_t cols, double alpha, const DVec& A, i
     if (trans) LaunchGemvT<double>(rows, cols, alpha, A.as<double>(), lda, x.as<double>(), beta, y.as<double>());
     else LaunchGemvN<double>(rows, cols, alpha, A.as<double>(), lda, x.as<double>(), beta, y.as<double>());
   }
+}
+
+namespace {
+// SymvTileKernel<T, true> for the right-hand sides of a batched sweep: the tile is loaded once,
+// then each right-hand side b runs the single kernel's row and column sums on it, in its order,
+// into its own partials (work + b * ws).
+template <class T>
+__global__ __launch_bounds__(kBlock) void SymvTileBatchKernel(int64_t n, const T* __restrict__ S,
+                                                              const LassoBatchInst<T>* __restrict__ tab, int count,
+                                                              T* __restrict__ work, int64_t ws, int64_t ntiles) {
+  __shared__ T xI[kSB], xJ[kSB];
+  __shared__ T red[32][kSB];
+  const int64_t lin = blockIdx.x;
+  int64_t I = static_cast<int64_t>((sqrt(8.0 * static_cast<double>(lin) + 1.0) - 1.0) * 0.5);
+  while ((I + 1) * (I + 2) / 2 <= lin) ++I;
+  while (I * (I + 1) / 2 > lin) --I;
+  const int64_t J = lin - I * (I + 1) / 2;
+  const int64_t i0 = I * kSB, j0 = J * kSB;
+  const int t = threadIdx.x;
+  const int rg = t & 7, cg = t >> 3;
+  T a[4][4][4];  // [k][q][v]
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int c = cg + 32 * k;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int r = 4 * (rg + 8 * q);
+      const T* src = S + lin * (kSB * kSB) + r + c * kSB;
+      if constexpr (sizeof(T) == 4) {
+        *reinterpret_cast<float4*>(a[k][q]) = *reinterpret_cast<const float4*>(src);
+      } else {
+        *reinterpret_cast<double2*>(&a[k][q][0]) = *reinterpret_cast<const double2*>(src);
+        *reinterpret_cast<double2*>(&a[k][q][2]) = *reinterpret_cast<const double2*>(src + 2);
+      }
+    }
+  }
+  for (int b = 0; b < count; ++b) {
+    const T* x = tab[b].p;
+    T* prow = work + b * ws;
+    T* pcol = prow + ntiles * kSB;
+    if (b > 0) __syncthreads();  // the previous right-hand side is out of xI / xJ / red
+    if (t < kSB) {
+      xI[t] = (i0 + t < n) ? x[i0 + t] : T(0);
+    } else {
+      const int c = t - kSB;
+      xJ[c] = (j0 + c < n) ? x[j0 + c] : T(0);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        T rs = T(0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) rs += a[k][q][v] * xJ[cg + 32 * k];
+        red[cg][4 * (rg + 8 * q) + v] = rs;
+      }
+    }
+    if (I != J) {
+      T xr[4][4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) xr[q][v] = xI[4 * (rg + 8 * q) + v];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        T cs = T(0);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int v = 0; v < 4; ++v) cs += a[k][q][v] * xr[q][v];
+        cs += __shfl_xor(cs, 1, 64);
+        cs += __shfl_xor(cs, 2, 64);
+        cs += __shfl_xor(cs, 4, 64);
+        if (rg == 0) pcol[lin * kSB + cg + 32 * k] = cs;
+      }
+    }
+    __syncthreads();
+    if (t < kSB) {
+      T s = red[0][t];
+#pragma unroll
+      for (int g = 1; g < 32; ++g) s += red[g][t];
+      prow[lin * kSB + t] = s;
+    }
+  }
+}
+
+template <class T>
+__global__ __launch_bounds__(kBlock) void SymvReduceBatchKernel(int64_t n, int64_t nb, const T* __restrict__ work,
+                                                                int64_t ws, int64_t ntiles, T alpha,
+                                                                const LassoBatchInst<T>* __restrict__ tab) {
+  const T* prow = work + blockIdx.y * ws;
+  SymvReduceBody<T>(n, nb, prow, prow + ntiles * kSB, alpha, T(0), const_cast<T*>(tab[blockIdx.y].w), blockIdx.x);
+}
+
+template <class T>
+void LaunchSymvPackedBatch(int64_t n, double alpha, const T* P, const LassoBatchInst<T>* tab, int count, T* work) {
+  hipStream_t s = Runtime::Get().stream();
+  const int64_t nb = (n + kSB - 1) / kSB;
+  const int64_t ntiles = nb * (nb + 1) / 2;
+  const int64_t ws = SymvWorkspace(n);
+  hipLaunchKernelGGL((SymvTileBatchKernel<T>), dim3(static_cast<unsigned>(ntiles)), dim3(kBlock), 0, s, n, P, tab,
+                     count, work, ws, ntiles);
+  hipLaunchKernelGGL((SymvReduceBatchKernel<T>), dim3(static_cast<unsigned>(nb), static_cast<unsigned>(count)),
+                     dim3(kBlock), 0, s, n, nb, work, ws, ntiles, T(alpha), tab);
+}
+}  // namespace
+
+void ReducePartialsBatch(int64_t m, int nparts, const DVec& table, int count, DType dt, bool rhs_aligned) {
+  if (m == 0 || count == 0) return;
+  EPS_CHECK(count <= 65535);
+  hipStream_t s = Runtime::Get().stream();
+  ProfScope prof("batch_reduce_partials", m, nparts);
+  // the form ReducePartials picks for each instance alone (its partials and p are allocations of
+  // their own, 16-byte aligned)
+  const bool four = dt == F32 && m % 4 == 0 && nparts >= 64 && rhs_aligned;
+  const unsigned gx = static_cast<unsigned>(four ? (m / 4 + kRQ4 - 1) / kRQ4 : (m + 63) / 64);
+  if (dt == F32)
+    hipLaunchKernelGGL(ReducePartialsBatchKernel<float>, dim3(gx, static_cast<unsigned>(count)), dim3(kBlock), 0, s,
+                       m, nparts, reinterpret_cast<const LassoBatchInst<float>*>(table.as<char>()), four);
+  else
+    hipLaunchKernelGGL(ReducePartialsBatchKernel<double>, dim3(gx, static_cast<unsigned>(count)), dim3(kBlock), 0, s,
+                       m, nparts, reinterpret_cast<const LassoBatchInst<double>*>(table.as<char>()), false);
+  EPS_HIP(hipGetLastError());
+}
+
+void SymvPackedBatch(int64_t m, double alpha, const DVec& P, const DVec& table, int count, const DVec& work) {
+  if (m == 0 || count == 0) return;
+  EPS_CHECK(P.n >= SymvPackedSize(m) && count <= 65535);
+  EPS_CHECK(work.dt == P.dt && work.n >= count * SymvWorkspace(m));
+  ProfScope prof("batch_symv_packed", m, count);
+  if (P.dt == F32)
+    LaunchSymvPackedBatch<float>(m, alpha, P.as<float>(), reinterpret_cast<const LassoBatchInst<float>*>(table.as<char>()),
+                                 count, work.as<float>());
+  else
+    LaunchSymvPackedBatch<double>(m, alpha, P.as<double>(),
+                                  reinterpret_cast<const LassoBatchInst<double>*>(table.as<char>()), count,
+                                  work.as<double>());
+  EPS_HIP(hipGetLastError());
 }
 
 }  // namespace k

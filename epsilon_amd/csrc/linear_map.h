@@ -90,6 +90,7 @@ class DataMap {
   std::vector<double> DenseHost(const pb::Constant& c);
   // Values bound to CVXPY Parameters for this call (reference solver.cc:109-116).
   void SetParameter(const std::string& id, const pb::Constant& c) { params_[id] = c; }
+  void ClearParameters() { params_.clear(); }
   const pb::Constant& Resolve(const pb::Constant& c) const;
 
  private:

@@ -100,6 +100,33 @@ int eps_solve(const void* problem, size_t problem_len, const void* solver_params
               size_t solver_params_len, const eps_blob* data, size_t ndata,
               const eps_param* params, size_t nparams, eps_result** out);
 
+/* K solves that share one data map and one SolverParams, each with its own problem bytes and
+ * its own parameter bindings: a regularisation path (lambda lives in the problem bytes), several
+ * right-hand sides b (a parameter or another constant blob), cross-validation folds.
+ * Contract: out[k] is exactly what eps_solve(problems[k], ..., params[k], nparams[k]) returns -
+ * the same SolverStatus (state, num_iterations, residuals; the timing fields are this call's)
+ * and the same variable values, bit for bit.  No reference counterpart.
+ *   problems[k], problem_lens[k]   serialized `Problem` of instance k (k < count)
+ *   params[k], nparams[k]          instance k's bindings; nparams == NULL: none for any instance,
+ *                                  params[k] may be NULL where nparams[k] == 0
+ *   data, solver_params            shared by all instances; host blobs are read during the call
+ *   out                            caller's array of `count` pointers; on success out[k] is
+ *                                  instance k's result (input order), owned by the caller and
+ *                                  freed with eps_result_free
+ * Instances of the fused "least squares + separable threshold" form (the compiled lasso with
+ * NORM_1 / SUM_DEADZONE / SUM_HINGE / SUM_QUANTILE, multi-block driver, one GPU) that share the
+ * data matrix run together: one Gram product and one inverse for all, then sweeps that read the
+ * matrix once for up to KB instances, each instance stopped at its own residual
+ * check.  Every other instance - and a fused one with no partner - is solved alone by eps_solve's
+ * code.  Per-iteration log lines (verbose) are not printed for instances solved together.
+ * Errors: count == 0 or a NULL array fails; an instance that fails to parse, to set up or to
+ * solve fails the whole call and eps_last_error() names its index.  On any failure every out[k]
+ * is NULL and nothing is left allocated. */
+int eps_solve_batch(const void* const* problems, const size_t* problem_lens, size_t count,
+                    const void* solver_params, size_t solver_params_len, const eps_blob* data,
+                    size_t ndata, const eps_param* const* params, const size_t* nparams,
+                    eps_result** out);
+
 /* Replaces `_solve.eval_prox(f_expr, lam, data, v)` (solvemodule.cc:189-242):
  * argmin_x lam*f(x) + 1/2||x - v||^2 for one PROX_FUNCTION expression.  `v` holds one
  * float64 host blob per variable id.  The result has an empty status. */
