@@ -458,9 +458,11 @@ class ProxADMMSolver final : public Solver {
     mem->y1prev = f.y1prev;
     mem->alpha_vec = f.sz.alpha_vec;
     mem->beta_vec = f.sz.beta_vec;
-    mem->p = f.p;
-    mem->rhs = f.ls.rhs_arg;
-    mem->kappa = -L.scale();
+    // whitened route: the reduction writes w_hat itself, with X rhs folded in
+    mem->p = f.whiten ? f.w : f.p;
+    mem->rhs = f.whiten ? f.rhat : f.ls.rhs_arg;
+    mem->kappa = PassKappa();
+    mem->pkappa = -L.scale();
     mem->Bs = f.sz.Bs;
     mem->Cs = f.sz.Cs;
     mem->a1 = f.a1;
@@ -477,15 +479,17 @@ class ProxADMMSolver final : public Solver {
             static_cast<uint64_t>(f.m), static_cast<uint64_t>(f.n), static_cast<uint64_t>(dt),
             bits(L.scale()), reinterpret_cast<uintptr_t>(D.data().data()), bits(D.scale()),
             reinterpret_cast<uintptr_t>(f.symv_packed.data()), f.symv_work.n > 0 ? 1u : 0u,
-            static_cast<uint64_t>(params_.max_iterations), static_cast<uint64_t>(params_.epoch_iterations)};
+            static_cast<uint64_t>(params_.max_iterations), static_cast<uint64_t>(params_.epoch_iterations),
+            f.whiten ? 1u : 0u, reinterpret_cast<uintptr_t>(f.Ahat.data())};
     return true;
   }
   const DVec& batch_packed_inverse() const { return fs_.symv_packed; }
   double batch_inverse_scale() const { return fs_.ls.Dinv_arg->scale(); }
   int batch_grid() const { return fs_.grid; }
+  bool batch_whitened() const { return fs_.whiten; }
   const DVec& batch_matrix(int64_t* lda) const {
-    *lda = fs_.ls.L_arg_var->rows();
-    return fs_.ls.L_arg_var->data();
+    *lda = fs_.whiten ? fs_.m : fs_.ls.L_arg_var->rows();
+    return fs_.whiten ? fs_.Ahat : fs_.ls.L_arg_var->data();
   }
   void BatchApplyInverse() { ApplyInverseFixed(); }
   // the residual check at sweep `iter`: its scalars into the next slots, then (after the fetch)
@@ -580,6 +584,10 @@ class ProxADMMSolver final : public Solver {
   }
 
   // ---- fused sweep: "least squares + separable threshold" (kernels_fused.hip) ------------------
+ private:
+  struct FusedState;  // (below)
+
+ protected:
   // Recognised structure (the compiled lasso): two terms [SUM_SQUARE with a dense
   // argument map, scaled-zone prox with scalar maps], one consensus constraint a0 x' + a1 x = 0
   // with a0 = 1 and no constant.  The sweep is then: one fused pass over A (back substitution of
@@ -661,7 +669,9 @@ class ProxADMMSolver final : public Solver {
     }
     {
       const DenseMatrixImpl& D = *f.ls.Dinv_arg;
-      if (D.symmetric() && D.rows() == f.m && D.rows() >= 1024 && !D.trans()) {
+      if (!f.use_peer && !ShardSpec::Get().active() && EnableWhiten(&f)) {
+        // no inverse apply in the sweep: no workspace, no packed copy
+      } else if (D.symmetric() && D.rows() == f.m && D.rows() >= 1024 && !D.trans()) {
         f.symv_work = DVec::Empty(k::SymvWorkspace(f.m), dt);
         // the apply reads a tile-packed copy of the lower tiles (EPSILON_HIP_SYMV_PACKED=0: the
         // matrix as it lies): +m^2/2 values of memory for a tenth of a millisecond at Init
@@ -691,6 +701,58 @@ class ProxADMMSolver final : public Solver {
     FusedForward(/*from_state=*/true);
   }
 
+  // The whitened route.  With Dinv_arg = c X^T X, where X = L^-1 is the inverse Cholesky factor
+  // kept by DenseMatrixImpl::Inverse, the forward product of a sweep is
+  //   d = A^T Dinv p = c (X A)^T (X p),   X p = X rhs - s_L (X A) v,
+  // so the pass streams A_hat = X A (same shape as A, formed once at Init) and its partials reduce
+  // to w_hat = X p directly: no m x m matrix is read in the sweep.  f32, one GPU, m >= 2048, n >= 2m.
+  bool EnableWhiten(FusedState* f) {
+    const DenseMatrixImpl& L = *f->ls.L_arg_var;
+    const DenseMatrixImpl& D = *f->ls.Dinv_arg;
+    OpCache* cache = CurrentOpCache();
+    if (!FusedWhitenEnabled() || cache == nullptr || data_->dtype() != F32 || L.dtype() != F32 ||
+        f->m < kWhitenMinRows)
+      return false;
+    // wide data only: A_hat is formed on the split-f16 matrix cores (about 4x the f32 rounding), and
+    // a nearly square A amplifies that in the iterates (10244 x 10260: 4e-5 off the generic path
+    // after 200 sweeps, twice the fused path's parity tolerance)
+    if (f->n < 2 * f->m) return false;
+    if (D.id() == 0 || D.trans() || D.rows() != f->m || D.cols() != f->m || L.rows() != f->m) return false;
+    // X belongs to exactly this inverse: the cached entry under D's key holds D's own buffer
+    const auto inv = cache->Find(D.id());
+    const auto X = cache->Find(FactorInverseKey(D.id()));
+    if (!inv || !X || inv->data().data() != D.data().data() || X->rows() != f->m || X->cols() != f->m)
+      return false;
+    // A_hat is shared like the packed inverse: a warm re-Init and the members of a batch find it
+    const uint64_t key = HashCombine(HashCombine(HashCombine(HashCombine(X->id(), 0x3a7),
+                                                             reinterpret_cast<uintptr_t>(L.data().data())),
+                                                 L.id()),
+                                     static_cast<uint64_t>(f->n));
+    DVec Ahat;
+    if (auto hit = cache->Find(key)) {
+      Ahat = hit->data();
+    } else {
+      Ahat = DVec::Empty(f->m * f->n, F32);
+      // X is lower triangular: each tile of the product runs over its own k range
+      if (!k::GemmSplitF16KRange(4, f->m, f->n, f->m, 1.0, X->data(), f->m, L.data(), f->m, Ahat, f->m))
+        k::Gemm(false, false, f->m, f->n, f->m, 1.0, X->data(), f->m, L.data(), f->m, 0.0, Ahat, f->m);
+      cache->Put(key, std::make_shared<DenseMatrixImpl>(Ahat, f->m, f->n, false, 1.0, key));
+    }
+    if (!k::LassoFusedSupported(f->m, f->n, Ahat, f->m)) return false;
+    // X rhs on every Init: parameters re-bind the rhs
+    if (f->ls.rhs_arg.n != 0) {
+      f->rhat = DVec::Empty(f->m, F32);
+      k::Gemv(false, f->m, f->m, 1.0, X->data(), f->m, f->ls.rhs_arg, 0.0, f->rhat);
+    }
+    f->X = X->data();
+    f->Ahat = Ahat;
+    f->wscale = D.scale();
+    f->whiten = true;
+    return true;
+  }
+  // kappa of the pass: x0 = v0 + kappa A^T w (whitened: c A_hat^T w_hat)
+  double PassKappa() const { return -fs_.ls.L_arg_var->scale() * (fs_.whiten ? fs_.wscale : 1.0); }
+
   // The tile-packed copy of the cached inverse; instances of a batch (shared cache) that share
   // the inverse share one copy.
   DVec PackInverse(const DenseMatrixImpl& D, int64_t m) {
@@ -708,6 +770,21 @@ class ProxADMMSolver final : public Solver {
   void FusedForward(bool from_state) {
     FusedState& f = fs_;
     const DenseMatrixImpl& L = *f.ls.L_arg_var;
+    if (f.whiten) {
+      if (from_state) {
+        // w_hat = X (rhs - L v0) once, from the current state
+        DVec v0 = f.u.Clone();
+        k::Axpby(v0, -1.0, f.y0, 1.0);
+        k::Axpby(v0, -1.0, f.y1, 1.0);
+        k::Axpby(v0, 1.0, f.y0, 1.0);
+        L.Apply(-1.0, v0, 0.0, f.p);
+        if (f.ls.rhs_arg.n != 0) k::Axpby(f.p, 1.0, f.ls.rhs_arg, 1.0);
+        k::Gemv(false, f.m, f.m, 1.0, f.X, f.m, f.p, 0.0, f.w);
+      } else {
+        k::ReducePartials(f.m, f.grid, f.tpart, -L.scale(), 0.0, f.w, f.rhat.n != 0 ? &f.rhat : nullptr);
+      }
+      return;
+    }
     if (from_state) {
       // v0 = ((u - y0) - y1) + y0 of the current state, then the generic forward product
       DVec v0 = f.u.Clone();
@@ -825,7 +902,7 @@ class ProxADMMSolver final : public Solver {
     if (GenericGraphWanted(count) && gg_.Run(count, StateHandles(), static_cast<size_t>(N_), [this] { Sweep(); })) return;
     const ShardSpec& sh = ShardSpec::Get();
     const bool rccl_in_sweep = fused_ && !fs_.use_peer && sh.active() && sh.IsSharded(fs_.ls.var_key);
-    const bool fixed_buffers = (fs_.use_peer && fs_.peer_slab) || fs_.symv_work.n > 0;
+    const bool fixed_buffers = (fs_.use_peer && fs_.peer_slab) || fs_.symv_work.n > 0 || fs_.whiten;
     const bool want = fused_ && !rccl_in_sweep && fixed_buffers &&
                       (mode == 1 || (mode != 0 && fs_.use_peer));
     if (!want || count < 2 || rt.profiling()) {
@@ -861,10 +938,10 @@ class ProxADMMSolver final : public Solver {
     k::LassoFusedArgs a;
     a.m = f.m;
     a.n = f.n;
-    a.lda = L.rows();
-    a.A = L.data();
+    a.lda = f.whiten ? f.m : L.rows();
+    a.A = f.whiten ? f.Ahat : L.data();
     a.w = f.w;
-    a.kappa = -L.scale();
+    a.kappa = PassKappa();
     a.Bs = f.sz.Bs;
     a.Cs = f.sz.Cs;
     a.a1 = f.a1;
@@ -1044,6 +1121,9 @@ class ProxADMMSolver final : public Solver {
     DVec symv_packed;  // the cached inverse's lower tiles, each contiguous (empty: apply from the matrix)
     DVec state_all, snapshot;  // u, x0, x1, y0, y1, y1prev in one buffer; its copy at a check
     DVec norm_work;            // partials + ticket of the one-launch residual norms
+    bool whiten = false;       // the pass streams Ahat = X A, w holds X p (EnableWhiten)
+    double wscale = 1;         // c of Dinv_arg = c X^T X
+    DVec X, Ahat, rhat;        // L^-1 of the inverse, X A (ld m), X rhs_arg (empty: no rhs)
   };
   bool fused_ = false;
   FusedState fs_;
@@ -1358,7 +1438,9 @@ void RunFusedGroup(const std::vector<ProxADMMSolver*>& g, const std::vector<k::L
     for (int first = 0; first < na; first += width)
       k::LassoBatchPass(m, n, lda, A, table, first, std::min(width, na - first));
     k::ReducePartialsBatch(m, grid, table, na, dt, rhs_aligned);
-    if (P.n > 0) {
+    if (lead.batch_whitened()) {
+      // the reduction wrote every member's w_hat: no inverse apply
+    } else if (P.n > 0) {
       k::SymvPackedBatch(m, dscale, P, table, na, symv_work);
     } else {
       for (int i : active) g[i]->BatchApplyInverse();  // D.Apply / Symv: per instance

@@ -100,11 +100,13 @@ template <class T> struct LassoBatchInst {
   T* p;              // m: the reduced partials (+ rhs), input of the inverse apply
   const T* rhs;      // m: constant part of the rhs (nullptr: none)
   T kappa, Bs, Cs, a1, lam, alpha, beta, M;
+  T pkappa;          // scale of the summed partials in p (kappa, but for the whitened route)
 };
 // Host view of one instance (scalars as double, narrowed per dtype on upload).
 struct LassoBatchMember {
   DVec w, tpart, u, x0, x1, y0, y1, y1prev, alpha_vec, beta_vec, p, rhs;
   double kappa = 0, Bs = 0, Cs = 0, a1 = 0, lam = 0, alpha = 1, beta = 1, M = 0;
+  double pkappa = 0;
 };
 // Instances one launch of the batched pass carries for (m, dtype) - set by the register budget
 // of its instantiation - or 0 where the single pass would take a form the batched one does not
@@ -117,8 +119,8 @@ void LassoBatchUpload(const std::vector<const LassoBatchMember*>& members, DType
 // loaded column of A feeds every instance's dot product, chain and forward update.
 void LassoBatchPass(int64_t m, int64_t n, int64_t lda, const DVec& A, const DVec& table, int first,
                     int count);
-// p = kappa * sum(tpart) (+ rhs) of `count` instances in one launch, each in the summation order
-// of ReducePartials(m, nparts, tpart, kappa, 0, p, rhs).  `rhs_aligned`: every rhs present is
+// p = pkappa * sum(tpart) (+ rhs) of `count` instances in one launch, each in the summation order
+// of ReducePartials(m, nparts, tpart, pkappa, 0, p, rhs).  `rhs_aligned`: every rhs present is
 // 16-byte aligned (picks the same kernel form as the single call).
 void ReducePartialsBatch(int64_t m, int nparts, const DVec& table, int count, DType dt,
                          bool rhs_aligned);
@@ -197,7 +199,8 @@ void KronDense(const DVec& dst, const DVec& A, int64_t mA, int64_t nA, const DVe
 // ---- K5: symmetric definite inverse (reference linear/dense_matrix_impl.cc:21-30) ---------
 // W (n x n, ld = n, symmetric positive definite, full storage) -> W^{-1} in place.
 // Blocked Cholesky + triangular inverse + X^T X, all on device.  Throws if a pivot is <= 0.
-void SpdInverseInPlace(const DVec& W, int64_t n);
+// `factor_inverse` (optional) receives X = L^-1 (n x n, ld n, zeros above the diagonal).
+void SpdInverseInPlace(const DVec& W, int64_t n, DVec* factor_inverse = nullptr);
 // Cholesky step form of the next factorisations: -1 by environment (default), 0 the fused f32 step,
 // 1 the diagonal + panel launches (tests hold the two forms to each other)
 void SetPotrfForm(int form);

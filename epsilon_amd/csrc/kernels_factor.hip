@@ -477,7 +477,7 @@ void CheckFlag(int* flag);
 void DoublingInverse(const DVec& W, const DVec& X, int64_t n, const DVec& dinv, int64_t cap);
 }  // namespace
 
-void SpdInverseInPlace(const DVec& W, int64_t n) {
+void SpdInverseInPlace(const DVec& W, int64_t n, DVec* factor_inverse) {
   EPS_CHECK(W.n >= n * n);
   if (n == 0) return;
   Runtime& rt = Runtime::Get();
@@ -520,6 +520,7 @@ void SpdInverseInPlace(const DVec& W, int64_t n) {
   SymmetrizeFromLower(W, n, ld);
 
   CheckFlag(flag);
+  if (factor_inverse) *factor_inverse = X;
 }
 
 namespace {

@@ -197,6 +197,7 @@ LassoBatchInst<T> Narrow(const LassoBatchMember& s) {
   d.p = s.p.as<T>();
   d.rhs = s.rhs.n > 0 ? s.rhs.as<T>() : nullptr;
   d.kappa = static_cast<T>(s.kappa);
+  d.pkappa = static_cast<T>(s.pkappa);
   d.Bs = static_cast<T>(s.Bs);
   d.Cs = static_cast<T>(s.Cs);
   d.a1 = static_cast<T>(s.a1);

@@ -218,6 +218,11 @@ __global__ __launch_bounds__(kThreads, 2) void GemmSplitF16Kernel(
     while ((I + 1) * (I + 2) / 2 <= lin) ++I;
     while (I * (I + 1) / 2 > lin) --I;
     J = lin - I * (I + 1) / 2;
+  } else if (tri == 4) {  // tile row I runs over (I + 1) TS of k: the longest rows go first, so the
+                          // last tiles to start are short ones (no long tile left alone at the end)
+    const int64_t TI = (M + TS - 1) / TS, TJ = (N + TS - 1) / TS;
+    I = TI - 1 - lin / TJ;
+    J = lin % TJ;
   } else {
     const int64_t TI = (M + TS - 1) / TS;
     I = lin % TI;

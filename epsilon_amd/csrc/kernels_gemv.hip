@@ -708,7 +708,7 @@ __global__ __launch_bounds__(kBlock) void ReducePartials4Kernel(int64_t rows, in
 }
 
 // ---- the same reductions for the instances of a batched fused sweep (kernels_fused_batch.hip):
-// workgroup row (blockIdx.y) b runs instance b's single reduction, p_b = kappa_b sum(tpart_b) + rhs_b
+// workgroup row (blockIdx.y) b runs instance b's single reduction, p_b = pkappa_b sum(tpart_b) + rhs_b
 template <class T>
 __global__ __launch_bounds__(kBlock) void ReducePartialsBatchKernel(int64_t rows, int nparts,
                                                                     const LassoBatchInst<T>* __restrict__ tab,
@@ -716,11 +716,11 @@ __global__ __launch_bounds__(kBlock) void ReducePartialsBatchKernel(int64_t rows
   const LassoBatchInst<T>& I = tab[blockIdx.y];
   if constexpr (sizeof(T) == 4) {
     if (four) {
-      ReducePartials4Body(rows, nparts, I.tpart, I.kappa, 0.f, I.p, I.rhs, blockIdx.x);
+      ReducePartials4Body(rows, nparts, I.tpart, I.pkappa, 0.f, I.p, I.rhs, blockIdx.x);
       return;
     }
   }
-  GemvNReduceBody<T>(rows, nparts, I.tpart, I.kappa, T(0), I.p, I.rhs, blockIdx.x);
+  GemvNReduceBody<T>(rows, nparts, I.tpart, I.pkappa, T(0), I.p, I.rhs, blockIdx.x);
 }
 }  // namespace
 

@@ -348,8 +348,10 @@ std::shared_ptr<const LinearMapImpl> DenseMatrixImpl::Inverse() const {
   }
   DVec W = DVec::Empty(nn * nn, data_.dt);
   k::MatCopy(trans_, nn, nn, sign * scale_, data_, rows_, W);
+  const bool keep_x = key != 0 && data_.dt == F32 && nn >= kWhitenMinRows && FusedWhitenEnabled();
+  DVec X;
   try {
-    k::SpdInverseInPlace(W, nn);
+    k::SpdInverseInPlace(W, nn, keep_x ? &X : nullptr);
   } catch (const Error&) {
     // Not definite.  The reference's LDLT (dense_matrix_impl.cc:25-29) also inverts symmetric
     // INDEFINITE matrices; the Schur complements of the prox KKT systems never are, so this is
@@ -358,10 +360,23 @@ std::shared_ptr<const LinearMapImpl> DenseMatrixImpl::Inverse() const {
     (void)hipGetLastError();
     k::MatCopy(trans_, nn, nn, sign * scale_, data_, rows_, W);
     W = SymmetricInverseByEig(W, nn);
+    X = DVec();  // no factor: solves with this inverse keep the explicit apply
   }
   auto result = std::make_shared<DenseMatrixImpl>(W, nn, nn, false, sign, key, true);
   if (cache && key) cache->Put(key, result);
+  if (cache && key && X.n > 0) {
+    const uint64_t xkey = FactorInverseKey(key);
+    cache->Put(xkey, std::make_shared<DenseMatrixImpl>(X, nn, nn, false, 1.0, xkey));
+  }
   return result;
+}
+
+bool FusedWhitenEnabled() {
+  static const bool on = [] {
+    const char* e = std::getenv("EPSILON_HIP_FUSED_WHITEN");
+    return !(e && e[0] == '0');
+  }();
+  return on;
 }
 std::shared_ptr<const LinearMapImpl> DenseMatrixImpl::InverseDistributed() const {
   Comm* comm = Runtime::Get().comm();
