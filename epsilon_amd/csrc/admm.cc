@@ -441,35 +441,14 @@ class ProxADMMSolver final : public Solver {
   // ---- batched solves (RunFusedBatches) -------------------------------------------------------
   // A fresh fused solve whose pass the batched one mirrors: its instance for the batched kernels
   // and the key of the group it can join (same data matrix, inverse, dtype and shape).
-  bool BatchView(k::LassoBatchMember* mem, std::vector<uint64_t>* key) const {
+  bool BatchView(k::LassoInstance* mem, std::vector<uint64_t>* key) const {
     if (!initialized_ || finished_ || iter_ != 0 || !fused_ || fs_.use_peer || ShardSpec::Get().active()) return false;
     const FusedState& f = fs_;
     const DenseMatrixImpl& L = *f.ls.L_arg_var;
     const DenseMatrixImpl& D = *f.ls.Dinv_arg;
     const DType dt = data_->dtype();
     if (L.dtype() != dt || k::LassoBatchWidth(f.m, f.n, dt) == 0) return false;
-    mem->w = f.w;
-    mem->tpart = f.tpart;
-    mem->u = f.u;
-    mem->x0 = f.x0;
-    mem->x1 = f.x1;
-    mem->y0 = f.y0;
-    mem->y1 = f.y1;
-    mem->y1prev = f.y1prev;
-    mem->alpha_vec = f.sz.alpha_vec;
-    mem->beta_vec = f.sz.beta_vec;
-    // whitened route: the reduction writes w_hat itself, with X rhs folded in
-    mem->p = f.whiten ? f.w : f.p;
-    mem->rhs = f.whiten ? f.rhat : f.ls.rhs_arg;
-    mem->kappa = PassKappa();
-    mem->pkappa = -L.scale();
-    mem->Bs = f.sz.Bs;
-    mem->Cs = f.sz.Cs;
-    mem->a1 = f.a1;
-    mem->lam = f.sz.lam;
-    mem->alpha = f.sz.alpha;
-    mem->beta = f.sz.beta;
-    mem->M = f.sz.M;
+    *mem = f.pass.inst;
     auto bits = [](double v) {
       uint64_t b;
       std::memcpy(&b, &v, 8);
@@ -489,8 +468,8 @@ class ProxADMMSolver final : public Solver {
   int batch_grid() const { return fs_.grid; }
   bool batch_whitened() const { return fs_.whiten; }
   const DVec& batch_matrix(int64_t* lda) const {
-    *lda = fs_.whiten ? fs_.m : fs_.ls.L_arg_var->rows();
-    return fs_.whiten ? fs_.Ahat : fs_.ls.L_arg_var->data();
+    *lda = fs_.pass.lda;
+    return fs_.pass.A;
   }
   void BatchApplyInverse() { ApplyInverseFixed(); }
   // the residual check at sweep `iter`: its scalars into the next slots, then (after the fetch)
@@ -685,6 +664,7 @@ class ProxADMMSolver final : public Solver {
     }
     ResetGraph();
     fs_ = f;
+    BuildPass();
     // the generic containers become views of the fused state
     x_[0] = BlockVector();
     x_[0].Set(fs_.ls.var_key, fs_.x0);
@@ -933,39 +913,50 @@ class ProxADMMSolver final : public Solver {
     EPS_HIP(hipGraphLaunch(graph_exec_, rt.stream()));
   }
 
-  void FusedSweep() {
+  // The pass's arguments with the instance as the kernels read it, once per Init: EnableWhiten has
+  // decided the matrix, kappa, p and rhs by now.  Only the peer exchange's epoch is set per sweep.
+  void BuildPass() {
     FusedState& f = fs_;
     const DenseMatrixImpl& L = *f.ls.L_arg_var;
-    k::LassoFusedArgs a;
+    k::LassoFusedArgs& a = f.pass;
     a.m = f.m;
     a.n = f.n;
     a.lda = f.whiten ? f.m : L.rows();
     a.A = f.whiten ? f.Ahat : L.data();
-    a.w = f.w;
-    a.kappa = PassKappa();
-    a.Bs = f.sz.Bs;
-    a.Cs = f.sz.Cs;
-    a.a1 = f.a1;
-    a.lam = f.sz.lam;
-    a.sz_alpha = f.sz.alpha;
-    a.sz_beta = f.sz.beta;
-    a.sz_alpha_vec = f.sz.alpha_vec;
-    a.sz_beta_vec = f.sz.beta_vec;
-    a.sz_M = f.sz.M;
-    a.u = f.u;
-    a.x0 = f.x0;
-    a.x1 = f.x1;
-    a.y0 = f.y0;
-    a.y1 = f.y1;
-    a.y1prev = f.y1prev;
-    a.tpart = f.tpart;
+    k::LassoInstance& s = a.inst;
+    s.w = f.w;
+    s.tpart = f.tpart;
+    s.u = f.u;
+    s.x0 = f.x0;
+    s.x1 = f.x1;
+    s.y0 = f.y0;
+    s.y1 = f.y1;
+    s.y1prev = f.y1prev;
+    s.alpha_vec = f.sz.alpha_vec;
+    s.beta_vec = f.sz.beta_vec;
+    // whitened route: the reduction writes w_hat itself, with X rhs folded in
+    s.p = f.whiten ? f.w : f.p;
+    s.rhs = f.whiten ? f.rhat : f.ls.rhs_arg;
+    s.kappa = PassKappa();
+    s.pkappa = -L.scale();
+    s.Bs = f.sz.Bs;
+    s.Cs = f.sz.Cs;
+    s.a1 = f.a1;
+    s.lam = f.sz.lam;
+    s.alpha = f.sz.alpha;
+    s.beta = f.sz.beta;
+    s.M = f.sz.M;
+  }
+
+  void FusedSweep() {
+    FusedState& f = fs_;
     if (f.use_peer) {
-      a.epoch = Runtime::Get().peer()->view().epoch;
-      k::LassoFusedPass(a);
+      f.pass.epoch = Runtime::Get().peer()->view().epoch;
+      k::LassoFusedPass(f.pass);
       FusedForwardPeer();
       return;
     }
-    k::LassoFusedPass(a);
+    k::LassoFusedPass(f.pass);
     FusedForward(/*from_state=*/false);
   }
 
@@ -1125,6 +1116,7 @@ class ProxADMMSolver final : public Solver {
     bool whiten = false;       // the pass streams Ahat = X A, w holds X p (EnableWhiten)
     double wscale = 1;         // c of Dinv_arg = c X^T X
     DVec X, Ahat, rhat;        // L^-1 of the inverse, X A (ld m), X rhs_arg (empty: no rhs)
+    k::LassoFusedArgs pass;    // what the pass and a batch read of all this (BuildPass)
   };
   bool fused_ = false;
   FusedState fs_;
@@ -1283,6 +1275,40 @@ class ProxADMMTwoBlockSolver final : public Solver {
     f.w = DVec::Zeros(f.m, dt);
     f.grid = k::LassoFusedGrid(f.m, f.n, dt);
     f.tpart = DVec::Empty(static_cast<int64_t>(f.grid) * f.m, dt);
+    {
+      // the pass's arguments, once per Init; chain 1 reads the state arrays as
+      // u -> u0, y0 -> z0, y1 -> z1, y1prev -> z0_prev, e0 -> u1, e1 -> z1_prev
+      k::LassoFusedArgs& a = f.pass;
+      a.m = f.m;
+      a.n = f.n;
+      a.lda = L.rows();
+      a.A = L.data();
+      a.chain = 1;
+      a.a0 = f.a0;
+      a.e0 = f.u1;
+      a.e1 = f.z1p;
+      k::LassoInstance& s = a.inst;
+      s.w = f.w;
+      s.tpart = f.tpart;
+      s.u = f.u0;
+      s.x0 = f.x0;
+      s.x1 = f.x1;
+      s.y0 = f.z0;
+      s.y1 = f.z1;
+      s.y1prev = f.z0p;
+      s.alpha_vec = f.sz.alpha_vec;
+      s.beta_vec = f.sz.beta_vec;
+      s.p = f.p;
+      s.rhs = f.ls.rhs_arg;
+      s.kappa = s.pkappa = -L.scale();
+      s.Bs = f.sz.Bs;
+      s.Cs = f.sz.Cs;
+      s.a1 = f.a1;
+      s.lam = f.sz.lam;
+      s.alpha = f.sz.alpha;
+      s.beta = f.sz.beta;
+      s.M = f.sz.M;
+    }
     fs_ = f;
     // the generic containers become views of the fused state
     auto two = [&](const DVec& a, const DVec& b) {
@@ -1307,34 +1333,7 @@ class ProxADMMTwoBlockSolver final : public Solver {
   void FusedSweep() {
     FusedState& f = fs_;
     const DenseMatrixImpl& L = *f.ls.L_arg_var;
-    k::LassoFusedArgs a;
-    a.m = f.m;
-    a.n = f.n;
-    a.lda = L.rows();
-    a.A = L.data();
-    a.w = f.w;
-    a.kappa = -L.scale();
-    a.Bs = f.sz.Bs;
-    a.Cs = f.sz.Cs;
-    a.a1 = f.a1;
-    a.a0 = f.a0;
-    a.lam = f.sz.lam;
-    a.sz_alpha = f.sz.alpha;
-    a.sz_beta = f.sz.beta;
-    a.sz_alpha_vec = f.sz.alpha_vec;
-    a.sz_beta_vec = f.sz.beta_vec;
-    a.sz_M = f.sz.M;
-    a.chain = 1;
-    a.u = f.u0;
-    a.x0 = f.x0;
-    a.x1 = f.x1;
-    a.y0 = f.z0;
-    a.y1 = f.z1;
-    a.y1prev = f.z0p;
-    a.e0 = f.u1;
-    a.e1 = f.z1p;
-    a.tpart = f.tpart;
-    k::LassoFusedPass(a);
+    k::LassoFusedPass(f.pass);
     k::ReducePartials(f.m, f.grid, f.tpart, -L.scale(), 0.0, f.p,
                       f.ls.rhs_arg.n != 0 ? &f.ls.rhs_arg : nullptr);
     f.ls.Dinv_arg->Apply(1.0, f.p, 0.0, f.w);
@@ -1389,6 +1388,7 @@ class ProxADMMTwoBlockSolver final : public Solver {
     int64_t m = 0, n = 0;
     int grid = 0;
     DVec x0, x1, z0, z1, u0, u1, z0p, z1p, p, w, tpart;
+    k::LassoFusedArgs pass;  // the pass's view of all this, built in TryEnableFused
   };
   bool fused_ = false;
   FusedState fs_;
@@ -1403,9 +1403,48 @@ class ProxADMMTwoBlockSolver final : public Solver {
 // ---------------------------------------------------------------------------------------------------
 namespace {
 
-void RunFusedGroup(const std::vector<ProxADMMSolver*>& g, const std::vector<k::LassoBatchMember>& mem) {
-  const double t0 = Now();
+// Run()'s iteration schedule without the pipelining, for a group of batched members: sweeps up to
+// the next multiple of the epoch, then one residual check of every active member with ONE fetch of
+// their scalars.  A member that stops is frozen: it leaves `active`, and `stopped(gone)` is told
+// which ones left (only when some did).  Members still active at the end get Run()'s
+// max-iterations status.
+template <class Sweep, class Stopped>
+void RunGroupSchedule(const std::vector<ProxADMMSolver*>& g, std::vector<int>* active, Sweep sweep,
+                      Stopped stopped) {
   Runtime& rt = Runtime::Get();
+  const pb::SolverParams& params = g[0]->params();
+  const int epoch = params.epoch_iterations > 0 ? params.epoch_iterations : 1;
+  const int max_it = params.max_iterations;
+  int iter = 0;
+  while (!active->empty() && iter < max_it) {
+    int batch = 1;
+    while ((iter + batch - 1) % epoch != 0) ++batch;
+    if (batch > max_it - iter) batch = max_it - iter;
+    for (int s = 0; s < batch; ++s) sweep();
+    iter += batch - 1;
+    if (iter % epoch == 0) {
+      rt.ResetSlots();
+      for (int i : *active) g[i]->BatchLaunchNorms(iter);
+      rt.FetchSlots();
+      std::vector<int> still, gone;
+      for (int i : *active) (g[i]->BatchFinishCheck() ? gone : still).push_back(i);
+      active->swap(still);
+      if (!gone.empty()) stopped(gone);
+    }
+    ++iter;
+  }
+  for (int i : *active) g[i]->BatchFinishMaxIterations(iter);
+}
+
+// The group's loop time, once the stream has drained.
+void FinishGroup(const std::vector<ProxADMMSolver*>& g, double t0) {
+  Runtime::Get().Sync();
+  const double loop = Now() - t0;
+  for (ProxADMMSolver* s : g) s->BatchSetLoopTime(loop);
+}
+
+void RunFusedGroup(const std::vector<ProxADMMSolver*>& g, const std::vector<k::LassoInstance>& mem) {
+  const double t0 = Now();
   ProxADMMSolver& lead = *g[0];
   const DType dt = lead.data()->dtype();
   SetCurrentDType(dt);
@@ -1416,9 +1455,6 @@ void RunFusedGroup(const std::vector<ProxADMMSolver*>& g, const std::vector<k::L
   const int grid = lead.batch_grid();
   const DVec& P = lead.batch_packed_inverse();
   const double dscale = lead.batch_inverse_scale();
-  const pb::SolverParams& params = lead.params();
-  const int epoch = params.epoch_iterations > 0 ? params.epoch_iterations : 1;
-  const int max_it = params.max_iterations;
   bool rhs_aligned = true;
   for (const auto& mb : mem)
     if (mb.rhs.n > 0) rhs_aligned = rhs_aligned && reinterpret_cast<uintptr_t>(mb.rhs.data()) % 16 == 0;
@@ -1429,7 +1465,7 @@ void RunFusedGroup(const std::vector<ProxADMMSolver*>& g, const std::vector<k::L
   for (int i = 0; i < K; ++i) active[i] = i;
   DVec table;
   auto upload = [&] {
-    std::vector<const k::LassoBatchMember*> v;
+    std::vector<const k::LassoInstance*> v;
     for (int i : active) v.push_back(&mem[i]);
     k::LassoBatchUpload(v, dt, &table);
   };
@@ -1447,33 +1483,11 @@ void RunFusedGroup(const std::vector<ProxADMMSolver*>& g, const std::vector<k::L
       for (int i : active) g[i]->BatchApplyInverse();  // D.Apply / Symv: per instance
     }
   };
-  // Run()'s iteration schedule without the pipelining: sweeps up to the next multiple of the
-  // epoch, then one residual check of every active instance with ONE fetch of their scalars
-  int iter = 0;
-  while (!active.empty() && iter < max_it) {
-    int batch = 1;
-    while ((iter + batch - 1) % epoch != 0) ++batch;
-    if (batch > max_it - iter) batch = max_it - iter;
-    for (int s = 0; s < batch; ++s) sweep();
-    iter += batch - 1;
-    if (iter % epoch == 0) {
-      rt.ResetSlots();
-      for (int i : active) g[i]->BatchLaunchNorms(iter);
-      rt.FetchSlots();
-      std::vector<int> still;
-      for (int i : active)
-        if (!g[i]->BatchFinishCheck()) still.push_back(i);
-      if (still.size() != active.size()) {  // the stopped ones are frozen: drop their descriptors
-        active.swap(still);
-        if (!active.empty()) upload();
-      }
-    }
-    ++iter;
-  }
-  for (int i : active) g[i]->BatchFinishMaxIterations(iter);
-  rt.Sync();
-  const double loop = Now() - t0;
-  for (ProxADMMSolver* s : g) s->BatchSetLoopTime(loop);
+  // the stopped ones are frozen: drop their descriptors
+  RunGroupSchedule(g, &active, sweep, [&](const std::vector<int>&) {
+    if (!active.empty()) upload();
+  });
+  FinishGroup(g, t0);
 }
 
 // EPSILON_HIP_BATCH_WIDE (eps_set_option "batch_wide"), read per batch: "1" sends eligible groups
@@ -1498,9 +1512,8 @@ int BatchWideMin() {  // EPSILON_HIP_BATCH_WIDE_MIN: tuning knob (the crossover 
 // the f32 matrix instruction.  The members' w (and p) live in instance-major panels for the
 // duration; a member keeps its slot until the group ends and a stopped one is masked, so no
 // summation order depends on who else is still iterating.  Not bit-identical to the single solve.
-void RunWideGroup(const std::vector<ProxADMMSolver*>& g, const std::vector<k::LassoBatchMember>& mem_in) {
+void RunWideGroup(const std::vector<ProxADMMSolver*>& g, const std::vector<k::LassoInstance>& mem_in) {
   const double t0 = Now();
-  Runtime& rt = Runtime::Get();
   ProxADMMSolver& lead = *g[0];
   SetCurrentDType(F32);
   int64_t lda = 0;
@@ -1508,16 +1521,13 @@ void RunWideGroup(const std::vector<ProxADMMSolver*>& g, const std::vector<k::La
   const int64_t m = mem_in[0].p.n, n = mem_in[0].u.n;
   const bool whiten = lead.batch_whitened();
   const DenseMatrixImpl& D = lead.batch_inverse();
-  const pb::SolverParams& params = lead.params();
-  const int epoch = params.epoch_iterations > 0 ? params.epoch_iterations : 1;
-  const int max_it = params.max_iterations;
   const int K = static_cast<int>(g.size());
   constexpr int PW = k::kLassoWidePanel;
   const int npanels = (K + PW - 1) / PW;
   const int64_t ldv = (n + 63) / 64 * 64;
   const int64_t panel_len = static_cast<int64_t>(PW) * m;
 
-  std::vector<k::LassoBatchMember> mem = mem_in;
+  std::vector<k::LassoInstance> mem = mem_in;
   DVec Wall = DVec::Zeros(npanels * panel_len, F32);
   DVec Pall = whiten ? DVec() : DVec::Zeros(npanels * panel_len, F32);
   DVec V = DVec::Zeros(static_cast<int64_t>(PW) * ldv, F32);
@@ -1536,7 +1546,7 @@ void RunWideGroup(const std::vector<ProxADMMSolver*>& g, const std::vector<k::La
   DVec apart = whiten ? DVec() : DVec::Empty(aparts * panel_len, F32);
   DVec table;
   {
-    std::vector<const k::LassoBatchMember*> v;
+    std::vector<const k::LassoInstance*> v;
     for (const auto& mb : mem) v.push_back(&mb);
     k::LassoBatchUpload(v, F32, &table);
   }
@@ -1572,32 +1582,13 @@ void RunWideGroup(const std::vector<ProxADMMSolver*>& g, const std::vector<k::La
       }
     }
   };
-  int iter = 0;
-  while (!active.empty() && iter < max_it) {
-    int batch = 1;
-    while ((iter + batch - 1) % epoch != 0) ++batch;
-    if (batch > max_it - iter) batch = max_it - iter;
-    for (int s = 0; s < batch; ++s) sweep();
-    iter += batch - 1;
-    if (iter % epoch == 0) {
-      rt.ResetSlots();
-      for (int i : active) g[i]->BatchLaunchNorms(iter);
-      rt.FetchSlots();
-      std::vector<int> still;
-      for (int i : active) {
-        if (!g[i]->BatchFinishCheck()) still.push_back(i);
-        else live[i / PW] &= ~(uint64_t(1) << (i % PW));  // frozen: its slot is masked from here on
-      }
-      active.swap(still);
-    }
-    ++iter;
-  }
-  for (int i : active) g[i]->BatchFinishMaxIterations(iter);
+  // frozen: their slots are masked from here on
+  RunGroupSchedule(g, &active, sweep, [&](const std::vector<int>& gone) {
+    for (int i : gone) live[i / PW] &= ~(uint64_t(1) << (i % PW));
+  });
   // every member's own w holds what its next sweep would read
   for (int i = 0; i < K; ++i) k::Copy(mem_in[i].w, mem[i].w);
-  rt.Sync();
-  const double loop = Now() - t0;
-  for (ProxADMMSolver* s : g) s->BatchSetLoopTime(loop);
+  FinishGroup(g, t0);
 }
 
 }  // namespace
@@ -1606,7 +1597,7 @@ std::vector<bool> RunFusedBatches(const std::vector<Solver*>& solvers) {
   std::vector<bool> ran(solvers.size(), false);
   const bool wide = BatchWideEnabled();
   std::map<std::vector<uint64_t>, std::vector<size_t>> groups;
-  std::vector<k::LassoBatchMember> mem(solvers.size());
+  std::vector<k::LassoInstance> mem(solvers.size());
   std::vector<std::vector<uint64_t>> order;  // groups in order of their first instance
   for (size_t i = 0; i < solvers.size(); ++i) {
     auto* s = dynamic_cast<ProxADMMSolver*>(solvers[i]);
@@ -1620,7 +1611,7 @@ std::vector<bool> RunFusedBatches(const std::vector<Solver*>& solvers) {
     const std::vector<size_t>& idx = groups[key];
     if (idx.size() < 2) continue;  // alone: the single path is the same solve, with pipelined checks
     std::vector<ProxADMMSolver*> g;
-    std::vector<k::LassoBatchMember> gm;
+    std::vector<k::LassoInstance> gm;
     for (size_t i : idx) {
       g.push_back(static_cast<ProxADMMSolver*>(solvers[i]));
       gm.push_back(mem[i]);

@@ -58,20 +58,28 @@ void ReducePartials(int64_t rows, int nparts, const DVec& partial, double alpha,
                     const DVec& y, const DVec* add = nullptr);
 
 // ---- fused lasso sweep: one pass over A per ADMM sweep (kernels_fused.hip) ------------------
+// One instance of the sweep as the kernels read it (host view: scalars as double, narrowed to
+// the compute type in one place, kernels_fused_chain.h): the multi-block driver's fused state
+// plus its forward vectors.  Built once per Init by the drivers; a batch uploads its members'.
+struct LassoInstance {
+  DVec w;        // m: the block-diagonal-scaled forward-substitution result of this sweep
+  DVec tpart;    // LassoFusedGrid(m, n) * m: per-workgroup partials of A v0'
+  DVec u, x0, x1, y0, y1, y1prev;   // n each, updated in place
+  DVec alpha_vec, beta_vec;         // optional per-column alpha / beta of the scaled zone (n entries)
+  DVec p, rhs;   // m: the reduced partials (+ rhs), input of the inverse apply; its constant part
+  double kappa = 0;                 // x0 = v0 + kappa * (A^T w)
+  double Bs = 0, Cs = 0, a1 = 0;    // prox-1 pre / post scaling, y1 = a1 * x1
+  double lam = 0, alpha = 1, beta = 1, M = 0;
+  double pkappa = 0;                // scale of the summed partials in p (see LassoBatchInst)
+};
 struct LassoFusedArgs {
   int64_t m = 0, n = 0, lda = 0;
   DVec A;        // m x n column-major
-  DVec w;        // m: the block-diagonal-scaled forward-substitution result of this sweep
-  double kappa = 0;                 // x0 = v0 + kappa * (A^T w)
-  double Bs = 0, Cs = 0, a1 = 0;    // prox-1 pre / post scaling, y1 = a1 * x1
-  double lam = 0, sz_alpha = 1, sz_beta = 1, sz_M = 0;
-  DVec sz_alpha_vec, sz_beta_vec;   // optional per-column alpha / beta (n entries; f32 pass only)
-  DVec u, x0, x1, y0, y1, y1prev;   // n each, updated in place
-  DVec tpart;                       // LassoFusedGrid(m, n) * m: per-workgroup partials of A v0'
+  LassoInstance inst;
   unsigned* epoch = nullptr;        // optional device counter, incremented once per launch
   // chain = 1: the two-block driver's sweep (prox_admm_two_block.cc:97-112); the arrays then mean
   // u -> u0, y0 -> z0, y1 -> z1, y1prev -> z0_prev, e0 -> u1, e1 -> z1_prev; a0, a1: the consensus
-  // constraint a0 x0 + a1 x1 = 0 the z-update projects onto.  f32 only.
+  // constraint a0 x0 + a1 x1 = 0 the z-update projects onto.  f32 and f64.
   int chain = 0;
   double a0 = 1;
   DVec e0, e1;
@@ -102,19 +110,13 @@ template <class T> struct LassoBatchInst {
   T kappa, Bs, Cs, a1, lam, alpha, beta, M;
   T pkappa;          // scale of the summed partials in p (kappa, but for the whitened route)
 };
-// Host view of one instance (scalars as double, narrowed per dtype on upload).
-struct LassoBatchMember {
-  DVec w, tpart, u, x0, x1, y0, y1, y1prev, alpha_vec, beta_vec, p, rhs;
-  double kappa = 0, Bs = 0, Cs = 0, a1 = 0, lam = 0, alpha = 1, beta = 1, M = 0;
-  double pkappa = 0;
-};
 // Instances one launch of the batched pass carries for (m, dtype) - set by the register budget
 // of its instantiation - or 0 where the single pass would take a form the batched one does not
-// mirror (512-thread workgroups, the pair kernel): such instances are solved one by one.
+// mirror (512-thread workgroups): such instances are solved one by one.
 int LassoBatchWidth(int64_t m, int64_t n, DType dt);
 // The descriptors of `members` in order into `table` (device; grown as needed): the active set
 // of a batch is this array, so an instance that stops is dropped by uploading the shorter list.
-void LassoBatchUpload(const std::vector<const LassoBatchMember*>& members, DType dt, DVec* table);
+void LassoBatchUpload(const std::vector<const LassoInstance*>& members, DType dt, DVec* table);
 // The fused pass of instances [first, first + count) of `table`, count <= LassoBatchWidth: each
 // loaded column of A feeds every instance's dot product, chain and forward update.
 void LassoBatchPass(int64_t m, int64_t n, int64_t lda, const DVec& A, const DVec& table, int first,

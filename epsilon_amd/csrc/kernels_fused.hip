@@ -15,16 +15,16 @@
 // each (this file is compiled with -ffp-contract=off), so given d_j the state is bit-identical
 // to the unfused path.  HBM traffic per sweep drops from (2mn + m^2)s to (mn + m^2)s.
 //
-// Geometry: 256 threads own all m rows (thread t: rows 4(t + 256q), q < NR - 16 B loads,
-// coalesced 4 KiB per q); w and the partial t' stay in registers for the whole launch; the dot
-// products are reduced with wave shuffles + LDS in a fixed order (deterministic); per-workgroup
-// partial t' vectors are summed by ReducePartials.  Two forms: LassoFusedKernel takes columns in
-// pairs (2*NR loads, then reduce / chain / update with nothing in flight);
-// LassoFusedStreamKernel (the default) takes one column per step with the next column's NR
-// loads already issued, so the memory pipe never drains.
+// Geometry: BS threads own all m rows (thread t: rows R(t + BS q), q < NR - 16 B loads of R = 4
+// f32 or 2 f64 rows, coalesced); w and the partial t' stay in registers for the whole launch; the
+// dot products are reduced with wave shuffles + LDS in a fixed order (deterministic);
+// per-workgroup partial t' vectors are summed by ReducePartials.  LassoFusedStreamKernelT takes
+// one column per step with the next column's NR loads already issued, so the memory pipe never
+// drains.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "kernels.h"
 #include "kernels_fused_chain.h"
@@ -36,345 +36,40 @@ namespace {
 
 constexpr int kBlock = 256;
 
-__device__ inline float WaveSumF(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-__device__ inline float ScaledZoneOne(float v, float lam, float alpha, float beta, float M) {
-  // reference prox/scaled_zone.cc:90-101 with C = 0
-  float xi = v;
-  if (fabsf(xi) <= M) return xi;
-  if (xi > M + lam * alpha) return xi - lam * alpha;
-  if (xi < -M - lam * beta) return xi + lam * beta;
-  if (xi > 0.0f) return M;
-  return -M;
-}
-
-struct FusedScalars {
-  float kappa;  // x0 = v0 + kappa * d
-  float Bs, Cs, a1;
-  float lam, alpha, beta, M;
-  float a0, inv_aa;  // two-block form: constraint a0 x0 + a1 x1 = 0, 1 / (a0^2 + a1^2)
-  const float* alpha_v;  // per-column alpha / beta of the scaled zone (nullptr: the uniform values)
-  const float* beta_v;
-};
-
-// One column of the TWO-BLOCK driver's sweep (reference algorithms/prox_admm_two_block.cc:97-112):
-//   zu = z - u ;  x0 = prox_0(zu)_0 = v0 + kappa d ;  x1 = prox_1(zu)_1 (scaled zone) ;
-//   z = projection of x + u onto {a0 z0 + a1 z1 = 0} ;  u += x - z.
-// Returns the next sweep's prox-0 input z0' - u0'.
-__device__ inline float ChainTwoBlock(float d, const FusedScalars& c, float z0p, float z1p, float u0p,
-                                      float u1p, float* x0o, float* x1o, float* z0o, float* z1o,
-                                      float* u0o, float* u1o);
-
-// The two-block driver's column (see ChainTwoBlock below for the line-by-line correspondence).
-template <class T>
-__device__ inline T ChainTwoBlockT(T d, const FusedScalarsT<T>& c, T z0p, T z1p, T u0p, T u1p, T* x0o,
-                                   T* x1o, T* z0o, T* z1o, T* u0o, T* u1o) {
-  const T v0 = z0p - u0p;
-  const T v1 = z1p - u1p;
-  const T x0 = c.kappa * d + v0;
-  const T x1 = c.Cs * ScaledZoneOneT<T>(c.Bs * v1, c.lam, c.alpha, c.beta, c.M);
-  const T w0 = x0 + u0p;
-  const T w1 = x1 + u1p;
-  const T t = (c.a0 * w0 + c.a1 * w1) * c.inv_aa;
-  const T z0 = w0 - c.a0 * t;
-  const T z1 = w1 - c.a1 * t;
-  const T u0 = u0p + (x0 - z0);
-  const T u1 = u1p + (x1 - z1);
-  *x0o = x0;
-  *x1o = x1;
-  *z0o = z0;
-  *z1o = z1;
-  *u0o = u0;
-  *u1o = u1;
-  return z0 - u0;
-}
-
-// f64 pass: 16-byte loads hold two rows, so 512 threads x 10 chunks own up to 10240 rows.
-// MODE 0 / 1 as in the f32 kernel below: the multi-block driver's chain, the two-block driver's.
-template <int NR, int BS, int MODE>
-__global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelF64(
-    int64_t m, int64_t n, const double* __restrict__ A, int64_t lda, const double* __restrict__ w,
-    FusedScalarsT<double> c, double* u, double* x0, double* x1, double* y0, double* y1,
-    double* y1prev, double* __restrict__ tpart, unsigned* epoch, double* e0, double* e1) {
-  __shared__ double red[2][BS / 64];
-  // the exchange kernels behind this pass tag their granules with the sweep number
-  if (epoch != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *epoch += 1u;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  double2 wv[NR], tp[NR];
-  int64_t row[NR];
-#pragma unroll
-  for (int q = 0; q < NR; ++q) {
-    row[q] = (static_cast<int64_t>(q) * BS + tid) * 2;
-    wv[q] = row[q] < m ? *reinterpret_cast<const double2*>(w + row[q]) : make_double2(0, 0);
-    tp[q] = make_double2(0, 0);
-  }
-  const int64_t npairs = (n + 1) / 2;
-  auto column = [&](int64_t step) -> int64_t {
-    const int64_t jp = blockIdx.x + (step >> 1) * gridDim.x;
-    const int64_t j = 2 * jp + (step & 1);
-    return (jp < npairs && j < n) ? j : -1;
-  };
-  auto load = [&](double2 (&a)[NR], int64_t j) {
-    const double* cp = A + j * lda;
-#pragma unroll
-    for (int q = 0; q < NR; ++q) {
-      if (row[q] < m) {
-        typedef double v2d __attribute__((ext_vector_type(2)));
-        const v2d v = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(cp + row[q]));
-        a[q] = make_double2(v.x, v.y);
-      } else {
-        a[q] = make_double2(0, 0);
-      }
-    }
-  };
-  double2 cur[NR], nxt[NR];
-  int64_t step = 0;
-  int64_t j = column(0);
-  if (j >= 0) load(cur, j);
-  int par = 0;
-  while (j >= 0) {
-    int64_t jn = column(step + 1);
-    if (jn < 0 && ((step + 1) & 1)) jn = column(step + 2);
-    const int64_t step_n = (jn >= 0 && column(step + 1) < 0) ? step + 2 : step + 1;
-    if (jn >= 0) load(nxt, jn);
-    const double uj = u[j], y0j = y0[j], y1j = y1[j];
-    double u1j = 0.0;
-    if (MODE == 1) u1j = e0[j];
-    double d = 0.0;
-#pragma unroll
-    for (int q = 0; q < NR; ++q) {
-      d += cur[q].x * wv[q].x;
-      d += cur[q].y * wv[q].y;
-    }
-    d = WaveSumT<double>(d);
-    if (lane == 0) red[par][wave] = d;
-    __syncthreads();
-    d = red[par][0];
-#pragma unroll
-    for (int w2 = 1; w2 < BS / 64; ++w2) d += red[par][w2];
-    par ^= 1;
-    FusedScalarsT<double> cj = c;
-    if (c.alpha_v != nullptr) cj.alpha = c.alpha_v[j];
-    if (c.beta_v != nullptr) cj.beta = c.beta_v[j];
-    double v0n;
-    if (MODE == 0) {
-      double nx0, nx1, ny0, ny1, nu;
-      v0n = ChainOneT<double>(d, cj, uj, y0j, y1j, &nx0, &nx1, &ny0, &ny1, &nu);
-      if (tid == 0) {
-        y1prev[j] = y1j;
-        x0[j] = nx0;
-        x1[j] = nx1;
-        y0[j] = ny0;
-        y1[j] = ny1;
-        u[j] = nu;
-      }
-    } else {
-      double nx0, nx1, nz0, nz1, nu0, nu1;
-      v0n = ChainTwoBlockT<double>(d, cj, y0j, y1j, uj, u1j, &nx0, &nx1, &nz0, &nz1, &nu0, &nu1);
-      if (tid == 0) {
-        y1prev[j] = y0j;  // z_prev
-        e1[j] = y1j;
-        x0[j] = nx0;
-        x1[j] = nx1;
-        y0[j] = nz0;
-        y1[j] = nz1;
-        u[j] = nu0;
-        e0[j] = nu1;
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < NR; ++q) {
-      tp[q].x += cur[q].x * v0n;
-      tp[q].y += cur[q].y * v0n;
-    }
-#pragma unroll
-    for (int q = 0; q < NR; ++q) cur[q] = nxt[q];
-    j = jn;
-    step = step_n;
-  }
-  double* out = tpart + static_cast<int64_t>(blockIdx.x) * m;
-#pragma unroll
-  for (int q = 0; q < NR; ++q)
-    if (row[q] < m) *reinterpret_cast<double2*>(out + row[q]) = tp[q];
-}
-
-// One column's elementwise chain.  Returns v0' (input of the next sweep's forward pass).
-__device__ inline float ChainOne(float d, const FusedScalars& c, float u, float y0p, float y1p,
-                                 float* x0o, float* x1o, float* y0o, float* y1o, float* uo) {
-  // sweep start: u -= y0; u -= y1; then term 0: u += y0       (prox_admm.cc:137-142)
-  float v0 = ((u - y0p) - y1p) + y0p;
-  float x0 = c.kappa * d + v0;        // back substitution epilogue: alpha*acc + 1*y
-  float y0 = x0;                       // y_0 = A_ x_0 with A_(c0,x) = I
-  float u1 = v0 - y0;                  // u -= y_0
-  float u2 = u1 + y1p;                 // term 1: u += y_1
-  float vin = c.Bs * u2;               // VectorProx: B v (+ g = 0)      (vector_prox.cc:141)
-  float xz = ScaledZoneOne(vin, c.lam, c.alpha, c.beta, c.M);
-  float x1 = c.Cs * xz;                // C (x - g)                       (vector_prox.cc:145)
-  float y1 = c.a1 * x1;                // y_1 = A_ x_1
-  float u3 = u2 - y1;                  // u -= y_1
-  *x0o = x0;
-  *x1o = x1;
-  *y0o = y0;
-  *y1o = y1;
-  *uo = u3;
-  // next sweep's prox-0 input
-  return ((u3 - y0) - y1) + y0;
-}
-
-__device__ inline float ChainTwoBlock(float d, const FusedScalars& c, float z0p, float z1p, float u0p,
-                                      float u1p, float* x0o, float* x1o, float* z0o, float* z1o,
-                                      float* u0o, float* u1o) {
-  const float v0 = z0p - u0p;
-  const float v1 = z1p - u1p;
-  const float x0 = c.kappa * d + v0;
-  const float x1 = c.Cs * ScaledZoneOne(c.Bs * v1, c.lam, c.alpha, c.beta, c.M);
-  const float w0 = x0 + u0p;
-  const float w1 = x1 + u1p;
-  const float t = (c.a0 * w0 + c.a1 * w1) * c.inv_aa;
-  const float z0 = w0 - c.a0 * t;
-  const float z1 = w1 - c.a1 * t;
-  const float u0 = u0p + (x0 - z0);
-  const float u1 = u1p + (x1 - z1);
-  *x0o = x0;
-  *x1o = x1;
-  *z0o = z0;
-  *z1o = z1;
-  *u0o = u0;
-  *u1o = u1;
-  return z0 - u0;
-}
-
-template <int NR>
-__global__ __launch_bounds__(kBlock, 2) void LassoFusedKernel(
-    int64_t m, int64_t n, const float* __restrict__ A, int64_t lda, const float* __restrict__ w,
-    FusedScalars c, float* u, float* x0, float* x1, float* y0, float* y1, float* y1prev,
-    float* __restrict__ tpart, unsigned* epoch) {
-  __shared__ float red[2][kBlock / 64][2];
-  if (epoch != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *epoch += 1u;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  float4 wv[NR], tp[NR];
-  int64_t row[NR];
-#pragma unroll
-  for (int q = 0; q < NR; ++q) {
-    row[q] = (static_cast<int64_t>(q) * kBlock + tid) * 4;
-    wv[q] = row[q] < m ? *reinterpret_cast<const float4*>(w + row[q]) : make_float4(0, 0, 0, 0);
-    tp[q] = make_float4(0, 0, 0, 0);
-  }
-  const int64_t npairs = (n + 1) / 2;
-  int par = 0;
-  for (int64_t jp = blockIdx.x; jp < npairs; jp += gridDim.x, par ^= 1) {
-    const int64_t j = 2 * jp;
-    const bool has2 = j + 1 < n;
-    const float* c0p = A + j * lda;
-    const float* c1p = c0p + lda;
-    float4 a0[NR], a1[NR];
-#pragma unroll
-    for (int q = 0; q < NR; ++q)
-      a0[q] = row[q] < m ? *reinterpret_cast<const float4*>(c0p + row[q]) : make_float4(0, 0, 0, 0);
-#pragma unroll
-    for (int q = 0; q < NR; ++q)
-      a1[q] = (has2 && row[q] < m) ? *reinterpret_cast<const float4*>(c1p + row[q])
-                                   : make_float4(0, 0, 0, 0);
-    // per-column state (same address in every lane: broadcast loads)
-    const float uj0 = u[j], y0j0 = y0[j], y1j0 = y1[j];
-    const int64_t j1 = has2 ? j + 1 : j;
-    const float uj1 = u[j1], y0j1 = y0[j1], y1j1 = y1[j1];
-
-    float d0 = 0.0f, d1 = 0.0f;
-#pragma unroll
-    for (int q = 0; q < NR; ++q) {
-      d0 += a0[q].x * wv[q].x;
-      d0 += a0[q].y * wv[q].y;
-      d0 += a0[q].z * wv[q].z;
-      d0 += a0[q].w * wv[q].w;
-      d1 += a1[q].x * wv[q].x;
-      d1 += a1[q].y * wv[q].y;
-      d1 += a1[q].z * wv[q].z;
-      d1 += a1[q].w * wv[q].w;
-    }
-    d0 = WaveSumF(d0);
-    d1 = WaveSumF(d1);
-    if (lane == 0) {
-      red[par][wave][0] = d0;
-      red[par][wave][1] = d1;
-    }
-    __syncthreads();
-    d0 = ((red[par][0][0] + red[par][1][0]) + red[par][2][0]) + red[par][3][0];
-    d1 = ((red[par][0][1] + red[par][1][1]) + red[par][2][1]) + red[par][3][1];
-
-    float nx0, nx1, ny0, ny1, nu;
-    const float v0n0 = ChainOne(d0, c, uj0, y0j0, y1j0, &nx0, &nx1, &ny0, &ny1, &nu);
-    if (tid == 0) {
-      y1prev[j] = y1j0;
-      x0[j] = nx0;
-      x1[j] = nx1;
-      y0[j] = ny0;
-      y1[j] = ny1;
-      u[j] = nu;
-    }
-    float v0n1 = 0.0f;
-    if (has2) {
-      v0n1 = ChainOne(d1, c, uj1, y0j1, y1j1, &nx0, &nx1, &ny0, &ny1, &nu);
-      if (tid == 0) {
-        y1prev[j + 1] = y1j1;
-        x0[j + 1] = nx0;
-        x1[j + 1] = nx1;
-        y0[j + 1] = ny0;
-        y1[j + 1] = ny1;
-        u[j + 1] = nu;
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < NR; ++q) {
-      tp[q].x += a0[q].x * v0n0;
-      tp[q].y += a0[q].y * v0n0;
-      tp[q].z += a0[q].z * v0n0;
-      tp[q].w += a0[q].w * v0n0;
-      tp[q].x += a1[q].x * v0n1;
-      tp[q].y += a1[q].y * v0n1;
-      tp[q].z += a1[q].z * v0n1;
-      tp[q].w += a1[q].w * v0n1;
-    }
-  }
-  float* out = tpart + static_cast<int64_t>(blockIdx.x) * m;
-#pragma unroll
-  for (int q = 0; q < NR; ++q)
-    if (row[q] < m) *reinterpret_cast<float4*>(out + row[q]) = tp[q];
-}
-
-// Streaming variant: ONE column per step, the next column already in flight.  The pair kernel
-// above issues 2*NR loads, waits for all of them and has nothing in flight while it reduces,
-// synchronises and runs the chain; here the loads of column j+1 are issued before the dot
-// product of column j is reduced, so every workgroup keeps NR 16-byte loads per lane outstanding
-// at all times.  Same arithmetic per column, bit-identical state.
-// BS threads own the m rows: 256 (two workgroups per CU) up to m = 10240; 512 (one workgroup of 8
-// waves per CU) up to m = 20480 (6.37 TB/s on 2e4 x 5e4).
-// MODE 0: the multi-block driver's chain (ChainOne).  MODE 1: the two-block driver's (ChainTwoBlock);
+// ONE column per step, the next column already in flight: the loads of column j+1 are issued
+// before the dot product of column j is reduced, so every workgroup keeps NR 16-byte loads per
+// lane outstanding at all times (6.0 TB/s on the 1e4 x 5e4 matrix, against 5.75 for a form that
+// took columns in pairs with nothing in flight while it reduced).
+// BS threads own the m rows: 256 (two workgroups per CU) up to m = 10240 in f32; 512 (one
+// workgroup of 8 waves per CU) up to m = 20480 (6.37 TB/s on 2e4 x 5e4).  In f64 a 16-byte load
+// holds two rows, so 512 threads x 10 chunks own up to 10240 rows.
+// MODE 0: the multi-block driver's chain (ChainOneT).  MODE 1: the two-block driver's (ChainTwoBlockT);
 // the state arrays then mean u -> u0, y0 -> z0, y1 -> z1, y1prev -> z0_prev, e0 -> u1, e1 -> z1_prev.
-template <int NR, int BS, int MODE>
-__global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernel(
-    int64_t m, int64_t n, const float* __restrict__ A, int64_t lda, const float* __restrict__ w,
-    FusedScalars c, float* u, float* x0, float* x1, float* y0, float* y1, float* y1prev,
-    float* __restrict__ tpart, unsigned* epoch, float* e0, float* e1) {
-  constexpr int kBlock = BS;  // (shadows the file-level constant inside this kernel)
-  __shared__ float red[2][kBlock / 64];
+template <class T, int NR, int BS, int MODE>
+__global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
+    int64_t m, int64_t n, const T* __restrict__ A, int64_t lda, const T* __restrict__ w,
+    FusedScalarsT<T> c, T* u, T* x0, T* x1, T* y0, T* y1, T* y1prev, T* __restrict__ tpart,
+    unsigned* epoch, T* e0, T* e1) {
+  typedef typename Chunk<T>::V V;
+  constexpr int R = Chunk<T>::R;
+  __shared__ T red[2][BS / 64];
   // sweep counter of the peer exchange (kernels_peer.hip): the two exchange kernels that follow
   // this pass in stream order tag their granules with it
   if (epoch != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *epoch += 1u;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  float4 wv[NR], tp[NR];
+  // (a constant, not a vector filled element by element: with the latter the compiler turns the
+  // guarded loads below into selects and drops their non-temporal hint)
+  const V zero = T(0);
+  V wv[NR], tp[NR];
   int64_t row[NR];
 #pragma unroll
   for (int q = 0; q < NR; ++q) {
-    row[q] = (static_cast<int64_t>(q) * kBlock + tid) * 4;
-    wv[q] = row[q] < m ? *reinterpret_cast<const float4*>(w + row[q]) : make_float4(0, 0, 0, 0);
-    tp[q] = make_float4(0, 0, 0, 0);
+    row[q] = (static_cast<int64_t>(q) * BS + tid) * R;
+    wv[q] = row[q] < m ? *reinterpret_cast<const V*>(w + row[q]) : zero;
+    tp[q] = zero;
   }
-  // this workgroup's columns: the same pairs the pair kernel would take, one column at a time
+  // this workgroup's columns: pairs (2 jp, 2 jp + 1), jp = blockIdx.x + k gridDim.x, one column
+  // at a time
   const int64_t npairs = (n + 1) / 2;
   auto column = [&](int64_t step) -> int64_t {  // step -> column index, or -1 past the end
     const int64_t jp = blockIdx.x + (step >> 1) * gridDim.x;
@@ -383,25 +78,15 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernel(
   };
   // The matrix is read once per sweep with no reuse: non-temporal loads keep it from evicting
   // the cached inverse (K3 operand, 200 MB of tiles) from the 256 MB Infinity Cache.
-  static const bool kNT = true;
-  auto load = [&](float4 (&a)[NR], int64_t j) {
-    const float* cp = A + j * lda;
+  auto load = [&](V (&a)[NR], int64_t j) {
+    const T* cp = A + j * lda;
 #pragma unroll
     for (int q = 0; q < NR; ++q) {
-      if (row[q] < m) {
-        typedef float v4f __attribute__((ext_vector_type(4)));
-        if (kNT) {
-          const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(cp + row[q]));
-          a[q] = make_float4(v.x, v.y, v.z, v.w);
-        } else {
-          a[q] = *reinterpret_cast<const float4*>(cp + row[q]);
-        }
-      } else {
-        a[q] = make_float4(0, 0, 0, 0);
-      }
+      if (row[q] < m) a[q] = __builtin_nontemporal_load(reinterpret_cast<const V*>(cp + row[q]));
+      else a[q] = zero;
     }
   };
-  float4 cur[NR], nxt[NR];
+  V cur[NR], nxt[NR];
   int64_t step = 0;
   int64_t j = column(0);
   if (j >= 0) load(cur, j);
@@ -412,31 +97,29 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernel(
     if (jn < 0 && ((step + 1) & 1)) jn = column(step + 2);
     const int64_t step_n = (jn >= 0 && column(step + 1) < 0) ? step + 2 : step + 1;
     if (jn >= 0) load(nxt, jn);
-    const float uj = u[j], y0j = y0[j], y1j = y1[j];
-    float u1j = 0.0f;
+    // per-column state (same address in every lane: broadcast loads)
+    const T uj = u[j], y0j = y0[j], y1j = y1[j];
+    T u1j = T(0);
     if (MODE == 1) u1j = e0[j];
-    float d = 0.0f;
+    T d = T(0);
 #pragma unroll
-    for (int q = 0; q < NR; ++q) {
-      d += cur[q].x * wv[q].x;
-      d += cur[q].y * wv[q].y;
-      d += cur[q].z * wv[q].z;
-      d += cur[q].w * wv[q].w;
-    }
-    d = WaveSumF(d);
+    for (int q = 0; q < NR; ++q)
+#pragma unroll
+      for (int r = 0; r < R; ++r) d += cur[q][r] * wv[q][r];
+    d = WaveSumT<T>(d);
     if (lane == 0) red[par][wave] = d;
     __syncthreads();
-    d = ((red[par][0] + red[par][1]) + red[par][2]) + red[par][3];
+    d = red[par][0];
 #pragma unroll
-    for (int wv2 = 4; wv2 < kBlock / 64; ++wv2) d += red[par][wv2];
+    for (int w2 = 1; w2 < BS / 64; ++w2) d += red[par][w2];
     par ^= 1;
-    FusedScalars cj = c;
+    FusedScalarsT<T> cj = c;
     if (c.alpha_v != nullptr) cj.alpha = c.alpha_v[j];
     if (c.beta_v != nullptr) cj.beta = c.beta_v[j];
-    float v0n;
+    T v0n;
     if (MODE == 0) {
-      float nx0, nx1, ny0, ny1, nu;
-      v0n = ChainOne(d, cj, uj, y0j, y1j, &nx0, &nx1, &ny0, &ny1, &nu);
+      T nx0, nx1, ny0, ny1, nu;
+      v0n = ChainOneT<T>(d, cj, uj, y0j, y1j, &nx0, &nx1, &ny0, &ny1, &nu);
       if (tid == 0) {
         y1prev[j] = y1j;
         x0[j] = nx0;
@@ -446,8 +129,8 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernel(
         u[j] = nu;
       }
     } else {
-      float nx0, nx1, nz0, nz1, nu0, nu1;
-      v0n = ChainTwoBlock(d, cj, y0j, y1j, uj, u1j, &nx0, &nx1, &nz0, &nz1, &nu0, &nu1);
+      T nx0, nx1, nz0, nz1, nu0, nu1;
+      v0n = ChainTwoBlockT<T>(d, cj, y0j, y1j, uj, u1j, &nx0, &nx1, &nz0, &nz1, &nu0, &nu1);
       if (tid == 0) {
         y1prev[j] = y0j;  // z_prev
         e1[j] = y1j;
@@ -460,46 +143,51 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernel(
       }
     }
 #pragma unroll
-    for (int q = 0; q < NR; ++q) {
-      tp[q].x += cur[q].x * v0n;
-      tp[q].y += cur[q].y * v0n;
-      tp[q].z += cur[q].z * v0n;
-      tp[q].w += cur[q].w * v0n;
-    }
+    for (int q = 0; q < NR; ++q)
+#pragma unroll
+      for (int r = 0; r < R; ++r) tp[q][r] += cur[q][r] * v0n;
 #pragma unroll
     for (int q = 0; q < NR; ++q) cur[q] = nxt[q];
     j = jn;
     step = step_n;
   }
-  float* out = tpart + static_cast<int64_t>(blockIdx.x) * m;
+  T* out = tpart + static_cast<int64_t>(blockIdx.x) * m;
 #pragma unroll
   for (int q = 0; q < NR; ++q)
-    if (row[q] < m) *reinterpret_cast<float4*>(out + row[q]) = tp[q];
+    if (row[q] < m) *reinterpret_cast<V*>(out + row[q]) = tp[q];
 }
 
-template <int NR, int BS>
-void LaunchFused(int grid, int64_t m, int64_t n, const float* A, int64_t lda, const float* w,
-                 const FusedScalars& c, float* u, float* x0, float* x1, float* y0, float* y1,
-                 float* y1prev, float* tpart, unsigned* epoch, int chain, float* e0, float* e1) {
-  if (chain == 1) {
-    hipLaunchKernelGGL((LassoFusedStreamKernel<NR, BS, 1>), dim3(grid), dim3(BS), 0,
-                       Runtime::Get().stream(), m, n, A, lda, w, c, u, x0, x1, y0, y1, y1prev, tpart,
-                       epoch, e0, e1);
+template <class T, int NR, int BS>
+void LaunchFused(const LassoFusedArgs& a, int grid) {
+  const LassoBatchInst<T> i = Narrow<T>(a.inst);
+  T* e0 = a.chain == 1 ? a.e0.as<T>() : nullptr;
+  T* e1 = a.chain == 1 ? a.e1.as<T>() : nullptr;
+  hipLaunchKernelGGL(
+      (a.chain == 1 ? LassoFusedStreamKernelT<T, NR, BS, 1> : LassoFusedStreamKernelT<T, NR, BS, 0>),
+      dim3(grid), dim3(BS), 0, Runtime::Get().stream(), a.m, a.n, a.A.as<T>(), a.lda, i.w,
+      ScalarsOf<T>(i, a.a0, a.inst.a1), i.u, i.x0, i.x1, i.y0, i.y1, i.y1prev, i.tpart, a.epoch, e0, e1);
+}
+
+// The instantiation for (type, threads, 16-byte row chunks a thread needs).  512 threads: the
+// f32 pass also has the 2 and 5 chunk forms (EPSILON_HIP_FUSED_BLOCK=512 below 10240 rows; 5
+// still fits two workgroups per CU), the f64 pass takes 512 threads only above 5120 rows.
+template <class T>
+void LaunchFusedT(const LassoFusedArgs& a, int grid, int block) {
+  const int64_t need = (a.m + Chunk<T>::R * block - 1) / (Chunk<T>::R * block);
+  if (block == 256) {
+    if (need <= 1) LaunchFused<T, 1, 256>(a, grid);
+    else if (need <= 2) LaunchFused<T, 2, 256>(a, grid);
+    else if (need <= 4) LaunchFused<T, 4, 256>(a, grid);
+    else if (need <= 8) LaunchFused<T, 8, 256>(a, grid);
+    else LaunchFused<T, 10, 256>(a, grid);
     return;
   }
-  // default: the streaming kernel (6.0 vs 5.75 TB/s on the 1e4 x 5e4 matrix); "pair" selects the
-  // two-column form (256-thread workgroups only)
-  static const char* env = std::getenv("EPSILON_HIP_FUSED_KERNEL");
-  const bool stream = !(env && env[0] == 'p') || BS != 256 || c.alpha_v != nullptr || c.beta_v != nullptr;
-  if (stream) {
-    hipLaunchKernelGGL((LassoFusedStreamKernel<NR, BS, 0>), dim3(grid), dim3(BS), 0,
-                       Runtime::Get().stream(), m, n, A, lda, w, c, u, x0, x1, y0, y1, y1prev,
-                       tpart, epoch, e0, e1);
-    return;
+  if constexpr (std::is_same<T, float>::value) {
+    if (need <= 2) return LaunchFused<T, 2, 512>(a, grid);
+    if (need <= 5) return LaunchFused<T, 5, 512>(a, grid);
   }
-  if constexpr (BS == 256)
-    hipLaunchKernelGGL(LassoFusedKernel<NR>, dim3(grid), dim3(kBlock), 0, Runtime::Get().stream(), m,
-                       n, A, lda, w, c, u, x0, x1, y0, y1, y1prev, tpart, epoch);
+  if (need <= 8) LaunchFused<T, 8, 512>(a, grid);
+  else LaunchFused<T, 10, 512>(a, grid);
 }
 
 }  // namespace
@@ -514,12 +202,6 @@ namespace {
 // one agent-scope ticket per workgroup; the last arriver reads with sc1 loads - MI355X_MICROARCH.md,
 // Valid forms, first row.)
 constexpr int kNormBlocks = 64;
-
-__device__ inline double WaveSumD(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
 
 template <class T>
 __global__ __launch_bounds__(kBlock) void LassoFusedNormsKernel(
@@ -544,7 +226,7 @@ __global__ __launch_bounds__(kBlock) void LassoFusedNormsKernel(
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
-    const double t = WaveSumD(s[k]);
+    const double t = WaveSumT<double>(s[k]);
     if (lane == 0) red[wave][k] = t;
   }
   __syncthreads();
@@ -640,109 +322,25 @@ int LassoFusedGrid(int64_t m, int64_t n, DType dt) {
   return static_cast<int>(g < 1 ? 1 : g);
 }
 
-namespace {
-void LassoFusedPassF64(const LassoFusedArgs& a, int grid, int block) {
-  FusedScalarsT<double> c{a.kappa, a.Bs, a.Cs, a.a1, a.lam, a.sz_alpha, a.sz_beta, a.sz_M,
-                          a.a0, 1.0 / (a.a0 * a.a0 + a.a1 * a.a1), nullptr, nullptr};
-  if (a.sz_alpha_vec.n > 0) {
-    EPS_CHECK(a.sz_alpha_vec.n == a.n && a.sz_alpha_vec.dt == F64);
-    c.alpha_v = a.sz_alpha_vec.as<double>();
-  }
-  if (a.sz_beta_vec.n > 0) {
-    EPS_CHECK(a.sz_beta_vec.n == a.n && a.sz_beta_vec.dt == F64);
-    c.beta_v = a.sz_beta_vec.as<double>();
-  }
-  if (a.chain == 1) EPS_CHECK(a.e0.n == a.n && a.e1.n == a.n && a.e0.dt == F64 && a.e1.dt == F64);
-  double* e0 = a.chain == 1 ? a.e0.as<double>() : nullptr;
-  double* e1 = a.chain == 1 ? a.e1.as<double>() : nullptr;
-  ProfScope prof("lasso_fused", a.m, a.n);
-  const int64_t need = (a.m + 2 * block - 1) / (2 * block);  // double2 row chunks per thread
-  hipStream_t s = Runtime::Get().stream();
-#define EPS_FUSED_CASE64(NRV, BSV)                                                                        \
-  do {                                                                                                    \
-    if (a.chain == 1)                                                                                     \
-      hipLaunchKernelGGL((LassoFusedStreamKernelF64<NRV, BSV, 1>), dim3(grid), dim3(BSV), 0, s, a.m, a.n, \
-                         a.A.as<double>(), a.lda, a.w.as<double>(), c, a.u.as<double>(),                  \
-                         a.x0.as<double>(), a.x1.as<double>(), a.y0.as<double>(), a.y1.as<double>(),      \
-                         a.y1prev.as<double>(), a.tpart.as<double>(), a.epoch, e0, e1);                   \
-    else                                                                                                  \
-      hipLaunchKernelGGL((LassoFusedStreamKernelF64<NRV, BSV, 0>), dim3(grid), dim3(BSV), 0, s, a.m, a.n, \
-                         a.A.as<double>(), a.lda, a.w.as<double>(), c, a.u.as<double>(),                  \
-                         a.x0.as<double>(), a.x1.as<double>(), a.y0.as<double>(), a.y1.as<double>(),      \
-                         a.y1prev.as<double>(), a.tpart.as<double>(), a.epoch, e0, e1);                   \
-  } while (0)
-  if (block == 256) {
-    if (need <= 1) EPS_FUSED_CASE64(1, 256);
-    else if (need <= 2) EPS_FUSED_CASE64(2, 256);
-    else if (need <= 4) EPS_FUSED_CASE64(4, 256);
-    else if (need <= 8) EPS_FUSED_CASE64(8, 256);
-    else EPS_FUSED_CASE64(10, 256);
-  } else {
-    if (need <= 8) EPS_FUSED_CASE64(8, 512);
-    else EPS_FUSED_CASE64(10, 512);
-  }
-#undef EPS_FUSED_CASE64
-  EPS_HIP(hipGetLastError());
-}
-}  // namespace
-
 void LassoFusedPass(const LassoFusedArgs& a) {
   EPS_CHECK(LassoFusedSupported(a.m, a.n, a.A, a.lda));
   const DType dt = a.A.dt;
-  EPS_CHECK(a.w.n == a.m && a.w.dt == dt);
-  for (const DVec* v : {&a.u, &a.x0, &a.x1, &a.y0, &a.y1, &a.y1prev})
+  const LassoInstance& s = a.inst;
+  EPS_CHECK(s.w.n == a.m && s.w.dt == dt);
+  for (const DVec* v : {&s.u, &s.x0, &s.x1, &s.y0, &s.y1, &s.y1prev})
     EPS_CHECK(v->n == a.n && v->dt == dt);
+  for (const DVec* v : {&s.alpha_vec, &s.beta_vec})
+    if (v->n > 0) EPS_CHECK(v->n == a.n && v->dt == dt);
+  if (a.chain == 1) EPS_CHECK(a.e0.n == a.n && a.e1.n == a.n && a.e0.dt == dt && a.e1.dt == dt);
   const int grid = LassoFusedGrid(a.m, a.n, dt);
   const int block = LassoFusedBlock(a.m, a.n, dt);
-  EPS_CHECK(a.tpart.n >= static_cast<int64_t>(grid) * a.m && a.tpart.dt == dt);
-  if (dt == F64) {
-    LassoFusedPassF64(a, grid, block);
-    return;
-  }
-  EPS_CHECK(reinterpret_cast<uintptr_t>(a.w.data()) % 16 == 0 &&
-            reinterpret_cast<uintptr_t>(a.tpart.data()) % 16 == 0);
-  FusedScalars c;
-  c.kappa = static_cast<float>(a.kappa);
-  c.Bs = static_cast<float>(a.Bs);
-  c.Cs = static_cast<float>(a.Cs);
-  c.a1 = static_cast<float>(a.a1);
-  c.lam = static_cast<float>(a.lam);
-  c.alpha = static_cast<float>(a.sz_alpha);
-  c.beta = static_cast<float>(a.sz_beta);
-  c.M = static_cast<float>(a.sz_M);
-  c.a0 = static_cast<float>(a.a0);
-  c.inv_aa = static_cast<float>(1.0 / (a.a0 * a.a0 + a.a1 * a.a1));
-  c.alpha_v = c.beta_v = nullptr;
-  if (a.sz_alpha_vec.n > 0) {
-    EPS_CHECK(a.sz_alpha_vec.n == a.n && a.sz_alpha_vec.dt == F32);
-    c.alpha_v = a.sz_alpha_vec.as<float>();
-  }
-  if (a.sz_beta_vec.n > 0) {
-    EPS_CHECK(a.sz_beta_vec.n == a.n && a.sz_beta_vec.dt == F32);
-    c.beta_v = a.sz_beta_vec.as<float>();
-  }
-  // (the pair kernel has no per-column parameters: the streaming kernel is forced below)
-  if (a.chain == 1) EPS_CHECK(a.e0.n == a.n && a.e1.n == a.n && a.e0.dt == F32 && a.e1.dt == F32);
+  EPS_CHECK(s.tpart.n >= static_cast<int64_t>(grid) * a.m && s.tpart.dt == dt);
+  EPS_CHECK(reinterpret_cast<uintptr_t>(s.w.data()) % 16 == 0 &&
+            reinterpret_cast<uintptr_t>(s.tpart.data()) % 16 == 0);
   ProfScope prof("lasso_fused", a.m, a.n);
-  const int64_t need = (a.m + 4 * block - 1) / (4 * block);  // float4 row chunks per thread
-#define EPS_FUSED_CASE(NRV, BSV)                                                                      \
-  LaunchFused<NRV, BSV>(grid, a.m, a.n, a.A.as<float>(), a.lda, a.w.as<float>(), c, a.u.as<float>(), \
-                        a.x0.as<float>(), a.x1.as<float>(), a.y0.as<float>(), a.y1.as<float>(),      \
-                        a.y1prev.as<float>(), a.tpart.as<float>(), a.epoch, a.chain,         \
-                        a.chain == 1 ? a.e0.as<float>() : nullptr, a.chain == 1 ? a.e1.as<float>() : nullptr)
-  if (block == 256) {
-    if (need <= 1) EPS_FUSED_CASE(1, 256);
-    else if (need <= 2) EPS_FUSED_CASE(2, 256);
-    else if (need <= 4) EPS_FUSED_CASE(4, 256);
-    else if (need <= 8) EPS_FUSED_CASE(8, 256);
-    else EPS_FUSED_CASE(10, 256);
-  } else {
-    if (need <= 2) EPS_FUSED_CASE(2, 512);
-    else if (need <= 5) EPS_FUSED_CASE(5, 512);
-    else if (need <= 8) EPS_FUSED_CASE(8, 512);
-    else EPS_FUSED_CASE(10, 512);
-  }
-#undef EPS_FUSED_CASE
+  if (dt == F32) LaunchFusedT<float>(a, grid, block);
+  else LaunchFusedT<double>(a, grid, block);
+  EPS_HIP(hipGetLastError());
 }
 
 }  // namespace k

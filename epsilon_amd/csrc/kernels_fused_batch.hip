@@ -2,7 +2,7 @@
 // share the data matrix A (a regularisation path, cross-validation folds, several right-hand
 // sides) in ONE pass over A per sweep instead of K.
 //
-// Same geometry as LassoFusedStreamKernel (kernels_fused.hip) with 256 threads: thread t owns
+// Same geometry as LassoFusedStreamKernelT (kernels_fused.hip) with 256 threads: thread t owns
 // rows R(t + 256q), q < NR, of every column (R = 4 in f32, 2 in f64: one 16-byte load); the
 // workgroups take the same columns in the same order (LassoFusedGrid), the next column's loads
 // are in flight while the current one is reduced.  Each loaded column feeds KB instances: their
@@ -17,7 +17,6 @@
 // is - so every instance's iterates are bit-identical to its own solve.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <vector>
 
 #include "kernels.h"
@@ -29,16 +28,6 @@ namespace k {
 namespace {
 
 constexpr int kBlock = 256;
-
-template <class T> struct Chunk;  // one 16-byte load: R rows
-template <> struct Chunk<float> {
-  static constexpr int R = 4;
-  typedef float V __attribute__((ext_vector_type(4)));
-};
-template <> struct Chunk<double> {
-  static constexpr int R = 2;
-  typedef double V __attribute__((ext_vector_type(2)));
-};
 
 template <class T, int NR, int KB>
 __global__ __launch_bounds__(kBlock) void LassoBatchStreamKernel(int64_t m, int64_t n, const T* __restrict__ A,
@@ -64,7 +53,7 @@ __global__ __launch_bounds__(kBlock) void LassoBatchStreamKernel(int64_t m, int6
       tp[i][q] = zero;
     }
   }
-  // this workgroup's columns: exactly those of LassoFusedStreamKernel, in its order
+  // this workgroup's columns: exactly those of LassoFusedStreamKernelT, in its order
   const int64_t npairs = (n + 1) / 2;
   auto column = [&](int64_t step) -> int64_t {
     const int64_t jp = blockIdx.x + (step >> 1) * gridDim.x;
@@ -182,37 +171,10 @@ void LaunchBatchT(int nr, int grid, int64_t m, int64_t n, const T* A, int64_t ld
 }
 
 template <class T>
-LassoBatchInst<T> Narrow(const LassoBatchMember& s) {
-  LassoBatchInst<T> d;
-  d.w = s.w.as<T>();
-  d.tpart = s.tpart.as<T>();
-  d.u = s.u.as<T>();
-  d.x0 = s.x0.as<T>();
-  d.x1 = s.x1.as<T>();
-  d.y0 = s.y0.as<T>();
-  d.y1 = s.y1.as<T>();
-  d.y1prev = s.y1prev.as<T>();
-  d.alpha_v = s.alpha_vec.n > 0 ? s.alpha_vec.as<T>() : nullptr;
-  d.beta_v = s.beta_vec.n > 0 ? s.beta_vec.as<T>() : nullptr;
-  d.p = s.p.as<T>();
-  d.rhs = s.rhs.n > 0 ? s.rhs.as<T>() : nullptr;
-  d.kappa = static_cast<T>(s.kappa);
-  d.pkappa = static_cast<T>(s.pkappa);
-  d.Bs = static_cast<T>(s.Bs);
-  d.Cs = static_cast<T>(s.Cs);
-  d.a1 = static_cast<T>(s.a1);
-  d.lam = static_cast<T>(s.lam);
-  d.alpha = static_cast<T>(s.alpha);
-  d.beta = static_cast<T>(s.beta);
-  d.M = static_cast<T>(s.M);
-  return d;
-}
-
-template <class T>
-void UploadT(const std::vector<const LassoBatchMember*>& members, DVec* table) {
+void UploadT(const std::vector<const LassoInstance*>& members, DVec* table) {
   std::vector<LassoBatchInst<T>> host;
   host.reserve(members.size());
-  for (const LassoBatchMember* s : members) host.push_back(Narrow<T>(*s));
+  for (const LassoInstance* s : members) host.push_back(Narrow<T>(*s));
   const size_t bytes = host.size() * sizeof(LassoBatchInst<T>);
   const int64_t words = static_cast<int64_t>((bytes + 7) / 8);
   if (table->n < words || table->dt != F64) *table = DVec::Empty(words < 1 ? 1 : words, F64);
@@ -226,14 +188,11 @@ void UploadT(const std::vector<const LassoBatchMember*>& members, DVec* table) {
 
 int LassoBatchWidth(int64_t m, int64_t n, DType dt) {
   if (LassoFusedBlock(m, n, dt) != kBlock) return 0;
-  // the single f32 pass may be switched to its two-column form, which the batch does not mirror
-  static const char* env = std::getenv("EPSILON_HIP_FUSED_KERNEL");
-  if (dt == F32 && env && env[0] == 'p') return 0;
   return WidthFor(ChunksPerThread(m, dt));
 }
 
-void LassoBatchUpload(const std::vector<const LassoBatchMember*>& members, DType dt, DVec* table) {
-  for (const LassoBatchMember* s : members)
+void LassoBatchUpload(const std::vector<const LassoInstance*>& members, DType dt, DVec* table) {
+  for (const LassoInstance* s : members)
     for (const DVec* v : {&s->w, &s->tpart, &s->u, &s->x0, &s->x1, &s->y0, &s->y1, &s->y1prev, &s->p})
       EPS_CHECK(v->dt == dt && v->n > 0);
   if (dt == F32) UploadT<float>(members, table);

@@ -1,22 +1,69 @@
 // Per-column arithmetic of the fused lasso sweep shared by the single pass (kernels_fused.hip)
-// and the batched pass (kernels_fused_batch.hip): both files are compiled with -ffp-contract=off,
-// so the same expressions give the same bits in either.
+// and the batched passes (kernels_fused_batch.hip, kernels_fused_wide.hip): these files are
+// compiled with -ffp-contract=off, so the same expressions give the same bits in each.
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include "kernels.h"
 
 namespace eps {
 namespace k {
 namespace {
 
+template <class T> struct Chunk;  // one 16-byte load: R rows
+template <> struct Chunk<float> {
+  static constexpr int R = 4;
+  typedef float V __attribute__((ext_vector_type(4)));
+};
+template <> struct Chunk<double> {
+  static constexpr int R = 2;
+  typedef double V __attribute__((ext_vector_type(2)));
+};
+
 // ---- the same pass in either precision (the f64 form serves the fp64 mode: the reference's own
 // arithmetic type, linear/linear_map.h:35) ---------------------------------------------------------
 template <class T> struct FusedScalarsT {
-  T kappa, Bs, Cs, a1, lam, alpha, beta, M;
+  T kappa;  // x0 = v0 + kappa * d
+  T Bs, Cs, a1, lam, alpha, beta, M;
   T a0, inv_aa;        // two-block form: constraint a0 x0 + a1 x1 = 0, 1 / (a0^2 + a1^2)
   const T* alpha_v;    // per-column alpha / beta of the scaled zone (nullptr: the uniform values)
   const T* beta_v;
 };
+
+// One instance in the compute type T, as the kernels read it: the only place where the host's
+// record (scalars as double) is narrowed.  The single pass takes its scalars from it
+// (ScalarsOf), the batched passes upload it as it is.
+template <class T> LassoBatchInst<T> Narrow(const LassoInstance& s) {
+  LassoBatchInst<T> d;
+  d.w = s.w.as<T>();
+  d.tpart = s.tpart.as<T>();
+  d.u = s.u.as<T>();
+  d.x0 = s.x0.as<T>();
+  d.x1 = s.x1.as<T>();
+  d.y0 = s.y0.as<T>();
+  d.y1 = s.y1.as<T>();
+  d.y1prev = s.y1prev.as<T>();
+  d.alpha_v = s.alpha_vec.n > 0 ? s.alpha_vec.as<T>() : nullptr;
+  d.beta_v = s.beta_vec.n > 0 ? s.beta_vec.as<T>() : nullptr;
+  d.p = s.p.as<T>();
+  d.rhs = s.rhs.n > 0 ? s.rhs.as<T>() : nullptr;
+  d.kappa = static_cast<T>(s.kappa);
+  d.pkappa = static_cast<T>(s.pkappa);
+  d.Bs = static_cast<T>(s.Bs);
+  d.Cs = static_cast<T>(s.Cs);
+  d.a1 = static_cast<T>(s.a1);
+  d.lam = static_cast<T>(s.lam);
+  d.alpha = static_cast<T>(s.alpha);
+  d.beta = static_cast<T>(s.beta);
+  d.M = static_cast<T>(s.M);
+  return d;
+}
+
+template <class T> FusedScalarsT<T> ScalarsOf(const LassoBatchInst<T>& i, double a0, double a1) {
+  return {i.kappa, i.Bs, i.Cs, i.a1, i.lam, i.alpha, i.beta, i.M,
+          static_cast<T>(a0), static_cast<T>(1.0 / (a0 * a0 + a1 * a1)), i.alpha_v, i.beta_v};
+}
 
 template <class T> __device__ inline T WaveSumT(T v) {
 #pragma unroll
@@ -33,27 +80,55 @@ template <class T> __device__ inline T ScaledZoneOneT(T xi, T lam, T alpha, T be
   return -M;
 }
 
-// One column's elementwise chain (see ChainOne in kernels_fused.hip for the line-by-line
-// correspondence).
+// One column's elementwise chain.  Returns v0' (input of the next sweep's forward pass).
 template <class T>
 __device__ inline T ChainOneT(T d, const FusedScalarsT<T>& c, T u, T y0p, T y1p, T* x0o, T* x1o,
                               T* y0o, T* y1o, T* uo) {
+  // sweep start: u -= y0; u -= y1; then term 0: u += y0       (prox_admm.cc:137-142)
   const T v0 = ((u - y0p) - y1p) + y0p;
-  const T x0 = c.kappa * d + v0;
-  const T y0 = x0;
-  const T u1 = v0 - y0;
-  const T u2 = u1 + y1p;
-  const T vin = c.Bs * u2;
+  const T x0 = c.kappa * d + v0;  // back substitution epilogue: alpha*acc + 1*y
+  const T y0 = x0;                // y_0 = A_ x_0 with A_(c0,x) = I
+  const T u1 = v0 - y0;           // u -= y_0
+  const T u2 = u1 + y1p;          // term 1: u += y_1
+  const T vin = c.Bs * u2;        // VectorProx: B v (+ g = 0)      (vector_prox.cc:141)
   const T xz = ScaledZoneOneT<T>(vin, c.lam, c.alpha, c.beta, c.M);
-  const T x1 = c.Cs * xz;
-  const T y1 = c.a1 * x1;
-  const T u3 = u2 - y1;
+  const T x1 = c.Cs * xz;         // C (x - g)                       (vector_prox.cc:145)
+  const T y1 = c.a1 * x1;         // y_1 = A_ x_1
+  const T u3 = u2 - y1;           // u -= y_1
   *x0o = x0;
   *x1o = x1;
   *y0o = y0;
   *y1o = y1;
   *uo = u3;
+  // next sweep's prox-0 input
   return ((u3 - y0) - y1) + y0;
+}
+
+// One column of the TWO-BLOCK driver's sweep (reference algorithms/prox_admm_two_block.cc:97-112):
+//   zu = z - u ;  x0 = prox_0(zu)_0 = v0 + kappa d ;  x1 = prox_1(zu)_1 (scaled zone) ;
+//   z = projection of x + u onto {a0 z0 + a1 z1 = 0} ;  u += x - z.
+// Returns the next sweep's prox-0 input z0' - u0'.
+template <class T>
+__device__ inline T ChainTwoBlockT(T d, const FusedScalarsT<T>& c, T z0p, T z1p, T u0p, T u1p, T* x0o,
+                                   T* x1o, T* z0o, T* z1o, T* u0o, T* u1o) {
+  const T v0 = z0p - u0p;
+  const T v1 = z1p - u1p;
+  const T x0 = c.kappa * d + v0;
+  const T x1 = c.Cs * ScaledZoneOneT<T>(c.Bs * v1, c.lam, c.alpha, c.beta, c.M);
+  const T w0 = x0 + u0p;
+  const T w1 = x1 + u1p;
+  const T t = (c.a0 * w0 + c.a1 * w1) * c.inv_aa;
+  const T z0 = w0 - c.a0 * t;
+  const T z1 = w1 - c.a1 * t;
+  const T u0 = u0p + (x0 - z0);
+  const T u1 = u1p + (x1 - z1);
+  *x0o = x0;
+  *x1o = x1;
+  *z0o = z0;
+  *z1o = z1;
+  *u0o = u0;
+  *u1o = u1;
+  return z0 - u0;
 }
 
 }  // namespace
