@@ -456,3 +456,22 @@ def tv1d(v, lam):
     _check(lib().eps_tv1d(v.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(v.size),
                           ctypes.c_double(lam), x.ctypes.data_as(ctypes.c_void_p)))
     return x
+
+
+def tv1d_batch(V, lam, axis=0):
+    """The TV-1D prox of every column (axis=0) or every row (axis=1) of the 2-D array V, each on
+    its own and all with the weight lam, in one device pass (eps_tv1d_batch).  Returns an array
+    of V's shape."""
+    V = np.asarray(V, dtype=np.float64)
+    if V.ndim != 2:
+        raise error("tv1d_batch: V must be a 2-D array, got %d dimension(s)" % V.ndim)
+    if axis not in (0, 1):
+        raise error("tv1d_batch: axis must be 0 or 1, got %r" % (axis,))
+    # the slices one after the other: the columns of V (axis 0) or its rows (axis 1)
+    S = np.ascontiguousarray(V.T if axis == 0 else V)
+    count, length = S.shape
+    X = np.empty_like(S)
+    _check(lib().eps_tv1d_batch(S.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(length),
+                                ctypes.c_size_t(count), ctypes.c_double(lam),
+                                X.ctypes.data_as(ctypes.c_void_p)))
+    return np.ascontiguousarray(X.T) if axis == 0 else X

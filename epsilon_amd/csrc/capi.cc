@@ -108,6 +108,18 @@ LinearMap ParseMap(const void* bytes, size_t len, DataMap* dm) {
   return BuildLinearMap(p, dm);
 }
 
+// count contiguous signals of len samples; checked before anything touches the device
+eps::k::Segs BatchSegs(size_t len, size_t count) {
+  const size_t limit = (size_t(1) << 31) - 1;  // (by division: the product may not fit a size_t)
+  EPS_CHECK_MSG(len == 0 || count <= (limit - 1) / len, "tv1d: len * count must be below 2^31");
+  eps::k::Segs S;
+  S.count = static_cast<int64_t>(count);
+  S.len = static_cast<int64_t>(len);
+  S.seg_stride = S.len;
+  S.elem_stride = 1;
+  return S;
+}
+
 }  // namespace
 
 extern "C" {
@@ -925,6 +937,38 @@ int eps_tv1d_device(const void* v_dev, void* x_dev, size_t n, int kind, double l
     Runtime::Get();
     EPS_HIP(hipDeviceSynchronize());  // v may have been produced on any stream of the caller
     k::Tv1d(x, v, lam);
+    Runtime::Get().Sync();
+    if (levels) *levels = k::Tv1dLastLevels();
+  });
+}
+
+int eps_tv1d_batch(const double* v, size_t len, size_t count, double lam, double* x) {
+  return Guard([&] {
+    const k::Segs S = BatchSegs(len, count);
+    const int64_t n = S.len * S.count;
+    if (n == 0) return;
+    EPS_CHECK(v != nullptr && x != nullptr);
+    const DType dt = ConfiguredDType();
+    DVec vd = DVec::FromHost(v, n, dt);
+    DVec xd = DVec::Empty(n, dt);
+    k::Tv1dSeg(xd, vd, lam, S);
+    xd.ToHost(x);
+  });
+}
+
+int eps_tv1d_batch_device(const void* v_dev, void* x_dev, size_t len, size_t count, int kind, double lam,
+                          int* levels) {
+  return Guard([&] {
+    EPS_CHECK_MSG(kind == EPS_BLOB_DEVICE_F32 || kind == EPS_BLOB_DEVICE_F64, "bad kind");
+    const k::Segs S = BatchSegs(len, count);
+    const int64_t n = S.len * S.count;
+    EPS_CHECK(n == 0 || (v_dev != nullptr && x_dev != nullptr));
+    const DType dt = kind == EPS_BLOB_DEVICE_F32 ? F32 : F64;
+    DVec v = DVec::Borrow(const_cast<void*>(v_dev), n, dt);
+    DVec x = DVec::Borrow(x_dev, n, dt);
+    Runtime::Get();
+    EPS_HIP(hipDeviceSynchronize());  // v may have been produced on any stream of the caller
+    k::Tv1dSeg(x, v, lam, S);
     Runtime::Get().Sync();
     if (levels) *levels = k::Tv1dLastLevels();
   });

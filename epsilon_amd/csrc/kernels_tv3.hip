@@ -36,11 +36,20 @@
 // 16-byte record per region end (the parent's tau / delta / right side, for the children's
 // delta), plus the fp64 prefix sums of y that only region boundaries touch.  All decisions in
 // fp64 (data may be f32), as in round 2.
+//
+// Tv1dSeg: many signals with one lam in the same passes.  K slices laid end to end are K initial
+// regions whose side codes say "no neighbour" (TvInitSegKernel instead of TvInitKernel); the
+// level kernels cross a region boundary only through those codes, so the level loop, the
+// termination test and the flush run on the concatenation as they are, and the depth is that of
+// the deepest slice.  Region means still come from ONE fp64 prefix sum over the concatenation.
+// Slices that are strided in memory (the rows of a column-major matrix) go through a tiled LDS
+// transpose into a scratch buffer and back; the level kernels keep their unit-stride form.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "kernels.h"
 
@@ -1116,7 +1125,48 @@ __global__ __launch_bounds__(64) void TvInitKernel(TvS<T> s) {
   }
 }
 
-template <class T> int Tv1dLevelSets3(const DVec& xv, const DVec& yv, double lam) {
+// Segmented form: `count` regions of `len` samples laid end to end, none with a neighbour (side
+// codes 0 / 0), so the level kernels never carry anything across a segment boundary.  `group`
+// lanes (a power of two up to 64, at least min(len, 64)) share a segment: each takes one block
+// mean for the delta guess, a butterfly adds them up in an order fixed by len.  The first nb
+// threads of the grid also write tile_head: the last segment start inside a tile, or -1.
+template <class T>
+__global__ __launch_bounds__(kBlock) void TvInitSegKernel(TvS<T> s, int64_t len, int64_t count, int group) {
+  const int64_t gid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (gid < s.nb) {
+    const int64_t lo = gid * kTile;
+    const int64_t hi = lo + kTile < s.n ? lo + kTile : s.n;
+    const int64_t h = (hi - 1) / len * len;
+    s.tile_head[gid] = h >= lo ? static_cast<int32_t>(h) : -1;
+  }
+  const int64_t seg = gid / group;
+  const int sub = static_cast<int>(gid % group);
+  const int64_t nblk = len < 64 ? len : 64;
+  const bool on = seg < count;
+  const int64_t base = on ? seg * len : 0;
+  double m = 0.0;
+  if (on && sub < nblk) {
+    const int64_t e0 = sub * len / nblk, e1 = (sub + 1) * len / nblk;
+    m = (s.Pp[base + e1] - s.Pp[base + e0]) / static_cast<double>(e1 > e0 ? e1 - e0 : 1);
+  }
+  double sum = m, sq = m * m;
+  for (int off = group >> 1; off > 0; off >>= 1) {
+    sum += __shfl_xor(sum, off, 64);
+    sq += __shfl_xor(sq, off, 64);
+  }
+  if (on && sub == 0) {
+    s.st[base] = static_cast<uint8_t>(kHead);  // (len >= 2: head and end are two bytes)
+    s.st[base + len - 1] = static_cast<uint8_t>(kEnd);
+    const double mean = sum / static_cast<double>(nblk);
+    const double var = fmax(sq / static_cast<double>(nblk) - mean * mean, 0.0);
+    s.hrec[base] = HeadRec{(s.Pp[base + len] - s.Pp[base]) / static_cast<double>(len),
+                           static_cast<float>(fmin(0.67 * sqrt(var), 1e30)), 0u};  // (any finite delta is valid)
+  }
+}
+
+// seg_len == 0: one region [0, n - 1] (Tv1d).  Otherwise n = seg_count * seg_len, seg_len >= 2.
+template <class T>
+int Tv1dLevelSets3(const DVec& xv, const DVec& yv, double lam, int64_t seg_len = 0, int64_t seg_count = 1) {
   const int64_t n = yv.n;
   Runtime& rt = Runtime::Get();
   hipStream_t q = rt.stream();
@@ -1175,7 +1225,15 @@ template <class T> int Tv1dLevelSets3(const DVec& xv, const DVec& yv, double lam
   EPS_HIP(hipMemsetAsync(s.cuts, 0, static_cast<size_t>(kMaxLevels) * sizeof(unsigned long long), q));
   s.st = stA;
   s.st2 = stB;
-  hipLaunchKernelGGL(TvInitKernel<T>, dim3(1), dim3(64), 0, q, s);
+  if (seg_len == 0) {
+    hipLaunchKernelGGL(TvInitKernel<T>, dim3(1), dim3(64), 0, q, s);
+  } else {
+    int group = 1;
+    while (group < 64 && group < seg_len) group <<= 1;
+    const int64_t threads = seg_count * group > nb ? seg_count * group : nb;
+    hipLaunchKernelGGL(TvInitSegKernel<T>, dim3(static_cast<unsigned>((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                       q, s, seg_len, seg_count, group);
+  }
 
   const dim3 grid(static_cast<unsigned>(nb)), block(kBlock);
   auto enqueue_level = [&](int level) {
@@ -1223,6 +1281,69 @@ template <class T> int Tv1dLevelSets3(const DVec& xv, const DVec& yv, double lam
 
 int g_last_levels = 0;
 
+// ---- transpose for slices that are strided in memory ----------------------------------------------
+// out[c * R + r] = in[r * C + c] for an R x C row-major `in`.  A workgroup moves a 64 x 64 tile
+// through LDS (rows padded by one element: the transposed reads of a wave fall on distinct
+// banks); both sides use 16-byte global accesses when the base and the row length allow it
+// (`vec_in` / `vec_out`) and the access lies inside the matrix, single elements otherwise.
+constexpr int kTrTile = 64;
+
+template <class T>
+__global__ __launch_bounds__(kBlock) void TransposeKernel(const T* __restrict__ in, T* __restrict__ out, int64_t R,
+                                                          int64_t C, int64_t tiles_c, int vec_in, int vec_out) {
+  constexpr int V = 16 / sizeof(T);        // elements of a 16-byte access
+  constexpr int kPerRow = kTrTile / V;     // threads along a tile row
+  constexpr int kRows = kBlock / kPerRow;  // tile rows per sweep of the workgroup
+  using Vec = typename std::conditional<sizeof(T) == 4, float4, double2>::type;
+  __shared__ T tile[kTrTile][kTrTile + 1];
+  const int64_t r0 = static_cast<int64_t>(blockIdx.x) / tiles_c * kTrTile;
+  const int64_t c0 = static_cast<int64_t>(blockIdx.x) % tiles_c * kTrTile;
+  const int tx = threadIdx.x % kPerRow, ty = threadIdx.x / kPerRow;
+#pragma unroll
+  for (int rr = ty; rr < kTrTile; rr += kRows) {
+    const int64_t r = r0 + rr, c = c0 + tx * V;
+    if (r >= R) continue;
+    if (vec_in && c + V <= C) {
+      const Vec a = *reinterpret_cast<const Vec*>(in + r * C + c);
+      T e[V];
+      memcpy(e, &a, sizeof(Vec));
+#pragma unroll
+      for (int q = 0; q < V; ++q) tile[rr][tx * V + q] = e[q];
+    } else {
+#pragma unroll
+      for (int q = 0; q < V; ++q)
+        if (c + q < C) tile[rr][tx * V + q] = in[r * C + c + q];
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int cc = ty; cc < kTrTile; cc += kRows) {
+    const int64_t c = c0 + cc, r = r0 + tx * V;
+    if (c >= C) continue;
+    if (vec_out && r + V <= R) {
+      T e[V];
+#pragma unroll
+      for (int q = 0; q < V; ++q) e[q] = tile[tx * V + q][cc];
+      Vec a;
+      memcpy(&a, e, sizeof(Vec));
+      *reinterpret_cast<Vec*>(out + c * R + r) = a;
+    } else {
+#pragma unroll
+      for (int q = 0; q < V; ++q)
+        if (r + q < R) out[c * R + r + q] = tile[tx * V + q][cc];
+    }
+  }
+}
+
+template <class T> void Transpose(const T* in, T* out, int64_t R, int64_t C) {
+  constexpr int V = 16 / sizeof(T);
+  const int64_t tiles_r = (R + kTrTile - 1) / kTrTile, tiles_c = (C + kTrTile - 1) / kTrTile;
+  const int vec_in = reinterpret_cast<uintptr_t>(in) % 16 == 0 && C % V == 0;
+  const int vec_out = reinterpret_cast<uintptr_t>(out) % 16 == 0 && R % V == 0;
+  hipLaunchKernelGGL(TransposeKernel<T>, dim3(static_cast<unsigned>(tiles_r * tiles_c)), dim3(kBlock), 0,
+                     Runtime::Get().stream(), in, out, R, C, tiles_c, vec_in, vec_out);
+}
+
 }  // namespace
 
 int Tv1dLastLevels() { return g_last_levels; }
@@ -1243,6 +1364,46 @@ void Tv1d(const DVec& x, const DVec& v, double lam) {
   }
   if (x.dt == F32) g_last_levels = Tv1dLevelSets3<float>(x, v, lam);
   else g_last_levels = Tv1dLevelSets3<double>(x, v, lam);
+}
+
+void Tv1dSeg(const DVec& x, const DVec& v, double lam, const Segs& S) {
+  EPS_CHECK(x.n == v.n && x.dt == v.dt);
+  if (S.count == 1) {  // the unsegmented operator, bit for bit
+    EPS_CHECK_MSG(S.len == x.n && S.elem_stride == 1, "tv1d: one slice must cover the argument");
+    Tv1d(x, v, lam);
+    return;
+  }
+  const int64_t n = x.n;
+  EPS_CHECK_MSG(S.count >= 0 && S.len >= 0 && S.count * S.len == n,
+                "tv1d: " << S.count << " slices of " << S.len << " samples do not cover " << n << " entries");
+  if (n == 0) return;
+  EPS_CHECK_MSG(n < (int64_t(1) << 31) - 1, "tv1d: len * count must be below 2^31");
+  const bool contiguous = S.elem_stride == 1 && S.seg_stride == S.len;
+  const bool strided = S.seg_stride == 1 && S.elem_stride == S.count;
+  EPS_CHECK_MSG(contiguous || strided || S.len == 1, "tv1d: slices must be the columns or the rows of a matrix");
+  if (S.len == 1 || lam == 0) {  // tf_dp's trivial cases, slice by slice
+    Copy(x, v);
+    g_last_levels = 0;
+    return;
+  }
+  if (contiguous) {
+    if (x.dt == F32) g_last_levels = Tv1dLevelSets3<float>(x, v, lam, S.len, S.count);
+    else g_last_levels = Tv1dLevelSets3<double>(x, v, lam, S.len, S.count);
+    return;
+  }
+  // slice s, entry p at s + p * count: a len x count row-major matrix.  The level-set kernels
+  // keep their unit-stride form: transpose, run on contiguous slices, transpose back.
+  DVec vt = DVec::Empty(n, v.dt), xt = DVec::Empty(n, v.dt);
+  if (x.dt == F32) {
+    Transpose<float>(v.as<float>(), vt.as<float>(), S.len, S.count);
+    g_last_levels = Tv1dLevelSets3<float>(xt, vt, lam, S.len, S.count);
+    Transpose<float>(xt.as<float>(), x.as<float>(), S.count, S.len);
+  } else {
+    Transpose<double>(v.as<double>(), vt.as<double>(), S.len, S.count);
+    g_last_levels = Tv1dLevelSets3<double>(xt, vt, lam, S.len, S.count);
+    Transpose<double>(xt.as<double>(), x.as<double>(), S.count, S.len);
+  }
+  EPS_HIP(hipGetLastError());
 }
 
 }  // namespace k

@@ -152,6 +152,53 @@ def tv_1d_prox_expr(n, lam_alpha=1.0):
     return ir.prox(ProxFunction.TOTAL_VARIATION_1D, x, alpha=lam_alpha)
 
 
+def tv_prox_expr(rows, cols, axis, lam_alpha=1.0):
+    """TOTAL_VARIATION_1D of every column (axis 0) or every row (axis 1) of a rows x cols matrix
+    variable, summed, for `eval_prox`."""
+    X = ir.variable(rows, cols, "var:X")
+    return ir.prox(ProxFunction.TOTAL_VARIATION_1D, X, alpha=lam_alpha, has_axis=True, axis=int(axis))
+
+
+def tv_2d_data(rows, cols, seed=0):
+    """A piecewise-constant image (a few rectangles of constant height on a flat ground) plus unit
+    noise, and the weight of the two TV terms."""
+    rng = np.random.RandomState(seed)
+    k = max(int(np.sqrt(rows * cols) / 4), 1)
+    X0 = np.ones((rows, cols))
+    for _ in range(k):
+        r = np.sort(rng.randint(0, rows + 1, 2))
+        c = np.sort(rng.randint(0, cols + 1, 2))
+        X0[r[0]:r[1], c[0]:c[1]] += 10 * (rng.rand() - 0.5)
+    B = X0 + rng.randn(rows, cols)
+    return B, 1.0
+
+
+def tv_2d(rows, cols, seed=0):
+    """Anisotropic 2-D total variation denoising,
+    0.5*sum_square(X' - B) + lam*TV_axis0(X'') + lam*TV_axis1(X)  s.t.  X' - X = 0, X'' - X = 0,
+    built like `fused_lasso`: the least-squares term and the column term work on copies tied to X,
+    the row term keeps X itself."""
+    B, lam = tv_2d_data(rows, cols, seed)
+    n = rows * cols
+    Xs = ir.variable(rows, cols, "separate:var:X:sum_square")
+    Xc = ir.variable(rows, cols, "separate:var:X:tv_axis0")
+    X = ir.variable(rows, cols, "var:X")
+    f0 = ir.prox(ProxFunction.SUM_SQUARE,
+                 ir.add(ir.reshape(Xs, n, 1),
+                        ir.linear_map(ir.scalar(-1, n), ir.constant(B.reshape(-1, 1, order="F")))),
+                 alpha=0.5, arg_size=[(n, 1)])
+    f1 = ir.prox(ProxFunction.TOTAL_VARIATION_1D, Xc, alpha=lam, has_axis=True, axis=0)
+    f2 = ir.prox(ProxFunction.TOTAL_VARIATION_1D, X, alpha=lam, has_axis=True, axis=1)
+    c0 = ir.zero(ir.add(ir.reshape(Xs, n, 1), ir.linear_map(ir.scalar(-1, n), ir.reshape(X, n, 1))))
+    c1 = ir.zero(ir.add(ir.reshape(Xc, n, 1), ir.linear_map(ir.scalar(-1, n), ir.reshape(X, n, 1))))
+    return ir.Problem([f0, f1, f2], [c0, c1]), dict(B=B, lam=lam)
+
+
+def tv_2d_objective(B, lam, X):
+    return float(0.5 * np.sum((X - B) ** 2) + lam * np.abs(np.diff(X, axis=0)).sum() +
+                 lam * np.abs(np.diff(X, axis=1)).sum())
+
+
 def robust_pca_data(n, r=10, density=0.1, seed=0):
     rng = np.random.RandomState(seed)
     L0 = rng.randn(n, r).dot(rng.randn(r, n))

@@ -327,6 +327,19 @@ int eps_tv1d(const double* v, size_t n, double lam, double* x);
  * level-set recursion.  Synchronises before returning. */
 int eps_tv1d_device(const void* v_dev, void* x_dev, size_t n, int kind, double lam, int* levels);
 
+/* The prox of `count` signals of `len` samples each in one pass: v and x hold the signals one
+ * after the other (signal s is v[s * len .. s * len + len - 1]), every signal is solved on its
+ * own - no term couples the last sample of one to the first sample of the next - and one lam
+ * serves all of them.  len * count must be below 2^31 - 1.  count == 1 is eps_tv1d. */
+int eps_tv1d_batch(const double* v, size_t len, size_t count, double lam, double* x);
+
+/* The same on device-resident data, with the conventions of eps_tv1d_device: v, x are device
+ * pointers to len * count elements of `kind`, signal s at elements [s * len, (s + 1) * len);
+ * *levels (may be NULL) receives the depth of the level-set recursion, the maximum over the
+ * signals.  Synchronises before returning. */
+int eps_tv1d_batch_device(const void* v_dev, void* x_dev, size_t len, size_t count, int kind, double lam,
+                          int* levels);
+
 #ifdef __cplusplus
 }
 #endif
