@@ -120,6 +120,37 @@ eps::k::Segs BatchSegs(size_t len, size_t count) {
   return S;
 }
 
+// one signal of n samples (its size limit is k::Tv1dSeg's check, after the data is on the device)
+eps::k::Segs OneSignal(size_t n) {
+  eps::k::Segs S;
+  S.len = S.seg_stride = static_cast<int64_t>(n);
+  return S;
+}
+
+// The bodies of the eps_tv1d* entries behind their argument checks.  Host data goes through device
+// buffers of the configured dtype; device data (of a checked `kind`) is borrowed, and the call
+// waits for the device on both sides of the prox.
+void Tv1dOnHostData(const double* v, double* x, const eps::k::Segs& S, double lam) {
+  const int64_t n = S.len * S.count;
+  const DType dt = ConfiguredDType();
+  DVec vd = DVec::FromHost(v, n, dt);
+  DVec xd = DVec::Empty(n, dt);
+  eps::k::Tv1dSeg(xd, vd, lam, S);
+  xd.ToHost(x);
+}
+
+void Tv1dOnDeviceData(const void* v_dev, void* x_dev, const eps::k::Segs& S, int kind, double lam, int* levels) {
+  const int64_t n = S.len * S.count;
+  const DType dt = kind == EPS_BLOB_DEVICE_F32 ? F32 : F64;
+  DVec v = DVec::Borrow(const_cast<void*>(v_dev), n, dt);
+  DVec x = DVec::Borrow(x_dev, n, dt);
+  Runtime::Get();
+  EPS_HIP(hipDeviceSynchronize());  // v may have been produced on any stream of the caller
+  const int depth = eps::k::Tv1dSeg(x, v, lam, S);
+  Runtime::Get().Sync();
+  if (levels) *levels = depth;
+}
+
 }  // namespace
 
 extern "C" {
@@ -918,41 +949,23 @@ int eps_bench_svd_device(const void* y_dev, int64_t m, int64_t n, int max_sweeps
 }
 
 int eps_tv1d(const double* v, size_t n, double lam, double* x) {
-  return Guard([&] {
-    const DType dt = ConfiguredDType();
-    DVec vd = DVec::FromHost(v, n, dt);
-    DVec xd = DVec::Empty(n, dt);
-    k::Tv1d(xd, vd, lam);
-    xd.ToHost(x);
-  });
+  return Guard([&] { Tv1dOnHostData(v, x, OneSignal(n), lam); });
 }
 
 int eps_tv1d_device(const void* v_dev, void* x_dev, size_t n, int kind, double lam, int* levels) {
   return Guard([&] {
     EPS_CHECK(v_dev != nullptr && x_dev != nullptr);
     EPS_CHECK_MSG(kind == EPS_BLOB_DEVICE_F32 || kind == EPS_BLOB_DEVICE_F64, "bad kind");
-    const DType dt = kind == EPS_BLOB_DEVICE_F32 ? F32 : F64;
-    DVec v = DVec::Borrow(const_cast<void*>(v_dev), static_cast<int64_t>(n), dt);
-    DVec x = DVec::Borrow(x_dev, static_cast<int64_t>(n), dt);
-    Runtime::Get();
-    EPS_HIP(hipDeviceSynchronize());  // v may have been produced on any stream of the caller
-    k::Tv1d(x, v, lam);
-    Runtime::Get().Sync();
-    if (levels) *levels = k::Tv1dLastLevels();
+    Tv1dOnDeviceData(v_dev, x_dev, OneSignal(n), kind, lam, levels);
   });
 }
 
 int eps_tv1d_batch(const double* v, size_t len, size_t count, double lam, double* x) {
   return Guard([&] {
     const k::Segs S = BatchSegs(len, count);
-    const int64_t n = S.len * S.count;
-    if (n == 0) return;
+    if (S.len * S.count == 0) return;
     EPS_CHECK(v != nullptr && x != nullptr);
-    const DType dt = ConfiguredDType();
-    DVec vd = DVec::FromHost(v, n, dt);
-    DVec xd = DVec::Empty(n, dt);
-    k::Tv1dSeg(xd, vd, lam, S);
-    xd.ToHost(x);
+    Tv1dOnHostData(v, x, S, lam);
   });
 }
 
@@ -961,16 +974,8 @@ int eps_tv1d_batch_device(const void* v_dev, void* x_dev, size_t len, size_t cou
   return Guard([&] {
     EPS_CHECK_MSG(kind == EPS_BLOB_DEVICE_F32 || kind == EPS_BLOB_DEVICE_F64, "bad kind");
     const k::Segs S = BatchSegs(len, count);
-    const int64_t n = S.len * S.count;
-    EPS_CHECK(n == 0 || (v_dev != nullptr && x_dev != nullptr));
-    const DType dt = kind == EPS_BLOB_DEVICE_F32 ? F32 : F64;
-    DVec v = DVec::Borrow(const_cast<void*>(v_dev), n, dt);
-    DVec x = DVec::Borrow(x_dev, n, dt);
-    Runtime::Get();
-    EPS_HIP(hipDeviceSynchronize());  // v may have been produced on any stream of the caller
-    k::Tv1dSeg(x, v, lam, S);
-    Runtime::Get().Sync();
-    if (levels) *levels = k::Tv1dLastLevels();
+    EPS_CHECK(S.len * S.count == 0 || (v_dev != nullptr && x_dev != nullptr));
+    Tv1dOnDeviceData(v_dev, x_dev, S, kind, lam, levels);
   });
 }
 

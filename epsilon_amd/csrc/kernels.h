@@ -318,16 +318,13 @@ void SegKlDivEpigraph(const DVec& x, const DVec& y, const DVec& t, const DVec& u
                       const DVec& s, const Segs& S);
 void ExpEpigraph(const DVec& x, const DVec& t, const DVec& v, const DVec& s);  // prox/exp.cc
 
-// reference prox/total_variation_1d.cc:21 (glmgen tf_dp): exact 1-D TV prox
-void Tv1d(const DVec& x, const DVec& v, double lam);
-int Tv1dLastLevels();  // depth of the level-set recursion of the last Tv1d / Tv1dSeg call
-// The same for every slice of S on its own (no term couples two slices), one lam for all, in the
-// passes of one call: S.count == 1 is Tv1d itself; slices are contiguous (elem_stride 1,
-// seg_stride len) or the rows of a column-major matrix (seg_stride 1, elem_stride count).
-void Tv1dSeg(const DVec& x, const DVec& v, double lam, const Segs& S);
-int Tv1dBinary(const DVec& x, const DVec& v, double lam);  // round-2 form (kernels_tv.hip), returns the depth
-// the same by Johnson's sequential DP on one lane (cross-check of the parallel kernel)
-void Tv1dSerial(const DVec& x, const DVec& v, double lam);
+// reference prox/total_variation_1d.cc:21 (glmgen tf_dp): exact 1-D TV prox of every slice of S
+// on its own (no term couples two slices), one lam for all, in the passes of one call.  Slices
+// are contiguous (elem_stride 1, seg_stride len) or the rows of a column-major matrix (seg_stride
+// 1, elem_stride count).  Returns the depth of the level-set recursion, the maximum over the
+// slices; 0 for the trivial cases (len <= 1 or lam == 0: x = v).  One signal is the single slice
+// that covers v (count 1, len n).
+int Tv1dSeg(const DVec& x, const DVec& v, double lam, const Segs& S);
 
 }  // namespace k
 }  // namespace eps

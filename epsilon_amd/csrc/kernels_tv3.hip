@@ -3,10 +3,27 @@
 //   x = argmin 1/2 ||x - y||^2 + lam * sum_i |x[i+1] - x[i]|
 //
 // The reference calls glmgen's `tf_dp` (reference src/epsilon/prox/total_variation_1d.cc:8,21):
-// Johnson's dynamic program, sequential.  kernels_tv.hip (round 2) computes the same unique
-// minimiser by divide and conquer over LEVEL SETS with one threshold per region and level (depth
-// ~ log2 of the number of constant pieces, every level three scans over all n).  This file keeps
-// the mathematics and changes the economics:
+// Johnson's dynamic program, inherently sequential (a forward knot sweep and a backward fill).
+// This kernel set computes the same unique minimiser with a divide-and-conquer over LEVEL SETS
+// (Hochbaum 2001 / Chambolle-Darbon 2009, specialised to a chain):
+//
+//   For a contiguous region R whose neighbours are known to lie strictly above / below it, the
+//   neighbour terms are linear and fold into the end samples (y'_l = y_l - lam*c_l, ...).
+//   With tau = mean(y'_R):  {i : x*_i > tau} is the minimal minimiser of the BINARY chain problem
+//       min_u  sum_i (tau - y'_i) u_i + lam * sum_i |u[i+1] - u[i]| ,   u in {0,1}^R ,
+//   and since mean(x*_R) = tau, the region is constant (= tau) iff that set is empty.
+//   Otherwise the runs of u are new regions, strictly ordered across every cut, and recurse.
+//
+// The binary chain problem is a 2-state Viterbi whose forward recursion on the cost difference
+// d_i = cost(u_i=1) - cost(u_i=0) is  d_i = a_i + clip(d_{i-1}, -lam, lam)  - a composition of
+// clamp-shift maps (p, lo, hi), which is associative => a parallel SCAN; the backward decode
+// u_i = [d_i < -lam] or [d_i < lam and u_{i+1}] is a "first definite value to the right" scan.
+// All decisions are taken in fp64 (data may be f32), so the partition matches the fp64 DP except
+// at exact ties.
+//
+// With one threshold per region and level (round 2) the depth is ~ log2 of the number of constant
+// pieces and every level is three scans over all n.  This file keeps the mathematics and changes
+// the economics:
 //
 //   * THREE thresholds per region and level.  For a region R whose neighbours are known to lie
 //     strictly above / below it, the restricted problem is a plain TV problem on the chain R with
@@ -18,8 +35,8 @@
 //     strictly ordered across every cut.  tau stays the region mean, so "the middle set is empty"
 //     still means "the region is constant".  delta is a guess (half the distance from the new
 //     mean to the nearest parent threshold that bounds the region): any value is valid, a good one
-//     makes the split 4-way.  Depth on the reference's tv_1d generator: 8 levels where the binary
-//     recursion takes 12 (n = 2e5), see tools_tv3_prototype.py (the CPU prototype of this file).
+//     makes the split 4-way.  Depth on the reference's tv_1d generator: 8 levels where one
+//     threshold takes 12 (n = 2e5), see tools_tv3_prototype.py (the CPU prototype of this file).
 //   * Four passes over the data per level instead of six: the apply phase of the forward scan
 //     also emits the tile aggregates of the backward decode scan, the decode's apply phase those
 //     of the backward boundary scan (it knows the label right of every sample from its own scan).
@@ -35,10 +52,10 @@
 // a 16-byte record per region head (tau, delta, sides of the neighbours, "did not split") and a
 // 16-byte record per region end (the parent's tau / delta / right side, for the children's
 // delta), plus the fp64 prefix sums of y that only region boundaries touch.  All decisions in
-// fp64 (data may be f32), as in round 2.
+// fp64 (data may be f32).
 //
 // Tv1dSeg: many signals with one lam in the same passes.  K slices laid end to end are K initial
-// regions whose side codes say "no neighbour" (TvInitSegKernel instead of TvInitKernel); the
+// regions whose side codes say "no neighbour" (TvInitSegKernel; one signal is K = 1); the
 // level kernels cross a region boundary only through those codes, so the level loop, the
 // termination test and the flush run on the concatenation as they are, and the depth is that of
 // the deepest slice.  Region means still come from ONE fp64 prefix sum over the concatenation.
@@ -47,7 +64,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <type_traits>
 
@@ -1099,37 +1115,12 @@ __global__ __launch_bounds__(kBlock) void TvFlushKernel(TvS<T> s) {
   }
 }
 
-template <class T>
-__global__ __launch_bounds__(64) void TvInitKernel(TvS<T> s) {
-  // one region [0, n-1] without neighbours; delta from the spread of 64 block means (one lane each)
-  const int lane = threadIdx.x;
-  const int64_t nblk = s.n < 64 ? s.n : 64;
-  double m = 0.0;
-  if (lane < nblk) {
-    const int64_t e0 = lane * s.n / nblk, e1 = (lane + 1) * s.n / nblk;
-    m = (s.Pp[e1] - s.Pp[e0]) / static_cast<double>(e1 > e0 ? e1 - e0 : 1);
-  }
-  double sum = m, sq = m * m;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    sum += __shfl_down(sum, off, 64);
-    sq += __shfl_down(sq, off, 64);
-  }
-  if (lane == 0) {
-    s.st[0] = static_cast<uint8_t>(s.st[0] | kHead);
-    s.st[s.n - 1] = static_cast<uint8_t>(s.st[s.n - 1] | kEnd);
-    const double mean = sum / static_cast<double>(nblk);
-    const double var = fmax(sq / static_cast<double>(nblk) - mean * mean, 0.0);
-    s.hrec[0] = HeadRec{s.Pp[s.n] / static_cast<double>(s.n), static_cast<float>(0.67 * sqrt(var)), 0u};
-    s.tile_head[0] = 0;
-  }
-}
-
-// Segmented form: `count` regions of `len` samples laid end to end, none with a neighbour (side
-// codes 0 / 0), so the level kernels never carry anything across a segment boundary.  `group`
-// lanes (a power of two up to 64, at least min(len, 64)) share a segment: each takes one block
-// mean for the delta guess, a butterfly adds them up in an order fixed by len.  The first nb
-// threads of the grid also write tile_head: the last segment start inside a tile, or -1.
+// Level 0: `count` regions of `len` samples laid end to end, none with a neighbour (side codes
+// 0 / 0), so the level kernels never carry anything across a segment boundary; a single signal is
+// count == 1.  `group` lanes (a power of two up to 64, at least min(len, 64)) share a segment:
+// each takes one block mean for the delta guess, a butterfly adds them up in an order fixed by
+// len.  The first nb threads of the grid also write tile_head: the last segment start inside a
+// tile, or -1.
 template <class T>
 __global__ __launch_bounds__(kBlock) void TvInitSegKernel(TvS<T> s, int64_t len, int64_t count, int group) {
   const int64_t gid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
@@ -1164,9 +1155,9 @@ __global__ __launch_bounds__(kBlock) void TvInitSegKernel(TvS<T> s, int64_t len,
   }
 }
 
-// seg_len == 0: one region [0, n - 1] (Tv1d).  Otherwise n = seg_count * seg_len, seg_len >= 2.
+// n = seg_count * seg_len samples, seg_len >= 2.  Returns the depth of the recursion.
 template <class T>
-int Tv1dLevelSets3(const DVec& xv, const DVec& yv, double lam, int64_t seg_len = 0, int64_t seg_count = 1) {
+int Tv1dLevelSets(const DVec& xv, const DVec& yv, double lam, int64_t seg_len, int64_t seg_count) {
   const int64_t n = yv.n;
   Runtime& rt = Runtime::Get();
   hipStream_t q = rt.stream();
@@ -1225,15 +1216,11 @@ int Tv1dLevelSets3(const DVec& xv, const DVec& yv, double lam, int64_t seg_len =
   EPS_HIP(hipMemsetAsync(s.cuts, 0, static_cast<size_t>(kMaxLevels) * sizeof(unsigned long long), q));
   s.st = stA;
   s.st2 = stB;
-  if (seg_len == 0) {
-    hipLaunchKernelGGL(TvInitKernel<T>, dim3(1), dim3(64), 0, q, s);
-  } else {
-    int group = 1;
-    while (group < 64 && group < seg_len) group <<= 1;
-    const int64_t threads = seg_count * group > nb ? seg_count * group : nb;
-    hipLaunchKernelGGL(TvInitSegKernel<T>, dim3(static_cast<unsigned>((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                       q, s, seg_len, seg_count, group);
-  }
+  int group = 1;
+  while (group < 64 && group < seg_len) group <<= 1;
+  const int64_t threads = seg_count * group > nb ? seg_count * group : nb;
+  hipLaunchKernelGGL(TvInitSegKernel<T>, dim3(static_cast<unsigned>((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, q,
+                     s, seg_len, seg_count, group);
 
   const dim3 grid(static_cast<unsigned>(nb)), block(kBlock);
   auto enqueue_level = [&](int level) {
@@ -1278,8 +1265,6 @@ int Tv1dLevelSets3(const DVec& xv, const DVec& yv, double lam, int64_t seg_len =
   EPS_HIP(hipGetLastError());
   return last + 1;
 }
-
-int g_last_levels = 0;
 
 // ---- transpose for slices that are strided in memory ----------------------------------------------
 // out[c * R + r] = in[r * C + c] for an R x C row-major `in`.  A workgroup moves a 64 x 64 tile
@@ -1344,66 +1329,37 @@ template <class T> void Transpose(const T* in, T* out, int64_t R, int64_t C) {
                      Runtime::Get().stream(), in, out, R, C, tiles_c, vec_in, vec_out);
 }
 
-}  // namespace
-
-int Tv1dLastLevels() { return g_last_levels; }
-
-void Tv1d(const DVec& x, const DVec& v, double lam) {
-  EPS_CHECK(x.n == v.n && x.dt == v.dt);
-  const int64_t n = x.n;
-  if (n == 0) return;
-  EPS_CHECK_MSG(n < (int64_t(1) << 31) - 1, "tv1d: n must be below 2^31");
-  if (n == 1 || lam == 0) {  // tf_dp's trivial cases
-    Copy(x, v);
-    return;
-  }
-  static const char* form = std::getenv("EPSILON_HIP_TV");
-  if (form != nullptr && form[0] == 'b') {
-    g_last_levels = Tv1dBinary(x, v, lam);
-    return;
-  }
-  if (x.dt == F32) g_last_levels = Tv1dLevelSets3<float>(x, v, lam);
-  else g_last_levels = Tv1dLevelSets3<double>(x, v, lam);
+// Contiguous slices run in place.  Strided ones (slice s, entry p at s + p * count: a len x count
+// row-major matrix) are transposed into scratch, solved there and transposed back, so the level
+// kernels keep their unit-stride form.
+template <class T> int Tv1dSlices(const DVec& x, const DVec& v, double lam, const Segs& S, bool contiguous) {
+  if (contiguous) return Tv1dLevelSets<T>(x, v, lam, S.len, S.count);
+  DVec vt = DVec::Empty(v.n, v.dt), xt = DVec::Empty(v.n, v.dt);
+  Transpose<T>(v.as<T>(), vt.as<T>(), S.len, S.count);
+  const int levels = Tv1dLevelSets<T>(xt, vt, lam, S.len, S.count);
+  Transpose<T>(xt.as<T>(), x.as<T>(), S.count, S.len);
+  EPS_HIP(hipGetLastError());
+  return levels;
 }
 
-void Tv1dSeg(const DVec& x, const DVec& v, double lam, const Segs& S) {
+}  // namespace
+
+int Tv1dSeg(const DVec& x, const DVec& v, double lam, const Segs& S) {
   EPS_CHECK(x.n == v.n && x.dt == v.dt);
-  if (S.count == 1) {  // the unsegmented operator, bit for bit
-    EPS_CHECK_MSG(S.len == x.n && S.elem_stride == 1, "tv1d: one slice must cover the argument");
-    Tv1d(x, v, lam);
-    return;
-  }
   const int64_t n = x.n;
   EPS_CHECK_MSG(S.count >= 0 && S.len >= 0 && S.count * S.len == n,
                 "tv1d: " << S.count << " slices of " << S.len << " samples do not cover " << n << " entries");
-  if (n == 0) return;
-  EPS_CHECK_MSG(n < (int64_t(1) << 31) - 1, "tv1d: len * count must be below 2^31");
-  const bool contiguous = S.elem_stride == 1 && S.seg_stride == S.len;
+  if (n == 0) return 0;
+  EPS_CHECK_MSG(n < (int64_t(1) << 31) - 1, "tv1d: " << (S.count == 1 ? "n" : "len * count") << " must be below 2^31");
+  // (one slice has no stride between slices: any unit-stride description of it is contiguous)
+  const bool contiguous = S.elem_stride == 1 && (S.seg_stride == S.len || S.count == 1);
   const bool strided = S.seg_stride == 1 && S.elem_stride == S.count;
   EPS_CHECK_MSG(contiguous || strided || S.len == 1, "tv1d: slices must be the columns or the rows of a matrix");
   if (S.len == 1 || lam == 0) {  // tf_dp's trivial cases, slice by slice
     Copy(x, v);
-    g_last_levels = 0;
-    return;
+    return 0;
   }
-  if (contiguous) {
-    if (x.dt == F32) g_last_levels = Tv1dLevelSets3<float>(x, v, lam, S.len, S.count);
-    else g_last_levels = Tv1dLevelSets3<double>(x, v, lam, S.len, S.count);
-    return;
-  }
-  // slice s, entry p at s + p * count: a len x count row-major matrix.  The level-set kernels
-  // keep their unit-stride form: transpose, run on contiguous slices, transpose back.
-  DVec vt = DVec::Empty(n, v.dt), xt = DVec::Empty(n, v.dt);
-  if (x.dt == F32) {
-    Transpose<float>(v.as<float>(), vt.as<float>(), S.len, S.count);
-    g_last_levels = Tv1dLevelSets3<float>(xt, vt, lam, S.len, S.count);
-    Transpose<float>(xt.as<float>(), x.as<float>(), S.count, S.len);
-  } else {
-    Transpose<double>(v.as<double>(), vt.as<double>(), S.len, S.count);
-    g_last_levels = Tv1dLevelSets3<double>(xt, vt, lam, S.len, S.count);
-    Transpose<double>(xt.as<double>(), x.as<double>(), S.count, S.len);
-  }
-  EPS_HIP(hipGetLastError());
+  return x.dt == F32 ? Tv1dSlices<float>(x, v, lam, S, contiguous) : Tv1dSlices<double>(x, v, lam, S, contiguous);
 }
 
 }  // namespace k

@@ -447,15 +447,9 @@ class TotalVariation1DProx final : public VectorProx {
  protected:
   void ApplyVector(const VectorProxInput& input, VectorProxOutput* output) override {
     const DVec& v = input.value_vec(0);
-    if (input.prox_function().has_axis) {  // every column / row is a chain of its own
-      const k::Segs S = SegsOf(input.prox_function(), 0, v.n);
-      DVec x = DVec::Empty(v.n, v.dt);
-      k::Tv1dSeg(x, v, input.lambda(), S);
-      output->set_value(0, x);
-      return;
-    }
+    // with an axis every column / row is a chain of its own, without one the whole argument is
     DVec x = DVec::Empty(v.n, v.dt);
-    k::Tv1d(x, v, input.lambda());
+    k::Tv1dSeg(x, v, input.lambda(), SegsOf(input.prox_function(), 0, v.n));
     output->set_value(0, x);
   }
 };

@@ -324,7 +324,8 @@ int eps_tv1d(const double* v, size_t n, double lam, double* x);
  * call waits for the device first, so v may come straight from the caller's streams): v, x are
  * device pointers to n elements of `kind`
  * (EPS_BLOB_DEVICE_F32 / EPS_BLOB_DEVICE_F64); *levels (may be NULL) receives the depth of the
- * level-set recursion.  Synchronises before returning. */
+ * level-set recursion of this call, 0 when the call is trivial (n <= 1 or lam == 0: x = v).
+ * Synchronises before returning. */
 int eps_tv1d_device(const void* v_dev, void* x_dev, size_t n, int kind, double lam, int* levels);
 
 /* The prox of `count` signals of `len` samples each in one pass: v and x hold the signals one
@@ -336,7 +337,8 @@ int eps_tv1d_batch(const double* v, size_t len, size_t count, double lam, double
 /* The same on device-resident data, with the conventions of eps_tv1d_device: v, x are device
  * pointers to len * count elements of `kind`, signal s at elements [s * len, (s + 1) * len);
  * *levels (may be NULL) receives the depth of the level-set recursion, the maximum over the
- * signals.  Synchronises before returning. */
+ * signals, 0 when the call is trivial (len <= 1, count == 0 or lam == 0).  Synchronises before
+ * returning. */
 int eps_tv1d_batch_device(const void* v_dev, void* x_dev, size_t len, size_t count, int kind, double lam,
                           int* levels);
 

@@ -1168,7 +1168,7 @@ def test_robust_pca_problem(solve_mod, dtype, n):
 
 @pytest.mark.parametrize("case", ["noise", "walk", "ties", "steps", "big", "tiny"])
 def test_tv1d_parallel_kernel(solve_mod, dtype, case):
-    """Exact parallel TV-1D prox (level-set divide and conquer, kernels_tv.hip) vs the DP
+    """Exact parallel TV-1D prox (level-set divide and conquer, kernels_tv3.hip) vs the DP
     oracle, plus the KKT certificate of SURVEY.md 8(c) on the device result."""
     from oracle import c_oracle
     rng = np.random.RandomState(11)

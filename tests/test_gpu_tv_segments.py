@@ -204,7 +204,7 @@ def test_batch_axis1_is_axis0_of_the_transpose(solve_mod, dtype, shape):
 
 def test_unsegmented_operator_is_untouched(solve_mod, dtype):
     """Check 5.  lam = 1 keeps every scaling of eval_prox exactly 1, so the operator hands
-    Tv1d the very input `tv1d` does."""
+    the prox the very input `tv1d` does."""
     rng = np.random.RandomState(2)
     V = rng.randn(40, 25)
     X = ir.variable(40, 25, "var:X")
@@ -292,3 +292,59 @@ def test_errors_are_raised_not_fatal(solve_mod):
         solve_mod.tv1d_batch(np.zeros(5), 1.0)
     # the library is still usable afterwards
     assert np.array_equal(solve_mod.tv1d_batch(np.full((3, 2), 1.0), 1.0), np.full((3, 2), 1.0))
+
+
+def device_levels(solve_mod, dtype, v, lam, length=None, count=None):
+    """(x, levels) of eps_tv1d_device, or of eps_tv1d_batch_device when length / count are given,
+    on a device copy of v."""
+    L = solve_mod.lib()
+    d = torch.from_numpy(np.ascontiguousarray(v)).to(torch.float32 if dtype == "f32" else torch.float64).to("cuda:0")
+    x = torch.zeros_like(d)
+    torch.cuda.synchronize()
+    lev = ctypes.c_int(-1)
+    kind = ctypes.c_int(1 if dtype == "f32" else 2)
+    pv, px = ctypes.c_void_p(d.data_ptr()), ctypes.c_void_p(x.data_ptr())
+    if length is None:
+        solve_mod._check(L.eps_tv1d_device(pv, px, ctypes.c_size_t(d.numel()), kind, ctypes.c_double(lam),
+                                           ctypes.byref(lev)))
+    else:
+        solve_mod._check(L.eps_tv1d_batch_device(pv, px, ctypes.c_size_t(length), ctypes.c_size_t(count), kind,
+                                                 ctypes.c_double(lam), ctypes.byref(lev)))
+    return x.cpu().numpy(), d.cpu().numpy(), lev.value
+
+
+def noisy_steps(n, seed):
+    rng = np.random.RandomState(seed)
+    return np.repeat(2.0 * rng.randn((n + 19) // 20), 20)[:n] + 0.3 * rng.randn(n)
+
+
+@pytest.mark.parametrize("n", [2, 63, 65, 2049, 524289])
+def test_single_signal_is_a_batch_of_one(solve_mod, dtype, n):
+    """One signal is the segmented prox with one slice: `tv1d`, a one-column batch and a one-row
+    batch give the same bytes, and the single and the batch device entry report the same depth.
+    63 and 65 straddle the width of the init kernel's lane group, 2049 is one tile plus a sample,
+    524289 the first size with more than 256 tiles (aggregate scans as launches of their own)."""
+    v, lam = noisy_steps(n, seed=n), 1.5
+    one = solve_mod.tv1d(v, lam)
+    col = solve_mod.tv1d_batch(v[:, None], lam, axis=0)
+    row = solve_mod.tv1d_batch(v[None, :], lam, axis=1)
+    assert col.shape == (n, 1) and row.shape == (1, n)
+    assert one.tobytes() == col.tobytes() == row.tobytes()
+    xs, _, lev_single = device_levels(solve_mod, dtype, v, lam)
+    xb, _, lev_batch = device_levels(solve_mod, dtype, v, lam, length=n, count=1)
+    assert xs.tobytes() == xb.tobytes() == one.astype(xs.dtype).tobytes()
+    assert lev_single == lev_batch and lev_single >= 1
+
+
+def test_trivial_calls_report_depth_zero(solve_mod, dtype):
+    """The depth belongs to the call: lam = 0 and n = 1 are copies and report 0 levels, whatever
+    the call before them reported."""
+    v = noisy_steps(300, seed=4)
+    _, _, lev = device_levels(solve_mod, dtype, v, 1.5)
+    assert lev >= 1
+    x, d, lev = device_levels(solve_mod, dtype, v, 0.0)
+    assert lev == 0 and np.array_equal(x, d)
+    _, _, lev = device_levels(solve_mod, dtype, v, 1.5)
+    assert lev >= 1
+    x, d, lev = device_levels(solve_mod, dtype, v[:1], 1.5)
+    assert lev == 0 and np.array_equal(x, d)

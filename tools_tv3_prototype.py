@@ -1,4 +1,4 @@
-"""CPU prototype of the three-threshold level-set recursion of kernels_tv.hip (round 3).
+"""CPU prototype of the three-threshold level-set recursion of kernels_tv3.hip (round 3).
 
 Same data flow as the device code - one state byte per sample, region records by head (hrec) and
 parent records by end (erec), the four passes of a level (clip forward scan, decode backward
