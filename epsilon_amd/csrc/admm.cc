@@ -382,6 +382,86 @@ class SweepGraph {
 };
 
 
+namespace {
+
+int BatchWideMin();  // (with the batched solves below)
+
+// Matrix variables X (n x k) under the data map I_k (x) A: the k columns run as k members of the
+// batched kernels inside one solve (ProxADMMSolver::TryEnableFused).  Below this many rows of A
+// the solve keeps the generic operator path (a constant: no crossover was measured).
+constexpr int64_t kMatrixFusedMinRows = 256;
+
+// EPSILON_HIP_FUSED_MATRIX (eps_set_option "fused_matrix"), read at every Init.
+enum MatrixRoute { kMatrixOff, kMatrixAuto, kMatrixPass, kMatrixWide };
+MatrixRoute FusedMatrixMode() {
+  const char* e = std::getenv("EPSILON_HIP_FUSED_MATRIX");
+  if (e == nullptr || std::strcmp(e, "auto") == 0) return kMatrixAuto;
+  if (std::strcmp(e, "0") == 0) return kMatrixOff;
+  if (std::strcmp(e, "pass") == 0) return kMatrixPass;
+  if (std::strcmp(e, "wide") == 0) return kMatrixWide;
+  EPS_FATAL("fused_matrix must be 0, pass, wide or auto, got " << e);
+}
+
+// One sweep of a panel of up to 64 f32 members on the wide route (kernels_fused_wide.hip): back
+// product + chain, forward product, reduction and - unless whitened - the cached inverse times
+// the panel.  The workspaces depend on (m, n) alone and serve every panel in turn.
+struct WideSweep {
+  static constexpr int PW = k::kLassoWidePanel;
+  int64_t m = 0, n = 0, lda = 0, ldv = 0, panel_len = 0;
+  DVec A;
+  bool whiten = false;
+  const DenseMatrixImpl* D = nullptr;  // the cached inverse (not whitened)
+  DVec V, T, apart;
+  int64_t akc = 0, afull = 0, arem = 0, aparts = 0;
+
+  void Init(int64_t m_, int64_t n_, const DVec& A_, int64_t lda_, bool whiten_, const DenseMatrixImpl* D_) {
+    m = m_;
+    n = n_;
+    A = A_;
+    lda = lda_;
+    whiten = whiten_;
+    D = D_;
+    ldv = (n + 63) / 64 * 64;
+    panel_len = static_cast<int64_t>(PW) * m;
+    V = DVec::Zeros(static_cast<int64_t>(PW) * ldv, F32);
+    T = DVec::Empty(static_cast<int64_t>(k::LassoWideSlabs(m, n)) * panel_len, F32);
+    // ranges of the inverse apply's contraction: at most 64, each a multiple of 32 rows
+    akc = std::max<int64_t>(32, ((m + 63) / 64 + 31) / 32 * 32);
+    afull = m / akc;
+    arem = m - afull * akc;
+    aparts = afull + (arem > 0 ? 1 : 0);
+    apart = whiten ? DVec() : DVec::Empty(aparts * panel_len, F32);
+  }
+
+  // Wp = Dinv Pp: always PW columns - the product kernel and its contraction order must not
+  // depend on the number of members.  The contraction is split into `aparts` ranges of `akc`
+  // rows whose products are summed by ReducePartials: one chain over all m rows would carry the
+  // rounding of an m-term sequential sum into w.
+  void ApplyInverse(const DVec& Pp, const DVec& Wp) const {
+    const int64_t sA = D->trans() ? akc : akc * D->rows();
+    k::GemmBatched(D->trans(), false, m, PW, akc, D->scale(), D->data(), D->rows(), sA, Pp, m, akc, 0.0, apart, m,
+                   panel_len, afull);
+    if (arem > 0) {
+      const int64_t oA = afull * sA, oB = afull * akc;
+      k::GemmBatched(D->trans(), false, m, PW, arem, D->scale(), D->data().Slice(oA, D->data().n - oA), D->rows(),
+                     0, Pp.Slice(oB, Pp.n - oB), m, 0, 0.0, apart.Slice(afull * panel_len, panel_len), m, 0, 1);
+    }
+    k::ReducePartials(panel_len, static_cast<int>(aparts), apart, 1.0, 0.0, Wp);
+  }
+
+  // slots [first, first + nk) of `table`, `live` as LassoWideBack's mask; Wp / Pp: the panel's w
+  // and p (Pp unused when whitened: the reduction writes w_hat into Wp through the descriptors)
+  void Run(const DVec& table, int first, int nk, uint64_t live, const DVec& Wp, const DVec& Pp,
+           const double* group_lam = nullptr) const {
+    k::LassoWideBack(m, n, lda, A, table, first, nk, live, Wp, m, V, ldv, group_lam);
+    k::LassoWideForward(m, n, lda, A, nk, V, ldv, T, m);
+    k::LassoWideReduce(m, n, table, first, nk, live, T, m);
+    if (!whiten) ApplyInverse(Pp, Wp);
+  }
+};
+
+}  // namespace
+
 // ---------------------------------------------------------------------------------------------------
 // ProxADMMSolver (reference algorithms/prox_admm.cc)
 // ---------------------------------------------------------------------------------------------------
@@ -444,6 +524,7 @@ class ProxADMMSolver final : public Solver {
   bool BatchView(k::LassoInstance* mem, std::vector<uint64_t>* key) const {
     if (!initialized_ || finished_ || iter_ != 0 || !fused_ || fs_.use_peer || ShardSpec::Get().active()) return false;
     const FusedState& f = fs_;
+    if (f.cols > 1) return false;  // a matrix variable is a batch of its own: it runs alone
     const DenseMatrixImpl& L = *f.ls.L_arg_var;
     const DenseMatrixImpl& D = *f.ls.Dinv_arg;
     const DType dt = data_->dtype();
@@ -583,7 +664,23 @@ class ProxADMMSolver final : public Solver {
     // consensus form: the threshold step averages over the ranks, which the fused pass does not
     if (ShardSpec::Get().active() && ShardSpec::Get().consensus_terms()) return;
     FusedState f;
-    if (!prox_[0]->DescribeLeastSquares(&f.ls) || !prox_[1]->DescribeScaledZone(&f.sz)) return;
+    if (!prox_[0]->DescribeLeastSquares(&f.ls)) return;
+    f.cols = f.ls.cols;
+    const MatrixRoute matrix_mode = f.cols > 1 ? FusedMatrixMode() : kMatrixAuto;
+    if (f.cols > 1 && (matrix_mode == kMatrixOff || ShardSpec::Get().active())) return;
+    if (!prox_[1]->DescribeScaledZone(&f.sz)) {
+      // group lasso: one group per row of the n x cols variable
+      GroupNorm2Desc gn;
+      if (f.cols == 1 || !prox_[1]->DescribeGroupNorm2(&gn) || gn.cols != f.cols) return;
+      f.group = true;
+      f.group_rows = gn.rows;
+      f.sz = ScaledZoneDesc();
+      f.sz.var_key = gn.var_key;
+      f.sz.constraint_key = gn.constraint_key;
+      f.sz.Bs = gn.Bs;
+      f.sz.Cs = gn.Cs;
+      f.sz.lam = gn.lam;
+    }
     if ((f.sz.alpha_vec.n > 0 && f.sz.alpha_vec.dt != data_->dtype()) ||
         (f.sz.beta_vec.n > 0 && f.sz.beta_vec.dt != data_->dtype()))
       return;
@@ -600,19 +697,21 @@ class ProxADMMSolver final : public Solver {
     if (L.trans()) return;
     f.m = L.rows();
     f.n = L.cols();
-    if (A0.impl().n() != f.n || A1.impl().n() != f.n) return;
+    const int64_t nx = f.n * f.cols;  // entries of the variable (a matrix variable: column c at c * n)
+    if (A0.impl().n() != nx || A1.impl().n() != nx) return;
     if (!k::LassoFusedSupported(f.m, f.n, L.data(), L.rows())) return;
-    if (f.ls.rhs_arg.n != 0 && f.ls.rhs_arg.n != f.m) return;
+    if (f.ls.rhs_arg.n != 0 && f.ls.rhs_arg.n != f.m * f.cols) return;
     const DType dt = data_->dtype();
+    if (f.cols > 1 && !ChooseMatrixRoute(&f, matrix_mode)) return;
     // the six state vectors are slices of ONE buffer, so that a residual check can snapshot the
     // iterates with a single copy (pipelined checks, Solver::Run)
-    const int64_t npad = (f.n + 63) / 64 * 64;
+    const int64_t npad = (nx + 63) / 64 * 64;
     f.state_all = DVec::Zeros(6 * npad, dt);
     f.snapshot = DVec::Empty(6 * npad, dt);
     f.norm_work = DVec::Zeros(64 * 5 + 1, F64);
     int next_slice = 0;
     auto state = [&](const BlockVector& src, const std::string& key) {
-      DVec v = f.state_all.Slice(static_cast<int64_t>(next_slice++) * npad, f.n);
+      DVec v = f.state_all.Slice(static_cast<int64_t>(next_slice++) * npad, nx);
       if (src.has_key(key)) k::Copy(v, src(key));
       return v;
     };
@@ -622,10 +721,15 @@ class ProxADMMSolver final : public Solver {
     f.y1 = state(y_[1], ck);
     f.u = state(u_, ck);
     f.y1prev = state(BlockVector(), ck);
-    f.p = DVec::Zeros(f.m, dt);
     f.grid = k::LassoFusedGrid(f.m, f.n, dt);
-    f.tpart = DVec::Empty(static_cast<int64_t>(f.grid) * f.m, dt);
-    {
+    // a matrix variable: column c's p and w at c * m (the wide route's instance-major panels,
+    // whole panels of 64), its partials at c * grid * m
+    const int64_t wlen = f.wide ? (f.cols + WideSweep::PW - 1) / WideSweep::PW * WideSweep::PW * f.m : f.cols * f.m;
+    f.p = DVec::Zeros(wlen, dt);
+    if (!f.wide) f.tpart = DVec::Empty(static_cast<int64_t>(f.grid) * f.m * f.cols, dt);
+    if (f.cols > 1) {
+      f.w = DVec::Zeros(wlen, dt);
+    } else {
       Comm* comm = Runtime::Get().comm();
       PeerExchange* px = Runtime::Get().peer();
       const ShardSpec& sh = ShardSpec::Get();
@@ -651,8 +755,10 @@ class ProxADMMSolver final : public Solver {
       const DenseMatrixImpl& D = *f.ls.Dinv_arg;
       if (!f.use_peer && !ShardSpec::Get().active() && EnableWhiten(&f)) {
         // no inverse apply in the sweep: no workspace, no packed copy
+      } else if (f.wide) {
+        // the inverse times the panel is a product of its own (WideSweep::ApplyInverse)
       } else if (D.symmetric() && D.rows() == f.m && D.rows() >= 1024 && !D.trans()) {
-        f.symv_work = DVec::Empty(k::SymvWorkspace(f.m), dt);
+        f.symv_work = DVec::Empty(f.cols * k::SymvWorkspace(f.m), dt);
         // the apply reads a tile-packed copy of the lower tiles (EPSILON_HIP_SYMV_PACKED=0: the
         // matrix as it lies): +m^2/2 values of memory for a tenth of a millisecond at Init
         static const bool packed = [] {
@@ -662,6 +768,7 @@ class ProxADMMSolver final : public Solver {
         if (packed) f.symv_packed = PackInverse(D, f.m);
       }
     }
+    if (f.wide) f.ws.Init(f.m, f.n, f.whiten ? f.Ahat : L.data(), f.whiten ? f.m : L.rows(), f.whiten, f.ls.Dinv_arg.get());
     ResetGraph();
     fs_ = f;
     BuildPass();
@@ -680,6 +787,27 @@ class ProxADMMSolver final : public Solver {
     y_prev_[1].Set(ck, fs_.y1prev);
     fused_ = true;
     FusedForward(/*from_state=*/true);
+  }
+
+  // Route of a matrix-variable solve: the batched pass (f32 / f64) or the wide
+  // kernels (f32).  The group threshold needs all columns in one launch (pass) or one panel (wide).
+  bool ChooseMatrixRoute(FusedState* f, MatrixRoute mode) {
+    const DenseMatrixImpl& L = *f->ls.L_arg_var;
+    const DenseMatrixImpl& D = *f->ls.Dinv_arg;
+    const DType dt = data_->dtype();
+    if (f->m < kMatrixFusedMinRows || L.dtype() != dt || D.dtype() != dt) return false;
+    if (f->group && f->group_rows != f->n) return false;
+    if (f->sz.alpha_vec.n > 0 && f->sz.alpha_vec.n != f->n * f->cols) return false;
+    if (f->sz.beta_vec.n > 0 && f->sz.beta_vec.n != f->n * f->cols) return false;
+    if (D.rows() != f->m || D.cols() != f->m) return false;
+    const int width = k::LassoBatchWidth(f->m, f->n, dt);
+    const bool pass_ok = width > 0 && (!f->group || f->cols <= width);
+    const bool wide_ok = dt == F32 && k::LassoWideSupported(f->m, f->n, L.data(), L.rows()) &&
+                         (!f->group || f->cols <= WideSweep::PW);
+    if (mode == kMatrixPass) f->wide = false;
+    else if (mode == kMatrixWide) f->wide = true;
+    else f->wide = wide_ok && (f->cols >= BatchWideMin() || !pass_ok);
+    return f->wide ? wide_ok : pass_ok;
   }
 
   // The whitened route.  With Dinv_arg = c X^T X, where X = L^-1 is the inverse Cholesky factor
@@ -721,7 +849,10 @@ class ProxADMMSolver final : public Solver {
     }
     if (!k::LassoFusedSupported(f->m, f->n, Ahat, f->m)) return false;
     // X rhs on every Init: parameters re-bind the rhs
-    if (f->ls.rhs_arg.n != 0) {
+    if (f->ls.rhs_arg.n != 0 && f->cols > 1) {  // all columns in one product
+      f->rhat = DVec::Empty(f->m * f->cols, F32);
+      k::Gemm(false, false, f->m, f->cols, f->m, 1.0, X->data(), f->m, f->ls.rhs_arg, f->m, 0.0, f->rhat, f->m);
+    } else if (f->ls.rhs_arg.n != 0) {
       f->rhat = DVec::Empty(f->m, F32);
       k::Gemv(false, f->m, f->m, 1.0, X->data(), f->m, f->ls.rhs_arg, 0.0, f->rhat);
     }
@@ -751,6 +882,25 @@ class ProxADMMSolver final : public Solver {
   void FusedForward(bool from_state) {
     FusedState& f = fs_;
     const DenseMatrixImpl& L = *f.ls.L_arg_var;
+    if (f.cols > 1) {
+      EPS_CHECK(from_state);  // (a sweep's own tail: MatrixSweep)
+      // column by column what the vector form does below
+      DVec v0 = f.u.Clone();
+      k::Axpby(v0, -1.0, f.y0, 1.0);
+      k::Axpby(v0, -1.0, f.y1, 1.0);
+      k::Axpby(v0, 1.0, f.y0, 1.0);
+      const int64_t mk = f.m * f.cols;
+      DVec p = f.whiten ? DVec::Empty(mk, v0.dt) : f.p.Slice(0, mk);
+      for (int64_t c = 0; c < f.cols; ++c) L.Apply(-1.0, v0.Slice(c * f.n, f.n), 0.0, p.Slice(c * f.m, f.m));
+      if (f.ls.rhs_arg.n != 0) k::Axpby(p, 1.0, f.ls.rhs_arg, 1.0);
+      if (f.whiten) {
+        for (int64_t c = 0; c < f.cols; ++c)
+          k::Gemv(false, f.m, f.m, 1.0, f.X, f.m, p.Slice(c * f.m, f.m), 0.0, f.w.Slice(c * f.m, f.m));
+      } else {
+        ApplyInverseFixed();
+      }
+      return;
+    }
     if (f.whiten) {
       if (from_state) {
         // w_hat = X (rhs - L v0) once, from the current state
@@ -838,6 +988,25 @@ class ProxADMMSolver final : public Solver {
   void ApplyInverseFixed() {
     FusedState& f = fs_;
     const DenseMatrixImpl& D = *f.ls.Dinv_arg;
+    if (f.wide) {
+      for (int64_t q = 0; q * f.ws.panel_len < f.w.n; ++q)
+        f.ws.ApplyInverse(f.p.Slice(q * f.ws.panel_len, f.ws.panel_len), f.w.Slice(q * f.ws.panel_len, f.ws.panel_len));
+      return;
+    }
+    if (f.cols > 1 && f.symv_packed.n > 0) {
+      k::SymvPackedBatch(f.m, D.scale(), f.symv_packed, f.table, static_cast<int>(f.cols), f.symv_work);
+      return;
+    }
+    for (int64_t c = 0; f.cols > 1 && c < f.cols; ++c) {
+      DVec pc = f.p.Slice(c * f.m, f.m), wc = f.w.Slice(c * f.m, f.m);
+      if (f.symv_work.n > 0) {
+        DVec work = f.symv_work.Slice(c * k::SymvWorkspace(f.m), k::SymvWorkspace(f.m));
+        k::Symv(f.m, D.scale(), D.data(), f.m, pc, 0.0, wc, &work);
+      } else {
+        D.Apply(1.0, pc, 0.0, wc);
+      }
+    }
+    if (f.cols > 1) return;
     if (f.symv_packed.n > 0) k::SymvPacked(f.m, D.scale(), f.symv_packed, f.p, 0.0, f.w, &f.symv_work);
     else if (f.symv_work.n > 0) k::Symv(f.m, D.scale(), D.data(), f.m, f.p, 0.0, f.w, &f.symv_work);
     else D.Apply(1.0, f.p, 0.0, f.w);
@@ -883,7 +1052,7 @@ class ProxADMMSolver final : public Solver {
     if (GenericGraphWanted(count) && gg_.Run(count, StateHandles(), static_cast<size_t>(N_), [this] { Sweep(); })) return;
     const ShardSpec& sh = ShardSpec::Get();
     const bool rccl_in_sweep = fused_ && !fs_.use_peer && sh.active() && sh.IsSharded(fs_.ls.var_key);
-    const bool fixed_buffers = (fs_.use_peer && fs_.peer_slab) || fs_.symv_work.n > 0 || fs_.whiten;
+    const bool fixed_buffers = (fs_.use_peer && fs_.peer_slab) || fs_.symv_work.n > 0 || fs_.whiten || fs_.wide;
     const bool want = fused_ && !rccl_in_sweep && fixed_buffers &&
                       (mode == 1 || (mode != 0 && fs_.use_peer));
     if (!want || count < 2 || rt.profiling()) {
@@ -946,10 +1115,59 @@ class ProxADMMSolver final : public Solver {
     s.alpha = f.sz.alpha;
     s.beta = f.sz.beta;
     s.M = f.sz.M;
+    if (f.cols == 1) return;
+    // a matrix variable: column c is member c, the slices of `inst` at its offsets; the table is
+    // uploaded here, so that a sweep makes no upload and no host synchronisation
+    f.members.assign(static_cast<size_t>(f.cols), s);
+    f.rhs_aligned = true;
+    for (int64_t c = 0; c < f.cols; ++c) {
+      k::LassoInstance& mb = f.members[static_cast<size_t>(c)];
+      auto col = [&](const DVec& v, int64_t len) { return v.n > 0 ? v.Slice(c * len, len) : v; };
+      mb.w = col(s.w, f.m);
+      mb.p = col(s.p, f.m);
+      mb.rhs = col(s.rhs, f.m);
+      if (!f.wide) mb.tpart = col(s.tpart, static_cast<int64_t>(f.grid) * f.m);
+      else mb.tpart = mb.w;  // (not read on the wide route: its partials are panels of WideSweep)
+      for (DVec k::LassoInstance::*v : {&k::LassoInstance::u, &k::LassoInstance::x0, &k::LassoInstance::x1,
+                                       &k::LassoInstance::y0, &k::LassoInstance::y1, &k::LassoInstance::y1prev,
+                                       &k::LassoInstance::alpha_vec, &k::LassoInstance::beta_vec})
+        mb.*v = col(s.*v, f.n);
+      if (mb.rhs.n > 0) f.rhs_aligned = f.rhs_aligned && reinterpret_cast<uintptr_t>(mb.rhs.data()) % 16 == 0;
+    }
+    std::vector<const k::LassoInstance*> v;
+    for (const auto& mb : f.members) v.push_back(&mb);
+    k::LassoBatchUpload(v, data_->dtype(), &f.table);
+  }
+
+  // A matrix variable's sweep: its columns through the batched or the wide kernels.
+  void MatrixSweep() {
+    FusedState& f = fs_;
+    const int K = static_cast<int>(f.cols);
+    const double* group_lam = f.group ? &f.sz.lam : nullptr;
+    if (f.wide) {
+      constexpr int PW = WideSweep::PW;
+      for (int first = 0; first < K; first += PW) {
+        const int nk = std::min(PW, K - first);
+        const uint64_t live = nk == 64 ? ~uint64_t(0) : (uint64_t(1) << nk) - 1;
+        const int64_t off = static_cast<int64_t>(first) * f.m;
+        f.ws.Run(f.table, first, nk, live, f.w.Slice(off, f.ws.panel_len),
+                 f.whiten ? DVec() : f.p.Slice(off, f.ws.panel_len), group_lam);
+      }
+      return;
+    }
+    const int width = k::LassoBatchWidth(f.m, f.n, data_->dtype());
+    for (int first = 0; first < K; first += width)
+      k::LassoBatchPass(f.m, f.n, f.pass.lda, f.pass.A, f.table, first, std::min(width, K - first), group_lam);
+    k::ReducePartialsBatch(f.m, f.grid, f.table, K, data_->dtype(), f.rhs_aligned);
+    if (!f.whiten) ApplyInverseFixed();
   }
 
   void FusedSweep() {
     FusedState& f = fs_;
+    if (f.cols > 1) {
+      MatrixSweep();
+      return;
+    }
     if (f.use_peer) {
       f.pass.epoch = Runtime::Get().peer()->view().epoch;
       k::LassoFusedPass(f.pass);
@@ -1117,6 +1335,15 @@ class ProxADMMSolver final : public Solver {
     double wscale = 1;         // c of Dinv_arg = c X^T X
     DVec X, Ahat, rhat;        // L^-1 of the inverse, X A (ld m), X rhs_arg (empty: no rhs)
     k::LassoFusedArgs pass;    // what the pass and a batch read of all this (BuildPass)
+    // matrix variable (n x cols under I_cols (x) A): its columns are members of the batched kernels
+    int64_t cols = 1;
+    bool group = false;      // the threshold is the group shrinkage of the rows (weight sz.lam)
+    int64_t group_rows = 0;
+    bool wide = false;       // the wide route (f32): w and p are whole panels of 64 members
+    bool rhs_aligned = true;
+    std::vector<k::LassoInstance> members;
+    DVec table;              // their descriptors on the device (LassoBatchUpload)
+    WideSweep ws;
   };
   bool fused_ = false;
   FusedState fs_;
@@ -1236,6 +1463,7 @@ class ProxADMMTwoBlockSolver final : public Solver {
     if (!constr_H_.b.data().empty()) return;
     FusedState f;
     if (!prox_[0]->DescribeLeastSquares(&f.ls) || !prox_[1]->DescribeScaledZone(&f.sz)) return;
+    if (f.ls.cols != 1) return;  // matrix variables: the multi-block driver only
     if (f.ls.var_key == f.sz.var_key) return;
     const std::string ck = affine::constraint_key(0);
     const BlockMatrix& H = constr_H_.A;
@@ -1522,16 +1750,15 @@ void RunWideGroup(const std::vector<ProxADMMSolver*>& g, const std::vector<k::La
   const bool whiten = lead.batch_whitened();
   const DenseMatrixImpl& D = lead.batch_inverse();
   const int K = static_cast<int>(g.size());
-  constexpr int PW = k::kLassoWidePanel;
+  constexpr int PW = WideSweep::PW;
   const int npanels = (K + PW - 1) / PW;
-  const int64_t ldv = (n + 63) / 64 * 64;
-  const int64_t panel_len = static_cast<int64_t>(PW) * m;
+  WideSweep ws;
+  ws.Init(m, n, A, lda, whiten, &D);
+  const int64_t panel_len = ws.panel_len;
 
   std::vector<k::LassoInstance> mem = mem_in;
   DVec Wall = DVec::Zeros(npanels * panel_len, F32);
   DVec Pall = whiten ? DVec() : DVec::Zeros(npanels * panel_len, F32);
-  DVec V = DVec::Zeros(static_cast<int64_t>(PW) * ldv, F32);
-  DVec T = DVec::Empty(static_cast<int64_t>(k::LassoWideSlabs(m, n)) * panel_len, F32);
   for (int i = 0; i < K; ++i) {
     for (const DVec* v : {&mem[i].u, &mem[i].x0, &mem[i].x1, &mem[i].y0, &mem[i].y1, &mem[i].y1prev})
       EPS_CHECK_MSG(reinterpret_cast<uintptr_t>(v->data()) % 16 == 0, "wide batch: unaligned state vector");
@@ -1540,10 +1767,6 @@ void RunWideGroup(const std::vector<ProxADMMSolver*>& g, const std::vector<k::La
     mem[i].w = slot;
     mem[i].p = whiten ? slot : Pall.Slice(static_cast<int64_t>(i) * m, m);
   }
-  // ranges of the inverse apply's contraction: at most 64, each a multiple of 32 rows
-  const int64_t akc = std::max<int64_t>(32, ((m + 63) / 64 + 31) / 32 * 32);
-  const int64_t afull = m / akc, arem = m - afull * akc, aparts = afull + (arem > 0 ? 1 : 0);
-  DVec apart = whiten ? DVec() : DVec::Empty(aparts * panel_len, F32);
   DVec table;
   {
     std::vector<const k::LassoInstance*> v;
@@ -1560,26 +1783,8 @@ void RunWideGroup(const std::vector<ProxADMMSolver*>& g, const std::vector<k::La
     for (int p = 0; p < npanels; ++p) {
       if (live[p] == 0) continue;
       const int first = p * PW, nk = std::min(PW, K - first);
-      DVec Wp = Wall.Slice(p * panel_len, panel_len);
-      k::LassoWideBack(m, n, lda, A, table, first, nk, live[p], Wp, m, V, ldv);
-      k::LassoWideForward(m, n, lda, A, nk, V, ldv, T, m);
-      k::LassoWideReduce(m, n, table, first, nk, live[p], T, m);
-      // The cached inverse times the whole panel, always PW columns: the product kernel and its
-      // contraction order must not depend on the number of members.  The contraction is split
-      // into `aparts` ranges of `akc` rows whose products are summed by ReducePartials: one
-      // chain over all m rows would carry the rounding of an m-term sequential sum into w.
-      if (!whiten) {
-        DVec Pp = Pall.Slice(p * panel_len, panel_len);
-        const int64_t sA = D.trans() ? akc : akc * D.rows();
-        k::GemmBatched(D.trans(), false, m, PW, akc, D.scale(), D.data(), D.rows(), sA, Pp, m, akc, 0.0, apart, m,
-                       panel_len, afull);
-        if (arem > 0) {
-          const int64_t oA = afull * sA, oB = afull * akc;
-          k::GemmBatched(D.trans(), false, m, PW, arem, D.scale(), D.data().Slice(oA, D.data().n - oA), D.rows(), 0,
-                         Pp.Slice(oB, Pp.n - oB), m, 0, 0.0, apart.Slice(afull * panel_len, panel_len), m, 0, 1);
-        }
-        k::ReducePartials(panel_len, static_cast<int>(aparts), apart, 1.0, 0.0, Wp);
-      }
+      ws.Run(table, first, nk, live[p], Wall.Slice(p * panel_len, panel_len),
+             whiten ? DVec() : Pall.Slice(p * panel_len, panel_len));
     }
   };
   // frozen: their slots are masked from here on

@@ -119,8 +119,11 @@ int LassoBatchWidth(int64_t m, int64_t n, DType dt);
 void LassoBatchUpload(const std::vector<const LassoInstance*>& members, DType dt, DVec* table);
 // The fused pass of instances [first, first + count) of `table`, count <= LassoBatchWidth: each
 // loaded column of A feeds every instance's dot product, chain and forward update.
+// `group_lam` (optional): the instances are ALL the columns of one matrix variable and the
+// threshold step is the group shrinkage of its rows with this weight (NORM_2 along axis 1)
+// instead of each instance's scaled zone.
 void LassoBatchPass(int64_t m, int64_t n, int64_t lda, const DVec& A, const DVec& table, int first,
-                    int count);
+                    int count, const double* group_lam = nullptr);
 // p = pkappa * sum(tpart) (+ rhs) of `count` instances in one launch, each in the summation order
 // of ReducePartials(m, nparts, tpart, pkappa, 0, p, rhs).  `rhs_aligned`: every rhs present is
 // 16-byte aligned (picks the same kernel form as the single call).
@@ -145,8 +148,11 @@ bool LassoWideSupported(int64_t m, int64_t n, const DVec& A, int64_t lda);
 // Column slabs of the forward product: a function of (m, n) alone.
 int LassoWideSlabs(int64_t m, int64_t n);
 // D = A^T W and the chain of every live slot: updates its x0, x1, y0, y1, u, y1prev and writes V.
+// `group_lam` (optional): the nk slots are all the columns of one matrix variable, all live, and
+// the threshold step is the group shrinkage of its rows with this weight (as LassoBatchPass).
 void LassoWideBack(int64_t m, int64_t n, int64_t lda, const DVec& A, const DVec& table, int first, int nk,
-                   uint64_t active, const DVec& W, int64_t ldw, const DVec& V, int64_t ldv);
+                   uint64_t active, const DVec& W, int64_t ldw, const DVec& V, int64_t ldv,
+                   const double* group_lam = nullptr);
 // T_s = A[:, slab s] V[slab s, :] for every slab s.
 void LassoWideForward(int64_t m, int64_t n, int64_t lda, const DVec& A, int nk, const DVec& V, int64_t ldv,
                       const DVec& T, int64_t ldt);

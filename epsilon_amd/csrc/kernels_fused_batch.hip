@@ -29,11 +29,14 @@ namespace {
 
 constexpr int kBlock = 256;
 
-template <class T, int NR, int KB>
+// GROUP: the nk instances are the columns of ONE matrix variable and the threshold is the group
+// shrinkage of its rows (NORM_2 along axis 1, weight glam): row j's nk threshold inputs are what
+// the pass computes for column j of A, and after the barrier every thread holds all of them.
+template <class T, int NR, int KB, bool GROUP>
 __global__ __launch_bounds__(kBlock) void LassoBatchStreamKernel(int64_t m, int64_t n, const T* __restrict__ A,
                                                                  int64_t lda,
                                                                  const LassoBatchInst<T>* __restrict__ tab,
-                                                                 int nk) {
+                                                                 int nk, double glam) {
   typedef typename Chunk<T>::V V;
   constexpr int R = Chunk<T>::R;
   __shared__ T red[2][KB][kBlock / 64];
@@ -93,36 +96,82 @@ __global__ __launch_bounds__(kBlock) void LassoBatchStreamKernel(int64_t m, int6
       if (lane == 0) red[par][i][wave] = d;
     }
     __syncthreads();
+    if constexpr (GROUP) {
+      auto scalars = [&](int i) {
+        const LassoBatchInst<T>& I = tab[i];
+        FusedScalarsT<T> c;
+        c.kappa = I.kappa;
+        c.Bs = I.Bs;
+        c.Cs = I.Cs;
+        c.a1 = I.a1;
+        c.lam = c.alpha = c.beta = c.M = T(0);  // (the scaled zone's: not read)
+        return c;
+      };
+      ChainHeadT<T> h[KB];
+      double ss = 0;
 #pragma unroll
-    for (int i = 0; i < KB; ++i) {
-      if (i >= nk) continue;
-      const LassoBatchInst<T>& I = tab[i];
-      T d = red[par][i][0];
+      for (int i = 0; i < KB; ++i) {
+        if (i >= nk) continue;
+        T d = red[par][i][0];
 #pragma unroll
-      for (int w2 = 1; w2 < kBlock / 64; ++w2) d += red[par][i][w2];
-      FusedScalarsT<T> c;
-      c.kappa = I.kappa;
-      c.Bs = I.Bs;
-      c.Cs = I.Cs;
-      c.a1 = I.a1;
-      c.lam = I.lam;
-      c.alpha = I.alpha_v != nullptr ? I.alpha_v[j] : I.alpha;
-      c.beta = I.beta_v != nullptr ? I.beta_v[j] : I.beta;
-      c.M = I.M;
-      T nx0, nx1, ny0, ny1, nu;
-      const T v0n = ChainOneT<T>(d, c, uj[i], y0j[i], y1j[i], &nx0, &nx1, &ny0, &ny1, &nu);
-      if (tid == 0) {
-        I.y1prev[j] = y1j[i];
-        I.x0[j] = nx0;
-        I.x1[j] = nx1;
-        I.y0[j] = ny0;
-        I.y1[j] = ny1;
-        I.u[j] = nu;
+        for (int w2 = 1; w2 < kBlock / 64; ++w2) d += red[par][i][w2];
+        h[i] = ChainHeadOfT<T>(d, scalars(i), uj[i], y0j[i], y1j[i]);
+        const double v = static_cast<double>(h[i].vin);
+        ss += v * v;
       }
+      const double scale = GroupScale(ss, glam);
 #pragma unroll
-      for (int q = 0; q < NR; ++q)
+      for (int i = 0; i < KB; ++i) {
+        if (i >= nk) continue;
+        const LassoBatchInst<T>& I = tab[i];
+        const T xz = static_cast<T>(scale * static_cast<double>(h[i].vin));
+        T nx0, nx1, ny0, ny1, nu;
+        const T v0n = ChainTailT<T>(h[i], xz, scalars(i), &nx0, &nx1, &ny0, &ny1, &nu);
+        if (tid == 0) {
+          I.y1prev[j] = y1j[i];
+          I.x0[j] = nx0;
+          I.x1[j] = nx1;
+          I.y0[j] = ny0;
+          I.y1[j] = ny1;
+          I.u[j] = nu;
+        }
 #pragma unroll
-        for (int r = 0; r < R; ++r) tp[i][q][r] += cur[q][r] * v0n;
+        for (int q = 0; q < NR; ++q)
+#pragma unroll
+          for (int r = 0; r < R; ++r) tp[i][q][r] += cur[q][r] * v0n;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < KB; ++i) {
+        if (i >= nk) continue;
+        const LassoBatchInst<T>& I = tab[i];
+        T d = red[par][i][0];
+#pragma unroll
+        for (int w2 = 1; w2 < kBlock / 64; ++w2) d += red[par][i][w2];
+        FusedScalarsT<T> c;
+        c.kappa = I.kappa;
+        c.Bs = I.Bs;
+        c.Cs = I.Cs;
+        c.a1 = I.a1;
+        c.lam = I.lam;
+        c.alpha = I.alpha_v != nullptr ? I.alpha_v[j] : I.alpha;
+        c.beta = I.beta_v != nullptr ? I.beta_v[j] : I.beta;
+        c.M = I.M;
+        T nx0, nx1, ny0, ny1, nu;
+        const T v0n = ChainOneT<T>(d, c, uj[i], y0j[i], y1j[i], &nx0, &nx1, &ny0, &ny1, &nu);
+        if (tid == 0) {
+          I.y1prev[j] = y1j[i];
+          I.x0[j] = nx0;
+          I.x1[j] = nx1;
+          I.y0[j] = ny0;
+          I.y1[j] = ny1;
+          I.u[j] = nu;
+        }
+#pragma unroll
+        for (int q = 0; q < NR; ++q)
+#pragma unroll
+          for (int r = 0; r < R; ++r) tp[i][q][r] += cur[q][r] * v0n;
+      }
     }
     par ^= 1;
 #pragma unroll
@@ -153,20 +202,25 @@ int ChunksPerThread(int64_t m, DType dt) {
 constexpr int WidthFor(int nr) { return nr <= 2 ? 8 : nr <= 4 ? 6 : nr <= 8 ? 5 : 4; }
 
 template <class T, int NR>
-void LaunchBatch(int grid, int64_t m, int64_t n, const T* A, int64_t lda, const LassoBatchInst<T>* tab, int nk) {
-  hipLaunchKernelGGL((LassoBatchStreamKernel<T, NR, WidthFor(NR)>), dim3(grid), dim3(kBlock), 0,
-                     Runtime::Get().stream(), m, n, A, lda, tab, nk);
+void LaunchBatch(int grid, int64_t m, int64_t n, const T* A, int64_t lda, const LassoBatchInst<T>* tab, int nk,
+                 const double* glam) {
+  if (glam != nullptr)
+    hipLaunchKernelGGL((LassoBatchStreamKernel<T, NR, WidthFor(NR), true>), dim3(grid), dim3(kBlock), 0,
+                       Runtime::Get().stream(), m, n, A, lda, tab, nk, *glam);
+  else
+    hipLaunchKernelGGL((LassoBatchStreamKernel<T, NR, WidthFor(NR), false>), dim3(grid), dim3(kBlock), 0,
+                       Runtime::Get().stream(), m, n, A, lda, tab, nk, 0.0);
 }
 
 template <class T>
 void LaunchBatchT(int nr, int grid, int64_t m, int64_t n, const T* A, int64_t lda, const LassoBatchInst<T>* tab,
-                  int nk) {
+                  int nk, const double* glam) {
   switch (nr) {
-    case 1: LaunchBatch<T, 1>(grid, m, n, A, lda, tab, nk); break;
-    case 2: LaunchBatch<T, 2>(grid, m, n, A, lda, tab, nk); break;
-    case 4: LaunchBatch<T, 4>(grid, m, n, A, lda, tab, nk); break;
-    case 8: LaunchBatch<T, 8>(grid, m, n, A, lda, tab, nk); break;
-    default: LaunchBatch<T, 10>(grid, m, n, A, lda, tab, nk); break;
+    case 1: LaunchBatch<T, 1>(grid, m, n, A, lda, tab, nk, glam); break;
+    case 2: LaunchBatch<T, 2>(grid, m, n, A, lda, tab, nk, glam); break;
+    case 4: LaunchBatch<T, 4>(grid, m, n, A, lda, tab, nk, glam); break;
+    case 8: LaunchBatch<T, 8>(grid, m, n, A, lda, tab, nk, glam); break;
+    default: LaunchBatch<T, 10>(grid, m, n, A, lda, tab, nk, glam); break;
   }
 }
 
@@ -199,7 +253,8 @@ void LassoBatchUpload(const std::vector<const LassoInstance*>& members, DType dt
   else UploadT<double>(members, table);
 }
 
-void LassoBatchPass(int64_t m, int64_t n, int64_t lda, const DVec& A, const DVec& table, int first, int count) {
+void LassoBatchPass(int64_t m, int64_t n, int64_t lda, const DVec& A, const DVec& table, int first, int count,
+                    const double* group_lam) {
   const DType dt = A.dt;
   EPS_CHECK(LassoFusedSupported(m, n, A, lda));
   const int width = LassoBatchWidth(m, n, dt);
@@ -210,10 +265,10 @@ void LassoBatchPass(int64_t m, int64_t n, int64_t lda, const DVec& A, const DVec
   ProfScope prof("batch_fused_pass", m, n);
   if (dt == F32)
     LaunchBatchT<float>(nr, grid, m, n, A.as<float>(), lda,
-                        reinterpret_cast<const LassoBatchInst<float>*>(table.as<char>()) + first, count);
+                        reinterpret_cast<const LassoBatchInst<float>*>(table.as<char>()) + first, count, group_lam);
   else
     LaunchBatchT<double>(nr, grid, m, n, A.as<double>(), lda,
-                         reinterpret_cast<const LassoBatchInst<double>*>(table.as<char>()) + first, count);
+                         reinterpret_cast<const LassoBatchInst<double>*>(table.as<char>()) + first, count, group_lam);
   EPS_HIP(hipGetLastError());
 }
 

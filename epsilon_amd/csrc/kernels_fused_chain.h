@@ -80,10 +80,13 @@ template <class T> __device__ inline T ScaledZoneOneT(T xi, T lam, T alpha, T be
   return -M;
 }
 
-// One column's elementwise chain.  Returns v0' (input of the next sweep's forward pass).
+// One column's elementwise chain in two halves around the threshold step, so that a threshold
+// that couples several instances (GroupShrinkT) can sit between them.
+template <class T> struct ChainHeadT {
+  T x0, u2, vin;  // x0 = y0; u after "term 1: u += y_1"; the threshold's input B v
+};
 template <class T>
-__device__ inline T ChainOneT(T d, const FusedScalarsT<T>& c, T u, T y0p, T y1p, T* x0o, T* x1o,
-                              T* y0o, T* y1o, T* uo) {
+__device__ inline ChainHeadT<T> ChainHeadOfT(T d, const FusedScalarsT<T>& c, T u, T y0p, T y1p) {
   // sweep start: u -= y0; u -= y1; then term 0: u += y0       (prox_admm.cc:137-142)
   const T v0 = ((u - y0p) - y1p) + y0p;
   const T x0 = c.kappa * d + v0;  // back substitution epilogue: alpha*acc + 1*y
@@ -91,17 +94,40 @@ __device__ inline T ChainOneT(T d, const FusedScalarsT<T>& c, T u, T y0p, T y1p,
   const T u1 = v0 - y0;           // u -= y_0
   const T u2 = u1 + y1p;          // term 1: u += y_1
   const T vin = c.Bs * u2;        // VectorProx: B v (+ g = 0)      (vector_prox.cc:141)
-  const T xz = ScaledZoneOneT<T>(vin, c.lam, c.alpha, c.beta, c.M);
+  return {x0, u2, vin};
+}
+// From the threshold's result xz on.  Returns v0' (input of the next sweep's forward pass).
+template <class T>
+__device__ inline T ChainTailT(const ChainHeadT<T>& h, T xz, const FusedScalarsT<T>& c, T* x0o, T* x1o,
+                               T* y0o, T* y1o, T* uo) {
+  const T y0 = h.x0;
   const T x1 = c.Cs * xz;         // C (x - g)                       (vector_prox.cc:145)
   const T y1 = c.a1 * x1;         // y_1 = A_ x_1
-  const T u3 = u2 - y1;           // u -= y_1
-  *x0o = x0;
+  const T u3 = h.u2 - y1;         // u -= y_1
+  *x0o = h.x0;
   *x1o = x1;
   *y0o = y0;
   *y1o = y1;
   *uo = u3;
   // next sweep's prox-0 input
   return ((u3 - y0) - y1) + y0;
+}
+
+// One column's elementwise chain.  Returns v0' (input of the next sweep's forward pass).
+template <class T>
+__device__ inline T ChainOneT(T d, const FusedScalarsT<T>& c, T u, T y0p, T y1p, T* x0o, T* x1o,
+                              T* y0o, T* y1o, T* uo) {
+  const ChainHeadT<T> h = ChainHeadOfT<T>(d, c, u, y0p, y1p);
+  const T xz = ScaledZoneOneT<T>(h.vin, c.lam, c.alpha, c.beta, c.M);
+  return ChainTailT<T>(h, xz, c, x0o, x1o, y0o, y1o, uo);
+}
+
+// The group threshold of one row of a matrix variable (NORM_2 with axis = 1): SegNorm2Kernel's
+// expressions (kernels_segprox.hip) on the sum of squares `ss` of the row's threshold inputs,
+// accumulated in fp64 in member order.  Returns the factor of xz_i = T(scale * double(vin_i)).
+__device__ inline double GroupScale(double ss, double lam) {
+  const double nv = sqrt(ss);
+  return (nv >= lam && nv > 0) ? 1.0 - lam / nv : 0.0;
 }
 
 // One column of the TWO-BLOCK driver's sweep (reference algorithms/prox_admm_two_block.cc:97-112):

@@ -43,12 +43,14 @@ constexpr int kBackLd = kBackRows + 4;      // LDS floats per instance (16-byte 
 constexpr int kBackCols = 64;               // columns of A per workgroup, 16 per wave
 constexpr int kBackChain = 2;               // MFMAs per chain (1, 2 or 4): 4 * kBackChain rows
 
-template <int NB>
+// GROUP: the nk slots are ALL the columns of one matrix variable (every one live) and the
+// threshold is the group shrinkage of its rows (NORM_2 along axis 1, weight glam).
+template <int NB, bool GROUP>
 __global__ __launch_bounds__(kBlock) void WideBackKernel(int64_t m, int64_t n, const float* __restrict__ A,
                                                          int64_t lda, const float* __restrict__ W, int64_t ldw,
                                                          const LassoBatchInst<float>* __restrict__ tab, int nk,
                                                          unsigned long long active, float* __restrict__ Vp,
-                                                         int64_t ldv) {
+                                                         int64_t ldv, double glam) {
   constexpr int KW = 16 * NB;
   constexpr int NW = KW / 8;  // 16-byte pieces of a W chunk per thread: KW * 32 / 256
   __shared__ __attribute__((aligned(16))) float lw[2][KW * kBackLd];
@@ -140,6 +142,69 @@ __global__ __launch_bounds__(kBlock) void WideBackKernel(int64_t m, int64_t n, c
 
   // C/D layout: acc[ib][i] = D[column j0 + 4 g + i][slot 16 ib + c16]
   const int64_t jb = j0 + 4 * g;
+  if constexpr (GROUP) {
+    // Row j's members sit in this lane's NB tiles and across the 16 lanes (c16) of its row group:
+    // the squares are summed in-lane over the tiles, then across the lanes by a butterfly whose
+    // two partners add the same two numbers, so all 16 lanes hold the same bits.  No lane leaves
+    // before the exchange; slots >= nk and columns >= n contribute zero.
+    ChainHeadT<float> h[NB][4];
+    float y1o[NB][4];
+    double ss[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int ib = 0; ib < NB; ++ib) {
+      const int slot = ib * 16 + c16;
+      const bool live = slot < nk;
+      const LassoBatchInst<float>& I = tab[live ? slot : 0];
+      FusedScalarsT<float> c;
+      c.kappa = I.kappa;
+      c.Bs = I.Bs;
+      c.Cs = I.Cs;
+      c.a1 = I.a1;
+      c.lam = c.alpha = c.beta = c.M = 0.f;  // (the scaled zone's: not read)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int64_t j = jb + i;
+        const bool ok = live && j < n;
+        y1o[ib][i] = ok ? I.y1[j] : 0.f;
+        h[ib][i] = ChainHeadOfT<float>(acc[ib][i], c, ok ? I.u[j] : 0.f, ok ? I.y0[j] : 0.f, y1o[ib][i]);
+        const double v = ok ? static_cast<double>(h[ib][i].vin) : 0.0;
+        ss[i] += v * v;
+      }
+    }
+#pragma unroll
+    for (int off = 1; off < 16; off <<= 1)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) ss[i] += __shfl_xor(ss[i], off, 64);
+#pragma unroll
+    for (int ib = 0; ib < NB; ++ib) {
+      const int slot = ib * 16 + c16;
+      if (slot >= nk) continue;
+      const LassoBatchInst<float>& I = tab[slot];
+      FusedScalarsT<float> c;
+      c.kappa = I.kappa;
+      c.Bs = I.Bs;
+      c.Cs = I.Cs;
+      c.a1 = I.a1;
+      c.lam = c.alpha = c.beta = c.M = 0.f;
+      float* vp = Vp + slot * ldv;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int64_t j = jb + i;
+        if (j >= n) continue;
+        const float xz = static_cast<float>(GroupScale(ss[i], glam) * static_cast<double>(h[ib][i].vin));
+        float x0, x1, z0, z1, uu;
+        const float v = ChainTailT<float>(h[ib][i], xz, c, &x0, &x1, &z0, &z1, &uu);
+        I.y1prev[j] = y1o[ib][i];
+        I.x0[j] = x0;
+        I.x1[j] = x1;
+        I.y0[j] = z0;
+        I.y1[j] = z1;
+        I.u[j] = uu;
+        vp[j] = v;
+      }
+    }
+    return;
+  }
   if (jb >= n) return;
 #pragma unroll
   for (int ib = 0; ib < NB; ++ib) {
@@ -156,7 +221,11 @@ __global__ __launch_bounds__(kBlock) void WideBackKernel(int64_t m, int64_t n, c
     c.beta = I.beta;
     c.M = I.M;
     float* vp = Vp + slot * ldv;
-    if (jb + 4 <= n) {
+    // (the columns of a matrix variable lie n apart: 16-byte pieces only where n allows)
+    const bool aligned = ((reinterpret_cast<uintptr_t>(I.u) | reinterpret_cast<uintptr_t>(I.x0) |
+                           reinterpret_cast<uintptr_t>(I.x1) | reinterpret_cast<uintptr_t>(I.y0) |
+                           reinterpret_cast<uintptr_t>(I.y1) | reinterpret_cast<uintptr_t>(I.y1prev)) & 15) == 0;
+    if (jb + 4 <= n && aligned) {
       const F4 u = *reinterpret_cast<const F4*>(I.u + jb);
       const F4 y0 = *reinterpret_cast<const F4*>(I.y0 + jb);
       const F4 y1 = *reinterpret_cast<const F4*>(I.y1 + jb);
@@ -373,7 +442,7 @@ int LassoWideSlabs(int64_t m, int64_t n) {
 }
 
 void LassoWideBack(int64_t m, int64_t n, int64_t lda, const DVec& A, const DVec& table, int first, int nk,
-                   uint64_t active, const DVec& W, int64_t ldw, const DVec& V, int64_t ldv) {
+                   uint64_t active, const DVec& W, int64_t ldw, const DVec& V, int64_t ldv, const double* group_lam) {
   EPS_CHECK(LassoWideSupported(m, n, A, lda));
   EPS_CHECK_MSG(nk >= 1 && nk <= kLassoWidePanel, "wide back product: " << nk << " instances in a panel");
   EPS_CHECK(W.dt == F32 && V.dt == F32 && ldw % 4 == 0 && ldw >= m && ldv % 4 == 0 && ldv >= n);
@@ -383,9 +452,19 @@ void LassoWideBack(int64_t m, int64_t n, int64_t lda, const DVec& A, const DVec&
   const dim3 grid(static_cast<unsigned>((n + kBackCols - 1) / kBackCols));
   hipStream_t s = Runtime::Get().stream();
   ProfScope prof("wide_back", m, n);
-#define EPS_WIDE_BACK(NB)                                                                                          \
-  hipLaunchKernelGGL(WideBackKernel<NB>, grid, dim3(kBlock), 0, s, m, n, A.as<float>(), lda, W.as<float>(), ldw, \
-                     tab, nk, static_cast<unsigned long long>(active), V.as<float>(), ldv)
+  const bool group = group_lam != nullptr;
+  if (group) {
+    const uint64_t all = nk == 64 ? ~uint64_t(0) : (uint64_t(1) << nk) - 1;
+    EPS_CHECK_MSG((active & all) == all, "wide back product: a group's members are all live");
+  }
+#define EPS_WIDE_BACK(NB)                                                                                       \
+  if (group)                                                                                                    \
+    hipLaunchKernelGGL((WideBackKernel<NB, true>), grid, dim3(kBlock), 0, s, m, n, A.as<float>(), lda,          \
+                       W.as<float>(), ldw, tab, nk, static_cast<unsigned long long>(active), V.as<float>(), ldv, \
+                       *group_lam);                                                                             \
+  else                                                                                                          \
+    hipLaunchKernelGGL((WideBackKernel<NB, false>), grid, dim3(kBlock), 0, s, m, n, A.as<float>(), lda,         \
+                       W.as<float>(), ldw, tab, nk, static_cast<unsigned long long>(active), V.as<float>(), ldv, 0.0)
   switch (PanelBlocks(nk)) {
     case 1: EPS_WIDE_BACK(1); break;
     case 2: EPS_WIDE_BACK(2); break;

@@ -403,6 +403,27 @@ class Norm2Prox final : public VectorProx {
  public:
   bool CaptureSafe() const override { return true; }
 
+  void Init(const ProxOperatorArg& arg) override {
+    VectorProx::Init(arg);
+    const pb::ProxFunction& f = arg.prox_function();
+    has_axis_ = f.has_axis;
+    axis_ = f.axis;
+    rows_ = cols_ = 0;
+    if (!f.arg_size.empty() && f.arg_size[0].dim.size() == 2) {
+      rows_ = f.arg_size[0].dim[0];
+      cols_ = f.arg_size[0].dim[1];
+    }
+  }
+
+  // Group lasso: one group per row of the n x k argument, scalar maps.
+  bool DescribeGroupNorm2(GroupNorm2Desc* d) const override {
+    if (!has_axis_ || axis_ != 1 || rows_ < 1 || cols_ < 1) return false;
+    if (!ScalarForm(&d->var_key, &d->constraint_key, &d->Bs, &d->Cs, &d->lam)) return false;
+    d->rows = rows_;
+    d->cols = cols_;
+    return true;
+  }
+
  protected:
   void ApplyVector(const VectorProxInput& input, VectorProxOutput* output) override {
     const DVec& v = input.value_vec(0);
@@ -422,6 +443,9 @@ class Norm2Prox final : public VectorProx {
 
  private:
   std::shared_ptr<Buffer> normsq_;
+  bool has_axis_ = false;
+  int axis_ = 0;
+  int64_t rows_ = 0, cols_ = 0;
 };
 REGISTER_PROX_OPERATOR(NORM_2, Norm2Prox);
 
@@ -521,17 +545,35 @@ class SumSquareProx final : public ProxOperator {
     if (!Di.has_key(ck, ck) || !Di.has_key(vk, vk) || !Di.has_key(ak, ak)) return false;
     if (!is_scalar(L(vk, ck), -1.0) || !is_scalar(Di(ck, ck), -1.0) || !is_scalar(Di(vk, vk), 1.0))
       return false;
-    if (L(ak, vk).impl().type() != DENSE_MATRIX || Di(ak, ak).impl().type() != DENSE_MATRIX)
-      return false;
     for (const auto& kv : b_.data())
       if (kv.first != ak) return false;
+    int64_t cols = 1, dcols = 1;
+    d->L_arg_var = DenseFactor(L(ak, vk), &cols);
+    d->Dinv_arg = DenseFactor(Di(ak, ak), &dcols);
+    if (!d->L_arg_var || !d->Dinv_arg || cols != dcols) return false;
     d->constraint_key = ck;
     d->var_key = vk;
     d->arg_key = ak;
-    d->L_arg_var = std::static_pointer_cast<const DenseMatrixImpl>(L(ak, vk).ptr());
-    d->Dinv_arg = std::static_pointer_cast<const DenseMatrixImpl>(Di(ak, ak).ptr());
-    if (b_.has_key(ak)) d->rhs_arg = b_(ak);
+    d->cols = cols;
+    d->rhs_arg = b_.has_key(ak) ? b_(ak) : DVec();
     return true;
+  }
+
+ private:
+  // The dense matrix of a block: the block itself, or - a matrix variable, whose data map is
+  // I_k (x) A - the dense factor of kron(s I_k, D) with s folded into its scale (the setup algebra
+  // keeps the product in this form: MultiplyScalarKron, AddScalarKron in linear_map.cc).
+  static std::shared_ptr<const DenseMatrixImpl> DenseFactor(const LinearMap& M, int64_t* cols) {
+    *cols = 1;
+    if (M.impl().type() == DENSE_MATRIX) return std::static_pointer_cast<const DenseMatrixImpl>(M.ptr());
+    if (M.impl().type() != KRONECKER_PRODUCT) return nullptr;
+    const auto& K = static_cast<const KroneckerProductImpl&>(M.impl());
+    if (K.A().impl().type() != SCALAR_MATRIX || K.B().impl().type() != DENSE_MATRIX) return nullptr;
+    const auto& D = static_cast<const DenseMatrixImpl&>(K.B().impl());
+    *cols = K.A().impl().n();
+    if (*cols < 1) return nullptr;
+    return std::make_shared<DenseMatrixImpl>(D.data(), D.rows(), D.cols(), D.trans(),
+                                             D.scale() * GetScalar(K.A()), D.id(), D.symmetric());
   }
 
  private:

@@ -42,12 +42,23 @@ struct LeastSquaresDesc {  // SumSquareProx after block elimination [constraint,
   std::shared_ptr<const DenseMatrixImpl> L_arg_var;  // L(arg, var): lazily scaled data matrix
   std::shared_ptr<const DenseMatrixImpl> Dinv_arg;   // cached explicit inverse (with its sign)
   DVec rhs_arg;                                      // constant part of the rhs on the arg row
+  // Matrix variable (n x cols, column-major): the maps are I_cols (x) L_arg_var and
+  // I_cols (x) Dinv_arg; the descriptors above are the dense factors with the scalar factor of the
+  // Kronecker product folded into their scale, rhs_arg has m * cols entries (column c at c * m).
+  int64_t cols = 1;
 };
 struct ScaledZoneDesc {  // ScaledZoneProx with scalar H, A and uniform parameters
   std::string var_key, constraint_key;
   double Bs = 0, Cs = 0;  // v' = Bs*v ; x = Cs*x'
   double lam = 0, alpha = 1, beta = 1, M = 0;
   DVec alpha_vec, beta_vec;  // per-element alpha / beta (SUM_QUANTILE with data vectors); empty: uniform
+};
+
+struct GroupNorm2Desc {  // Norm2Prox with axis = 1 on an n x cols argument: one group per row
+  std::string var_key, constraint_key;
+  double Bs = 0, Cs = 0;  // v' = Bs*v ; x = Cs*x'
+  double lam = 0;
+  int64_t rows = 0, cols = 0;
 };
 
 class ProxOperator {  // reference prox/prox.h:37-43
@@ -57,6 +68,7 @@ class ProxOperator {  // reference prox/prox.h:37-43
   virtual BlockVector Apply(const BlockVector& v) = 0;
   virtual bool DescribeLeastSquares(LeastSquaresDesc* d) const { return false; }
   virtual bool DescribeScaledZone(ScaledZoneDesc* d) const { return false; }
+  virtual bool DescribeGroupNorm2(GroupNorm2Desc* d) const { return false; }
   // true: Apply is a fixed sequence of launches on the library's stream - no host
   // synchronisation, no decision on device data, no state carried from one call to the next -
   // so a sweep through this operator can be captured into a hipGraph and replayed (admm.cc).

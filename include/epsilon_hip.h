@@ -91,7 +91,14 @@ const char* eps_version(void);
  * share the data matrix on the wide route (two matrix products per sweep on the f32 matrix
  * instruction, up to 64 instances per read of the matrix); such groups match eps_solve to f32
  * rounding, not bit for bit - see eps_solve_batch.  Any other value is an error that names it
- * (env EPSILON_HIP_BATCH_WIDE). */
+ * (env EPSILON_HIP_BATCH_WIDE).
+ * "fused_matrix" = "auto" (default) | "0" | "pass" | "wide"  least squares on a matrix variable
+ * X (n x k, data map I_k (x) A, at least 256 rows; multi-block driver, one GPU) with an l1 or a
+ * row-group (multi-task group lasso) penalty: the k columns run as k members of the batched fused
+ * pass ("pass": f32 and f64, per column the arithmetic of the fused vector lasso) or of
+ * the wide kernels ("wide": f32 only, results to f32 rounding) inside one solve.  A forced route
+ * that the problem cannot take and "0" mean the generic operator path; "auto" picks by shape.
+ * Read at every Init.  Any other value is an error that names it (env EPSILON_HIP_FUSED_MATRIX). */
 int eps_set_option(const char* key, const char* value);
 /* Number of visible HIP devices (0 if none); never fails. */
 int eps_device_count(void);
