@@ -450,6 +450,90 @@ def linear_map_inverse(A):
     return dense.reshape((A.n, A.m), order="F")
 
 
+class _Block(ctypes.Structure):
+    _fields_ = [("row", ctypes.c_char_p), ("col", ctypes.c_char_p),
+                ("linear_map", ctypes.c_void_p), ("len", ctypes.c_size_t)]
+
+
+FILL_MAX = -1  # block_solve's fill bound of a key without a diagonal block
+
+
+def block_solve(blocks, rhs=None, mode="factor", keys=None):
+    """Test entry for the block LDL^T (include/epsilon_hip.h eps_test_block_solve).
+
+    blocks: [(row key, col key, ir.LMap)] - both triangles of the symmetric matrix (for the modes
+    "forward" / "back": the blocks of L / L^T); rhs: {key: float64 values}; keys: the substitution
+    order of "forward" / "back".  Returns a dict with the entries the mode produces:
+
+      "fill"                {key: bound}                          ("fill"; FILL_MAX: no diagonal block)
+      "trace"               [({key: bound}, pivot)] per step      ("factor", "solve")
+      "order"               [key]
+      "L", "D_inv"          {(row, col): (ImplType, m x n array)}  ("factor"; a Kronecker product
+                            has (4, ImplType of A, ImplType of B) in place of the ImplType)
+      "condition_estimate", "refine_steps"
+      "x", "x_again"        {key: array}    Solve(rhs) twice on the one factorisation; for
+                                            "forward" / "back" "x" is the substituted vector
+    """
+    L = lib()
+    keep = []
+    blocks = list(blocks) if blocks is not None else None
+    data = {}
+    if blocks is None:
+        barr, nblocks = None, 0
+    else:
+        nblocks = len(blocks)
+        barr = (_Block * max(nblocks, 1))()
+        for i, (row, col, lmap) in enumerate(blocks):
+            rb, cb = row.encode("utf-8"), col.encode("utf-8")
+            if isinstance(lmap, (bytes, bytearray)):
+                payload = bytes(lmap)
+            else:
+                payload = lmap.proto.SerializeToString()
+                data.update(lmap.data)
+            buf = ctypes.create_string_buffer(payload, max(len(payload), 1))
+            keep.extend([rb, cb, buf])
+            barr[i].row, barr[i].col = rb, cb
+            barr[i].linear_map = ctypes.cast(buf, ctypes.c_void_p)
+            barr[i].len = len(payload)
+    dblobs, nd = _blobs(data, keep)
+    rblobs, nr = _blobs({k: np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+                         for k, v in (rhs or {}).items()}, keep)
+    kb = [k.encode("utf-8") for k in (keys or [])]
+    karr = (ctypes.c_char_p * max(len(kb), 1))(*kb)
+    res = ctypes.c_void_p()
+    _check(L.eps_test_block_solve(mode.encode("utf-8"), barr, ctypes.c_size_t(nblocks), dblobs,
+                                  ctypes.c_size_t(nd), rblobs, ctypes.c_size_t(nr), karr,
+                                  ctypes.c_size_t(len(kb)), ctypes.byref(res)))
+    out = {}
+    steps = {}
+    order = {}
+    for name, raw in _take_result(res)[1].items():
+        f = name.split("\t")
+        v = np.frombuffer(raw, dtype=np.float64)
+        if f[0] == "fill":
+            out.setdefault("fill", {})[f[1]] = int(v[0])
+        elif f[0] == "trace":
+            steps.setdefault(int(f[1]), [{}, None])[0][f[2]] = int(v[0])
+        elif f[0] == "pivot":
+            steps.setdefault(int(f[1]), [{}, None])[1] = f[2]
+        elif f[0] == "order":
+            order[int(f[1])] = f[2]
+        elif f[0] in ("L", "D_inv"):
+            m, n = int(v[1]), int(v[2])
+            kind = int(v[0]) if v[3] < 0 else (int(v[0]), int(v[3]), int(v[4]))
+            out.setdefault(f[0], {})[(f[1], f[2])] = (kind, v[5:].reshape((m, n), order="F").copy())
+        elif f[0] in ("x", "x_again"):
+            out.setdefault(f[0], {})[f[1]] = v.copy()
+        elif f[0] == "refine_steps":
+            out[f[0]] = int(v[0])
+        else:
+            out[f[0]] = float(v[0])
+    if mode in ("factor", "solve"):
+        out["trace"] = [tuple(steps[s]) for s in sorted(steps)]
+        out["order"] = [order[i] for i in sorted(order)]
+    return out
+
+
 def tv1d(v, lam):
     v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
     x = np.empty_like(v)

@@ -391,7 +391,6 @@ void BlockMatrix::Remove(const std::string& row, const std::string& col) {
 
 // ---- BlockCholesky (reference vector/block_cholesky.cc) ---------------------------------------------
 
-static const uint64_t kFillMax = std::numeric_limits<uint64_t>::max();
 static const uint64_t kFillForbidden = kFillMax - 1;  // sharded solve: would couple ranks
 
 // Upper bound on the non-zeros that eliminating column k adds to the remaining matrix: the
@@ -443,11 +442,13 @@ uint64_t ComputeFill(const BlockMatrix& A, const std::string& k) {
 
 // Greedy minimum-fill pivot: the first key, in column order, with the smallest bound (the
 // tie-break matters: it decides which of two equal candidates the solver eliminates first).
-std::string NextKey(const BlockMatrix& A) {
+std::string NextKey(const BlockMatrix& A, FillBounds* bounds) {
   const std::set<std::string> key_set = A.col_keys();  // sorted: the order of the reference's loop
   const std::vector<std::string> keys(key_set.begin(), key_set.end());
   std::vector<uint64_t> bound(keys.size());
   for (size_t c = 0; c < keys.size(); ++c) bound[c] = ComputeFill(A, keys[c]);
+  if (bounds != nullptr)
+    for (size_t c = 0; c < keys.size(); ++c) bounds->emplace_back(keys[c], bound[c]);
   const auto best = std::min_element(bound.begin(), bound.end());
   EPS_CHECK_MSG(best != bound.end() && *best != kFillMax, "block LDL: no key with a diagonal block\n"
                                                               << A.DebugString());
@@ -569,7 +570,9 @@ void BlockCholesky::Compute(BlockMatrix A) {
   refine_steps_ = 0;
   bool any_f32 = false;
   for (size_t left = A.col_keys().size(); left > 0; --left) {
-    const std::string pivot = NextKey(A);
+    if (trace_ != nullptr) trace_->emplace_back();
+    const std::string pivot = NextKey(A, trace_ != nullptr ? &trace_->back().fills : nullptr);
+    if (trace_ != nullptr) trace_->back().pivot = pivot;
     const LinearMap& block = A(pivot, pivot);
     // a replicated block of a sharded solve is the same matrix on every rank (its sharded
     // contributions were all-reduced): split the work of inverting a large dense one

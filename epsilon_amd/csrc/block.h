@@ -7,6 +7,7 @@
 // per-iteration deep copies (`y_prev_ = y_`, prox_admm.cc:135) cost nothing here.
 #pragma once
 
+#include <limits>
 #include <map>
 #include <set>
 #include <string>
@@ -101,13 +102,25 @@ struct AffineOperator {  // reference affine/affine.h:15-18
 };
 
 // reference vector/block_cholesky.cc
+// ComputeFill's value for a key without a diagonal block (it cannot be eliminated).
+constexpr uint64_t kFillMax = std::numeric_limits<uint64_t>::max();
+typedef std::vector<std::pair<std::string, uint64_t>> FillBounds;  // (key, ComputeFill) in key order
 uint64_t ComputeFill(const BlockMatrix& A, const std::string& k);
-std::string NextKey(const BlockMatrix& A);
+// `bounds` (may be null) receives the bound of every key the choice was made from.
+std::string NextKey(const BlockMatrix& A, FillBounds* bounds = nullptr);
 BlockVector ForwardSub(const BlockMatrix& L, const std::vector<std::string>& keys, BlockVector b);
 BlockVector BackSub(const BlockMatrix& LT, const std::vector<std::string>& keys, BlockVector b);
 
 class BlockCholesky {
  public:
+  // One elimination step as Compute() took it (tests): the bounds of the remaining keys, the pivot.
+  struct Step {
+    FillBounds fills;
+    std::string pivot;
+  };
+  // Compute() appends its steps to *trace (null: no record); a step whose choice fails is
+  // recorded with an empty pivot before the error is raised.
+  void set_trace(std::vector<Step>* trace) { trace_ = trace; }
   void Compute(BlockMatrix A);
   BlockVector Solve(const BlockVector& b) const;
   const std::vector<std::string>& order() const { return p_; }
@@ -127,6 +140,7 @@ class BlockCholesky {
   BlockMatrix A_;  // the matrix as given (shares every block's buffer): refinement residuals
   double cond_ = 1.0;
   int refine_steps_ = 0;
+  std::vector<Step>* trace_ = nullptr;
 };
 
 // Process-wide record of the last factorisations' condition estimates (tests / diagnostics):

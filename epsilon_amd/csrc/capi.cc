@@ -2,16 +2,19 @@
 // reference interface it replaces (python/epopt/solvemodule.cc).
 #include "../../include/epsilon_hip.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
+#include <set>
 #include <string>
 #include <vector>
 
 #include "admm.h"
+#include "block.h"
 #include "comm.h"
 #include "kernels.h"
 #include "linear_map.h"
@@ -149,6 +152,142 @@ void Tv1dOnDeviceData(const void* v_dev, void* x_dev, const eps::k::Segs& S, int
   const int depth = eps::k::Tv1dSeg(x, v, lam, S);
   Runtime::Get().Sync();
   if (levels) *levels = depth;
+}
+
+
+// ---- eps_test_block_solve --------------------------------------------------------------------------
+
+HostArray HostArrayOf(const std::vector<double>& v) {
+  HostArray a;
+  a.n = v.size();
+  a.mem = AllocHostBuffer(std::max<size_t>(v.size(), 1) * sizeof(double));
+  if (!v.empty()) std::memcpy(a.data(), v.data(), v.size() * sizeof(double));
+  return a;
+}
+
+void PutValues(eps_result* r, const std::string& id, const std::vector<double>& v) {
+  r->ids.push_back(id);
+  r->values.push_back(HostArrayOf(v));
+}
+
+double FillValue(uint64_t bound) { return bound == kFillMax ? -1.0 : static_cast<double>(bound); }
+
+// [ImplType, m, n, ImplType of the two factors of a Kronecker product (else -1, -1), values of the
+// m x n map in column-major order]
+void PutBlocks(eps_result* r, const char* name, const BlockMatrix& M) {
+  for (const auto& col : M.data())
+    for (const auto& row : col.second) {
+      const LinearMapImpl& B = row.second.impl();
+      std::vector<double> v = {static_cast<double>(B.type()), static_cast<double>(B.m()),
+                               static_cast<double>(B.n()), -1.0, -1.0};
+      if (B.type() == KRONECKER_PRODUCT) {
+        const auto& K = static_cast<const KroneckerProductImpl&>(B);
+        v[3] = static_cast<double>(K.A().impl().type());
+        v[4] = static_cast<double>(K.B().impl().type());
+      }
+      const std::vector<double> dense = ToDense(B, MapDType(B, CurrentDType()))->data().ToHost();
+      EPS_CHECK(static_cast<int64_t>(dense.size()) == B.m() * B.n());
+      v.insert(v.end(), dense.begin(), dense.end());
+      PutValues(r, std::string(name) + "\t" + row.first + "\t" + col.first, v);
+    }
+}
+
+void PutVector(eps_result* r, const char* name, const BlockVector& x) {
+  for (const auto& kv : x.data()) {
+    r->ids.push_back(std::string(name) + "\t" + kv.first);
+    r->values.push_back(kv.second.ToHostArray());
+  }
+}
+
+// The argument checks of eps_test_block_solve: everything that can be decided from the payloads
+// alone, so that no device work starts on arguments that do not fit together.
+struct BlockSolveArgs {
+  enum Mode { FILL, FACTOR, SOLVE, FORWARD, BACK } mode;
+  std::vector<pb::LinearMap> maps;          // blocks[i], parsed
+  std::map<std::string, int64_t> dim;       // size of every row / column key
+  std::vector<std::string> keys;            // substitution order (FORWARD / BACK)
+};
+
+BlockSolveArgs CheckBlockSolveArgs(const char* mode, const eps_block* blocks, size_t nblocks,
+                                   const eps_blob* rhs, size_t nrhs, const char* const* keys,
+                                   size_t nkeys) {
+  const char* const fn = "eps_test_block_solve: ";
+  BlockSolveArgs a;
+  EPS_CHECK_MSG(mode != nullptr, fn << "mode is null");
+  const std::string m(mode);
+  if (m == "fill") a.mode = BlockSolveArgs::FILL;
+  else if (m == "factor") a.mode = BlockSolveArgs::FACTOR;
+  else if (m == "solve") a.mode = BlockSolveArgs::SOLVE;
+  else if (m == "forward") a.mode = BlockSolveArgs::FORWARD;
+  else if (m == "back") a.mode = BlockSolveArgs::BACK;
+  else EPS_FATAL(fn << "mode must be fill, factor, solve, forward or back, got " << m);
+  const bool substitution = a.mode == BlockSolveArgs::FORWARD || a.mode == BlockSolveArgs::BACK;
+  EPS_CHECK_MSG(blocks != nullptr && nblocks > 0, fn << "blocks is null or empty");
+  EPS_CHECK_MSG(nrhs == 0 || rhs != nullptr, fn << "rhs is null with nrhs " << nrhs);
+  EPS_CHECK_MSG(nkeys == 0 || keys != nullptr, fn << "keys is null with nkeys " << nkeys);
+  std::set<std::pair<std::string, std::string>> seen;
+  auto set_dim = [&](const std::string& key, int64_t d, size_t i) {
+    auto ins = a.dim.insert(std::make_pair(key, d));
+    EPS_CHECK_MSG(ins.first->second == d, fn << "block " << i << " gives key " << key << " the size " << d
+                                             << ", an earlier block " << ins.first->second);
+  };
+  for (size_t i = 0; i < nblocks; ++i) {
+    EPS_CHECK_MSG(blocks[i].row != nullptr && blocks[i].col != nullptr, fn << "block " << i << " has a null key");
+    const std::string row(blocks[i].row), col(blocks[i].col);
+    EPS_CHECK_MSG(seen.insert(std::make_pair(row, col)).second,
+                  fn << "block (" << row << ", " << col << ") is given twice");
+    EPS_CHECK_MSG(blocks[i].linear_map != nullptr && blocks[i].len > 0,
+                  fn << "block (" << row << ", " << col << ") has an empty LinearMap payload");
+    try {
+      a.maps.push_back(pb::ParseLinearMap(blocks[i].linear_map, blocks[i].len));
+    } catch (const std::exception& e) {
+      EPS_FATAL(fn << "block (" << row << ", " << col << "): malformed LinearMap: " << e.what());
+    }
+    const pb::LinearMap& p = a.maps.back();
+    EPS_CHECK_MSG(p.linear_map_type != pb::LinearMap::UNKNOWN && p.m > 0 && p.n > 0,
+                  fn << "block (" << row << ", " << col << "): malformed LinearMap: type "
+                     << p.linear_map_type << ", " << p.m << " x " << p.n);
+    set_dim(row, p.m, i);
+    set_dim(col, p.n, i);
+  }
+  if (substitution) {
+    std::set<std::string> order;
+    for (size_t i = 0; i < nkeys; ++i) {
+      EPS_CHECK_MSG(keys[i] != nullptr, fn << "keys[" << i << "] is null");
+      EPS_CHECK_MSG(order.insert(keys[i]).second, fn << "key " << keys[i] << " is given twice in keys");
+      a.keys.push_back(keys[i]);
+    }
+    EPS_CHECK_MSG(!a.keys.empty(), fn << "mode " << m << " needs the key order in keys");
+    for (const auto& kv : a.dim)
+      EPS_CHECK_MSG(order.count(kv.first) != 0, fn << "block key " << kv.first << " is not in keys");
+  } else {
+    // symmetric in structure: both triangles given, every key a column
+    for (const auto& rc : seen)
+      EPS_CHECK_MSG(seen.count(std::make_pair(rc.second, rc.first)) != 0,
+                    fn << "block (" << rc.first << ", " << rc.second << ") has no transpose ("
+                       << rc.second << ", " << rc.first << ")");
+  }
+  std::set<std::string> rhs_seen;
+  for (size_t i = 0; i < nrhs; ++i) {
+    EPS_CHECK_MSG(rhs[i].key != nullptr, fn << "rhs " << i << " has a null key");
+    const std::string key(rhs[i].key);
+    EPS_CHECK_MSG(rhs_seen.insert(key).second, fn << "rhs key " << key << " is given twice");
+    if (substitution && a.dim.count(key) == 0) {
+      // a key of the order that no block touches: its block passes through unchanged
+      EPS_CHECK_MSG(std::find(a.keys.begin(), a.keys.end(), key) != a.keys.end(),
+                    fn << "rhs key " << key << " is not in keys");
+    } else {
+      EPS_CHECK_MSG(a.dim.count(key) != 0, fn << "rhs key " << key << " is not a key of the matrix");
+    }
+    EPS_CHECK_MSG(rhs[i].kind == EPS_BLOB_HOST && rhs[i].len % sizeof(double) == 0 &&
+                      (rhs[i].len == 0 || rhs[i].ptr != nullptr),
+                  fn << "rhs " << key << " must be host float64 bytes");
+    auto d = a.dim.find(key);
+    EPS_CHECK_MSG(d == a.dim.end() || static_cast<int64_t>(rhs[i].len / sizeof(double)) == d->second,
+                  fn << "rhs " << key << " has " << rhs[i].len / sizeof(double) << " entries, the matrix "
+                     << d->second);
+  }
+  return a;
 }
 
 }  // namespace
@@ -779,6 +918,71 @@ int eps_test_spd_inverse_repeat(int64_t n, int form_a, int form_b, double* diff_
     rt.FetchSlots();
     *diff_fro = std::sqrt(rt.SlotValue(s0));
     *norm_fro = std::sqrt(rt.SlotValue(s1));
+  });
+}
+
+int eps_test_block_solve(const char* mode, const eps_block* blocks, size_t nblocks,
+                         const eps_blob* data, size_t ndata, const eps_blob* rhs, size_t nrhs,
+                         const char* const* keys, size_t nkeys, eps_result** out) {
+  if (out != nullptr) *out = nullptr;
+  return Guard([&] {
+    EPS_CHECK_MSG(out != nullptr, "eps_test_block_solve: out is null");
+    const BlockSolveArgs args = CheckBlockSolveArgs(mode, blocks, nblocks, rhs, nrhs, keys, nkeys);
+    const DType dt = ConfiguredDType();
+    SetCurrentDType(dt);
+    auto dm = MakeDataMap(data, ndata, dt);
+    BlockMatrix A;
+    for (size_t i = 0; i < nblocks; ++i) {
+      LinearMap B = BuildLinearMap(args.maps[i], dm.get());
+      EPS_CHECK_MSG(B.impl().m() == args.maps[i].m && B.impl().n() == args.maps[i].n,
+                    "eps_test_block_solve: block (" << blocks[i].row << ", " << blocks[i].col << ") is "
+                        << B.impl().m() << " x " << B.impl().n() << ", its LinearMap says "
+                        << args.maps[i].m << " x " << args.maps[i].n);
+      A(blocks[i].row, blocks[i].col) = B;
+    }
+    BlockVector b;
+    for (size_t i = 0; i < nrhs; ++i)
+      b.Set(rhs[i].key, DVec::FromHost(static_cast<const double*>(rhs[i].ptr),
+                                       static_cast<int64_t>(rhs[i].len / sizeof(double)), dt));
+    std::unique_ptr<eps_result> r(new eps_result);
+    switch (args.mode) {
+      case BlockSolveArgs::FILL:
+        for (const std::string& key : A.col_keys())
+          PutValues(r.get(), "fill\t" + key, {FillValue(ComputeFill(A, key))});
+        break;
+      case BlockSolveArgs::FORWARD:
+        PutVector(r.get(), "x", ForwardSub(A, args.keys, b));
+        break;
+      case BlockSolveArgs::BACK:
+        PutVector(r.get(), "x", BackSub(A, args.keys, b));
+        break;
+      case BlockSolveArgs::FACTOR:
+      case BlockSolveArgs::SOLVE: {
+        BlockCholesky chol;
+        std::vector<BlockCholesky::Step> trace;
+        chol.set_trace(&trace);
+        chol.Compute(A);
+        for (size_t s = 0; s < trace.size(); ++s) {
+          for (const auto& f : trace[s].fills)
+            PutValues(r.get(), "trace\t" + std::to_string(s) + "\t" + f.first, {FillValue(f.second)});
+          PutValues(r.get(), "pivot\t" + std::to_string(s) + "\t" + trace[s].pivot, {static_cast<double>(s)});
+        }
+        for (size_t i = 0; i < chol.order().size(); ++i)
+          PutValues(r.get(), "order\t" + std::to_string(i) + "\t" + chol.order()[i], {static_cast<double>(i)});
+        if (args.mode == BlockSolveArgs::FACTOR) {
+          PutBlocks(r.get(), "L", chol.L());
+          PutBlocks(r.get(), "D_inv", chol.D_inv());
+        }
+        PutValues(r.get(), "condition_estimate", {chol.condition_estimate()});
+        PutValues(r.get(), "refine_steps", {static_cast<double>(chol.refine_steps())});
+        if (nrhs > 0) {
+          PutVector(r.get(), "x", chol.Solve(b));
+          PutVector(r.get(), "x_again", chol.Solve(b));
+        }
+        break;
+      }
+    }
+    *out = r.release();
   });
 }
 

@@ -305,6 +305,38 @@ int eps_bench_spd_inverse_columns(int64_t n, int64_t cnt, int iters, double* ms_
  * between the workgroups of a launch shows as a non-zero difference, above all on a busy GPU). */
 int eps_test_spd_inverse_repeat(int64_t n, int form_a, int form_b, double* diff_fro, double* norm_fro);
 
+/* Test entry: the block LDL^T behind SUM_SQUARE / ZERO / AFFINE (reference
+ * vector/block_cholesky.cc) on a caller-given block matrix, with the "dtype" and "refine" options
+ * of a solve.  blocks: one serialized `LinearMap` per (row key, column key) - both triangles of
+ * the symmetric matrix, every pair at most once; data: the blobs the maps refer to; rhs: one
+ * float64 host blob per key.  `mode` selects what runs; the result holds float64 arrays whose ids
+ * are tab-separated fields (a fill bound of "no diagonal block" is -1):
+ *   "fill"     ComputeFill of every column key of the matrix as given:  "fill\t<key>" -> [bound]
+ *   "factor"   BlockCholesky::Compute and, with a rhs, Solve twice on that factorisation:
+ *              "trace\t<step>\t<key>" -> [bound] for every key left at that step,
+ *              "pivot\t<step>\t<key>" -> [step],  "order\t<i>\t<key>" -> [i],
+ *              "L\t<row>\t<col>" and "D_inv\t<row>\t<col>" -> [ImplType, m, n, ImplType of the two
+ *              factors of a Kronecker product (else -1, -1), m*n dense values (column-major)],
+ *              "x\t<key>" and "x_again\t<key>" -> solution block,
+ *              "condition_estimate" -> [kappa],  "refine_steps" -> [steps]
+ *   "solve"    the same without the L and D_inv blocks
+ *   "forward"  ForwardSub(blocks, keys, rhs) with the blocks taken as L (no factorisation, no
+ *   "back"     symmetry asked; BackSub takes them as L^T) over the key order `keys`: "x\t<key>"
+ * `keys` is read by "forward" / "back" only.  Argument errors - an unknown mode, no blocks, a null
+ * key, a pair given twice, a payload that does not parse, blocks whose sizes or transposes do not
+ * fit, a rhs key the matrix (or `keys`) lacks or of another length - fail before any device work and
+ * name the key or argument; a matrix with no eliminable key fails in Compute.  *out is NULL on
+ * failure. */
+typedef struct eps_block {
+  const char* row;
+  const char* col;
+  const void* linear_map; /* protobuf wire bytes of `LinearMap` */
+  size_t len;
+} eps_block;
+int eps_test_block_solve(const char* mode, const eps_block* blocks, size_t nblocks,
+                         const eps_blob* data, size_t ndata, const eps_blob* rhs, size_t nrhs,
+                         const char* const* keys, size_t nkeys, eps_result** out);
+
 /* Microbenchmark: average milliseconds of one launch of a standalone elementwise prox kernel on
  * n synthetic elements of the configured dtype - kind 0 scaled-zone (NORM_1) with scalar
  * parameters, 1 with a per-element threshold vector, 2 projection onto R+ (reference
