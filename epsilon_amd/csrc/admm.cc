@@ -402,6 +402,19 @@ MatrixRoute FusedMatrixMode() {
   EPS_FATAL("fused_matrix must be 0, pass, wide or auto, got " << e);
 }
 
+// ZERO-term problems (basis pursuit, hinge / deadzone + l1 in graph form) on the fused sweep
+// (ProxADMMSolver::TryEnableZeroFused).  Below this many rows of the data matrix
+// the solve keeps the generic operator path (a constant: no crossover was measured).
+constexpr int64_t kZeroFusedMinRows = 256;
+
+// EPSILON_HIP_FUSED_ZERO (eps_set_option "fused_zero"), read at every Init.
+bool FusedZeroAuto() {
+  const char* e = std::getenv("EPSILON_HIP_FUSED_ZERO");
+  if (e == nullptr || std::strcmp(e, "auto") == 0) return true;
+  if (std::strcmp(e, "0") == 0) return false;
+  EPS_FATAL("fused_zero must be 0 or auto, got " << e);
+}
+
 // One sweep of a panel of up to 64 f32 members on the wide route (kernels_fused_wide.hip): back
 // product + chain, forward product, reduction and - unless whitened - the cached inverse times
 // the panel.  The workspaces depend on (m, n) alone and serve every panel in turn.
@@ -497,6 +510,7 @@ class ProxADMMSolver final : public Solver {
     status_ = pb::SolverStatus();
     initialized_ = true;
     TryEnableFused();
+    TryEnableZeroFused();
     mark("fused state");
     capture_safe_ = true;
     for (const auto& op : prox_) capture_safe_ = capture_safe_ && op->CaptureSafe();
@@ -1012,6 +1026,220 @@ class ProxADMMSolver final : public Solver {
     else D.Apply(1.0, f.p, 0.0, f.w);
   }
 
+  // ---- fused sweep of ZERO-term problems --------------------------------------
+  // Recognised structure: the last term is a ZERO term over private copies (x', and z' unless the
+  // problem has no z: basis pursuit) whose block LDL^T is the projection ZeroProx describes; the
+  // other terms are one scaled-zone term on x and at most one on z (which may carry an offset),
+  // each tied to its copy by a consensus constraint copy + a var = 0 without a constant.  The
+  // sweep is then: the pass over the data matrix (chain 2: back product, column chain, forward
+  // product), the row kernel (row chain, the partials' sum, r) - basis pursuit: the partials'
+  // reduction alone - and the apply of the cached inverse.  The residual check is the generic one
+  // on views of the fused state.  One GPU, every dtype the compute type.
+  void TryEnableZeroFused() {
+    zfused_ = false;
+    const bool mode_auto = FusedZeroAuto();
+    const char* env = std::getenv("EPSILON_HIP_FUSED");
+    if (fused_ || !mode_auto || (env && env[0] == '0')) return;
+    if (ShardSpec::Get().active() || !b_.data().empty()) return;
+    const int nc = static_cast<int>(problem_.constraint.size());
+    if (nc < 1 || nc > 2 || N_ != nc + 1) return;
+    ZeroFusedState f;
+    if (!prox_[N_ - 1]->DescribeZeroProjection(&f.zp)) return;
+    f.has_z = !f.zp.z_key.empty();
+    if (f.has_z != (nc == 2)) return;
+    f.ix = f.iz = -1;
+    for (int i = 0; i + 1 < N_; ++i) {
+      ScaledZoneDesc d;
+      if (!prox_[i]->DescribeScaledZoneOffset(&d)) return;
+      if (f.ix < 0 && d.constraint_key == f.zp.x_constraint_key && d.g.n == 0) {
+        f.sx = d;
+        f.ix = i;
+      } else if (f.has_z && f.iz < 0 && d.constraint_key == f.zp.z_constraint_key) {
+        f.sz = d;
+        f.iz = i;
+      } else {
+        return;
+      }
+    }
+    if (f.ix < 0 || (f.has_z && f.iz < 0)) return;
+    const DenseMatrixImpl& L = *f.zp.L_arg_x;
+    const DenseMatrixImpl& D = *f.zp.Dinv_arg;
+    const DType dt = data_->dtype();
+    f.m = L.rows();
+    f.n = L.cols();
+    if (f.m < kZeroFusedMinRows || L.dtype() != dt || D.dtype() != dt) return;
+    if (D.rows() != f.m || D.cols() != f.m) return;
+    if (!k::LassoFusedSupported(f.m, f.n, L.data(), L.rows())) return;
+    // the consensus constraints: copy + a var = 0, scalar maps, nothing else in their rows
+    if (static_cast<int>(A_.data().size()) != 2 * nc) return;
+    auto tie = [&](const std::string& ck, const std::string& copy, const std::string& var, int64_t len, double* a) {
+      if (copy == var || !A_.has_key(ck, copy) || !A_.has_key(ck, var)) return false;
+      if (A_.col(copy).size() != 1 || A_.col(var).size() != 1) return false;
+      const LinearMap& A0 = A_(ck, copy);
+      const LinearMap& A1 = A_(ck, var);
+      if (A0.impl().type() != SCALAR_MATRIX || A1.impl().type() != SCALAR_MATRIX) return false;
+      if (GetScalar(A0) != 1.0 || A0.impl().n() != len || A1.impl().n() != len) return false;
+      *a = GetScalar(A1);
+      return true;
+    };
+    if (!tie(f.zp.x_constraint_key, f.zp.x_key, f.sx.var_key, f.n, &f.ax)) return;
+    if (f.has_z && !tie(f.zp.z_constraint_key, f.zp.z_key, f.sz.var_key, f.m, &f.az)) return;
+    auto fits = [&](const DVec& v, int64_t len) { return v.n == 0 || (v.n == len && v.dt == dt); };
+    if (!fits(f.zp.rhs_arg, f.m) || !fits(f.sx.alpha_vec, f.n) || !fits(f.sx.beta_vec, f.n)) return;
+    if (!fits(f.sz.alpha_vec, f.m) || !fits(f.sz.beta_vec, f.m) || !fits(f.sz.g, f.m)) return;
+
+    // state: u, var, copy, y of the separable term, y of the ZERO term, their previous values -
+    // per constraint row, taken over from the generic containers (warm start)
+    auto side = [&](int64_t len, const std::string& ck, int term, const std::string& var, const std::string& copy,
+                    DVec* all, DVec (&v)[7]) {
+      const int64_t pad = (len + 63) / 64 * 64;
+      *all = DVec::Zeros(7 * pad, dt);
+      for (int q = 0; q < 7; ++q) v[q] = all->Slice(q * pad, len);
+      auto take = [&](const DVec& dst, const BlockVector& src, const std::string& key) {
+        if (src.has_key(key)) {
+          EPS_CHECK(src(key).n == dst.n);
+          k::Copy(dst, src(key));
+        }
+      };
+      take(v[0], u_, ck);
+      take(v[1], x_[term], var);
+      take(v[2], x_[N_ - 1], copy);
+      take(v[3], y_[term], ck);
+      take(v[4], y_[N_ - 1], ck);
+    };
+    side(f.n, f.zp.x_constraint_key, f.ix, f.sx.var_key, f.zp.x_key, &f.state_n, f.sn);
+    if (f.has_z) side(f.m, f.zp.z_constraint_key, f.iz, f.sz.var_key, f.zp.z_key, &f.state_m, f.sm);
+    f.grid = k::LassoFusedGrid(f.m, f.n, dt);
+    f.w = DVec::Zeros(f.m, dt);
+    f.p = DVec::Zeros(f.m, dt);
+    f.tpart = DVec::Empty(static_cast<int64_t>(f.grid) * f.m, dt);
+    if (D.symmetric() && f.m >= 1024 && !D.trans()) {
+      f.symv_work = DVec::Empty(k::SymvWorkspace(f.m), dt);
+      f.symv_packed = PackInverse(D, f.m);
+    }
+    {
+      k::LassoFusedArgs& a = f.pass;
+      a.m = f.m;
+      a.n = f.n;
+      a.lda = L.rows();
+      a.A = L.data();
+      a.chain = 2;
+      a.e0 = f.sn[6];
+      k::LassoInstance& s = a.inst;
+      s.w = f.w;
+      s.tpart = f.tpart;
+      s.p = f.p;
+      s.rhs = f.zp.rhs_arg;
+      s.u = f.sn[0];
+      s.x1 = f.sn[1];
+      s.x0 = f.sn[2];
+      s.y1 = f.sn[3];
+      s.y0 = f.sn[4];
+      s.y1prev = f.sn[5];
+      s.alpha_vec = f.sx.alpha_vec;
+      s.beta_vec = f.sx.beta_vec;
+      s.kappa = s.pkappa = -L.scale();
+      s.Bs = f.sx.Bs;
+      s.Cs = f.sx.Cs;
+      s.a1 = f.ax;
+      s.lam = f.sx.lam;
+      s.alpha = f.sx.alpha;
+      s.beta = f.sx.beta;
+      s.M = f.sx.M;
+    }
+    if (f.has_z) {
+      k::ZeroRowsArgs& r = f.rows;
+      r.m = f.m;
+      r.nparts = f.grid;
+      r.w = f.w;
+      r.tpart = f.tpart;
+      r.r = f.p;
+      r.rhs = f.zp.rhs_arg;
+      r.g = f.sz.g;
+      r.u = f.sm[0];
+      r.z = f.sm[1];
+      r.zq = f.sm[2];
+      r.yz = f.sm[3];
+      r.yq = f.sm[4];
+      r.yzprev = f.sm[5];
+      r.yqprev = f.sm[6];
+      r.alpha_vec = f.sz.alpha_vec;
+      r.beta_vec = f.sz.beta_vec;
+      r.e = f.zp.e;
+      r.pkappa = -L.scale();
+      r.Bs = f.sz.Bs;
+      r.Cs = f.sz.Cs;
+      r.a1 = f.az;
+      r.lam = f.sz.lam;
+      r.alpha = f.sz.alpha;
+      r.beta = f.sz.beta;
+      r.M = f.sz.M;
+    }
+    ResetGraph();
+    zs_ = f;
+    // the generic containers become views of the fused state
+    const std::string &ckx = zs_.zp.x_constraint_key, &ckz = zs_.zp.z_constraint_key;
+    x_.assign(N_, BlockVector());
+    y_.assign(N_, BlockVector());
+    y_prev_.assign(N_, BlockVector());
+    u_ = BlockVector();
+    u_.Set(ckx, zs_.sn[0]);
+    x_[zs_.ix].Set(zs_.sx.var_key, zs_.sn[1]);
+    x_[N_ - 1].Set(zs_.zp.x_key, zs_.sn[2]);
+    y_[zs_.ix].Set(ckx, zs_.sn[3]);
+    y_[N_ - 1].Set(ckx, zs_.sn[4]);
+    y_prev_[zs_.ix].Set(ckx, zs_.sn[5]);
+    y_prev_[N_ - 1].Set(ckx, zs_.sn[6]);
+    if (zs_.has_z) {
+      u_.Set(ckz, zs_.sm[0]);
+      x_[zs_.iz].Set(zs_.sz.var_key, zs_.sm[1]);
+      x_[N_ - 1].Set(zs_.zp.z_key, zs_.sm[2]);
+      y_[zs_.iz].Set(ckz, zs_.sm[3]);
+      y_[N_ - 1].Set(ckz, zs_.sm[4]);
+      y_prev_[zs_.iz].Set(ckz, zs_.sm[5]);
+      y_prev_[N_ - 1].Set(ckz, zs_.sm[6]);
+    }
+    zfused_ = true;
+    ZeroForwardFromState();
+  }
+
+  // w of the first sweep from the current state, with the generic operators: the sweep up to the
+  // ZERO prox's input v (on copies: the state is not touched), then the forward substitution
+  // r = (rhs - e v_z) - L(arg, x') v_x and the inverse apply.
+  void ZeroForwardFromState() {
+    ZeroFusedState& f = zs_;
+    BlockVector u = u_;
+    for (int i = 0; i < N_; ++i) u -= y_[i];
+    for (int i = 0; i + 1 < N_; ++i) {
+      u += y_[i];
+      u -= A_ * prox_[i]->Apply(u);
+    }
+    u += y_[N_ - 1];
+    if (f.zp.rhs_arg.n != 0) k::Copy(f.p, f.zp.rhs_arg);
+    else k::Fill(f.p, 0.0);
+    if (f.has_z) k::Axpby(f.p, -f.zp.e, u(f.zp.z_constraint_key), 1.0);
+    f.zp.L_arg_x->Apply(-1.0, u(f.zp.x_constraint_key), 1.0, f.p);
+    ZeroApplyInverse();
+  }
+
+  void ZeroApplyInverse() {
+    ZeroFusedState& f = zs_;
+    const DenseMatrixImpl& D = *f.zp.Dinv_arg;
+    if (f.symv_packed.n > 0) k::SymvPacked(f.m, D.scale(), f.symv_packed, f.p, 0.0, f.w, &f.symv_work);
+    else D.Apply(1.0, f.p, 0.0, f.w);
+  }
+
+  void ZeroSweep() {
+    ZeroFusedState& f = zs_;
+    k::LassoFusedPass(f.pass);
+    if (f.has_z)
+      k::ZeroFusedRows(f.rows);
+    else
+      k::ReducePartials(f.m, f.grid, f.tpart, f.pass.inst.pkappa, 0.0, f.p,
+                        f.zp.rhs_arg.n != 0 ? &f.zp.rhs_arg : nullptr);
+    ZeroApplyInverse();
+  }
+
   void ResetGraph() {
     if (graph_exec_) (void)hipGraphExecDestroy(graph_exec_);
     if (graph_) (void)hipGraphDestroy(graph_);
@@ -1033,7 +1261,7 @@ class ProxADMMSolver final : public Solver {
   }
 
   bool GenericGraphWanted(int count) {
-    if (fused_ || !capture_safe_ || eager_sweeps_ < SweepGraph::EagerSweepsFirst() ||
+    if (fused_ || zfused_ || !capture_safe_ || eager_sweeps_ < SweepGraph::EagerSweepsFirst() ||
         static_cast<int>(y_prev_.size()) != N_)
       return false;
     return gg_.Wanted(count, StateHandles());
@@ -1181,6 +1409,10 @@ class ProxADMMSolver final : public Solver {
   void Sweep() override {  // :135-147
     if (fused_) {
       FusedSweep();
+      return;
+    }
+    if (zfused_) {
+      ZeroSweep();
       return;
     }
     y_prev_ = y_;  // shallow: blocks are replaced, never mutated, below
@@ -1345,8 +1577,25 @@ class ProxADMMSolver final : public Solver {
     DVec table;              // their descriptors on the device (LassoBatchUpload)
     WideSweep ws;
   };
+  struct ZeroFusedState {
+    ZeroProjectionDesc zp;
+    ScaledZoneDesc sx, sz;  // the separable terms on x and on z
+    bool has_z = false;
+    int ix = -1, iz = -1;   // their positions among the objective terms
+    double ax = 0, az = 0;  // constraint maps of x and z (their copies': 1)
+    int64_t m = 0, n = 0;
+    int grid = 0;
+    // u, var, copy, y of the separable term, y of the ZERO term, the two previous y: slices of one
+    // buffer per side (n: the x constraint's rows, m: the z constraint's)
+    DVec state_n, state_m, sn[7], sm[7];
+    DVec w, p, tpart, symv_work, symv_packed;
+    k::LassoFusedArgs pass;
+    k::ZeroRowsArgs rows;
+  };
   bool fused_ = false;
+  bool zfused_ = false;
   FusedState fs_;
+  ZeroFusedState zs_;
   int norm_slot_ = 0;
   hipGraph_t graph_ = nullptr;
   hipGraphExec_t graph_exec_ = nullptr;

@@ -322,6 +322,10 @@ int eps_set_option(const char* key, const char* value) {
       for (const char* v : {"0", "pass", "wide", "auto"}) ok = ok || std::strcmp(value, v) == 0;
       if (!ok) EPS_FATAL("fused_matrix must be 0, pass, wide or auto, got " << value);
       setenv("EPSILON_HIP_FUSED_MATRIX", value, 1);
+    } else if (std::strcmp(key, "fused_zero") == 0) {
+      if (std::strcmp(value, "0") != 0 && std::strcmp(value, "auto") != 0)
+        EPS_FATAL("fused_zero must be 0 or auto, got " << value);
+      setenv("EPSILON_HIP_FUSED_ZERO", value, 1);
     } else if (std::strcmp(key, "graph_generic") == 0) {
       setenv("EPSILON_HIP_GRAPH_GENERIC", value, 1);
     } else if (std::strcmp(key, "refine") == 0) {

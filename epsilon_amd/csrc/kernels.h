@@ -80,10 +80,30 @@ struct LassoFusedArgs {
   // chain = 1: the two-block driver's sweep (prox_admm_two_block.cc:97-112); the arrays then mean
   // u -> u0, y0 -> z0, y1 -> z1, y1prev -> z0_prev, e0 -> u1, e1 -> z1_prev; a0, a1: the consensus
   // constraint a0 x0 + a1 x1 = 0 the z-update projects onto.  f32 and f64.
+  // chain = 2: the sweep of a ZERO-term problem (scaled-zone term on x first, the
+  // projection's copy x' = v_x + kappa A^T w last); the arrays then mean u -> u on the x constraint,
+  // x0 -> x', x1 -> x, y0 -> y of the ZERO term, y1 -> y of the x term, y1prev -> the x term's
+  // previous y, e0 -> the ZERO term's previous y.  Profile tag "zero_fused".  f32 and f64.
   int chain = 0;
   double a0 = 1;
   DVec e0, e1;
 };
+
+// The row side of the ZERO-term sweep (kernels_fused.hip), one launch, profile tag
+// "zero_fused_rows".  Per row: finishes sweep k with w (z' = v_z - e w, y and u on the z
+// constraint), runs the z term of sweep k + 1 (zone(Bs v + g) - g, scaled by Cs), forms the next
+// v_z, sums the pass's partials in a fixed order and writes r = (rhs - e v_z) + pkappa sum(tpart).
+struct ZeroRowsArgs {
+  int64_t m = 0;
+  int nparts = 0;
+  DVec w, tpart, r, rhs, g;            // rhs, g: optional (empty: zero)
+  DVec u, z, zq, yz, yq, yzprev, yqprev;  // m each, in place: u on the z constraint, z, z', y of the
+                                          // z term and of the ZERO term, their previous values
+  DVec alpha_vec, beta_vec;            // optional per-row alpha / beta of the scaled zone
+  double e = 0, pkappa = 0;
+  double Bs = 0, Cs = 0, a1 = 0, lam = 0, alpha = 1, beta = 1, M = 0;
+};
+void ZeroFusedRows(const ZeroRowsArgs& args);
 bool LassoFusedSupported(int64_t m, int64_t n, const DVec& A, int64_t lda);
 int LassoFusedGrid(int64_t m, int64_t n, DType dt = F32);
 int LassoFusedBlock(int64_t m, int64_t n, DType dt);  // threads per workgroup of the pass

@@ -45,6 +45,8 @@ constexpr int kBlock = 256;
 // holds two rows, so 512 threads x 10 chunks own up to 10240 rows.
 // MODE 0: the multi-block driver's chain (ChainOneT).  MODE 1: the two-block driver's (ChainTwoBlockT);
 // the state arrays then mean u -> u0, y0 -> z0, y1 -> z1, y1prev -> z0_prev, e0 -> u1, e1 -> z1_prev.
+// MODE 2: the column side of a ZERO-term problem (ZeroChainT); x0 -> x', x1 -> x, y0 -> the ZERO
+// term's y, y1 -> the x term's y, y1prev / e0 -> their previous values.
 template <class T, int NR, int BS, int MODE>
 __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
     int64_t m, int64_t n, const T* __restrict__ A, int64_t lda, const T* __restrict__ w,
@@ -128,6 +130,18 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
         y1[j] = ny1;
         u[j] = nu;
       }
+    } else if (MODE == 2) {
+      T ns, nq, nys, nyq, nu;
+      v0n = ZeroChainT<T>(d, cj, T(0), uj, y1j, y0j, &ns, &nq, &nys, &nyq, &nu);
+      if (tid == 0) {
+        y1prev[j] = y1j;
+        e0[j] = y0j;
+        x1[j] = ns;
+        x0[j] = nq;
+        y1[j] = nys;
+        y0[j] = nyq;
+        u[j] = nu;
+      }
     } else {
       T nx0, nx1, nz0, nz1, nu0, nu1;
       v0n = ChainTwoBlockT<T>(d, cj, y0j, y1j, uj, u1j, &nx0, &nx1, &nz0, &nz1, &nu0, &nu1);
@@ -160,10 +174,11 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
 template <class T, int NR, int BS>
 void LaunchFused(const LassoFusedArgs& a, int grid) {
   const LassoBatchInst<T> i = Narrow<T>(a.inst);
-  T* e0 = a.chain == 1 ? a.e0.as<T>() : nullptr;
+  T* e0 = a.chain != 0 ? a.e0.as<T>() : nullptr;
   T* e1 = a.chain == 1 ? a.e1.as<T>() : nullptr;
   hipLaunchKernelGGL(
-      (a.chain == 1 ? LassoFusedStreamKernelT<T, NR, BS, 1> : LassoFusedStreamKernelT<T, NR, BS, 0>),
+      (a.chain == 1 ? LassoFusedStreamKernelT<T, NR, BS, 1>
+                    : a.chain == 2 ? LassoFusedStreamKernelT<T, NR, BS, 2> : LassoFusedStreamKernelT<T, NR, BS, 0>),
       dim3(grid), dim3(BS), 0, Runtime::Get().stream(), a.m, a.n, a.A.as<T>(), a.lda, i.w,
       ScalarsOf<T>(i, a.a0, a.inst.a1), i.u, i.x0, i.x1, i.y0, i.y1, i.y1prev, i.tpart, a.epoch, e0, e1);
 }
@@ -190,7 +205,86 @@ void LaunchFusedT(const LassoFusedArgs& a, int grid, int block) {
   else LaunchFused<T, 10, 512>(a, grid);
 }
 
+// ---- the row side of a ZERO-term sweep ------------------------------------------------------------
+// A workgroup owns kZeroRows rows: thread (rl, pl) = (t % kZeroRows, t / kZeroRows) sums row rl's
+// partials k = pl, pl + kZeroLanes, ... (independent loads), the lanes of a row are added in lane
+// order through LDS - a fixed summation order - and lane 0 runs the row's chain (ZeroChainT with
+// d = w_i, kappa = -e) and writes r.  A workgroup reads and writes the state of its own rows only.
+constexpr int kZeroRows = 16, kZeroLanes = kBlock / kZeroRows;
+
+template <class T>
+__global__ __launch_bounds__(kBlock) void ZeroFusedRowsKernel(
+    int64_t m, int nparts, const T* __restrict__ tpart, const T* __restrict__ w, FusedScalarsT<T> c,
+    T pkappa, const T* __restrict__ rhs, const T* __restrict__ g, T* u, T* z, T* zq, T* yz, T* yq,
+    T* yzprev, T* yqprev, T* __restrict__ r) {
+  __shared__ T part[kZeroLanes][kZeroRows];
+  const int t = threadIdx.x, rl = t % kZeroRows, pl = t / kZeroRows;
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kZeroRows + rl;
+  T s = T(0);
+  if (i < m) {
+    const T* p = tpart + i;
+    int k = pl;
+    for (; k + 7 * kZeroLanes < nparts; k += 8 * kZeroLanes) {
+      T v[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v[q] = p[static_cast<int64_t>(k + q * kZeroLanes) * m];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) s += v[q];
+    }
+    for (; k < nparts; k += kZeroLanes) s += p[static_cast<int64_t>(k) * m];
+  }
+  part[pl][rl] = s;
+  __syncthreads();
+  if (pl != 0 || i >= m) return;
+  T sum = part[0][rl];
+#pragma unroll
+  for (int q = 1; q < kZeroLanes; ++q) sum += part[q][rl];
+  FusedScalarsT<T> ci = c;
+  if (c.alpha_v != nullptr) ci.alpha = c.alpha_v[i];
+  if (c.beta_v != nullptr) ci.beta = c.beta_v[i];
+  const T gi = g != nullptr ? g[i] : T(0);
+  const T yzi = yz[i], yqi = yq[i];
+  T ns, nq, nys, nyq, nu;
+  const T vn = ZeroChainT<T>(w[i], ci, gi, u[i], yzi, yqi, &ns, &nq, &nys, &nyq, &nu);
+  yzprev[i] = yzi;
+  yqprev[i] = yqi;
+  z[i] = ns;
+  zq[i] = nq;
+  yz[i] = nys;
+  yq[i] = nyq;
+  u[i] = nu;
+  // forward substitution of the next sweep: (rhs - e v_z) first, then the product with x' on top
+  const T base = c.kappa * vn + (rhs != nullptr ? rhs[i] : T(0));
+  r[i] = pkappa * sum + base;
+}
+
+template <class T>
+void LaunchZeroRows(const ZeroRowsArgs& a) {
+  auto opt = [](const DVec& v) { return v.n > 0 ? v.as<T>() : nullptr; };
+  FusedScalarsT<T> c = {static_cast<T>(-a.e), static_cast<T>(a.Bs), static_cast<T>(a.Cs), static_cast<T>(a.a1),
+                        static_cast<T>(a.lam), static_cast<T>(a.alpha), static_cast<T>(a.beta), static_cast<T>(a.M),
+                        T(1), T(1), opt(a.alpha_vec), opt(a.beta_vec)};
+  const unsigned grid = static_cast<unsigned>((a.m + kZeroRows - 1) / kZeroRows);
+  hipLaunchKernelGGL(ZeroFusedRowsKernel<T>, dim3(grid), dim3(kBlock), 0, Runtime::Get().stream(), a.m, a.nparts,
+                     a.tpart.as<T>(), a.w.as<T>(), c, static_cast<T>(a.pkappa), opt(a.rhs), opt(a.g), a.u.as<T>(),
+                     a.z.as<T>(), a.zq.as<T>(), a.yz.as<T>(), a.yq.as<T>(), a.yzprev.as<T>(), a.yqprev.as<T>(),
+                     a.r.as<T>());
+}
+
 }  // namespace
+
+void ZeroFusedRows(const ZeroRowsArgs& a) {
+  const DType dt = a.w.dt;
+  EPS_CHECK(a.m >= 1 && a.nparts >= 1 && a.tpart.dt == dt && a.tpart.n >= static_cast<int64_t>(a.nparts) * a.m);
+  for (const DVec* v : {&a.w, &a.r, &a.u, &a.z, &a.zq, &a.yz, &a.yq, &a.yzprev, &a.yqprev})
+    EPS_CHECK(v->n == a.m && v->dt == dt);
+  for (const DVec* v : {&a.rhs, &a.g, &a.alpha_vec, &a.beta_vec})
+    if (v->n > 0) EPS_CHECK(v->n == a.m && v->dt == dt);
+  ProfScope prof("zero_fused_rows", a.m, a.nparts);
+  if (dt == F32) LaunchZeroRows<float>(a);
+  else LaunchZeroRows<double>(a);
+  EPS_HIP(hipGetLastError());
+}
 
 namespace {
 
@@ -332,12 +426,13 @@ void LassoFusedPass(const LassoFusedArgs& a) {
   for (const DVec* v : {&s.alpha_vec, &s.beta_vec})
     if (v->n > 0) EPS_CHECK(v->n == a.n && v->dt == dt);
   if (a.chain == 1) EPS_CHECK(a.e0.n == a.n && a.e1.n == a.n && a.e0.dt == dt && a.e1.dt == dt);
+  if (a.chain == 2) EPS_CHECK(a.e0.n == a.n && a.e0.dt == dt);
   const int grid = LassoFusedGrid(a.m, a.n, dt);
   const int block = LassoFusedBlock(a.m, a.n, dt);
   EPS_CHECK(s.tpart.n >= static_cast<int64_t>(grid) * a.m && s.tpart.dt == dt);
   EPS_CHECK(reinterpret_cast<uintptr_t>(s.w.data()) % 16 == 0 &&
             reinterpret_cast<uintptr_t>(s.tpart.data()) % 16 == 0);
-  ProfScope prof("lasso_fused", a.m, a.n);
+  ProfScope prof(a.chain == 2 ? "zero_fused" : "lasso_fused", a.m, a.n);
   if (dt == F32) LaunchFusedT<float>(a, grid, block);
   else LaunchFusedT<double>(a, grid, block);
   EPS_HIP(hipGetLastError());

@@ -122,6 +122,40 @@ __device__ inline T ChainOneT(T d, const FusedScalarsT<T>& c, T u, T y0p, T y1p,
   return ChainTailT<T>(h, xz, c, x0o, x1o, y0o, y1o, uo);
 }
 
+// ---- ZERO-term problems: per constraint row the sweep is
+//   u -= y_s; u -= y_q;  separable term: u += y_s, s = Cs (zone(Bs u + g) - g), y_s = a1 s, u -= y_s;
+//   ZERO term: u += y_q, v = u, q = v + (factor) * (product with w), y_q = q, u -= y_q
+// (prox_admm.cc:135-147 with the separable term before the ZERO term).  The head runs up to v and
+// needs the boundary state alone; the tail needs this sweep's w.
+template <class T> struct ZeroHeadT {
+  T s, ys, v;  // the separable term's variable and y; the ZERO prox's input on this row
+};
+template <class T>
+__device__ inline ZeroHeadT<T> ZeroHeadOfT(const FusedScalarsT<T>& c, T g, T u, T ysp, T yqp) {
+  const T ub = ((u - ysp) - yqp) + ysp;  // sweep start, then the separable term's u += y_s
+  const T vin = c.Bs * ub + g;           // VectorProx: B v + g            (vector_prox.cc:141)
+  const T xz = ScaledZoneOneT<T>(vin, c.lam, c.alpha, c.beta, c.M);
+  const T s = c.Cs * (xz - g);           // C (x - g)                      (vector_prox.cc:145)
+  const T ys = c.a1 * s;                 // y_s = A_ s
+  const T uc = ub - ys;                  // u -= y_s
+  return {s, ys, uc + yqp};              // ZERO term: u += y_q
+}
+// Finishes the sweep from the product `d` with this sweep's w (q = kappa d + v), writes the
+// boundary state and returns the NEXT sweep's v, computed in registers from that state.
+template <class T>
+__device__ inline T ZeroChainT(T d, const FusedScalarsT<T>& c, T g, T u, T ysp, T yqp, T* so, T* qo, T* yso,
+                               T* yqo, T* uo) {
+  const ZeroHeadT<T> h = ZeroHeadOfT<T>(c, g, u, ysp, yqp);
+  const T q = c.kappa * d + h.v;  // back substitution epilogue: alpha*acc + 1*y
+  const T un = h.v - q;           // y_q = q (its constraint map is I); u -= y_q
+  *so = h.s;
+  *qo = q;
+  *yso = h.ys;
+  *yqo = q;
+  *uo = un;
+  return ZeroHeadOfT<T>(c, g, un, h.ys, q).v;
+}
+
 // The group threshold of one row of a matrix variable (NORM_2 with axis = 1): SegNorm2Kernel's
 // expressions (kernels_segprox.hip) on the sum of squares `ss` of the row's threshold inputs,
 // accumulated in fp64 in member order.  Returns the factor of xz_i = T(scale * double(vin_i)).

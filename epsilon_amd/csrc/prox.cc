@@ -181,8 +181,9 @@ BlockVector VectorProx::Apply(const BlockVector& v) {  // vector_prox.cc:140-183
 }
 
 bool VectorProx::ScalarForm(std::string* var_key, std::string* constraint_key, double* Bs,
-                            double* Cs, double* lam) const {
-  if (input_.elementwise_ || !D_.data().empty() || !g_.data().empty()) return false;
+                            double* Cs, double* lam, DVec* g) const {
+  if (input_.elementwise_ || !D_.data().empty()) return false;
+  if (g == nullptr ? !g_.data().empty() : g_.data().size() > 1) return false;
   if (B_.data().size() != 1 || B_.data().begin()->second.size() != 1) return false;
   if (C_.data().size() != 1 || C_.data().begin()->second.size() != 1) return false;
   const auto& bcol = *B_.data().begin();  // (arg:0, constraint)
@@ -196,6 +197,13 @@ bool VectorProx::ScalarForm(std::string* var_key, std::string* constraint_key, d
   *Bs = GetScalar(Bm);
   *Cs = GetScalar(Cm);
   *lam = input_.lambda_;
+  if (g != nullptr) {
+    *g = DVec();
+    if (!g_.data().empty()) {
+      if (g_.data().begin()->first != ccol.first) return false;  // the offset of arg:0
+      *g = g_.data().begin()->second;
+    }
+  }
   return true;
 }
 
@@ -290,9 +298,15 @@ class ScaledZoneProx final : public VectorProx {
   }
 
  public:
-  bool DescribeScaledZone(ScaledZoneDesc* d) const override {
+  bool DescribeScaledZone(ScaledZoneDesc* d) const override { return Describe(d, false); }
+  bool DescribeScaledZoneOffset(ScaledZoneDesc* d) const override { return Describe(d, true); }
+
+ private:
+  bool Describe(ScaledZoneDesc* d, bool offset) const {
     if (has_axis_) return false;
-    if (!ScalarForm(&d->var_key, &d->constraint_key, &d->Bs, &d->Cs, &d->lam)) return false;
+    d->g = DVec();
+    if (!ScalarForm(&d->var_key, &d->constraint_key, &d->Bs, &d->Cs, &d->lam, offset ? &d->g : nullptr))
+      return false;
     d->alpha = alpha_.value;
     d->beta = beta_.value;
     d->alpha_vec = alpha_.is_vec ? alpha_.vec : DVec();
@@ -622,6 +636,64 @@ class ZeroProx final : public ProxOperator {
   }
   BlockVector Apply(const BlockVector& v) override {
     return chol_.Solve(b_ + v).Select(var_keys_);
+  }
+
+  // Pattern of the compiled graph forms: every variable of the term is a private
+  // copy tied to one constraint row with L(var, constraint) = -1, Dinv(constraint) = -1,
+  // Dinv(var) = 1; one copy (x') enters the arg row through a dense map, the other (z', optional)
+  // through a scalar; the order ends in the dense arg pivot.  Then with v the prox input
+  //   Solve(b_ + v)[x'] = v_x - L(arg,x')^T w,  [z'] = v_z - e w,
+  //   w = Dinv_arg ((rhs_arg - e v_z) - L(arg,x') v_x).
+  bool DescribeZeroProjection(ZeroProjectionDesc* d) const override {
+    const std::vector<std::string>& p = chol_.order();
+    if (chol_.refine_steps() > 0) return false;
+    const size_t nv = var_keys_.size();
+    if ((nv != 1 && nv != 2) || p.size() != 2 * nv + 1) return false;
+    const std::string& ak = p.back();
+    if (var_keys_.count(ak) != 0) return false;
+    const BlockMatrix& L = chol_.L();
+    const BlockMatrix& Di = chol_.D_inv();
+    auto is_scalar = [](const LinearMap& m, double a) {
+      return m.impl().type() == SCALAR_MATRIX && GetScalar(m) == a;
+    };
+    if (!Di.has_key(ak, ak) || Di(ak, ak).impl().type() != DENSE_MATRIX) return false;
+    *d = ZeroProjectionDesc();
+    for (const std::string& vk : var_keys_) {
+      // its constraint row: the one key before the arg pivot whose column reaches vk
+      std::string ck;
+      for (size_t i = 0; i + 1 < p.size(); ++i) {
+        if (var_keys_.count(p[i]) != 0 || !L.has_key(vk, p[i])) continue;
+        if (!ck.empty()) return false;
+        ck = p[i];
+      }
+      if (ck.empty() || L.has_key(ak, ck) || !L.has_key(ak, vk)) return false;
+      if (!Di.has_key(ck, ck) || !Di.has_key(vk, vk)) return false;
+      if (!is_scalar(L(vk, ck), -1.0) || !is_scalar(Di(ck, ck), -1.0) || !is_scalar(Di(vk, vk), 1.0))
+        return false;
+      for (const std::string& other : var_keys_)
+        if (other != vk && (L.has_key(other, vk) || L.has_key(vk, other) || L.has_key(other, ck))) return false;
+      const LinearMap& Lav = L(ak, vk);
+      if (Lav.impl().type() == DENSE_MATRIX) {
+        if (d->L_arg_x) return false;
+        d->L_arg_x = std::static_pointer_cast<const DenseMatrixImpl>(Lav.ptr());
+        d->x_key = vk;
+        d->x_constraint_key = ck;
+      } else if (Lav.impl().type() == SCALAR_MATRIX) {
+        if (!d->z_key.empty()) return false;
+        d->e = GetScalar(Lav);
+        d->z_key = vk;
+        d->z_constraint_key = ck;
+      } else {
+        return false;
+      }
+    }
+    if (!d->L_arg_x || d->L_arg_x->trans() || (nv == 2 && d->z_key.empty())) return false;
+    for (const auto& kv : b_.data())
+      if (kv.first != ak) return false;
+    d->arg_key = ak;
+    d->Dinv_arg = std::static_pointer_cast<const DenseMatrixImpl>(Di(ak, ak).ptr());
+    d->rhs_arg = b_.has_key(ak) ? b_(ak) : DVec();
+    return true;
   }
 
  private:

@@ -52,6 +52,7 @@ struct ScaledZoneDesc {  // ScaledZoneProx with scalar H, A and uniform paramete
   double Bs = 0, Cs = 0;  // v' = Bs*v ; x = Cs*x'
   double lam = 0, alpha = 1, beta = 1, M = 0;
   DVec alpha_vec, beta_vec;  // per-element alpha / beta (SUM_QUANTILE with data vectors); empty: uniform
+  DVec g;  // constant offset of the argument, x = Cs * (zone(Bs*v + g) - g): DescribeScaledZoneOffset only
 };
 
 struct GroupNorm2Desc {  // Norm2Prox with axis = 1 on an n x cols argument: one group per row
@@ -59,6 +60,19 @@ struct GroupNorm2Desc {  // Norm2Prox with axis = 1 on an n x cols argument: one
   double Bs = 0, Cs = 0;  // v' = Bs*v ; x = Cs*x'
   double lam = 0;
   int64_t rows = 0, cols = 0;
+};
+
+// ZeroProx after block elimination [constraints and copies (scalar pivots) ..., arg]: the
+// projection onto {C x' + e z' + d = 0} of the graph-form problems,
+//   w = Dinv_arg (rhs_arg - e v_z - s C v_x),  x' = v_x - s C^T w,  z' = v_z - e w
+// with s C = L_arg_x (lazily scaled) and Dinv_arg = -(C C^T + e^2 I)^-1 as the factorisation holds it.
+struct ZeroProjectionDesc {
+  std::string x_key, z_key, arg_key;             // z_key empty: no z block (basis pursuit)
+  std::string x_constraint_key, z_constraint_key;
+  std::shared_ptr<const DenseMatrixImpl> L_arg_x;   // L(arg, x'): lazily scaled data matrix
+  std::shared_ptr<const DenseMatrixImpl> Dinv_arg;  // cached explicit inverse (with its sign)
+  double e = 0;                                     // L(arg, z')
+  DVec rhs_arg;                                     // constant part of the rhs on the arg row
 };
 
 class ProxOperator {  // reference prox/prox.h:37-43
@@ -69,6 +83,9 @@ class ProxOperator {  // reference prox/prox.h:37-43
   virtual bool DescribeLeastSquares(LeastSquaresDesc* d) const { return false; }
   virtual bool DescribeScaledZone(ScaledZoneDesc* d) const { return false; }
   virtual bool DescribeGroupNorm2(GroupNorm2Desc* d) const { return false; }
+  // DescribeScaledZone for an argument that may carry a constant offset (d->g; empty: none)
+  virtual bool DescribeScaledZoneOffset(ScaledZoneDesc* d) const { return false; }
+  virtual bool DescribeZeroProjection(ZeroProjectionDesc* d) const { return false; }
   // true: Apply is a fixed sequence of launches on the library's stream - no host
   // synchronisation, no decision on device data, no state carried from one call to the next -
   // so a sweep through this operator can be captured into a hipGraph and replayed (admm.cc).
@@ -136,8 +153,9 @@ class VectorProx : public ProxOperator {
   virtual void ApplyVector(const VectorProxInput& input, VectorProxOutput* output) = 0;
 
   // For DescribeScaledZone: true iff B_, C_ are single scalar blocks, no offset, scalar lambda.
+  // With `g` an offset on the argument row is accepted and handed out (empty: there is none).
   bool ScalarForm(std::string* var_key, std::string* constraint_key, double* Bs, double* Cs,
-                  double* lam) const;
+                  double* lam, DVec* g = nullptr) const;
 
  private:
   BlockMatrix B_, C_, D_;

@@ -524,6 +524,20 @@ def hinge_l1(m, n, lam=None, seed=0):
     return _graph_form(terms, C, None), dict(C=C, lam=lam)
 
 
+def deadzone_l1(m, n, frac=0.3, M=0.5, seed=0):
+    """eps-insensitive regression sum_i max(|a_i^T x - b_i| - M, 0) + lam ||x||_1: sum_deadzone(z)
+    with z = A x - b, lam = frac * max|A^T sign(b)|."""
+    rng = np.random.RandomState(seed)
+    A = rng.randn(m, n)
+    b = A.dot(rng.randn(n) * (rng.rand(n) < 0.1)) + rng.randn(m)
+    lam = frac * np.abs(A.T.dot(np.sign(b))).max()
+
+    def terms(x, z):
+        return [ir.prox(ProxFunction.SUM_DEADZONE, z, scaled_zone_params=wire.ProxScaledZoneParams(m=M)),
+                ir.prox(ProxFunction.NORM_1, x, alpha=lam)]
+    return _graph_form(terms, A, -b), dict(A=A, b=b, lam=lam, M=M)
+
+
 def quantile(m, n, tau=0.3, seed=0):
     """Quantile regression sum_i rho_tau(b_i - a_i^T x): sum_quantile(z), z = A x - b, with
     alpha = 1 - tau on the positive and beta = tau on the negative part of z."""

@@ -98,7 +98,14 @@ const char* eps_version(void);
  * pass ("pass": f32 and f64, per column the arithmetic of the fused vector lasso) or of
  * the wide kernels ("wide": f32 only, results to f32 rounding) inside one solve.  A forced route
  * that the problem cannot take and "0" mean the generic operator path; "auto" picks by shape.
- * Read at every Init.  Any other value is an error that names it (env EPSILON_HIP_FUSED_MATRIX). */
+ * Read at every Init.  Any other value is an error that names it (env EPSILON_HIP_FUSED_MATRIX).
+ * "fused_zero" = "auto" (default) | "0"  problems whose data enters through an equality, compiled
+ * as a ZERO term over private copies (basis pursuit; hinge, deadzone or quantile loss of
+ * z = C x + d with an l1 penalty): the sweep as one pass over C, one row kernel and the apply of
+ * the cached inverse.  Taken for fat C with 256 to 20480 rows (f64: 10240), rows a multiple of
+ * 4 (f64: 2), multi-block driver, one GPU, every operand in the compute type; anything else, "0"
+ * and "fused" = "0" mean the generic operator path.  Read at every Init.  Any other value is an
+ * error that names it (env EPSILON_HIP_FUSED_ZERO). */
 int eps_set_option(const char* key, const char* value);
 /* Number of visible HIP devices (0 if none); never fails. */
 int eps_device_count(void);
