@@ -4,7 +4,9 @@
 // src/epsilon/algorithms/prox_admm.cc:131-217) and `ProxADMMTwoBlockSolver` (Jacobi x-updates +
 // projection z-update, prox_admm_two_block.cc:96-156) behind the `Solver` base
 // (algorithms/solver.h:42-102).  All iterate state stays in HBM; the only host round trip in
-// the loop is one copy of the residual scalars every `epoch_iterations` sweeps.
+// the loop is one copy of the residual scalars every `epoch_iterations` sweeps.  A problem whose
+// structure has a fused sweep runs it through a `FusedRoute` (fused_route.h): the drivers know a
+// route only by that interface.
 //
 // Unlike the reference, a solver can be driven in pieces (Init / Run(k) / status / variable
 // read-back) so a caller can keep it - and its cached factorisation - alive across calls
@@ -22,10 +24,13 @@
 
 namespace eps {
 
+class FusedRoute;  // fused_route.h
+double Now();      // steady clock, seconds
+
 class Solver {
  public:
   Solver(pb::Problem problem, std::shared_ptr<DataMap> data, pb::SolverParams params);
-  virtual ~Solver() {}
+  virtual ~Solver();
 
   // Build operators and factorisations (everything the reference does in Init()).
   virtual void Init() = 0;
@@ -47,6 +52,15 @@ class Solver {
   // Batched solves: Init memoises its Gram products, inverses and packed inverse copies in `c`
   // instead of this solver's own cache, so instances that share the data matrix share them.
   void set_shared_cache(OpCache* c) { shared_cache_ = c; }
+  // What a group of batched solves (RunFusedBatches) needs of a member: the route of a fresh
+  // solve (null: none, or already run), the residual check at sweep `iter` in its two halves
+  // (scalars into the next slots; after the fetch the status - true: the member stops here), the
+  // end at max_iterations, and the group's loop time.
+  FusedRoute* batch_route() const;
+  void BatchLaunchCheck(int iter);
+  bool BatchFinishCheck();
+  void BatchFinishMaxIterations(int iter);
+  void BatchAddLoopTime(double seconds);
 
  protected:
   virtual void Sweep() = 0;
@@ -67,6 +81,7 @@ class Solver {
   virtual void EndResiduals() {}
   virtual void SaveSnapshot() {}
   virtual void RestoreSnapshot() {}
+  virtual void FinishRouteCheck() {}  // the status from the fetched scalars of route_'s own check
   void LogStatus();
   void FinishResiduals(double r2, double s2, double eps_pri, double eps_dual);
 
@@ -79,6 +94,7 @@ class Solver {
   bool finished_ = false;
   double init_seconds_ = 0, loop_seconds_ = 0;
   std::function<void(const std::string&)> log_;
+  std::unique_ptr<FusedRoute> route_;  // the fused sweep of the problem's structure (null: none)
   // Gram products / inverses of previous Inits of this solver, by content id (warm start).
   OpCache op_cache_;
   OpCache* shared_cache_ = nullptr;  // set_shared_cache
@@ -88,8 +104,8 @@ class Solver {
 std::unique_ptr<Solver> CreateSolver(pb::Problem problem, std::shared_ptr<DataMap> data,
                                      pb::SolverParams params);
 
-// Batched solves (eps_solve_batch).  Of the initialised, not yet run `solvers`, those whose sweep
-// is the multi-block driver's fused pass in a form the batched pass mirrors
+// Batched solves (eps_solve_batch, fused_route.cc).  Of the initialised, not yet run `solvers`, those
+// whose sweep is the lasso route's fused pass in a form the batched pass mirrors
 // (k::LassoBatchWidth) are grouped by shared data matrix and cached inverse; every group of two
 // or more runs its sweeps together (kernels_fused_batch.hip: one pass over A for up to KB
 // instances, one reduction and one inverse apply for all), with each instance's residual check
@@ -101,11 +117,5 @@ std::vector<bool> RunFusedBatches(const std::vector<Solver*>& solvers);
 // One prox evaluation (reference python/epopt/solvemodule.cc:189-242).
 BlockVector EvalProx(const pb::Expression& f_expr, double lambda, DataMap* data,
                      const BlockVector& v);
-
-// generic-path graph replay counters (eps_graph_stats)
-struct GraphStats {
-  long long replayed_sweeps = 0, captures = 0;
-  static GraphStats& Get();
-};
 
 }  // namespace eps

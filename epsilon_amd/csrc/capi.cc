@@ -326,8 +326,6 @@ int eps_set_option(const char* key, const char* value) {
       if (std::strcmp(value, "0") != 0 && std::strcmp(value, "auto") != 0)
         EPS_FATAL("fused_zero must be 0 or auto, got " << value);
       setenv("EPSILON_HIP_FUSED_ZERO", value, 1);
-    } else if (std::strcmp(key, "graph_generic") == 0) {
-      setenv("EPSILON_HIP_GRAPH_GENERIC", value, 1);
     } else if (std::strcmp(key, "refine") == 0) {
       if (std::strcmp(value, "auto") == 0) unsetenv("EPSILON_HIP_REFINE");
       else setenv("EPSILON_HIP_REFINE", value, 1);
@@ -672,15 +670,6 @@ int eps_block_solve_stats(double* max_condition, int* max_refine_steps, int rese
     if (max_condition) *max_condition = st.max_condition;
     if (max_refine_steps) *max_refine_steps = st.max_refine_steps;
     if (reset) st.Reset();
-  });
-}
-
-int eps_graph_stats(long long* replayed_sweeps, long long* captures, int reset) {
-  return Guard([&] {
-    GraphStats& g = GraphStats::Get();
-    if (replayed_sweeps) *replayed_sweeps = g.replayed_sweeps;
-    if (captures) *captures = g.captures;
-    if (reset) g = GraphStats();
   });
 }
 

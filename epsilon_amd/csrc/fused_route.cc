@@ -1,0 +1,1146 @@
+// The fused routes (fused_route.h): the lasso structure with its sharded / peer, whitened,
+// matrix-variable and wide forms and the batched solves that run on it, the ZERO-term structure,
+// and the lasso structure in two-block form.
+#include "fused_route.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+
+#include "admm.h"
+#include "comm.h"
+#include "kernels.h"
+
+namespace eps {
+namespace {
+
+// ---------------------------------------------------------------------------------------------------
+// What the routes share
+// ---------------------------------------------------------------------------------------------------
+
+// The scaled-zone fields of a kernel record (k::LassoInstance, k::ZeroRowsArgs) from the
+// operator's description; a1: the scalar of the term's variable in its consensus constraint.
+template <class Record>
+void SetThreshold(Record* s, const ScaledZoneDesc& z, double a1) {
+  s->alpha_vec = z.alpha_vec;
+  s->beta_vec = z.beta_vec;
+  s->Bs = z.Bs;
+  s->Cs = z.Cs;
+  s->a1 = a1;
+  s->lam = z.lam;
+  s->alpha = z.alpha;
+  s->beta = z.beta;
+  s->M = z.M;
+}
+
+// The consensus tie a0 copy + a1 var = 0: row `ck` of A holds scalar maps of length `len` on
+// `copy` and on `var`.  (That nothing else is in the row is the caller's count of A's columns.)
+bool ConsensusTie(const BlockMatrix& A, const std::string& ck, const std::string& copy, const std::string& var,
+                  int64_t len, double* a0, double* a1) {
+  if (copy == var || !A.has_key(ck, copy) || !A.has_key(ck, var)) return false;
+  const LinearMap& A0 = A(ck, copy);
+  const LinearMap& A1 = A(ck, var);
+  if (A0.impl().type() != SCALAR_MATRIX || A1.impl().type() != SCALAR_MATRIX) return false;
+  if (A0.impl().n() != len || A1.impl().n() != len) return false;
+  *a0 = GetScalar(A0);
+  *a1 = GetScalar(A1);
+  return true;
+}
+
+// w = Dinv p with every buffer at a fixed address (what a captured launch needs).  A symmetric
+// m x m inverse from m = 1024 up is applied from its lower tiles with a fixed workspace, and from
+// a tile-packed copy of them unless EPSILON_HIP_SYMV_PACKED=0 (the matrix as it lies): +m^2/2
+// values of memory for a tenth of a millisecond at Init.
+struct InverseApply {
+  std::shared_ptr<const DenseMatrixImpl> D;
+  int64_t m = 0;
+  DVec p, w, work, packed;
+
+  // p and w may hold `count` columns (column c at c * m): Column(c).  Instances that share the
+  // inverse and the cache `shared` (a batch) share one packed copy.
+  void Init(std::shared_ptr<const DenseMatrixImpl> D_, int64_t m_, const DVec& p_, const DVec& w_, OpCache* shared,
+            int64_t count = 1) {
+    D = std::move(D_);
+    m = m_;
+    p = p_;
+    w = w_;
+    if (!D->symmetric() || D->rows() != m || m < 1024 || D->trans()) return;
+    work = DVec::Empty(count * k::SymvWorkspace(m), p.dt);
+    static const bool pack = [] {
+      const char* e = std::getenv("EPSILON_HIP_SYMV_PACKED");
+      return !(e && e[0] == '0');
+    }();
+    if (!pack) return;
+    uint64_t key = 0;
+    if (shared != nullptr) {
+      key = HashCombine(HashCombine(reinterpret_cast<uintptr_t>(D->data().data()), 0x9ac4ed), m);
+      if (auto hit = shared->Find(key)) {
+        packed = hit->data();
+        return;
+      }
+    }
+    packed = k::SymvPack(m, D->data(), m);
+    if (key) shared->Put(key, std::make_shared<DenseMatrixImpl>(packed, packed.n, 1, false, 1.0, key));
+  }
+  InverseApply Column(int64_t c) const {
+    InverseApply a = *this;
+    a.p = p.Slice(c * m, m);
+    a.w = w.Slice(c * m, m);
+    if (work.n > 0) a.work = work.Slice(c * k::SymvWorkspace(m), k::SymvWorkspace(m));
+    return a;
+  }
+  void Apply() const {
+    if (packed.n > 0) k::SymvPacked(m, D->scale(), packed, p, 0.0, w, &work);
+    else if (work.n > 0) k::Symv(m, D->scale(), D->data(), m, p, 0.0, w, &work);
+    else D->Apply(1.0, p, 0.0, w);
+  }
+};
+
+// A slice of a route's state and the block of the driver's containers it stands for.
+struct StateSlice {
+  BlockVector* home;
+  std::string key;
+  DVec v;
+  bool take = true;  // false: a "previous iterate", written by every sweep before it is read
+};
+// The slices take over what their blocks hold (warm start); then `homes`, the driver's
+// containers, become views of the slices and of nothing else.
+void AdoptState(const std::vector<StateSlice>& table, const std::vector<BlockVector*>& homes) {
+  for (const StateSlice& s : table) {
+    if (!s.take || !s.home->has_key(s.key)) continue;
+    EPS_CHECK((*s.home)(s.key).n == s.v.n);
+    k::Copy(s.v, (*s.home)(s.key));
+  }
+  for (BlockVector* h : homes) *h = BlockVector();
+  for (const StateSlice& s : table) s.home->Set(s.key, s.v);
+}
+std::vector<BlockVector*> Homes(const MultiBlockParts& a) {
+  std::vector<BlockVector*> h = {&a.u};
+  for (auto* c : {&a.x, &a.y, &a.y_prev})
+    for (BlockVector& v : *c) h.push_back(&v);
+  return h;
+}
+
+bool FusedDisabled() {  // EPSILON_HIP_FUSED=0 (eps_set_option "fused"), read at every Init
+  const char* env = std::getenv("EPSILON_HIP_FUSED");
+  return env && env[0] == '0';
+}
+
+int BatchWideMin();  // (with the batched solves below)
+
+// Matrix variables X (n x k) under the data map I_k (x) A: the k columns run as k members of the
+// batched kernels inside one solve (LassoRoute).  Below this many rows of A the solve keeps the
+// generic operator path (a constant: no crossover was measured).
+constexpr int64_t kMatrixFusedMinRows = 256;
+
+// EPSILON_HIP_FUSED_MATRIX (eps_set_option "fused_matrix"), read at every Init.
+enum MatrixRoute { kMatrixOff, kMatrixAuto, kMatrixPass, kMatrixWide };
+MatrixRoute FusedMatrixMode() {
+  const char* e = std::getenv("EPSILON_HIP_FUSED_MATRIX");
+  if (e == nullptr || std::strcmp(e, "auto") == 0) return kMatrixAuto;
+  if (std::strcmp(e, "0") == 0) return kMatrixOff;
+  if (std::strcmp(e, "pass") == 0) return kMatrixPass;
+  if (std::strcmp(e, "wide") == 0) return kMatrixWide;
+  EPS_FATAL("fused_matrix must be 0, pass, wide or auto, got " << e);
+}
+
+// ZERO-term problems (basis pursuit, hinge / deadzone + l1 in graph form) on the fused sweep
+// (ZeroRoute).  Below this many rows of the data matrix the solve keeps the
+// generic operator path (a constant: no crossover was measured).
+constexpr int64_t kZeroFusedMinRows = 256;
+
+// EPSILON_HIP_FUSED_ZERO (eps_set_option "fused_zero"), read at every Init.
+bool FusedZeroAuto() {
+  const char* e = std::getenv("EPSILON_HIP_FUSED_ZERO");
+  if (e == nullptr || std::strcmp(e, "auto") == 0) return true;
+  if (std::strcmp(e, "0") == 0) return false;
+  EPS_FATAL("fused_zero must be 0 or auto, got " << e);
+}
+
+// One sweep of a panel of up to 64 f32 members on the wide route (kernels_fused_wide.hip): back
+// product + chain, forward product, reduction and - unless whitened - the cached inverse times
+// the panel.  The workspaces depend on (m, n) alone and serve every panel in turn.
+struct WideSweep {
+  static constexpr int PW = k::kLassoWidePanel;
+  int64_t m = 0, n = 0, lda = 0, ldv = 0, panel_len = 0;
+  DVec A;
+  bool whiten = false;
+  const DenseMatrixImpl* D = nullptr;  // the cached inverse (not whitened)
+  DVec V, T, apart;
+  int64_t akc = 0, afull = 0, arem = 0, aparts = 0;
+
+  void Init(int64_t m_, int64_t n_, const DVec& A_, int64_t lda_, bool whiten_, const DenseMatrixImpl* D_) {
+    m = m_;
+    n = n_;
+    A = A_;
+    lda = lda_;
+    whiten = whiten_;
+    D = D_;
+    ldv = (n + 63) / 64 * 64;
+    panel_len = static_cast<int64_t>(PW) * m;
+    V = DVec::Zeros(static_cast<int64_t>(PW) * ldv, F32);
+    T = DVec::Empty(static_cast<int64_t>(k::LassoWideSlabs(m, n)) * panel_len, F32);
+    // ranges of the inverse apply's contraction: at most 64, each a multiple of 32 rows
+    akc = std::max<int64_t>(32, ((m + 63) / 64 + 31) / 32 * 32);
+    afull = m / akc;
+    arem = m - afull * akc;
+    aparts = afull + (arem > 0 ? 1 : 0);
+    apart = whiten ? DVec() : DVec::Empty(aparts * panel_len, F32);
+  }
+
+  // Wp = Dinv Pp: always PW columns - the product kernel and its contraction order must not
+  // depend on the number of members.  The contraction is split into `aparts` ranges of `akc`
+  // rows whose products are summed by ReducePartials: one chain over all m rows would carry the
+  // rounding of an m-term sequential sum into w.
+  void ApplyInverse(const DVec& Pp, const DVec& Wp) const {
+    const int64_t sA = D->trans() ? akc : akc * D->rows();
+    k::GemmBatched(D->trans(), false, m, PW, akc, D->scale(), D->data(), D->rows(), sA, Pp, m, akc, 0.0, apart, m,
+                   panel_len, afull);
+    if (arem > 0) {
+      const int64_t oA = afull * sA, oB = afull * akc;
+      k::GemmBatched(D->trans(), false, m, PW, arem, D->scale(), D->data().Slice(oA, D->data().n - oA), D->rows(),
+                     0, Pp.Slice(oB, Pp.n - oB), m, 0, 0.0, apart.Slice(afull * panel_len, panel_len), m, 0, 1);
+    }
+    k::ReducePartials(panel_len, static_cast<int>(aparts), apart, 1.0, 0.0, Wp);
+  }
+
+  // slots [first, first + nk) of `table`, `live` as LassoWideBack's mask; Wp / Pp: the panel's w
+  // and p (Pp unused when whitened: the reduction writes w_hat into Wp through the descriptors)
+  void Run(const DVec& table, int first, int nk, uint64_t live, const DVec& Wp, const DVec& Pp,
+           const double* group_lam = nullptr) const {
+    k::LassoWideBack(m, n, lda, A, table, first, nk, live, Wp, m, V, ldv, group_lam);
+    k::LassoWideForward(m, n, lda, A, nk, V, ldv, T, m);
+    k::LassoWideReduce(m, n, table, first, nk, live, T, m);
+    if (!whiten) ApplyInverse(Pp, Wp);
+  }
+};
+
+// ---------------------------------------------------------------------------------------------------
+// The lasso route: "least squares + separable threshold" (kernels_fused.hip)
+// ---------------------------------------------------------------------------------------------------
+// Recognised structure (the compiled lasso): two terms [SUM_SQUARE with a dense
+// argument map, scaled-zone prox with scalar maps], one consensus constraint a0 x' + a1 x = 0
+// with a0 = 1 and no constant.  The sweep is then: one fused pass over A (back substitution of
+// this sweep, elementwise chain, forward substitution of the next sweep), a partial-sum
+// reduction (+ the all-reduce when sharded) and the apply of the cached inverse.
+struct LassoRoute final : FusedRoute {
+  LeastSquaresDesc ls;
+  ScaledZoneDesc sz;
+  DType dt = F32;
+  double a1 = 0;
+  int64_t m = 0, n = 0;
+  int grid = 0;
+  int64_t slab = 0;  // rows of the cached inverse applied per rank (sharded runs)
+  bool sharded = false;    // the least-squares variable is split over the ranks
+  bool use_peer = false;   // exchanges ride in the sweep's kernels (peer window), not in RCCL
+  bool peer_slab = false;  // ... and the inverse is applied by row slabs
+  DVec w, p, tpart, wpad, wslice;
+  InverseApply inv;          // (unused when whitened or wide)
+  DVec state_all, snapshot;  // x0, x1, y0, y1, u, y1prev in one buffer; its copy at a check
+  DVec norm_work;            // partials + ticket of the one-launch residual norms
+  int norm_slot = 0;
+  bool whiten = false;       // the pass streams Ahat = X A, w holds X p (EnableWhiten)
+  double wscale = 1;         // c of Dinv_arg = c X^T X
+  DVec X, Ahat, rhat;        // L^-1 of the inverse, X A (ld m), X rhs_arg (empty: no rhs)
+  k::LassoFusedArgs pass;    // the state vectors, and what the pass and a batch read of the rest (BuildPass)
+  // matrix variable (n x cols under I_cols (x) A): its columns are members of the batched kernels
+  int64_t cols = 1;
+  bool group = false;      // the threshold is the group shrinkage of the rows (weight sz.lam)
+  int64_t group_rows = 0;
+  bool wide = false;       // the wide route (f32): w and p are whole panels of 64 members
+  bool rhs_aligned = true;
+  std::vector<k::LassoInstance> members;
+  DVec table;              // their descriptors on the device (LassoBatchUpload)
+  WideSweep ws;
+
+  bool Enable(const MultiBlockParts& a) {
+    if (FusedDisabled() || a.prox.size() != 2 || a.num_constraints != 1 || !a.b.data().empty()) return false;
+    const ShardSpec& sh = ShardSpec::Get();
+    // consensus form: the threshold step averages over the ranks, which the fused pass does not
+    if (sh.active() && sh.consensus_terms()) return false;
+    if (!a.prox[0]->DescribeLeastSquares(&ls)) return false;
+    cols = ls.cols;
+    const MatrixRoute matrix_mode = cols > 1 ? FusedMatrixMode() : kMatrixAuto;
+    if (cols > 1 && (matrix_mode == kMatrixOff || sh.active())) return false;
+    if (!a.prox[1]->DescribeScaledZone(&sz)) {
+      // group lasso: one group per row of the n x cols variable
+      GroupNorm2Desc gn;
+      if (cols == 1 || !a.prox[1]->DescribeGroupNorm2(&gn) || gn.cols != cols) return false;
+      group = true;
+      group_rows = gn.rows;
+      sz = ScaledZoneDesc();
+      sz.var_key = gn.var_key;
+      sz.constraint_key = gn.constraint_key;
+      sz.Bs = gn.Bs;
+      sz.Cs = gn.Cs;
+      sz.lam = gn.lam;
+    }
+    dt = a.data->dtype();
+    if ((sz.alpha_vec.n > 0 && sz.alpha_vec.dt != dt) || (sz.beta_vec.n > 0 && sz.beta_vec.dt != dt)) return false;
+    const std::string ck = affine::constraint_key(0);
+    if (ls.constraint_key != ck || sz.constraint_key != ck || a.A.data().size() != 2) return false;
+    const DenseMatrixImpl& L = *ls.L_arg_var;
+    if (L.trans()) return false;
+    m = L.rows();
+    n = L.cols();
+    const int64_t nx = n * cols;  // entries of the variable (a matrix variable: column c at c * n)
+    double a0 = 0;
+    if (!ConsensusTie(a.A, ck, ls.var_key, sz.var_key, nx, &a0, &a1) || a0 != 1.0) return false;
+    if (!k::LassoFusedSupported(m, n, L.data(), L.rows())) return false;
+    if (ls.rhs_arg.n != 0 && ls.rhs_arg.n != m * cols) return false;
+    if (cols > 1 && !ChooseMatrixRoute(matrix_mode)) return false;
+    // the six state vectors are slices of ONE buffer, so that a residual check can snapshot the
+    // iterates with a single copy (pipelined checks, Solver::Run)
+    const int64_t npad = (nx + 63) / 64 * 64;
+    state_all = DVec::Zeros(6 * npad, dt);
+    snapshot = DVec::Empty(6 * npad, dt);
+    norm_work = DVec::Zeros(64 * 5 + 1, F64);
+    a.y_prev.resize(2);
+    std::vector<StateSlice> views = {{&a.x[0], ls.var_key}, {&a.x[1], sz.var_key}, {&a.y[0], ck},
+                                     {&a.y[1], ck},         {&a.u, ck},            {&a.y_prev[1], ck}};
+    views[5].take = false;
+    for (size_t q = 0; q < views.size(); ++q) views[q].v = state_all.Slice(static_cast<int64_t>(q) * npad, nx);
+    k::LassoInstance& s = pass.inst;
+    s.x0 = views[0].v, s.x1 = views[1].v, s.y0 = views[2].v, s.y1 = views[3].v, s.u = views[4].v;
+    s.y1prev = views[5].v;
+    grid = k::LassoFusedGrid(m, n, dt);
+    // a matrix variable: column c's p and w at c * m (the wide route's instance-major panels,
+    // whole panels of 64), its partials at c * grid * m
+    const int64_t wlen = wide ? (cols + WideSweep::PW - 1) / WideSweep::PW * WideSweep::PW * m : cols * m;
+    p = DVec::Zeros(wlen, dt);
+    if (!wide) tpart = DVec::Empty(static_cast<int64_t>(grid) * m * cols, dt);
+    if (cols > 1) {
+      w = DVec::Zeros(wlen, dt);
+    } else {
+      Comm* comm = Runtime::Get().comm();
+      PeerExchange* px = Runtime::Get().peer();
+      sharded = sh.active() && sh.IsSharded(ls.var_key);
+      // one-shot peer-write exchange inside the sweep's own kernels (kernels_peer.hip) when the
+      // ranks share a window and the m-float message fits its slots; RCCL collectives otherwise
+      // (a granule carries 32 value bits: an f64 value takes two)
+      use_peer = sharded && px != nullptr && m * (dt == F64 ? 2 : 1) <= px->slot() && ls.Dinv_arg != nullptr &&
+                 !ls.Dinv_arg->trans() && ls.Dinv_arg->rows() == m;
+      const int G = use_peer ? px->view().G : (comm ? comm->size() : 1);
+      slab = ((m + G - 1) / G + 3) / 4 * 4;
+      wpad = DVec::Zeros(slab * G, dt);
+      wslice = DVec::Zeros(slab, dt);
+      w = wpad.Slice(0, m);  // the gathered vector IS w (first m entries)
+      // the inverse is applied by row slabs + all-gather from 3 ranks up; with 2 ranks the
+      // symmetric apply of the whole matrix reads the same m^2/2 entries and needs no exchange
+      const char* e = std::getenv("EPSILON_HIP_SHARDED_APPLY");
+      const bool want_slab = e ? e[0] != 'r' : G >= 3;
+      peer_slab = use_peer && want_slab && k::PeerSlabApplySupported(px->view(), m, slab, ls.Dinv_arg->data(), m);
+    }
+    if (!use_peer && !sh.active() && EnableWhiten()) {
+      // no inverse apply in the sweep: no workspace, no packed copy
+    } else if (wide) {
+      // the inverse times the panel is a product of its own (WideSweep::ApplyInverse)
+    } else {
+      inv.Init(ls.Dinv_arg, m, p, w, a.shared_cache, cols);
+    }
+    if (wide) ws.Init(m, n, whiten ? Ahat : L.data(), whiten ? m : L.rows(), whiten, ls.Dinv_arg.get());
+    BuildPass();
+    AdoptState(views, Homes(a));
+    ForwardFromState();
+    return true;
+  }
+
+  // Route of a matrix-variable solve: the batched pass (f32 / f64) or the wide
+  // kernels (f32).  The group threshold needs all columns in one launch (pass) or one panel (wide).
+  bool ChooseMatrixRoute(MatrixRoute mode) {
+    const DenseMatrixImpl& L = *ls.L_arg_var;
+    const DenseMatrixImpl& D = *ls.Dinv_arg;
+    if (m < kMatrixFusedMinRows || L.dtype() != dt || D.dtype() != dt) return false;
+    if (group && group_rows != n) return false;
+    if (sz.alpha_vec.n > 0 && sz.alpha_vec.n != n * cols) return false;
+    if (sz.beta_vec.n > 0 && sz.beta_vec.n != n * cols) return false;
+    if (D.rows() != m || D.cols() != m) return false;
+    const int width = k::LassoBatchWidth(m, n, dt);
+    const bool pass_ok = width > 0 && (!group || cols <= width);
+    const bool wide_ok = dt == F32 && k::LassoWideSupported(m, n, L.data(), L.rows()) &&
+                         (!group || cols <= WideSweep::PW);
+    if (mode == kMatrixPass) wide = false;
+    else if (mode == kMatrixWide) wide = true;
+    else wide = wide_ok && (cols >= BatchWideMin() || !pass_ok);
+    return wide ? wide_ok : pass_ok;
+  }
+
+  // The whitened route.  With Dinv_arg = c X^T X, where X = L^-1 is the inverse Cholesky factor
+  // kept by DenseMatrixImpl::Inverse, the forward product of a sweep is
+  //   d = A^T Dinv p = c (X A)^T (X p),   X p = X rhs - s_L (X A) v,
+  // so the pass streams A_hat = X A (same shape as A, formed once at Init) and its partials reduce
+  // to w_hat = X p directly: no m x m matrix is read in the sweep.  f32, one GPU, m >= 2048, n >= 2m.
+  bool EnableWhiten() {
+    const DenseMatrixImpl& L = *ls.L_arg_var;
+    const DenseMatrixImpl& D = *ls.Dinv_arg;
+    OpCache* cache = CurrentOpCache();
+    if (!FusedWhitenEnabled() || cache == nullptr || dt != F32 || L.dtype() != F32 || m < kWhitenMinRows)
+      return false;
+    // wide data only: A_hat is formed on the split-f16 matrix cores (about 4x the f32 rounding), and
+    // a nearly square A amplifies that in the iterates (10244 x 10260: 4e-5 off the generic path
+    // after 200 sweeps, twice the fused path's parity tolerance)
+    if (n < 2 * m) return false;
+    if (D.id() == 0 || D.trans() || D.rows() != m || D.cols() != m || L.rows() != m) return false;
+    // X belongs to exactly this inverse: the cached entry under D's key holds D's own buffer
+    const auto cached = cache->Find(D.id());
+    const auto Xm = cache->Find(FactorInverseKey(D.id()));
+    if (!cached || !Xm || cached->data().data() != D.data().data() || Xm->rows() != m || Xm->cols() != m)
+      return false;
+    // A_hat is shared like the packed inverse: a warm re-Init and the members of a batch find it
+    const uint64_t key = HashCombine(HashCombine(HashCombine(HashCombine(Xm->id(), 0x3a7),
+                                                             reinterpret_cast<uintptr_t>(L.data().data())),
+                                                 L.id()),
+                                     static_cast<uint64_t>(n));
+    DVec Ah;
+    if (auto hit = cache->Find(key)) {
+      Ah = hit->data();
+    } else {
+      Ah = DVec::Empty(m * n, F32);
+      // X is lower triangular: each tile of the product runs over its own k range
+      if (!k::GemmSplitF16KRange(4, m, n, m, 1.0, Xm->data(), m, L.data(), m, Ah, m))
+        k::Gemm(false, false, m, n, m, 1.0, Xm->data(), m, L.data(), m, 0.0, Ah, m);
+      cache->Put(key, std::make_shared<DenseMatrixImpl>(Ah, m, n, false, 1.0, key));
+    }
+    if (!k::LassoFusedSupported(m, n, Ah, m)) return false;
+    // X rhs on every Init: parameters re-bind the rhs
+    if (ls.rhs_arg.n != 0 && cols > 1) {  // all columns in one product
+      rhat = DVec::Empty(m * cols, F32);
+      k::Gemm(false, false, m, cols, m, 1.0, Xm->data(), m, ls.rhs_arg, m, 0.0, rhat, m);
+    } else if (ls.rhs_arg.n != 0) {
+      rhat = DVec::Empty(m, F32);
+      k::Gemv(false, m, m, 1.0, Xm->data(), m, ls.rhs_arg, 0.0, rhat);
+    }
+    X = Xm->data();
+    Ahat = Ah;
+    wscale = D.scale();
+    whiten = true;
+    return true;
+  }
+
+  // w of the first sweep from the current state: p = rhs_arg - L(arg,var) v0 with
+  // v0 = ((u - y0) - y1) + y0, column by column for a matrix variable, then w = Dinv_arg p
+  // (whitened: w_hat = X p).
+  void ForwardFromState() {
+    const DenseMatrixImpl& L = *ls.L_arg_var;
+    const k::LassoInstance& s = pass.inst;
+    DVec v0 = s.u.Clone();
+    k::Axpby(v0, -1.0, s.y0, 1.0);
+    k::Axpby(v0, -1.0, s.y1, 1.0);
+    k::Axpby(v0, 1.0, s.y0, 1.0);
+    if (cols == 1 && !whiten) {
+      L.Apply(-1.0, v0, 0.0, p);
+      ForwardTail(/*reduced=*/false);
+      return;
+    }
+    const int64_t mk = m * cols;
+    DVec pp = whiten && cols > 1 ? DVec::Empty(mk, v0.dt) : p.Slice(0, mk);
+    for (int64_t c = 0; c < cols; ++c) L.Apply(-1.0, v0.Slice(c * n, n), 0.0, pp.Slice(c * m, m));
+    if (ls.rhs_arg.n != 0) k::Axpby(pp, 1.0, ls.rhs_arg, 1.0);
+    for (int64_t c = 0; whiten && c < cols; ++c)
+      k::Gemv(false, m, m, 1.0, X, m, pp.Slice(c * m, m), 0.0, w.Slice(c * m, m));
+    if (!whiten) ApplyInverseFixed();
+  }
+
+  // The vector form's tail, one GPU or RCCL: p from the pass's partials (`reduced`) or as
+  // ForwardFromState left it, all-reduced when sharded, + rhs_arg, then w = Dinv_arg p.
+  void ForwardTail(bool reduced) {
+    const DenseMatrixImpl& L = *ls.L_arg_var;
+    if (whiten) {
+      k::ReducePartials(m, grid, tpart, -L.scale(), 0.0, w, rhat.n != 0 ? &rhat : nullptr);
+      return;
+    }
+    bool rhs_added = false;
+    if (reduced) {
+      // the constant part of the rhs rides in the reduction kernel (same rounding order as the
+      // separate axpy: sum first, then + rhs); in a sharded run rank 0 alone contributes it to
+      // the sum over ranks - one launch less in a sweep that is launch-latency-bound at N = 8
+      const bool have_rhs = ls.rhs_arg.n != 0;
+      const bool fold = have_rhs && (!sharded || Runtime::Get().comm()->rank() == 0);
+      k::ReducePartials(m, grid, tpart, -L.scale(), 0.0, p, fold ? &ls.rhs_arg : nullptr);
+      rhs_added = have_rhs;  // folded here, or by rank 0 into the all-reduced sum
+    }
+    if (sharded) Runtime::Get().comm()->AllReduceSum(p);
+    if (ls.rhs_arg.n != 0 && !rhs_added) k::Axpby(p, 1.0, ls.rhs_arg, 1.0);
+    const DenseMatrixImpl& D = *ls.Dinv_arg;
+    Comm* comm = Runtime::Get().comm();
+    // EPSILON_HIP_SHARDED_APPLY=replicated: every rank applies the whole inverse instead (no
+    // all-gather; m^2 bytes per rank) - the cheaper form when the collective's latency exceeds
+    // the apply, to be decided on the machine
+    static const bool replicated_apply = [] {
+      const char* e = std::getenv("EPSILON_HIP_SHARDED_APPLY");
+      return e && e[0] == 'r';
+    }();
+    if (sharded && comm->size() > 1 && !D.trans() && D.rows() == m && !replicated_apply) {
+      // The cached inverse is replicated and symmetric: each rank applies only its slab of rows
+      // (= columns, read contiguously) and the slices are all-gathered, so the m^2 bytes of the
+      // apply are split over the ranks like the data matrix is.
+      const int64_t per = slab;  // multiple of 4, G*per >= m
+      const int64_t lo = std::min<int64_t>(m, comm->rank() * per);
+      const int64_t cnt = std::min<int64_t>(m, lo + per) - lo;
+      DVec mine = wslice;
+      if (cnt < per) k::Fill(mine, 0.0);
+      if (cnt > 0) {
+        DVec rows = D.data().Slice(lo * m, cnt * m);
+        k::Gemv(true, m, cnt, D.scale(), rows, m, p, 0.0, mine.Slice(0, cnt));
+      }
+      comm->AllGather(mine.data(), wpad.data(), static_cast<size_t>(per), wpad.dt);
+    } else {
+      ApplyInverseFixed();
+    }
+  }
+
+  // The sharded sweep's tail on the peer window: 2 launches, no collective call.
+  void ForwardTailPeer() {
+    const DenseMatrixImpl& L = *ls.L_arg_var;
+    const DenseMatrixImpl& D = *ls.Dinv_arg;
+    const PeerView& pv = Runtime::Get().peer()->view();
+    k::PeerReduceExchange(pv, m, grid, tpart, -L.scale(), ls.rhs_arg.n != 0 ? &ls.rhs_arg : nullptr, p);
+    if (peer_slab) {
+      const int64_t lo = std::min<int64_t>(m, static_cast<int64_t>(pv.rank) * slab);
+      k::PeerSlabApplyExchange(pv, m, slab, lo, D.data(), m, D.scale(), p, wpad);
+    } else {
+      ApplyInverseFixed();
+    }
+  }
+
+  // w = Dinv p, every column
+  void ApplyInverseFixed() {
+    if (wide) {
+      for (int64_t q = 0; q * ws.panel_len < w.n; ++q)
+        ws.ApplyInverse(p.Slice(q * ws.panel_len, ws.panel_len), w.Slice(q * ws.panel_len, ws.panel_len));
+    } else if (cols == 1) {
+      inv.Apply();
+    } else if (inv.packed.n > 0) {
+      k::SymvPackedBatch(m, inv.D->scale(), inv.packed, table, static_cast<int>(cols), inv.work);
+    } else {
+      for (int64_t c = 0; c < cols; ++c) inv.Column(c).Apply();
+    }
+  }
+
+  // The pass's arguments with the instance as the kernels read it, once per Init: EnableWhiten has
+  // decided the matrix, kappa, p and rhs by now.  Only the peer exchange's epoch is set per sweep.
+  void BuildPass() {
+    const DenseMatrixImpl& L = *ls.L_arg_var;
+    pass.m = m;
+    pass.n = n;
+    pass.lda = whiten ? m : L.rows();
+    pass.A = whiten ? Ahat : L.data();
+    k::LassoInstance& s = pass.inst;
+    s.w = w;
+    s.tpart = tpart;
+    // whitened route: the reduction writes w_hat itself, with X rhs folded in
+    s.p = whiten ? w : p;
+    s.rhs = whiten ? rhat : ls.rhs_arg;
+    // x0 = v0 + kappa A^T w (whitened: c A_hat^T w_hat)
+    s.kappa = -L.scale() * (whiten ? wscale : 1.0);
+    s.pkappa = -L.scale();
+    SetThreshold(&s, sz, a1);
+    if (cols == 1) return;
+    // a matrix variable: column c is member c, the slices of `inst` at its offsets; the table is
+    // uploaded here, so that a sweep makes no upload and no host synchronisation
+    members.assign(static_cast<size_t>(cols), s);
+    rhs_aligned = true;
+    for (int64_t c = 0; c < cols; ++c) {
+      k::LassoInstance& mb = members[static_cast<size_t>(c)];
+      auto col = [&](const DVec& v, int64_t len) { return v.n > 0 ? v.Slice(c * len, len) : v; };
+      mb.w = col(s.w, m);
+      mb.p = col(s.p, m);
+      mb.rhs = col(s.rhs, m);
+      if (!wide) mb.tpart = col(s.tpart, static_cast<int64_t>(grid) * m);
+      else mb.tpart = mb.w;  // (not read on the wide route: its partials are panels of WideSweep)
+      for (DVec k::LassoInstance::*v : {&k::LassoInstance::u, &k::LassoInstance::x0, &k::LassoInstance::x1,
+                                       &k::LassoInstance::y0, &k::LassoInstance::y1, &k::LassoInstance::y1prev,
+                                       &k::LassoInstance::alpha_vec, &k::LassoInstance::beta_vec})
+        mb.*v = col(s.*v, n);
+      if (mb.rhs.n > 0) rhs_aligned = rhs_aligned && reinterpret_cast<uintptr_t>(mb.rhs.data()) % 16 == 0;
+    }
+    std::vector<const k::LassoInstance*> v;
+    for (const auto& mb : members) v.push_back(&mb);
+    k::LassoBatchUpload(v, dt, &table);
+  }
+
+  // A matrix variable's sweep: its columns through the batched or the wide kernels.
+  void MatrixSweep() {
+    const int K = static_cast<int>(cols);
+    const double* group_lam = group ? &sz.lam : nullptr;
+    if (wide) {
+      constexpr int PW = WideSweep::PW;
+      for (int first = 0; first < K; first += PW) {
+        const int nk = std::min(PW, K - first);
+        const uint64_t live = nk == 64 ? ~uint64_t(0) : (uint64_t(1) << nk) - 1;
+        const int64_t off = static_cast<int64_t>(first) * m;
+        ws.Run(table, first, nk, live, w.Slice(off, ws.panel_len), whiten ? DVec() : p.Slice(off, ws.panel_len),
+               group_lam);
+      }
+      return;
+    }
+    const int width = k::LassoBatchWidth(m, n, dt);
+    for (int first = 0; first < K; first += width)
+      k::LassoBatchPass(m, n, pass.lda, pass.A, table, first, std::min(width, K - first), group_lam);
+    k::ReducePartialsBatch(m, grid, table, K, dt, rhs_aligned);
+    if (!whiten) ApplyInverseFixed();
+  }
+
+  void Sweep() override {
+    if (cols > 1) {
+      MatrixSweep();
+    } else if (use_peer) {
+      pass.epoch = Runtime::Get().peer()->view().epoch;
+      k::LassoFusedPass(pass);
+      ForwardTailPeer();
+    } else {
+      k::LassoFusedPass(pass);
+      ForwardTail(/*reduced=*/true);
+    }
+  }
+
+  // ---- residual check: one launch, splittable for pipelining -----------------------------------
+  // With A = [a0 I, a1 I] (a0 = 1), b empty and N = 2 the quantities of prox_admm.cc:178-217 are
+  //   ||A x_i|| = ||y_i||,  r = ||y0 + y1||,  s = rho ||A_0^T (y1 - y1_prev)|| = rho ||y1 - y1_prev||,
+  //   ||A^T u||^2 = (a0^2 + a1^2) ||u||^2.
+  bool HasCheck() const override { return true; }
+  bool PipelineChecks() const override {
+    static const bool off = [] {
+      const char* e = std::getenv("EPSILON_HIP_PIPELINE_CHECKS");
+      return e && e[0] == '0';
+    }();
+    return !off;
+  }
+  // the check's six scalars into the next six slots
+  void LaunchNorms() override {
+    Runtime& rt = Runtime::Get();
+    norm_slot = rt.NewSlot();
+    for (int q = 1; q < 6; ++q) rt.NewSlot();
+    const k::LassoInstance& s = pass.inst;
+    k::LassoFusedNorms(s.u, s.y0, s.y1, s.y1prev, sharded ? rt.ShardSlotPtr(norm_slot) : rt.SlotPtr(norm_slot), norm_work,
+                       use_peer ? rt.peer()->device_error_word() : nullptr);
+  }
+  Check FinishCheck() override {
+    Runtime& rt = Runtime::Get();
+    // a timed-out exchange on ANY rank shows in the all-reduced sixth value: every rank raises at
+    // the same check, none is left waiting in a collective the others never enter
+    if (rt.SlotValue(norm_slot + 5) > 0) {
+      rt.Sync();
+      if (rt.peer()) rt.peer()->ClearError();
+      EPS_FATAL("peer exchange: a poll timed out on at least one rank (a peer did not deliver its part)");
+    }
+    const double ny0 = rt.SlotValue(norm_slot), ny1 = rt.SlotValue(norm_slot + 1), nr = rt.SlotValue(norm_slot + 2),
+                 ns = rt.SlotValue(norm_slot + 3), nu = rt.SlotValue(norm_slot + 4);
+    Check c;
+    c.r = std::sqrt(nr);
+    c.s = std::sqrt(ns);
+    c.max_norm = std::fmax(std::sqrt(ny0), std::sqrt(ny1));
+    c.atu = std::sqrt((1.0 + a1 * a1) * nu);
+    return c;
+  }
+  void SaveSnapshot() override { k::Copy(snapshot, state_all); }
+  void RestoreSnapshot() override {
+    Runtime::Get().Sync();  // let the discarded sweeps drain
+    if (Runtime::Get().peer()) Runtime::Get().peer()->CheckError();
+    k::Copy(state_all, snapshot);
+  }
+
+  bool Capturable() const override {
+    const bool fixed_buffers = (use_peer && peer_slab) || inv.work.n > 0 || whiten || wide;
+    return fixed_buffers && !(sharded && !use_peer);  // (RCCL calls in the sweep are not captured)
+  }
+  bool CaptureByDefault() const override { return use_peer; }
+
+  // ---- batched solves (RunFusedBatches) ---------------------------------------------------------
+  // The key of the group a fresh solve on this route can join (same data matrix, inverse, dtype,
+  // shape and schedule); false: its pass is none the batched one mirrors.
+  bool BatchKey(const pb::SolverParams& params, std::vector<uint64_t>* key) const {
+    if (use_peer || ShardSpec::Get().active()) return false;
+    if (cols > 1) return false;  // a matrix variable is a batch of its own: it runs alone
+    const DenseMatrixImpl& L = *ls.L_arg_var;
+    const DenseMatrixImpl& D = *ls.Dinv_arg;
+    if (L.dtype() != dt || k::LassoBatchWidth(m, n, dt) == 0) return false;
+    auto bits = [](double v) {
+      uint64_t b;
+      std::memcpy(&b, &v, 8);
+      return b;
+    };
+    *key = {reinterpret_cast<uintptr_t>(L.data().data()), static_cast<uint64_t>(L.rows()),
+            static_cast<uint64_t>(m), static_cast<uint64_t>(n), static_cast<uint64_t>(dt),
+            bits(L.scale()), reinterpret_cast<uintptr_t>(D.data().data()), bits(D.scale()),
+            reinterpret_cast<uintptr_t>(inv.packed.data()), inv.work.n > 0 ? 1u : 0u,
+            static_cast<uint64_t>(params.max_iterations), static_cast<uint64_t>(params.epoch_iterations),
+            whiten ? 1u : 0u, reinterpret_cast<uintptr_t>(Ahat.data())};
+    return true;
+  }
+};
+
+// ---------------------------------------------------------------------------------------------------
+// The ZERO-term route
+// ---------------------------------------------------------------------------------------------------
+// Recognised structure: the last term is a ZERO term over private copies (x', and z' unless the
+// problem has no z: basis pursuit) whose block LDL^T is the projection ZeroProx describes; the
+// other terms are one scaled-zone term on x and at most one on z (which may carry an offset),
+// each tied to its copy by a consensus constraint copy + a var = 0 without a constant.  The
+// sweep is then: the pass over the data matrix (chain 2: back product, column chain, forward
+// product), the row kernel (row chain, the partials' sum, r) - basis pursuit: the partials'
+// reduction alone - and the apply of the cached inverse.  The residual check is the driver's
+// generic one on views of the state.  One GPU, every dtype the compute type.
+struct ZeroRoute final : FusedRoute {
+  ZeroProjectionDesc zp;
+  ScaledZoneDesc sx, sz;  // the separable terms on x and on z
+  bool has_z = false;
+  int64_t m = 0, n = 0;
+  int grid = 0;
+  DVec state_n, state_m;  // the slices of a side's state in one buffer (n: the x constraint's rows)
+  DVec w, p, tpart;
+  InverseApply inv;
+  k::LassoFusedArgs pass;
+  k::ZeroRowsArgs rows;
+
+  bool Enable(const MultiBlockParts& a) {
+    if (FusedDisabled() || ShardSpec::Get().active() || !a.b.data().empty()) return false;
+    const int nc = a.num_constraints, N = static_cast<int>(a.prox.size());
+    if (nc < 1 || nc > 2 || N != nc + 1) return false;
+    if (!a.prox[N - 1]->DescribeZeroProjection(&zp)) return false;
+    has_z = !zp.z_key.empty();
+    if (has_z != (nc == 2)) return false;
+    int ix = -1, iz = -1;  // positions of the separable terms among the objective terms
+    for (int i = 0; i + 1 < N; ++i) {
+      ScaledZoneDesc d;
+      if (!a.prox[i]->DescribeScaledZoneOffset(&d)) return false;
+      if (ix < 0 && d.constraint_key == zp.x_constraint_key && d.g.n == 0) {
+        sx = d;
+        ix = i;
+      } else if (has_z && iz < 0 && d.constraint_key == zp.z_constraint_key) {
+        sz = d;
+        iz = i;
+      } else {
+        return false;
+      }
+    }
+    if (ix < 0 || (has_z && iz < 0)) return false;
+    const DenseMatrixImpl& L = *zp.L_arg_x;
+    const DenseMatrixImpl& D = *zp.Dinv_arg;
+    const DType dt = a.data->dtype();
+    m = L.rows();
+    n = L.cols();
+    if (m < kZeroFusedMinRows || L.dtype() != dt || D.dtype() != dt) return false;
+    if (D.rows() != m || D.cols() != m) return false;
+    if (!k::LassoFusedSupported(m, n, L.data(), L.rows())) return false;
+    // the consensus constraints: copy + a var = 0, nothing else in their rows or columns
+    if (static_cast<int>(a.A.data().size()) != 2 * nc) return false;
+    double ax = 0, az = 0;  // constraint maps of x and z (their copies': 1)
+    auto tie = [&](const std::string& ck, const std::string& copy, const std::string& var, int64_t len, double* av) {
+      double a0 = 0;
+      return ConsensusTie(a.A, ck, copy, var, len, &a0, av) && a0 == 1.0 && a.A.col(copy).size() == 1 &&
+             a.A.col(var).size() == 1;
+    };
+    if (!tie(zp.x_constraint_key, zp.x_key, sx.var_key, n, &ax)) return false;
+    if (has_z && !tie(zp.z_constraint_key, zp.z_key, sz.var_key, m, &az)) return false;
+    auto fits = [&](const DVec& v, int64_t len) { return v.n == 0 || (v.n == len && v.dt == dt); };
+    if (!fits(zp.rhs_arg, m) || !fits(sx.alpha_vec, n) || !fits(sx.beta_vec, n)) return false;
+    if (!fits(sz.alpha_vec, m) || !fits(sz.beta_vec, m) || !fits(sz.g, m)) return false;
+
+    // state: u, var, copy, y of the separable term, y of the ZERO term, their previous values -
+    // per constraint row, taken over from the generic containers (warm start)
+    a.y_prev.resize(N);
+    std::vector<StateSlice> views;
+    auto side = [&](int64_t len, const std::string& ck, int term, const std::string& var, const std::string& copy,
+                    DVec* all) {
+      const int64_t pad = (len + 63) / 64 * 64;
+      *all = DVec::Zeros(7 * pad, dt);
+      const size_t first = views.size();
+      views.insert(views.end(), {{&a.u, ck},
+                                 {&a.x[term], var},
+                                 {&a.x[N - 1], copy},
+                                 {&a.y[term], ck},
+                                 {&a.y[N - 1], ck},
+                                 {&a.y_prev[term], ck, DVec(), false},
+                                 {&a.y_prev[N - 1], ck, DVec(), false}});
+      for (int q = 0; q < 7; ++q) views[first + q].v = all->Slice(q * pad, len);
+      return &views[first];
+    };
+    grid = k::LassoFusedGrid(m, n, dt);
+    w = DVec::Zeros(m, dt);
+    p = DVec::Zeros(m, dt);
+    tpart = DVec::Empty(static_cast<int64_t>(grid) * m, dt);
+    inv.Init(zp.Dinv_arg, m, p, w, a.shared_cache);
+    {
+      const StateSlice* sn = side(n, zp.x_constraint_key, ix, sx.var_key, zp.x_key, &state_n);
+      pass.m = m;
+      pass.n = n;
+      pass.lda = L.rows();
+      pass.A = L.data();
+      pass.chain = 2;
+      pass.e0 = sn[6].v;
+      k::LassoInstance& s = pass.inst;
+      s.w = w;
+      s.tpart = tpart;
+      s.p = p;
+      s.rhs = zp.rhs_arg;
+      s.u = sn[0].v;
+      s.x1 = sn[1].v;
+      s.x0 = sn[2].v;
+      s.y1 = sn[3].v;
+      s.y0 = sn[4].v;
+      s.y1prev = sn[5].v;
+      s.kappa = s.pkappa = -L.scale();
+      SetThreshold(&s, sx, ax);
+    }
+    if (has_z) {
+      const StateSlice* sm = side(m, zp.z_constraint_key, iz, sz.var_key, zp.z_key, &state_m);
+      rows.m = m;
+      rows.nparts = grid;
+      rows.w = w;
+      rows.tpart = tpart;
+      rows.r = p;
+      rows.rhs = zp.rhs_arg;
+      rows.g = sz.g;
+      rows.u = sm[0].v;
+      rows.z = sm[1].v;
+      rows.zq = sm[2].v;
+      rows.yz = sm[3].v;
+      rows.yq = sm[4].v;
+      rows.yzprev = sm[5].v;
+      rows.yqprev = sm[6].v;
+      rows.e = zp.e;
+      rows.pkappa = -L.scale();
+      SetThreshold(&rows, sz, az);
+    }
+    AdoptState(views, Homes(a));
+    ForwardFromState(a);
+    return true;
+  }
+
+  // w of the first sweep from the current state, with the generic operators: the sweep up to the
+  // ZERO prox's input v (on copies: the state is not touched), then the forward substitution
+  // r = (rhs - e v_z) - L(arg, x') v_x and the inverse apply.
+  void ForwardFromState(const MultiBlockParts& a) {
+    const size_t N = a.prox.size();
+    BlockVector v = a.u;
+    for (size_t i = 0; i < N; ++i) v -= a.y[i];
+    for (size_t i = 0; i + 1 < N; ++i) {
+      v += a.y[i];
+      v -= a.A * a.prox[i]->Apply(v);
+    }
+    v += a.y[N - 1];
+    if (zp.rhs_arg.n != 0) k::Copy(p, zp.rhs_arg);
+    else k::Fill(p, 0.0);
+    if (has_z) k::Axpby(p, -zp.e, v(zp.z_constraint_key), 1.0);
+    zp.L_arg_x->Apply(-1.0, v(zp.x_constraint_key), 1.0, p);
+    inv.Apply();
+  }
+
+  void Sweep() override {
+    k::LassoFusedPass(pass);
+    if (has_z)
+      k::ZeroFusedRows(rows);
+    else
+      k::ReducePartials(m, grid, tpart, pass.inst.pkappa, 0.0, p, zp.rhs_arg.n != 0 ? &zp.rhs_arg : nullptr);
+    inv.Apply();
+  }
+};
+
+// ---------------------------------------------------------------------------------------------------
+// The lasso structure in two-block form
+// ---------------------------------------------------------------------------------------------------
+// [SUM_SQUARE with a dense argument map, scaled-zone prox], one constraint a0 x0 + a1 x1 = 0
+// without a constant: the x-updates are the same two operators as in the multi-block driver, the
+// z-update is the closed-form projection onto the constraint, so one pass over the data matrix
+// does a whole sweep (kernels_fused.hip, chain 1).  f32 and f64, single GPU.  The residual check
+// is the driver's generic one on views of the state.
+struct TwoBlockRoute final : FusedRoute {
+  LeastSquaresDesc ls;
+  ScaledZoneDesc sz;
+  int64_t m = 0, n = 0;
+  int grid = 0;
+  DVec p, w, tpart;
+  k::LassoFusedArgs pass;
+
+  bool Enable(const TwoBlockParts& a) {
+    if (FusedDisabled() || a.prox.size() != 2 || a.num_constraints != 1) return false;
+    if (ShardSpec::Get().active() || !a.constr_H.b.data().empty()) return false;
+    if (!a.prox[0]->DescribeLeastSquares(&ls) || !a.prox[1]->DescribeScaledZone(&sz)) return false;
+    if (ls.cols != 1) return false;  // matrix variables: the multi-block driver only
+    const DenseMatrixImpl& L = *ls.L_arg_var;
+    if (L.trans()) return false;
+    m = L.rows();
+    n = L.cols();
+    const BlockMatrix& H = a.constr_H.A;
+    double a0 = 0, a1 = 0;
+    if (H.data().size() != 2 || !ConsensusTie(H, affine::constraint_key(0), ls.var_key, sz.var_key, n, &a0, &a1))
+      return false;
+    if (a0 == 0 || a1 == 0) return false;
+    if (!k::LassoFusedSupported(m, n, L.data(), L.rows())) return false;
+    if (ls.rhs_arg.n != 0 && ls.rhs_arg.n != m) return false;
+    const DenseMatrixImpl& D = *ls.Dinv_arg;
+    if (D.trans() || D.rows() != m) return false;
+    const DType dt = a.data->dtype();
+    if ((sz.alpha_vec.n > 0 && sz.alpha_vec.dt != dt) || (sz.beta_vec.n > 0 && sz.beta_vec.dt != dt)) return false;
+    if (L.dtype() != dt || D.dtype() != dt) return false;
+    // x, z, u and the previous z of the two variables
+    std::vector<StateSlice> views;
+    for (BlockVector* home : {&a.x, &a.z, &a.u, &a.z_prev})
+      for (const std::string& key : {ls.var_key, sz.var_key})
+        views.push_back({home, key, DVec::Zeros(n, dt), home != &a.z_prev});
+    const DVec &x0 = views[0].v, &x1 = views[1].v, &z0 = views[2].v, &z1 = views[3].v, &u0 = views[4].v,
+               &u1 = views[5].v, &z0p = views[6].v, &z1p = views[7].v;
+    p = DVec::Zeros(m, dt);
+    w = DVec::Zeros(m, dt);
+    grid = k::LassoFusedGrid(m, n, dt);
+    tpart = DVec::Empty(static_cast<int64_t>(grid) * m, dt);
+    // the pass's arguments, once per Init; chain 1 reads the state arrays as
+    // u -> u0, y0 -> z0, y1 -> z1, y1prev -> z0_prev, e0 -> u1, e1 -> z1_prev
+    pass.m = m;
+    pass.n = n;
+    pass.lda = L.rows();
+    pass.A = L.data();
+    pass.chain = 1;
+    pass.a0 = a0;
+    pass.e0 = u1;
+    pass.e1 = z1p;
+    k::LassoInstance& s = pass.inst;
+    s.w = w;
+    s.tpart = tpart;
+    s.u = u0;
+    s.x0 = x0;
+    s.x1 = x1;
+    s.y0 = z0;
+    s.y1 = z1;
+    s.y1prev = z0p;
+    s.p = p;
+    s.rhs = ls.rhs_arg;
+    s.kappa = s.pkappa = -L.scale();
+    SetThreshold(&s, sz, a1);
+    AdoptState(views, {&a.x, &a.z, &a.u, &a.z_prev});
+    // p = rhs_arg - L(arg, var) (z0 - u0) of the current state, w = Dinv_arg p
+    DVec v0 = z0.Clone();
+    k::Axpby(v0, -1.0, u0, 1.0);
+    L.Apply(-1.0, v0, 0.0, p);
+    if (ls.rhs_arg.n != 0) k::Axpby(p, 1.0, ls.rhs_arg, 1.0);
+    D.Apply(1.0, p, 0.0, w);
+    return true;
+  }
+
+  void Sweep() override {
+    k::LassoFusedPass(pass);
+    k::ReducePartials(m, grid, tpart, pass.inst.pkappa, 0.0, p, ls.rhs_arg.n != 0 ? &ls.rhs_arg : nullptr);
+    ls.Dinv_arg->Apply(1.0, p, 0.0, w);
+  }
+};
+
+template <class Route, class Parts>
+std::unique_ptr<FusedRoute> Recognise(const Parts& parts) {
+  std::unique_ptr<Route> r(new Route);
+  if (!r->Enable(parts)) return nullptr;
+  return std::unique_ptr<FusedRoute>(std::move(r));
+}
+
+}  // namespace
+
+std::unique_ptr<FusedRoute> RecogniseMultiBlockRoute(const MultiBlockParts& parts) {
+  const bool zero = FusedZeroAuto();  // (read first: a bad value is an error whatever the problem)
+  if (auto r = Recognise<LassoRoute>(parts)) return r;
+  return zero ? Recognise<ZeroRoute>(parts) : nullptr;
+}
+
+std::unique_ptr<FusedRoute> RecogniseTwoBlockRoute(const TwoBlockParts& parts) {
+  return Recognise<TwoBlockRoute>(parts);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Batched solves: one group of instances on the lasso route sharing A and the cached inverse
+// ---------------------------------------------------------------------------------------------------
+namespace {
+
+struct BatchMember {
+  Solver* solver;
+  LassoRoute* route;
+};
+using Group = std::vector<BatchMember>;
+
+// Run()'s iteration schedule without the pipelining, for a group of batched members: sweeps up to
+// the next multiple of the epoch, then one residual check of every active member with ONE fetch of
+// their scalars.  A member that stops is frozen: it leaves `active`, and `stopped(gone)` is told
+// which ones left (only when some did).  Members still active at the end get Run()'s
+// max-iterations status.  Ends with the group's loop time since `t0`, once the stream has drained.
+template <class Sweep, class Stopped>
+void RunGroupSchedule(const Group& g, double t0, std::vector<int>* active, Sweep sweep, Stopped stopped) {
+  Runtime& rt = Runtime::Get();
+  const pb::SolverParams& params = g[0].solver->params();
+  const int epoch = params.epoch_iterations > 0 ? params.epoch_iterations : 1;
+  const int max_it = params.max_iterations;
+  int iter = 0;
+  while (!active->empty() && iter < max_it) {
+    int batch = 1;
+    while ((iter + batch - 1) % epoch != 0) ++batch;
+    if (batch > max_it - iter) batch = max_it - iter;
+    for (int s = 0; s < batch; ++s) sweep();
+    iter += batch - 1;
+    if (iter % epoch == 0) {
+      rt.ResetSlots();
+      for (int i : *active) g[i].solver->BatchLaunchCheck(iter);
+      rt.FetchSlots();
+      std::vector<int> still, gone;
+      for (int i : *active) (g[i].solver->BatchFinishCheck() ? gone : still).push_back(i);
+      active->swap(still);
+      if (!gone.empty()) stopped(gone);
+    }
+    ++iter;
+  }
+  for (int i : *active) g[i].solver->BatchFinishMaxIterations(iter);
+  rt.Sync();
+  const double loop = Now() - t0;
+  for (const BatchMember& b : g) b.solver->BatchAddLoopTime(loop);
+}
+
+void RunFusedGroup(const Group& g) {
+  const double t0 = Now();
+  const LassoRoute& lead = *g[0].route;
+  const DType dt = lead.dt;
+  SetCurrentDType(dt);
+  const int64_t m = lead.m, n = lead.n;
+  const int width = k::LassoBatchWidth(m, n, dt);
+  const DVec& P = lead.inv.packed;
+  bool rhs_aligned = true;
+  for (const BatchMember& b : g) {
+    const DVec& rhs = b.route->pass.inst.rhs;
+    if (rhs.n > 0) rhs_aligned = rhs_aligned && reinterpret_cast<uintptr_t>(rhs.data()) % 16 == 0;
+  }
+  const int K = static_cast<int>(g.size());
+  DVec symv_work = P.n > 0 ? DVec::Empty(K * k::SymvWorkspace(m), dt) : DVec();
+
+  std::vector<int> active(K);
+  for (int i = 0; i < K; ++i) active[i] = i;
+  DVec table;
+  auto upload = [&] {
+    std::vector<const k::LassoInstance*> v;
+    for (int i : active) v.push_back(&g[i].route->pass.inst);
+    k::LassoBatchUpload(v, dt, &table);
+  };
+  upload();
+  auto sweep = [&] {
+    const int na = static_cast<int>(active.size());
+    for (int first = 0; first < na; first += width)
+      k::LassoBatchPass(m, n, lead.pass.lda, lead.pass.A, table, first, std::min(width, na - first));
+    k::ReducePartialsBatch(m, lead.grid, table, na, dt, rhs_aligned);
+    if (lead.whiten) {
+      // the reduction wrote every member's w_hat: no inverse apply
+    } else if (P.n > 0) {
+      k::SymvPackedBatch(m, lead.inv.D->scale(), P, table, na, symv_work);
+    } else {
+      for (int i : active) g[i].route->inv.Apply();  // D.Apply / Symv: per instance
+    }
+  };
+  // the stopped ones are frozen: drop their descriptors
+  RunGroupSchedule(g, t0, &active, sweep, [&](const std::vector<int>&) {
+    if (!active.empty()) upload();
+  });
+}
+
+// EPSILON_HIP_BATCH_WIDE (eps_set_option "batch_wide"), read per batch: "1" sends eligible groups
+// to the wide route below.
+bool BatchWideEnabled() {
+  const char* e = std::getenv("EPSILON_HIP_BATCH_WIDE");
+  if (e == nullptr || std::strcmp(e, "0") == 0) return false;
+  EPS_CHECK_MSG(std::strcmp(e, "1") == 0, "batch_wide must be 0 or 1, got " << e);
+  return true;
+}
+
+// Smallest group the wide route takes.  Measured crossovers against the batched pass on MI355X
+// (DESIGN.md 3.8), rounded up to a multiple of 8.
+constexpr int kWideMin = 8;
+int BatchWideMin() {  // EPSILON_HIP_BATCH_WIDE_MIN: tuning knob (the crossover measurements)
+  const char* e = std::getenv("EPSILON_HIP_BATCH_WIDE_MIN");
+  return e && std::atoi(e) >= 2 ? std::atoi(e) : kWideMin;
+}
+
+// The wide route (kernels_fused_wide.hip): RunFusedGroup's schedule and residual checks, with the
+// sweep of a panel of up to 64 members as back product + chain, forward product and reduction on
+// the f32 matrix instruction.  The members' w (and p) live in instance-major panels for the
+// duration; a member keeps its slot until the group ends and a stopped one is masked, so no
+// summation order depends on who else is still iterating.  Not bit-identical to the single solve.
+void RunWideGroup(const Group& g) {
+  const double t0 = Now();
+  const LassoRoute& lead = *g[0].route;
+  SetCurrentDType(F32);
+  const int64_t m = lead.m, n = lead.n;
+  const bool whiten = lead.whiten;
+  const int K = static_cast<int>(g.size());
+  constexpr int PW = WideSweep::PW;
+  const int npanels = (K + PW - 1) / PW;
+  WideSweep ws;
+  ws.Init(m, n, lead.pass.A, lead.pass.lda, whiten, lead.ls.Dinv_arg.get());
+  const int64_t panel_len = ws.panel_len;
+
+  std::vector<k::LassoInstance> mem;
+  DVec Wall = DVec::Zeros(npanels * panel_len, F32);
+  DVec Pall = whiten ? DVec() : DVec::Zeros(npanels * panel_len, F32);
+  for (int i = 0; i < K; ++i) {
+    mem.push_back(g[i].route->pass.inst);
+    for (const DVec* v : {&mem[i].u, &mem[i].x0, &mem[i].x1, &mem[i].y0, &mem[i].y1, &mem[i].y1prev})
+      EPS_CHECK_MSG(reinterpret_cast<uintptr_t>(v->data()) % 16 == 0, "wide batch: unaligned state vector");
+    DVec slot = Wall.Slice(static_cast<int64_t>(i) * m, m);
+    k::Copy(slot, mem[i].w);  // ForwardFromState's result at Init
+    mem[i].w = slot;
+    mem[i].p = whiten ? slot : Pall.Slice(static_cast<int64_t>(i) * m, m);
+  }
+  DVec table;
+  {
+    std::vector<const k::LassoInstance*> v;
+    for (const auto& mb : mem) v.push_back(&mb);
+    k::LassoBatchUpload(v, F32, &table);
+  }
+  std::vector<uint64_t> live(npanels, 0);
+  std::vector<int> active(K);
+  for (int i = 0; i < K; ++i) {
+    active[i] = i;
+    live[i / PW] |= uint64_t(1) << (i % PW);
+  }
+  auto sweep = [&] {
+    for (int q = 0; q < npanels; ++q) {
+      if (live[q] == 0) continue;
+      const int first = q * PW, nk = std::min(PW, K - first);
+      ws.Run(table, first, nk, live[q], Wall.Slice(q * panel_len, panel_len),
+             whiten ? DVec() : Pall.Slice(q * panel_len, panel_len));
+    }
+  };
+  // frozen: their slots are masked from here on
+  RunGroupSchedule(g, t0, &active, sweep, [&](const std::vector<int>& gone) {
+    for (int i : gone) live[i / PW] &= ~(uint64_t(1) << (i % PW));
+  });
+  // every member's own w holds what its next sweep would read
+  for (int i = 0; i < K; ++i) k::Copy(g[i].route->pass.inst.w, mem[i].w);
+}
+
+}  // namespace
+
+std::vector<bool> RunFusedBatches(const std::vector<Solver*>& solvers) {
+  std::vector<bool> ran(solvers.size(), false);
+  const bool wide = BatchWideEnabled();
+  std::map<std::vector<uint64_t>, std::vector<size_t>> groups;
+  std::vector<LassoRoute*> routes(solvers.size(), nullptr);
+  std::vector<std::vector<uint64_t>> order;  // groups in order of their first instance
+  for (size_t i = 0; i < solvers.size(); ++i) {
+    routes[i] = dynamic_cast<LassoRoute*>(solvers[i]->batch_route());
+    std::vector<uint64_t> key;
+    if (routes[i] == nullptr || !routes[i]->BatchKey(solvers[i]->params(), &key)) continue;
+    auto& members = groups[key];
+    if (members.empty()) order.push_back(key);
+    members.push_back(i);
+  }
+  for (const auto& key : order) {
+    const std::vector<size_t>& idx = groups[key];
+    if (idx.size() < 2) continue;  // alone: the single path is the same solve, with pipelined checks
+    Group g;
+    for (size_t i : idx) g.push_back({solvers[i], routes[i]});
+    const LassoRoute& lead = *g[0].route;
+    if (wide && static_cast<int>(g.size()) >= BatchWideMin() && lead.dt == F32 &&
+        k::LassoWideSupported(lead.m, lead.n, lead.pass.A, lead.pass.lda))
+      RunWideGroup(g);
+    else
+      RunFusedGroup(g);
+    for (size_t i : idx) ran[i] = true;
+  }
+  return ran;
+}
+
+}  // namespace eps

@@ -263,7 +263,7 @@ inline uint64_t HashDouble(uint64_t h, double d) {
   return HashCombine(h, b);
 }
 
-// The whitened route of the fused lasso sweep (admm.cc): DenseMatrixImpl::Inverse keeps the
+// The whitened route of the fused lasso sweep (fused_route.cc): DenseMatrixImpl::Inverse keeps the
 // inverse Cholesky factor X = L^-1 of W^-1 = X^T X in the OpCache under FactorInverseKey(key of
 // the inverse) for f32 blocks of at least kWhitenMinRows rows, unless EPSILON_HIP_FUSED_WHITEN=0.
 constexpr int64_t kWhitenMinRows = 2048;

@@ -262,7 +262,6 @@ void InitZoneParams(const ProxOperatorArg& arg, ZoneParam* alpha, ZoneParam* bet
 
 class ScaledZoneProx final : public VectorProx {
  public:
-  bool CaptureSafe() const override { return true; }
 
  public:
   void Init(const ProxOperatorArg& arg) override {
@@ -415,7 +414,6 @@ REGISTER_EPIGRAPH_OPERATOR(SUM_QUANTILE, ScaledZoneEpigraph);
 
 class Norm2Prox final : public VectorProx {
  public:
-  bool CaptureSafe() const override { return true; }
 
   void Init(const ProxOperatorArg& arg) override {
     VectorProx::Init(arg);
@@ -467,7 +465,6 @@ REGISTER_PROX_OPERATOR(NORM_2, Norm2Prox);
 
 class NonNegativeProx final : public VectorProx {
  public:
-  bool CaptureSafe() const override { return true; }
 
  protected:
   void ApplyVector(const VectorProxInput& input, VectorProxOutput* output) override {
@@ -497,7 +494,6 @@ REGISTER_PROX_OPERATOR(TOTAL_VARIATION_1D, TotalVariation1DProx);
 
 class SumSquareProx final : public ProxOperator {
  public:
-  bool CaptureSafe() const override { return true; }
 
  public:
   void Init(const ProxOperatorArg& arg) override {
@@ -622,7 +618,6 @@ REGISTER_EPIGRAPH_OPERATOR(SUM_SQUARE, SumSquareEpigraph);
 
 class ZeroProx final : public ProxOperator {
  public:
-  bool CaptureSafe() const override { return true; }
 
  public:
   void Init(const ProxOperatorArg& arg) override {
@@ -707,7 +702,6 @@ REGISTER_PROX_OPERATOR(ZERO, ZeroProx);
 
 class AffineProx final : public ProxOperator {
  public:
-  bool CaptureSafe() const override { return true; }
 
  public:
   void Init(const ProxOperatorArg& arg) override {

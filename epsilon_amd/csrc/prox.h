@@ -35,7 +35,7 @@ class ProxOperatorArg {  // reference prox/prox.h:11-35
   const AffineOperator& A_;
 };
 
-// What the sweep fuser (admm.cc) needs to know about an operator to replace its Apply by a
+// What a fused route (fused_route.cc) needs to know about an operator to replace its Apply by a
 // fused kernel; an operator that cannot be described this way keeps the generic path.
 struct LeastSquaresDesc {  // SumSquareProx after block elimination [constraint, variable, arg]
   std::string var_key, arg_key, constraint_key;
@@ -86,10 +86,6 @@ class ProxOperator {  // reference prox/prox.h:37-43
   // DescribeScaledZone for an argument that may carry a constant offset (d->g; empty: none)
   virtual bool DescribeScaledZoneOffset(ScaledZoneDesc* d) const { return false; }
   virtual bool DescribeZeroProjection(ZeroProjectionDesc* d) const { return false; }
-  // true: Apply is a fixed sequence of launches on the library's stream - no host
-  // synchronisation, no decision on device data, no state carried from one call to the next -
-  // so a sweep through this operator can be captured into a hipGraph and replayed (admm.cc).
-  virtual bool CaptureSafe() const { return false; }
 };
 
 std::unique_ptr<ProxOperator> CreateProxOperator(int type, bool epigraph);
