@@ -1,4 +1,4 @@
-"""ZERO-term problems in graph form (problems.basis_pursuit / hinge_l1 / deadzone_l1): a fixed number
+"""ZERO-term problems in graph form (problems.basis_pursuit / hinge_l1 / deadzone_l1 / logreg_l1): a fixed number
 of sweeps on each route of the option "fused_zero" - "0" the generic operator path, "auto" the fused
 sweep (one pass over the data matrix, one row kernel, the inverse apply) - on one GPU.
 
@@ -11,11 +11,13 @@ per shape:
   spread            {route: (max - min) / median of the three runs}
   speedup           ms_per_sweep["0"] / ms_per_sweep["auto"]
 
-    python bench_zero.py [--shapes bp,bp64,hinge,hinge64,hinge_big,deadzone,floor,floor64] [--steps 200] [--warmup 20]
+    python bench_zero.py [--shapes bp,bp64,hinge,hinge64,hinge_big,deadzone,logreg,logreg64,logreg_big,floor,floor64]
+                         [--steps 200] [--warmup 20]
 
 Shapes: bp = basis pursuit 1000 x 3000 and hinge = hinge + l1 1500 x 5000, the reference's sizes
 (bp64 / hinge64 the same in f64); hinge_big = hinge + l1 4096 x 16384; deadzone = deadzone + l1
-1500 x 5000; floor = hinge + l1 256 x 601, the smallest row count the route takes (floor64 in f64).
+1500 x 5000; logreg = logistic loss + l1 1500 x 5000 (logreg64 in f64), logreg_big = the same at
+4096 x 16384; floor = hinge + l1 256 x 601, the smallest row count the route takes (floor64 in f64).
 """
 
 import argparse
@@ -31,6 +33,9 @@ SHAPES = {
     "hinge64": ("hinge_l1", 1500, 5000, "f64"),
     "hinge_big": ("hinge_l1", 4096, 16384, "f32"),
     "deadzone": ("deadzone_l1", 1500, 5000, "f32"),
+    "logreg": ("logreg_l1", 1500, 5000, "f32"),
+    "logreg64": ("logreg_l1", 1500, 5000, "f64"),
+    "logreg_big": ("logreg_l1", 4096, 16384, "f32"),
     "floor": ("hinge_l1", 256, 601, "f32"),
     "floor64": ("hinge_l1", 256, 601, "f64"),
 }
@@ -39,7 +44,7 @@ ROUTES = ("0", "auto")
 
 def parse():
     p = argparse.ArgumentParser()
-    p.add_argument("--shapes", default="bp,bp64,hinge,hinge64,hinge_big,deadzone")
+    p.add_argument("--shapes", default="bp,bp64,hinge,hinge64,hinge_big,deadzone,logreg,logreg64")
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=20)
     return p.parse_args()

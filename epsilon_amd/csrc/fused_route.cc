@@ -677,7 +677,8 @@ struct LassoRoute final : FusedRoute {
 // ---------------------------------------------------------------------------------------------------
 // Recognised structure: the last term is a ZERO term over private copies (x', and z' unless the
 // problem has no z: basis pursuit) whose block LDL^T is the projection ZeroProx describes; the
-// other terms are one scaled-zone term on x and at most one on z (which may carry an offset),
+// other terms are one scaled-zone term on x and at most one on z (which may carry an offset, and
+// may be SUM_LOGISTIC, a smooth separable term, instead of a scaled zone),
 // each tied to its copy by a consensus constraint copy + a var = 0 without a constant.  The
 // sweep is then: the pass over the data matrix (chain 2: back product, column chain, forward
 // product), the row kernel (row chain, the partials' sum, r) - basis pursuit: the partials'
@@ -691,6 +692,7 @@ struct ZeroRoute final : FusedRoute {
   int grid = 0;
   DVec state_n, state_m;  // the slices of a side's state in one buffer (n: the x constraint's rows)
   DVec w, p, tpart;
+  DVec head;  // a smooth z term: the row kernel's carried head (s, y_s, v of the coming sweep)
   InverseApply inv;
   k::LassoFusedArgs pass;
   k::ZeroRowsArgs rows;
@@ -705,13 +707,25 @@ struct ZeroRoute final : FusedRoute {
     int ix = -1, iz = -1;  // positions of the separable terms among the objective terms
     for (int i = 0; i + 1 < N; ++i) {
       ScaledZoneDesc d;
-      if (!a.prox[i]->DescribeScaledZoneOffset(&d)) return false;
-      if (ix < 0 && d.constraint_key == zp.x_constraint_key && d.g.n == 0) {
+      SmoothSeparableDesc sm;
+      const bool smooth = !a.prox[i]->DescribeScaledZoneOffset(&d);
+      if (smooth) {  // the scalar form is the zone's; its parameters are not read
+        if (!a.prox[i]->DescribeSmoothSeparable(&sm)) return false;
+        d.var_key = sm.var_key;
+        d.constraint_key = sm.constraint_key;
+        d.Bs = sm.Bs;
+        d.Cs = sm.Cs;
+        d.lam = sm.lam;
+        d.g = sm.g;
+      }
+      if (!smooth && ix < 0 && d.constraint_key == zp.x_constraint_key && d.g.n == 0) {
         sx = d;
         ix = i;
       } else if (has_z && iz < 0 && d.constraint_key == zp.z_constraint_key) {
         sz = d;
         iz = i;
+        rows.smooth = smooth;
+        rows.fn = sm.fn;
       } else {
         return false;
       }
@@ -804,8 +818,15 @@ struct ZeroRoute final : FusedRoute {
       rows.e = zp.e;
       rows.pkappa = -L.scale();
       SetThreshold(&rows, sz, az);
+      if (rows.smooth) {
+        head = DVec::Zeros(3 * m, dt);
+        rows.hs = head.Slice(0, m);
+        rows.hys = head.Slice(m, m);
+        rows.hv = head.Slice(2 * m, m);
+      }
     }
     AdoptState(views, Homes(a));
+    if (rows.smooth) k::ZeroSmoothHead(rows);
     ForwardFromState(a);
     return true;
   }

@@ -89,10 +89,17 @@ struct LassoFusedArgs {
   DVec e0, e1;
 };
 
+// The smooth separable functions of the Newton family (SmoothProx below; kernels_smooth_fn.h).
+enum SmoothFn { SMOOTH_EXP, SMOOTH_LOGISTIC, SMOOTH_NEG_ENTR, SMOOTH_INV_POS, SMOOTH_NEG_LOG };
+
 // The row side of the ZERO-term sweep (kernels_fused.hip), one launch, profile tag
 // "zero_fused_rows".  Per row: finishes sweep k with w (z' = v_z - e w, y and u on the z
 // constraint), runs the z term of sweep k + 1 (zone(Bs v + g) - g, scaled by Cs), forms the next
 // v_z, sums the pass's partials in a fixed order and writes r = (rhs - e v_z) + pkappa sum(tpart).
+// smooth: the z term is the smooth separable function `fn` (SMOOTH_LOGISTIC alone) in place of the
+// zone, prox_{lam fn}(Bs v + g) by the fp64 Newton of SmoothProx.  The z term of sweep k + 1 (s,
+// y_s, v_z) is then carried to the next launch in hs, hys, hv instead of being recomputed there:
+// ZeroSmoothHead fills them from the state before the first launch.
 struct ZeroRowsArgs {
   int64_t m = 0;
   int nparts = 0;
@@ -102,8 +109,12 @@ struct ZeroRowsArgs {
   DVec alpha_vec, beta_vec;            // optional per-row alpha / beta of the scaled zone
   double e = 0, pkappa = 0;
   double Bs = 0, Cs = 0, a1 = 0, lam = 0, alpha = 1, beta = 1, M = 0;
+  bool smooth = false;
+  SmoothFn fn = SMOOTH_LOGISTIC;
+  DVec hs, hys, hv;                    // smooth: m each, private to the caller
 };
 void ZeroFusedRows(const ZeroRowsArgs& args);
+void ZeroSmoothHead(const ZeroRowsArgs& args);  // profile tag "zero_fused_head"
 bool LassoFusedSupported(int64_t m, int64_t n, const DVec& A, int64_t lda);
 int LassoFusedGrid(int64_t m, int64_t n, DType dt = F32);
 int LassoFusedBlock(int64_t m, int64_t n, DType dt);  // threads per workgroup of the pass
@@ -333,7 +344,6 @@ void SegSocProject(const DVec& x, const DVec& t, const DVec& v, const DVec& tin,
 void SegLogSumExpProx(const DVec& x, const DVec& v, double lam, const Segs& S);
 void SegLogSumExpEpigraph(const DVec& x, const DVec& t, const DVec& v, const DVec& s,
                           const Segs& S);
-enum SmoothFn { SMOOTH_EXP, SMOOTH_LOGISTIC, SMOOTH_NEG_ENTR, SMOOTH_INV_POS, SMOOTH_NEG_LOG };
 // elementwise argmin lam f(x) + 1/2 (x - v)^2 (prox/newton.cc:49-112, sum_neg_log.cc:9-24)
 void SmoothProx(SmoothFn fn, const DVec& x, const DVec& v, double lam, const DVec* lam_vec);
 void SegSmoothEpigraph(SmoothFn fn, const DVec& x, const DVec& t, const DVec& v, const DVec& s,

@@ -206,20 +206,27 @@ void LaunchFusedT(const LassoFusedArgs& a, int grid, int block) {
 }
 
 // ---- the row side of a ZERO-term sweep ------------------------------------------------------------
-// A workgroup owns kZeroRows rows: thread (rl, pl) = (t % kZeroRows, t / kZeroRows) sums row rl's
-// partials k = pl, pl + kZeroLanes, ... (independent loads), the lanes of a row are added in lane
-// order through LDS - a fixed summation order - and lane 0 runs the row's chain (ZeroChainT with
-// d = w_i, kappa = -e) and writes r.  A workgroup reads and writes the state of its own rows only.
-constexpr int kZeroRows = 16, kZeroLanes = kBlock / kZeroRows;
+// A workgroup owns ROWS rows: thread (rl, pl) = (t % ROWS, t / ROWS) sums row rl's partials
+// k = pl, pl + kZeroLanes, ... (independent loads), the lanes of a row are added in lane order
+// through LDS - a fixed summation order, a function of (m, nparts) alone - and lane 0 runs the
+// row's chain (d = w_i, kappa = -e) and writes r.  A workgroup reads and writes the state of its
+// own rows only.
+// Fn = void, 16 rows: the z term is a scaled zone (ZeroChainT; a threshold on 16 lanes).
+// Fn a smooth function, 64 rows: the lanes pl = 0 are one whole wave, so the fp64 Newton runs on
+// every lane of the only wave that is still alive; consecutive lanes load consecutive rows of a
+// partial vector.  The head of this sweep (s, y_s, v) comes from the previous launch in hs, hys,
+// hv, and the next one is computed once and left there: one Newton solve per row and sweep.  A
+// head is a function of the stored boundary state alone, so carrying it changes no bit.
+constexpr int kZeroLanes = 16, kZeroRows = kBlock / kZeroLanes, kZeroSmoothRows = 64;
 
-template <class T>
-__global__ __launch_bounds__(kBlock) void ZeroFusedRowsKernel(
+template <class T, int ROWS, class Fn>
+__global__ __launch_bounds__(ROWS * kZeroLanes) void ZeroFusedRowsKernel(
     int64_t m, int nparts, const T* __restrict__ tpart, const T* __restrict__ w, FusedScalarsT<T> c,
     T pkappa, const T* __restrict__ rhs, const T* __restrict__ g, T* u, T* z, T* zq, T* yz, T* yq,
-    T* yzprev, T* yqprev, T* __restrict__ r) {
-  __shared__ T part[kZeroLanes][kZeroRows];
-  const int t = threadIdx.x, rl = t % kZeroRows, pl = t / kZeroRows;
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kZeroRows + rl;
+    T* yzprev, T* yqprev, T* __restrict__ r, double lam64, T* hs, T* hys, T* hv) {
+  __shared__ T part[kZeroLanes][ROWS];
+  const int t = threadIdx.x, rl = t % ROWS, pl = t / ROWS;
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * ROWS + rl;
   T s = T(0);
   if (i < m) {
     const T* p = tpart + i;
@@ -244,8 +251,21 @@ __global__ __launch_bounds__(kBlock) void ZeroFusedRowsKernel(
   if (c.beta_v != nullptr) ci.beta = c.beta_v[i];
   const T gi = g != nullptr ? g[i] : T(0);
   const T yzi = yz[i], yqi = yq[i];
-  T ns, nq, nys, nyq, nu;
-  const T vn = ZeroChainT<T>(w[i], ci, gi, u[i], yzi, yqi, &ns, &nq, &nys, &nyq, &nu);
+  T ns, nq, nys, nyq, nu, vn;
+  if constexpr (std::is_void<Fn>::value) {
+    vn = ZeroChainT<T>(w[i], ci, gi, u[i], yzi, yqi, &ns, &nq, &nys, &nyq, &nu);
+  } else {
+    // ZeroChainT from the carried head on: q = kappa d + v, y_q = q, u -= y_q
+    ns = hs[i];
+    nys = hys[i];
+    const T v = hv[i];
+    nq = nyq = c.kappa * w[i] + v;
+    nu = v - nq;
+    const ZeroHeadT<T> hn = ZeroHeadOfT<T, Fn>(ci, gi, nu, nys, nq, lam64);
+    hs[i] = hn.s;
+    hys[i] = hn.ys;
+    hv[i] = vn = hn.v;
+  }
   yzprev[i] = yzi;
   yqprev[i] = yqi;
   z[i] = ns;
@@ -258,31 +278,80 @@ __global__ __launch_bounds__(kBlock) void ZeroFusedRowsKernel(
   r[i] = pkappa * sum + base;
 }
 
-template <class T>
-void LaunchZeroRows(const ZeroRowsArgs& a) {
-  auto opt = [](const DVec& v) { return v.n > 0 ? v.as<T>() : nullptr; };
-  FusedScalarsT<T> c = {static_cast<T>(-a.e), static_cast<T>(a.Bs), static_cast<T>(a.Cs), static_cast<T>(a.a1),
-                        static_cast<T>(a.lam), static_cast<T>(a.alpha), static_cast<T>(a.beta), static_cast<T>(a.M),
-                        T(1), T(1), opt(a.alpha_vec), opt(a.beta_vec)};
-  const unsigned grid = static_cast<unsigned>((a.m + kZeroRows - 1) / kZeroRows);
-  hipLaunchKernelGGL(ZeroFusedRowsKernel<T>, dim3(grid), dim3(kBlock), 0, Runtime::Get().stream(), a.m, a.nparts,
-                     a.tpart.as<T>(), a.w.as<T>(), c, static_cast<T>(a.pkappa), opt(a.rhs), opt(a.g), a.u.as<T>(),
-                     a.z.as<T>(), a.zq.as<T>(), a.yz.as<T>(), a.yq.as<T>(), a.yzprev.as<T>(), a.yqprev.as<T>(),
-                     a.r.as<T>());
+// The first head of a smooth z term from the adopted boundary state, a thread per row.
+template <class T, class Fn>
+__global__ __launch_bounds__(kBlock) void ZeroSmoothHeadKernel(
+    int64_t m, FusedScalarsT<T> c, double lam64, const T* __restrict__ g, const T* __restrict__ u,
+    const T* __restrict__ yz, const T* __restrict__ yq, T* __restrict__ hs, T* __restrict__ hys,
+    T* __restrict__ hv) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= m) return;
+  const ZeroHeadT<T> h = ZeroHeadOfT<T, Fn>(c, g != nullptr ? g[i] : T(0), u[i], yz[i], yq[i], lam64);
+  hs[i] = h.s;
+  hys[i] = h.ys;
+  hv[i] = h.v;
 }
 
-}  // namespace
+template <class T> const T* OptT(const DVec& v) { return v.n > 0 ? v.as<T>() : nullptr; }
 
-void ZeroFusedRows(const ZeroRowsArgs& a) {
+template <class T> FusedScalarsT<T> ZeroRowScalars(const ZeroRowsArgs& a) {
+  return {static_cast<T>(-a.e), static_cast<T>(a.Bs), static_cast<T>(a.Cs), static_cast<T>(a.a1),
+          static_cast<T>(a.lam), static_cast<T>(a.alpha), static_cast<T>(a.beta), static_cast<T>(a.M),
+          T(1), T(1), OptT<T>(a.alpha_vec), OptT<T>(a.beta_vec)};
+}
+
+template <class T, int ROWS, class Fn>
+void LaunchZeroRows(const ZeroRowsArgs& a) {
+  const unsigned grid = static_cast<unsigned>((a.m + ROWS - 1) / ROWS);
+  const bool smooth = !std::is_void<Fn>::value;
+  hipLaunchKernelGGL((ZeroFusedRowsKernel<T, ROWS, Fn>), dim3(grid), dim3(ROWS * kZeroLanes), 0,
+                     Runtime::Get().stream(), a.m, a.nparts, a.tpart.as<T>(), a.w.as<T>(), ZeroRowScalars<T>(a),
+                     static_cast<T>(a.pkappa), OptT<T>(a.rhs), OptT<T>(a.g), a.u.as<T>(), a.z.as<T>(), a.zq.as<T>(),
+                     a.yz.as<T>(), a.yq.as<T>(), a.yzprev.as<T>(), a.yqprev.as<T>(), a.r.as<T>(), a.lam,
+                     smooth ? a.hs.as<T>() : nullptr, smooth ? a.hys.as<T>() : nullptr,
+                     smooth ? a.hv.as<T>() : nullptr);
+}
+
+template <class T>
+void LaunchZeroSmoothHead(const ZeroRowsArgs& a) {
+  hipLaunchKernelGGL((ZeroSmoothHeadKernel<T, FnLogistic>), dim3(static_cast<unsigned>((a.m + kBlock - 1) / kBlock)),
+                     dim3(kBlock), 0, Runtime::Get().stream(), a.m, ZeroRowScalars<T>(a), a.lam, OptT<T>(a.g),
+                     a.u.as<T>(), a.yz.as<T>(), a.yq.as<T>(), a.hs.as<T>(), a.hys.as<T>(), a.hv.as<T>());
+}
+
+void CheckZeroRows(const ZeroRowsArgs& a) {
   const DType dt = a.w.dt;
   EPS_CHECK(a.m >= 1 && a.nparts >= 1 && a.tpart.dt == dt && a.tpart.n >= static_cast<int64_t>(a.nparts) * a.m);
   for (const DVec* v : {&a.w, &a.r, &a.u, &a.z, &a.zq, &a.yz, &a.yq, &a.yzprev, &a.yqprev})
     EPS_CHECK(v->n == a.m && v->dt == dt);
   for (const DVec* v : {&a.rhs, &a.g, &a.alpha_vec, &a.beta_vec})
     if (v->n > 0) EPS_CHECK(v->n == a.m && v->dt == dt);
+  if (!a.smooth) return;
+  EPS_CHECK_MSG(a.fn == SMOOTH_LOGISTIC, "the fused ZERO-term rows take SUM_LOGISTIC alone, got " << a.fn);
+  for (const DVec* v : {&a.hs, &a.hys, &a.hv}) EPS_CHECK(v->n == a.m && v->dt == dt);
+}
+
+}  // namespace
+
+void ZeroFusedRows(const ZeroRowsArgs& a) {
+  CheckZeroRows(a);
   ProfScope prof("zero_fused_rows", a.m, a.nparts);
-  if (dt == F32) LaunchZeroRows<float>(a);
-  else LaunchZeroRows<double>(a);
+  if (a.smooth) {
+    if (a.w.dt == F32) LaunchZeroRows<float, kZeroSmoothRows, FnLogistic>(a);
+    else LaunchZeroRows<double, kZeroSmoothRows, FnLogistic>(a);
+  } else {
+    if (a.w.dt == F32) LaunchZeroRows<float, kZeroRows, void>(a);
+    else LaunchZeroRows<double, kZeroRows, void>(a);
+  }
+  EPS_HIP(hipGetLastError());
+}
+
+void ZeroSmoothHead(const ZeroRowsArgs& a) {
+  EPS_CHECK(a.smooth);
+  CheckZeroRows(a);
+  ProfScope prof("zero_fused_head", a.m);
+  if (a.w.dt == F32) LaunchZeroSmoothHead<float>(a);
+  else LaunchZeroSmoothHead<double>(a);
   EPS_HIP(hipGetLastError());
 }
 

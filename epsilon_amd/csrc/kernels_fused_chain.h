@@ -5,7 +5,10 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "kernels.h"
+#include "kernels_smooth_fn.h"
 
 namespace eps {
 namespace k {
@@ -127,14 +130,18 @@ __device__ inline T ChainOneT(T d, const FusedScalarsT<T>& c, T u, T y0p, T y1p,
 //   ZERO term: u += y_q, v = u, q = v + (factor) * (product with w), y_q = q, u -= y_q
 // (prox_admm.cc:135-147 with the separable term before the ZERO term).  The head runs up to v and
 // needs the boundary state alone; the tail needs this sweep's w.
+// Fn (kernels_smooth_fn.h): a smooth separable term in place of the zone, its prox the fp64 Newton
+// of SmoothProxKernel on the rounded input with the operator's own weight `lam64`.
 template <class T> struct ZeroHeadT {
   T s, ys, v;  // the separable term's variable and y; the ZERO prox's input on this row
 };
-template <class T>
-__device__ inline ZeroHeadT<T> ZeroHeadOfT(const FusedScalarsT<T>& c, T g, T u, T ysp, T yqp) {
+template <class T, class Fn = void>
+__device__ inline ZeroHeadT<T> ZeroHeadOfT(const FusedScalarsT<T>& c, T g, T u, T ysp, T yqp, double lam64 = 0) {
   const T ub = ((u - ysp) - yqp) + ysp;  // sweep start, then the separable term's u += y_s
   const T vin = c.Bs * ub + g;           // VectorProx: B v + g            (vector_prox.cc:141)
-  const T xz = ScaledZoneOneT<T>(vin, c.lam, c.alpha, c.beta, c.M);
+  T xz;
+  if constexpr (std::is_void<Fn>::value) xz = ScaledZoneOneT<T>(vin, c.lam, c.alpha, c.beta, c.M);
+  else xz = static_cast<T>(ProxElem<Fn>(static_cast<double>(vin), lam64));
   const T s = c.Cs * (xz - g);           // C (x - g)                      (vector_prox.cc:145)
   const T ys = c.a1 * s;                 // y_s = A_ s
   const T uc = ub - ys;                  // u -= y_s

@@ -54,6 +54,15 @@ struct ScaledZoneDesc {  // ScaledZoneProx with scalar H, A and uniform paramete
   DVec alpha_vec, beta_vec;  // per-element alpha / beta (SUM_QUANTILE with data vectors); empty: uniform
   DVec g;  // constant offset of the argument, x = Cs * (zone(Bs*v + g) - g): DescribeScaledZoneOffset only
 };
+// A smooth separable term of the Newton family in the same scalar form,
+// x = Cs * (prox_{lam fn}(Bs*v + g) - g) with one weight for every element (SmoothProxOp;
+// SUM_LOGISTIC alone answers).
+struct SmoothSeparableDesc {
+  k::SmoothFn fn = k::SMOOTH_LOGISTIC;
+  std::string var_key, constraint_key;
+  double Bs = 0, Cs = 0, lam = 0;
+  DVec g;  // constant offset of the argument (empty: none)
+};
 
 struct GroupNorm2Desc {  // Norm2Prox with axis = 1 on an n x cols argument: one group per row
   std::string var_key, constraint_key;
@@ -85,6 +94,7 @@ class ProxOperator {  // reference prox/prox.h:37-43
   virtual bool DescribeGroupNorm2(GroupNorm2Desc* d) const { return false; }
   // DescribeScaledZone for an argument that may carry a constant offset (d->g; empty: none)
   virtual bool DescribeScaledZoneOffset(ScaledZoneDesc* d) const { return false; }
+  virtual bool DescribeSmoothSeparable(SmoothSeparableDesc* d) const { return false; }
   virtual bool DescribeZeroProjection(ZeroProjectionDesc* d) const { return false; }
 };
 
@@ -148,7 +158,8 @@ class VectorProx : public ProxOperator {
   // and handles the axis itself; elementwise operators are axis-agnostic.
   virtual void ApplyVector(const VectorProxInput& input, VectorProxOutput* output) = 0;
 
-  // For DescribeScaledZone: true iff B_, C_ are single scalar blocks, no offset, scalar lambda.
+  // For DescribeScaledZone / DescribeSmoothSeparable: true iff B_, C_ are single scalar blocks,
+  // no offset, scalar lambda.
   // With `g` an offset on the argument row is accepted and handed out (empty: there is none).
   bool ScalarForm(std::string* var_key, std::string* constraint_key, double* Bs, double* Cs,
                   double* lam, DVec* g = nullptr) const;

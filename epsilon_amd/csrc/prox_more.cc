@@ -100,6 +100,15 @@ REGISTER_EPIGRAPH_OPERATOR(LOG_SUM_EXP, LogSumExpEpigraph);
 //      sum_neg_entr.cc, sum_inv_pos.cc, sum_neg_log.cc) --------------------------------------------------
 
 template <k::SmoothFn FN> class SmoothProxOp final : public VectorProx {
+ public:
+  // SUM_LOGISTIC alone: the domain projections of the others and the closed form of SUM_NEG_LOG
+  // have no fused row chain.
+  bool DescribeSmoothSeparable(SmoothSeparableDesc* d) const override {
+    if (FN != k::SMOOTH_LOGISTIC) return false;
+    d->fn = FN;
+    return ScalarForm(&d->var_key, &d->constraint_key, &d->Bs, &d->Cs, &d->lam, &d->g);
+  }
+
  protected:
   void ApplyVector(const VectorProxInput& input, VectorProxOutput* output) override {
     const DVec& v = input.value_vec(0);

@@ -407,7 +407,8 @@ def logreg_l1(m, n, lam=None, seed=0):
     (reference python/epopt/problems/logreg_l1.py, compiled like docs/notebooks):
 
       sum_logistic(z) + norm_1(x)[lam] + zero(C x' - z')   s.t.  x' - x = 0,  z' - z = 0
-    with C = -diag(y) A."""
+    with C = -diag(y) A.  Fat C with at least 256 rows runs on the fused sweep of ZERO-term
+    problems, the logistic prox inside its row kernel (option "fused_zero")."""
     rng = np.random.RandomState(seed)
     A = rng.randn(m, n)
     x0 = rng.randn(n) * (rng.rand(n) < 0.3)
