@@ -16,6 +16,7 @@
 #include "admm.h"
 #include "block.h"
 #include "comm.h"
+#include "fused_route.h"
 #include "kernels.h"
 #include "linear_map.h"
 #include "wire.h"
@@ -326,6 +327,9 @@ int eps_set_option(const char* key, const char* value) {
       if (std::strcmp(value, "0") != 0 && std::strcmp(value, "auto") != 0)
         EPS_FATAL("fused_zero must be 0 or auto, got " << value);
       setenv("EPSILON_HIP_FUSED_ZERO", value, 1);
+    } else if (std::strcmp(key, "fused_resident") == 0) {
+      (void)ParseFusedResident(value);  // a bad value is an error here, not at the next Init
+      setenv("EPSILON_HIP_FUSED_RESIDENT_KB", value, 1);
     } else if (std::strcmp(key, "refine") == 0) {
       if (std::strcmp(value, "auto") == 0) unsetenv("EPSILON_HIP_REFINE");
       else setenv("EPSILON_HIP_REFINE", value, 1);
@@ -830,6 +834,50 @@ int eps_bench_stream(const void* device_ptr, size_t bytes, int mode, int grid, i
                      scratch.as<float>(), grid);
     });
     (void)rt;
+  });
+}
+
+int eps_bench_stream_resident(const void* device_ptr, size_t bytes, size_t resident_bytes, int grid, int iters,
+                              double* ms_avg) {
+  return Guard([&] {
+    const size_t column = 40000;  // k::StreamResidentProbe's
+    EPS_CHECK_MSG(bytes >= column && resident_bytes <= bytes && iters >= 1 && ms_avg != nullptr,
+                  "eps_bench_stream_resident: bad arguments");
+    DVec own;
+    const void* src = device_ptr;
+    if (src == nullptr) {
+      own = Synthetic(static_cast<int64_t>(bytes / 4), F32, 1.0);
+      src = own.data();
+    }
+    EPS_HIP(hipDeviceSynchronize());  // a borrowed pointer may still be written by another stream
+    if (grid <= 0) grid = 2048;
+    DVec scratch = DVec::Empty(grid, F32);
+    const int64_t per_column = static_cast<int64_t>(resident_bytes / (bytes / column)) / 16 * 16;
+    // TimeLaunches' two untimed launches fill the cache: the average is of launches that find it filled
+    *ms_avg = TimeLaunches(iters, [&] {
+      k::StreamResidentProbe(src, static_cast<int64_t>(bytes), per_column, scratch.as<float>(), grid);
+    });
+  });
+}
+
+int eps_fused_residency(int64_t m, int64_t n, int f64, int64_t budget_bytes, int* qfull, int64_t* jcut,
+                        int64_t* resident_bytes) {
+  return Guard([&] {
+    EPS_CHECK_MSG(m >= 1 && n >= 1 && qfull != nullptr && jcut != nullptr && resident_bytes != nullptr,
+                  "eps_fused_residency: bad arguments");
+    const k::FusedResidency r = k::LassoFusedResidency(m, n, f64 ? F64 : F32, budget_bytes);
+    *qfull = r.qfull;
+    *jcut = r.jcut;
+    *resident_bytes = r.bytes;
+  });
+}
+
+int eps_fused_residency_last(int* qfull, int64_t* jcut) {
+  return Guard([&] {
+    EPS_CHECK_MSG(qfull != nullptr && jcut != nullptr, "eps_fused_residency_last: bad arguments");
+    const k::FusedResidency r = k::LastFusedResidency();
+    *qfull = r.qfull;
+    *jcut = r.jcut;
   });
 }
 

@@ -130,6 +130,29 @@ bool FusedDisabled() {  // EPSILON_HIP_FUSED=0 (eps_set_option "fused"), read at
 
 int BatchWideMin();  // (with the batched solves below)
 
+// What the Infinity Cache holds of lines loaded with the default policy before re-reads start to
+// miss: the upper end of the plateau of the budget sweep on the pass ("A resident
+// slab of the streamed matrix").
+constexpr int64_t kResidentLimitBytes = int64_t(224) << 20;
+
+// EPSILON_HIP_FUSED_RESIDENT_KB (eps_set_option "fused_resident"), read at every Init: the budget
+// in bytes, -1 for "auto".
+int64_t FusedResidentOption() {
+  const char* e = std::getenv("EPSILON_HIP_FUSED_RESIDENT_KB");
+  return e == nullptr ? -1 : ParseFusedResident(e);
+}
+
+// The share of the pass's m x n matrix that stays in the Infinity Cache (k::LassoFusedResidency)
+// under the option.  `touched`: the bytes the sweep itself moves with the default policy between
+// two uses of a matrix line - "auto" leaves them their room.  `auto_on`: false on the routes whose
+// sweep has not been timed with a resident share - there "auto" streams everything
+// and only an explicit number of KiB gives a share.
+k::FusedResidency ResidentShare(int64_t m, int64_t n, DType dt, int64_t touched, bool auto_on) {
+  int64_t budget = FusedResidentOption();
+  if (budget < 0) budget = auto_on ? std::max<int64_t>(0, kResidentLimitBytes - touched) : 0;
+  return k::LassoFusedResidency(m, n, dt, budget);
+}
+
 // Matrix variables X (n x k) under the data map I_k (x) A: the k columns run as k members of the
 // batched kernels inside one solve (LassoRoute).  Below this many rows of A the solve keeps the
 // generic operator path (a constant: no crossover was measured).
@@ -254,6 +277,18 @@ struct LassoRoute final : FusedRoute {
   std::vector<k::LassoInstance> members;
   DVec table;              // their descriptors on the device (LassoBatchUpload)
   WideSweep ws;
+  k::FusedResidency res;   // the matrix's share that stays in the Infinity Cache (BuildPass)
+
+  // ... for a sweep of `count` members on this matrix: each has its partials (written and re-read:
+  // the same lines), six state vectors, p and w; the explicit apply reads the inverse.  Sharded and
+  // peer sweeps and the wide kernels stream everything; so does "auto" for more than one member
+  // (a batch, a matrix variable): the batched pass has not been timed with a share.
+  k::FusedResidency Residency(int64_t count) const {
+    if (sharded || use_peer || wide || ShardSpec::Get().active()) return k::FusedResidency();
+    const int64_t sz = dt == F32 ? 4 : 8;
+    const int64_t touched = (count * (static_cast<int64_t>(grid) * m + 6 * n + 2 * m) + (whiten ? 0 : m * m)) * sz;
+    return ResidentShare(m, n, dt, touched, /*auto_on=*/count == 1 && cols == 1);
+  }
 
   bool Enable(const MultiBlockParts& a) {
     if (FusedDisabled() || a.prox.size() != 2 || a.num_constraints != 1 || !a.b.data().empty()) return false;
@@ -527,6 +562,9 @@ struct LassoRoute final : FusedRoute {
     pass.n = n;
     pass.lda = whiten ? m : L.rows();
     pass.A = whiten ? Ahat : L.data();
+    res = Residency(cols);
+    pass.qfull = res.qfull;
+    pass.jcut = res.jcut;
     k::LassoInstance& s = pass.inst;
     s.w = w;
     s.tpart = tpart;
@@ -578,7 +616,7 @@ struct LassoRoute final : FusedRoute {
     }
     const int width = k::LassoBatchWidth(m, n, dt);
     for (int first = 0; first < K; first += width)
-      k::LassoBatchPass(m, n, pass.lda, pass.A, table, first, std::min(width, K - first), group_lam);
+      k::LassoBatchPass(m, n, pass.lda, pass.A, table, first, std::min(width, K - first), group_lam, res);
     k::ReducePartialsBatch(m, grid, table, K, dt, rhs_aligned);
     if (!whiten) ApplyInverseFixed();
   }
@@ -785,6 +823,13 @@ struct ZeroRoute final : FusedRoute {
       pass.A = L.data();
       pass.chain = 2;
       pass.e0 = sn[6].v;
+      // beside the matrix the sweep touches the partials (the rows kernel re-reads them), the seven
+      // state vectors of either side, p, w, and the inverse
+      const int64_t sz = dt == F32 ? 4 : 8;
+      const k::FusedResidency res =
+          ResidentShare(m, n, dt, (static_cast<int64_t>(grid) * m + 7 * (n + m) + 2 * m + m * m) * sz, /*auto_on=*/false);
+      pass.qfull = res.qfull;
+      pass.jcut = res.jcut;
       k::LassoInstance& s = pass.inst;
       s.w = w;
       s.tpart = tpart;
@@ -916,6 +961,13 @@ struct TwoBlockRoute final : FusedRoute {
     pass.A = L.data();
     pass.chain = 1;
     pass.a0 = a0;
+    {  // beside the matrix: the partials, eight state vectors, p, w, and the inverse
+      const int64_t sz = dt == F32 ? 4 : 8;
+      const k::FusedResidency res =
+          ResidentShare(m, n, dt, (static_cast<int64_t>(grid) * m + 8 * n + 2 * m + m * m) * sz, /*auto_on=*/false);
+      pass.qfull = res.qfull;
+      pass.jcut = res.jcut;
+    }
     pass.e0 = u1;
     pass.e1 = z1p;
     k::LassoInstance& s = pass.inst;
@@ -956,6 +1008,19 @@ std::unique_ptr<FusedRoute> Recognise(const Parts& parts) {
 }
 
 }  // namespace
+
+int64_t ParseFusedResident(const char* value) {
+  if (std::strcmp(value, "auto") == 0) return -1;
+  const int64_t cap = int64_t(1) << 40;  // KiB: far beyond any matrix, and kb * 1024 cannot overflow
+  int64_t kb = 0;
+  bool ok = value[0] != '\0';
+  for (const char* c = value; ok && *c != '\0'; ++c) {
+    ok = *c >= '0' && *c <= '9';
+    if (ok) kb = std::min(cap, kb * 10 + (*c - '0'));
+  }
+  if (!ok) EPS_FATAL("fused_resident must be auto or a number of KiB, got " << value);
+  return kb * 1024;
+}
 
 std::unique_ptr<FusedRoute> RecogniseMultiBlockRoute(const MultiBlockParts& parts) {
   const bool zero = FusedZeroAuto();  // (read first: a bad value is an error whatever the problem)
@@ -1028,6 +1093,7 @@ void RunFusedGroup(const Group& g) {
   }
   const int K = static_cast<int>(g.size());
   DVec symv_work = P.n > 0 ? DVec::Empty(K * k::SymvWorkspace(m), dt) : DVec();
+  const k::FusedResidency res = lead.Residency(K);
 
   std::vector<int> active(K);
   for (int i = 0; i < K; ++i) active[i] = i;
@@ -1041,7 +1107,7 @@ void RunFusedGroup(const Group& g) {
   auto sweep = [&] {
     const int na = static_cast<int>(active.size());
     for (int first = 0; first < na; first += width)
-      k::LassoBatchPass(m, n, lead.pass.lda, lead.pass.A, table, first, std::min(width, na - first));
+      k::LassoBatchPass(m, n, lead.pass.lda, lead.pass.A, table, first, std::min(width, na - first), nullptr, res);
     k::ReducePartialsBatch(m, lead.grid, table, na, dt, rhs_aligned);
     if (lead.whiten) {
       // the reduction wrote every member's w_hat: no inverse apply

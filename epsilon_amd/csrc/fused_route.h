@@ -62,6 +62,11 @@ struct TwoBlockParts {
 
 // The route of the problem, or null: the lasso structure, then the ZERO-term structure
 // (multi-block driver); the lasso structure in two-block form.
+// The option "fused_resident" (eps_set_option, EPSILON_HIP_FUSED_RESIDENT_KB): "auto" gives -1, a
+// number of KiB (decimal digits alone) its bytes, clamped to 2^50; anything else is an error that
+// names the value.
+int64_t ParseFusedResident(const char* value);
+
 std::unique_ptr<FusedRoute> RecogniseMultiBlockRoute(const MultiBlockParts& parts);
 std::unique_ptr<FusedRoute> RecogniseTwoBlockRoute(const TwoBlockParts& parts);
 

@@ -87,6 +87,10 @@ struct LassoFusedArgs {
   int chain = 0;
   double a0 = 1;
   DVec e0, e1;
+  // the matrix's share that is loaded to stay in the Infinity Cache (LassoFusedResidency); 0, 0:
+  // every load non-temporal
+  int qfull = 0;
+  int64_t jcut = 0;
 };
 
 // The smooth separable functions of the Newton family (SmoothProx below; kernels_smooth_fn.h).
@@ -118,6 +122,23 @@ void ZeroSmoothHead(const ZeroRowsArgs& args);  // profile tag "zero_fused_head"
 bool LassoFusedSupported(int64_t m, int64_t n, const DVec& A, int64_t lda);
 int LassoFusedGrid(int64_t m, int64_t n, DType dt = F32);
 int LassoFusedBlock(int64_t m, int64_t n, DType dt);  // threads per workgroup of the pass
+// The share of the m x n matrix that the pass keeps resident in the Infinity Cache under a budget
+// of `budget` bytes.  A row chunk is the rows one load instruction of the workgroup covers
+// (LassoFusedBlock threads x 16 bytes of a column); chunk q of column j is resident iff
+// q < qfull || (q == qfull && j < jcut) - every column carries its piece, so cache hits and HBM
+// reads are in flight together.  `bytes` is the largest total of this form that is <= budget;
+// a matrix that fits is resident as a whole, budget <= 0 gives qfull = jcut = 0.  A pure function
+// of its arguments: no device is touched.
+struct FusedResidency {
+  int qfull = 0;
+  int64_t jcut = 0;
+  int64_t bytes = 0;
+};
+FusedResidency LassoFusedResidency(int64_t m, int64_t n, DType dt, int64_t budget);
+// What the most recent launch of the pass (single or batched) in this process was given: lets a
+// test see that an option reached the kernel, since no iterate depends on it.
+FusedResidency LastFusedResidency();
+void NoteFusedResidency(int qfull, int64_t jcut);
 void LassoFusedPass(const LassoFusedArgs& args);
 // out6 = {||y0||^2, ||y1||^2, ||y0 + y1||^2, ||y1 - y1prev||^2, ||u||^2, peer_err ? 1 : 0} (device
 // doubles), one launch; `work`: 64 * 5 + 1 doubles, zero-initialised once (the last double is a
@@ -153,8 +174,9 @@ void LassoBatchUpload(const std::vector<const LassoInstance*>& members, DType dt
 // `group_lam` (optional): the instances are ALL the columns of one matrix variable and the
 // threshold step is the group shrinkage of its rows with this weight (NORM_2 along axis 1)
 // instead of each instance's scaled zone.
+// `res`: the matrix's resident share, as in LassoFusedArgs.
 void LassoBatchPass(int64_t m, int64_t n, int64_t lda, const DVec& A, const DVec& table, int first,
-                    int count, const double* group_lam = nullptr);
+                    int count, const double* group_lam = nullptr, const FusedResidency& res = FusedResidency());
 // p = pkappa * sum(tpart) (+ rhs) of `count` instances in one launch, each in the summation order
 // of ReducePartials(m, nparts, tpart, pkappa, 0, p, rhs).  `rhs_aligned`: every rhs present is
 // 16-byte aligned (picks the same kernel form as the single call).
@@ -242,6 +264,9 @@ bool MultiGemv(bool transA, int64_t M, int64_t N, int64_t K, double alpha, const
                const DVec& B, int64_t ldb, double beta, const DVec& C, int64_t ldc);
 // HBM ceiling probes: mode 0 read (non-temporal), 1 read, 2 copy; scratch holds `grid` floats.
 void StreamProbe(int mode, const void* src, void* dst, int64_t bytes, float* scratch, int grid);
+// Residency probe: reads the buffer as 40000-byte columns, the first `resident_per_column` bytes
+// (a multiple of 16) of each with the default policy, the rest non-temporal.
+void StreamResidentProbe(const void* src, int64_t bytes, int64_t resident_per_column, float* scratch, int grid);
 
 // dst (rows x cols, ld = rows) = alpha * op(src)
 void MatCopy(bool trans, int64_t rows, int64_t cols, double alpha, const DVec& src,

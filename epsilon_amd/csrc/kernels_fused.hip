@@ -23,6 +23,7 @@
 // drains.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
@@ -51,7 +52,7 @@ template <class T, int NR, int BS, int MODE>
 __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
     int64_t m, int64_t n, const T* __restrict__ A, int64_t lda, const T* __restrict__ w,
     FusedScalarsT<T> c, T* u, T* x0, T* x1, T* y0, T* y1, T* y1prev, T* __restrict__ tpart,
-    unsigned* epoch, T* e0, T* e1) {
+    unsigned* epoch, T* e0, T* e1, int qfull, int64_t jcut) {
   typedef typename Chunk<T>::V V;
   constexpr int R = Chunk<T>::R;
   __shared__ T red[2][BS / 64];
@@ -78,13 +79,16 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
     const int64_t j = 2 * jp + (step & 1);
     return (jp < npairs && j < n) ? j : -1;
   };
-  // The matrix is read once per sweep with no reuse: non-temporal loads keep it from evicting
-  // the cached inverse (K3 operand, 200 MB of tiles) from the 256 MB Infinity Cache.
+  // The matrix is read once per sweep.  Its resident share (LassoFusedResidency: row chunks below
+  // qfull of every column, chunk qfull of the columns below jcut) is loaded with the default
+  // policy and stays in the 256 MB Infinity Cache from sweep to sweep; the rest is non-temporal,
+  // which neither displaces that share nor the cached inverse where the sweep applies one.
   auto load = [&](V (&a)[NR], int64_t j) {
     const T* cp = A + j * lda;
+    const int nres = qfull + (j < jcut ? 1 : 0);  // uniform: the choice below is a scalar branch
 #pragma unroll
     for (int q = 0; q < NR; ++q) {
-      if (row[q] < m) a[q] = __builtin_nontemporal_load(reinterpret_cast<const V*>(cp + row[q]));
+      if (row[q] < m) a[q] = LoadMatrixChunk<T>(cp + row[q], q < nres);
       else a[q] = zero;
     }
   };
@@ -180,7 +184,8 @@ void LaunchFused(const LassoFusedArgs& a, int grid) {
       (a.chain == 1 ? LassoFusedStreamKernelT<T, NR, BS, 1>
                     : a.chain == 2 ? LassoFusedStreamKernelT<T, NR, BS, 2> : LassoFusedStreamKernelT<T, NR, BS, 0>),
       dim3(grid), dim3(BS), 0, Runtime::Get().stream(), a.m, a.n, a.A.as<T>(), a.lda, i.w,
-      ScalarsOf<T>(i, a.a0, a.inst.a1), i.u, i.x0, i.x1, i.y0, i.y1, i.y1prev, i.tpart, a.epoch, e0, e1);
+      ScalarsOf<T>(i, a.a0, a.inst.a1), i.u, i.x0, i.x1, i.y0, i.y1, i.y1prev, i.tpart, a.epoch, e0, e1,
+      a.qfull, a.jcut);
 }
 
 // The instantiation for (type, threads, 16-byte row chunks a thread needs).  512 threads: the
@@ -485,8 +490,41 @@ int LassoFusedGrid(int64_t m, int64_t n, DType dt) {
   return static_cast<int>(g < 1 ? 1 : g);
 }
 
+FusedResidency LassoFusedResidency(int64_t m, int64_t n, DType dt, int64_t budget) {
+  FusedResidency r;
+  if (budget <= 0 || m < 1 || n < 1) return r;
+  const int64_t elem = dt == F32 ? 4 : 8;
+  const int64_t chunk_rows = static_cast<int64_t>(LassoFusedBlock(m, n, dt)) * (16 / elem);
+  const int64_t nchunks = (m + chunk_rows - 1) / chunk_rows;
+  // whole chunks of every column while they fit, then the next chunk of as many columns as fit
+  // (the last chunk of a column may be partly filled: it costs its own bytes)
+  for (int64_t q = 0; q < nchunks; ++q) {
+    const int64_t piece = std::min(chunk_rows, m - q * chunk_rows) * elem;
+    const int64_t left = budget - r.bytes;
+    if (left / piece >= n) {
+      r.bytes += piece * n;
+      r.qfull = static_cast<int>(q + 1);
+      continue;
+    }
+    r.jcut = left / piece;
+    r.bytes += piece * r.jcut;
+    break;
+  }
+  return r;
+}
+
+namespace {
+FusedResidency g_last_residency;
+}
+FusedResidency LastFusedResidency() { return g_last_residency; }
+void NoteFusedResidency(int qfull, int64_t jcut) {
+  g_last_residency.qfull = qfull;
+  g_last_residency.jcut = jcut;
+}
+
 void LassoFusedPass(const LassoFusedArgs& a) {
   EPS_CHECK(LassoFusedSupported(a.m, a.n, a.A, a.lda));
+  EPS_CHECK(a.qfull >= 0 && a.jcut >= 0 && a.jcut <= a.n);
   const DType dt = a.A.dt;
   const LassoInstance& s = a.inst;
   EPS_CHECK(s.w.n == a.m && s.w.dt == dt);
@@ -502,6 +540,7 @@ void LassoFusedPass(const LassoFusedArgs& a) {
   EPS_CHECK(reinterpret_cast<uintptr_t>(s.w.data()) % 16 == 0 &&
             reinterpret_cast<uintptr_t>(s.tpart.data()) % 16 == 0);
   ProfScope prof(a.chain == 2 ? "zero_fused" : "lasso_fused", a.m, a.n);
+  NoteFusedResidency(a.qfull, a.jcut);
   if (dt == F32) LaunchFusedT<float>(a, grid, block);
   else LaunchFusedT<double>(a, grid, block);
   EPS_HIP(hipGetLastError());

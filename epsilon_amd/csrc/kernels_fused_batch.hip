@@ -36,14 +36,15 @@ template <class T, int NR, int KB, bool GROUP>
 __global__ __launch_bounds__(kBlock) void LassoBatchStreamKernel(int64_t m, int64_t n, const T* __restrict__ A,
                                                                  int64_t lda,
                                                                  const LassoBatchInst<T>* __restrict__ tab,
-                                                                 int nk, double glam) {
+                                                                 int nk, double glam, int qfull,
+                                                                 int64_t jcut) {
   typedef typename Chunk<T>::V V;
   constexpr int R = Chunk<T>::R;
   __shared__ T red[2][KB][kBlock / 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  V zero;
-#pragma unroll
-  for (int r = 0; r < R; ++r) zero[r] = T(0);
+  // (a constant, as in the single pass: filled element by element, the guarded loads below
+  // become selects and lose their non-temporal hint)
+  const V zero = T(0);
   V wv[KB][NR], tp[KB][NR];
   int64_t row[NR];
 #pragma unroll
@@ -63,11 +64,15 @@ __global__ __launch_bounds__(kBlock) void LassoBatchStreamKernel(int64_t m, int6
     const int64_t j = 2 * jp + (step & 1);
     return (jp < npairs && j < n) ? j : -1;
   };
+  // the single pass's loads: its resident share with the default policy, the rest non-temporal
   auto load = [&](V (&a)[NR], int64_t j) {
     const T* cp = A + j * lda;
+    const int nres = qfull + (j < jcut ? 1 : 0);
 #pragma unroll
-    for (int q = 0; q < NR; ++q)
-      a[q] = row[q] < m ? __builtin_nontemporal_load(reinterpret_cast<const V*>(cp + row[q])) : zero;
+    for (int q = 0; q < NR; ++q) {
+      if (row[q] < m) a[q] = LoadMatrixChunk<T>(cp + row[q], q < nres);
+      else a[q] = zero;
+    }
   };
   V cur[NR], nxt[NR];
   int64_t step = 0;
@@ -203,24 +208,24 @@ constexpr int WidthFor(int nr) { return nr <= 2 ? 8 : nr <= 4 ? 6 : nr <= 8 ? 5 
 
 template <class T, int NR>
 void LaunchBatch(int grid, int64_t m, int64_t n, const T* A, int64_t lda, const LassoBatchInst<T>* tab, int nk,
-                 const double* glam) {
+                 const double* glam, const FusedResidency& res) {
   if (glam != nullptr)
     hipLaunchKernelGGL((LassoBatchStreamKernel<T, NR, WidthFor(NR), true>), dim3(grid), dim3(kBlock), 0,
-                       Runtime::Get().stream(), m, n, A, lda, tab, nk, *glam);
+                       Runtime::Get().stream(), m, n, A, lda, tab, nk, *glam, res.qfull, res.jcut);
   else
     hipLaunchKernelGGL((LassoBatchStreamKernel<T, NR, WidthFor(NR), false>), dim3(grid), dim3(kBlock), 0,
-                       Runtime::Get().stream(), m, n, A, lda, tab, nk, 0.0);
+                       Runtime::Get().stream(), m, n, A, lda, tab, nk, 0.0, res.qfull, res.jcut);
 }
 
 template <class T>
 void LaunchBatchT(int nr, int grid, int64_t m, int64_t n, const T* A, int64_t lda, const LassoBatchInst<T>* tab,
-                  int nk, const double* glam) {
+                  int nk, const double* glam, const FusedResidency& res) {
   switch (nr) {
-    case 1: LaunchBatch<T, 1>(grid, m, n, A, lda, tab, nk, glam); break;
-    case 2: LaunchBatch<T, 2>(grid, m, n, A, lda, tab, nk, glam); break;
-    case 4: LaunchBatch<T, 4>(grid, m, n, A, lda, tab, nk, glam); break;
-    case 8: LaunchBatch<T, 8>(grid, m, n, A, lda, tab, nk, glam); break;
-    default: LaunchBatch<T, 10>(grid, m, n, A, lda, tab, nk, glam); break;
+    case 1: LaunchBatch<T, 1>(grid, m, n, A, lda, tab, nk, glam, res); break;
+    case 2: LaunchBatch<T, 2>(grid, m, n, A, lda, tab, nk, glam, res); break;
+    case 4: LaunchBatch<T, 4>(grid, m, n, A, lda, tab, nk, glam, res); break;
+    case 8: LaunchBatch<T, 8>(grid, m, n, A, lda, tab, nk, glam, res); break;
+    default: LaunchBatch<T, 10>(grid, m, n, A, lda, tab, nk, glam, res); break;
   }
 }
 
@@ -254,21 +259,23 @@ void LassoBatchUpload(const std::vector<const LassoInstance*>& members, DType dt
 }
 
 void LassoBatchPass(int64_t m, int64_t n, int64_t lda, const DVec& A, const DVec& table, int first, int count,
-                    const double* group_lam) {
+                    const double* group_lam, const FusedResidency& res) {
   const DType dt = A.dt;
   EPS_CHECK(LassoFusedSupported(m, n, A, lda));
+  EPS_CHECK(res.qfull >= 0 && res.jcut >= 0 && res.jcut <= n);
   const int width = LassoBatchWidth(m, n, dt);
   EPS_CHECK_MSG(width > 0 && count >= 1 && count <= width,
                 "batched fused pass: " << count << " instances, width " << width);
   const int grid = LassoFusedGrid(m, n, dt);
   const int nr = ChunksPerThread(m, dt);
   ProfScope prof("batch_fused_pass", m, n);
+  NoteFusedResidency(res.qfull, res.jcut);
   if (dt == F32)
     LaunchBatchT<float>(nr, grid, m, n, A.as<float>(), lda,
-                        reinterpret_cast<const LassoBatchInst<float>*>(table.as<char>()) + first, count, group_lam);
+                        reinterpret_cast<const LassoBatchInst<float>*>(table.as<char>()) + first, count, group_lam, res);
   else
     LaunchBatchT<double>(nr, grid, m, n, A.as<double>(), lda,
-                         reinterpret_cast<const LassoBatchInst<double>*>(table.as<char>()) + first, count, group_lam);
+                         reinterpret_cast<const LassoBatchInst<double>*>(table.as<char>()) + first, count, group_lam, res);
   EPS_HIP(hipGetLastError());
 }
 

@@ -24,6 +24,23 @@ template <> struct Chunk<double> {
   typedef double V __attribute__((ext_vector_type(2)));
 };
 
+// One 16-byte load of the streamed matrix (the single pass and the batched pass).  `resident`:
+// the default policy, so the line stays in the Infinity Cache for the next sweep; otherwise
+// non-temporal, which passes through without displacing what is resident (DESIGN.md 3.7,
+// "Residency").  `resident` must be uniform over the workgroup, and the disassembly must show
+// both an `nt` and a plain global_load_dwordx4 behind scalar control flow.  Written as two loads
+// of one pointer, the compiler merges them into a single plain load and the hint is lost (as it
+// did once with the guarded load: kernels_fused.hip, `const V zero`).  So the resident load reads
+// through a pointer to the constant address space: the matrix is read-only for the whole launch,
+// a per-lane address gives the same global_load instruction, and loads of two pointer types are
+// not merged.
+template <class T> __device__ inline typename Chunk<T>::V LoadMatrixChunk(const T* p, bool resident) {
+  typedef typename Chunk<T>::V V;
+  typedef const V __attribute__((address_space(4))) * ConstV;
+  if (resident) return *(ConstV)(p);
+  return __builtin_nontemporal_load(reinterpret_cast<const V*>(p));
+}
+
 // ---- the same pass in either precision (the f64 form serves the fp64 mode: the reference's own
 // arithmetic type, linear/linear_map.h:35) ---------------------------------------------------------
 template <class T> struct FusedScalarsT {

@@ -509,6 +509,43 @@ __global__ __launch_bounds__(256) void StreamReadKernel(const f32x4_probe* __res
   if (threadIdx.x == 0) out[blockIdx.x] = red[0];
 }
 
+// The residency probe ("Residency"): the buffer as columns of kProbeColumn
+// 16-byte vectors (the headline matrix's 10^4 f32 rows), a column per workgroup step, ten loads
+// per thread in flight.  The first `rv` vectors of every column are read with the default policy
+// and are meant to stay in the Infinity Cache from launch to launch, the rest non-temporally.
+// (The plain load goes through a constant-address-space pointer: two loads of one pointer are
+// merged into a single plain one, kernels_fused_chain.h LoadMatrixChunk.)
+constexpr int kProbeColumn = 2500;
+
+__global__ __launch_bounds__(256) void StreamResidentKernel(const f32x4_probe* __restrict__ p, int64_t ncols,
+                                                            int rv, float* __restrict__ out) {
+  typedef const f32x4_probe __attribute__((address_space(4))) * ConstV;
+  constexpr int kPer = (kProbeColumn + 255) / 256;
+  const int tid = threadIdx.x;
+  float acc = 0.f;
+  for (int64_t c = blockIdx.x; c < ncols; c += gridDim.x) {
+    const f32x4_probe* cp = p + c * kProbeColumn;
+    f32x4_probe v[kPer];
+#pragma unroll
+    for (int q = 0; q < kPer; ++q) {
+      const int i = q * 256 + tid;
+      if (i >= kProbeColumn) v[q] = 0.f;
+      else if (i < rv) v[q] = *(ConstV)(cp + i);
+      else v[q] = __builtin_nontemporal_load(cp + i);
+    }
+#pragma unroll
+    for (int q = 0; q < kPer; ++q) acc += (v[q].x + v[q].y) + (v[q].z + v[q].w);
+  }
+  __shared__ float red[256];
+  red[tid] = acc;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off) red[tid] += red[tid + off];
+    __syncthreads();
+  }
+  if (tid == 0) out[blockIdx.x] = red[0];
+}
+
 __global__ __launch_bounds__(256) void StreamCopyKernel(const f32x4_probe* __restrict__ src,
                                                         f32x4_probe* __restrict__ dst, int64_t n4) {
   const int64_t stride = static_cast<int64_t>(gridDim.x) * 256;
@@ -527,6 +564,16 @@ void StreamProbe(int mode, const void* src, void* dst, int64_t bytes, float* scr
     hipLaunchKernelGGL(StreamReadKernel<false>, dim3(grid), dim3(256), 0, s, p, n4, scratch);
   else
     hipLaunchKernelGGL(StreamCopyKernel, dim3(grid), dim3(256), 0, s, p, static_cast<f32x4_probe*>(dst), n4);
+}
+
+void StreamResidentProbe(const void* src, int64_t bytes, int64_t resident_per_column, float* scratch, int grid) {
+  const int64_t ncols = bytes / (16 * kProbeColumn);
+  int64_t rv = resident_per_column / 16;
+  if (rv < 0) rv = 0;
+  if (rv > kProbeColumn) rv = kProbeColumn;
+  if (ncols < 1) return;
+  hipLaunchKernelGGL(StreamResidentKernel, dim3(grid), dim3(256), 0, Runtime::Get().stream(),
+                     static_cast<const f32x4_probe*>(src), ncols, static_cast<int>(rv), scratch);
 }
 
 }  // namespace k

@@ -101,7 +101,16 @@ const char* eps_version(void);
  * the cached inverse.  Taken for fat C with 256 to 20480 rows (f64: 10240), rows a multiple of
  * 4 (f64: 2), multi-block driver, one GPU, every operand in the compute type; anything else, "0"
  * and "fused" = "0" mean the generic operator path.  Read at every Init.  Any other value is an
- * error that names it (env EPSILON_HIP_FUSED_ZERO). */
+ * error that names it (env EPSILON_HIP_FUSED_ZERO).
+ * "fused_resident" = "auto" (default) | "<KiB>"  bytes of the data matrix that the fused pass
+ * (single and batched; one GPU) loads with the default cache policy, so that they stay in the
+ * 256 MiB Infinity Cache from sweep to sweep, while the rest is streamed with non-temporal loads.
+ * "0" streams everything.  "auto": on the single pass of the multi-block driver, what the cache
+ * holds beside the sweep's own vectors (and beside the cached inverse where the sweep applies
+ * one); on the batched pass, the ZERO-term route and the two-block driver, which have not been
+ * timed with a resident share, nothing - a number of KiB applies there too.  The iterates do not
+ * depend on it, bit for bit.  Read at every Init.  Any other value is an error that names it
+ * (env EPSILON_HIP_FUSED_RESIDENT_KB). */
 int eps_set_option(const char* key, const char* value);
 /* Number of visible HIP devices (0 if none); never fails. */
 int eps_device_count(void);
@@ -290,6 +299,23 @@ int eps_bench_gemv(int trans, int64_t rows, int64_t cols, int iters, double* ms_
  * a fraction of these beside the 8 TB/s vendor peak. */
 int eps_bench_stream(const void* device_ptr, size_t bytes, int mode, int grid, int iters,
                      double* ms_avg);
+/* Infinity Cache residency probe: reads `bytes` (device_ptr or NULL as above) as columns of 40000
+ * bytes, the first resident_bytes / columns bytes of every column (rounded down to 16) with the
+ * default cache policy, the rest with non-temporal loads.  Two untimed launches fill the cache;
+ * the average is over the `iters` launches after them.  Measurement only. */
+int eps_bench_stream_resident(const void* device_ptr, size_t bytes, size_t resident_bytes, int grid,
+                              int iters, double* ms_avg);
+/* The fused pass's residency rule for an m x n matrix (f64 != 0: fp64) under a budget in bytes
+ * (option "fused_resident"): row chunk q of column j - a chunk is the rows one load instruction
+ * of the workgroup covers - is loaded to stay in the Infinity Cache iff q < qfull, or q == qfull
+ * and j < jcut.  resident_bytes is the total, the largest of this form within the budget.  A pure
+ * host function: no device is needed. */
+int eps_fused_residency(int64_t m, int64_t n, int f64, int64_t budget_bytes, int* qfull, int64_t* jcut,
+                        int64_t* resident_bytes);
+/* Test entry: the (qfull, jcut) that the most recent launch of the fused pass in this process,
+ * single or batched, received (0, 0 before any).  No iterate depends on the budget, so this is
+ * how a test sees that the option reached the kernel. */
+int eps_fused_residency_last(int* qfull, int64_t* jcut);
 /* Same for C = op(A) op(B) (M x N x K); lower_only = SYRK-style. */
 int eps_bench_gemm(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, int lower_only,
                    int iters, double* ms_avg);
