@@ -18,13 +18,36 @@ Shapes: bp = basis pursuit 1000 x 3000 and hinge = hinge + l1 1500 x 5000, the r
 (bp64 / hinge64 the same in f64); hinge_big = hinge + l1 4096 x 16384; deadzone = deadzone + l1
 1500 x 5000; logreg = logistic loss + l1 1500 x 5000 (logreg64 in f64), logreg_big = the same at
 4096 x 16384; floor = hinge + l1 256 x 601, the smallest row count the route takes (floor64 in f64).
+
+--path K1,K2,...: instead, a K-member lambda path (basis pursuit: K right-hand sides on one matrix)
+through _solve.solve_batch, --steps sweeps with abs_tol = rel_tol = 0, per shape and K.  The members
+share the data matrix, so they run as one batched group.  One JSON line per
+(shape, K):
+  ms_per_sweep      median over --runs calls of the batch's loop time / steps (all K members advance
+                    one sweep); spread = (max - min) / median
+  tags              launches per sweep of the batched kernels in a profiled call ({} where the
+                    members were solved one by one)
+--lib PATH loads another build of the library (say the parent commit's, built in a second checkout)
+in place of this tree's: the same inputs through its solve_batch.
+--against PATH runs this tree's library and the one at PATH in child processes of one job, the two
+alternated --rounds times (each child: one warm-up call and --runs timed calls per cell), and prints
+per (shape, K) the median over the rounds and the spread of either side, the speedup, and whether
+the batched side wins by more than the two spreads combined (ZERO paragraph).
+
+    python bench_zero.py --path 2,4,8 [--shapes hinge,logreg,bp,hinge_big,floor] [--steps 100]
+                         [--runs 3] [--lib PATH | --against PATH [--rounds 3]]
 """
 
 import argparse
 import json
+import os
 import statistics
+import subprocess
+import sys
 
-from epsilon_amd import _solve, problems, wire
+import numpy as np
+
+from epsilon_amd import _solve, ir, problems, wire
 
 SHAPES = {
     "bp": ("basis_pursuit", 1000, 3000, "f32"),
@@ -47,7 +70,105 @@ def parse():
     p.add_argument("--shapes", default="bp,bp64,hinge,hinge64,hinge_big,deadzone,logreg,logreg64")
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=20)
+    p.add_argument("--path", default="", help="member counts of a batched lambda path, e.g. 2,4,8")
+    p.add_argument("--runs", type=int, default=3)
+    p.add_argument("--rounds", type=int, default=3)
+    p.add_argument("--lib", default="")
+    p.add_argument("--against", default="")
     return p.parse_args()
+
+
+PATH_FRACS = (0.5, 0.35, 0.25, 0.18, 0.13, 0.09, 0.065, 0.045)  # of the generators' lambda scale
+
+
+def path_members(kind, m, n, K):
+    """K members on one data matrix (seed 0): lambda falls along PATH_FRACS; basis pursuit has no
+    lambda and takes K right-hand sides"""
+    if kind == "basis_pursuit":
+        A = problems.basis_pursuit(m, n)[1]["A"]
+        rng = np.random.RandomState(1)
+        return [problems.basis_pursuit(m, n, b=A.dot(rng.randn(n) * (rng.rand(n) < 0.2)))[0] for _ in range(K)]
+    if kind == "deadzone_l1":
+        return [problems.deadzone_l1(m, n, frac=f)[0] for f in PATH_FRACS[:K]]
+    C = getattr(problems, kind)(m, n)[1]["C"]
+    if kind == "hinge_l1":  # problems.hinge_l1's terms on its C, without drawing the matrix again per member
+        scale = np.abs(C.sum(axis=0)).max()
+
+        def terms(lam):
+            return lambda x, z: [
+                ir.prox(wire.ProxFunction.SUM_HINGE,
+                        ir.add(ir.linear_map(ir.scalar(-1, m), z), ir.scalar_constant(1.0, (m, 1)))),
+                ir.prox(wire.ProxFunction.NORM_1, x, alpha=lam)]
+        return [problems._graph_form(terms(f * scale), C, None) for f in PATH_FRACS[:K]]
+    scale = np.abs(C.T.dot(np.full(m, 0.5))).max()
+    return [getattr(problems, kind)(m, n, lam=f * scale)[0] for f in PATH_FRACS[:K]]
+
+
+def path_lines(a):
+    """the --path cells of this process's library"""
+    ks = sorted(int(k) for k in a.path.split(","))
+    assert 2 <= ks[0] and ks[-1] <= len(PATH_FRACS), "--path takes member counts from 2 to %d" % len(PATH_FRACS)
+    sb = wire.SolverParams(max_iterations=a.steps, abs_tol=0.0, rel_tol=0.0).SerializeToString()
+    short = wire.SolverParams(max_iterations=10, abs_tol=0.0, rel_tol=0.0).SerializeToString()
+    for name in a.shapes.split(","):
+        kind, m, n, dtype = SHAPES[name]
+        probs = path_members(kind, m, n, ks[-1])
+        data = {}
+        for p in probs:
+            data.update(p.expression_data())
+        pbs = [p.SerializeToString() for p in probs]
+        _solve.set_option("dtype", dtype)
+        try:
+            for K in ks:
+                _solve.profile_reset()
+                _solve.profile_enable(True)
+                try:
+                    _solve.solve_batch(pbs[:K], None, short, data)  # warm-up, and the launch counts
+                    tags = {}
+                    for t, (c, _) in _solve.profile_dump().items():
+                        if t.startswith("batch_"):
+                            tags[t.split(":")[0]] = tags.get(t.split(":")[0], 0) + c / 10.0
+                finally:
+                    _solve.profile_enable(False)
+                times = []
+                for _ in range(a.runs):
+                    res = _solve.solve_batch(pbs[:K], None, sb, data)
+                    sts = [wire.SolverStatus.FromString(st) for st, _ in res]
+                    assert all(s.num_iterations == a.steps for s in sts)
+                    # a group's members all carry the group's loop time; members solved one by one
+                    # carry their own
+                    loops = [s.timing.total_time - s.timing.init_time for s in sts]
+                    times.append((loops[0] if tags else sum(loops)) / a.steps)
+                med = statistics.median(times)
+                yield dict(bench="zero_path", shape=name, problem=kind, m=m, n=n, dtype=dtype, gpus=1, K=K,
+                           steps=a.steps, runs=a.runs, ms_per_sweep=1e3 * med,
+                           spread=(max(times) - min(times)) / med, tags=tags)
+        finally:
+            _solve.set_option("dtype", "f32")
+
+
+def path_against(a):
+    """this tree's library and --against, alternated in child processes"""
+    cells = {}
+    for r in range(a.rounds):
+        for side, lib in (("this", ""), ("base", a.against)):
+            print("round %d of %d, %s" % (r + 1, a.rounds, side), file=sys.stderr, flush=True)
+            cmd = [sys.executable, os.path.abspath(__file__), "--path", a.path, "--shapes", a.shapes, "--steps",
+                   str(a.steps), "--runs", str(a.runs)] + (["--lib", lib] if lib else [])
+            out = subprocess.run(cmd, check=True, stdout=subprocess.PIPE, text=True, timeout=900).stdout
+            for line in out.splitlines():
+                d = json.loads(line)
+                cells.setdefault((d["shape"], d["K"]), {"this": [], "base": [], "meta": d})[side].append(d["ms_per_sweep"])
+    for (shape, K), c in cells.items():
+        med = {s: statistics.median(c[s]) for s in ("this", "base")}
+        spread = {s: (max(c[s]) - min(c[s])) / med[s] for s in ("this", "base")}
+        d = c["meta"]
+        print(json.dumps(dict(
+            bench="zero_path_vs_base", shape=shape, problem=d["problem"], m=d["m"], n=d["n"], dtype=d["dtype"],
+            gpus=1, K=K, steps=a.steps, rounds=a.rounds, runs=a.runs, ms_per_sweep=med, spread=spread,
+            speedup=med["base"] / med["this"],
+            wins=med["base"] - med["this"] > spread["this"] * med["this"] + spread["base"] * med["base"])),
+            flush=True)
 
 
 def names_of_one_sweep(s):
@@ -62,6 +183,14 @@ def names_of_one_sweep(s):
 
 def main():
     a = parse()
+    if a.lib:
+        _solve.LIB_PATH = os.path.abspath(a.lib)  # (before the first call loads the library)
+    if a.path:
+        if a.against:
+            return path_against(a)
+        for line in path_lines(a):
+            print(json.dumps(line), flush=True)
+        return
     for name in a.shapes.split(","):
         kind, m, n, dtype = SHAPES[name]
         prob = getattr(problems, kind)(m, n)[0]

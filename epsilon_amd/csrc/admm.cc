@@ -81,12 +81,15 @@ Solver::Solver(pb::Problem problem, std::shared_ptr<DataMap> data, pb::SolverPar
 Solver::~Solver() {}
 
 FusedRoute* Solver::batch_route() const { return initialized_ && !finished_ && iter_ == 0 ? route_.get() : nullptr; }
+// (a route without a check of its own - the ZERO-term route - launches nothing ahead: its member
+// runs the driver's generic check, waited for, when it is asked for the outcome)
 void Solver::BatchLaunchCheck(int iter) {
   iter_ = iter;
-  route_->LaunchNorms();
+  if (route_->HasCheck()) route_->LaunchNorms();
 }
 bool Solver::BatchFinishCheck() {
-  FinishRouteCheck();
+  if (route_->HasCheck()) FinishRouteCheck();
+  else ComputeResiduals();
   finished_ = status_.state == pb::SolverStatus::OPTIMAL;
   return finished_;
 }

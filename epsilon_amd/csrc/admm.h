@@ -54,8 +54,9 @@ class Solver {
   void set_shared_cache(OpCache* c) { shared_cache_ = c; }
   // What a group of batched solves (RunFusedBatches) needs of a member: the route of a fresh
   // solve (null: none, or already run), the residual check at sweep `iter` in its two halves
-  // (scalars into the next slots; after the fetch the status - true: the member stops here), the
-  // end at max_iterations, and the group's loop time.
+  // (scalars into the next slots; after the fetch the status - true: the member stops here; a route
+  // without a check of its own launches nothing and runs the driver's generic check, waited for,
+  // in the second half), the end at max_iterations, and the group's loop time.
   FusedRoute* batch_route() const;
   void BatchLaunchCheck(int iter);
   bool BatchFinishCheck();
@@ -105,10 +106,11 @@ std::unique_ptr<Solver> CreateSolver(pb::Problem problem, std::shared_ptr<DataMa
                                      pb::SolverParams params);
 
 // Batched solves (eps_solve_batch, fused_route.cc).  Of the initialised, not yet run `solvers`, those
-// whose sweep is the lasso route's fused pass in a form the batched pass mirrors
-// (k::LassoBatchWidth) are grouped by shared data matrix and cached inverse; every group of two
-// or more runs its sweeps together (kernels_fused_batch.hip: one pass over A for up to KB
-// instances, one reduction and one inverse apply for all), with each instance's residual check
+// whose sweep is the lasso route's or the ZERO-term route's fused pass in a form the batched pass
+// mirrors (k::LassoBatchWidth) are grouped by shared data matrix and cached inverse; every group of
+// two or more runs its sweeps together (kernels_fused_batch.hip: one pass over A for up to KB
+// instances, one reduction - ZERO-term members: one row launch - and one inverse apply for all),
+// with each instance's residual check
 // every epoch_iterations sweeps and each frozen at the check that stops it.  Every solver run
 // here ends with exactly the status and iterates its own Run(-1) would give.  Returns, per
 // solver, whether it was run; the others are untouched.

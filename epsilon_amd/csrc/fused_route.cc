@@ -173,6 +173,9 @@ MatrixRoute FusedMatrixMode() {
 // (ZeroRoute).  Below this many rows of the data matrix the solve keeps the
 // generic operator path (a constant: no crossover was measured).
 constexpr int64_t kZeroFusedMinRows = 256;
+// First word of a ZERO group's batch key (the lasso's begins with a pointer): the two kinds of
+// members never share a group.
+constexpr uint64_t kZeroGroupTag = 2;
 
 // EPSILON_HIP_FUSED_ZERO (eps_set_option "fused_zero"), read at every Init.
 bool FusedZeroAuto() {
@@ -734,6 +737,7 @@ struct ZeroRoute final : FusedRoute {
   InverseApply inv;
   k::LassoFusedArgs pass;
   k::ZeroRowsArgs rows;
+  k::FusedResidency res;  // the matrix's share that stays in the Infinity Cache (none under "auto")
 
   bool Enable(const MultiBlockParts& a) {
     if (FusedDisabled() || ShardSpec::Get().active() || !a.b.data().empty()) return false;
@@ -823,11 +827,12 @@ struct ZeroRoute final : FusedRoute {
       pass.A = L.data();
       pass.chain = 2;
       pass.e0 = sn[6].v;
+      pass.inst.e0 = sn[6].v;  // (a batched member carries it in its record)
       // beside the matrix the sweep touches the partials (the rows kernel re-reads them), the seven
       // state vectors of either side, p, w, and the inverse
       const int64_t sz = dt == F32 ? 4 : 8;
-      const k::FusedResidency res =
-          ResidentShare(m, n, dt, (static_cast<int64_t>(grid) * m + 7 * (n + m) + 2 * m + m * m) * sz, /*auto_on=*/false);
+      res = ResidentShare(m, n, dt, (static_cast<int64_t>(grid) * m + 7 * (n + m) + 2 * m + m * m) * sz,
+                          /*auto_on=*/false);
       pass.qfull = res.qfull;
       pass.jcut = res.jcut;
       k::LassoInstance& s = pass.inst;
@@ -902,6 +907,31 @@ struct ZeroRoute final : FusedRoute {
     else
       k::ReducePartials(m, grid, tpart, pass.inst.pkappa, 0.0, p, zp.rhs_arg.n != 0 ? &zp.rhs_arg : nullptr);
     inv.Apply();
+  }
+
+  // ---- batched solves (RunFusedBatches) ---------------------------------------------------------
+  // The key of the group a fresh solve on this route can join: the same data matrix, the same
+  // inverse (and packed copy), the same e and z block, the same form of the row kernel and the
+  // same schedule.  Everything else - the zones' parameters and vectors, the offset g, the rhs -
+  // is per member, so a hinge and a deadzone member on one matrix share a group.  false: the
+  // single pass takes a form the batched one does not mirror (512-thread workgroups).
+  bool BatchKey(const pb::SolverParams& params, std::vector<uint64_t>* key) const {
+    const DenseMatrixImpl& L = *zp.L_arg_x;
+    const DenseMatrixImpl& D = *zp.Dinv_arg;
+    const DType dt = w.dt;
+    if (k::LassoBatchWidth(m, n, dt, 2) == 0) return false;
+    auto bits = [](double v) {
+      uint64_t b;
+      std::memcpy(&b, &v, 8);
+      return b;
+    };
+    *key = {kZeroGroupTag, reinterpret_cast<uintptr_t>(L.data().data()), static_cast<uint64_t>(L.rows()),
+            static_cast<uint64_t>(m), static_cast<uint64_t>(n), static_cast<uint64_t>(dt),
+            bits(L.scale()), reinterpret_cast<uintptr_t>(D.data().data()), bits(D.scale()),
+            reinterpret_cast<uintptr_t>(inv.packed.data()), inv.work.n > 0 ? 1u : 0u, bits(zp.e),
+            has_z ? 1u : 0u, rows.smooth ? 1u : 0u, static_cast<uint64_t>(params.max_iterations),
+            static_cast<uint64_t>(params.epoch_iterations)};
+    return true;
   }
 };
 
@@ -1033,19 +1063,25 @@ std::unique_ptr<FusedRoute> RecogniseTwoBlockRoute(const TwoBlockParts& parts) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Batched solves: one group of instances on the lasso route sharing A and the cached inverse
+// Batched solves: groups of instances on the lasso route or on the ZERO-term route that share the
+// data matrix and the cached inverse
 // ---------------------------------------------------------------------------------------------------
 namespace {
 
+// A member of a group: its solver and its route, a LassoRoute or a ZeroRoute - every member of a
+// group has the lead's kind (the keys differ), and the group's runner knows which.
 struct BatchMember {
   Solver* solver;
-  LassoRoute* route;
+  FusedRoute* route;
+  const LassoRoute& lasso() const { return *static_cast<const LassoRoute*>(route); }
+  const ZeroRoute& zero() const { return *static_cast<const ZeroRoute*>(route); }
 };
 using Group = std::vector<BatchMember>;
 
 // Run()'s iteration schedule without the pipelining, for a group of batched members: sweeps up to
 // the next multiple of the epoch, then one residual check of every active member with ONE fetch of
-// their scalars.  A member that stops is frozen: it leaves `active`, and `stopped(gone)` is told
+// their scalars (a route without a check of its own: the driver's generic check, waited for, member
+// by member).  A member that stops is frozen: it leaves `active`, and `stopped(gone)` is told
 // which ones left (only when some did).  Members still active at the end get Run()'s
 // max-iterations status.  Ends with the group's loop time since `t0`, once the stream has drained.
 template <class Sweep, class Stopped>
@@ -1080,7 +1116,7 @@ void RunGroupSchedule(const Group& g, double t0, std::vector<int>* active, Sweep
 
 void RunFusedGroup(const Group& g) {
   const double t0 = Now();
-  const LassoRoute& lead = *g[0].route;
+  const LassoRoute& lead = g[0].lasso();
   const DType dt = lead.dt;
   SetCurrentDType(dt);
   const int64_t m = lead.m, n = lead.n;
@@ -1088,7 +1124,7 @@ void RunFusedGroup(const Group& g) {
   const DVec& P = lead.inv.packed;
   bool rhs_aligned = true;
   for (const BatchMember& b : g) {
-    const DVec& rhs = b.route->pass.inst.rhs;
+    const DVec& rhs = b.lasso().pass.inst.rhs;
     if (rhs.n > 0) rhs_aligned = rhs_aligned && reinterpret_cast<uintptr_t>(rhs.data()) % 16 == 0;
   }
   const int K = static_cast<int>(g.size());
@@ -1100,7 +1136,7 @@ void RunFusedGroup(const Group& g) {
   DVec table;
   auto upload = [&] {
     std::vector<const k::LassoInstance*> v;
-    for (int i : active) v.push_back(&g[i].route->pass.inst);
+    for (int i : active) v.push_back(&g[i].lasso().pass.inst);
     k::LassoBatchUpload(v, dt, &table);
   };
   upload();
@@ -1114,10 +1150,66 @@ void RunFusedGroup(const Group& g) {
     } else if (P.n > 0) {
       k::SymvPackedBatch(m, lead.inv.D->scale(), P, table, na, symv_work);
     } else {
-      for (int i : active) g[i].route->inv.Apply();  // D.Apply / Symv: per instance
+      for (int i : active) g[i].lasso().inv.Apply();  // D.Apply / Symv: per instance
     }
   };
   // the stopped ones are frozen: drop their descriptors
+  RunGroupSchedule(g, t0, &active, sweep, [&](const std::vector<int>&) {
+    if (!active.empty()) upload();
+  });
+}
+
+// A group of ZERO-term members: per sweep one batched pass with the ZERO column
+// chain per `width` active members, ONE row launch for all of them (basis pursuit, which has no z
+// block: one batched reduction of the partials with the rhs folded in) and one batched apply of the
+// packed inverse (below m = 1024: each member's own apply).  Each launch does per member what the
+// member's own sweep does, so its iterates are the single solve's bit for bit; the residual check
+// is the driver's generic one, at the sweeps of the member's own Run().
+void RunZeroGroup(const Group& g) {
+  const double t0 = Now();
+  const ZeroRoute& lead = g[0].zero();
+  const DType dt = lead.w.dt;
+  SetCurrentDType(dt);
+  const int64_t m = lead.m, n = lead.n;
+  const int width = k::LassoBatchWidth(m, n, dt, 2);
+  const DVec& P = lead.inv.packed;
+  bool rhs_aligned = true;
+  for (const BatchMember& b : g) {
+    const DVec& rhs = b.zero().pass.inst.rhs;
+    if (rhs.n > 0) rhs_aligned = rhs_aligned && reinterpret_cast<uintptr_t>(rhs.data()) % 16 == 0;
+  }
+  const int K = static_cast<int>(g.size());
+  DVec symv_work = P.n > 0 ? DVec::Empty(K * k::SymvWorkspace(m), dt) : DVec();
+  const k::FusedResidency res = lead.res;  // the lead's share (none under "auto": DESIGN.md 7)
+
+  std::vector<int> active(K);
+  for (int i = 0; i < K; ++i) active[i] = i;
+  DVec table, row_table;
+  auto upload = [&] {
+    std::vector<const k::LassoInstance*> v;
+    std::vector<const k::ZeroRowsArgs*> r;
+    for (int i : active) {
+      EPS_CHECK(g[i].zero().pass.inst.e0.n == n);  // the ZERO chain stores through it
+      v.push_back(&g[i].zero().pass.inst);
+      r.push_back(&g[i].zero().rows);
+    }
+    k::LassoBatchUpload(v, dt, &table);
+    if (lead.has_z) k::ZeroRowsBatchUpload(r, &row_table);
+  };
+  upload();
+  auto sweep = [&] {
+    const int na = static_cast<int>(active.size());
+    for (int first = 0; first < na; first += width)
+      k::LassoBatchPass(m, n, lead.pass.lda, lead.pass.A, table, first, std::min(width, na - first), nullptr, res,
+                        /*chain=*/2);
+    if (lead.has_z) k::ZeroFusedRowsBatch(m, lead.grid, lead.rows.smooth, dt, row_table, na);
+    else k::ReducePartialsBatch(m, lead.grid, table, na, dt, rhs_aligned);
+    if (P.n > 0) {
+      k::SymvPackedBatch(m, lead.inv.D->scale(), P, table, na, symv_work);
+    } else {
+      for (int i : active) g[i].zero().inv.Apply();
+    }
+  };
   RunGroupSchedule(g, t0, &active, sweep, [&](const std::vector<int>&) {
     if (!active.empty()) upload();
   });
@@ -1147,7 +1239,7 @@ int BatchWideMin() {  // EPSILON_HIP_BATCH_WIDE_MIN: tuning knob (the crossover 
 // summation order depends on who else is still iterating.  Not bit-identical to the single solve.
 void RunWideGroup(const Group& g) {
   const double t0 = Now();
-  const LassoRoute& lead = *g[0].route;
+  const LassoRoute& lead = g[0].lasso();
   SetCurrentDType(F32);
   const int64_t m = lead.m, n = lead.n;
   const bool whiten = lead.whiten;
@@ -1162,7 +1254,7 @@ void RunWideGroup(const Group& g) {
   DVec Wall = DVec::Zeros(npanels * panel_len, F32);
   DVec Pall = whiten ? DVec() : DVec::Zeros(npanels * panel_len, F32);
   for (int i = 0; i < K; ++i) {
-    mem.push_back(g[i].route->pass.inst);
+    mem.push_back(g[i].lasso().pass.inst);
     for (const DVec* v : {&mem[i].u, &mem[i].x0, &mem[i].x1, &mem[i].y0, &mem[i].y1, &mem[i].y1prev})
       EPS_CHECK_MSG(reinterpret_cast<uintptr_t>(v->data()) % 16 == 0, "wide batch: unaligned state vector");
     DVec slot = Wall.Slice(static_cast<int64_t>(i) * m, m);
@@ -1195,7 +1287,7 @@ void RunWideGroup(const Group& g) {
     for (int i : gone) live[i / PW] &= ~(uint64_t(1) << (i % PW));
   });
   // every member's own w holds what its next sweep would read
-  for (int i = 0; i < K; ++i) k::Copy(g[i].route->pass.inst.w, mem[i].w);
+  for (int i = 0; i < K; ++i) k::Copy(g[i].lasso().pass.inst.w, mem[i].w);
 }
 
 }  // namespace
@@ -1204,12 +1296,18 @@ std::vector<bool> RunFusedBatches(const std::vector<Solver*>& solvers) {
   std::vector<bool> ran(solvers.size(), false);
   const bool wide = BatchWideEnabled();
   std::map<std::vector<uint64_t>, std::vector<size_t>> groups;
-  std::vector<LassoRoute*> routes(solvers.size(), nullptr);
+  std::vector<FusedRoute*> routes(solvers.size(), nullptr);
   std::vector<std::vector<uint64_t>> order;  // groups in order of their first instance
   for (size_t i = 0; i < solvers.size(); ++i) {
-    routes[i] = dynamic_cast<LassoRoute*>(solvers[i]->batch_route());
+    routes[i] = solvers[i]->batch_route();
     std::vector<uint64_t> key;
-    if (routes[i] == nullptr || !routes[i]->BatchKey(solvers[i]->params(), &key)) continue;
+    if (auto* lasso = dynamic_cast<LassoRoute*>(routes[i])) {
+      if (!lasso->BatchKey(solvers[i]->params(), &key)) continue;
+    } else if (auto* zero = dynamic_cast<ZeroRoute*>(routes[i])) {
+      if (!zero->BatchKey(solvers[i]->params(), &key)) continue;
+    } else {
+      continue;
+    }
     auto& members = groups[key];
     if (members.empty()) order.push_back(key);
     members.push_back(i);
@@ -1219,12 +1317,16 @@ std::vector<bool> RunFusedBatches(const std::vector<Solver*>& solvers) {
     if (idx.size() < 2) continue;  // alone: the single path is the same solve, with pipelined checks
     Group g;
     for (size_t i : idx) g.push_back({solvers[i], routes[i]});
-    const LassoRoute& lead = *g[0].route;
-    if (wide && static_cast<int>(g.size()) >= BatchWideMin() && lead.dt == F32 &&
-        k::LassoWideSupported(lead.m, lead.n, lead.pass.A, lead.pass.lda))
-      RunWideGroup(g);
-    else
-      RunFusedGroup(g);
+    if (key[0] == kZeroGroupTag) {
+      RunZeroGroup(g);
+    } else {
+      const LassoRoute& lead = g[0].lasso();
+      if (wide && static_cast<int>(g.size()) >= BatchWideMin() && lead.dt == F32 &&
+          k::LassoWideSupported(lead.m, lead.n, lead.pass.A, lead.pass.lda))
+        RunWideGroup(g);
+      else
+        RunFusedGroup(g);
+    }
     for (size_t i : idx) ran[i] = true;
   }
   return ran;

@@ -67,6 +67,7 @@ struct LassoInstance {
   DVec u, x0, x1, y0, y1, y1prev;   // n each, updated in place
   DVec alpha_vec, beta_vec;         // optional per-column alpha / beta of the scaled zone (n entries)
   DVec p, rhs;   // m: the reduced partials (+ rhs), input of the inverse apply; its constant part
+  DVec e0;       // chain 2 alone (LassoFusedArgs::e0, which a batched member carries here): n
   double kappa = 0;                 // x0 = v0 + kappa * (A^T w)
   double Bs = 0, Cs = 0, a1 = 0;    // prox-1 pre / post scaling, y1 = a1 * x1
   double lam = 0, alpha = 1, beta = 1, M = 0;
@@ -119,6 +120,13 @@ struct ZeroRowsArgs {
 };
 void ZeroFusedRows(const ZeroRowsArgs& args);
 void ZeroSmoothHead(const ZeroRowsArgs& args);  // profile tag "zero_fused_head"
+// The row side of `count` members of a batch in ONE launch, profile tag "batch_zero_rows": member b
+// (grid row b) runs ZeroFusedRows' own workgroups on its own record, so its result is that of its
+// own launch bit for bit.  The members share m, nparts, the dtype and the form (zone or smooth).
+// ZeroRowsBatchUpload writes their records in order into `table` (device; grown as needed): as with
+// LassoBatchUpload, a member that stops is dropped by uploading the shorter list.
+void ZeroRowsBatchUpload(const std::vector<const ZeroRowsArgs*>& members, DVec* table);
+void ZeroFusedRowsBatch(int64_t m, int nparts, bool smooth, DType dt, const DVec& table, int count);
 bool LassoFusedSupported(int64_t m, int64_t n, const DVec& A, int64_t lda);
 int LassoFusedGrid(int64_t m, int64_t n, DType dt = F32);
 int LassoFusedBlock(int64_t m, int64_t n, DType dt);  // threads per workgroup of the pass
@@ -161,11 +169,13 @@ template <class T> struct LassoBatchInst {
   const T* rhs;      // m: constant part of the rhs (nullptr: none)
   T kappa, Bs, Cs, a1, lam, alpha, beta, M;
   T pkappa;          // scale of the summed partials in p (kappa, but for the whitened route)
+  T* e0;             // n: the ZERO chain's second "previous y" (nullptr on the lasso chain)
 };
 // Instances one launch of the batched pass carries for (m, dtype) - set by the register budget
 // of its instantiation - or 0 where the single pass would take a form the batched one does not
-// mirror (512-thread workgroups): such instances are solved one by one.
-int LassoBatchWidth(int64_t m, int64_t n, DType dt);
+// mirror (512-thread workgroups): such instances are solved one by one.  `chain`: 0 the lasso
+// chain, 2 the ZERO-term column chain (LassoFusedArgs::chain), which has widths of its own.
+int LassoBatchWidth(int64_t m, int64_t n, DType dt, int chain = 0);
 // The descriptors of `members` in order into `table` (device; grown as needed): the active set
 // of a batch is this array, so an instance that stops is dropped by uploading the shorter list.
 void LassoBatchUpload(const std::vector<const LassoInstance*>& members, DType dt, DVec* table);
@@ -175,8 +185,11 @@ void LassoBatchUpload(const std::vector<const LassoInstance*>& members, DType dt
 // threshold step is the group shrinkage of its rows with this weight (NORM_2 along axis 1)
 // instead of each instance's scaled zone.
 // `res`: the matrix's resident share, as in LassoFusedArgs.
+// `chain` = 2: the column side of ZERO-term members (every record carries e0; no group_lam; profile
+// tag "batch_zero_pass", count <= LassoBatchWidth(m, n, dt, 2)); 0: the lasso chain ("batch_fused_pass").
 void LassoBatchPass(int64_t m, int64_t n, int64_t lda, const DVec& A, const DVec& table, int first,
-                    int count, const double* group_lam = nullptr, const FusedResidency& res = FusedResidency());
+                    int count, const double* group_lam = nullptr, const FusedResidency& res = FusedResidency(),
+                    int chain = 0);
 // p = pkappa * sum(tpart) (+ rhs) of `count` instances in one launch, each in the summation order
 // of ReducePartials(m, nparts, tpart, pkappa, 0, p, rhs).  `rhs_aligned`: every rhs present is
 // 16-byte aligned (picks the same kernel form as the single call).

@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
+#include <vector>
 
 #include "kernels.h"
 #include "kernels_fused_chain.h"
@@ -224,17 +225,31 @@ void LaunchFusedT(const LassoFusedArgs& a, int grid, int block) {
 // head is a function of the stored boundary state alone, so carrying it changes no bit.
 constexpr int kZeroLanes = 16, kZeroRows = kBlock / kZeroLanes, kZeroSmoothRows = 64;
 
+// One member's row side as the kernels read it (compute type T): the single launch takes it as
+// its argument, the batched launch reads row blockIdx.y of a device table of them.
+template <class T> struct ZeroRowsInst {
+  const T* tpart;
+  const T* w;
+  const T* rhs;  // nullptr: none
+  const T* g;    // nullptr: none
+  T* u; T* z; T* zq; T* yz; T* yq; T* yzprev; T* yqprev;
+  T* r;
+  T* hs; T* hys; T* hv;  // smooth form alone
+  FusedScalarsT<T> c;
+  T pkappa;
+  double lam64;
+};
+
+// Workgroup `block` of one member's row side: the body of the single and of the batched kernel.
 template <class T, int ROWS, class Fn>
-__global__ __launch_bounds__(ROWS * kZeroLanes) void ZeroFusedRowsKernel(
-    int64_t m, int nparts, const T* __restrict__ tpart, const T* __restrict__ w, FusedScalarsT<T> c,
-    T pkappa, const T* __restrict__ rhs, const T* __restrict__ g, T* u, T* z, T* zq, T* yz, T* yq,
-    T* yzprev, T* yqprev, T* __restrict__ r, double lam64, T* hs, T* hys, T* hv) {
+__device__ __forceinline__ void ZeroRowsBody(int64_t m, int nparts, const ZeroRowsInst<T>& I, unsigned block) {
   __shared__ T part[kZeroLanes][ROWS];
+  const FusedScalarsT<T>& c = I.c;
   const int t = threadIdx.x, rl = t % ROWS, pl = t / ROWS;
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * ROWS + rl;
+  const int64_t i = static_cast<int64_t>(block) * ROWS + rl;
   T s = T(0);
   if (i < m) {
-    const T* p = tpart + i;
+    const T* p = I.tpart + i;
     int k = pl;
     for (; k + 7 * kZeroLanes < nparts; k += 8 * kZeroLanes) {
       T v[8];
@@ -254,33 +269,47 @@ __global__ __launch_bounds__(ROWS * kZeroLanes) void ZeroFusedRowsKernel(
   FusedScalarsT<T> ci = c;
   if (c.alpha_v != nullptr) ci.alpha = c.alpha_v[i];
   if (c.beta_v != nullptr) ci.beta = c.beta_v[i];
-  const T gi = g != nullptr ? g[i] : T(0);
-  const T yzi = yz[i], yqi = yq[i];
+  const T gi = I.g != nullptr ? I.g[i] : T(0);
+  const T yzi = I.yz[i], yqi = I.yq[i];
   T ns, nq, nys, nyq, nu, vn;
   if constexpr (std::is_void<Fn>::value) {
-    vn = ZeroChainT<T>(w[i], ci, gi, u[i], yzi, yqi, &ns, &nq, &nys, &nyq, &nu);
+    vn = ZeroChainT<T>(I.w[i], ci, gi, I.u[i], yzi, yqi, &ns, &nq, &nys, &nyq, &nu);
   } else {
     // ZeroChainT from the carried head on: q = kappa d + v, y_q = q, u -= y_q
-    ns = hs[i];
-    nys = hys[i];
-    const T v = hv[i];
-    nq = nyq = c.kappa * w[i] + v;
+    ns = I.hs[i];
+    nys = I.hys[i];
+    const T v = I.hv[i];
+    nq = nyq = c.kappa * I.w[i] + v;
     nu = v - nq;
-    const ZeroHeadT<T> hn = ZeroHeadOfT<T, Fn>(ci, gi, nu, nys, nq, lam64);
-    hs[i] = hn.s;
-    hys[i] = hn.ys;
-    hv[i] = vn = hn.v;
+    const ZeroHeadT<T> hn = ZeroHeadOfT<T, Fn>(ci, gi, nu, nys, nq, I.lam64);
+    I.hs[i] = hn.s;
+    I.hys[i] = hn.ys;
+    I.hv[i] = vn = hn.v;
   }
-  yzprev[i] = yzi;
-  yqprev[i] = yqi;
-  z[i] = ns;
-  zq[i] = nq;
-  yz[i] = nys;
-  yq[i] = nyq;
-  u[i] = nu;
+  I.yzprev[i] = yzi;
+  I.yqprev[i] = yqi;
+  I.z[i] = ns;
+  I.zq[i] = nq;
+  I.yz[i] = nys;
+  I.yq[i] = nyq;
+  I.u[i] = nu;
   // forward substitution of the next sweep: (rhs - e v_z) first, then the product with x' on top
-  const T base = c.kappa * vn + (rhs != nullptr ? rhs[i] : T(0));
-  r[i] = pkappa * sum + base;
+  const T base = c.kappa * vn + (I.rhs != nullptr ? I.rhs[i] : T(0));
+  I.r[i] = I.pkappa * sum + base;
+}
+
+template <class T, int ROWS, class Fn>
+__global__ __launch_bounds__(ROWS * kZeroLanes) void ZeroFusedRowsKernel(int64_t m, int nparts, ZeroRowsInst<T> I) {
+  ZeroRowsBody<T, ROWS, Fn>(m, nparts, I, blockIdx.x);
+}
+
+// The members of a batch: grid row b is member b's single launch, workgroup for workgroup.  A
+// workgroup touches its own member's rows alone; nothing waits on another workgroup.
+template <class T, int ROWS, class Fn>
+__global__ __launch_bounds__(ROWS * kZeroLanes) void ZeroFusedRowsBatchKernel(
+    int64_t m, int nparts, const ZeroRowsInst<T>* __restrict__ tab) {
+  const ZeroRowsInst<T> I = tab[blockIdx.y];
+  ZeroRowsBody<T, ROWS, Fn>(m, nparts, I, blockIdx.x);
 }
 
 // The first head of a smooth z term from the adopted boundary state, a thread per row.
@@ -305,16 +334,56 @@ template <class T> FusedScalarsT<T> ZeroRowScalars(const ZeroRowsArgs& a) {
           T(1), T(1), OptT<T>(a.alpha_vec), OptT<T>(a.beta_vec)};
 }
 
+template <class T> ZeroRowsInst<T> RowsInstOf(const ZeroRowsArgs& a) {
+  ZeroRowsInst<T> d;
+  d.tpart = a.tpart.as<T>();
+  d.w = a.w.as<T>();
+  d.rhs = OptT<T>(a.rhs);
+  d.g = OptT<T>(a.g);
+  d.u = a.u.as<T>();
+  d.z = a.z.as<T>();
+  d.zq = a.zq.as<T>();
+  d.yz = a.yz.as<T>();
+  d.yq = a.yq.as<T>();
+  d.yzprev = a.yzprev.as<T>();
+  d.yqprev = a.yqprev.as<T>();
+  d.r = a.r.as<T>();
+  d.hs = a.smooth ? a.hs.as<T>() : nullptr;
+  d.hys = a.smooth ? a.hys.as<T>() : nullptr;
+  d.hv = a.smooth ? a.hv.as<T>() : nullptr;
+  d.c = ZeroRowScalars<T>(a);
+  d.pkappa = static_cast<T>(a.pkappa);
+  d.lam64 = a.lam;
+  return d;
+}
+
 template <class T, int ROWS, class Fn>
 void LaunchZeroRows(const ZeroRowsArgs& a) {
   const unsigned grid = static_cast<unsigned>((a.m + ROWS - 1) / ROWS);
-  const bool smooth = !std::is_void<Fn>::value;
   hipLaunchKernelGGL((ZeroFusedRowsKernel<T, ROWS, Fn>), dim3(grid), dim3(ROWS * kZeroLanes), 0,
-                     Runtime::Get().stream(), a.m, a.nparts, a.tpart.as<T>(), a.w.as<T>(), ZeroRowScalars<T>(a),
-                     static_cast<T>(a.pkappa), OptT<T>(a.rhs), OptT<T>(a.g), a.u.as<T>(), a.z.as<T>(), a.zq.as<T>(),
-                     a.yz.as<T>(), a.yq.as<T>(), a.yzprev.as<T>(), a.yqprev.as<T>(), a.r.as<T>(), a.lam,
-                     smooth ? a.hs.as<T>() : nullptr, smooth ? a.hys.as<T>() : nullptr,
-                     smooth ? a.hv.as<T>() : nullptr);
+                     Runtime::Get().stream(), a.m, a.nparts, RowsInstOf<T>(a));
+}
+
+template <class T, int ROWS, class Fn>
+void LaunchZeroRowsBatch(int64_t m, int nparts, const DVec& table, int count) {
+  const unsigned grid = static_cast<unsigned>((m + ROWS - 1) / ROWS);
+  hipLaunchKernelGGL((ZeroFusedRowsBatchKernel<T, ROWS, Fn>), dim3(grid, static_cast<unsigned>(count)),
+                     dim3(ROWS * kZeroLanes), 0, Runtime::Get().stream(), m, nparts,
+                     reinterpret_cast<const ZeroRowsInst<T>*>(table.as<char>()));
+}
+
+template <class T>
+void UploadRowsT(const std::vector<const ZeroRowsArgs*>& members, DVec* table) {
+  std::vector<ZeroRowsInst<T>> host;
+  host.reserve(members.size());
+  for (const ZeroRowsArgs* a : members) host.push_back(RowsInstOf<T>(*a));
+  const size_t bytes = host.size() * sizeof(ZeroRowsInst<T>);
+  const int64_t words = static_cast<int64_t>((bytes + 7) / 8);
+  if (table->n < words || table->dt != F64) *table = DVec::Empty(words < 1 ? 1 : words, F64);
+  if (bytes == 0) return;
+  Runtime& rt = Runtime::Get();
+  EPS_HIP(hipMemcpyAsync(table->data(), host.data(), bytes, hipMemcpyHostToDevice, rt.stream()));
+  rt.Sync();  // `host` goes out of scope
 }
 
 template <class T>
@@ -347,6 +416,32 @@ void ZeroFusedRows(const ZeroRowsArgs& a) {
   } else {
     if (a.w.dt == F32) LaunchZeroRows<float, kZeroRows, void>(a);
     else LaunchZeroRows<double, kZeroRows, void>(a);
+  }
+  EPS_HIP(hipGetLastError());
+}
+
+void ZeroRowsBatchUpload(const std::vector<const ZeroRowsArgs*>& members, DVec* table) {
+  EPS_CHECK(!members.empty());
+  const ZeroRowsArgs& lead = *members[0];
+  for (const ZeroRowsArgs* a : members) {
+    CheckZeroRows(*a);
+    EPS_CHECK(a->m == lead.m && a->nparts == lead.nparts && a->smooth == lead.smooth && a->w.dt == lead.w.dt);
+  }
+  if (lead.w.dt == F32) UploadRowsT<float>(members, table);
+  else UploadRowsT<double>(members, table);
+}
+
+void ZeroFusedRowsBatch(int64_t m, int nparts, bool smooth, DType dt, const DVec& table, int count) {
+  const int64_t record = dt == F32 ? sizeof(ZeroRowsInst<float>) : sizeof(ZeroRowsInst<double>);
+  EPS_CHECK(m >= 1 && nparts >= 1 && count >= 1 && count <= 65535);
+  EPS_CHECK(table.dt == F64 && table.n * 8 >= count * record);
+  ProfScope prof("batch_zero_rows", m, count);
+  if (smooth) {
+    if (dt == F32) LaunchZeroRowsBatch<float, kZeroSmoothRows, FnLogistic>(m, nparts, table, count);
+    else LaunchZeroRowsBatch<double, kZeroSmoothRows, FnLogistic>(m, nparts, table, count);
+  } else {
+    if (dt == F32) LaunchZeroRowsBatch<float, kZeroRows, void>(m, nparts, table, count);
+    else LaunchZeroRowsBatch<double, kZeroRows, void>(m, nparts, table, count);
   }
   EPS_HIP(hipGetLastError());
 }

@@ -15,6 +15,10 @@
 // product, the same shuffle tree and LDS sum, the same chain (kernels_fused_chain.h), the same
 // order of forward updates, and this file is compiled with -ffp-contract=off as kernels_fused.hip
 // is - so every instance's iterates are bit-identical to its own solve.
+//
+// CHAIN 2: the instances are ZERO-term problems and a column runs the single
+// pass's MODE 2 - ZeroChainT and its stores, e0 among them - in place of ChainOneT; everything
+// around the chain is the same code.
 #include <hip/hip_runtime.h>
 
 #include <vector>
@@ -32,7 +36,7 @@ constexpr int kBlock = 256;
 // GROUP: the nk instances are the columns of ONE matrix variable and the threshold is the group
 // shrinkage of its rows (NORM_2 along axis 1, weight glam): row j's nk threshold inputs are what
 // the pass computes for column j of A, and after the barrier every thread holds all of them.
-template <class T, int NR, int KB, bool GROUP>
+template <class T, int NR, int KB, bool GROUP, int CHAIN>
 __global__ __launch_bounds__(kBlock) void LassoBatchStreamKernel(int64_t m, int64_t n, const T* __restrict__ A,
                                                                  int64_t lda,
                                                                  const LassoBatchInst<T>* __restrict__ tab,
@@ -162,15 +166,30 @@ __global__ __launch_bounds__(kBlock) void LassoBatchStreamKernel(int64_t m, int6
         c.alpha = I.alpha_v != nullptr ? I.alpha_v[j] : I.alpha;
         c.beta = I.beta_v != nullptr ? I.beta_v[j] : I.beta;
         c.M = I.M;
-        T nx0, nx1, ny0, ny1, nu;
-        const T v0n = ChainOneT<T>(d, c, uj[i], y0j[i], y1j[i], &nx0, &nx1, &ny0, &ny1, &nu);
-        if (tid == 0) {
-          I.y1prev[j] = y1j[i];
-          I.x0[j] = nx0;
-          I.x1[j] = nx1;
-          I.y0[j] = ny0;
-          I.y1[j] = ny1;
-          I.u[j] = nu;
+        T v0n;
+        if constexpr (CHAIN == 2) {
+          T ns, nq, nys, nyq, nu;
+          v0n = ZeroChainT<T>(d, c, T(0), uj[i], y1j[i], y0j[i], &ns, &nq, &nys, &nyq, &nu);
+          if (tid == 0) {
+            I.y1prev[j] = y1j[i];
+            I.e0[j] = y0j[i];
+            I.x1[j] = ns;
+            I.x0[j] = nq;
+            I.y1[j] = nys;
+            I.y0[j] = nyq;
+            I.u[j] = nu;
+          }
+        } else {
+          T nx0, nx1, ny0, ny1, nu;
+          v0n = ChainOneT<T>(d, c, uj[i], y0j[i], y1j[i], &nx0, &nx1, &ny0, &ny1, &nu);
+          if (tid == 0) {
+            I.y1prev[j] = y1j[i];
+            I.x0[j] = nx0;
+            I.x1[j] = nx1;
+            I.y0[j] = ny0;
+            I.y1[j] = ny1;
+            I.u[j] = nu;
+          }
         }
 #pragma unroll
         for (int q = 0; q < NR; ++q)
@@ -205,27 +224,35 @@ int ChunksPerThread(int64_t m, DType dt) {
 // either type, the column and the next one in flight 8 NR more.  Chosen so that no
 // instantiation spills to scratch (hipcc -Rpass-analysis=kernel-resource-usage).
 constexpr int WidthFor(int nr) { return nr <= 2 ? 8 : nr <= 4 ? 6 : nr <= 8 ? 5 : 4; }
+// The ZERO chain's widths (CHAIN 2): its column step keeps a few more values live than the lasso's
+// ("Registers"), so a form that would spill at the lasso's width takes a smaller
+// one here; the lasso's widths are not touched.
+constexpr int ZeroWidthFor(int nr) { return WidthFor(nr); }
+constexpr int WidthFor(int nr, int chain) { return chain == 2 ? ZeroWidthFor(nr) : WidthFor(nr); }
 
 template <class T, int NR>
 void LaunchBatch(int grid, int64_t m, int64_t n, const T* A, int64_t lda, const LassoBatchInst<T>* tab, int nk,
-                 const double* glam, const FusedResidency& res) {
-  if (glam != nullptr)
-    hipLaunchKernelGGL((LassoBatchStreamKernel<T, NR, WidthFor(NR), true>), dim3(grid), dim3(kBlock), 0,
+                 const double* glam, const FusedResidency& res, int chain) {
+  if (chain == 2)
+    hipLaunchKernelGGL((LassoBatchStreamKernel<T, NR, ZeroWidthFor(NR), false, 2>), dim3(grid), dim3(kBlock), 0,
+                       Runtime::Get().stream(), m, n, A, lda, tab, nk, 0.0, res.qfull, res.jcut);
+  else if (glam != nullptr)
+    hipLaunchKernelGGL((LassoBatchStreamKernel<T, NR, WidthFor(NR), true, 0>), dim3(grid), dim3(kBlock), 0,
                        Runtime::Get().stream(), m, n, A, lda, tab, nk, *glam, res.qfull, res.jcut);
   else
-    hipLaunchKernelGGL((LassoBatchStreamKernel<T, NR, WidthFor(NR), false>), dim3(grid), dim3(kBlock), 0,
+    hipLaunchKernelGGL((LassoBatchStreamKernel<T, NR, WidthFor(NR), false, 0>), dim3(grid), dim3(kBlock), 0,
                        Runtime::Get().stream(), m, n, A, lda, tab, nk, 0.0, res.qfull, res.jcut);
 }
 
 template <class T>
 void LaunchBatchT(int nr, int grid, int64_t m, int64_t n, const T* A, int64_t lda, const LassoBatchInst<T>* tab,
-                  int nk, const double* glam, const FusedResidency& res) {
+                  int nk, const double* glam, const FusedResidency& res, int chain) {
   switch (nr) {
-    case 1: LaunchBatch<T, 1>(grid, m, n, A, lda, tab, nk, glam, res); break;
-    case 2: LaunchBatch<T, 2>(grid, m, n, A, lda, tab, nk, glam, res); break;
-    case 4: LaunchBatch<T, 4>(grid, m, n, A, lda, tab, nk, glam, res); break;
-    case 8: LaunchBatch<T, 8>(grid, m, n, A, lda, tab, nk, glam, res); break;
-    default: LaunchBatch<T, 10>(grid, m, n, A, lda, tab, nk, glam, res); break;
+    case 1: LaunchBatch<T, 1>(grid, m, n, A, lda, tab, nk, glam, res, chain); break;
+    case 2: LaunchBatch<T, 2>(grid, m, n, A, lda, tab, nk, glam, res, chain); break;
+    case 4: LaunchBatch<T, 4>(grid, m, n, A, lda, tab, nk, glam, res, chain); break;
+    case 8: LaunchBatch<T, 8>(grid, m, n, A, lda, tab, nk, glam, res, chain); break;
+    default: LaunchBatch<T, 10>(grid, m, n, A, lda, tab, nk, glam, res, chain); break;
   }
 }
 
@@ -245,37 +272,41 @@ void UploadT(const std::vector<const LassoInstance*>& members, DVec* table) {
 
 }  // namespace
 
-int LassoBatchWidth(int64_t m, int64_t n, DType dt) {
+int LassoBatchWidth(int64_t m, int64_t n, DType dt, int chain) {
   if (LassoFusedBlock(m, n, dt) != kBlock) return 0;
-  return WidthFor(ChunksPerThread(m, dt));
+  return WidthFor(ChunksPerThread(m, dt), chain);
 }
 
 void LassoBatchUpload(const std::vector<const LassoInstance*>& members, DType dt, DVec* table) {
   for (const LassoInstance* s : members)
     for (const DVec* v : {&s->w, &s->tpart, &s->u, &s->x0, &s->x1, &s->y0, &s->y1, &s->y1prev, &s->p})
       EPS_CHECK(v->dt == dt && v->n > 0);
+  for (const LassoInstance* s : members) EPS_CHECK(s->e0.n == 0 || (s->e0.dt == dt && s->e0.n == s->u.n));
   if (dt == F32) UploadT<float>(members, table);
   else UploadT<double>(members, table);
 }
 
 void LassoBatchPass(int64_t m, int64_t n, int64_t lda, const DVec& A, const DVec& table, int first, int count,
-                    const double* group_lam, const FusedResidency& res) {
+                    const double* group_lam, const FusedResidency& res, int chain) {
   const DType dt = A.dt;
+  EPS_CHECK_MSG(chain == 0 || (chain == 2 && group_lam == nullptr), "batched fused pass: chain " << chain);
   EPS_CHECK(LassoFusedSupported(m, n, A, lda));
   EPS_CHECK(res.qfull >= 0 && res.jcut >= 0 && res.jcut <= n);
-  const int width = LassoBatchWidth(m, n, dt);
+  const int width = LassoBatchWidth(m, n, dt, chain);
   EPS_CHECK_MSG(width > 0 && count >= 1 && count <= width,
                 "batched fused pass: " << count << " instances, width " << width);
   const int grid = LassoFusedGrid(m, n, dt);
   const int nr = ChunksPerThread(m, dt);
-  ProfScope prof("batch_fused_pass", m, n);
+  ProfScope prof(chain == 2 ? "batch_zero_pass" : "batch_fused_pass", m, n);
   NoteFusedResidency(res.qfull, res.jcut);
   if (dt == F32)
     LaunchBatchT<float>(nr, grid, m, n, A.as<float>(), lda,
-                        reinterpret_cast<const LassoBatchInst<float>*>(table.as<char>()) + first, count, group_lam, res);
+                        reinterpret_cast<const LassoBatchInst<float>*>(table.as<char>()) + first, count, group_lam, res,
+                        chain);
   else
     LaunchBatchT<double>(nr, grid, m, n, A.as<double>(), lda,
-                         reinterpret_cast<const LassoBatchInst<double>*>(table.as<char>()) + first, count, group_lam, res);
+                         reinterpret_cast<const LassoBatchInst<double>*>(table.as<char>()) + first, count, group_lam, res,
+                         chain);
   EPS_HIP(hipGetLastError());
 }
 

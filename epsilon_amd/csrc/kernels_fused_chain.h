@@ -77,6 +77,7 @@ template <class T> LassoBatchInst<T> Narrow(const LassoInstance& s) {
   d.alpha = static_cast<T>(s.alpha);
   d.beta = static_cast<T>(s.beta);
   d.M = static_cast<T>(s.M);
+  d.e0 = s.e0.n > 0 ? s.e0.as<T>() : nullptr;
   return d;
 }
 

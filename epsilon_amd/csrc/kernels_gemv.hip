@@ -611,6 +611,7 @@ DVec SymvPack(int64_t n, const DVec& S, int64_t lds) {
   const int64_t nb = (n + kSB - 1) / kSB;
   const unsigned tiles = static_cast<unsigned>(nb * (nb + 1) / 2);
   hipStream_t s = Runtime::Get().stream();
+  ProfScope prof("pack_inverse", n);  // (a setup step: the members of a batch share one copy)
   if (S.dt == F32)
     hipLaunchKernelGGL(SymvPackKernel<float>, dim3(tiles), dim3(kBlock), 0, s, n, S.as<float>(), lds, P.as<float>());
   else

@@ -343,8 +343,14 @@ std::shared_ptr<const LinearMapImpl> DenseMatrixImpl::Inverse() const {
   OpCache* cache = CurrentOpCache();
   if (cache && id_) {
     key = HashDouble(HashCombine(HashCombine(id_, 0x1171), trans_ ? 2 : 1), scale_);
-    if (auto hit = cache->Find(key))
-      return std::make_shared<DenseMatrixImpl>(hit->data(), nn, nn, false, sign, key, true);
+    if (auto hit = cache->Find(key)) {
+      auto again = std::make_shared<DenseMatrixImpl>(hit->data(), nn, nn, false, sign, key, true);
+      // the same buffer: the tile-packed copy Apply() made of it serves this view as well (the
+      // members of a batch end up with one)
+      again->packed_ = hit->packed_;
+      again->applies_ = hit->applies_;
+      return again;
+    }
   }
   DVec W = DVec::Empty(nn * nn, data_.dt);
   k::MatCopy(trans_, nn, nn, sign * scale_, data_, rows_, W);

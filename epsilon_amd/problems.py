@@ -487,11 +487,17 @@ def _graph_form(f_terms, C, d, x_key="var:x", z_key="var:z", x_in_terms=True):
     return ir.Problem(terms, cons)
 
 
-def basis_pursuit(m, n, seed=0):
-    """min ||x||_1  s.t.  A x = b."""
+def basis_pursuit(m, n, seed=0, b=None):
+    """min ||x||_1  s.t.  A x = b.  `b` (m values; default: A times a sparse vector drawn after A)
+    replaces the right-hand side alone: problems of one seed share A, so several signals on one
+    dictionary are members of one batched group (_solve.solve_batch)."""
     rng = np.random.RandomState(seed)
     A = rng.randn(m, n)
-    b = A.dot(rng.randn(n) * (rng.rand(n) < 0.2))
+    if b is None:
+        b = A.dot(rng.randn(n) * (rng.rand(n) < 0.2))
+    else:
+        b = np.asarray(b, dtype=np.float64).reshape(-1)
+        assert b.shape == (m,), "basis_pursuit: b has %d entries for %d rows" % (b.size, m)
     xp = ir.variable(n, 1, "separate:var:x:zero")
     x = ir.variable(n, 1, "var:x")
     f0 = ir.prox(ProxFunction.NORM_1, x)

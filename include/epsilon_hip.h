@@ -141,8 +141,15 @@ int eps_solve(const void* problem, size_t problem_len, const void* solver_params
  * NORM_1 / SUM_DEADZONE / SUM_HINGE / SUM_QUANTILE, multi-block driver, one GPU) that share the
  * data matrix run together: one Gram product and one inverse for all, then sweeps that read the
  * matrix once for up to KB instances, each instance stopped at its own residual
- * check.  Every other instance - and a fused one with no partner - is solved alone by eps_solve's
- * code.  Per-iteration log lines (verbose) are not printed for instances solved together.
+ * check.  The same holds for instances of the fused ZERO-term form (basis
+ * pursuit, hinge / deadzone / logistic loss + l1 in graph form, fat data matrix with at least 256
+ * rows, option "fused_zero") that share the data matrix - a lambda path, several right-hand sides:
+ * one Gram product and one inverse for all, then per sweep one pass over the matrix for up to KB
+ * of them, one launch for the row side of all and one inverse apply for all; lambda, the loss's
+ * parameters and vectors, the offset and the right-hand side may differ per instance, so hinge and
+ * deadzone instances on one matrix run together.  Every other instance - tall data, the two-block
+ * driver, shapes above 10240 rows in f32 or 5120 in f64, sharded solves, and a fused one with no
+ * partner - is solved alone by eps_solve's code.  Per-iteration log lines (verbose) are not printed for instances solved together.
  * With the option "batch_wide" = "1" the contract above is relaxed for the members of a WIDE
  * group and for them only: a group as formed above, f32, with at least 8 members (DESIGN.md 3.8;
  * measured: 6.8x the instance-sweeps/s of 8 instances on the default route at K = 32 on the
