@@ -36,6 +36,17 @@ the batched side wins by more than the two spreads combined (ZERO p
 
     python bench_zero.py --path 2,4,8 [--shapes hinge,logreg,bp,hinge_big,floor] [--steps 100]
                          [--runs 3] [--lib PATH | --against PATH [--rounds 3]]
+
+Tall cells (more rows than columns; DESIGN.md 3.11 "Tall C"): the same measurement on the two
+routes of the option "fused_zero_tall" - "0" the generic operator path, which is what these
+problems took before the route existed, and "1" the fused sweep over a transposed copy of the data
+matrix - with the routes under those names in ms_per_sweep / spread and sweeps_per_s beside them:
+hinge_tall = hinge + l1 5000 x 1500 (hinge_tall64 in f64), hinge_tall_big = 16384 x 4096,
+deadzone_tall = deadzone + l1 5000 x 1500, mnist_shape = hinge + l1 60000 x 784, and the ladder
+ladder256 / ladder512 / ladder1024 / ladder2048 = hinge + l1 4n x n, which sets the floor of "auto":
+the smallest n from which the fused median is at least 1.05 x the generic one.
+
+    python bench_zero.py --shapes hinge_tall,hinge_tall64,hinge_tall_big,deadzone_tall,mnist_shape,ladder256,ladder512,ladder1024,ladder2048
 """
 
 import argparse
@@ -61,8 +72,18 @@ SHAPES = {
     "logreg_big": ("logreg_l1", 4096, 16384, "f32"),
     "floor": ("hinge_l1", 256, 601, "f32"),
     "floor64": ("hinge_l1", 256, 601, "f64"),
+    "hinge_tall": ("hinge_l1", 5000, 1500, "f32"),
+    "hinge_tall64": ("hinge_l1", 5000, 1500, "f64"),
+    "hinge_tall_big": ("hinge_l1", 16384, 4096, "f32"),
+    "deadzone_tall": ("deadzone_l1", 5000, 1500, "f32"),
+    "mnist_shape": ("hinge_l1", 60000, 784, "f32"),
+    "ladder256": ("hinge_l1", 1024, 256, "f32"),
+    "ladder512": ("hinge_l1", 2048, 512, "f32"),
+    "ladder1024": ("hinge_l1", 4096, 1024, "f32"),
+    "ladder2048": ("hinge_l1", 8192, 2048, "f32"),
 }
 ROUTES = ("0", "auto")
+TALL_ROUTES = ("0", "1")  # of "fused_zero_tall", for the cells with more rows than columns
 
 
 def parse():
@@ -193,20 +214,23 @@ def main():
         return
     for name in a.shapes.split(","):
         kind, m, n, dtype = SHAPES[name]
+        tall = m > n
+        option, routes, tag = (("fused_zero_tall", TALL_ROUTES, "zero_tall") if tall else
+                               ("fused_zero", ROUTES, "zero_fused"))
         prob = getattr(problems, kind)(m, n)[0]
         pb, data = prob.SerializeToString(), prob.expression_data()
         sb = wire.SolverParams(max_iterations=10 ** 9, ignore_stopping_criteria=True).SerializeToString()
         _solve.set_option("dtype", dtype)
         handles = {}
         try:
-            for route in ROUTES:
-                _solve.set_option("fused_zero", route)  # read at Init
+            for route in routes:
+                _solve.set_option(option, route)  # read at Init
                 s = _solve.Solver(pb, sb, data)
                 s.init()
                 s.run(a.warmup)
-                fused = "zero_fused" in names_of_one_sweep(s)
+                fused = tag in names_of_one_sweep(s)
                 assert not (route == "0" and fused)
-                if route == "auto" and not fused:
+                if route != "0" and not fused:
                     s.close()  # fell back: the generic path again
                 else:
                     handles[route] = s
@@ -219,15 +243,17 @@ def main():
         finally:
             for s in handles.values():
                 s.close()
-            _solve.set_option("fused_zero", "auto")
+            _solve.set_option(option, "auto")
             _solve.set_option("dtype", "f32")
-        ms = {r: (1e3 * statistics.median(times[r]) if r in times else None) for r in ROUTES}
+        ms = {r: (1e3 * statistics.median(times[r]) if r in times else None) for r in routes}
         spread = {r: ((max(times[r]) - min(times[r])) / statistics.median(times[r]) if r in times else None)
-                  for r in ROUTES}
-        print(json.dumps(dict(
-            bench="zero_routes", shape=name, problem=kind, m=m, n=n, dtype=dtype, gpus=1, steps=a.steps,
-            warmup=a.warmup, ms_per_sweep=ms, spread=spread,
-            speedup=(ms["0"] / ms["auto"] if ms["auto"] else None))), flush=True)
+                  for r in routes}
+        line = dict(bench="zero_routes", shape=name, problem=kind, m=m, n=n, dtype=dtype, gpus=1, steps=a.steps,
+                    warmup=a.warmup, ms_per_sweep=ms, spread=spread,
+                    speedup=(ms["0"] / ms[routes[1]] if ms[routes[1]] else None))
+        if tall:
+            line["sweeps_per_s"] = {r: (1e3 / ms[r] if ms[r] else None) for r in routes}
+        print(json.dumps(line), flush=True)
 
 
 if __name__ == "__main__":

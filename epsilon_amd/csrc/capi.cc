@@ -327,6 +327,11 @@ int eps_set_option(const char* key, const char* value) {
       if (std::strcmp(value, "0") != 0 && std::strcmp(value, "auto") != 0)
         EPS_FATAL("fused_zero must be 0 or auto, got " << value);
       setenv("EPSILON_HIP_FUSED_ZERO", value, 1);
+    } else if (std::strcmp(key, "fused_zero_tall") == 0) {
+      bool ok = false;
+      for (const char* v : {"0", "1", "auto"}) ok = ok || std::strcmp(value, v) == 0;
+      if (!ok) EPS_FATAL("fused_zero_tall must be 0, 1 or auto, got " << value);
+      setenv("EPSILON_HIP_FUSED_ZERO_TALL", value, 1);
     } else if (std::strcmp(key, "fused_resident") == 0) {
       (void)ParseFusedResident(value);  // a bad value is an error here, not at the next Init
       setenv("EPSILON_HIP_FUSED_RESIDENT_KB", value, 1);

@@ -185,6 +185,25 @@ bool FusedZeroAuto() {
   EPS_FATAL("fused_zero must be 0 or auto, got " << e);
 }
 
+// Tall ZERO-term problems (more rows than columns: the order of the block LDL^T ends in x') on
+// the fused sweep (ZeroTallRoute, DESIGN.md 3.11 "Tall C").  Below this many columns of the data
+// matrix the solve keeps the generic operator path whatever the option says.
+constexpr int64_t kZeroTallMinCols = 256;
+// The floor of "auto": the smallest n of the 4n x n ladder of bench_zero.py at which the fused
+// sweep measured at least 1.05 x the generic one (5.5 x at n = 256, the first cell, and
+// no cell above it below 2.9 x); 0 would mean that no cell got there and "auto" is "0".
+constexpr int64_t kZeroTallAutoMinCols = 256;
+
+// EPSILON_HIP_FUSED_ZERO_TALL (eps_set_option "fused_zero_tall"), read at every Init.
+enum ZeroTallMode { kZeroTallOff, kZeroTallAuto, kZeroTallOn };
+ZeroTallMode FusedZeroTallMode() {
+  const char* e = std::getenv("EPSILON_HIP_FUSED_ZERO_TALL");
+  if (e == nullptr || std::strcmp(e, "auto") == 0) return kZeroTallAuto;
+  if (std::strcmp(e, "0") == 0) return kZeroTallOff;
+  if (std::strcmp(e, "1") == 0) return kZeroTallOn;
+  EPS_FATAL("fused_zero_tall must be 0, 1 or auto, got " << e);
+}
+
 // One sweep of a panel of up to 64 f32 members on the wide route (kernels_fused_wide.hip): back
 // product + chain, forward product, reduction and - unless whitened - the cached inverse times
 // the panel.  The workspaces depend on (m, n) alone and serve every panel in turn.
@@ -936,6 +955,197 @@ struct ZeroRoute final : FusedRoute {
 };
 
 // ---------------------------------------------------------------------------------------------------
+// The ZERO-term route for tall C ("Tall C")
+// ---------------------------------------------------------------------------------------------------
+// Recognised structure: ZeroRoute's terms and consensus ties, with the ZERO term's block LDL^T in
+// the tall order (ZeroProx::DescribeZeroTallProjection): arg is a scalar pivot, x' the dense one.
+// Everything between C x' of sweep k and C^T f_arg of sweep k+1 is element-wise in the sample, so
+// the pass streams C^T (features x samples, one contiguous copy made at Init): per sample the
+// product with x', the z-side chain and the forward product (chain 3); then the x-side kernel (the
+// partials' sum, the chain on x, f_x) and the apply of Dinv(x').  A smooth z term is refused: its
+// Newton cannot sit in the per-column step of the pass.  No batched form: a member of a batch on
+// this route is solved by itself.
+struct ZeroTallRoute final : FusedRoute {
+  ZeroTallProjectionDesc zp;
+  ScaledZoneDesc sx, sz;
+  int64_t m = 0, n = 0;  // C is m x n, m > n
+  int grid = 0;
+  DVec state_n, state_m;
+  DVec CT;  // C^T, n x m, ld n: shared through the solve's cache
+  DVec w, p, tpart;  // x' of the coming sweep, f_x, the pass's partials (n-long vectors)
+  InverseApply inv;
+  k::LassoFusedArgs pass;
+  k::ZeroRowsArgs cols;
+  k::FusedResidency res;
+  bool auto_mode = false;  // the option is "auto": the measured floor applies
+
+  bool Enable(const MultiBlockParts& a) {
+    if (FusedDisabled() || ShardSpec::Get().active() || !a.b.data().empty()) return false;
+    const int N = static_cast<int>(a.prox.size());
+    if (a.num_constraints != 2 || N != 3) return false;
+    if (!a.prox[N - 1]->DescribeZeroTallProjection(&zp)) return false;
+    int ix = -1, iz = -1;
+    for (int i = 0; i + 1 < N; ++i) {
+      ScaledZoneDesc d;
+      if (!a.prox[i]->DescribeScaledZoneOffset(&d)) return false;  // (SUM_LOGISTIC: the generic path)
+      if (ix < 0 && d.constraint_key == zp.x_constraint_key && d.g.n == 0) {
+        sx = d;
+        ix = i;
+      } else if (iz < 0 && d.constraint_key == zp.z_constraint_key) {
+        sz = d;
+        iz = i;
+      } else {
+        return false;
+      }
+    }
+    if (ix < 0 || iz < 0) return false;
+    const DenseMatrixImpl& L = *zp.L_x_arg;  // trans() set: its buffer is C, m x n
+    const DenseMatrixImpl& D = *zp.Dinv_x;
+    const DType dt = a.data->dtype();
+    m = L.rows();
+    n = L.cols();
+    if (n < kZeroTallMinCols || m <= n || L.dtype() != dt || D.dtype() != dt) return false;
+    if (auto_mode && (kZeroTallAutoMinCols == 0 || n < kZeroTallAutoMinCols)) return false;
+    if (D.rows() != n || D.cols() != n) return false;
+    // the pass's shape conditions, on the copy's geometry, before the copy is made
+    const int64_t chunk = dt == F32 ? 4 : 2;
+    if (n % chunk != 0 || n > (dt == F32 ? 20 : 10) * 1024) return false;
+    if (static_cast<int>(a.A.data().size()) != 4) return false;
+    double ax = 0, az = 0;
+    auto tie = [&](const std::string& ck, const std::string& copy, const std::string& var, int64_t len, double* av) {
+      double a0 = 0;
+      return ConsensusTie(a.A, ck, copy, var, len, &a0, av) && a0 == 1.0 && a.A.col(copy).size() == 1 &&
+             a.A.col(var).size() == 1;
+    };
+    if (!tie(zp.x_constraint_key, zp.x_key, sx.var_key, n, &ax)) return false;
+    if (!tie(zp.z_constraint_key, zp.z_key, sz.var_key, m, &az)) return false;
+    auto fits = [&](const DVec& v, int64_t len) { return v.n == 0 || (v.n == len && v.dt == dt); };
+    if (!fits(zp.rhs_arg, m) || !fits(sx.alpha_vec, n) || !fits(sx.beta_vec, n)) return false;
+    if (!fits(sz.alpha_vec, m) || !fits(sz.beta_vec, m) || !fits(sz.g, m)) return false;
+
+    // C^T as the pass streams it: one untransposed contiguous copy of the factor's operand
+    // (unscaled: the scale stays in kappa), shared like the packed inverse
+    uint64_t key = 0;
+    if (a.shared_cache != nullptr) {
+      key = HashCombine(HashCombine(HashCombine(reinterpret_cast<uintptr_t>(L.data().data()), 0x7a11c7), L.id()),
+                        static_cast<uint64_t>(m * n));
+      if (auto hit = a.shared_cache->Find(key)) CT = hit->data();
+    }
+    if (CT.n == 0) {
+      CT = DVec::Empty(m * n, dt);
+      k::MatCopy(true, n, m, 1.0, L.data(), L.rows(), CT);
+      if (key) a.shared_cache->Put(key, std::make_shared<DenseMatrixImpl>(CT, n, m, false, 1.0, key));
+    }
+    if (!k::LassoFusedSupported(n, m, CT, n)) return false;
+
+    a.y_prev.resize(N);
+    std::vector<StateSlice> views;
+    auto side = [&](int64_t len, const std::string& ck, int term, const std::string& var, const std::string& copy,
+                    DVec* all) {
+      const int64_t pad = (len + 63) / 64 * 64;
+      *all = DVec::Zeros(7 * pad, dt);
+      const size_t first = views.size();
+      views.insert(views.end(), {{&a.u, ck},
+                                 {&a.x[term], var},
+                                 {&a.x[N - 1], copy},
+                                 {&a.y[term], ck},
+                                 {&a.y[N - 1], ck},
+                                 {&a.y_prev[term], ck, DVec(), false},
+                                 {&a.y_prev[N - 1], ck, DVec(), false}});
+      for (int q = 0; q < 7; ++q) views[first + q].v = all->Slice(q * pad, len);
+      return first;
+    };
+    // the pass's register-held dimension is n, its streamed columns are the m samples
+    grid = k::LassoFusedGrid(n, m, dt);
+    w = DVec::Zeros(n, dt);
+    p = DVec::Zeros(n, dt);
+    tpart = DVec::Empty(static_cast<int64_t>(grid) * n, dt);
+    inv.Init(zp.Dinv_x, n, p, w, a.shared_cache);
+    const size_t fn = side(n, zp.x_constraint_key, ix, sx.var_key, zp.x_key, &state_n);
+    const size_t fm = side(m, zp.z_constraint_key, iz, sz.var_key, zp.z_key, &state_m);
+    {
+      const StateSlice* sm = &views[fm];
+      pass.m = n;
+      pass.n = m;
+      pass.lda = n;
+      pass.A = CT;
+      pass.chain = 3;
+      pass.e0 = sm[6].v;
+      pass.zg = sz.g;
+      pass.zrhs = zp.rhs_arg;
+      pass.ke = -zp.e;
+      pass.dinv = zp.dinv_arg;
+      // beside the matrix the sweep touches the partials, the seven state vectors of either side,
+      // p, w and the inverse
+      const int64_t sz_b = dt == F32 ? 4 : 8;
+      res = ResidentShare(n, m, dt, (static_cast<int64_t>(grid) * n + 7 * (n + m) + 2 * n + n * n) * sz_b,
+                          /*auto_on=*/false);
+      pass.qfull = res.qfull;
+      pass.jcut = res.jcut;
+      k::LassoInstance& s = pass.inst;
+      s.w = w;
+      s.tpart = tpart;
+      s.p = p;
+      s.u = sm[0].v;
+      s.x1 = sm[1].v;
+      s.x0 = sm[2].v;
+      s.y1 = sm[3].v;
+      s.y0 = sm[4].v;
+      s.y1prev = sm[5].v;
+      s.e0 = sm[6].v;
+      s.kappa = s.pkappa = -L.scale();
+      SetThreshold(&s, sz, az);
+    }
+    {
+      const StateSlice* sn = &views[fn];
+      cols.tall = true;
+      cols.m = n;
+      cols.nparts = grid;
+      cols.w = w;
+      cols.tpart = tpart;
+      cols.r = p;
+      cols.u = sn[0].v;
+      cols.z = sn[1].v;
+      cols.zq = sn[2].v;
+      cols.yz = sn[3].v;
+      cols.yq = sn[4].v;
+      cols.yzprev = sn[5].v;
+      cols.yqprev = sn[6].v;
+      cols.pkappa = -L.scale();
+      SetThreshold(&cols, sx, ax);
+    }
+    AdoptState(views, Homes(a));
+    ForwardFromState(a);
+    return true;
+  }
+
+  // x' of the first sweep from the current state, with the generic operators: the sweep up to the
+  // ZERO prox's input v (on copies: the state is not touched), then the forward substitution
+  // f_arg = rhs - e v_z, f_x = v_x - L(x', arg) f_arg and the apply of Dinv(x').
+  void ForwardFromState(const MultiBlockParts& a) {
+    const size_t N = a.prox.size();
+    BlockVector v = a.u;
+    for (size_t i = 0; i < N; ++i) v -= a.y[i];
+    for (size_t i = 0; i + 1 < N; ++i) {
+      v += a.y[i];
+      v -= a.A * a.prox[i]->Apply(v);
+    }
+    v += a.y[N - 1];
+    DVec farg = zp.rhs_arg.n != 0 ? zp.rhs_arg.Clone() : DVec::Zeros(m, w.dt);
+    k::Axpby(farg, -zp.e, v(zp.z_constraint_key), 1.0);
+    k::Copy(p, v(zp.x_constraint_key));
+    zp.L_x_arg->Apply(-1.0, farg, 1.0, p);
+    inv.Apply();
+  }
+
+  void Sweep() override {
+    k::LassoFusedPass(pass);
+    k::ZeroFusedRows(cols);
+    inv.Apply();
+  }
+};
+
+// ---------------------------------------------------------------------------------------------------
 // The lasso structure in two-block form
 // ---------------------------------------------------------------------------------------------------
 // [SUM_SQUARE with a dense argument map, scaled-zone prox], one constraint a0 x0 + a1 x1 = 0
@@ -1054,8 +1264,15 @@ int64_t ParseFusedResident(const char* value) {
 
 std::unique_ptr<FusedRoute> RecogniseMultiBlockRoute(const MultiBlockParts& parts) {
   const bool zero = FusedZeroAuto();  // (read first: a bad value is an error whatever the problem)
+  const ZeroTallMode tall = FusedZeroTallMode();
   if (auto r = Recognise<LassoRoute>(parts)) return r;
-  return zero ? Recognise<ZeroRoute>(parts) : nullptr;
+  if (!zero) return nullptr;
+  if (auto r = Recognise<ZeroRoute>(parts)) return r;
+  if (tall == kZeroTallOff) return nullptr;
+  std::unique_ptr<ZeroTallRoute> r(new ZeroTallRoute);
+  r->auto_mode = tall == kZeroTallAuto;
+  if (!r->Enable(parts)) return nullptr;
+  return std::unique_ptr<FusedRoute>(std::move(r));
 }
 
 std::unique_ptr<FusedRoute> RecogniseTwoBlockRoute(const TwoBlockParts& parts) {

@@ -85,9 +85,17 @@ struct LassoFusedArgs {
   // projection's copy x' = v_x + kappa A^T w last); the arrays then mean u -> u on the x constraint,
   // x0 -> x', x1 -> x, y0 -> y of the ZERO term, y1 -> y of the x term, y1prev -> the x term's
   // previous y, e0 -> the ZERO term's previous y.  Profile tag "zero_fused".  f32 and f64.
+  // chain = 3: the sample side of a TALL ZERO-term problem ("Tall C"): A is C^T
+  // (features x samples), w the copy x' of this sweep, the arrays are chain 2's on the z constraint
+  // (x0 -> z', x1 -> z, y0 -> y of the ZERO term, y1 -> y of the z term, y1prev / e0 -> their
+  // previous values); zg, zrhs: the z term's offset and the constant of the arg row per sample
+  // (optional), ke = -L(arg, z'), dinv = Dinv(arg)'s scalar; inst.kappa scales the product.  The
+  // partials are those of C^T f_arg of the next sweep.  Profile tag "zero_tall".  f32 and f64.
   int chain = 0;
   double a0 = 1;
   DVec e0, e1;
+  DVec zg, zrhs;
+  double ke = 0, dinv = 0;
   // the matrix's share that is loaded to stay in the Infinity Cache (LassoFusedResidency); 0, 0:
   // every load non-temporal
   int qfull = 0;
@@ -117,6 +125,10 @@ struct ZeroRowsArgs {
   bool smooth = false;
   SmoothFn fn = SMOOTH_LOGISTIC;
   DVec hs, hys, hv;                    // smooth: m each, private to the caller
+  // The x side of a tall problem (profile tag "zero_tall_cols"): the m entries are those of x, w is
+  // the copy x' as the inverse apply left it (q = w, no product on top), the term is the one on x
+  // and r = v_x' + pkappa sum(tpart) is the next f_x; rhs, g and e are not read.  Scaled zone alone.
+  bool tall = false;
 };
 void ZeroFusedRows(const ZeroRowsArgs& args);
 void ZeroSmoothHead(const ZeroRowsArgs& args);  // profile tag "zero_fused_head"

@@ -49,11 +49,16 @@ constexpr int kBlock = 256;
 // the state arrays then mean u -> u0, y0 -> z0, y1 -> z1, y1prev -> z0_prev, e0 -> u1, e1 -> z1_prev.
 // MODE 2: the column side of a ZERO-term problem (ZeroChainT); x0 -> x', x1 -> x, y0 -> the ZERO
 // term's y, y1 -> the x term's y, y1prev / e0 -> their previous values.
+// MODE 3: the sample side of a tall ZERO-term problem (ZeroTallChainT, tag "zero_tall").  The matrix
+// is C^T, so the register-held dimension is the feature index and a streamed column is a sample:
+// w -> x', the state arrays are the m-long ones of the z constraint with MODE 2's meaning (x0 -> z',
+// x1 -> z, y0 -> the ZERO term's y, y1 -> the z term's y), and `zt` has the per-sample offset and
+// rhs and the two scalar pivots.  The value returned into the forward product is the next f_arg.
 template <class T, int NR, int BS, int MODE>
 __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
     int64_t m, int64_t n, const T* __restrict__ A, int64_t lda, const T* __restrict__ w,
     FusedScalarsT<T> c, T* u, T* x0, T* x1, T* y0, T* y1, T* y1prev, T* __restrict__ tpart,
-    unsigned* epoch, T* e0, T* e1, int qfull, int64_t jcut) {
+    unsigned* epoch, T* e0, T* e1, int qfull, int64_t jcut, ZeroTallScalarsT<T> zt) {
   typedef typename Chunk<T>::V V;
   constexpr int R = Chunk<T>::R;
   __shared__ T red[2][BS / 64];
@@ -108,6 +113,11 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
     const T uj = u[j], y0j = y0[j], y1j = y1[j];
     T u1j = T(0);
     if (MODE == 1) u1j = e0[j];
+    T gj = T(0), rj = T(0);
+    if (MODE == 3) {
+      if (zt.g != nullptr) gj = zt.g[j];
+      if (zt.rhs != nullptr) rj = zt.rhs[j];
+    }
     T d = T(0);
 #pragma unroll
     for (int q = 0; q < NR; ++q)
@@ -147,6 +157,18 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
         y0[j] = nyq;
         u[j] = nu;
       }
+    } else if (MODE == 3) {
+      T ns, nq, nys, nyq, nu;
+      v0n = ZeroTallChainT<T>(d, cj, zt.ke, zt.dinv, gj, rj, uj, y1j, y0j, &ns, &nq, &nys, &nyq, &nu);
+      if (tid == 0) {
+        y1prev[j] = y1j;
+        e0[j] = y0j;
+        x1[j] = ns;
+        x0[j] = nq;
+        y1[j] = nys;
+        y0[j] = nyq;
+        u[j] = nu;
+      }
     } else {
       T nx0, nx1, nz0, nz1, nu0, nu1;
       v0n = ChainTwoBlockT<T>(d, cj, y0j, y1j, uj, u1j, &nx0, &nx1, &nz0, &nz1, &nu0, &nu1);
@@ -176,17 +198,23 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
     if (row[q] < m) *reinterpret_cast<V*>(out + row[q]) = tp[q];
 }
 
+template <class T> const T* OptT(const DVec& v) { return v.n > 0 ? v.as<T>() : nullptr; }
+
 template <class T, int NR, int BS>
 void LaunchFused(const LassoFusedArgs& a, int grid) {
   const LassoBatchInst<T> i = Narrow<T>(a.inst);
   T* e0 = a.chain != 0 ? a.e0.as<T>() : nullptr;
   T* e1 = a.chain == 1 ? a.e1.as<T>() : nullptr;
+  ZeroTallScalarsT<T> zt = {nullptr, nullptr, T(0), T(0)};
+  if (a.chain == 3) zt = {OptT<T>(a.zg), OptT<T>(a.zrhs), static_cast<T>(a.ke), static_cast<T>(a.dinv)};
   hipLaunchKernelGGL(
       (a.chain == 1 ? LassoFusedStreamKernelT<T, NR, BS, 1>
-                    : a.chain == 2 ? LassoFusedStreamKernelT<T, NR, BS, 2> : LassoFusedStreamKernelT<T, NR, BS, 0>),
+                    : a.chain == 2 ? LassoFusedStreamKernelT<T, NR, BS, 2>
+                                   : a.chain == 3 ? LassoFusedStreamKernelT<T, NR, BS, 3>
+                                                  : LassoFusedStreamKernelT<T, NR, BS, 0>),
       dim3(grid), dim3(BS), 0, Runtime::Get().stream(), a.m, a.n, a.A.as<T>(), a.lda, i.w,
       ScalarsOf<T>(i, a.a0, a.inst.a1), i.u, i.x0, i.x1, i.y0, i.y1, i.y1prev, i.tpart, a.epoch, e0, e1,
-      a.qfull, a.jcut);
+      a.qfull, a.jcut, zt);
 }
 
 // The instantiation for (type, threads, 16-byte row chunks a thread needs).  512 threads: the
@@ -241,7 +269,10 @@ template <class T> struct ZeroRowsInst {
 };
 
 // Workgroup `block` of one member's row side: the body of the single and of the batched kernel.
-template <class T, int ROWS, class Fn>
+// TALL (tag "zero_tall_cols"): the x side of a tall problem over the n entries of x.  The same
+// summation of the partials; the chain takes q = x'_j as the inverse apply left it in w
+// (ZeroTallColsChainT) and r_j = f_x = v_x' + pkappa sum: no rhs on this side.
+template <class T, int ROWS, class Fn, bool TALL = false>
 __device__ __forceinline__ void ZeroRowsBody(int64_t m, int nparts, const ZeroRowsInst<T>& I, unsigned block) {
   __shared__ T part[kZeroLanes][ROWS];
   const FusedScalarsT<T>& c = I.c;
@@ -272,7 +303,10 @@ __device__ __forceinline__ void ZeroRowsBody(int64_t m, int nparts, const ZeroRo
   const T gi = I.g != nullptr ? I.g[i] : T(0);
   const T yzi = I.yz[i], yqi = I.yq[i];
   T ns, nq, nys, nyq, nu, vn;
-  if constexpr (std::is_void<Fn>::value) {
+  if constexpr (TALL) {
+    nq = nyq = I.w[i];
+    vn = ZeroTallColsChainT<T>(nq, ci, gi, I.u[i], yzi, yqi, &ns, &nys, &nu);
+  } else if constexpr (std::is_void<Fn>::value) {
     vn = ZeroChainT<T>(I.w[i], ci, gi, I.u[i], yzi, yqi, &ns, &nq, &nys, &nyq, &nu);
   } else {
     // ZeroChainT from the carried head on: q = kappa d + v, y_q = q, u -= y_q
@@ -293,14 +327,18 @@ __device__ __forceinline__ void ZeroRowsBody(int64_t m, int nparts, const ZeroRo
   I.yz[i] = nys;
   I.yq[i] = nyq;
   I.u[i] = nu;
+  if constexpr (TALL) {
+    I.r[i] = I.pkappa * sum + vn;  // f_x = v_x - L(x', arg) f_arg
+    return;
+  }
   // forward substitution of the next sweep: (rhs - e v_z) first, then the product with x' on top
   const T base = c.kappa * vn + (I.rhs != nullptr ? I.rhs[i] : T(0));
   I.r[i] = I.pkappa * sum + base;
 }
 
-template <class T, int ROWS, class Fn>
+template <class T, int ROWS, class Fn, bool TALL = false>
 __global__ __launch_bounds__(ROWS * kZeroLanes) void ZeroFusedRowsKernel(int64_t m, int nparts, ZeroRowsInst<T> I) {
-  ZeroRowsBody<T, ROWS, Fn>(m, nparts, I, blockIdx.x);
+  ZeroRowsBody<T, ROWS, Fn, TALL>(m, nparts, I, blockIdx.x);
 }
 
 // The members of a batch: grid row b is member b's single launch, workgroup for workgroup.  A
@@ -325,8 +363,6 @@ __global__ __launch_bounds__(kBlock) void ZeroSmoothHeadKernel(
   hys[i] = h.ys;
   hv[i] = h.v;
 }
-
-template <class T> const T* OptT(const DVec& v) { return v.n > 0 ? v.as<T>() : nullptr; }
 
 template <class T> FusedScalarsT<T> ZeroRowScalars(const ZeroRowsArgs& a) {
   return {static_cast<T>(-a.e), static_cast<T>(a.Bs), static_cast<T>(a.Cs), static_cast<T>(a.a1),
@@ -357,10 +393,10 @@ template <class T> ZeroRowsInst<T> RowsInstOf(const ZeroRowsArgs& a) {
   return d;
 }
 
-template <class T, int ROWS, class Fn>
+template <class T, int ROWS, class Fn, bool TALL = false>
 void LaunchZeroRows(const ZeroRowsArgs& a) {
   const unsigned grid = static_cast<unsigned>((a.m + ROWS - 1) / ROWS);
-  hipLaunchKernelGGL((ZeroFusedRowsKernel<T, ROWS, Fn>), dim3(grid), dim3(ROWS * kZeroLanes), 0,
+  hipLaunchKernelGGL((ZeroFusedRowsKernel<T, ROWS, Fn, TALL>), dim3(grid), dim3(ROWS * kZeroLanes), 0,
                      Runtime::Get().stream(), a.m, a.nparts, RowsInstOf<T>(a));
 }
 
@@ -400,6 +436,7 @@ void CheckZeroRows(const ZeroRowsArgs& a) {
     EPS_CHECK(v->n == a.m && v->dt == dt);
   for (const DVec* v : {&a.rhs, &a.g, &a.alpha_vec, &a.beta_vec})
     if (v->n > 0) EPS_CHECK(v->n == a.m && v->dt == dt);
+  EPS_CHECK_MSG(!(a.tall && a.smooth), "the tall ZERO-term x side has no smooth form");
   if (!a.smooth) return;
   EPS_CHECK_MSG(a.fn == SMOOTH_LOGISTIC, "the fused ZERO-term rows take SUM_LOGISTIC alone, got " << a.fn);
   for (const DVec* v : {&a.hs, &a.hys, &a.hv}) EPS_CHECK(v->n == a.m && v->dt == dt);
@@ -409,8 +446,11 @@ void CheckZeroRows(const ZeroRowsArgs& a) {
 
 void ZeroFusedRows(const ZeroRowsArgs& a) {
   CheckZeroRows(a);
-  ProfScope prof("zero_fused_rows", a.m, a.nparts);
-  if (a.smooth) {
+  ProfScope prof(a.tall ? "zero_tall_cols" : "zero_fused_rows", a.m, a.nparts);
+  if (a.tall) {
+    if (a.w.dt == F32) LaunchZeroRows<float, kZeroRows, void, true>(a);
+    else LaunchZeroRows<double, kZeroRows, void, true>(a);
+  } else if (a.smooth) {
     if (a.w.dt == F32) LaunchZeroRows<float, kZeroSmoothRows, FnLogistic>(a);
     else LaunchZeroRows<double, kZeroSmoothRows, FnLogistic>(a);
   } else {
@@ -426,6 +466,7 @@ void ZeroRowsBatchUpload(const std::vector<const ZeroRowsArgs*>& members, DVec* 
   for (const ZeroRowsArgs* a : members) {
     CheckZeroRows(*a);
     EPS_CHECK(a->m == lead.m && a->nparts == lead.nparts && a->smooth == lead.smooth && a->w.dt == lead.w.dt);
+    EPS_CHECK(!a->tall);  // a tall member is solved by itself
   }
   if (lead.w.dt == F32) UploadRowsT<float>(members, table);
   else UploadRowsT<double>(members, table);
@@ -628,13 +669,17 @@ void LassoFusedPass(const LassoFusedArgs& a) {
   for (const DVec* v : {&s.alpha_vec, &s.beta_vec})
     if (v->n > 0) EPS_CHECK(v->n == a.n && v->dt == dt);
   if (a.chain == 1) EPS_CHECK(a.e0.n == a.n && a.e1.n == a.n && a.e0.dt == dt && a.e1.dt == dt);
-  if (a.chain == 2) EPS_CHECK(a.e0.n == a.n && a.e0.dt == dt);
+  if (a.chain == 2 || a.chain == 3) EPS_CHECK(a.e0.n == a.n && a.e0.dt == dt);
+  EPS_CHECK(a.chain >= 0 && a.chain <= 3);
+  if (a.chain == 3)
+    for (const DVec* v : {&a.zg, &a.zrhs})
+      if (v->n > 0) EPS_CHECK(v->n == a.n && v->dt == dt);
   const int grid = LassoFusedGrid(a.m, a.n, dt);
   const int block = LassoFusedBlock(a.m, a.n, dt);
   EPS_CHECK(s.tpart.n >= static_cast<int64_t>(grid) * a.m && s.tpart.dt == dt);
   EPS_CHECK(reinterpret_cast<uintptr_t>(s.w.data()) % 16 == 0 &&
             reinterpret_cast<uintptr_t>(s.tpart.data()) % 16 == 0);
-  ProfScope prof(a.chain == 2 ? "zero_fused" : "lasso_fused", a.m, a.n);
+  ProfScope prof(a.chain == 3 ? "zero_tall" : a.chain == 2 ? "zero_fused" : "lasso_fused", a.m, a.n);
   NoteFusedResidency(a.qfull, a.jcut);
   if (dt == F32) LaunchFusedT<float>(a, grid, block);
   else LaunchFusedT<double>(a, grid, block);

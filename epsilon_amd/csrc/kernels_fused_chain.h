@@ -181,6 +181,54 @@ __device__ inline T ZeroChainT(T d, const FusedScalarsT<T>& c, T g, T u, T ysp, 
   return ZeroHeadOfT<T>(c, g, un, h.ys, q).v;
 }
 
+// ---- tall ZERO-term problems ("Tall C"): the block LDL^T eliminates
+// [constraints, z', arg, x'], so the arg row is a scalar pivot between the two copies and the
+// sample side of a sweep is, per sample i with d = C[i,:] . x' of this sweep,
+//   f_arg = rhs - e v        forward substitution          (block.cc Substitute: alpha*(e v) + rhs)
+//   g_arg = Dinv_arg f_arg   the scalar pivot              (D_inv_ * b)
+//   arg   = kappa d + g_arg  back substitution through L(x', arg)^T  (GEMV epilogue alpha*acc + y)
+//   q     = v - e arg        back substitution through L(arg, z')
+// with v the ZERO prox's input on the sample's row (ZeroHeadOfT), then y_q = q, u = v - q.
+// The scalars beside the zone's: c.kappa scales d (-scale of L(x', arg)), `ke` = -e, `dinv` =
+// Dinv(arg)'s scalar.
+template <class T> struct ZeroTallScalarsT {
+  const T* g;    // the z term's offset (nullptr: none)
+  const T* rhs;  // the constant on the arg row (nullptr: none)
+  T ke, dinv;
+};
+// The next sweep's f_arg from the ZERO prox's input v: the weight of the forward product.
+template <class T> __device__ inline T ZeroTallForwardT(T v, T rhs, T ke) { return ke * v + rhs; }
+// Finishes the sample's sweep from the product `d`, writes the boundary state and returns the
+// NEXT sweep's f_arg, computed in registers from that state.
+template <class T>
+__device__ inline T ZeroTallChainT(T d, const FusedScalarsT<T>& c, T ke, T dinv, T g, T rhs, T u, T ysp, T yqp,
+                                   T* so, T* qo, T* yso, T* yqo, T* uo) {
+  const ZeroHeadT<T> h = ZeroHeadOfT<T>(c, g, u, ysp, yqp);
+  const T farg = ZeroTallForwardT<T>(h.v, rhs, ke);
+  const T garg = dinv * farg;
+  const T arg = c.kappa * d + garg;
+  const T q = ke * arg + h.v;
+  const T un = h.v - q;  // y_q = q (its constraint map is I); u -= y_q
+  *so = h.s;
+  *qo = q;
+  *yso = h.ys;
+  *yqo = q;
+  *uo = un;
+  return ZeroTallForwardT<T>(ZeroHeadOfT<T>(c, g, un, h.ys, q).v, rhs, ke);
+}
+// The x side of the same sweep: x'_j comes from the apply of Dinv(x') as it is (q = x'_j, no
+// product on top), y_q = q, u = v - q; returns the NEXT sweep's v_x.
+template <class T>
+__device__ inline T ZeroTallColsChainT(T q, const FusedScalarsT<T>& c, T g, T u, T ysp, T yqp, T* so, T* yso,
+                                       T* uo) {
+  const ZeroHeadT<T> h = ZeroHeadOfT<T>(c, g, u, ysp, yqp);
+  const T un = h.v - q;
+  *so = h.s;
+  *yso = h.ys;
+  *uo = un;
+  return ZeroHeadOfT<T>(c, g, un, h.ys, q).v;
+}
+
 // The group threshold of one row of a matrix variable (NORM_2 with axis = 1): SegNorm2Kernel's
 // expressions (kernels_segprox.hip) on the sum of squares `ss` of the row's threshold inputs,
 // accumulated in fp64 in member order.  Returns the factor of xz_i = T(scale * double(vin_i)).

@@ -691,6 +691,60 @@ class ZeroProx final : public ProxOperator {
     return true;
   }
 
+  // The same graph forms with tall C: the order is [constraint, constraint, z', arg, x'] - both
+  // copies tied to their constraint rows as above (Dinv(z') = 1), the arg pivot a scalar matrix
+  // between them with L(arg, z') a scalar, L(x', arg) the dense transposed data matrix and
+  // Dinv(x') the only dense pivot; nothing else in L.  Then with v the prox input
+  //   f_arg = rhs_arg - e v_z,  Solve(b_ + v)[x'] = Dinv(x') (v_x - L(x',arg) f_arg),
+  //   arg = Dinv(arg) f_arg - L(x',arg)^T x',  [z'] = v_z - e arg.
+  bool DescribeZeroTallProjection(ZeroTallProjectionDesc* d) const override {
+    const std::vector<std::string>& p = chol_.order();
+    if (chol_.refine_steps() > 0) return false;
+    if (var_keys_.size() != 2 || p.size() != 5) return false;
+    const std::string &zk = p[2], &ak = p[3], &xk = p[4];
+    if (var_keys_.count(zk) == 0 || var_keys_.count(xk) == 0 || var_keys_.count(ak) != 0) return false;
+    if (var_keys_.count(p[0]) != 0 || var_keys_.count(p[1]) != 0) return false;
+    const BlockMatrix& L = chol_.L();
+    const BlockMatrix& Di = chol_.D_inv();
+    auto is_scalar = [](const LinearMap& m, double a) {
+      return m.impl().type() == SCALAR_MATRIX && GetScalar(m) == a;
+    };
+    // the constraint row of each copy: the one of the first two keys whose column reaches it
+    auto row_of = [&](const std::string& vk, std::string* ck) {
+      const bool r0 = L.has_key(vk, p[0]), r1 = L.has_key(vk, p[1]);
+      if (r0 == r1) return false;
+      *ck = r0 ? p[0] : p[1];
+      return Di.has_key(*ck, *ck) && is_scalar(L(vk, *ck), -1.0) && is_scalar(Di(*ck, *ck), -1.0);
+    };
+    std::string cx, cz;
+    if (!row_of(xk, &cx) || !row_of(zk, &cz) || cx == cz) return false;
+    // L holds these four blocks and no other
+    size_t blocks = 0;
+    for (const auto& col : L.data()) blocks += col.second.size();
+    if (blocks != 4 || !L.has_key(ak, zk) || !L.has_key(xk, ak)) return false;
+    if (!Di.has_key(zk, zk) || !Di.has_key(ak, ak) || !Di.has_key(xk, xk)) return false;
+    if (!is_scalar(Di(zk, zk), 1.0)) return false;
+    if (Di(ak, ak).impl().type() != SCALAR_MATRIX || L(ak, zk).impl().type() != SCALAR_MATRIX) return false;
+    if (L(xk, ak).impl().type() != DENSE_MATRIX || Di(xk, xk).impl().type() != DENSE_MATRIX) return false;
+    auto Lxa = std::static_pointer_cast<const DenseMatrixImpl>(L(xk, ak).ptr());
+    auto Dx = std::static_pointer_cast<const DenseMatrixImpl>(Di(xk, xk).ptr());
+    if (!Lxa->trans() || Dx->rows() != Lxa->m() || Dx->cols() != Lxa->m()) return false;
+    for (const auto& kv : b_.data())
+      if (kv.first != ak) return false;
+    *d = ZeroTallProjectionDesc();
+    d->x_key = xk;
+    d->z_key = zk;
+    d->arg_key = ak;
+    d->x_constraint_key = cx;
+    d->z_constraint_key = cz;
+    d->L_x_arg = Lxa;
+    d->Dinv_x = Dx;
+    d->dinv_arg = GetScalar(Di(ak, ak));
+    d->e = GetScalar(L(ak, zk));
+    d->rhs_arg = b_.has_key(ak) ? b_(ak) : DVec();
+    return true;
+  }
+
  private:
   BlockCholesky chol_;
   BlockVector b_;

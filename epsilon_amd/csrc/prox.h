@@ -84,6 +84,22 @@ struct ZeroProjectionDesc {
   DVec rhs_arg;                                     // constant part of the rhs on the arg row
 };
 
+// ZeroProx of the same graph forms for TALL C (more rows than columns): the fill model eliminates
+// [constraint, constraint, z', arg, x'], so arg is a scalar pivot and x' the only dense one
+// ("Tall C").  With v the prox input and f_arg = rhs_arg - e v_z:
+//   x' = Dinv_x (v_x - L_x_arg f_arg),  arg = dinv_arg f_arg - L_x_arg^T x',  z' = v_z - e arg
+// with L_x_arg = L(x', arg) = -C^T / e^2 as the factorisation holds it (transposed, lazily scaled)
+// and Dinv_x = (I + C^T C / e^2)^-1.
+struct ZeroTallProjectionDesc {
+  std::string x_key, z_key, arg_key;
+  std::string x_constraint_key, z_constraint_key;
+  std::shared_ptr<const DenseMatrixImpl> L_x_arg;  // L(x', arg): trans() set, n x m as a map
+  std::shared_ptr<const DenseMatrixImpl> Dinv_x;   // cached explicit inverse, n x n
+  double dinv_arg = 0;                             // Dinv(arg)'s scalar
+  double e = 0;                                    // L(arg, z')
+  DVec rhs_arg;                                    // constant part of the rhs on the arg row
+};
+
 class ProxOperator {  // reference prox/prox.h:37-43
  public:
   virtual ~ProxOperator() {}
@@ -96,6 +112,7 @@ class ProxOperator {  // reference prox/prox.h:37-43
   virtual bool DescribeScaledZoneOffset(ScaledZoneDesc* d) const { return false; }
   virtual bool DescribeSmoothSeparable(SmoothSeparableDesc* d) const { return false; }
   virtual bool DescribeZeroProjection(ZeroProjectionDesc* d) const { return false; }
+  virtual bool DescribeZeroTallProjection(ZeroTallProjectionDesc* d) const { return false; }
 };
 
 std::unique_ptr<ProxOperator> CreateProxOperator(int type, bool epigraph);

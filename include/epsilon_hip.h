@@ -102,6 +102,15 @@ const char* eps_version(void);
  * 4 (f64: 2), multi-block driver, one GPU, every operand in the compute type; anything else, "0"
  * and "fused" = "0" mean the generic operator path.  Read at every Init.  Any other value is an
  * error that names it (env EPSILON_HIP_FUSED_ZERO).
+ * "fused_zero_tall" = "auto" (default) | "0" | "1"  the same problems with tall C (more rows than
+ * columns; hinge or deadzone loss with an l1 penalty, not the logistic loss): the sweep as one
+ * pass over a transposed copy of C (made once per Init: the matrix's footprint doubles), one
+ * kernel on the x side and the apply of the cached n x n inverse.  "1": wherever the route is
+ * supported - 256 to 20480 columns (f64: 10240), columns a multiple of 4 (f64: 2), multi-block
+ * driver, one GPU, every operand in the compute type; "0": never; "auto": from the measured floor
+ * on the number of columns (256, so "auto" is "1" at present).  "fused_zero" = "0" and
+ * "fused" = "0" switch it off as well.  Read at every Init.  Any other value is an error that
+ * names it (env EPSILON_HIP_FUSED_ZERO_TALL).
  * "fused_resident" = "auto" (default) | "<KiB>"  bytes of the data matrix that the fused pass
  * (single and batched; one GPU) loads with the default cache policy, so that they stay in the
  * 256 MiB Infinity Cache from sweep to sweep, while the rest is streamed with non-temporal loads.
