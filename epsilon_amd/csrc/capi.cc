@@ -315,22 +315,16 @@ int eps_set_option(const char* key, const char* value) {
     } else if (std::strcmp(key, "fused") == 0) {
       setenv("EPSILON_HIP_FUSED", value, 1);
     } else if (std::strcmp(key, "batch_wide") == 0) {
-      if (std::strcmp(value, "0") != 0 && std::strcmp(value, "1") != 0)
-        EPS_FATAL("batch_wide must be 0 or 1, got " << value);
+      (void)ParseChoiceOption(key, value);  // a bad value is an error here, not at the next read
       setenv("EPSILON_HIP_BATCH_WIDE", value, 1);
     } else if (std::strcmp(key, "fused_matrix") == 0) {
-      bool ok = false;
-      for (const char* v : {"0", "pass", "wide", "auto"}) ok = ok || std::strcmp(value, v) == 0;
-      if (!ok) EPS_FATAL("fused_matrix must be 0, pass, wide or auto, got " << value);
+      (void)ParseChoiceOption(key, value);
       setenv("EPSILON_HIP_FUSED_MATRIX", value, 1);
     } else if (std::strcmp(key, "fused_zero") == 0) {
-      if (std::strcmp(value, "0") != 0 && std::strcmp(value, "auto") != 0)
-        EPS_FATAL("fused_zero must be 0 or auto, got " << value);
+      (void)ParseChoiceOption(key, value);
       setenv("EPSILON_HIP_FUSED_ZERO", value, 1);
     } else if (std::strcmp(key, "fused_zero_tall") == 0) {
-      bool ok = false;
-      for (const char* v : {"0", "1", "auto"}) ok = ok || std::strcmp(value, v) == 0;
-      if (!ok) EPS_FATAL("fused_zero_tall must be 0, 1 or auto, got " << value);
+      (void)ParseChoiceOption(key, value);
       setenv("EPSILON_HIP_FUSED_ZERO_TALL", value, 1);
     } else if (std::strcmp(key, "fused_resident") == 0) {
       (void)ParseFusedResident(value);  // a bad value is an error here, not at the next Init

@@ -4,6 +4,7 @@
 #include "fused_route.h"
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -130,6 +131,33 @@ bool FusedDisabled() {  // EPSILON_HIP_FUSED=0 (eps_set_option "fused"), read at
 
 int BatchWideMin();  // (with the batched solves below)
 
+// The options with a choice of words (ParseChoiceOption): the variable that holds the option, its
+// words in the order of their indices, the error's text and the word that holds while the variable
+// is unset.  "fused_zero", "fused_zero_tall" and "fused_matrix" are read at every Init,
+// "batch_wide" per batch ("1" sends eligible groups to the wide route).
+const struct ChoiceOption {
+  const char *name, *env, *words[5], *error, *unset;
+} kChoiceOptions[] = {
+    {"fused_zero", "EPSILON_HIP_FUSED_ZERO", {"0", "auto"}, "fused_zero must be 0 or auto, got ", "auto"},
+    {"fused_zero_tall", "EPSILON_HIP_FUSED_ZERO_TALL", {"0", "1", "auto"},
+     "fused_zero_tall must be 0, 1 or auto, got ", "auto"},
+    {"fused_matrix", "EPSILON_HIP_FUSED_MATRIX", {"0", "pass", "wide", "auto"},
+     "fused_matrix must be 0, pass, wide or auto, got ", "auto"},
+    {"batch_wide", "EPSILON_HIP_BATCH_WIDE", {"0", "1"}, "batch_wide must be 0 or 1, got ", "0"},
+};
+enum ZeroTallMode { kZeroTallOff, kZeroTallOn, kZeroTallAuto };
+enum MatrixRoute { kMatrixOff, kMatrixPass, kMatrixWide, kMatrixAuto };
+
+// The option as its variable holds it now.
+int ChoiceOptionNow(const char* name) {
+  for (const ChoiceOption& o : kChoiceOptions) {
+    if (std::strcmp(o.name, name) != 0) continue;
+    const char* e = std::getenv(o.env);
+    return ParseChoiceOption(name, e != nullptr ? e : o.unset);
+  }
+  EPS_FATAL("unknown option " << name);
+}
+
 // What the Infinity Cache holds of lines loaded with the default policy before re-reads start to
 // miss: the upper end of the plateau of the budget sweep on the pass ("A resident
 // slab of the streamed matrix").
@@ -143,14 +171,20 @@ int64_t FusedResidentOption() {
 }
 
 // The share of the pass's m x n matrix that stays in the Infinity Cache (k::LassoFusedResidency)
-// under the option.  `touched`: the bytes the sweep itself moves with the default policy between
-// two uses of a matrix line - "auto" leaves them their room.  `auto_on`: false on the routes whose
-// sweep has not been timed with a resident share - there "auto" streams everything
-// and only an explicit number of KiB gives a share.
-k::FusedResidency ResidentShare(int64_t m, int64_t n, DType dt, int64_t touched, bool auto_on) {
+// under the option, written into `pass` when one is given.  `touched`: the values the sweep itself
+// moves with the default policy between two uses of a matrix line - "auto" leaves them their room.
+// `auto_on`: false on the routes whose sweep has not been timed with a resident share
+//  - there "auto" streams everything and only an explicit number of KiB gives a share.
+k::FusedResidency ResidentShare(int64_t m, int64_t n, DType dt, int64_t touched, bool auto_on,
+                                k::LassoFusedArgs* pass = nullptr) {
   int64_t budget = FusedResidentOption();
-  if (budget < 0) budget = auto_on ? std::max<int64_t>(0, kResidentLimitBytes - touched) : 0;
-  return k::LassoFusedResidency(m, n, dt, budget);
+  if (budget < 0) budget = auto_on ? std::max<int64_t>(0, kResidentLimitBytes - touched * (dt == F32 ? 4 : 8)) : 0;
+  const k::FusedResidency res = k::LassoFusedResidency(m, n, dt, budget);
+  if (pass != nullptr) {
+    pass->qfull = res.qfull;
+    pass->jcut = res.jcut;
+  }
+  return res;
 }
 
 // Matrix variables X (n x k) under the data map I_k (x) A: the k columns run as k members of the
@@ -158,50 +192,33 @@ k::FusedResidency ResidentShare(int64_t m, int64_t n, DType dt, int64_t touched,
 // generic operator path (a constant: no crossover was measured).
 constexpr int64_t kMatrixFusedMinRows = 256;
 
-// EPSILON_HIP_FUSED_MATRIX (eps_set_option "fused_matrix"), read at every Init.
-enum MatrixRoute { kMatrixOff, kMatrixAuto, kMatrixPass, kMatrixWide };
-MatrixRoute FusedMatrixMode() {
-  const char* e = std::getenv("EPSILON_HIP_FUSED_MATRIX");
-  if (e == nullptr || std::strcmp(e, "auto") == 0) return kMatrixAuto;
-  if (std::strcmp(e, "0") == 0) return kMatrixOff;
-  if (std::strcmp(e, "pass") == 0) return kMatrixPass;
-  if (std::strcmp(e, "wide") == 0) return kMatrixWide;
-  EPS_FATAL("fused_matrix must be 0, pass, wide or auto, got " << e);
-}
-
 // ZERO-term problems (basis pursuit, hinge / deadzone + l1 in graph form) on the fused sweep
 // (ZeroRoute).  Below this many rows of the data matrix the solve keeps the
 // generic operator path (a constant: no crossover was measured).
 constexpr int64_t kZeroFusedMinRows = 256;
-// First word of a ZERO group's batch key (the lasso's begins with a pointer): the two kinds of
-// members never share a group.
-constexpr uint64_t kZeroGroupTag = 2;
-
-// EPSILON_HIP_FUSED_ZERO (eps_set_option "fused_zero"), read at every Init.
-bool FusedZeroAuto() {
-  const char* e = std::getenv("EPSILON_HIP_FUSED_ZERO");
-  if (e == nullptr || std::strcmp(e, "auto") == 0) return true;
-  if (std::strcmp(e, "0") == 0) return false;
-  EPS_FATAL("fused_zero must be 0 or auto, got " << e);
-}
 
 // Tall ZERO-term problems (more rows than columns: the order of the block LDL^T ends in x') on
-// the fused sweep (ZeroTallRoute, DESIGN.md 3.11 "Tall C").  Below this many columns of the data
-// matrix the solve keeps the generic operator path whatever the option says.
+// the fused sweep (ZeroRoute with `tall`, DESIGN.md 3.11 "Tall C").  Below this many columns of the
+// data matrix the solve keeps the generic operator path whatever the option says.
 constexpr int64_t kZeroTallMinCols = 256;
 // The floor of "auto": the smallest n of the 4n x n ladder of bench_zero.py at which the fused
 // sweep measured at least 1.05 x the generic one (5.5 x at n = 256, the first cell, and
 // no cell above it below 2.9 x); 0 would mean that no cell got there and "auto" is "0".
 constexpr int64_t kZeroTallAutoMinCols = 256;
 
-// EPSILON_HIP_FUSED_ZERO_TALL (eps_set_option "fused_zero_tall"), read at every Init.
-enum ZeroTallMode { kZeroTallOff, kZeroTallAuto, kZeroTallOn };
-ZeroTallMode FusedZeroTallMode() {
-  const char* e = std::getenv("EPSILON_HIP_FUSED_ZERO_TALL");
-  if (e == nullptr || std::strcmp(e, "auto") == 0) return kZeroTallAuto;
-  if (std::strcmp(e, "0") == 0) return kZeroTallOff;
-  if (std::strcmp(e, "1") == 0) return kZeroTallOn;
-  EPS_FATAL("fused_zero_tall must be 0, 1 or auto, got " << e);
+// The bits of a scalar, as a word of a batch key.
+uint64_t Bits(double v) {
+  uint64_t b;
+  std::memcpy(&b, &v, 8);
+  return b;
+}
+
+// Every rhs that is given lies on a 16-byte boundary (k::ReducePartialsBatch's `rhs_aligned`).
+bool RhsAligned(const std::vector<const k::LassoInstance*>& members) {
+  bool aligned = true;
+  for (const k::LassoInstance* s : members)
+    if (s->rhs.n > 0) aligned = aligned && reinterpret_cast<uintptr_t>(s->rhs.data()) % 16 == 0;
+  return aligned;
 }
 
 // One sweep of a panel of up to 64 f32 members on the wide route (kernels_fused_wide.hip): back
@@ -263,6 +280,62 @@ struct WideSweep {
 };
 
 // ---------------------------------------------------------------------------------------------------
+// What the routes on the batched pass share (the lasso route, the ZERO-term route)
+// ---------------------------------------------------------------------------------------------------
+// The shape, the forward vectors, the cached inverse and the pass's record of a route whose solves
+// can run as members of a group (RunFusedBatches), and the launches of a sweep of such members.
+struct BatchRoute : FusedRoute {
+  DType dt = F32;
+  int64_t m = 0, n = 0;  // the data matrix
+  int grid = 0;
+  DVec w, p, tpart;
+  InverseApply inv;          // (unused when whitened or wide)
+  bool whiten = false;       // the lasso route alone: the pass streams Ahat = X A, w holds X p (EnableWhiten)
+  k::LassoFusedArgs pass;    // the state vectors, and what the pass and a batch read of the rest
+  k::FusedResidency res;     // the matrix's share that stays in the Infinity Cache
+
+  // The key of the group a fresh solve on this route can join; false: it is solved by itself.
+  virtual bool BatchKey(const pb::SolverParams& params, std::vector<uint64_t>* key) const = 0;
+  // The record of the row kernel (a ZERO-term member with a z block); null: the partials go
+  // through the reduction.
+  virtual const k::ZeroRowsArgs* Rows() const { return nullptr; }
+  // The resident share of a sweep of `count` members on this route's matrix.
+  virtual k::FusedResidency Residency(int64_t count) const { return res; }
+
+  // What every key begins with: the pass's chain (a lasso member and a ZERO-term member never
+  // share a group), the data matrix, the shape, the dtype, the inverse with its packed copy, and
+  // the schedule.
+  std::vector<uint64_t> KeyHead(const DenseMatrixImpl& L, const DenseMatrixImpl& D,
+                                const pb::SolverParams& params) const {
+    return {static_cast<uint64_t>(pass.chain), reinterpret_cast<uintptr_t>(L.data().data()),
+            static_cast<uint64_t>(L.rows()), static_cast<uint64_t>(m), static_cast<uint64_t>(n),
+            static_cast<uint64_t>(dt), Bits(L.scale()), reinterpret_cast<uintptr_t>(D.data().data()),
+            Bits(D.scale()), reinterpret_cast<uintptr_t>(inv.packed.data()), inv.work.n > 0 ? 1u : 0u,
+            static_cast<uint64_t>(params.max_iterations), static_cast<uint64_t>(params.epoch_iterations)};
+  }
+
+  // One sweep of the `count` members of `table` (k::LassoBatchUpload) on this route's matrix: the
+  // batched pass per `width` members; the row kernel on `row_table` (k::ZeroRowsBatchUpload) for
+  // ZERO-term members with a z block, else the batched reduction of the partials; then - unless
+  // whitened: the reduction wrote every member's w_hat - one batched apply of the packed inverse
+  // (`work`: count * k::SymvWorkspace(m)), or `own_applies` without a packed copy (D.Apply / Symv:
+  // per member).
+  template <class Applies>
+  void BatchSweep(const DVec& table, const DVec& row_table, int count, const double* group_lam,
+                  const k::FusedResidency& share, bool rhs_aligned, const DVec& work, Applies own_applies) const {
+    const int width = k::LassoBatchWidth(m, n, dt, pass.chain);
+    for (int first = 0; first < count; first += width)
+      k::LassoBatchPass(m, n, pass.lda, pass.A, table, first, std::min(width, count - first), group_lam, share,
+                        pass.chain);
+    if (Rows() != nullptr) k::ZeroFusedRowsBatch(m, grid, Rows()->smooth, dt, row_table, count);
+    else k::ReducePartialsBatch(m, grid, table, count, dt, rhs_aligned);
+    if (whiten) return;
+    if (inv.packed.n > 0) k::SymvPackedBatch(m, inv.D->scale(), inv.packed, table, count, work);
+    else own_applies();
+  }
+};
+
+// ---------------------------------------------------------------------------------------------------
 // The lasso route: "least squares + separable threshold" (kernels_fused.hip)
 // ---------------------------------------------------------------------------------------------------
 // Recognised structure (the compiled lasso): two terms [SUM_SQUARE with a dense
@@ -270,26 +343,21 @@ struct WideSweep {
 // with a0 = 1 and no constant.  The sweep is then: one fused pass over A (back substitution of
 // this sweep, elementwise chain, forward substitution of the next sweep), a partial-sum
 // reduction (+ the all-reduce when sharded) and the apply of the cached inverse.
-struct LassoRoute final : FusedRoute {
+struct LassoRoute final : BatchRoute {
   LeastSquaresDesc ls;
   ScaledZoneDesc sz;
-  DType dt = F32;
   double a1 = 0;
-  int64_t m = 0, n = 0;
-  int grid = 0;
   int64_t slab = 0;  // rows of the cached inverse applied per rank (sharded runs)
   bool sharded = false;    // the least-squares variable is split over the ranks
   bool use_peer = false;   // exchanges ride in the sweep's kernels (peer window), not in RCCL
   bool peer_slab = false;  // ... and the inverse is applied by row slabs
-  DVec w, p, tpart, wpad, wslice;
-  InverseApply inv;          // (unused when whitened or wide)
+  bool replicated_apply = false;  // EPSILON_HIP_SHARDED_APPLY=replicated (Enable)
+  DVec wpad, wslice;
   DVec state_all, snapshot;  // x0, x1, y0, y1, u, y1prev in one buffer; its copy at a check
   DVec norm_work;            // partials + ticket of the one-launch residual norms
   int norm_slot = 0;
-  bool whiten = false;       // the pass streams Ahat = X A, w holds X p (EnableWhiten)
   double wscale = 1;         // c of Dinv_arg = c X^T X
   DVec X, Ahat, rhat;        // L^-1 of the inverse, X A (ld m), X rhs_arg (empty: no rhs)
-  k::LassoFusedArgs pass;    // the state vectors, and what the pass and a batch read of the rest (BuildPass)
   // matrix variable (n x cols under I_cols (x) A): its columns are members of the batched kernels
   int64_t cols = 1;
   bool group = false;      // the threshold is the group shrinkage of the rows (weight sz.lam)
@@ -299,18 +367,18 @@ struct LassoRoute final : FusedRoute {
   std::vector<k::LassoInstance> members;
   DVec table;              // their descriptors on the device (LassoBatchUpload)
   WideSweep ws;
-  k::FusedResidency res;   // the matrix's share that stays in the Infinity Cache (BuildPass)
 
-  // ... for a sweep of `count` members on this matrix: each has its partials (written and re-read:
-  // the same lines), six state vectors, p and w; the explicit apply reads the inverse.  Sharded and
-  // peer sweeps and the wide kernels stream everything; so does "auto" for more than one member
-  // (a batch, a matrix variable): the batched pass has not been timed with a share.
-  k::FusedResidency Residency(int64_t count) const {
+  // The matrix's resident share for a sweep of `count` members on it (`into`: the pass's record,
+  // BuildPass): each has its partials (written and re-read: the same lines), six state vectors, p
+  // and w; the explicit apply reads the inverse.  Sharded and peer sweeps and the wide kernels
+  // stream everything; so does "auto" for more than one member (a batch, a matrix variable): the
+  // batched pass has not been timed with a share.
+  k::FusedResidency Residency(int64_t count, k::LassoFusedArgs* into) const {
     if (sharded || use_peer || wide || ShardSpec::Get().active()) return k::FusedResidency();
-    const int64_t sz = dt == F32 ? 4 : 8;
-    const int64_t touched = (count * (static_cast<int64_t>(grid) * m + 6 * n + 2 * m) + (whiten ? 0 : m * m)) * sz;
-    return ResidentShare(m, n, dt, touched, /*auto_on=*/count == 1 && cols == 1);
+    return ResidentShare(m, n, dt, count * (static_cast<int64_t>(grid) * m + 6 * n + 2 * m) + (whiten ? 0 : m * m),
+                         /*auto_on=*/count == 1 && cols == 1, into);
   }
+  k::FusedResidency Residency(int64_t count) const override { return Residency(count, nullptr); }
 
   bool Enable(const MultiBlockParts& a) {
     if (FusedDisabled() || a.prox.size() != 2 || a.num_constraints != 1 || !a.b.data().empty()) return false;
@@ -319,7 +387,7 @@ struct LassoRoute final : FusedRoute {
     if (sh.active() && sh.consensus_terms()) return false;
     if (!a.prox[0]->DescribeLeastSquares(&ls)) return false;
     cols = ls.cols;
-    const MatrixRoute matrix_mode = cols > 1 ? FusedMatrixMode() : kMatrixAuto;
+    const int matrix_mode = cols > 1 ? ChoiceOptionNow("fused_matrix") : kMatrixAuto;
     if (cols > 1 && (matrix_mode == kMatrixOff || sh.active())) return false;
     if (!a.prox[1]->DescribeScaledZone(&sz)) {
       // group lasso: one group per row of the n x cols variable
@@ -386,8 +454,12 @@ struct LassoRoute final : FusedRoute {
       w = wpad.Slice(0, m);  // the gathered vector IS w (first m entries)
       // the inverse is applied by row slabs + all-gather from 3 ranks up; with 2 ranks the
       // symmetric apply of the whole matrix reads the same m^2/2 entries and needs no exchange
+      // EPSILON_HIP_SHARDED_APPLY=replicated: every rank applies the whole inverse instead (no
+      // all-gather; m^2 bytes per rank) - the cheaper form when the collective's latency exceeds
+      // the apply, to be decided on the machine
       const char* e = std::getenv("EPSILON_HIP_SHARDED_APPLY");
-      const bool want_slab = e ? e[0] != 'r' : G >= 3;
+      replicated_apply = e && e[0] == 'r';
+      const bool want_slab = e ? !replicated_apply : G >= 3;
       peer_slab = use_peer && want_slab && k::PeerSlabApplySupported(px->view(), m, slab, ls.Dinv_arg->data(), m);
     }
     if (!use_peer && !sh.active() && EnableWhiten()) {
@@ -406,7 +478,7 @@ struct LassoRoute final : FusedRoute {
 
   // Route of a matrix-variable solve: the batched pass (f32 / f64) or the wide
   // kernels (f32).  The group threshold needs all columns in one launch (pass) or one panel (wide).
-  bool ChooseMatrixRoute(MatrixRoute mode) {
+  bool ChooseMatrixRoute(int mode) {
     const DenseMatrixImpl& L = *ls.L_arg_var;
     const DenseMatrixImpl& D = *ls.Dinv_arg;
     if (m < kMatrixFusedMinRows || L.dtype() != dt || D.dtype() != dt) return false;
@@ -522,13 +594,6 @@ struct LassoRoute final : FusedRoute {
     if (ls.rhs_arg.n != 0 && !rhs_added) k::Axpby(p, 1.0, ls.rhs_arg, 1.0);
     const DenseMatrixImpl& D = *ls.Dinv_arg;
     Comm* comm = Runtime::Get().comm();
-    // EPSILON_HIP_SHARDED_APPLY=replicated: every rank applies the whole inverse instead (no
-    // all-gather; m^2 bytes per rank) - the cheaper form when the collective's latency exceeds
-    // the apply, to be decided on the machine
-    static const bool replicated_apply = [] {
-      const char* e = std::getenv("EPSILON_HIP_SHARDED_APPLY");
-      return e && e[0] == 'r';
-    }();
     if (sharded && comm->size() > 1 && !D.trans() && D.rows() == m && !replicated_apply) {
       // The cached inverse is replicated and symmetric: each rank applies only its slab of rows
       // (= columns, read contiguously) and the slices are all-gathered, so the m^2 bytes of the
@@ -584,9 +649,7 @@ struct LassoRoute final : FusedRoute {
     pass.n = n;
     pass.lda = whiten ? m : L.rows();
     pass.A = whiten ? Ahat : L.data();
-    res = Residency(cols);
-    pass.qfull = res.qfull;
-    pass.jcut = res.jcut;
+    res = Residency(cols, &pass);
     k::LassoInstance& s = pass.inst;
     s.w = w;
     s.tpart = tpart;
@@ -601,7 +664,6 @@ struct LassoRoute final : FusedRoute {
     // a matrix variable: column c is member c, the slices of `inst` at its offsets; the table is
     // uploaded here, so that a sweep makes no upload and no host synchronisation
     members.assign(static_cast<size_t>(cols), s);
-    rhs_aligned = true;
     for (int64_t c = 0; c < cols; ++c) {
       k::LassoInstance& mb = members[static_cast<size_t>(c)];
       auto col = [&](const DVec& v, int64_t len) { return v.n > 0 ? v.Slice(c * len, len) : v; };
@@ -614,10 +676,10 @@ struct LassoRoute final : FusedRoute {
                                        &k::LassoInstance::y0, &k::LassoInstance::y1, &k::LassoInstance::y1prev,
                                        &k::LassoInstance::alpha_vec, &k::LassoInstance::beta_vec})
         mb.*v = col(s.*v, n);
-      if (mb.rhs.n > 0) rhs_aligned = rhs_aligned && reinterpret_cast<uintptr_t>(mb.rhs.data()) % 16 == 0;
     }
     std::vector<const k::LassoInstance*> v;
     for (const auto& mb : members) v.push_back(&mb);
+    rhs_aligned = RhsAligned(v);
     k::LassoBatchUpload(v, dt, &table);
   }
 
@@ -636,11 +698,9 @@ struct LassoRoute final : FusedRoute {
       }
       return;
     }
-    const int width = k::LassoBatchWidth(m, n, dt);
-    for (int first = 0; first < K; first += width)
-      k::LassoBatchPass(m, n, pass.lda, pass.A, table, first, std::min(width, K - first), group_lam, res);
-    k::ReducePartialsBatch(m, grid, table, K, dt, rhs_aligned);
-    if (!whiten) ApplyInverseFixed();
+    BatchSweep(table, DVec(), K, group_lam, res, rhs_aligned, inv.work, [&] {
+      for (int64_t c = 0; c < cols; ++c) inv.Column(c).Apply();
+    });
   }
 
   void Sweep() override {
@@ -711,23 +771,13 @@ struct LassoRoute final : FusedRoute {
   // ---- batched solves (RunFusedBatches) ---------------------------------------------------------
   // The key of the group a fresh solve on this route can join (same data matrix, inverse, dtype,
   // shape and schedule); false: its pass is none the batched one mirrors.
-  bool BatchKey(const pb::SolverParams& params, std::vector<uint64_t>* key) const {
+  bool BatchKey(const pb::SolverParams& params, std::vector<uint64_t>* key) const override {
     if (use_peer || ShardSpec::Get().active()) return false;
     if (cols > 1) return false;  // a matrix variable is a batch of its own: it runs alone
     const DenseMatrixImpl& L = *ls.L_arg_var;
-    const DenseMatrixImpl& D = *ls.Dinv_arg;
     if (L.dtype() != dt || k::LassoBatchWidth(m, n, dt) == 0) return false;
-    auto bits = [](double v) {
-      uint64_t b;
-      std::memcpy(&b, &v, 8);
-      return b;
-    };
-    *key = {reinterpret_cast<uintptr_t>(L.data().data()), static_cast<uint64_t>(L.rows()),
-            static_cast<uint64_t>(m), static_cast<uint64_t>(n), static_cast<uint64_t>(dt),
-            bits(L.scale()), reinterpret_cast<uintptr_t>(D.data().data()), bits(D.scale()),
-            reinterpret_cast<uintptr_t>(inv.packed.data()), inv.work.n > 0 ? 1u : 0u,
-            static_cast<uint64_t>(params.max_iterations), static_cast<uint64_t>(params.epoch_iterations),
-            whiten ? 1u : 0u, reinterpret_cast<uintptr_t>(Ahat.data())};
+    *key = KeyHead(L, *ls.Dinv_arg, params);
+    key->insert(key->end(), {whiten ? 1u : 0u, reinterpret_cast<uintptr_t>(Ahat.data())});
     return true;
   }
 };
@@ -744,25 +794,39 @@ struct LassoRoute final : FusedRoute {
 // product), the row kernel (row chain, the partials' sum, r) - basis pursuit: the partials'
 // reduction alone - and the apply of the cached inverse.  The residual check is the driver's
 // generic one on views of the state.  One GPU, every dtype the compute type.
-struct ZeroRoute final : FusedRoute {
+//
+// Tall C (`tall`, DESIGN.md 3.11 "Tall C"): the same terms and ties with the ZERO term's block
+// LDL^T in the tall order: arg is a scalar pivot, x' the dense one.
+// Everything between C x' of sweep k and C^T f_arg of sweep k+1 is element-wise in the sample, so
+// the pass streams C^T (features x samples, one contiguous copy made at Init): per sample the
+// product with x', the z-side chain and the forward product (chain 3); then the x-side kernel (the
+// partials' sum, the chain on x, f_x) and the apply of Dinv(x').  A smooth z term is refused: its
+// Newton cannot sit in the per-column step of the pass.  No batched form: a member of a batch on
+// this route is solved by itself.
+struct ZeroRoute final : BatchRoute {
+  // u, var, copy, y of the separable term, y of the ZERO term, their previous values: the state of
+  // one consensus constraint
+  using Side = std::array<DVec, 7>;
+
   ZeroProjectionDesc zp;
   ScaledZoneDesc sx, sz;  // the separable terms on x and on z
+  bool tall = false;
   bool has_z = false;
-  int64_t m = 0, n = 0;
-  int grid = 0;
+  // m, n: C is m x n.  w, p, tpart: the dense pivot's vectors (tall: x' of the coming sweep, f_x and
+  // the pass's partials, n-long)
   DVec state_n, state_m;  // the slices of a side's state in one buffer (n: the x constraint's rows)
-  DVec w, p, tpart;
+  DVec CT;    // tall: C^T, n x m, ld n: shared through the solve's cache
   DVec head;  // a smooth z term: the row kernel's carried head (s, y_s, v of the coming sweep)
-  InverseApply inv;
-  k::LassoFusedArgs pass;
-  k::ZeroRowsArgs rows;
-  k::FusedResidency res;  // the matrix's share that stays in the Infinity Cache (none under "auto")
+  k::ZeroRowsArgs rows;  // the side that is not in the pass: z (tall: x)
 
-  bool Enable(const MultiBlockParts& a) {
+  // `tall_mode`: the option "fused_zero_tall"; under "auto" the measured floor applies
+  bool Enable(const MultiBlockParts& a, int tall_mode) {
     if (FusedDisabled() || ShardSpec::Get().active() || !a.b.data().empty()) return false;
     const int nc = a.num_constraints, N = static_cast<int>(a.prox.size());
     if (nc < 1 || nc > 2 || N != nc + 1) return false;
     if (!a.prox[N - 1]->DescribeZeroProjection(&zp)) return false;
+    tall = zp.tall;
+    if (tall && tall_mode == kZeroTallOff) return false;
     has_z = !zp.z_key.empty();
     if (has_z != (nc == 2)) return false;
     int ix = -1, iz = -1;  // positions of the separable terms among the objective terms
@@ -771,7 +835,7 @@ struct ZeroRoute final : FusedRoute {
       SmoothSeparableDesc sm;
       const bool smooth = !a.prox[i]->DescribeScaledZoneOffset(&d);
       if (smooth) {  // the scalar form is the zone's; its parameters are not read
-        if (!a.prox[i]->DescribeSmoothSeparable(&sm)) return false;
+        if (tall || !a.prox[i]->DescribeSmoothSeparable(&sm)) return false;  // (tall SUM_LOGISTIC: the generic path)
         d.var_key = sm.var_key;
         d.constraint_key = sm.constraint_key;
         d.Bs = sm.Bs;
@@ -792,14 +856,22 @@ struct ZeroRoute final : FusedRoute {
       }
     }
     if (ix < 0 || (has_z && iz < 0)) return false;
-    const DenseMatrixImpl& L = *zp.L_arg_x;
-    const DenseMatrixImpl& D = *zp.Dinv_arg;
-    const DType dt = a.data->dtype();
+    const DenseMatrixImpl& L = *zp.L;  // (tall: trans() set: its buffer is C, m x n)
+    const DenseMatrixImpl& D = *zp.Dinv;
+    dt = a.data->dtype();
     m = L.rows();
     n = L.cols();
-    if (m < kZeroFusedMinRows || L.dtype() != dt || D.dtype() != dt) return false;
-    if (D.rows() != m || D.cols() != m) return false;
-    if (!k::LassoFusedSupported(m, n, L.data(), L.rows())) return false;
+    const int64_t nw = tall ? n : m;  // the order of the dense pivot
+    if (L.dtype() != dt || D.dtype() != dt || D.rows() != nw || D.cols() != nw) return false;
+    if (tall) {
+      if (n < kZeroTallMinCols || m <= n) return false;
+      if (tall_mode == kZeroTallAuto && (kZeroTallAutoMinCols == 0 || n < kZeroTallAutoMinCols)) return false;
+      // the pass's shape conditions, on the copy's geometry, before the copy is made
+      const int64_t chunk = dt == F32 ? 4 : 2;
+      if (n % chunk != 0 || n > (dt == F32 ? 20 : 10) * 1024) return false;
+    } else {
+      if (m < kZeroFusedMinRows || !k::LassoFusedSupported(m, n, L.data(), L.rows())) return false;
+    }
     // the consensus constraints: copy + a var = 0, nothing else in their rows or columns
     if (static_cast<int>(a.A.data().size()) != 2 * nc) return false;
     double ax = 0, az = 0;  // constraint maps of x and z (their copies': 1)
@@ -813,6 +885,7 @@ struct ZeroRoute final : FusedRoute {
     auto fits = [&](const DVec& v, int64_t len) { return v.n == 0 || (v.n == len && v.dt == dt); };
     if (!fits(zp.rhs_arg, m) || !fits(sx.alpha_vec, n) || !fits(sx.beta_vec, n)) return false;
     if (!fits(sz.alpha_vec, m) || !fits(sz.beta_vec, m) || !fits(sz.g, m)) return false;
+    if (tall && !TransposedCopy(a.shared_cache)) return false;
 
     // state: u, var, copy, y of the separable term, y of the ZERO term, their previous values -
     // per constraint row, taken over from the generic containers (warm start)
@@ -822,87 +895,135 @@ struct ZeroRoute final : FusedRoute {
                     DVec* all) {
       const int64_t pad = (len + 63) / 64 * 64;
       *all = DVec::Zeros(7 * pad, dt);
-      const size_t first = views.size();
-      views.insert(views.end(), {{&a.u, ck},
-                                 {&a.x[term], var},
-                                 {&a.x[N - 1], copy},
-                                 {&a.y[term], ck},
-                                 {&a.y[N - 1], ck},
-                                 {&a.y_prev[term], ck, DVec(), false},
-                                 {&a.y_prev[N - 1], ck, DVec(), false}});
-      for (int q = 0; q < 7; ++q) views[first + q].v = all->Slice(q * pad, len);
-      return &views[first];
-    };
-    grid = k::LassoFusedGrid(m, n, dt);
-    w = DVec::Zeros(m, dt);
-    p = DVec::Zeros(m, dt);
-    tpart = DVec::Empty(static_cast<int64_t>(grid) * m, dt);
-    inv.Init(zp.Dinv_arg, m, p, w, a.shared_cache);
-    {
-      const StateSlice* sn = side(n, zp.x_constraint_key, ix, sx.var_key, zp.x_key, &state_n);
-      pass.m = m;
-      pass.n = n;
-      pass.lda = L.rows();
-      pass.A = L.data();
-      pass.chain = 2;
-      pass.e0 = sn[6].v;
-      pass.inst.e0 = sn[6].v;  // (a batched member carries it in its record)
-      // beside the matrix the sweep touches the partials (the rows kernel re-reads them), the seven
-      // state vectors of either side, p, w, and the inverse
-      const int64_t sz = dt == F32 ? 4 : 8;
-      res = ResidentShare(m, n, dt, (static_cast<int64_t>(grid) * m + 7 * (n + m) + 2 * m + m * m) * sz,
-                          /*auto_on=*/false);
-      pass.qfull = res.qfull;
-      pass.jcut = res.jcut;
-      k::LassoInstance& s = pass.inst;
-      s.w = w;
-      s.tpart = tpart;
-      s.p = p;
-      s.rhs = zp.rhs_arg;
-      s.u = sn[0].v;
-      s.x1 = sn[1].v;
-      s.x0 = sn[2].v;
-      s.y1 = sn[3].v;
-      s.y0 = sn[4].v;
-      s.y1prev = sn[5].v;
-      s.kappa = s.pkappa = -L.scale();
-      SetThreshold(&s, sx, ax);
-    }
-    if (has_z) {
-      const StateSlice* sm = side(m, zp.z_constraint_key, iz, sz.var_key, zp.z_key, &state_m);
-      rows.m = m;
-      rows.nparts = grid;
-      rows.w = w;
-      rows.tpart = tpart;
-      rows.r = p;
-      rows.rhs = zp.rhs_arg;
-      rows.g = sz.g;
-      rows.u = sm[0].v;
-      rows.z = sm[1].v;
-      rows.zq = sm[2].v;
-      rows.yz = sm[3].v;
-      rows.yq = sm[4].v;
-      rows.yzprev = sm[5].v;
-      rows.yqprev = sm[6].v;
-      rows.e = zp.e;
-      rows.pkappa = -L.scale();
-      SetThreshold(&rows, sz, az);
-      if (rows.smooth) {
-        head = DVec::Zeros(3 * m, dt);
-        rows.hs = head.Slice(0, m);
-        rows.hys = head.Slice(m, m);
-        rows.hv = head.Slice(2 * m, m);
+      const std::vector<StateSlice> seven = {{&a.u, ck},
+                                             {&a.x[term], var},
+                                             {&a.x[N - 1], copy},
+                                             {&a.y[term], ck},
+                                             {&a.y[N - 1], ck},
+                                             {&a.y_prev[term], ck, DVec(), false},
+                                             {&a.y_prev[N - 1], ck, DVec(), false}};
+      Side s;
+      for (int q = 0; q < 7; ++q) {
+        s[q] = all->Slice(q * pad, len);
+        views.push_back(seven[q]);
+        views.back().v = s[q];
       }
-    }
+      return s;
+    };
+    // (tall: the pass's register-held dimension is n, its streamed columns are the m samples)
+    grid = tall ? k::LassoFusedGrid(n, m, dt) : k::LassoFusedGrid(m, n, dt);
+    w = DVec::Zeros(nw, dt);
+    p = DVec::Zeros(nw, dt);
+    tpart = DVec::Empty(static_cast<int64_t>(grid) * nw, dt);
+    inv.Init(zp.Dinv, nw, p, w, a.shared_cache);
+    const Side sn = side(n, zp.x_constraint_key, ix, sx.var_key, zp.x_key, &state_n);
+    const Side sm = has_z ? side(m, zp.z_constraint_key, iz, sz.var_key, zp.z_key, &state_m) : Side();
+    if (tall) FillTall(sn, ax, sm, az);
+    else FillFat(sn, ax, sm, az);
+    // beside the matrix the sweep touches the partials (the rows kernel re-reads them), the seven
+    // state vectors of either side, p, w, and the inverse
+    res = ResidentShare(pass.m, pass.n, dt, static_cast<int64_t>(grid) * nw + 7 * (n + m) + 2 * nw + nw * nw,
+                        /*auto_on=*/false, &pass);
     AdoptState(views, Homes(a));
     if (rows.smooth) k::ZeroSmoothHead(rows);
     ForwardFromState(a);
     return true;
   }
 
-  // w of the first sweep from the current state, with the generic operators: the sweep up to the
-  // ZERO prox's input v (on copies: the state is not touched), then the forward substitution
-  // r = (rhs - e v_z) - L(arg, x') v_x and the inverse apply.
+  // Tall: C^T as the pass streams it: one untransposed contiguous copy of the factor's operand
+  // (unscaled: the scale stays in kappa), shared like the packed inverse
+  bool TransposedCopy(OpCache* shared) {
+    const DenseMatrixImpl& L = *zp.L;
+    uint64_t key = 0;
+    if (shared != nullptr) {
+      key = HashCombine(HashCombine(HashCombine(reinterpret_cast<uintptr_t>(L.data().data()), 0x7a11c7), L.id()),
+                        static_cast<uint64_t>(m * n));
+      if (auto hit = shared->Find(key)) CT = hit->data();
+    }
+    if (CT.n == 0) {
+      CT = DVec::Empty(m * n, dt);
+      k::MatCopy(true, n, m, 1.0, L.data(), L.rows(), CT);
+      if (key) shared->Put(key, std::make_shared<DenseMatrixImpl>(CT, n, m, false, 1.0, key));
+    }
+    return k::LassoFusedSupported(n, m, CT, n);
+  }
+
+  // The pass's instance from the side it runs (chains 2 and 3 read the arrays alike,
+  // k::LassoFusedArgs), the row kernel's record from the other side.
+  void PassSide(int chain, const Side& s, const ScaledZoneDesc& zone, double a1) {
+    pass.chain = chain;
+    pass.e0 = s[6];
+    k::LassoInstance& i = pass.inst;
+    i.w = w;
+    i.tpart = tpart;
+    i.p = p;
+    i.u = s[0];
+    i.x1 = s[1];
+    i.x0 = s[2];
+    i.y1 = s[3];
+    i.y0 = s[4];
+    i.y1prev = s[5];
+    i.e0 = s[6];  // (a batched member carries it in its record)
+    i.kappa = i.pkappa = -zp.L->scale();
+    SetThreshold(&i, zone, a1);
+  }
+  void RowsSide(const Side& s, const ScaledZoneDesc& zone, double a1) {
+    rows.m = w.n;
+    rows.nparts = grid;
+    rows.w = w;
+    rows.tpart = tpart;
+    rows.r = p;
+    rows.u = s[0];
+    rows.z = s[1];
+    rows.zq = s[2];
+    rows.yz = s[3];
+    rows.yq = s[4];
+    rows.yzprev = s[5];
+    rows.yqprev = s[6];
+    rows.pkappa = -zp.L->scale();
+    SetThreshold(&rows, zone, a1);
+  }
+
+  // Fat: the x side into the pass (chain 2), the z side into the rows.
+  void FillFat(const Side& sn, double ax, const Side& sm, double az) {
+    pass.m = m;
+    pass.n = n;
+    pass.lda = zp.L->rows();
+    pass.A = zp.L->data();
+    PassSide(2, sn, sx, ax);
+    pass.inst.rhs = zp.rhs_arg;
+    if (!has_z) return;
+    RowsSide(sm, sz, az);
+    rows.rhs = zp.rhs_arg;
+    rows.g = sz.g;
+    rows.e = zp.e;
+    if (rows.smooth) {
+      head = DVec::Zeros(3 * m, dt);
+      rows.hs = head.Slice(0, m);
+      rows.hys = head.Slice(m, m);
+      rows.hv = head.Slice(2 * m, m);
+    }
+  }
+
+  // Tall: the z side into the pass (chain 3) over the transposed copy, the x side into the rows.
+  void FillTall(const Side& sn, double ax, const Side& sm, double az) {
+    pass.m = n;
+    pass.n = m;
+    pass.lda = n;
+    pass.A = CT;
+    PassSide(3, sm, sz, az);
+    pass.zg = sz.g;
+    pass.zrhs = zp.rhs_arg;
+    pass.ke = -zp.e;
+    pass.dinv = zp.dinv_arg;
+    RowsSide(sn, sx, ax);
+    rows.tall = true;
+  }
+
+  // The dense pivot's vector of the first sweep from the current state, with the generic
+  // operators: the sweep up to the ZERO prox's input v (on copies: the state is not touched), then
+  // the forward substitution and the inverse apply.  Fat: r = (rhs - e v_z) - L(arg, x') v_x.
+  // Tall: f_arg = rhs - e v_z, f_x = v_x - L(x', arg) f_arg.
   void ForwardFromState(const MultiBlockParts& a) {
     const size_t N = a.prox.size();
     BlockVector v = a.u;
@@ -912,10 +1033,17 @@ struct ZeroRoute final : FusedRoute {
       v -= a.A * a.prox[i]->Apply(v);
     }
     v += a.y[N - 1];
-    if (zp.rhs_arg.n != 0) k::Copy(p, zp.rhs_arg);
-    else k::Fill(p, 0.0);
-    if (has_z) k::Axpby(p, -zp.e, v(zp.z_constraint_key), 1.0);
-    zp.L_arg_x->Apply(-1.0, v(zp.x_constraint_key), 1.0, p);
+    if (tall) {
+      DVec farg = zp.rhs_arg.n != 0 ? zp.rhs_arg.Clone() : DVec::Zeros(m, dt);
+      k::Axpby(farg, -zp.e, v(zp.z_constraint_key), 1.0);
+      k::Copy(p, v(zp.x_constraint_key));
+      zp.L->Apply(-1.0, farg, 1.0, p);
+    } else {
+      if (zp.rhs_arg.n != 0) k::Copy(p, zp.rhs_arg);
+      else k::Fill(p, 0.0);
+      if (has_z) k::Axpby(p, -zp.e, v(zp.z_constraint_key), 1.0);
+      zp.L->Apply(-1.0, v(zp.x_constraint_key), 1.0, p);
+    }
     inv.Apply();
   }
 
@@ -929,219 +1057,17 @@ struct ZeroRoute final : FusedRoute {
   }
 
   // ---- batched solves (RunFusedBatches) ---------------------------------------------------------
+  const k::ZeroRowsArgs* Rows() const override { return has_z ? &rows : nullptr; }
   // The key of the group a fresh solve on this route can join: the same data matrix, the same
   // inverse (and packed copy), the same e and z block, the same form of the row kernel and the
   // same schedule.  Everything else - the zones' parameters and vectors, the offset g, the rhs -
-  // is per member, so a hinge and a deadzone member on one matrix share a group.  false: the
-  // single pass takes a form the batched one does not mirror (512-thread workgroups).
-  bool BatchKey(const pb::SolverParams& params, std::vector<uint64_t>* key) const {
-    const DenseMatrixImpl& L = *zp.L_arg_x;
-    const DenseMatrixImpl& D = *zp.Dinv_arg;
-    const DType dt = w.dt;
-    if (k::LassoBatchWidth(m, n, dt, 2) == 0) return false;
-    auto bits = [](double v) {
-      uint64_t b;
-      std::memcpy(&b, &v, 8);
-      return b;
-    };
-    *key = {kZeroGroupTag, reinterpret_cast<uintptr_t>(L.data().data()), static_cast<uint64_t>(L.rows()),
-            static_cast<uint64_t>(m), static_cast<uint64_t>(n), static_cast<uint64_t>(dt),
-            bits(L.scale()), reinterpret_cast<uintptr_t>(D.data().data()), bits(D.scale()),
-            reinterpret_cast<uintptr_t>(inv.packed.data()), inv.work.n > 0 ? 1u : 0u, bits(zp.e),
-            has_z ? 1u : 0u, rows.smooth ? 1u : 0u, static_cast<uint64_t>(params.max_iterations),
-            static_cast<uint64_t>(params.epoch_iterations)};
+  // is per member, so a hinge and a deadzone member on one matrix share a group.  false: tall, or
+  // the single pass takes a form the batched one does not mirror (512-thread workgroups).
+  bool BatchKey(const pb::SolverParams& params, std::vector<uint64_t>* key) const override {
+    if (tall || k::LassoBatchWidth(m, n, dt, 2) == 0) return false;
+    *key = KeyHead(*zp.L, *zp.Dinv, params);
+    key->insert(key->end(), {Bits(zp.e), has_z ? 1u : 0u, rows.smooth ? 1u : 0u});
     return true;
-  }
-};
-
-// ---------------------------------------------------------------------------------------------------
-// The ZERO-term route for tall C ("Tall C")
-// ---------------------------------------------------------------------------------------------------
-// Recognised structure: ZeroRoute's terms and consensus ties, with the ZERO term's block LDL^T in
-// the tall order (ZeroProx::DescribeZeroTallProjection): arg is a scalar pivot, x' the dense one.
-// Everything between C x' of sweep k and C^T f_arg of sweep k+1 is element-wise in the sample, so
-// the pass streams C^T (features x samples, one contiguous copy made at Init): per sample the
-// product with x', the z-side chain and the forward product (chain 3); then the x-side kernel (the
-// partials' sum, the chain on x, f_x) and the apply of Dinv(x').  A smooth z term is refused: its
-// Newton cannot sit in the per-column step of the pass.  No batched form: a member of a batch on
-// this route is solved by itself.
-struct ZeroTallRoute final : FusedRoute {
-  ZeroTallProjectionDesc zp;
-  ScaledZoneDesc sx, sz;
-  int64_t m = 0, n = 0;  // C is m x n, m > n
-  int grid = 0;
-  DVec state_n, state_m;
-  DVec CT;  // C^T, n x m, ld n: shared through the solve's cache
-  DVec w, p, tpart;  // x' of the coming sweep, f_x, the pass's partials (n-long vectors)
-  InverseApply inv;
-  k::LassoFusedArgs pass;
-  k::ZeroRowsArgs cols;
-  k::FusedResidency res;
-  bool auto_mode = false;  // the option is "auto": the measured floor applies
-
-  bool Enable(const MultiBlockParts& a) {
-    if (FusedDisabled() || ShardSpec::Get().active() || !a.b.data().empty()) return false;
-    const int N = static_cast<int>(a.prox.size());
-    if (a.num_constraints != 2 || N != 3) return false;
-    if (!a.prox[N - 1]->DescribeZeroTallProjection(&zp)) return false;
-    int ix = -1, iz = -1;
-    for (int i = 0; i + 1 < N; ++i) {
-      ScaledZoneDesc d;
-      if (!a.prox[i]->DescribeScaledZoneOffset(&d)) return false;  // (SUM_LOGISTIC: the generic path)
-      if (ix < 0 && d.constraint_key == zp.x_constraint_key && d.g.n == 0) {
-        sx = d;
-        ix = i;
-      } else if (iz < 0 && d.constraint_key == zp.z_constraint_key) {
-        sz = d;
-        iz = i;
-      } else {
-        return false;
-      }
-    }
-    if (ix < 0 || iz < 0) return false;
-    const DenseMatrixImpl& L = *zp.L_x_arg;  // trans() set: its buffer is C, m x n
-    const DenseMatrixImpl& D = *zp.Dinv_x;
-    const DType dt = a.data->dtype();
-    m = L.rows();
-    n = L.cols();
-    if (n < kZeroTallMinCols || m <= n || L.dtype() != dt || D.dtype() != dt) return false;
-    if (auto_mode && (kZeroTallAutoMinCols == 0 || n < kZeroTallAutoMinCols)) return false;
-    if (D.rows() != n || D.cols() != n) return false;
-    // the pass's shape conditions, on the copy's geometry, before the copy is made
-    const int64_t chunk = dt == F32 ? 4 : 2;
-    if (n % chunk != 0 || n > (dt == F32 ? 20 : 10) * 1024) return false;
-    if (static_cast<int>(a.A.data().size()) != 4) return false;
-    double ax = 0, az = 0;
-    auto tie = [&](const std::string& ck, const std::string& copy, const std::string& var, int64_t len, double* av) {
-      double a0 = 0;
-      return ConsensusTie(a.A, ck, copy, var, len, &a0, av) && a0 == 1.0 && a.A.col(copy).size() == 1 &&
-             a.A.col(var).size() == 1;
-    };
-    if (!tie(zp.x_constraint_key, zp.x_key, sx.var_key, n, &ax)) return false;
-    if (!tie(zp.z_constraint_key, zp.z_key, sz.var_key, m, &az)) return false;
-    auto fits = [&](const DVec& v, int64_t len) { return v.n == 0 || (v.n == len && v.dt == dt); };
-    if (!fits(zp.rhs_arg, m) || !fits(sx.alpha_vec, n) || !fits(sx.beta_vec, n)) return false;
-    if (!fits(sz.alpha_vec, m) || !fits(sz.beta_vec, m) || !fits(sz.g, m)) return false;
-
-    // C^T as the pass streams it: one untransposed contiguous copy of the factor's operand
-    // (unscaled: the scale stays in kappa), shared like the packed inverse
-    uint64_t key = 0;
-    if (a.shared_cache != nullptr) {
-      key = HashCombine(HashCombine(HashCombine(reinterpret_cast<uintptr_t>(L.data().data()), 0x7a11c7), L.id()),
-                        static_cast<uint64_t>(m * n));
-      if (auto hit = a.shared_cache->Find(key)) CT = hit->data();
-    }
-    if (CT.n == 0) {
-      CT = DVec::Empty(m * n, dt);
-      k::MatCopy(true, n, m, 1.0, L.data(), L.rows(), CT);
-      if (key) a.shared_cache->Put(key, std::make_shared<DenseMatrixImpl>(CT, n, m, false, 1.0, key));
-    }
-    if (!k::LassoFusedSupported(n, m, CT, n)) return false;
-
-    a.y_prev.resize(N);
-    std::vector<StateSlice> views;
-    auto side = [&](int64_t len, const std::string& ck, int term, const std::string& var, const std::string& copy,
-                    DVec* all) {
-      const int64_t pad = (len + 63) / 64 * 64;
-      *all = DVec::Zeros(7 * pad, dt);
-      const size_t first = views.size();
-      views.insert(views.end(), {{&a.u, ck},
-                                 {&a.x[term], var},
-                                 {&a.x[N - 1], copy},
-                                 {&a.y[term], ck},
-                                 {&a.y[N - 1], ck},
-                                 {&a.y_prev[term], ck, DVec(), false},
-                                 {&a.y_prev[N - 1], ck, DVec(), false}});
-      for (int q = 0; q < 7; ++q) views[first + q].v = all->Slice(q * pad, len);
-      return first;
-    };
-    // the pass's register-held dimension is n, its streamed columns are the m samples
-    grid = k::LassoFusedGrid(n, m, dt);
-    w = DVec::Zeros(n, dt);
-    p = DVec::Zeros(n, dt);
-    tpart = DVec::Empty(static_cast<int64_t>(grid) * n, dt);
-    inv.Init(zp.Dinv_x, n, p, w, a.shared_cache);
-    const size_t fn = side(n, zp.x_constraint_key, ix, sx.var_key, zp.x_key, &state_n);
-    const size_t fm = side(m, zp.z_constraint_key, iz, sz.var_key, zp.z_key, &state_m);
-    {
-      const StateSlice* sm = &views[fm];
-      pass.m = n;
-      pass.n = m;
-      pass.lda = n;
-      pass.A = CT;
-      pass.chain = 3;
-      pass.e0 = sm[6].v;
-      pass.zg = sz.g;
-      pass.zrhs = zp.rhs_arg;
-      pass.ke = -zp.e;
-      pass.dinv = zp.dinv_arg;
-      // beside the matrix the sweep touches the partials, the seven state vectors of either side,
-      // p, w and the inverse
-      const int64_t sz_b = dt == F32 ? 4 : 8;
-      res = ResidentShare(n, m, dt, (static_cast<int64_t>(grid) * n + 7 * (n + m) + 2 * n + n * n) * sz_b,
-                          /*auto_on=*/false);
-      pass.qfull = res.qfull;
-      pass.jcut = res.jcut;
-      k::LassoInstance& s = pass.inst;
-      s.w = w;
-      s.tpart = tpart;
-      s.p = p;
-      s.u = sm[0].v;
-      s.x1 = sm[1].v;
-      s.x0 = sm[2].v;
-      s.y1 = sm[3].v;
-      s.y0 = sm[4].v;
-      s.y1prev = sm[5].v;
-      s.e0 = sm[6].v;
-      s.kappa = s.pkappa = -L.scale();
-      SetThreshold(&s, sz, az);
-    }
-    {
-      const StateSlice* sn = &views[fn];
-      cols.tall = true;
-      cols.m = n;
-      cols.nparts = grid;
-      cols.w = w;
-      cols.tpart = tpart;
-      cols.r = p;
-      cols.u = sn[0].v;
-      cols.z = sn[1].v;
-      cols.zq = sn[2].v;
-      cols.yz = sn[3].v;
-      cols.yq = sn[4].v;
-      cols.yzprev = sn[5].v;
-      cols.yqprev = sn[6].v;
-      cols.pkappa = -L.scale();
-      SetThreshold(&cols, sx, ax);
-    }
-    AdoptState(views, Homes(a));
-    ForwardFromState(a);
-    return true;
-  }
-
-  // x' of the first sweep from the current state, with the generic operators: the sweep up to the
-  // ZERO prox's input v (on copies: the state is not touched), then the forward substitution
-  // f_arg = rhs - e v_z, f_x = v_x - L(x', arg) f_arg and the apply of Dinv(x').
-  void ForwardFromState(const MultiBlockParts& a) {
-    const size_t N = a.prox.size();
-    BlockVector v = a.u;
-    for (size_t i = 0; i < N; ++i) v -= a.y[i];
-    for (size_t i = 0; i + 1 < N; ++i) {
-      v += a.y[i];
-      v -= a.A * a.prox[i]->Apply(v);
-    }
-    v += a.y[N - 1];
-    DVec farg = zp.rhs_arg.n != 0 ? zp.rhs_arg.Clone() : DVec::Zeros(m, w.dt);
-    k::Axpby(farg, -zp.e, v(zp.z_constraint_key), 1.0);
-    k::Copy(p, v(zp.x_constraint_key));
-    zp.L_x_arg->Apply(-1.0, farg, 1.0, p);
-    inv.Apply();
-  }
-
-  void Sweep() override {
-    k::LassoFusedPass(pass);
-    k::ZeroFusedRows(cols);
-    inv.Apply();
   }
 };
 
@@ -1201,13 +1127,8 @@ struct TwoBlockRoute final : FusedRoute {
     pass.A = L.data();
     pass.chain = 1;
     pass.a0 = a0;
-    {  // beside the matrix: the partials, eight state vectors, p, w, and the inverse
-      const int64_t sz = dt == F32 ? 4 : 8;
-      const k::FusedResidency res =
-          ResidentShare(m, n, dt, (static_cast<int64_t>(grid) * m + 8 * n + 2 * m + m * m) * sz, /*auto_on=*/false);
-      pass.qfull = res.qfull;
-      pass.jcut = res.jcut;
-    }
+    // beside the matrix: the partials, eight state vectors, p, w, and the inverse
+    ResidentShare(m, n, dt, static_cast<int64_t>(grid) * m + 8 * n + 2 * m + m * m, /*auto_on=*/false, &pass);
     pass.e0 = u1;
     pass.e1 = z1p;
     k::LassoInstance& s = pass.inst;
@@ -1240,10 +1161,10 @@ struct TwoBlockRoute final : FusedRoute {
   }
 };
 
-template <class Route, class Parts>
-std::unique_ptr<FusedRoute> Recognise(const Parts& parts) {
+template <class Route, class Parts, class... Options>
+std::unique_ptr<FusedRoute> Recognise(const Parts& parts, Options... options) {
   std::unique_ptr<Route> r(new Route);
-  if (!r->Enable(parts)) return nullptr;
+  if (!r->Enable(parts, options...)) return nullptr;
   return std::unique_ptr<FusedRoute>(std::move(r));
 }
 
@@ -1262,17 +1183,22 @@ int64_t ParseFusedResident(const char* value) {
   return kb * 1024;
 }
 
+int ParseChoiceOption(const char* name, const char* value) {
+  for (const ChoiceOption& o : kChoiceOptions) {
+    if (std::strcmp(o.name, name) != 0) continue;
+    for (int i = 0; o.words[i] != nullptr; ++i)
+      if (std::strcmp(o.words[i], value) == 0) return i;
+    EPS_FATAL(o.error << value);
+  }
+  EPS_FATAL("unknown option " << name);
+}
+
 std::unique_ptr<FusedRoute> RecogniseMultiBlockRoute(const MultiBlockParts& parts) {
-  const bool zero = FusedZeroAuto();  // (read first: a bad value is an error whatever the problem)
-  const ZeroTallMode tall = FusedZeroTallMode();
+  const bool zero = ChoiceOptionNow("fused_zero") != 0;  // (read first: a bad value is an error whatever the problem)
+  const int tall = ChoiceOptionNow("fused_zero_tall");
   if (auto r = Recognise<LassoRoute>(parts)) return r;
   if (!zero) return nullptr;
-  if (auto r = Recognise<ZeroRoute>(parts)) return r;
-  if (tall == kZeroTallOff) return nullptr;
-  std::unique_ptr<ZeroTallRoute> r(new ZeroTallRoute);
-  r->auto_mode = tall == kZeroTallAuto;
-  if (!r->Enable(parts)) return nullptr;
-  return std::unique_ptr<FusedRoute>(std::move(r));
+  return Recognise<ZeroRoute>(parts, tall);  // fat, then tall
 }
 
 std::unique_ptr<FusedRoute> RecogniseTwoBlockRoute(const TwoBlockParts& parts) {
@@ -1285,13 +1211,11 @@ std::unique_ptr<FusedRoute> RecogniseTwoBlockRoute(const TwoBlockParts& parts) {
 // ---------------------------------------------------------------------------------------------------
 namespace {
 
-// A member of a group: its solver and its route, a LassoRoute or a ZeroRoute - every member of a
-// group has the lead's kind (the keys differ), and the group's runner knows which.
+// A member of a group: its solver and its route.  Every member of a group has the lead's kind:
+// the keys begin with the pass's chain.
 struct BatchMember {
   Solver* solver;
-  FusedRoute* route;
-  const LassoRoute& lasso() const { return *static_cast<const LassoRoute*>(route); }
-  const ZeroRoute& zero() const { return *static_cast<const ZeroRoute*>(route); }
+  BatchRoute* route;
 };
 using Group = std::vector<BatchMember>;
 
@@ -1331,73 +1255,23 @@ void RunGroupSchedule(const Group& g, double t0, std::vector<int>* active, Sweep
   for (const BatchMember& b : g) b.solver->BatchAddLoopTime(loop);
 }
 
-void RunFusedGroup(const Group& g) {
+// A group on the batched pass: per sweep one batched pass per `width` active members, ONE launch
+// for all of them that sums the partials - the row kernel for ZERO-term members (DESIGN.md 3.11;
+// basis pursuit, which has no z block, and the lasso: one batched reduction of the partials with
+// the rhs folded in) - and one batched apply of the packed inverse (below m = 1024: each member's
+// own apply; whitened: none).  Each launch does per member what the member's own sweep does, so
+// its iterates are the single solve's bit for bit; a ZERO-term member's residual check is the
+// driver's generic one, at the sweeps of the member's own Run().
+void RunPassGroup(const Group& g) {
   const double t0 = Now();
-  const LassoRoute& lead = g[0].lasso();
-  const DType dt = lead.dt;
-  SetCurrentDType(dt);
-  const int64_t m = lead.m, n = lead.n;
-  const int width = k::LassoBatchWidth(m, n, dt);
-  const DVec& P = lead.inv.packed;
-  bool rhs_aligned = true;
-  for (const BatchMember& b : g) {
-    const DVec& rhs = b.lasso().pass.inst.rhs;
-    if (rhs.n > 0) rhs_aligned = rhs_aligned && reinterpret_cast<uintptr_t>(rhs.data()) % 16 == 0;
-  }
+  const BatchRoute& lead = *g[0].route;
+  SetCurrentDType(lead.dt);
   const int K = static_cast<int>(g.size());
-  DVec symv_work = P.n > 0 ? DVec::Empty(K * k::SymvWorkspace(m), dt) : DVec();
-  const k::FusedResidency res = lead.Residency(K);
-
-  std::vector<int> active(K);
-  for (int i = 0; i < K; ++i) active[i] = i;
-  DVec table;
-  auto upload = [&] {
-    std::vector<const k::LassoInstance*> v;
-    for (int i : active) v.push_back(&g[i].lasso().pass.inst);
-    k::LassoBatchUpload(v, dt, &table);
-  };
-  upload();
-  auto sweep = [&] {
-    const int na = static_cast<int>(active.size());
-    for (int first = 0; first < na; first += width)
-      k::LassoBatchPass(m, n, lead.pass.lda, lead.pass.A, table, first, std::min(width, na - first), nullptr, res);
-    k::ReducePartialsBatch(m, lead.grid, table, na, dt, rhs_aligned);
-    if (lead.whiten) {
-      // the reduction wrote every member's w_hat: no inverse apply
-    } else if (P.n > 0) {
-      k::SymvPackedBatch(m, lead.inv.D->scale(), P, table, na, symv_work);
-    } else {
-      for (int i : active) g[i].lasso().inv.Apply();  // D.Apply / Symv: per instance
-    }
-  };
-  // the stopped ones are frozen: drop their descriptors
-  RunGroupSchedule(g, t0, &active, sweep, [&](const std::vector<int>&) {
-    if (!active.empty()) upload();
-  });
-}
-
-// A group of ZERO-term members: per sweep one batched pass with the ZERO column
-// chain per `width` active members, ONE row launch for all of them (basis pursuit, which has no z
-// block: one batched reduction of the partials with the rhs folded in) and one batched apply of the
-// packed inverse (below m = 1024: each member's own apply).  Each launch does per member what the
-// member's own sweep does, so its iterates are the single solve's bit for bit; the residual check
-// is the driver's generic one, at the sweeps of the member's own Run().
-void RunZeroGroup(const Group& g) {
-  const double t0 = Now();
-  const ZeroRoute& lead = g[0].zero();
-  const DType dt = lead.w.dt;
-  SetCurrentDType(dt);
-  const int64_t m = lead.m, n = lead.n;
-  const int width = k::LassoBatchWidth(m, n, dt, 2);
-  const DVec& P = lead.inv.packed;
-  bool rhs_aligned = true;
-  for (const BatchMember& b : g) {
-    const DVec& rhs = b.zero().pass.inst.rhs;
-    if (rhs.n > 0) rhs_aligned = rhs_aligned && reinterpret_cast<uintptr_t>(rhs.data()) % 16 == 0;
-  }
-  const int K = static_cast<int>(g.size());
-  DVec symv_work = P.n > 0 ? DVec::Empty(K * k::SymvWorkspace(m), dt) : DVec();
-  const k::FusedResidency res = lead.res;  // the lead's share (none under "auto": DESIGN.md 7)
+  std::vector<const k::LassoInstance*> all;
+  for (const BatchMember& b : g) all.push_back(&b.route->pass.inst);
+  const bool rhs_aligned = RhsAligned(all);
+  DVec symv_work = lead.inv.packed.n > 0 ? DVec::Empty(K * k::SymvWorkspace(lead.m), lead.dt) : DVec();
+  const k::FusedResidency res = lead.Residency(K);  // (a ZERO-term lead's own: none under "auto")
 
   std::vector<int> active(K);
   for (int i = 0; i < K; ++i) active[i] = i;
@@ -1406,39 +1280,24 @@ void RunZeroGroup(const Group& g) {
     std::vector<const k::LassoInstance*> v;
     std::vector<const k::ZeroRowsArgs*> r;
     for (int i : active) {
-      EPS_CHECK(g[i].zero().pass.inst.e0.n == n);  // the ZERO chain stores through it
-      v.push_back(&g[i].zero().pass.inst);
-      r.push_back(&g[i].zero().rows);
+      const BatchRoute& mb = *g[i].route;
+      EPS_CHECK(mb.pass.chain == 0 || mb.pass.inst.e0.n == lead.n);  // the ZERO chain stores through it
+      v.push_back(&mb.pass.inst);
+      if (mb.Rows() != nullptr) r.push_back(mb.Rows());
     }
-    k::LassoBatchUpload(v, dt, &table);
-    if (lead.has_z) k::ZeroRowsBatchUpload(r, &row_table);
+    k::LassoBatchUpload(v, lead.dt, &table);
+    if (lead.Rows() != nullptr) k::ZeroRowsBatchUpload(r, &row_table);
   };
   upload();
   auto sweep = [&] {
-    const int na = static_cast<int>(active.size());
-    for (int first = 0; first < na; first += width)
-      k::LassoBatchPass(m, n, lead.pass.lda, lead.pass.A, table, first, std::min(width, na - first), nullptr, res,
-                        /*chain=*/2);
-    if (lead.has_z) k::ZeroFusedRowsBatch(m, lead.grid, lead.rows.smooth, dt, row_table, na);
-    else k::ReducePartialsBatch(m, lead.grid, table, na, dt, rhs_aligned);
-    if (P.n > 0) {
-      k::SymvPackedBatch(m, lead.inv.D->scale(), P, table, na, symv_work);
-    } else {
-      for (int i : active) g[i].zero().inv.Apply();
-    }
+    lead.BatchSweep(table, row_table, static_cast<int>(active.size()), nullptr, res, rhs_aligned, symv_work, [&] {
+      for (int i : active) g[i].route->inv.Apply();
+    });
   };
+  // the stopped ones are frozen: drop their descriptors
   RunGroupSchedule(g, t0, &active, sweep, [&](const std::vector<int>&) {
     if (!active.empty()) upload();
   });
-}
-
-// EPSILON_HIP_BATCH_WIDE (eps_set_option "batch_wide"), read per batch: "1" sends eligible groups
-// to the wide route below.
-bool BatchWideEnabled() {
-  const char* e = std::getenv("EPSILON_HIP_BATCH_WIDE");
-  if (e == nullptr || std::strcmp(e, "0") == 0) return false;
-  EPS_CHECK_MSG(std::strcmp(e, "1") == 0, "batch_wide must be 0 or 1, got " << e);
-  return true;
 }
 
 // Smallest group the wide route takes.  Measured crossovers against the batched pass on MI355X
@@ -1449,14 +1308,14 @@ int BatchWideMin() {  // EPSILON_HIP_BATCH_WIDE_MIN: tuning knob (the crossover 
   return e && std::atoi(e) >= 2 ? std::atoi(e) : kWideMin;
 }
 
-// The wide route (kernels_fused_wide.hip): RunFusedGroup's schedule and residual checks, with the
+// The wide route (kernels_fused_wide.hip), lasso members alone: RunPassGroup's schedule and residual checks, with the
 // sweep of a panel of up to 64 members as back product + chain, forward product and reduction on
 // the f32 matrix instruction.  The members' w (and p) live in instance-major panels for the
 // duration; a member keeps its slot until the group ends and a stopped one is masked, so no
 // summation order depends on who else is still iterating.  Not bit-identical to the single solve.
 void RunWideGroup(const Group& g) {
   const double t0 = Now();
-  const LassoRoute& lead = g[0].lasso();
+  const BatchRoute& lead = *g[0].route;
   SetCurrentDType(F32);
   const int64_t m = lead.m, n = lead.n;
   const bool whiten = lead.whiten;
@@ -1464,14 +1323,14 @@ void RunWideGroup(const Group& g) {
   constexpr int PW = WideSweep::PW;
   const int npanels = (K + PW - 1) / PW;
   WideSweep ws;
-  ws.Init(m, n, lead.pass.A, lead.pass.lda, whiten, lead.ls.Dinv_arg.get());
+  ws.Init(m, n, lead.pass.A, lead.pass.lda, whiten, lead.inv.D.get());
   const int64_t panel_len = ws.panel_len;
 
   std::vector<k::LassoInstance> mem;
   DVec Wall = DVec::Zeros(npanels * panel_len, F32);
   DVec Pall = whiten ? DVec() : DVec::Zeros(npanels * panel_len, F32);
   for (int i = 0; i < K; ++i) {
-    mem.push_back(g[i].lasso().pass.inst);
+    mem.push_back(g[i].route->pass.inst);
     for (const DVec* v : {&mem[i].u, &mem[i].x0, &mem[i].x1, &mem[i].y0, &mem[i].y1, &mem[i].y1prev})
       EPS_CHECK_MSG(reinterpret_cast<uintptr_t>(v->data()) % 16 == 0, "wide batch: unaligned state vector");
     DVec slot = Wall.Slice(static_cast<int64_t>(i) * m, m);
@@ -1504,27 +1363,21 @@ void RunWideGroup(const Group& g) {
     for (int i : gone) live[i / PW] &= ~(uint64_t(1) << (i % PW));
   });
   // every member's own w holds what its next sweep would read
-  for (int i = 0; i < K; ++i) k::Copy(g[i].lasso().pass.inst.w, mem[i].w);
+  for (int i = 0; i < K; ++i) k::Copy(g[i].route->pass.inst.w, mem[i].w);
 }
 
 }  // namespace
 
 std::vector<bool> RunFusedBatches(const std::vector<Solver*>& solvers) {
   std::vector<bool> ran(solvers.size(), false);
-  const bool wide = BatchWideEnabled();
+  const bool wide = ChoiceOptionNow("batch_wide") != 0;
   std::map<std::vector<uint64_t>, std::vector<size_t>> groups;
-  std::vector<FusedRoute*> routes(solvers.size(), nullptr);
+  std::vector<BatchRoute*> routes(solvers.size(), nullptr);
   std::vector<std::vector<uint64_t>> order;  // groups in order of their first instance
   for (size_t i = 0; i < solvers.size(); ++i) {
-    routes[i] = solvers[i]->batch_route();
+    routes[i] = dynamic_cast<BatchRoute*>(solvers[i]->batch_route());
     std::vector<uint64_t> key;
-    if (auto* lasso = dynamic_cast<LassoRoute*>(routes[i])) {
-      if (!lasso->BatchKey(solvers[i]->params(), &key)) continue;
-    } else if (auto* zero = dynamic_cast<ZeroRoute*>(routes[i])) {
-      if (!zero->BatchKey(solvers[i]->params(), &key)) continue;
-    } else {
-      continue;
-    }
+    if (routes[i] == nullptr || !routes[i]->BatchKey(solvers[i]->params(), &key)) continue;
     auto& members = groups[key];
     if (members.empty()) order.push_back(key);
     members.push_back(i);
@@ -1534,16 +1387,13 @@ std::vector<bool> RunFusedBatches(const std::vector<Solver*>& solvers) {
     if (idx.size() < 2) continue;  // alone: the single path is the same solve, with pipelined checks
     Group g;
     for (size_t i : idx) g.push_back({solvers[i], routes[i]});
-    if (key[0] == kZeroGroupTag) {
-      RunZeroGroup(g);
-    } else {
-      const LassoRoute& lead = g[0].lasso();
-      if (wide && static_cast<int>(g.size()) >= BatchWideMin() && lead.dt == F32 &&
-          k::LassoWideSupported(lead.m, lead.n, lead.pass.A, lead.pass.lda))
-        RunWideGroup(g);
-      else
-        RunFusedGroup(g);
-    }
+    const BatchRoute& lead = *g[0].route;
+    // the wide kernels run the lasso chain alone
+    if (wide && lead.pass.chain == 0 && static_cast<int>(g.size()) >= BatchWideMin() && lead.dt == F32 &&
+        k::LassoWideSupported(lead.m, lead.n, lead.pass.A, lead.pass.lda))
+      RunWideGroup(g);
+    else
+      RunPassGroup(g);
     for (size_t i : idx) ran[i] = true;
   }
   return ran;

@@ -34,6 +34,9 @@ std::unique_ptr<ProxOperator> CreateProxOperator(int type, bool epigraph) {
 
 namespace {
 
+// A scalar map with exactly this value (the describers' test of a block of L or Dinv).
+bool is_scalar(const LinearMap& m, double a) { return m.impl().type() == SCALAR_MATRIX && GetScalar(m) == a; }
+
 // What the argument map H and the constraint row A look like to an elementwise prox: the
 // diagonals of H^T H and of H A^T A H^T, provided both are block diagonal with one and the same
 // diagonal on every block (the test of reference vector_prox.cc:4-49).  `uniform` = every block
@@ -548,9 +551,6 @@ class SumSquareProx final : public ProxOperator {
     if (vk != *var_keys_.begin()) return false;
     const BlockMatrix& L = chol_.L();
     const BlockMatrix& Di = chol_.D_inv();
-    auto is_scalar = [](const LinearMap& m, double a) {
-      return m.impl().type() == SCALAR_MATRIX && GetScalar(m) == a;
-    };
     if (!L.has_key(vk, ck) || !L.has_key(ak, vk) || L.has_key(ak, ck)) return false;
     if (!Di.has_key(ck, ck) || !Di.has_key(vk, vk) || !Di.has_key(ak, ak)) return false;
     if (!is_scalar(L(vk, ck), -1.0) || !is_scalar(Di(ck, ck), -1.0) || !is_scalar(Di(vk, vk), 1.0))
@@ -633,13 +633,20 @@ class ZeroProx final : public ProxOperator {
     return chol_.Solve(b_ + v).Select(var_keys_);
   }
 
+  // The fat order, then the tall one (no factorisation has both patterns: the fat order ends in
+  // the arg pivot, the tall one in a copy).
+  bool DescribeZeroProjection(ZeroProjectionDesc* d) const override {
+    return DescribeFat(d) || DescribeTall(d);
+  }
+
+ private:
   // Pattern of the compiled graph forms: every variable of the term is a private
   // copy tied to one constraint row with L(var, constraint) = -1, Dinv(constraint) = -1,
   // Dinv(var) = 1; one copy (x') enters the arg row through a dense map, the other (z', optional)
   // through a scalar; the order ends in the dense arg pivot.  Then with v the prox input
   //   Solve(b_ + v)[x'] = v_x - L(arg,x')^T w,  [z'] = v_z - e w,
   //   w = Dinv_arg ((rhs_arg - e v_z) - L(arg,x') v_x).
-  bool DescribeZeroProjection(ZeroProjectionDesc* d) const override {
+  bool DescribeFat(ZeroProjectionDesc* d) const {
     const std::vector<std::string>& p = chol_.order();
     if (chol_.refine_steps() > 0) return false;
     const size_t nv = var_keys_.size();
@@ -648,9 +655,6 @@ class ZeroProx final : public ProxOperator {
     if (var_keys_.count(ak) != 0) return false;
     const BlockMatrix& L = chol_.L();
     const BlockMatrix& Di = chol_.D_inv();
-    auto is_scalar = [](const LinearMap& m, double a) {
-      return m.impl().type() == SCALAR_MATRIX && GetScalar(m) == a;
-    };
     if (!Di.has_key(ak, ak) || Di(ak, ak).impl().type() != DENSE_MATRIX) return false;
     *d = ZeroProjectionDesc();
     for (const std::string& vk : var_keys_) {
@@ -669,8 +673,8 @@ class ZeroProx final : public ProxOperator {
         if (other != vk && (L.has_key(other, vk) || L.has_key(vk, other) || L.has_key(other, ck))) return false;
       const LinearMap& Lav = L(ak, vk);
       if (Lav.impl().type() == DENSE_MATRIX) {
-        if (d->L_arg_x) return false;
-        d->L_arg_x = std::static_pointer_cast<const DenseMatrixImpl>(Lav.ptr());
+        if (d->L) return false;
+        d->L = std::static_pointer_cast<const DenseMatrixImpl>(Lav.ptr());
         d->x_key = vk;
         d->x_constraint_key = ck;
       } else if (Lav.impl().type() == SCALAR_MATRIX) {
@@ -682,11 +686,11 @@ class ZeroProx final : public ProxOperator {
         return false;
       }
     }
-    if (!d->L_arg_x || d->L_arg_x->trans() || (nv == 2 && d->z_key.empty())) return false;
+    if (!d->L || d->L->trans() || (nv == 2 && d->z_key.empty())) return false;
     for (const auto& kv : b_.data())
       if (kv.first != ak) return false;
     d->arg_key = ak;
-    d->Dinv_arg = std::static_pointer_cast<const DenseMatrixImpl>(Di(ak, ak).ptr());
+    d->Dinv = std::static_pointer_cast<const DenseMatrixImpl>(Di(ak, ak).ptr());
     d->rhs_arg = b_.has_key(ak) ? b_(ak) : DVec();
     return true;
   }
@@ -697,7 +701,7 @@ class ZeroProx final : public ProxOperator {
   // Dinv(x') the only dense pivot; nothing else in L.  Then with v the prox input
   //   f_arg = rhs_arg - e v_z,  Solve(b_ + v)[x'] = Dinv(x') (v_x - L(x',arg) f_arg),
   //   arg = Dinv(arg) f_arg - L(x',arg)^T x',  [z'] = v_z - e arg.
-  bool DescribeZeroTallProjection(ZeroTallProjectionDesc* d) const override {
+  bool DescribeTall(ZeroProjectionDesc* d) const {
     const std::vector<std::string>& p = chol_.order();
     if (chol_.refine_steps() > 0) return false;
     if (var_keys_.size() != 2 || p.size() != 5) return false;
@@ -706,9 +710,6 @@ class ZeroProx final : public ProxOperator {
     if (var_keys_.count(p[0]) != 0 || var_keys_.count(p[1]) != 0) return false;
     const BlockMatrix& L = chol_.L();
     const BlockMatrix& Di = chol_.D_inv();
-    auto is_scalar = [](const LinearMap& m, double a) {
-      return m.impl().type() == SCALAR_MATRIX && GetScalar(m) == a;
-    };
     // the constraint row of each copy: the one of the first two keys whose column reaches it
     auto row_of = [&](const std::string& vk, std::string* ck) {
       const bool r0 = L.has_key(vk, p[0]), r1 = L.has_key(vk, p[1]);
@@ -731,21 +732,21 @@ class ZeroProx final : public ProxOperator {
     if (!Lxa->trans() || Dx->rows() != Lxa->m() || Dx->cols() != Lxa->m()) return false;
     for (const auto& kv : b_.data())
       if (kv.first != ak) return false;
-    *d = ZeroTallProjectionDesc();
+    *d = ZeroProjectionDesc();
+    d->tall = true;
     d->x_key = xk;
     d->z_key = zk;
     d->arg_key = ak;
     d->x_constraint_key = cx;
     d->z_constraint_key = cz;
-    d->L_x_arg = Lxa;
-    d->Dinv_x = Dx;
+    d->L = Lxa;
+    d->Dinv = Dx;
     d->dinv_arg = GetScalar(Di(ak, ak));
     d->e = GetScalar(L(ak, zk));
     d->rhs_arg = b_.has_key(ak) ? b_(ak) : DVec();
     return true;
   }
 
- private:
   BlockCholesky chol_;
   BlockVector b_;
   std::set<std::string> var_keys_;

@@ -71,33 +71,27 @@ struct GroupNorm2Desc {  // Norm2Prox with axis = 1 on an n x cols argument: one
   int64_t rows = 0, cols = 0;
 };
 
-// ZeroProx after block elimination [constraints and copies (scalar pivots) ..., arg]: the
-// projection onto {C x' + e z' + d = 0} of the graph-form problems,
-//   w = Dinv_arg (rhs_arg - e v_z - s C v_x),  x' = v_x - s C^T w,  z' = v_z - e w
-// with s C = L_arg_x (lazily scaled) and Dinv_arg = -(C C^T + e^2 I)^-1 as the factorisation holds it.
+// ZeroProx after block elimination: the projection onto {C x' + e z' + d = 0} of the graph-form
+// problems, in one of two orders; v is the prox input.
+// Fat C, [constraints and copies (scalar pivots) ..., arg] (tall = false):
+//   w = Dinv (rhs_arg - e v_z - s C v_x),  x' = v_x - s C^T w,  z' = v_z - e w
+// with L = L(arg, x') = s C (lazily scaled) and Dinv = Dinv(arg) = -(C C^T + e^2 I)^-1 as the
+// factorisation holds it.
+// Tall C (more rows than columns): the fill model eliminates [constraint, constraint, z', arg, x'],
+// so arg is a scalar pivot and x' the only dense one ("Tall C"; tall = true).  With
+// f_arg = rhs_arg - e v_z:
+//   x' = Dinv (v_x - L f_arg),  arg = dinv_arg f_arg - L^T x',  z' = v_z - e arg
+// with L = L(x', arg) = -C^T / e^2 as the factorisation holds it (transposed, lazily scaled) and
+// Dinv = Dinv(x') = (I + C^T C / e^2)^-1.
 struct ZeroProjectionDesc {
+  bool tall = false;
   std::string x_key, z_key, arg_key;             // z_key empty: no z block (basis pursuit)
   std::string x_constraint_key, z_constraint_key;
-  std::shared_ptr<const DenseMatrixImpl> L_arg_x;   // L(arg, x'): lazily scaled data matrix
-  std::shared_ptr<const DenseMatrixImpl> Dinv_arg;  // cached explicit inverse (with its sign)
-  double e = 0;                                     // L(arg, z')
-  DVec rhs_arg;                                     // constant part of the rhs on the arg row
-};
-
-// ZeroProx of the same graph forms for TALL C (more rows than columns): the fill model eliminates
-// [constraint, constraint, z', arg, x'], so arg is a scalar pivot and x' the only dense one
-// ("Tall C").  With v the prox input and f_arg = rhs_arg - e v_z:
-//   x' = Dinv_x (v_x - L_x_arg f_arg),  arg = dinv_arg f_arg - L_x_arg^T x',  z' = v_z - e arg
-// with L_x_arg = L(x', arg) = -C^T / e^2 as the factorisation holds it (transposed, lazily scaled)
-// and Dinv_x = (I + C^T C / e^2)^-1.
-struct ZeroTallProjectionDesc {
-  std::string x_key, z_key, arg_key;
-  std::string x_constraint_key, z_constraint_key;
-  std::shared_ptr<const DenseMatrixImpl> L_x_arg;  // L(x', arg): trans() set, n x m as a map
-  std::shared_ptr<const DenseMatrixImpl> Dinv_x;   // cached explicit inverse, n x n
-  double dinv_arg = 0;                             // Dinv(arg)'s scalar
-  double e = 0;                                    // L(arg, z')
-  DVec rhs_arg;                                    // constant part of the rhs on the arg row
+  std::shared_ptr<const DenseMatrixImpl> L;     // the dense map: lazily scaled data matrix (tall: trans() set)
+  std::shared_ptr<const DenseMatrixImpl> Dinv;  // cached explicit inverse of the dense pivot (with its sign)
+  double dinv_arg = 0;                           // tall: Dinv(arg)'s scalar
+  double e = 0;                                  // L(arg, z')
+  DVec rhs_arg;                                  // constant part of the rhs on the arg row
 };
 
 class ProxOperator {  // reference prox/prox.h:37-43
@@ -112,7 +106,6 @@ class ProxOperator {  // reference prox/prox.h:37-43
   virtual bool DescribeScaledZoneOffset(ScaledZoneDesc* d) const { return false; }
   virtual bool DescribeSmoothSeparable(SmoothSeparableDesc* d) const { return false; }
   virtual bool DescribeZeroProjection(ZeroProjectionDesc* d) const { return false; }
-  virtual bool DescribeZeroTallProjection(ZeroTallProjectionDesc* d) const { return false; }
 };
 
 std::unique_ptr<ProxOperator> CreateProxOperator(int type, bool epigraph);
