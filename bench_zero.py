@@ -47,6 +47,17 @@ ladder256 / ladder512 / ladder1024 / ladder2048 = hinge + l1 4n x n, which sets 
 the smallest n from which the fused median is at least 1.05 x the generic one.
 
     python bench_zero.py --shapes hinge_tall,hinge_tall64,hinge_tall_big,deadzone_tall,mnist_shape,ladder256,ladder512,ladder1024,ladder2048
+
+Tall logistic cells (a smooth z term on the tall route: five launches per sweep, DESIGN.md 3.11 "Tall
+C"): the routes are those of the option "fused_zero_tall_smooth" - "0" the generic operator path,
+which is what these problems took before the route existed, and "1" - with "fused_zero_tall" = "1":
+logreg_tall = logistic loss + l1 5000 x 1500 (logreg_tall64 in f64), logreg_mnist_shape = 60000 x 784,
+and the ladder logreg_ladder512 / logreg_ladder1024 / logreg_ladder2048 = 4n x n, which sets the floor
+of that option's "auto" by the same rule.  --resident KB sets the option "fused_resident" for every
+handle (default auto); the line carries it.
+
+    python bench_zero.py --shapes logreg_tall,logreg_tall64,logreg_ladder512,logreg_ladder1024,logreg_ladder2048
+    python bench_zero.py --shapes logreg_tall --resident 29297
 """
 
 import argparse
@@ -81,6 +92,12 @@ SHAPES = {
     "ladder512": ("hinge_l1", 2048, 512, "f32"),
     "ladder1024": ("hinge_l1", 4096, 1024, "f32"),
     "ladder2048": ("hinge_l1", 8192, 2048, "f32"),
+    "logreg_tall": ("logreg_l1", 5000, 1500, "f32"),
+    "logreg_tall64": ("logreg_l1", 5000, 1500, "f64"),
+    "logreg_ladder512": ("logreg_l1", 2048, 512, "f32"),
+    "logreg_ladder1024": ("logreg_l1", 4096, 1024, "f32"),
+    "logreg_ladder2048": ("logreg_l1", 8192, 2048, "f32"),
+    "logreg_mnist_shape": ("logreg_l1", 60000, 784, "f32"),
 }
 ROUTES = ("0", "auto")
 TALL_ROUTES = ("0", "1")  # of "fused_zero_tall", for the cells with more rows than columns
@@ -96,6 +113,7 @@ def parse():
     p.add_argument("--rounds", type=int, default=3)
     p.add_argument("--lib", default="")
     p.add_argument("--against", default="")
+    p.add_argument("--resident", default="auto", help="the option fused_resident: auto or a number of KiB")
     return p.parse_args()
 
 
@@ -215,12 +233,17 @@ def main():
     for name in a.shapes.split(","):
         kind, m, n, dtype = SHAPES[name]
         tall = m > n
-        option, routes, tag = (("fused_zero_tall", TALL_ROUTES, "zero_tall") if tall else
+        option, routes, tag = (("fused_zero_tall_smooth", TALL_ROUTES, "zero_tall_samples")
+                               if tall and kind == "logreg_l1" else
+                               ("fused_zero_tall", TALL_ROUTES, "zero_tall") if tall else
                                ("fused_zero", ROUTES, "zero_fused"))
         prob = getattr(problems, kind)(m, n)[0]
         pb, data = prob.SerializeToString(), prob.expression_data()
         sb = wire.SolverParams(max_iterations=10 ** 9, ignore_stopping_criteria=True).SerializeToString()
         _solve.set_option("dtype", dtype)
+        _solve.set_option("fused_resident", a.resident)
+        if option == "fused_zero_tall_smooth":
+            _solve.set_option("fused_zero_tall", "1")
         handles = {}
         try:
             for route in routes:
@@ -244,6 +267,8 @@ def main():
             for s in handles.values():
                 s.close()
             _solve.set_option(option, "auto")
+            _solve.set_option("fused_zero_tall", "auto")
+            _solve.set_option("fused_resident", "auto")
             _solve.set_option("dtype", "f32")
         ms = {r: (1e3 * statistics.median(times[r]) if r in times else None) for r in routes}
         spread = {r: ((max(times[r]) - min(times[r])) / statistics.median(times[r]) if r in times else None)
@@ -251,6 +276,8 @@ def main():
         line = dict(bench="zero_routes", shape=name, problem=kind, m=m, n=n, dtype=dtype, gpus=1, steps=a.steps,
                     warmup=a.warmup, ms_per_sweep=ms, spread=spread,
                     speedup=(ms["0"] / ms[routes[1]] if ms[routes[1]] else None))
+        if a.resident != "auto":
+            line["fused_resident_kb"] = int(a.resident)
         if tall:
             line["sweeps_per_s"] = {r: (1e3 / ms[r] if ms[r] else None) for r in routes}
         print(json.dumps(line), flush=True)

@@ -326,6 +326,9 @@ int eps_set_option(const char* key, const char* value) {
     } else if (std::strcmp(key, "fused_zero_tall") == 0) {
       (void)ParseChoiceOption(key, value);
       setenv("EPSILON_HIP_FUSED_ZERO_TALL", value, 1);
+    } else if (std::strcmp(key, "fused_zero_tall_smooth") == 0) {
+      (void)ParseChoiceOption(key, value);
+      setenv("EPSILON_HIP_FUSED_ZERO_TALL_SMOOTH", value, 1);
     } else if (std::strcmp(key, "fused_resident") == 0) {
       (void)ParseFusedResident(value);  // a bad value is an error here, not at the next Init
       setenv("EPSILON_HIP_FUSED_RESIDENT_KB", value, 1);

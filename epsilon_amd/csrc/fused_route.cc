@@ -133,7 +133,8 @@ int BatchWideMin();  // (with the batched solves below)
 
 // The options with a choice of words (ParseChoiceOption): the variable that holds the option, its
 // words in the order of their indices, the error's text and the word that holds while the variable
-// is unset.  "fused_zero", "fused_zero_tall" and "fused_matrix" are read at every Init,
+// is unset.  "fused_zero", "fused_zero_tall", "fused_zero_tall_smooth" and "fused_matrix" are read
+// at every Init,
 // "batch_wide" per batch ("1" sends eligible groups to the wide route).
 const struct ChoiceOption {
   const char *name, *env, *words[5], *error, *unset;
@@ -141,11 +142,13 @@ const struct ChoiceOption {
     {"fused_zero", "EPSILON_HIP_FUSED_ZERO", {"0", "auto"}, "fused_zero must be 0 or auto, got ", "auto"},
     {"fused_zero_tall", "EPSILON_HIP_FUSED_ZERO_TALL", {"0", "1", "auto"},
      "fused_zero_tall must be 0, 1 or auto, got ", "auto"},
+    {"fused_zero_tall_smooth", "EPSILON_HIP_FUSED_ZERO_TALL_SMOOTH", {"0", "1", "auto"},
+     "fused_zero_tall_smooth must be 0, 1 or auto, got ", "auto"},
     {"fused_matrix", "EPSILON_HIP_FUSED_MATRIX", {"0", "pass", "wide", "auto"},
      "fused_matrix must be 0, pass, wide or auto, got ", "auto"},
     {"batch_wide", "EPSILON_HIP_BATCH_WIDE", {"0", "1"}, "batch_wide must be 0 or 1, got ", "0"},
 };
-enum ZeroTallMode { kZeroTallOff, kZeroTallOn, kZeroTallAuto };
+enum ZeroTallMode { kZeroTallOff, kZeroTallOn, kZeroTallAuto };  // of either tall option
 enum MatrixRoute { kMatrixOff, kMatrixPass, kMatrixWide, kMatrixAuto };
 
 // The option as its variable holds it now.
@@ -205,6 +208,13 @@ constexpr int64_t kZeroTallMinCols = 256;
 // sweep measured at least 1.05 x the generic one (5.5 x at n = 256, the first cell, and
 // no cell above it below 2.9 x); 0 would mean that no cell got there and "auto" is "0".
 constexpr int64_t kZeroTallAutoMinCols = 256;
+// A smooth z term on the tall route (SUM_LOGISTIC; option "fused_zero_tall_smooth"): the sweep is five
+// launches, with the sample kernel between the halves of the pass.  The floor of its "auto" by the
+// same rule on the logreg_ladder cells of bench_zero.py, from n = 512 on (at n = 256 the default
+// stays the generic path); 0 means that no cell got there, or that the cells were not run, and "auto"
+// is "0".
+// Measured: 3.5 x at n = 512, the first cell, and no cell above it below 2.4 x.
+constexpr int64_t kZeroTallSmoothAutoMinCols = 512;
 
 // The bits of a scalar, as a word of a batch key.
 uint64_t Bits(double v) {
@@ -800,9 +810,11 @@ struct LassoRoute final : BatchRoute {
 // Everything between C x' of sweep k and C^T f_arg of sweep k+1 is element-wise in the sample, so
 // the pass streams C^T (features x samples, one contiguous copy made at Init): per sample the
 // product with x', the z-side chain and the forward product (chain 3); then the x-side kernel (the
-// partials' sum, the chain on x, f_x) and the apply of Dinv(x').  A smooth z term is refused: its
-// Newton cannot sit in the per-column step of the pass.  No batched form: a member of a batch on
-// this route is solved by itself.
+// partials' sum, the chain on x, f_x) and the apply of Dinv(x').  A smooth z term (`samples_smooth`:
+// SUM_LOGISTIC, under the option "fused_zero_tall_smooth") has its Newton in a kernel of its own over
+// the samples, between the two halves of the pass: the dot products C x' (chain 4), the sample kernel
+// with the carried head, the forward product (chain 5).  No batched form: a member of a batch on this
+// route is solved by itself.
 struct ZeroRoute final : BatchRoute {
   // u, var, copy, y of the separable term, y of the ZERO term, their previous values: the state of
   // one consensus constraint
@@ -816,11 +828,18 @@ struct ZeroRoute final : BatchRoute {
   // the pass's partials, n-long)
   DVec state_n, state_m;  // the slices of a side's state in one buffer (n: the x constraint's rows)
   DVec CT;    // tall: C^T, n x m, ld n: shared through the solve's cache
-  DVec head;  // a smooth z term: the row kernel's carried head (s, y_s, v of the coming sweep)
+  DVec head;  // a smooth z term: the carried head (s, y_s, v of the coming sweep)
   k::ZeroRowsArgs rows;  // the side that is not in the pass: z (tall: x)
+  // tall with a smooth z term: the sample kernel's record, its vectors d and f_arg, and the second
+  // half of the pass (`pass` is the first)
+  bool samples_smooth = false;
+  k::ZeroTallSamplesArgs samples;
+  DVec dfarg;
+  k::LassoFusedArgs acc;
 
-  // `tall_mode`: the option "fused_zero_tall"; under "auto" the measured floor applies
-  bool Enable(const MultiBlockParts& a, int tall_mode) {
+  // `tall_mode`, `tall_smooth_mode`: the options "fused_zero_tall" and "fused_zero_tall_smooth";
+  // under "auto" the measured floors apply
+  bool Enable(const MultiBlockParts& a, int tall_mode, int tall_smooth_mode) {
     if (FusedDisabled() || ShardSpec::Get().active() || !a.b.data().empty()) return false;
     const int nc = a.num_constraints, N = static_cast<int>(a.prox.size());
     if (nc < 1 || nc > 2 || N != nc + 1) return false;
@@ -835,7 +854,8 @@ struct ZeroRoute final : BatchRoute {
       SmoothSeparableDesc sm;
       const bool smooth = !a.prox[i]->DescribeScaledZoneOffset(&d);
       if (smooth) {  // the scalar form is the zone's; its parameters are not read
-        if (tall || !a.prox[i]->DescribeSmoothSeparable(&sm)) return false;  // (tall SUM_LOGISTIC: the generic path)
+        if (!a.prox[i]->DescribeSmoothSeparable(&sm)) return false;
+        if (tall && (tall_smooth_mode == kZeroTallOff || sm.fn != k::SMOOTH_LOGISTIC)) return false;
         d.var_key = sm.var_key;
         d.constraint_key = sm.constraint_key;
         d.Bs = sm.Bs;
@@ -849,8 +869,9 @@ struct ZeroRoute final : BatchRoute {
       } else if (has_z && iz < 0 && d.constraint_key == zp.z_constraint_key) {
         sz = d;
         iz = i;
-        rows.smooth = smooth;
-        rows.fn = sm.fn;
+        // (the smooth form belongs to the z side: tall, that is the sample kernel, not the rows)
+        (tall ? samples_smooth : rows.smooth) = smooth;
+        (tall ? samples.fn : rows.fn) = sm.fn;
       } else {
         return false;
       }
@@ -869,6 +890,13 @@ struct ZeroRoute final : BatchRoute {
       // the pass's shape conditions, on the copy's geometry, before the copy is made
       const int64_t chunk = dt == F32 ? 4 : 2;
       if (n % chunk != 0 || n > (dt == F32 ? 20 : 10) * 1024) return false;
+      if (samples_smooth) {
+        if (tall_smooth_mode == kZeroTallAuto &&
+            (kZeroTallSmoothAutoMinCols == 0 || n < kZeroTallSmoothAutoMinCols))
+          return false;
+        // the halves of the pass exist in the 256-thread shapes alone
+        if (k::LassoFusedBlock(n, m, dt) != 256) return false;
+      }
     } else {
       if (m < kZeroFusedMinRows || !k::LassoFusedSupported(m, n, L.data(), L.rows())) return false;
     }
@@ -921,11 +949,17 @@ struct ZeroRoute final : BatchRoute {
     if (tall) FillTall(sn, ax, sm, az);
     else FillFat(sn, ax, sm, az);
     // beside the matrix the sweep touches the partials (the rows kernel re-reads them), the seven
-    // state vectors of either side, p, w, and the inverse
-    res = ResidentShare(pass.m, pass.n, dt, static_cast<int64_t>(grid) * nw + 7 * (n + m) + 2 * nw + nw * nw,
+    // state vectors of either side, p, w, the inverse, and the sample kernel's head, d and f_arg
+    res = ResidentShare(pass.m, pass.n, dt,
+                        static_cast<int64_t>(grid) * nw + 7 * (n + m) + 2 * nw + nw * nw + head.n + dfarg.n,
                         /*auto_on=*/false, &pass);
+    if (samples_smooth) {  // the share holds for both halves: the matrix is read twice per sweep
+      acc = pass;
+      acc.chain = 5;
+    }
     AdoptState(views, Homes(a));
     if (rows.smooth) k::ZeroSmoothHead(rows);
+    if (samples_smooth) k::ZeroTallSamplesHead(samples);
     ForwardFromState(a);
     return true;
   }
@@ -1018,6 +1052,38 @@ struct ZeroRoute final : BatchRoute {
     pass.dinv = zp.dinv_arg;
     RowsSide(sn, sx, ax);
     rows.tall = true;
+    if (!samples_smooth) return;
+    // the pass in two halves (chains 4 and 5) around the sample kernel, which takes the z side's
+    // state, offset, rhs and pivots from the pass's record
+    pass.chain = 4;
+    head = DVec::Zeros(3 * m, dt);
+    dfarg = DVec::Zeros(2 * m, dt);
+    pass.zd = dfarg.Slice(0, m);
+    pass.zfarg = dfarg.Slice(m, m);
+    k::ZeroTallSamplesArgs& t = samples;
+    const k::LassoInstance& i = pass.inst;
+    t.m = m;
+    t.d = pass.zd;
+    t.farg = pass.zfarg;
+    t.rhs = pass.zrhs;
+    t.g = pass.zg;
+    t.u = i.u;
+    t.z = i.x1;
+    t.zq = i.x0;
+    t.yz = i.y1;
+    t.yq = i.y0;
+    t.yzprev = i.y1prev;
+    t.yqprev = i.e0;
+    t.hs = head.Slice(0, m);
+    t.hys = head.Slice(m, m);
+    t.hv = head.Slice(2 * m, m);
+    t.kappa = i.kappa;
+    t.ke = pass.ke;
+    t.dinv = pass.dinv;
+    t.Bs = i.Bs;
+    t.Cs = i.Cs;
+    t.a1 = i.a1;
+    t.lam = i.lam;
   }
 
   // The dense pivot's vector of the first sweep from the current state, with the generic
@@ -1049,6 +1115,10 @@ struct ZeroRoute final : BatchRoute {
 
   void Sweep() override {
     k::LassoFusedPass(pass);
+    if (samples_smooth) {
+      k::ZeroTallSamples(samples);
+      k::LassoFusedPass(acc);
+    }
     if (has_z)
       k::ZeroFusedRows(rows);
     else
@@ -1196,9 +1266,10 @@ int ParseChoiceOption(const char* name, const char* value) {
 std::unique_ptr<FusedRoute> RecogniseMultiBlockRoute(const MultiBlockParts& parts) {
   const bool zero = ChoiceOptionNow("fused_zero") != 0;  // (read first: a bad value is an error whatever the problem)
   const int tall = ChoiceOptionNow("fused_zero_tall");
+  const int tall_smooth = ChoiceOptionNow("fused_zero_tall_smooth");
   if (auto r = Recognise<LassoRoute>(parts)) return r;
   if (!zero) return nullptr;
-  return Recognise<ZeroRoute>(parts, tall);  // fat, then tall
+  return Recognise<ZeroRoute>(parts, tall, tall_smooth);  // fat, then tall
 }
 
 std::unique_ptr<FusedRoute> RecogniseTwoBlockRoute(const TwoBlockParts& parts) {

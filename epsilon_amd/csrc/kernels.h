@@ -91,11 +91,16 @@ struct LassoFusedArgs {
   // previous values); zg, zrhs: the z term's offset and the constant of the arg row per sample
   // (optional), ke = -L(arg, z'), dinv = Dinv(arg)'s scalar; inst.kappa scales the product.  The
   // partials are those of C^T f_arg of the next sweep.  Profile tag "zero_tall".  f32 and f64.
+  // chain = 4, 5: chain 3 in two launches around ZeroTallSamples, for a smooth z term (256-thread
+  // shapes alone).  4 (profile tag "zero_tall_dot"): zd[j] = A[:,j] . w per sample, nothing else is
+  // read or written.  5 (profile tag "zero_tall_acc"): the partials of sum_j A[:,j] zfarg[j]; w and
+  // the state are not read.  zd, zfarg: n each.
   int chain = 0;
   double a0 = 1;
   DVec e0, e1;
   DVec zg, zrhs;
   double ke = 0, dinv = 0;
+  DVec zd, zfarg;
   // the matrix's share that is loaded to stay in the Infinity Cache (LassoFusedResidency); 0, 0:
   // every load non-temporal
   int qfull = 0;
@@ -130,6 +135,26 @@ struct ZeroRowsArgs {
   // and r = v_x' + pkappa sum(tpart) is the next f_x; rhs, g and e are not read.  Scaled zone alone.
   bool tall = false;
 };
+// The sample side of a tall ZERO-term sweep whose z term is smooth (SMOOTH_LOGISTIC alone), between
+// the two halves of the pass (LassoFusedArgs::chain 4 and 5), one launch, a thread per sample,
+// profile tag "zero_tall_samples".  Per sample: finishes sweep k from d = C[i,:] . x' (chain 3's
+// arithmetic: f_arg, the scalar pivot, arg, z' = v + ke arg, y and u on the z constraint) with the z
+// term of this sweep taken from the carried head hs, hys, hv; runs the z term of sweep k + 1 -
+// prox_{lam fn}(Bs v + g) by the fp64 Newton of SmoothProx, once - leaves it in hs, hys, hv and
+// writes farg = rhs + ke v_z of sweep k + 1.  ZeroTallSamplesHead (profile tag "zero_tall_head")
+// fills hs, hys, hv from the state before the first launch.
+struct ZeroTallSamplesArgs {
+  int64_t m = 0;
+  DVec d, farg;                           // m each: in, out
+  DVec rhs, g;                            // optional (empty: zero)
+  DVec u, z, zq, yz, yq, yzprev, yqprev;  // m each, in place (ZeroRowsArgs' meaning)
+  DVec hs, hys, hv;                       // m each, private to the caller
+  double kappa = 0, ke = 0, dinv = 0;     // scale of d; -L(arg, z'); Dinv(arg)'s scalar
+  double Bs = 0, Cs = 0, a1 = 0, lam = 0;
+  SmoothFn fn = SMOOTH_LOGISTIC;
+};
+void ZeroTallSamples(const ZeroTallSamplesArgs& args);
+void ZeroTallSamplesHead(const ZeroTallSamplesArgs& args);
 void ZeroFusedRows(const ZeroRowsArgs& args);
 void ZeroSmoothHead(const ZeroRowsArgs& args);  // profile tag "zero_fused_head"
 // The row side of `count` members of a batch in ONE launch, profile tag "batch_zero_rows": member b

@@ -54,6 +54,13 @@ constexpr int kBlock = 256;
 // w -> x', the state arrays are the m-long ones of the z constraint with MODE 2's meaning (x0 -> z',
 // x1 -> z, y0 -> the ZERO term's y, y1 -> the z term's y), and `zt` has the per-sample offset and
 // rhs and the two scalar pivots.  The value returned into the forward product is the next f_arg.
+// MODE 4 and MODE 5: MODE 3 in two halves, for a z term whose prox does not fit the per-column step
+// (a smooth term: ZeroTallSamplesKernel runs between them).  They stream C^T exactly as MODE 3 does.
+// MODE 4 (tag "zero_tall_dot") is the dot product alone: per sample j thread 0 stores d_j =
+// C[j,:] . x' to `e0`, here the m-long vector d; no partials, no state access.  MODE 5 (tag
+// "zero_tall_acc") is the forward product alone: per sample a broadcast load of f_arg_j from `zt.rhs`,
+// here the m-long vector the sample kernel wrote, then t' += C[j,:]^T f_arg_j; no dot product, no
+// reduction, no barrier.
 template <class T, int NR, int BS, int MODE>
 __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
     int64_t m, int64_t n, const T* __restrict__ A, int64_t lda, const T* __restrict__ w,
@@ -74,8 +81,8 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
 #pragma unroll
   for (int q = 0; q < NR; ++q) {
     row[q] = (static_cast<int64_t>(q) * BS + tid) * R;
-    wv[q] = row[q] < m ? *reinterpret_cast<const V*>(w + row[q]) : zero;
-    tp[q] = zero;
+    if constexpr (MODE != 5) wv[q] = row[q] < m ? *reinterpret_cast<const V*>(w + row[q]) : zero;
+    if constexpr (MODE != 4) tp[q] = zero;
   }
   // this workgroup's columns: pairs (2 jp, 2 jp + 1), jp = blockIdx.x + k gridDim.x, one column
   // at a time
@@ -110,7 +117,12 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
     const int64_t step_n = (jn >= 0 && column(step + 1) < 0) ? step + 2 : step + 1;
     if (jn >= 0) load(nxt, jn);
     // per-column state (same address in every lane: broadcast loads)
-    const T uj = u[j], y0j = y0[j], y1j = y1[j];
+    T uj = T(0), y0j = T(0), y1j = T(0);
+    if constexpr (MODE <= 3) {
+      uj = u[j];
+      y0j = y0[j];
+      y1j = y1[j];
+    }
     T u1j = T(0);
     if (MODE == 1) u1j = e0[j];
     T gj = T(0), rj = T(0);
@@ -119,22 +131,28 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
       if (zt.rhs != nullptr) rj = zt.rhs[j];
     }
     T d = T(0);
+    if constexpr (MODE != 5) {
 #pragma unroll
-    for (int q = 0; q < NR; ++q)
+      for (int q = 0; q < NR; ++q)
 #pragma unroll
-      for (int r = 0; r < R; ++r) d += cur[q][r] * wv[q][r];
-    d = WaveSumT<T>(d);
-    if (lane == 0) red[par][wave] = d;
-    __syncthreads();
-    d = red[par][0];
+        for (int r = 0; r < R; ++r) d += cur[q][r] * wv[q][r];
+      d = WaveSumT<T>(d);
+      if (lane == 0) red[par][wave] = d;
+      __syncthreads();
+      d = red[par][0];
 #pragma unroll
-    for (int w2 = 1; w2 < BS / 64; ++w2) d += red[par][w2];
-    par ^= 1;
+      for (int w2 = 1; w2 < BS / 64; ++w2) d += red[par][w2];
+      par ^= 1;
+    }
     FusedScalarsT<T> cj = c;
     if (c.alpha_v != nullptr) cj.alpha = c.alpha_v[j];
     if (c.beta_v != nullptr) cj.beta = c.beta_v[j];
-    T v0n;
-    if (MODE == 0) {
+    T v0n = T(0);
+    if constexpr (MODE == 4) {
+      if (tid == 0) e0[j] = d;
+    } else if constexpr (MODE == 5) {
+      v0n = zt.rhs[j];
+    } else if (MODE == 0) {
       T nx0, nx1, ny0, ny1, nu;
       v0n = ChainOneT<T>(d, cj, uj, y0j, y1j, &nx0, &nx1, &ny0, &ny1, &nu);
       if (tid == 0) {
@@ -183,19 +201,23 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
         e0[j] = nu1;
       }
     }
+    if constexpr (MODE != 4) {
 #pragma unroll
-    for (int q = 0; q < NR; ++q)
+      for (int q = 0; q < NR; ++q)
 #pragma unroll
-      for (int r = 0; r < R; ++r) tp[q][r] += cur[q][r] * v0n;
+        for (int r = 0; r < R; ++r) tp[q][r] += cur[q][r] * v0n;
+    }
 #pragma unroll
     for (int q = 0; q < NR; ++q) cur[q] = nxt[q];
     j = jn;
     step = step_n;
   }
-  T* out = tpart + static_cast<int64_t>(blockIdx.x) * m;
+  if constexpr (MODE != 4) {
+    T* out = tpart + static_cast<int64_t>(blockIdx.x) * m;
 #pragma unroll
-  for (int q = 0; q < NR; ++q)
-    if (row[q] < m) *reinterpret_cast<V*>(out + row[q]) = tp[q];
+    for (int q = 0; q < NR; ++q)
+      if (row[q] < m) *reinterpret_cast<V*>(out + row[q]) = tp[q];
+  }
 }
 
 template <class T> const T* OptT(const DVec& v) { return v.n > 0 ? v.as<T>() : nullptr; }
@@ -207,11 +229,19 @@ void LaunchFused(const LassoFusedArgs& a, int grid) {
   T* e1 = a.chain == 1 ? a.e1.as<T>() : nullptr;
   ZeroTallScalarsT<T> zt = {nullptr, nullptr, T(0), T(0)};
   if (a.chain == 3) zt = {OptT<T>(a.zg), OptT<T>(a.zrhs), static_cast<T>(a.ke), static_cast<T>(a.dinv)};
+  if (a.chain == 4) e0 = a.zd.as<T>();        // MODE 4 stores d through it
+  if (a.chain == 5) zt.rhs = a.zfarg.as<T>();  // MODE 5 reads f_arg through it
+  auto kernel = LassoFusedStreamKernelT<T, NR, BS, 0>;
+  if (a.chain == 1) kernel = LassoFusedStreamKernelT<T, NR, BS, 1>;
+  if (a.chain == 2) kernel = LassoFusedStreamKernelT<T, NR, BS, 2>;
+  if (a.chain == 3) kernel = LassoFusedStreamKernelT<T, NR, BS, 3>;
+  // the halves of the tall pass exist in the 256-thread shapes alone (ZeroRoute takes no other)
+  if constexpr (BS == 256) {
+    if (a.chain == 4) kernel = LassoFusedStreamKernelT<T, NR, BS, 4>;
+    if (a.chain == 5) kernel = LassoFusedStreamKernelT<T, NR, BS, 5>;
+  }
   hipLaunchKernelGGL(
-      (a.chain == 1 ? LassoFusedStreamKernelT<T, NR, BS, 1>
-                    : a.chain == 2 ? LassoFusedStreamKernelT<T, NR, BS, 2>
-                                   : a.chain == 3 ? LassoFusedStreamKernelT<T, NR, BS, 3>
-                                                  : LassoFusedStreamKernelT<T, NR, BS, 0>),
+      kernel,
       dim3(grid), dim3(BS), 0, Runtime::Get().stream(), a.m, a.n, a.A.as<T>(), a.lda, i.w,
       ScalarsOf<T>(i, a.a0, a.inst.a1), i.u, i.x0, i.x1, i.y0, i.y1, i.y1prev, i.tpart, a.epoch, e0, e1,
       a.qfull, a.jcut, zt);
@@ -237,6 +267,43 @@ void LaunchFusedT(const LassoFusedArgs& a, int grid, int block) {
   }
   if (need <= 8) LaunchFused<T, 8, 512>(a, grid);
   else LaunchFused<T, 10, 512>(a, grid);
+}
+
+// ---- the sample side of a tall ZERO-term sweep with a smooth z term --------------------------------
+// Between the two halves of the tall pass ("zero_tall_dot", "zero_tall_acc"): a thread per sample,
+// so the fp64 Newton of the z term runs once per sample and sweep, on whole waves.  ZeroTallChainT
+// from its second line on, with the head of this sweep (s, y_s, v) carried from the previous launch
+// in hs, hys, hv as on the fat route's row kernel: finishes the sweep from d_i = C[i,:] . x', stores
+// the boundary state as MODE 3 does, computes the next head once, leaves it in hs, hys, hv and
+// writes the next f_arg_i for the accumulate pass.  A thread reads and writes its own sample alone.
+template <class T, class Fn>
+__global__ __launch_bounds__(kBlock) void ZeroTallSamplesKernel(
+    int64_t m, FusedScalarsT<T> c, double lam64, T ke, T dinv, const T* __restrict__ g,
+    const T* __restrict__ rhs, const T* __restrict__ d, T* __restrict__ u, T* __restrict__ z,
+    T* __restrict__ zq, T* __restrict__ yz, T* __restrict__ yq, T* __restrict__ yzprev,
+    T* __restrict__ yqprev, T* __restrict__ hs, T* __restrict__ hys, T* __restrict__ hv,
+    T* __restrict__ farg) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= m) return;
+  const T gi = g != nullptr ? g[i] : T(0), ri = rhs != nullptr ? rhs[i] : T(0);
+  const T s = hs[i], ys = hys[i], v = hv[i];
+  const T fa = ZeroTallForwardT<T>(v, ri, ke);
+  const T garg = dinv * fa;
+  const T arg = c.kappa * d[i] + garg;
+  const T q = ke * arg + v;
+  const T un = v - q;  // y_q = q (its constraint map is I); u -= y_q
+  yzprev[i] = yz[i];
+  yqprev[i] = yq[i];
+  z[i] = s;
+  zq[i] = q;
+  yz[i] = ys;
+  yq[i] = q;
+  u[i] = un;
+  const ZeroHeadT<T> hn = ZeroHeadOfT<T, Fn>(c, gi, un, ys, q, lam64);
+  hs[i] = hn.s;
+  hys[i] = hn.ys;
+  hv[i] = hn.v;
+  farg[i] = ZeroTallForwardT<T>(hn.v, ri, ke);
 }
 
 // ---- the row side of a ZERO-term sweep ------------------------------------------------------------
@@ -460,6 +527,56 @@ void ZeroFusedRows(const ZeroRowsArgs& a) {
   EPS_HIP(hipGetLastError());
 }
 
+namespace {
+
+template <class T> FusedScalarsT<T> ZeroTallSampleScalars(const ZeroTallSamplesArgs& a) {
+  return {static_cast<T>(a.kappa), static_cast<T>(a.Bs), static_cast<T>(a.Cs), static_cast<T>(a.a1),
+          static_cast<T>(a.lam), T(1), T(1), T(0), T(1), T(1), nullptr, nullptr};
+}
+
+void CheckZeroTallSamples(const ZeroTallSamplesArgs& a) {
+  const DType dt = a.d.dt;
+  EPS_CHECK(a.m >= 1);
+  for (const DVec* v : {&a.d, &a.farg, &a.u, &a.z, &a.zq, &a.yz, &a.yq, &a.yzprev, &a.yqprev, &a.hs, &a.hys, &a.hv})
+    EPS_CHECK(v->n == a.m && v->dt == dt);
+  for (const DVec* v : {&a.rhs, &a.g})
+    if (v->n > 0) EPS_CHECK(v->n == a.m && v->dt == dt);
+  EPS_CHECK_MSG(a.fn == SMOOTH_LOGISTIC, "the tall ZERO-term sample side takes SUM_LOGISTIC alone, got " << a.fn);
+}
+
+template <class T>
+void LaunchZeroTallSamples(const ZeroTallSamplesArgs& a, bool head_only) {
+  const dim3 grid(static_cast<unsigned>((a.m + kBlock - 1) / kBlock));
+  if (head_only)
+    hipLaunchKernelGGL((ZeroSmoothHeadKernel<T, FnLogistic>), grid, dim3(kBlock), 0, Runtime::Get().stream(), a.m,
+                       ZeroTallSampleScalars<T>(a), a.lam, OptT<T>(a.g), a.u.as<T>(), a.yz.as<T>(), a.yq.as<T>(),
+                       a.hs.as<T>(), a.hys.as<T>(), a.hv.as<T>());
+  else
+    hipLaunchKernelGGL((ZeroTallSamplesKernel<T, FnLogistic>), grid, dim3(kBlock), 0, Runtime::Get().stream(), a.m,
+                       ZeroTallSampleScalars<T>(a), a.lam, static_cast<T>(a.ke), static_cast<T>(a.dinv), OptT<T>(a.g),
+                       OptT<T>(a.rhs), a.d.as<T>(), a.u.as<T>(), a.z.as<T>(), a.zq.as<T>(), a.yz.as<T>(),
+                       a.yq.as<T>(), a.yzprev.as<T>(), a.yqprev.as<T>(), a.hs.as<T>(), a.hys.as<T>(), a.hv.as<T>(),
+                       a.farg.as<T>());
+}
+
+}  // namespace
+
+void ZeroTallSamples(const ZeroTallSamplesArgs& a) {
+  CheckZeroTallSamples(a);
+  ProfScope prof("zero_tall_samples", a.m);
+  if (a.d.dt == F32) LaunchZeroTallSamples<float>(a, false);
+  else LaunchZeroTallSamples<double>(a, false);
+  EPS_HIP(hipGetLastError());
+}
+
+void ZeroTallSamplesHead(const ZeroTallSamplesArgs& a) {
+  CheckZeroTallSamples(a);
+  ProfScope prof("zero_tall_head", a.m);
+  if (a.d.dt == F32) LaunchZeroTallSamples<float>(a, true);
+  else LaunchZeroTallSamples<double>(a, true);
+  EPS_HIP(hipGetLastError());
+}
+
 void ZeroRowsBatchUpload(const std::vector<const ZeroRowsArgs*>& members, DVec* table) {
   EPS_CHECK(!members.empty());
   const ZeroRowsArgs& lead = *members[0];
@@ -670,7 +787,9 @@ void LassoFusedPass(const LassoFusedArgs& a) {
     if (v->n > 0) EPS_CHECK(v->n == a.n && v->dt == dt);
   if (a.chain == 1) EPS_CHECK(a.e0.n == a.n && a.e1.n == a.n && a.e0.dt == dt && a.e1.dt == dt);
   if (a.chain == 2 || a.chain == 3) EPS_CHECK(a.e0.n == a.n && a.e0.dt == dt);
-  EPS_CHECK(a.chain >= 0 && a.chain <= 3);
+  EPS_CHECK(a.chain >= 0 && a.chain <= 5);
+  if (a.chain == 4) EPS_CHECK(a.zd.n == a.n && a.zd.dt == dt);
+  if (a.chain == 5) EPS_CHECK(a.zfarg.n == a.n && a.zfarg.dt == dt);
   if (a.chain == 3)
     for (const DVec* v : {&a.zg, &a.zrhs})
       if (v->n > 0) EPS_CHECK(v->n == a.n && v->dt == dt);
@@ -679,7 +798,10 @@ void LassoFusedPass(const LassoFusedArgs& a) {
   EPS_CHECK(s.tpart.n >= static_cast<int64_t>(grid) * a.m && s.tpart.dt == dt);
   EPS_CHECK(reinterpret_cast<uintptr_t>(s.w.data()) % 16 == 0 &&
             reinterpret_cast<uintptr_t>(s.tpart.data()) % 16 == 0);
-  ProfScope prof(a.chain == 3 ? "zero_tall" : a.chain == 2 ? "zero_fused" : "lasso_fused", a.m, a.n);
+  EPS_CHECK_MSG(a.chain < 4 || block == 256, "the halves of the tall pass take 256-thread shapes alone");
+  static const char* const kTags[] = {"lasso_fused", "lasso_fused", "zero_fused", "zero_tall", "zero_tall_dot",
+                                      "zero_tall_acc"};
+  ProfScope prof(kTags[a.chain], a.m, a.n);
   NoteFusedResidency(a.qfull, a.jcut);
   if (dt == F32) LaunchFusedT<float>(a, grid, block);
   else LaunchFusedT<double>(a, grid, block);

@@ -408,7 +408,11 @@ def logreg_l1(m, n, lam=None, seed=0):
 
       sum_logistic(z) + norm_1(x)[lam] + zero(C x' - z')   s.t.  x' - x = 0,  z' - z = 0
     with C = -diag(y) A.  Fat C with at least 256 rows runs on the fused sweep of ZERO-term
-    problems, the logistic prox inside its row kernel (option "fused_zero")."""
+    problems, the logistic prox inside its row kernel (option "fused_zero").  Tall C
+    (more rows than columns, 256 to 10240 columns, f64: 5120) runs on the tall route in five launches
+    per sweep, the logistic prox in a kernel of its own over the samples (option
+    "fused_zero_tall_smooth": "1" from 256 columns, the default "auto" from 512; DESIGN.md 3.11
+    "A smooth z term on tall C")."""
     rng = np.random.RandomState(seed)
     A = rng.randn(m, n)
     x0 = rng.randn(n) * (rng.rand(n) < 0.3)

@@ -103,7 +103,7 @@ const char* eps_version(void);
  * and "fused" = "0" mean the generic operator path.  Read at every Init.  Any other value is an
  * error that names it (env EPSILON_HIP_FUSED_ZERO).
  * "fused_zero_tall" = "auto" (default) | "0" | "1"  the same problems with tall C (more rows than
- * columns; hinge or deadzone loss with an l1 penalty, not the logistic loss): the sweep as one
+ * columns; hinge or deadzone loss with an l1 penalty; the logistic loss: the next option): the sweep as one
  * pass over a transposed copy of C (made once per Init: the matrix's footprint doubles), one
  * kernel on the x side and the apply of the cached n x n inverse.  "1": wherever the route is
  * supported - 256 to 20480 columns (f64: 10240), columns a multiple of 4 (f64: 2), multi-block
@@ -111,6 +111,15 @@ const char* eps_version(void);
  * on the number of columns (256, so "auto" is "1" at present).  "fused_zero" = "0" and
  * "fused" = "0" switch it off as well.  Read at every Init.  Any other value is an error that
  * names it (env EPSILON_HIP_FUSED_ZERO_TALL).
+ * "fused_zero_tall_smooth" = "auto" (default) | "0" | "1"  l1 logistic regression with tall C on
+ * that route: five launches per sweep - the products C x' over the transposed copy, one kernel
+ * over the samples with the logistic prox in it (its fp64 Newton once per sample and sweep), the
+ * forward product, the x side and the apply of the cached n x n inverse.  "1": wherever the
+ * route is supported - the conditions of "fused_zero_tall" with at most 10240 columns (f64:
+ * 5120); "0": never; "auto": from the measured floor on the number of columns (512).
+ * "fused_zero_tall" = "0", "fused_zero" = "0" and "fused" = "0" switch it off as well.  It touches
+ * nothing but tall problems with a smooth term on z.  Read at every Init.  Any other value is an
+ * error that names it (env EPSILON_HIP_FUSED_ZERO_TALL_SMOOTH).
  * "fused_resident" = "auto" (default) | "<KiB>"  bytes of the data matrix that the fused pass
  * (single and batched; one GPU) loads with the default cache policy, so that they stay in the
  * 256 MiB Infinity Cache from sweep to sweep, while the rest is streamed with non-temporal loads.
