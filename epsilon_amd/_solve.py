@@ -527,6 +527,61 @@ def block_solve(blocks, rhs=None, mode="factor", keys=None):
     return out
 
 
+class _DenseOp(ctypes.Structure):
+    _fields_ = [("op", ctypes.c_char_p),
+                ("rows", ctypes.c_int64), ("cols", ctypes.c_int64), ("lda", ctypes.c_int64),
+                ("nparts", ctypes.c_int), ("alpha", ctypes.c_double), ("beta", ctypes.c_double),
+                ("a", ctypes.c_void_p), ("a_len", ctypes.c_int64), ("a_off", ctypes.c_int64),
+                ("x", ctypes.c_void_p), ("x_len", ctypes.c_int64), ("x_off", ctypes.c_int64),
+                ("y", ctypes.c_void_p), ("y_len", ctypes.c_int64), ("y_off", ctypes.c_int64),
+                ("add", ctypes.c_void_p), ("add_len", ctypes.c_int64), ("add_off", ctypes.c_int64),
+                ("accumulate", ctypes.c_int), ("use_work", ctypes.c_int), ("with_add", ctypes.c_int),
+                ("alias_xy", ctypes.c_int), ("preset", ctypes.c_double)]
+
+
+DENSE_OP_GUARD = 8            # EPS_DENSE_OP_GUARD
+DENSE_OP_SENTINEL = -777.25   # EPS_DENSE_OP_SENTINEL
+DENSE_OP_REDUCTIONS = ("sumsq", "sumsq_diff", "dot")
+
+
+def dense_op(op, rows=0, cols=0, lda=None, nparts=1, alpha=1.0, beta=0.0, a=None, x=None, y=None,
+             add=None, a_off=0, x_off=0, y_off=0, add_off=0, accumulate=False, use_work=False,
+             with_add=None, alias_xy=False, preset=0.0):
+    """Test entry for the dense mat-vec layer (include/epsilon_hip.h eps_test_dense_op): one call
+    of the launcher `op` names on the given float64 operands (a: the matrix, column-major with
+    leading dimension lda, the partials, or the diagonal), each placed *_off elements into a
+    larger device allocation.
+
+    The reductions return the slot's value (it holds `preset` before the call).  The others return
+    the output with its DENSE_OP_GUARD guard elements on each side (DENSE_OP_SENTINEL if nothing
+    stored outside the output); "symv_packed" returns the pair (packed apply, plain Symv)."""
+    L = lib()
+    L.eps_test_dense_op.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    g = _DenseOp()
+    g.op = op.encode("utf-8") if op is not None else None
+    g.rows, g.cols, g.nparts = rows, cols, nparts
+    g.lda = rows if lda is None else lda
+    g.alpha, g.beta, g.preset = alpha, beta, preset
+    keep = []
+    for name, v in (("a", a), ("x", x), ("y", y), ("add", add)):
+        if v is not None:
+            v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+            keep.append(v)
+            setattr(g, name, v.ctypes.data_as(ctypes.c_void_p))
+            setattr(g, name + "_len", v.size)
+    g.a_off, g.x_off, g.y_off, g.add_off = a_off, x_off, y_off, add_off
+    g.accumulate, g.use_work, g.alias_xy = int(accumulate), int(use_work), int(alias_xy)
+    g.with_add = int(add is not None if with_add is None else with_add)
+    n_out = 1 if op in DENSE_OP_REDUCTIONS else g.y_len + 2 * DENSE_OP_GUARD
+    out = np.full(max(n_out, 1), np.nan)
+    out2 = np.full(max(n_out, 1), np.nan) if op == "symv_packed" else None
+    _check(L.eps_test_dense_op(ctypes.byref(g), out.ctypes.data_as(ctypes.c_void_p),
+                               out2.ctypes.data_as(ctypes.c_void_p) if out2 is not None else None))
+    if op in DENSE_OP_REDUCTIONS:
+        return float(out[0])
+    return (out[:n_out], out2[:n_out]) if out2 is not None else out[:n_out]
+
+
 def tv1d(v, lam):
     v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
     x = np.empty_like(v)

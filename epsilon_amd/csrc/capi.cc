@@ -291,6 +291,100 @@ BlockSolveArgs CheckBlockSolveArgs(const char* mode, const eps_block* blocks, si
   return a;
 }
 
+// ---- eps_test_dense_op -----------------------------------------------------------------------------
+
+// The argument checks of eps_test_dense_op, host only: the op, and that every operand the op reads
+// is there with the length its dimensions need, so that no launcher is given a short buffer.
+struct DenseOpArgs {
+  enum Op { GEMV_N, GEMV_T, SYMV, SYMV_PACKED, REDUCE_PARTIALS, SUMSQ, SUMSQ_DIFF, DOT, AXPBY, DIAG_MUL } op;
+  bool reduction = false;  // the result is a slot, not a vector
+  bool use_a = false, use_x = false, use_y = false, use_add = false;
+};
+
+DenseOpArgs CheckDenseOpArgs(const eps_dense_op* g, const double* out, const double* out2) {
+  const char* const fn = "eps_test_dense_op: ";
+  DenseOpArgs a;
+  EPS_CHECK_MSG(g != nullptr, fn << "args is null");
+  EPS_CHECK_MSG(g->op != nullptr, fn << "op is null");
+  const std::string op(g->op);
+  if (op == "gemv_n") a.op = DenseOpArgs::GEMV_N;
+  else if (op == "gemv_t") a.op = DenseOpArgs::GEMV_T;
+  else if (op == "symv") a.op = DenseOpArgs::SYMV;
+  else if (op == "symv_packed") a.op = DenseOpArgs::SYMV_PACKED;
+  else if (op == "reduce_partials") a.op = DenseOpArgs::REDUCE_PARTIALS;
+  else if (op == "sumsq") a.op = DenseOpArgs::SUMSQ;
+  else if (op == "sumsq_diff") a.op = DenseOpArgs::SUMSQ_DIFF;
+  else if (op == "dot") a.op = DenseOpArgs::DOT;
+  else if (op == "axpby") a.op = DenseOpArgs::AXPBY;
+  else if (op == "diag_mul") a.op = DenseOpArgs::DIAG_MUL;
+  else
+    EPS_FATAL(fn << "op must be gemv_n, gemv_t, symv, symv_packed, reduce_partials, sumsq, sumsq_diff, dot, "
+                    "axpby or diag_mul, got " << op);
+  EPS_CHECK_MSG(out != nullptr, fn << "out is null");
+  EPS_CHECK_MSG(a.op != DenseOpArgs::SYMV_PACKED || out2 != nullptr, fn << "out2 is null");
+  EPS_CHECK_MSG(g->rows >= 0, fn << "rows is negative: " << g->rows);
+  const bool gemv = a.op == DenseOpArgs::GEMV_N || a.op == DenseOpArgs::GEMV_T;
+  const bool symv = a.op == DenseOpArgs::SYMV || a.op == DenseOpArgs::SYMV_PACKED;
+  if (gemv) EPS_CHECK_MSG(g->cols >= 0, fn << "cols is negative: " << g->cols);
+  struct Operand { const char* name; const double* p; int64_t len, off; };
+  const Operand A = {"a", g->a, g->a_len, g->a_off}, X = {"x", g->x, g->x_len, g->x_off},
+                Y = {"y", g->y, g->y_len, g->y_off}, ADD = {"add", g->add, g->add_len, g->add_off};
+  for (const Operand& o : {A, X, Y, ADD}) {
+    EPS_CHECK_MSG(o.len >= 0, fn << o.name << "_len is negative: " << o.len);
+    EPS_CHECK_MSG(o.off >= 0, fn << o.name << "_off is negative: " << o.off);
+  }
+  auto need = [&](const Operand& o, int64_t len) {
+    EPS_CHECK_MSG(len == 0 || o.p != nullptr, fn << o.name << " is null");
+    EPS_CHECK_MSG(o.len == len, fn << o.name << " has " << o.len << " entries, the dimensions need " << len);
+  };
+  const int64_t n = g->rows;
+  int64_t a_need = 0, x_need = 0, y_need = n, add_need = 0;
+  if (gemv || symv) {
+    const int64_t cols = symv ? n : g->cols;
+    EPS_CHECK_MSG(g->lda >= n, fn << "lda " << g->lda << " < rows " << n);
+    EPS_CHECK_MSG(cols == 0 || g->lda <= (INT64_MAX - n) / cols, fn << "lda * cols overflows");
+    a_need = cols == 0 ? 0 : (cols - 1) * g->lda + n;
+    x_need = a.op == DenseOpArgs::GEMV_T ? n : cols;
+    y_need = a.op == DenseOpArgs::GEMV_T ? cols : n;
+    a.use_a = a.use_x = a.use_y = true;
+  } else if (a.op == DenseOpArgs::REDUCE_PARTIALS) {
+    EPS_CHECK_MSG(g->nparts >= 1, fn << "nparts must be at least 1, got " << g->nparts);
+    EPS_CHECK_MSG(n == 0 || g->nparts <= INT64_MAX / n, fn << "nparts * rows overflows");
+    a_need = static_cast<int64_t>(g->nparts) * n;
+    add_need = g->with_add ? n : 0;
+    a.use_a = a.use_y = true;
+    a.use_add = g->with_add != 0;
+  } else if (a.op == DenseOpArgs::SUMSQ) {
+    a.reduction = a.use_x = true;
+    x_need = n;
+    y_need = 0;
+  } else if (a.op == DenseOpArgs::SUMSQ_DIFF || a.op == DenseOpArgs::DOT) {
+    a.reduction = a.use_x = a.use_y = true;
+    x_need = n;
+  } else if (a.op == DenseOpArgs::AXPBY) {
+    a.use_x = !g->alias_xy;
+    a.use_y = true;
+    x_need = g->alias_xy ? 0 : n;
+  } else {  // DIAG_MUL
+    a.use_a = a.use_x = a.use_y = true;
+    a_need = x_need = n;
+  }
+  if (a.use_a) need(A, a_need);
+  if (a.use_x) need(X, x_need);
+  if (a.use_y) need(Y, y_need);
+  if (a.use_add) need(ADD, add_need);
+  return a;
+}
+
+// `len` host doubles as the slice [off + guard, off + guard + len) of a device allocation of the
+// configured dtype whose other elements hold EPS_DENSE_OP_SENTINEL; *whole receives the allocation.
+DVec PlaceOperand(const double* p, int64_t len, int64_t off, int64_t guard, DType dt, DVec* whole) {
+  std::vector<double> h(static_cast<size_t>(off + 2 * guard + len), EPS_DENSE_OP_SENTINEL);
+  if (len > 0) std::memcpy(h.data() + off + guard, p, static_cast<size_t>(len) * sizeof(double));
+  *whole = DVec::FromHost(h.data(), static_cast<int64_t>(h.size()), dt);
+  return whole->Slice(off + guard, len);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1026,6 +1120,77 @@ int eps_test_block_solve(const char* mode, const eps_block* blocks, size_t nbloc
       }
     }
     *out = r.release();
+  });
+}
+
+int eps_test_dense_op(const eps_dense_op* g, double* out, double* out2) {
+  return Guard([&] {
+    const DenseOpArgs args = CheckDenseOpArgs(g, out, out2);
+    const DType dt = ConfiguredDType();
+    constexpr int64_t G = EPS_DENSE_OP_GUARD;
+    const int64_t n = g->rows;
+    DVec a_all, x_all, y_all, add_all, a, x, y, add, work;
+    if (args.use_a) a = PlaceOperand(g->a, g->a_len, g->a_off, 0, dt, &a_all);
+    if (args.use_x) x = PlaceOperand(g->x, g->x_len, g->x_off, 0, dt, &x_all);
+    if (args.use_add) add = PlaceOperand(g->add, g->add_len, g->add_off, 0, dt, &add_all);
+    if (args.reduction) {
+      if (args.use_y) y = PlaceOperand(g->y, g->y_len, g->y_off, 0, dt, &y_all);
+      Runtime& rt = Runtime::Get();
+      rt.ResetSlots();
+      const int slot = rt.NewSlot();
+      EPS_HIP(hipMemcpyAsync(rt.SlotPtr(slot), &g->preset, sizeof(double), hipMemcpyHostToDevice, rt.stream()));
+      rt.Sync();
+      const bool acc = g->accumulate != 0;
+      if (args.op == DenseOpArgs::SUMSQ) k::SumSq(x, rt.SlotPtr(slot), acc);
+      else if (args.op == DenseOpArgs::SUMSQ_DIFF) k::SumSqDiff(x, y, rt.SlotPtr(slot), acc);
+      else k::Dot(x, y, rt.SlotPtr(slot), acc);
+      EPS_HIP(hipGetLastError());
+      rt.FetchSlots();
+      out[0] = rt.SlotValue(slot);
+      rt.ResetSlots();
+      return;
+    }
+    // the output between its guards; (y_off + G) elements in is 16-byte aligned for y_off = 0
+    static_assert(EPS_DENSE_OP_GUARD % 4 == 0, "the guard keeps offset 0 aligned");
+    auto place_y = [&] { y = PlaceOperand(g->y, g->y_len, g->y_off, G, dt, &y_all); };
+    auto fetch_y = [&](double* dst) { y_all.Slice(g->y_off, g->y_len + 2 * G).ToHost(dst); };
+    place_y();
+    const bool symv = args.op == DenseOpArgs::SYMV || args.op == DenseOpArgs::SYMV_PACKED;
+    if (symv && g->use_work) work = DVec::Empty(k::SymvWorkspace(n), dt);
+    const DVec* wp = (symv && g->use_work) ? &work : nullptr;
+    switch (args.op) {
+      case DenseOpArgs::GEMV_N:
+      case DenseOpArgs::GEMV_T:
+        k::Gemv(args.op == DenseOpArgs::GEMV_T, n, g->cols, g->alpha, a, g->lda, x, g->beta, y);
+        break;
+      case DenseOpArgs::SYMV:
+        k::Symv(n, g->alpha, a, g->lda, x, g->beta, y, wp);
+        break;
+      case DenseOpArgs::SYMV_PACKED: {
+        const DVec P = k::SymvPack(n, a, g->lda);
+        k::SymvPacked(n, g->alpha, P, x, g->beta, y, wp);
+        EPS_HIP(hipGetLastError());
+        fetch_y(out);
+        place_y();
+        k::Symv(n, g->alpha, a, g->lda, x, g->beta, y, wp);
+        EPS_HIP(hipGetLastError());
+        fetch_y(out2);
+        return;
+      }
+      case DenseOpArgs::REDUCE_PARTIALS:
+        k::ReducePartials(n, g->nparts, a, g->alpha, g->beta, y, args.use_add ? &add : nullptr);
+        break;
+      case DenseOpArgs::AXPBY:
+        k::Axpby(y, g->alpha, g->alias_xy ? y : x, g->beta);
+        break;
+      case DenseOpArgs::DIAG_MUL:
+        k::DiagMul(y, g->alpha, a, x, g->beta);
+        break;
+      default:
+        EPS_FATAL("eps_test_dense_op: unreachable");
+    }
+    EPS_HIP(hipGetLastError());
+    fetch_y(out);
   });
 }
 

@@ -386,6 +386,44 @@ int eps_test_block_solve(const char* mode, const eps_block* blocks, size_t nbloc
                          const eps_blob* data, size_t ndata, const eps_blob* rhs, size_t nrhs,
                          const char* const* keys, size_t nkeys, eps_result** out);
 
+/* Test entry: ONE call of a public launcher of the dense mat-vec layer (csrc/kernels.h: Gemv,
+ * Symv, SymvPack + SymvPacked, ReducePartials, SumSq, SumSqDiff, Dot, Axpby, DiagMul) on
+ * caller-given operands, in the configured dtype.  `op` and what the operands mean:
+ *   "gemv_n"           y = alpha A x + beta y        a: A, rows x cols, leading dimension lda
+ *   "gemv_t"           y = alpha A^T x + beta y      (a has (cols - 1) lda + rows entries)
+ *   "symv"             y = alpha S x + beta y        a: S, n x n with n = rows, lda = lds
+ *   "symv_packed"      the same through SymvPack + SymvPacked into out, and through Symv on the
+ *                      same operands into out2
+ *   "reduce_partials"  y = alpha sum_k a[k rows + r] + beta y (+ add with with_add), k < nparts
+ *   "sumsq" "sumsq_diff" "dot"   slot (+)= sum x^2, sum (x - y)^2, sum x y over n = rows entries;
+ *                      the slot holds `preset` before the call, out[0] receives it afterwards
+ *   "axpby"            y = alpha x + beta y over n = rows entries; alias_xy: x IS y (x not read
+ *                      from the caller)
+ *   "diag_mul"         y = alpha a .* x + beta y
+ * Every operand is uploaded into a larger allocation and handed to the launcher as the slice that
+ * starts *_off elements in: offset 0 is 16-byte aligned, an odd offset is not.  The output y
+ * starts as the caller's y_len values between EPS_DENSE_OP_GUARD guard elements on each side, all
+ * EPS_DENSE_OP_SENTINEL; out receives guard + y_len + guard values, so a store outside the output
+ * shows.  use_work: Symv / SymvPacked with a caller-side workspace instead of the pool's.
+ * The argument checks - an unknown op, a null operand or result, a negative size or offset,
+ * lda < rows, nparts < 1, an operand whose length is not what the dimensions need - fail before
+ * any device work and name the argument. */
+#define EPS_DENSE_OP_GUARD 8
+#define EPS_DENSE_OP_SENTINEL (-777.25)
+typedef struct eps_dense_op {
+  const char* op;
+  int64_t rows, cols, lda;
+  int nparts;
+  double alpha, beta;
+  const double* a;   int64_t a_len, a_off;
+  const double* x;   int64_t x_len, x_off;
+  const double* y;   int64_t y_len, y_off;
+  const double* add; int64_t add_len, add_off;
+  int accumulate, use_work, with_add, alias_xy;
+  double preset;
+} eps_dense_op;
+int eps_test_dense_op(const eps_dense_op* args, double* out, double* out2);
+
 /* Microbenchmark: average milliseconds of one launch of a standalone elementwise prox kernel on
  * n synthetic elements of the configured dtype - kind 0 scaled-zone (NORM_1) with scalar
  * parameters, 1 with a per-element threshold vector, 2 projection onto R+ (reference
