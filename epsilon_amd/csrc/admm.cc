@@ -9,6 +9,7 @@
 
 #include "comm.h"
 #include "fused_route.h"
+#include "options.h"
 
 namespace eps {
 
@@ -224,7 +225,7 @@ class ProxADMMSolver final : public Solver {
     const double t0 = Now();
     if (op_cache_.size() > 64) op_cache_.Clear();
     OpCacheScope cache_scope(InitCache());
-    static const bool trace = std::getenv("EPSILON_HIP_INIT_TRACE") != nullptr;
+    static const bool trace = opt::IsSet(opt::kInitTrace);  // any value, 0 included
     auto mark = [&](const char* what) {  // host wall clock + device drain, debugging aid only
       if (!trace) return;
       const double th = Now();
@@ -345,10 +346,8 @@ class ProxADMMSolver final : public Solver {
   // jitter would otherwise sit on the critical path.  Iterates are bit-identical to the eager
   // launches (same kernels, same arguments; the exchange tags come from a device counter).
   void SweepBatch(int count) override {
-    static const int mode = [] {  // EPSILON_HIP_GRAPH: 0 never, 1 always (fused), default: peer mode
-      const char* e = std::getenv("EPSILON_HIP_GRAPH");
-      return e ? std::atoi(e) : -1;
-    }();
+    // EPSILON_HIP_GRAPH: 0 never, 1 always (fused), default: peer mode
+    static const int mode = opt::Int(opt::kGraph, -1);
     Runtime& rt = Runtime::Get();
     const bool want = route_ && route_->Capturable() && (mode == 1 || (mode != 0 && route_->CaptureByDefault()));
     if (!want || count < 2 || rt.profiling()) {

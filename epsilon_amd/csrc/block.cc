@@ -9,6 +9,7 @@
 
 #include "comm.h"
 #include "kernels.h"
+#include "options.h"
 
 namespace eps {
 
@@ -549,7 +550,7 @@ namespace {
 // error by ~ cond * 6e-8 again, down to cond(KKT) * 6e-8.  EPSILON_HIP_REFINE = <steps> forces a
 // count (0 = the unrefined reference sequence of operations), "auto" / unset = by estimate.
 int RefineStepsFor(double cond) {
-  if (const char* e = std::getenv("EPSILON_HIP_REFINE")) {
+  if (const char* e = opt::Raw(opt::kRefine)) {
     if (e[0] >= '0' && e[0] <= '9') return std::atoi(e);
   }
   if (!(cond > 1e3)) return 0;  // unrefined error <= ~1e-4, the fp32 mode's stated tolerance

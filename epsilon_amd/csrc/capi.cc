@@ -16,9 +16,9 @@
 #include "admm.h"
 #include "block.h"
 #include "comm.h"
-#include "fused_route.h"
 #include "kernels.h"
 #include "linear_map.h"
+#include "options.h"
 #include "wire.h"
 
 using namespace eps;
@@ -42,7 +42,7 @@ int g_dtype_option = -1;  // -1: take EPSILON_HIP_DTYPE / default
 
 DType ConfiguredDType() {
   if (g_dtype_option >= 0) return static_cast<DType>(g_dtype_option);
-  const char* e = std::getenv("EPSILON_HIP_DTYPE");
+  const char* e = opt::Raw(opt::kDtype);
   if (e && (std::strcmp(e, "f64") == 0 || std::strcmp(e, "float64") == 0)) return F64;
   return F32;
 }
@@ -400,37 +400,10 @@ int eps_set_option(const char* key, const char* value) {
       if (std::strcmp(value, "f32") == 0) g_dtype_option = F32;
       else if (std::strcmp(value, "f64") == 0) g_dtype_option = F64;
       else EPS_FATAL("dtype must be f32 or f64, got " << value);
-    } else if (std::strcmp(key, "device") == 0) {
-      setenv("EPSILON_HIP_DEVICE", value, 1);
-    } else if (std::strcmp(key, "gemm") == 0) {
-      setenv("EPSILON_HIP_GEMM", value, 1);
     } else if (std::strcmp(key, "profile_filter") == 0) {
       Runtime::Get().set_prof_filter(value);
-    } else if (std::strcmp(key, "fused") == 0) {
-      setenv("EPSILON_HIP_FUSED", value, 1);
-    } else if (std::strcmp(key, "batch_wide") == 0) {
-      (void)ParseChoiceOption(key, value);  // a bad value is an error here, not at the next read
-      setenv("EPSILON_HIP_BATCH_WIDE", value, 1);
-    } else if (std::strcmp(key, "fused_matrix") == 0) {
-      (void)ParseChoiceOption(key, value);
-      setenv("EPSILON_HIP_FUSED_MATRIX", value, 1);
-    } else if (std::strcmp(key, "fused_zero") == 0) {
-      (void)ParseChoiceOption(key, value);
-      setenv("EPSILON_HIP_FUSED_ZERO", value, 1);
-    } else if (std::strcmp(key, "fused_zero_tall") == 0) {
-      (void)ParseChoiceOption(key, value);
-      setenv("EPSILON_HIP_FUSED_ZERO_TALL", value, 1);
-    } else if (std::strcmp(key, "fused_zero_tall_smooth") == 0) {
-      (void)ParseChoiceOption(key, value);
-      setenv("EPSILON_HIP_FUSED_ZERO_TALL_SMOOTH", value, 1);
-    } else if (std::strcmp(key, "fused_resident") == 0) {
-      (void)ParseFusedResident(value);  // a bad value is an error here, not at the next Init
-      setenv("EPSILON_HIP_FUSED_RESIDENT_KB", value, 1);
-    } else if (std::strcmp(key, "refine") == 0) {
-      if (std::strcmp(value, "auto") == 0) unsetenv("EPSILON_HIP_REFINE");
-      else setenv("EPSILON_HIP_REFINE", value, 1);
     } else {
-      EPS_FATAL("unknown option " << key);
+      opt::Set(key, value);  // every key stored in the environment: the table of options.cc
     }
   });
 }
@@ -984,7 +957,7 @@ int eps_bench_gemm(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, in
     // EPSILON_HIP_BENCH_RANDOM=1: operands with independent pseudo-random entries instead of the
     // repeating 1024-value pattern (the Gram product inside a solve multiplies random data and
     // runs 4.8 ms slower than this microbenchmark on the pattern: is it the data?)
-    const bool rnd = std::getenv("EPSILON_HIP_BENCH_RANDOM") != nullptr;
+    const bool rnd = opt::IsSet(opt::kBenchRandom);
     auto operand = [&](int64_t count, uint64_t seed) {
       if (!rnd) return Synthetic(count, dt, 1.0);
       DVec v = DVec::Empty(count, dt);

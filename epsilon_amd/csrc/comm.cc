@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "options.h"
 
 namespace eps {
 
@@ -36,7 +37,7 @@ bool ShardSpec::active() const {
   if (c == nullptr) return false;
   // EPSILON_HIP_FORCE_SHARDED=1 runs the sharded code path (and its collectives) on a
   // single-rank communicator: lets a 1-GPU box exercise the RCCL backend end to end.
-  static const bool force = std::getenv("EPSILON_HIP_FORCE_SHARDED") != nullptr;
+  static const bool force = opt::IsSet(opt::kForceSharded);
   return c->size() > 1 || force;
 }
 
@@ -61,7 +62,7 @@ struct RcclApi {
 RcclApi& Api() {
   static RcclApi api;
   if (api.handle) return api;
-  const char* env = std::getenv("EPSILON_HIP_RCCL");
+  const char* env = opt::Raw(opt::kRccl);
   void* h = nullptr;
   if (env) h = dlopen(env, RTLD_NOW | RTLD_LOCAL);
   // prefer the copy a host framework (torch) already loaded, so one RCCL lives in the process
@@ -190,7 +191,7 @@ enum WindowMemory { kWindowUncached = 0, kWindowFineGrained = 1, kWindowPlain = 
 
 void* AllocWindow(size_t bytes, WindowMemory* kind) {
   void* p = nullptr;
-  const char* force = std::getenv("EPSILON_HIP_PEER_WINDOW_MEMORY");  // tests: "plain"
+  const char* force = opt::Raw(opt::kPeerWindowMemory);  // tests: "plain"
   const bool plain_only = force && std::strcmp(force, "plain") == 0;
   if (!plain_only) {
 #ifdef hipDeviceMallocUncached

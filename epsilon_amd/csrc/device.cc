@@ -13,6 +13,7 @@
 
 #include "comm.h"
 #include "kernels.h"
+#include "options.h"
 
 namespace eps {
 
@@ -32,9 +33,7 @@ Runtime::Runtime() {
     EPS_FATAL("no HIP device available: the epsilon_hip solver has no CPU fallback ("
               << hipGetErrorString(e) << ")");
   }
-  const char* env = std::getenv("EPSILON_HIP_DEVICE");
-  if (env == nullptr) env = std::getenv("LOCAL_RANK");
-  device_ = env ? std::atoi(env) % count : 0;
+  device_ = opt::DeviceOrdinal(0) % count;
   EPS_HIP(hipSetDevice(device_));
   EPS_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
   EPS_HIP(hipMalloc(reinterpret_cast<void**>(&slots_dev_), 2 * kMaxSlots * sizeof(double)));
@@ -279,8 +278,7 @@ PinnedStage* GetPinnedStage() {
 
 int HostThreads() {
   static const int n = [] {
-    const char* e = std::getenv("EPSILON_HIP_HOST_THREADS");
-    int v = e ? std::atoi(e) : 0;
+    int v = opt::Int(opt::kHostThreads, 0);
     if (v <= 0) {
       v = static_cast<int>(std::thread::hardware_concurrency());
       if (v > 16) v = 16;  // (a container's CPU quota is usually far below the host's core count)
@@ -320,10 +318,7 @@ template <class D> bool UploadThroughPinned(D* dev, const double* src, int64_t n
   const int64_t chunk = static_cast<int64_t>(PinnedStage::kBytes / sizeof(D));
   int which = 0;
   bool used[2] = {false, false};
-  static const bool trace = [] {
-    const char* e = std::getenv("EPSILON_HIP_INIT_TRACE");
-    return e && e[0] == '2';
-  }();
+  static const bool trace = opt::InitTraceLevel() >= 2;
   const auto t0 = std::chrono::steady_clock::now();
   double conv_ms = 0;
   for (int64_t off = 0; off < n; off += chunk, which ^= 1) {
@@ -426,6 +421,11 @@ template <class S> bool DownloadThroughPinned(double* dst, const S* dev, int64_t
   }
   return true;
 }
+
+bool PinnedEnabled() {  // EPSILON_HIP_PINNED_UPLOAD=0: plain staged copies both ways
+  static const bool on = !opt::Is0(opt::kPinnedUpload);
+  return on;
+}
 }  // namespace
 
 DVec DVec::FromHost(const double* src, int64_t n, DType dt) {
@@ -434,11 +434,7 @@ DVec DVec::FromHost(const double* src, int64_t n, DType dt) {
   Runtime& rt = Runtime::Get();
   // 64 MB of doubles and more (pinning the two buffers costs 10-70 ms once per process: a 60 MB
   // matrix is quicker through the plain copy)
-  static const bool pinned_on = [] {
-    const char* e = std::getenv("EPSILON_HIP_PINNED_UPLOAD");
-    return !(e && e[0] == '0');
-  }();
-  if (pinned_on && n >= (int64_t(1) << 23)) {
+  if (PinnedEnabled() && n >= (int64_t(1) << 23)) {
     const bool ok = dt == F64 ? UploadThroughPinned(v.as<double>(), src, n, rt.stream())
                               : UploadThroughPinned(v.as<float>(), src, n, rt.stream());
     if (ok) return v;
@@ -495,11 +491,7 @@ void DVec::ToHost(double* dst) const {
   // Large vectors (the 10^8-entry iterates of configs 3 and 5): in their own type over the link
   // into pinned buffers, widened to the boundary's float64 by the host threads meanwhile - a
   // pageable copy of converted doubles moved twice the bytes at a fifth of the rate.
-  static const bool pinned_ok = [] {
-    const char* e = std::getenv("EPSILON_HIP_PINNED_UPLOAD");
-    return !(e && e[0] == '0');
-  }();
-  if (pinned_ok && n >= (int64_t(1) << 22)) {
+  if (PinnedEnabled() && n >= (int64_t(1) << 22)) {
     const bool done = dt == F64 ? DownloadThroughPinned(dst, as<double>(), n, rt.stream())
                                 : DownloadThroughPinned(dst, as<float>(), n, rt.stream());
     if (done) return;

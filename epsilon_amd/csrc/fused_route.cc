@@ -6,13 +6,13 @@
 #include <algorithm>
 #include <array>
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <map>
 
 #include "admm.h"
 #include "comm.h"
 #include "kernels.h"
+#include "options.h"
 
 namespace eps {
 namespace {
@@ -69,10 +69,7 @@ struct InverseApply {
     w = w_;
     if (!D->symmetric() || D->rows() != m || m < 1024 || D->trans()) return;
     work = DVec::Empty(count * k::SymvWorkspace(m), p.dt);
-    static const bool pack = [] {
-      const char* e = std::getenv("EPSILON_HIP_SYMV_PACKED");
-      return !(e && e[0] == '0');
-    }();
+    static const bool pack = opt::SymvPacked() != opt::kSymvPackedOff;
     if (!pack) return;
     uint64_t key = 0;
     if (shared != nullptr) {
@@ -124,54 +121,18 @@ std::vector<BlockVector*> Homes(const MultiBlockParts& a) {
   return h;
 }
 
-bool FusedDisabled() {  // EPSILON_HIP_FUSED=0 (eps_set_option "fused"), read at every Init
-  const char* env = std::getenv("EPSILON_HIP_FUSED");
-  return env && env[0] == '0';
-}
-
 int BatchWideMin();  // (with the batched solves below)
 
-// The options with a choice of words (ParseChoiceOption): the variable that holds the option, its
-// words in the order of their indices, the error's text and the word that holds while the variable
-// is unset.  "fused_zero", "fused_zero_tall", "fused_zero_tall_smooth" and "fused_matrix" are read
-// at every Init,
-// "batch_wide" per batch ("1" sends eligible groups to the wide route).
-const struct ChoiceOption {
-  const char *name, *env, *words[5], *error, *unset;
-} kChoiceOptions[] = {
-    {"fused_zero", "EPSILON_HIP_FUSED_ZERO", {"0", "auto"}, "fused_zero must be 0 or auto, got ", "auto"},
-    {"fused_zero_tall", "EPSILON_HIP_FUSED_ZERO_TALL", {"0", "1", "auto"},
-     "fused_zero_tall must be 0, 1 or auto, got ", "auto"},
-    {"fused_zero_tall_smooth", "EPSILON_HIP_FUSED_ZERO_TALL_SMOOTH", {"0", "1", "auto"},
-     "fused_zero_tall_smooth must be 0, 1 or auto, got ", "auto"},
-    {"fused_matrix", "EPSILON_HIP_FUSED_MATRIX", {"0", "pass", "wide", "auto"},
-     "fused_matrix must be 0, pass, wide or auto, got ", "auto"},
-    {"batch_wide", "EPSILON_HIP_BATCH_WIDE", {"0", "1"}, "batch_wide must be 0 or 1, got ", "0"},
-};
+// The indices of the options' words (options.cc).  "fused" (off with a leading 0), "fused_zero",
+// "fused_zero_tall", "fused_zero_tall_smooth", "fused_matrix" and "fused_resident" are read at
+// every Init, "batch_wide" per batch ("1" sends eligible groups to the wide route).
 enum ZeroTallMode { kZeroTallOff, kZeroTallOn, kZeroTallAuto };  // of either tall option
 enum MatrixRoute { kMatrixOff, kMatrixPass, kMatrixWide, kMatrixAuto };
-
-// The option as its variable holds it now.
-int ChoiceOptionNow(const char* name) {
-  for (const ChoiceOption& o : kChoiceOptions) {
-    if (std::strcmp(o.name, name) != 0) continue;
-    const char* e = std::getenv(o.env);
-    return ParseChoiceOption(name, e != nullptr ? e : o.unset);
-  }
-  EPS_FATAL("unknown option " << name);
-}
 
 // What the Infinity Cache holds of lines loaded with the default policy before re-reads start to
 // miss: the upper end of the plateau of the budget sweep on the pass ("A resident
 // slab of the streamed matrix").
 constexpr int64_t kResidentLimitBytes = int64_t(224) << 20;
-
-// EPSILON_HIP_FUSED_RESIDENT_KB (eps_set_option "fused_resident"), read at every Init: the budget
-// in bytes, -1 for "auto".
-int64_t FusedResidentOption() {
-  const char* e = std::getenv("EPSILON_HIP_FUSED_RESIDENT_KB");
-  return e == nullptr ? -1 : ParseFusedResident(e);
-}
 
 // The share of the pass's m x n matrix that stays in the Infinity Cache (k::LassoFusedResidency)
 // under the option, written into `pass` when one is given.  `touched`: the values the sweep itself
@@ -180,7 +141,7 @@ int64_t FusedResidentOption() {
 //  - there "auto" streams everything and only an explicit number of KiB gives a share.
 k::FusedResidency ResidentShare(int64_t m, int64_t n, DType dt, int64_t touched, bool auto_on,
                                 k::LassoFusedArgs* pass = nullptr) {
-  int64_t budget = FusedResidentOption();
+  int64_t budget = opt::FusedResident();
   if (budget < 0) budget = auto_on ? std::max<int64_t>(0, kResidentLimitBytes - touched * (dt == F32 ? 4 : 8)) : 0;
   const k::FusedResidency res = k::LassoFusedResidency(m, n, dt, budget);
   if (pass != nullptr) {
@@ -391,13 +352,13 @@ struct LassoRoute final : BatchRoute {
   k::FusedResidency Residency(int64_t count) const override { return Residency(count, nullptr); }
 
   bool Enable(const MultiBlockParts& a) {
-    if (FusedDisabled() || a.prox.size() != 2 || a.num_constraints != 1 || !a.b.data().empty()) return false;
+    if (opt::Is0(opt::kFused) || a.prox.size() != 2 || a.num_constraints != 1 || !a.b.data().empty()) return false;
     const ShardSpec& sh = ShardSpec::Get();
     // consensus form: the threshold step averages over the ranks, which the fused pass does not
     if (sh.active() && sh.consensus_terms()) return false;
     if (!a.prox[0]->DescribeLeastSquares(&ls)) return false;
     cols = ls.cols;
-    const int matrix_mode = cols > 1 ? ChoiceOptionNow("fused_matrix") : kMatrixAuto;
+    const int matrix_mode = cols > 1 ? opt::Word(opt::kFusedMatrix) : kMatrixAuto;
     if (cols > 1 && (matrix_mode == kMatrixOff || sh.active())) return false;
     if (!a.prox[1]->DescribeScaledZone(&sz)) {
       // group lasso: one group per row of the n x cols variable
@@ -467,7 +428,7 @@ struct LassoRoute final : BatchRoute {
       // EPSILON_HIP_SHARDED_APPLY=replicated: every rank applies the whole inverse instead (no
       // all-gather; m^2 bytes per rank) - the cheaper form when the collective's latency exceeds
       // the apply, to be decided on the machine
-      const char* e = std::getenv("EPSILON_HIP_SHARDED_APPLY");
+      const char* e = opt::Raw(opt::kShardedApply);
       replicated_apply = e && e[0] == 'r';
       const bool want_slab = e ? !replicated_apply : G >= 3;
       peer_slab = use_peer && want_slab && k::PeerSlabApplySupported(px->view(), m, slab, ls.Dinv_arg->data(), m);
@@ -732,10 +693,7 @@ struct LassoRoute final : BatchRoute {
   //   ||A^T u||^2 = (a0^2 + a1^2) ||u||^2.
   bool HasCheck() const override { return true; }
   bool PipelineChecks() const override {
-    static const bool off = [] {
-      const char* e = std::getenv("EPSILON_HIP_PIPELINE_CHECKS");
-      return e && e[0] == '0';
-    }();
+    static const bool off = opt::Is0(opt::kPipelineChecks);
     return !off;
   }
   // the check's six scalars into the next six slots
@@ -840,7 +798,7 @@ struct ZeroRoute final : BatchRoute {
   // `tall_mode`, `tall_smooth_mode`: the options "fused_zero_tall" and "fused_zero_tall_smooth";
   // under "auto" the measured floors apply
   bool Enable(const MultiBlockParts& a, int tall_mode, int tall_smooth_mode) {
-    if (FusedDisabled() || ShardSpec::Get().active() || !a.b.data().empty()) return false;
+    if (opt::Is0(opt::kFused) || ShardSpec::Get().active() || !a.b.data().empty()) return false;
     const int nc = a.num_constraints, N = static_cast<int>(a.prox.size());
     if (nc < 1 || nc > 2 || N != nc + 1) return false;
     if (!a.prox[N - 1]->DescribeZeroProjection(&zp)) return false;
@@ -1158,7 +1116,7 @@ struct TwoBlockRoute final : FusedRoute {
   k::LassoFusedArgs pass;
 
   bool Enable(const TwoBlockParts& a) {
-    if (FusedDisabled() || a.prox.size() != 2 || a.num_constraints != 1) return false;
+    if (opt::Is0(opt::kFused) || a.prox.size() != 2 || a.num_constraints != 1) return false;
     if (ShardSpec::Get().active() || !a.constr_H.b.data().empty()) return false;
     if (!a.prox[0]->DescribeLeastSquares(&ls) || !a.prox[1]->DescribeScaledZone(&sz)) return false;
     if (ls.cols != 1) return false;  // matrix variables: the multi-block driver only
@@ -1240,33 +1198,10 @@ std::unique_ptr<FusedRoute> Recognise(const Parts& parts, Options... options) {
 
 }  // namespace
 
-int64_t ParseFusedResident(const char* value) {
-  if (std::strcmp(value, "auto") == 0) return -1;
-  const int64_t cap = int64_t(1) << 40;  // KiB: far beyond any matrix, and kb * 1024 cannot overflow
-  int64_t kb = 0;
-  bool ok = value[0] != '\0';
-  for (const char* c = value; ok && *c != '\0'; ++c) {
-    ok = *c >= '0' && *c <= '9';
-    if (ok) kb = std::min(cap, kb * 10 + (*c - '0'));
-  }
-  if (!ok) EPS_FATAL("fused_resident must be auto or a number of KiB, got " << value);
-  return kb * 1024;
-}
-
-int ParseChoiceOption(const char* name, const char* value) {
-  for (const ChoiceOption& o : kChoiceOptions) {
-    if (std::strcmp(o.name, name) != 0) continue;
-    for (int i = 0; o.words[i] != nullptr; ++i)
-      if (std::strcmp(o.words[i], value) == 0) return i;
-    EPS_FATAL(o.error << value);
-  }
-  EPS_FATAL("unknown option " << name);
-}
-
 std::unique_ptr<FusedRoute> RecogniseMultiBlockRoute(const MultiBlockParts& parts) {
-  const bool zero = ChoiceOptionNow("fused_zero") != 0;  // (read first: a bad value is an error whatever the problem)
-  const int tall = ChoiceOptionNow("fused_zero_tall");
-  const int tall_smooth = ChoiceOptionNow("fused_zero_tall_smooth");
+  const bool zero = opt::Word(opt::kFusedZero) != 0;  // (read first: a bad value is an error whatever the problem)
+  const int tall = opt::Word(opt::kFusedZeroTall);
+  const int tall_smooth = opt::Word(opt::kFusedZeroTallSmooth);
   if (auto r = Recognise<LassoRoute>(parts)) return r;
   if (!zero) return nullptr;
   return Recognise<ZeroRoute>(parts, tall, tall_smooth);  // fat, then tall
@@ -1375,8 +1310,8 @@ void RunPassGroup(const Group& g) {
 // (DESIGN.md 3.8), rounded up to a multiple of 8.
 constexpr int kWideMin = 8;
 int BatchWideMin() {  // EPSILON_HIP_BATCH_WIDE_MIN: tuning knob (the crossover measurements)
-  const char* e = std::getenv("EPSILON_HIP_BATCH_WIDE_MIN");
-  return e && std::atoi(e) >= 2 ? std::atoi(e) : kWideMin;
+  const int v = opt::Int(opt::kBatchWideMin, 0);
+  return v >= 2 ? v : kWideMin;
 }
 
 // The wide route (kernels_fused_wide.hip), lasso members alone: RunPassGroup's schedule and residual checks, with the
@@ -1441,7 +1376,7 @@ void RunWideGroup(const Group& g) {
 
 std::vector<bool> RunFusedBatches(const std::vector<Solver*>& solvers) {
   std::vector<bool> ran(solvers.size(), false);
-  const bool wide = ChoiceOptionNow("batch_wide") != 0;
+  const bool wide = opt::Word(opt::kBatchWide) != 0;
   std::map<std::vector<uint64_t>, std::vector<size_t>> groups;
   std::vector<BatchRoute*> routes(solvers.size(), nullptr);
   std::vector<std::vector<uint64_t>> order;  // groups in order of their first instance

@@ -62,16 +62,6 @@ struct TwoBlockParts {
 
 // The route of the problem, or null: the lasso structure, then the ZERO-term structure
 // (multi-block driver); the lasso structure in two-block form.
-// The option "fused_resident" (eps_set_option, EPSILON_HIP_FUSED_RESIDENT_KB): "auto" gives -1, a
-// number of KiB (decimal digits alone) its bytes, clamped to 2^50; anything else is an error that
-// names the value.
-int64_t ParseFusedResident(const char* value);
-// The options with a choice of words - "fused_zero" (0, auto), "fused_zero_tall" and
-// "fused_zero_tall_smooth" (0, 1, auto), "fused_matrix" (0, pass, wide, auto) and "batch_wide" (0, 1), each with its variable
-// EPSILON_HIP_<NAME>: the position of `value` among the option's words in this order; anything
-// else is an error that names the option, its words and the value.
-int ParseChoiceOption(const char* name, const char* value);
-
 std::unique_ptr<FusedRoute> RecogniseMultiBlockRoute(const MultiBlockParts& parts);
 std::unique_ptr<FusedRoute> RecogniseTwoBlockRoute(const TwoBlockParts& parts);
 

@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "options.h"
 
 namespace eps {
 namespace k {
@@ -619,7 +620,7 @@ void PotrfBlocked(const DVec& W, int64_t n, const DVec& dinv, int* flag) {
     // formed for all blocks at once at the end.
     // (read per call: tests compare the two forms in one process, eps_test_spd_inverse_repeat)
     const bool two_kernels = g_potrf_form == 1 ||
-                             (g_potrf_form < 0 && std::getenv("EPSILON_HIP_POTRF_TWO_KERNELS") != nullptr);
+                             (g_potrf_form < 0 && opt::IsSet(opt::kPotrfTwoKernels));
     const unsigned nblk = static_cast<unsigned>((n + NB - 1) / NB);
     const bool fused = dt == F32 && !two_kernels;
     std::shared_ptr<Buffer> dfac_buf;

@@ -30,6 +30,7 @@
 
 #include "kernels.h"
 #include "kernels_fused_chain.h"
+#include "options.h"
 
 namespace eps {
 namespace k {
@@ -719,8 +720,8 @@ int LassoFusedBlock(int64_t m, int64_t n, DType dt) {
   (void)n;
   if (dt == F64) return m > 5 * 1024 ? 512 : 256;
   if (m > 10 * 1024) return 512;
-  static const char* env = std::getenv("EPSILON_HIP_FUSED_BLOCK");
-  if (env && std::atoi(env) == 512 && m >= 2048) return 512;
+  static const int block = opt::Int(opt::kFusedBlock, 0);
+  if (block == 512 && m >= 2048) return 512;
   return 256;
 }
 
@@ -731,8 +732,8 @@ int LassoFusedGrid(int64_t m, int64_t n, DType dt) {
   const int64_t rows_per_chunk = dt == F32 ? 4 : 2;
   const bool one_per_cu = LassoFusedBlock(m, n, dt) == 512 && m > 512 * 5 * rows_per_chunk;
   int64_t g = one_per_cu ? 256 : 512;
-  static const char* env = std::getenv("EPSILON_HIP_FUSED_GRID");  // tuning knob
-  if (env && std::atoi(env) > 0) g = std::atoi(env);
+  static const int grid = opt::Int(opt::kFusedGrid, 0);  // tuning knob
+  if (grid > 0) g = grid;
   if (g > npairs) g = npairs;
   if (g < 1) g = 1;
   // equal shares: with `per` column pairs per workgroup, ceil(npairs / per) workgroups leave no

@@ -23,6 +23,7 @@
 #include <cstring>
 
 #include "kernels.h"
+#include "options.h"
 
 namespace eps {
 namespace k {
@@ -656,16 +657,13 @@ __global__ __launch_bounds__(256) void GemmSmallKernel(int tA, int tB, int64_t M
 }
 
 bool SmallGemmWanted(int64_t M, int64_t N, int64_t K) {
-  static const bool off = [] {
-    const char* e = std::getenv("EPSILON_HIP_GEMM_SMALL");
-    return e && e[0] == '0';
-  }();
+  static const bool off = opt::Is0(opt::kGemmSmall);
   return !off && M >= 1 && N >= 1 && M <= 256 && N <= 256 && K <= 4096;
 }
 
 int GemmMode() {  // 0 auto, 1 generic, 2 mfma, 3 mfma without the pipelined kernel
   // (read on every call: eps_set_option("gemm", ...) switches it between products in the tests)
-  const char* e = std::getenv("EPSILON_HIP_GEMM");
+  const char* e = opt::Raw(opt::kGemm);
   int mode = 0;
   if (e && std::strcmp(e, "generic") == 0) mode = 1;
   if (e && std::strcmp(e, "mfma") == 0) mode = 2;
@@ -776,7 +774,7 @@ void GemmBatched(bool transA, bool transB, int64_t M, int64_t N, int64_t K, doub
     if (aligned && mode != 3) {
       const float al = static_cast<float>(alpha), be = static_cast<float>(beta);
       int lo = lower_only ? 1 : 0;
-      static const bool compact = std::getenv("EPSILON_HIP_SYRK_2D") == nullptr;
+      static const bool compact = !opt::IsSet(opt::kSyrk2d);
       int64_t lin0 = 0, kchunk = 0, tail = 0;
       int S = 1;
       float* P = nullptr;
@@ -791,10 +789,7 @@ void GemmBatched(bool transA, bool transB, int64_t M, int64_t N, int64_t K, doub
         // holds 512, a seventh round as long as the six full ones.  The tail tiles are split over
         // K instead (S chunks each, S * tail <= 512: one short round), their partial tiles summed
         // in a fixed order by a fix-up launch.
-        static const bool split_tail = [] {
-          const char* e = std::getenv("EPSILON_HIP_SYRK_TAIL");
-          return !(e && e[0] == '0');
-        }();
+        static const bool split_tail = !opt::Is0(opt::kSyrkTail);
         const int64_t slots = 512;
         tail = total % slots;
         if (split_tail && K >= 8192 && total > slots && tail > 0 && tail <= slots / 2) {

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "options.h"
 
 namespace eps {
 namespace k {
@@ -686,15 +687,14 @@ struct ConvertedOperand {
 // EPSILON_HIP_GEMM_STAGE = reg: the register-staged loop (V = 0); EPSILON_HIP_GEMM_ORDER = 0: tiles
 // in plain linear order.  Read on every call (the microbenchmark switches them between launches).
 int StageVariant() {
-  const char* e = std::getenv("EPSILON_HIP_GEMM_STAGE");
+  const char* e = opt::Raw(opt::kGemmStage);
   if (e == nullptr) return 3;
   if (std::strcmp(e, "reg") == 0) return 0;  // register-staged, padded image (round 2)
   if (std::strcmp(e, "lds") == 0) return 1;  // LDS-DMA, two 32-deep buffers, compiler-scheduled
   return 3;                                   // "ring": four 16-deep steps
 }
 bool PatchOrderEnabled() {
-  const char* e = std::getenv("EPSILON_HIP_GEMM_ORDER");
-  return !(e != nullptr && e[0] == '0');
+  return !opt::Is0(opt::kGemmOrder);
 }
 
 // The tiles of a TI x TJ grid (lower: J <= I only) in patch-major order, as (I << 16 | J) words on
@@ -784,15 +784,12 @@ ConvertedOperand ConvertOperand(const float* X, int64_t rows, int64_t K, int64_t
 // EPSILON_HIP_GEMM = generic / mfma / mfma_simple forces another kernel family (read on every
 // call: the tests switch it between products)
 bool AutoKernelChoice() {
-  const char* e = std::getenv("EPSILON_HIP_GEMM");
+  const char* e = opt::Raw(opt::kGemm);
   return e == nullptr || e[0] == 0 || std::strcmp(e, "auto") == 0;
 }
 
 bool SplitEnabled() {
-  static const bool off = [] {
-    const char* e = std::getenv("EPSILON_HIP_GRAM_F16SPLIT");
-    return e && e[0] == '0';
-  }();
+  static const bool off = opt::Is0(opt::kGramF16Split);
   return !off;
 }
 

@@ -31,6 +31,7 @@
 
 #include "kernels.h"
 #include "kernels_smooth_fn.h"
+#include "options.h"
 
 namespace eps {
 namespace k {
@@ -1321,8 +1322,9 @@ struct GridZoneEpi {
 // slices at least this long, and few of them, take the grid-wide route
 constexpr int64_t kGridMinLen = int64_t(1) << 17;
 inline bool UseGridRoute(const Segs& S) {
-  const char* e = std::getenv("EPSILON_HIP_SEG_GRID");  // "0": one workgroup per slice whatever its length
-  if (e && e[0] == '0') return false;                  // (read per call: the tests compare the two routes)
+  // EPSILON_HIP_SEG_GRID=0: one workgroup per slice whatever its length (read per call: the tests
+  // compare the two routes)
+  if (opt::Is0(opt::kSegGrid)) return false;
   return S.count >= 1 && S.count <= 8 && S.len >= kGridMinLen;
 }
 

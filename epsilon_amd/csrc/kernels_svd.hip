@@ -18,6 +18,7 @@
 
 #include "comm.h"
 #include "kernels.h"
+#include "options.h"
 
 namespace eps {
 namespace k {
@@ -445,11 +446,22 @@ __global__ __launch_bounds__(512) void SmallJacobiSvdFastKernel(float* Wg, int m
 }
 
 bool SmallFastEnabled() {
-  static const bool off = [] {
-    const char* e = std::getenv("EPSILON_HIP_SVD_SMALL_FAST");
-    return e && e[0] == '0';
-  }();
+  static const bool off = opt::Is0(opt::kSvdSmallFast);
   return !off;
+}
+
+// EPSILON_HIP_SVD = "scalar" | "block": the first letter of a forced form, 0 without one (read
+// per call: the tests force a form in-process).
+char SvdForm() {
+  const char* e = opt::Raw(opt::kSvd);
+  return e != nullptr ? e[0] : '\0';
+}
+bool SvdVerbose() { return opt::IsSet(opt::kSvdVerbose); }
+// EPSILON_HIP_SVD_MFMA=0: the block form without the matrix-core kernels.  One value for the
+// process: JacobiSvdCanSkipV must predict what BlockJacobiImpl does.
+bool SvdMfmaOff() {
+  static const bool off = opt::Is0(opt::kSvdMfma);
+  return off;
 }
 
 // false: shape outside the fast kernel's range (the general kernel takes it).  keep_v == false: V is
@@ -1101,12 +1113,11 @@ int BlockJacobiImpl(const DVec& W, int64_t m, int64_t n, const DVec& V, int max_
   hipStream_t s = rt.stream();
   const DType dt = W.dt;
   // fp32: Gram, rotation solve and update on the matrix-core / fast-rotation kernels
-  static const bool mfma_off = [] {
-    const char* e = std::getenv("EPSILON_HIP_SVD_MFMA");
-    return e && e[0] == '0';
-  }();
   if constexpr (kMfma) {
-    if (mfma_off) return BlockJacobiImpl<T, false>(W, m, n, V, max_sweeps, warm, row_sharded);
+    if (SvdMfmaOff()) {
+      EPS_CHECK(keep_v);  // (the form below accumulates V: JacobiSvdCanSkipV refuses this case)
+      return BlockJacobiImpl<T, false>(W, m, n, V, max_sweeps, warm, row_sharded);
+    }
   }
   if (!kMfma) keep_v = true;
   int64_t nb = (n + kJB - 1) / kJB;
@@ -1120,10 +1131,7 @@ int BlockJacobiImpl(const DVec& W, int64_t m, int64_t n, const DVec& V, int max_
   // `last_below` ends below last_below^2 / (relative gaps) - with 3e-4 that is 1e-7 against the
   // 3e-6 floor of the fp32 Gram products - and the sweep that would only confirm it (one of the
   // 4-5 sweeps of a warm-started decomposition) is not run.  EPSILON_HIP_SVD_CONFIRM=1 runs it.
-  static const bool confirm = [] {
-    const char* e = std::getenv("EPSILON_HIP_SVD_CONFIRM");
-    return e && e[0] == '1';
-  }();
+  static const bool confirm = opt::Is1(opt::kSvdConfirm);
   const double stop_tol = done_tol;
   const double last_below = (dt == F32 && !confirm) ? 3e-4 : 0.0;
   // split-K for the Gram products so that more than h workgroups run; rows are padded with
@@ -1138,8 +1146,8 @@ int BlockJacobiImpl(const DVec& W, int64_t m, int64_t n, const DVec& V, int max_
   if constexpr (kMfma) {
     // matrix-core Gram: a workgroup is four waves that each take every fourth 32-row block of the
     // chunk; enough workgroups (~5 per CU) that the dispatcher evens out the CUs
-    static const char* ns_env = std::getenv("EPSILON_HIP_SVD_NSPLIT");  // tuning knob
-    const int64_t want = ns_env && std::atoi(ns_env) > 0 ? std::atoi(ns_env) : 512;
+    static const int ns = opt::Int(opt::kSvdNsplit, 0);  // tuning knob
+    const int64_t want = ns > 0 ? ns : 512;
     while (nsplit < 16 && h * nsplit < want && m_ref / (nsplit * 2) >= 256) nsplit *= 2;
   } else {
     while (nsplit < 8 && h * nsplit < 512 && m_ref / (nsplit * 2) >= 256) nsplit *= 2;
@@ -1208,10 +1216,10 @@ int BlockJacobiImpl(const DVec& W, int64_t m, int64_t n, const DVec& V, int max_
     skip_buf = rt.Alloc(static_cast<size_t>(h) * sizeof(int32_t));
     skip_dev = static_cast<int32_t*>(skip_buf->p);
   }
-  static const char* inner_env = std::getenv("EPSILON_HIP_SVD_INNER");  // tuning knob
+  static const int inner_opt = opt::Int(opt::kSvdInner, 0);  // tuning knob
   // one inner sweep per step: measured 7-18 % faster than two, cold and warm-started, at n = 2048
   // and 4096 (three is slower still); the outer iteration absorbs what an inner sweep leaves
-  const int inner = inner_env && std::atoi(inner_env) > 0 ? std::atoi(inner_env) : 1;
+  const int inner = inner_opt > 0 ? inner_opt : 1;
   int sweeps = 0;
   float prev_mx = 1e30f;
   for (; sweeps < max_sweeps; ++sweeps) {
@@ -1286,7 +1294,7 @@ int BlockJacobiImpl(const DVec& W, int64_t m, int64_t n, const DVec& V, int max_
     EPS_HIP(hipStreamSynchronize(s));
     float mx;
     std::memcpy(&mx, &bits, sizeof(mx));
-    if (std::getenv("EPSILON_HIP_SVD_VERBOSE"))
+    if (SvdVerbose())
       std::fprintf(stderr, "block jacobi sweep %d: max |cos| %.3e\n", sweeps, static_cast<double>(mx));
     // converged, or stagnating at the noise floor of the Gram products (fp32: ~1e-5)
     if (mx <= stop_tol || mx <= last_below || (sweeps >= 3 && mx < 1e-3f && mx >= 0.5f * prev_mx)) {
@@ -1332,19 +1340,10 @@ int BlockJacobiSvd(const DVec& W, int64_t m, int64_t n, const DVec& V, int max_s
 bool JacobiSvdCanSkipV(int64_t m, int64_t n, DType dt) {
   if (dt != F32 || m == 0) return false;
   // the one-launch on-chip kernel (robust PCA at the reference's published size, n = 100)
-  const char* form = std::getenv("EPSILON_HIP_SVD");  // "scalar" | "block": a forced form keeps its old routes
-  const bool on_chip = m <= 128 && n <= 128 && n >= 2 && SmallFastEnabled() && !(form && form[0] != 0);
+  const char form = SvdForm();  // a forced form keeps its old routes
+  const bool on_chip = m <= 128 && n <= 128 && n >= 2 && SmallFastEnabled() && form == '\0';
   if (!on_chip && n < 512) return false;
-  if (const char* env = std::getenv("EPSILON_HIP_SVD")) {
-    if (env[0] == 's') return false;
-  }
-  if (const char* e = std::getenv("EPSILON_HIP_SVD_MFMA")) {
-    if (e[0] == '0') return false;
-  }
-  if (const char* e = std::getenv("EPSILON_HIP_SVD_NO_V")) {
-    if (e[0] == '0') return false;
-  }
-  return true;
+  return form != 's' && !SvdMfmaOff() && !opt::Is0(opt::kSvdNoV);
 }
 
 // One-sided Jacobi on the columns of W with the rotations applied to W only (see BlockJacobiImpl,
@@ -1354,7 +1353,7 @@ int JacobiSvdNoV(const DVec& W, int64_t m, int64_t n, int max_sweeps) {
   EPS_CHECK(W.n >= m * n && JacobiSvdCanSkipV(m, n, W.dt));
   if (m <= 128 && n <= 128) {
     ProfScope prof("jacobi_svd_no_v_on_chip", m, n);
-    static const bool verbose = std::getenv("EPSILON_HIP_SVD_VERBOSE") != nullptr;
+    static const bool verbose = SvdVerbose();
     int done = -1;  // unknown unless asked for: fetching the count would stall the host once per prox
     EPS_CHECK(SmallJacobiSvdFast(W, m, n, DVec(), max_sweeps, 2e-7, false, verbose ? &done : nullptr, false));
     if (verbose)
@@ -1367,10 +1366,7 @@ int JacobiSvdNoV(const DVec& W, int64_t m, int64_t n, int max_sweeps) {
   // which order the orthogonal columns come back) - measured at n = 1e4 on the reference's
   // robust-PCA matrix: 18 sweeps with and without (gpurun_out r3k), so it is off;
   // EPSILON_HIP_SVD_SORT=1 switches it on.
-  static const bool sort_cols = [] {
-    const char* e = std::getenv("EPSILON_HIP_SVD_SORT");
-    return e && e[0] == '1';
-  }();
+  static const bool sort_cols = opt::Is1(opt::kSvdSort);
   if (sort_cols && n > 1) {
     Runtime& rt = Runtime::Get();
     hipStream_t s = rt.stream();
@@ -1398,8 +1394,8 @@ int JacobiSvd(const DVec& W, int64_t m, int64_t n, const DVec& V, int max_sweeps
   if (row_sharded) return BlockJacobiSvd(W, m, n, V, max_sweeps, warm, true);  // the sharded form
   if (m == 0) return 0;
   {
-    const char* env = std::getenv("EPSILON_HIP_SVD");  // "scalar" | "block" (read per call)
-    const bool force_scalar = env && env[0] == 's', force_block = env && env[0] == 'b';
+    const char form = SvdForm();
+    const bool force_scalar = form == 's', force_block = form == 'b';
     if (!force_scalar && (force_block || n >= 1536))
       return BlockJacobiSvd(W, m, n, V, max_sweeps, warm, false);
     // fp32: with its kernels on the matrix cores the block form also wins below 1536 columns,
@@ -1415,12 +1411,11 @@ int JacobiSvd(const DVec& W, int64_t m, int64_t n, const DVec& V, int max_sweeps
   const bool f32 = W.dt == F32;
   const double tol = f32 ? 2e-7 : 1e-15;
   {
-    const char* env = std::getenv("EPSILON_HIP_SVD");
     int done = 0;
-    if (!(env && env[0] == 's') && n >= 2 &&
+    if (SvdForm() != 's' && n >= 2 &&
         (f32 ? SmallJacobiSvd<float>(W, m, n, V, max_sweeps, tol, warm, &done)
              : SmallJacobiSvd<double>(W, m, n, V, max_sweeps, tol, warm, &done))) {
-      if (std::getenv("EPSILON_HIP_SVD_VERBOSE"))
+      if (SvdVerbose())
         std::fprintf(stderr, "[svd] on-chip %lld x %lld: %d sweeps\n", static_cast<long long>(m),
                      static_cast<long long>(n), done);
       return done;
@@ -1454,7 +1449,7 @@ int JacobiSvd(const DVec& W, int64_t m, int64_t n, const DVec& V, int max_sweeps
     EPS_HIP(hipStreamSynchronize(s));
     if (h == 0) break;
   }
-  if (std::getenv("EPSILON_HIP_SVD_VERBOSE"))
+  if (SvdVerbose())
     std::fprintf(stderr, "[svd] step launches %lld x %lld: %d sweeps\n", static_cast<long long>(m),
                  static_cast<long long>(n), sweeps);
   return sweeps;

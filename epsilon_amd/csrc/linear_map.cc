@@ -13,6 +13,7 @@
 
 #include "comm.h"
 #include "kernels.h"
+#include "options.h"
 #include "sparse.h"
 
 namespace eps {
@@ -100,10 +101,7 @@ DVec DataMap::DenseDevice(const pb::Constant& c_in) {
     EPS_CHECK_MSG(b.len == static_cast<size_t>(count) * sizeof(double),
                   "dense blob '" << c.data_location << "' has " << b.len << " bytes, expected "
                                  << count * sizeof(double));
-    static const bool trace = [] {
-      const char* e = std::getenv("EPSILON_HIP_INIT_TRACE");
-      return e && std::atoi(e) >= 2;
-    }();
+    static const bool trace = opt::InitTraceLevel() >= 2;
     auto now = [] {
       return std::chrono::duration<double, std::milli>(
                  std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -378,10 +376,7 @@ std::shared_ptr<const LinearMapImpl> DenseMatrixImpl::Inverse() const {
 }
 
 bool FusedWhitenEnabled() {
-  static const bool on = [] {
-    const char* e = std::getenv("EPSILON_HIP_FUSED_WHITEN");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = !opt::Is0(opt::kFusedWhiten);
   return on;
 }
 std::shared_ptr<const LinearMapImpl> DenseMatrixImpl::InverseDistributed() const {
@@ -391,8 +386,7 @@ std::shared_ptr<const LinearMapImpl> DenseMatrixImpl::InverseDistributed() const
   // 19.7 ms, a quarter 22.3 ms, a half 27.5 ms - the Cholesky (13.3 ms) is the common part, so
   // with the all-gather on top the split is marginal on one node.  Kept (and tested) for
   // larger blocks / more ranks: EPSILON_HIP_DIST_INVERSE=<min ranks> turns it on (tests use 2).
-  int min_ranks = 16;
-  if (const char* e = std::getenv("EPSILON_HIP_DIST_INVERSE")) min_ranks = std::atoi(e);
+  const int min_ranks = opt::Int(opt::kDistInverse, 16);
   if (comm == nullptr || comm->size() < std::max(2, min_ranks) || m() != nn || nn < 1024)
     return Inverse();
   double d0;
@@ -444,9 +438,9 @@ void DenseMatrixImpl::Apply(double alpha, const DVec& x, double beta, const DVec
   if (symmetric_ && rows_ >= 1024) {  // half the bytes; below that the two launches cost more
     // from the third apply on from a tile-packed copy (+ rows^2 / 2 values): 41 -> 31 us at 1e4
     // (EPSILON_HIP_SYMV_PACKED=0: never; =2: from the first apply - tests; read per call)
-    const char* e = std::getenv("EPSILON_HIP_SYMV_PACKED");
-    const bool packed = !(e && e[0] == '0');
-    const int first = (e && e[0] == '2') ? 1 : 3;
+    const opt::SymvPackedMode mode = opt::SymvPacked();
+    const bool packed = mode != opt::kSymvPackedOff;
+    const int first = mode == opt::kSymvPackedFirst ? 1 : 3;
     if (!packed) packed_ = DVec();
     if (packed && packed_.n == 0 && ++applies_ >= first && !Runtime::Get().capturing())
       packed_ = k::SymvPack(rows_, data_, rows_);

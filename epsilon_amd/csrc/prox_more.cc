@@ -9,6 +9,7 @@
 
 #include "comm.h"
 #include "kernels.h"
+#include "options.h"
 #include "prox.h"
 
 namespace eps {
@@ -312,15 +313,10 @@ class OrthoInvariantProx : public VectorProx {
     V_prev_ = DVec();
     basis_prev_ = DVec();
     basis_is_left_ = false;
-    {
-      const char* pe2 = std::getenv("EPSILON_HIP_SVD_POLAR");
-      polar_enabled_ = !(pe2 && pe2[0] == '0');
-    }
+    polar_enabled_ = !opt::Is0(opt::kSvdPolar);
     calls_ = 0;
-    const char* e = std::getenv("EPSILON_HIP_SVD_WARM");
-    warm_start_ = !(e && e[0] == '0');
-    const char* pe = std::getenv("EPSILON_HIP_SVD_PARTIAL");
-    partial_enabled_ = !(pe && pe[0] == '0');
+    warm_start_ = !opt::Is0(opt::kSvdWarm);
+    partial_enabled_ = !opt::Is0(opt::kSvdPartial);
     partial_backoff_ = 0;
     partial_fail_streak_ = 0;
     last_rank_ = -1;
@@ -346,7 +342,7 @@ class OrthoInvariantProx : public VectorProx {
         --partial_backoff_;
       } else {
         DVec X;
-        static const bool trace = std::getenv("EPSILON_HIP_SVD_TRACE") != nullptr;
+        static const bool trace = opt::IsSet(opt::kSvdTrace);
         const bool ok = ThresholdedPartialSvd(y, input.lambda(), &X);
         if (trace)
           std::fprintf(stderr, "[svd] call %lld: partial route %s (values above lambda: %lld)\n",
@@ -361,7 +357,7 @@ class OrthoInvariantProx : public VectorProx {
         // an ADMM run (an argument far from its low-rank limit) say little about the later ones:
         // skip 1, 2, 4 ... 16 applications after consecutive failures.
         partial_backoff_ = std::min(16, 1 << std::min(partial_fail_streak_, 4));
-        if (const char* e = std::getenv("EPSILON_HIP_SVD_PARTIAL_BACKOFF")) partial_backoff_ = std::atoi(e);
+        partial_backoff_ = opt::Int(opt::kSvdPartialBackoff, partial_backoff_);
         ++partial_fail_streak_;
       }
     }
@@ -618,7 +614,7 @@ class OrthoInvariantProx : public VectorProx {
     const int64_t m = m_, n = n_;
     const DType dt = y.dt;
     ProfScope prof("polar_prox", m, n);
-    static const bool trace = std::getenv("EPSILON_HIP_SVD_TRACE") != nullptr;
+    static const bool trace = opt::IsSet(opt::kSvdTrace);
     // ---- 1. the dominant block: randomized range finder (two power steps), small SVD
     const int64_t k = 32;
     DVec Z = DVec::Empty(n * k, dt), Q0 = DVec::Empty(m * k, dt);

@@ -12,6 +12,7 @@
 #include <sstream>
 
 #include "kernels.h"
+#include "options.h"
 
 namespace eps {
 
@@ -25,10 +26,7 @@ struct HostTrace {
   std::chrono::steady_clock::time_point t0;
   bool on;
   HostTrace(const char* n, int64_t a_ = 0, int64_t b_ = 0) : name(n), a(a_), b(b_) {
-    static const bool enabled = [] {
-      const char* e = std::getenv("EPSILON_HIP_INIT_TRACE");
-      return e && e[0] == '2';
-    }();
+    static const bool enabled = opt::InitTraceLevel() >= 2;
     on = enabled;
     if (on) t0 = std::chrono::steady_clock::now();
   }
