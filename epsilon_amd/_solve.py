@@ -582,6 +582,55 @@ def dense_op(op, rows=0, cols=0, lda=None, nparts=1, alpha=1.0, beta=0.0, a=None
     return (out[:n_out], out2[:n_out]) if out2 is not None else out[:n_out]
 
 
+class _GemmOp(ctypes.Structure):
+    _fields_ = [("op", ctypes.c_char_p), ("trans_a", ctypes.c_int), ("trans_b", ctypes.c_int),
+                ("M", ctypes.c_int64), ("N", ctypes.c_int64), ("K", ctypes.c_int64),
+                ("alpha", ctypes.c_double), ("beta", ctypes.c_double),
+                ("lda", ctypes.c_int64), ("ldb", ctypes.c_int64), ("ldc", ctypes.c_int64),
+                ("a_off", ctypes.c_int64), ("b_off", ctypes.c_int64), ("c_off", ctypes.c_int64),
+                ("batch", ctypes.c_int64), ("outer", ctypes.c_int64), ("sA", ctypes.c_int64),
+                ("sB", ctypes.c_int64), ("sC", ctypes.c_int64), ("sA2", ctypes.c_int64), ("sB2", ctypes.c_int64),
+                ("lower_only", ctypes.c_int),
+                ("a", ctypes.c_void_p), ("a_len", ctypes.c_int64), ("b", ctypes.c_void_p), ("b_len", ctypes.c_int64),
+                ("c", ctypes.c_void_p), ("c_len", ctypes.c_int64), ("d", ctypes.c_void_p), ("d_len", ctypes.c_int64)]
+
+
+def gemm_op(op, M=0, N=0, K=0, trans_a=False, trans_b=False, alpha=1.0, beta=0.0, lda=None, ldb=None,
+            ldc=None, a=None, b=None, c=None, d=None, a_off=0, b_off=0, c_off=0, batch=1, outer=1,
+            sA=0, sB=0, sC=0, sA2=0, sB2=0, lower_only=False):
+    """Test entry for the dense mat-mat layer (include/epsilon_hip.h eps_test_gemm_op): one call of
+    the launcher `op` names on float64 operands that are copied verbatim - the caller fills the
+    padding rows of every column and the gaps between batch members - *_off elements into larger
+    device allocations.  A leading dimension left None is the smallest that holds the operand.
+
+    Returns (out, route): the whole result allocation with its DENSE_OP_GUARD guard elements on
+    each side (DENSE_OP_SENTINEL if nothing stored there), and the branch Gemm took ("" for the
+    helpers)."""
+    L = lib()
+    L.eps_test_gemm_op.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+    g = _GemmOp()
+    g.op = op.encode("utf-8") if op is not None else None
+    g.trans_a, g.trans_b, g.lower_only = int(trans_a), int(trans_b), int(lower_only)
+    g.M, g.N, g.K, g.alpha, g.beta = M, N, K, alpha, beta
+    g.lda = ((N if op == "mat_copy" else K) if trans_a else M) if lda is None else lda
+    g.ldb = (N if trans_b else K) if ldb is None else ldb
+    g.ldc = M if ldc is None else ldc
+    g.a_off, g.b_off, g.c_off = a_off, b_off, c_off
+    g.batch, g.outer, g.sA, g.sB, g.sC, g.sA2, g.sB2 = batch, outer, sA, sB, sC, sA2, sB2
+    keep = []
+    for name, v in (("a", a), ("b", b), ("c", c), ("d", d)):
+        if v is not None:
+            v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+            keep.append(v)
+            setattr(g, name, v.ctypes.data_as(ctypes.c_void_p))
+            setattr(g, name + "_len", v.size)
+    n_out = (max(N, 0) if op == "col_abs_sums" else g.c_len) + 2 * DENSE_OP_GUARD
+    out = np.full(n_out, np.nan)
+    route = ctypes.create_string_buffer(32)
+    _check(L.eps_test_gemm_op(ctypes.byref(g), out.ctypes.data_as(ctypes.c_void_p), route, ctypes.c_size_t(32)))
+    return out, route.value.decode()
+
+
 def tv1d(v, lam):
     v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
     x = np.empty_like(v)

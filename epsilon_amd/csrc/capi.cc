@@ -385,6 +385,119 @@ DVec PlaceOperand(const double* p, int64_t len, int64_t off, int64_t guard, DTyp
   return whole->Slice(off + guard, len);
 }
 
+// ---- eps_test_gemm_op ------------------------------------------------------------------------------
+
+// The argument checks of eps_test_gemm_op, host only, and the operand lengths the dimensions need.
+struct GemmOpArgs {
+  enum Op { GEMM, GEMM_BATCHED, MAT_COPY, ADD_DIAG, SYMMETRIZE, COL_ABS_SUMS, KRON } op;
+  bool use_a = false, use_b = false, use_c = false, use_d = false;
+  int64_t out_len = 0;  // values between the guards of the result
+};
+
+GemmOpArgs CheckGemmOpArgs(const eps_gemm_op* g, const double* out, const char* route, size_t route_cap) {
+  const char* const fn = "eps_test_gemm_op: ";
+  GemmOpArgs a;
+  EPS_CHECK_MSG(g != nullptr, fn << "args is null");
+  EPS_CHECK_MSG(g->op != nullptr, fn << "op is null");
+  const std::string op(g->op);
+  if (op == "gemm") a.op = GemmOpArgs::GEMM;
+  else if (op == "gemm_batched") a.op = GemmOpArgs::GEMM_BATCHED;
+  else if (op == "mat_copy") a.op = GemmOpArgs::MAT_COPY;
+  else if (op == "add_diag") a.op = GemmOpArgs::ADD_DIAG;
+  else if (op == "symmetrize") a.op = GemmOpArgs::SYMMETRIZE;
+  else if (op == "col_abs_sums") a.op = GemmOpArgs::COL_ABS_SUMS;
+  else if (op == "kron") a.op = GemmOpArgs::KRON;
+  else
+    EPS_FATAL(fn << "op must be gemm, gemm_batched, mat_copy, add_diag, symmetrize, col_abs_sums or kron, got "
+                 << op);
+  EPS_CHECK_MSG(out != nullptr, fn << "out is null");
+  EPS_CHECK_MSG(route != nullptr && route_cap >= 16, fn << "route needs room for 16 characters");
+  const bool gemm = a.op == GemmOpArgs::GEMM || a.op == GemmOpArgs::GEMM_BATCHED;
+  const bool batched = a.op == GemmOpArgs::GEMM_BATCHED;
+  const int64_t M = g->M, N = g->N, K = g->K;
+  EPS_CHECK_MSG(M >= 0, fn << "M is negative: " << M);
+  EPS_CHECK_MSG(N >= 0, fn << "N is negative: " << N);
+  EPS_CHECK_MSG(K >= 0, fn << "K is negative: " << K);
+  struct Operand { const char* name; const double* p; int64_t len, off; };
+  const Operand A = {"a", g->a, g->a_len, g->a_off}, B = {"b", g->b, g->b_len, g->b_off},
+                C = {"c", g->c, g->c_len, g->c_off}, D = {"d", g->d, g->d_len, 0};
+  for (const Operand& o : {A, B, C, D}) {
+    EPS_CHECK_MSG(o.len >= 0, fn << o.name << "_len is negative: " << o.len);
+    EPS_CHECK_MSG(o.off >= 0, fn << o.name << "_off is negative: " << o.off);
+  }
+  const int64_t big = int64_t(1) << 40;  // keeps every product of two sizes below inside int64
+  EPS_CHECK_MSG(M < big && N < big && K < big, fn << "M, N and K must be below 2^40");
+  auto need = [&](const Operand& o, int64_t len) {
+    EPS_CHECK_MSG(len == 0 || o.p != nullptr, fn << o.name << " is null");
+    EPS_CHECK_MSG(o.len == len, fn << o.name << " has " << o.len << " entries, the dimensions need " << len);
+  };
+  auto ld_holds = [&](const char* name, int64_t ld, int64_t rows) {
+    EPS_CHECK_MSG(ld >= rows, fn << name << " " << ld << " < rows " << rows);
+    EPS_CHECK_MSG(ld < big, fn << name << " must be below 2^40");
+  };
+  // a rows x cols matrix with leading dimension ld: (cols - 1) ld + rows entries
+  auto span = [](int64_t rows, int64_t cols, int64_t ld) {
+    return rows == 0 || cols == 0 ? int64_t(0) : (cols - 1) * ld + rows;
+  };
+  if (gemm) {
+    int64_t n1 = 1, outer = 1, sA = 0, sB = 0, sC = 0, sA2 = 0, sB2 = 0;
+    if (batched) {
+      n1 = g->batch, outer = g->outer, sA = g->sA, sB = g->sB, sC = g->sC, sA2 = g->sA2, sB2 = g->sB2;
+      EPS_CHECK_MSG(n1 >= 1 && n1 <= 255, fn << "batch must be 1..255, got " << n1);
+      EPS_CHECK_MSG(outer >= 1 && outer <= 255, fn << "outer must be 1..255, got " << outer);
+      const std::pair<const char*, int64_t> strides[] = {{"sA", sA}, {"sB", sB}, {"sC", sC}, {"sA2", sA2}, {"sB2", sB2}};
+      for (const auto& s : strides)
+        EPS_CHECK_MSG(s.second >= 0 && s.second < big, fn << s.first << " must be 0..2^40, got " << s.second);
+    }
+    EPS_CHECK_MSG(!g->lower_only || M == N, fn << "lower_only needs M == N, got " << M << " x " << N);
+    const int64_t a_rows = g->trans_a ? K : M, a_cols = g->trans_a ? M : K;
+    const int64_t b_rows = g->trans_b ? N : K, b_cols = g->trans_b ? K : N;
+    ld_holds("lda", g->lda, a_rows);
+    ld_holds("ldb", g->ldb, b_rows);
+    ld_holds("ldc", g->ldc, M);
+    const int64_t a_one = span(a_rows, a_cols, g->lda), b_one = span(b_rows, b_cols, g->ldb),
+                  c_one = span(M, N, g->ldc);
+    if (batched && c_one > 0)
+      EPS_CHECK_MSG(n1 * outer == 1 || sC >= c_one, fn << "sC " << sC << " < the " << c_one
+                                                       << " entries of one result: the results overlap");
+    a.use_a = a.use_b = a.use_c = true;
+    need(A, a_one == 0 ? 0 : (n1 - 1) * sA + (outer - 1) * sA2 + a_one);
+    need(B, b_one == 0 ? 0 : (n1 - 1) * sB + (outer - 1) * sB2 + b_one);
+    need(C, c_one == 0 ? 0 : (n1 * outer - 1) * sC + c_one);
+    a.out_len = g->c_len;
+  } else if (a.op == GemmOpArgs::MAT_COPY) {  // c (M x N, ld M) = alpha op(a)
+    ld_holds("lda", g->lda, g->trans_a ? N : M);
+    a.use_a = a.use_c = true;
+    need(A, g->trans_a ? span(N, M, g->lda) : span(M, N, g->lda));
+    need(C, M * N);
+    a.out_len = g->c_len;
+  } else if (a.op == GemmOpArgs::ADD_DIAG || a.op == GemmOpArgs::SYMMETRIZE) {  // c: M x M, ldc
+    ld_holds("ldc", g->ldc, M);
+    a.use_c = true;
+    need(C, span(M, M, g->ldc));
+    if (a.op == GemmOpArgs::ADD_DIAG && g->d != nullptr) {
+      a.use_d = true;
+      need(D, M);
+    }
+    a.out_len = g->c_len;
+  } else if (a.op == GemmOpArgs::COL_ABS_SUMS) {  // a: M x N, lda; the result: N sums
+    ld_holds("lda", g->lda, M);
+    a.use_a = true;
+    need(A, span(M, N, g->lda));
+    a.out_len = N;
+  } else {  // KRON: c = a (M x N) kron b (K x batch), all contiguous
+    EPS_CHECK_MSG(g->batch >= 0 && g->batch < big, fn << "batch (the columns of b) must be 0..2^40, got " << g->batch);
+    EPS_CHECK_MSG(M * N < big && K * g->batch < big && (M * N == 0 || K * g->batch < big / (M * N)),
+                  fn << "the Kronecker product is too large");
+    a.use_a = a.use_b = a.use_c = true;
+    need(A, M * N);
+    need(B, K * g->batch);
+    need(C, M * N * K * g->batch);
+    a.out_len = g->c_len;
+  }
+  return a;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1164,6 +1277,56 @@ int eps_test_dense_op(const eps_dense_op* g, double* out, double* out2) {
     }
     EPS_HIP(hipGetLastError());
     fetch_y(out);
+  });
+}
+
+int eps_test_gemm_op(const eps_gemm_op* g, double* out, char* route, size_t route_cap) {
+  return Guard([&] {
+    const GemmOpArgs args = CheckGemmOpArgs(g, out, route, route_cap);
+    route[0] = '\0';
+    const DType dt = ConfiguredDType();
+    constexpr int64_t G = EPS_DENSE_OP_GUARD;
+    const int64_t M = g->M, N = g->N, K = g->K;
+    DVec a_all, b_all, c_all, d_all, a, b, c, d;
+    if (args.use_a) a = PlaceOperand(g->a, g->a_len, g->a_off, G, dt, &a_all);
+    if (args.use_b) b = PlaceOperand(g->b, g->b_len, g->b_off, G, dt, &b_all);
+    if (args.use_c) c = PlaceOperand(g->c, g->c_len, g->c_off, G, dt, &c_all);
+    if (args.use_d) d = PlaceOperand(g->d, g->d_len, 0, G, dt, &d_all);
+    k::GemmClearRoute();
+    switch (args.op) {
+      case GemmOpArgs::GEMM:
+        k::Gemm(g->trans_a != 0, g->trans_b != 0, M, N, K, g->alpha, a, g->lda, b, g->ldb, g->beta, c, g->ldc,
+                g->lower_only != 0);
+        break;
+      case GemmOpArgs::GEMM_BATCHED:
+        k::GemmBatched(g->trans_a != 0, g->trans_b != 0, M, N, K, g->alpha, a, g->lda, g->sA, b, g->ldb, g->sB,
+                       g->beta, c, g->ldc, g->sC, g->batch, g->lower_only != 0, g->outer, g->sA2, g->sB2);
+        break;
+      case GemmOpArgs::MAT_COPY:
+        k::MatCopy(g->trans_a != 0, M, N, g->alpha, a, g->lda, c);
+        break;
+      case GemmOpArgs::ADD_DIAG:
+        k::AddDiag(c, M, g->ldc, g->alpha, args.use_d ? &d : nullptr);
+        break;
+      case GemmOpArgs::SYMMETRIZE:
+        k::SymmetrizeFromLower(c, M, g->ldc);
+        break;
+      case GemmOpArgs::COL_ABS_SUMS: {
+        // the sums are device doubles whatever the dtype
+        std::vector<double> h(static_cast<size_t>(N + 2 * G), EPS_DENSE_OP_SENTINEL);
+        c_all = DVec::FromHost(h.data(), N + 2 * G, F64);
+        k::ColAbsSums(a, M, N, g->lda, c_all.as<double>() + G);
+        EPS_HIP(hipGetLastError());
+        c_all.ToHost(out);
+        return;
+      }
+      case GemmOpArgs::KRON:
+        k::KronDense(c, a, M, N, b, K, g->batch);
+        break;
+    }
+    EPS_HIP(hipGetLastError());
+    std::snprintf(route, route_cap, "%s", k::GemmLastRoute());
+    c_all.Slice(g->c_off, g->c_len + 2 * G).ToHost(out);
   });
 }
 

@@ -288,9 +288,14 @@ void GemmBatched(bool transA, bool transB, int64_t M, int64_t N, int64_t K, doub
                  double beta, const DVec& C, int64_t ldc, int64_t sC, int64_t batch,
                  bool lower_only = false, int64_t outer = 1, int64_t sA2 = 0, int64_t sB2 = 0);
 void SymmetrizeFromLower(const DVec& C, int64_t n, int64_t ldc);
+// The branch the last Gemm / GemmBatched call of this thread took, a host-side record for the tests:
+// "small", "generic", "mfma_f32", "mfma_f32_pipe", "mfma_f64", "mfma_f64_pipe", "split_k",
+// "multi_gemv_n", "multi_gemv_t" or "f16split"; "" after GemmClearRoute or a call that launched nothing.
+const char* GemmLastRoute();
+void GemmClearRoute();
 // Large f32 products on the f16 matrix cores with two-term split operands
 // (kernels_gemm_f16split.hip): f32 accuracy at 3/16 of the f32 MFMA time.  Gemm routes there by
-// itself (f32, M, N >= 2048, K >= 256, >= 8e9 multiply-adds); false = not eligible, nothing done.
+// itself (f32, M, N >= 1024, K >= 256, >= 8e9 multiply-adds); false = not eligible, nothing done.
 bool GemmSplitF16(bool transA, bool transB, int64_t M, int64_t N, int64_t K, double alpha, const DVec& A,
                   int64_t lda, const DVec& B, int64_t ldb, double beta, const DVec& C, int64_t ldc,
                   bool lower_only);

@@ -671,7 +671,13 @@ int GemmMode() {  // 0 auto, 1 generic, 2 mfma, 3 mfma without the pipelined ker
   return mode;
 }
 
+// which branch the last Gemm / GemmBatched of this thread took (GemmLastRoute)
+thread_local const char* g_route = "";
+
 }  // namespace
+
+const char* GemmLastRoute() { return g_route; }
+void GemmClearRoute() { g_route = ""; }
 
 void Gemm(bool transA, bool transB, int64_t M, int64_t N, int64_t K, double alpha,
           const DVec& A, int64_t lda, const DVec& B, int64_t ldb, double beta, const DVec& C,
@@ -679,16 +685,20 @@ void Gemm(bool transA, bool transB, int64_t M, int64_t N, int64_t K, double alph
   // large f32 products (the Gram product, the GEMMs of the Cholesky inverse): f16 matrix cores
   // with split operands
   if (A.dt == F32 && GemmMode() == 0 &&
-      GemmSplitF16(transA, transB, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, lower_only))
+      GemmSplitF16(transA, transB, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, lower_only)) {
+    g_route = "f16split";
     return;
+  }
   // A long contraction into a small result (X^T R of the multiclass hinge: 784 x 10 out of
   // K = 60000) has a handful of output tiles, each looping over all of K on one workgroup - 7
   // workgroups on 256 CUs, 7.3 ms.  Split K over batches into partial results and add them in
   // a fixed order (deterministic): 29 x 7 workgroups, ~0.1 ms.
   // a few right-hand sides: a mat-vec that reads the matrix once, not a matrix product
   if (!transB && !lower_only && N <= 16 && M * K >= (int64_t(1) << 18) &&
-      MultiGemv(transA, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc))
+      MultiGemv(transA, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc)) {
+    g_route = transA ? "multi_gemv_t" : "multi_gemv_n";
     return;
+  }
   if (!lower_only && GemmMode() == 0 && SmallGemmWanted(M, N, K)) {
     EPS_CHECK(A.dt == B.dt && A.dt == C.dt);
     const int64_t a_rows = transA ? K : M, a_cols = transA ? M : K, b_rows = transB ? N : K, b_cols = transB ? K : N;
@@ -697,6 +707,7 @@ void Gemm(bool transA, bool transB, int64_t M, int64_t N, int64_t K, double alph
                   "gemm: operand buffer too small");
     EPS_CHECK_MSG(C.n >= (N - 1) * ldc + M, "gemm: C buffer too small");
     ProfScope prof("gemm_small", M * N, K);
+    g_route = "small";
     const dim3 grid(static_cast<unsigned>((M + 31) / 32), static_cast<unsigned>((N + 31) / 32));
     hipStream_t st = Runtime::Get().stream();
     if (A.dt == F32)
@@ -734,6 +745,7 @@ void Gemm(bool transA, bool transB, int64_t M, int64_t N, int64_t K, double alph
         for (int64_t j = 0; j < N; ++j)  // strided C: column by column (N is small here)
           Axpby(C.Slice(j * ldc, M), 1.0, S.Slice(j * M, M), beta);
       }
+      g_route = "split_k";  // whatever kernel the parts ran on
       return;
     }
   }
@@ -772,6 +784,7 @@ void GemmBatched(bool transA, bool transB, int64_t M, int64_t N, int64_t K, doub
                          reinterpret_cast<uintptr_t>(A.data()) % 16 == 0 &&
                          reinterpret_cast<uintptr_t>(B.data()) % 16 == 0;
     if (aligned && mode != 3) {
+      g_route = "mfma_f32_pipe";
       const float al = static_cast<float>(alpha), be = static_cast<float>(beta);
       int lo = lower_only ? 1 : 0;
       static const bool compact = !opt::IsSet(opt::kSyrk2d);
@@ -826,6 +839,7 @@ void GemmBatched(bool transA, bool transB, int64_t M, int64_t N, int64_t K, doub
 #undef EPS_PIPE
       return;
     }
+    g_route = "mfma_f32";
     hipLaunchKernelGGL(GemmMfmaF32Kernel, grid, dim3(kBlock), 0, s, transA ? 1 : 0,
                        transB ? 1 : 0, M, N, K, static_cast<float>(alpha), A.as<float>(), lda,
                        B.as<float>(), ldb, static_cast<float>(beta), C.as<float>(), ldc,
@@ -838,11 +852,14 @@ void GemmBatched(bool transA, bool transB, int64_t M, int64_t N, int64_t K, doub
   // of EPSILON_HIP_GEMM=mfma.
   if (A.dt == F64 && mode != 1 && mode != 3 && (mode == 2 || (M >= 64 && N >= 64 && K >= 32)) &&
       GemmF64Pipe(transA, transB, M, N, K, alpha, A, lda, sA, B, ldb, sB, beta, C, ldc, sC, n1, batch,
-                  lower_only, sA2, sB2))
+                  lower_only, sA2, sB2)) {
+    g_route = "mfma_f64_pipe";
     return;
+  }
   if (A.dt == F64 && mode >= 2) {
     dim3 grid(static_cast<unsigned>((M + MT - 1) / MT), static_cast<unsigned>((N + MT - 1) / MT),
               static_cast<unsigned>(batch));
+    g_route = "mfma_f64";
     hipLaunchKernelGGL(GemmMfmaF64Kernel, grid, dim3(kBlock), 0, s, transA ? 1 : 0, transB ? 1 : 0, M, N,
                        K, alpha, A.as<double>(), lda, B.as<double>(), ldb, beta, C.as<double>(), ldc,
                        lower_only ? 1 : 0, sA, sB, sC, n1, sA2, sB2);
@@ -850,6 +867,7 @@ void GemmBatched(bool transA, bool transB, int64_t M, int64_t N, int64_t K, doub
   }
   dim3 grid(static_cast<unsigned>((M + GT - 1) / GT), static_cast<unsigned>((N + GT - 1) / GT),
             static_cast<unsigned>(batch));
+  g_route = "generic";
   if (A.dt == F32) {
     hipLaunchKernelGGL(GemmGenericKernel<float>, grid, dim3(kBlock), 0, s, transA ? 1 : 0,
                        transB ? 1 : 0, M, N, K, static_cast<float>(alpha), A.as<float>(), lda,

@@ -424,6 +424,44 @@ typedef struct eps_dense_op {
 } eps_dense_op;
 int eps_test_dense_op(const eps_dense_op* args, double* out, double* out2);
 
+/* Test entry: ONE call of a public launcher of the dense mat-mat layer (csrc/kernels.h: Gemm,
+ * GemmBatched, MatCopy, AddDiag, SymmetrizeFromLower, ColAbsSums, KronDense) on caller-given
+ * column-major operands, in the configured dtype.  `op` and what the operands mean:
+ *   "gemm"          C (M x N, ldc) = alpha op(A) op(B) + beta C; op(A) is M x K, op(B) K x N, a
+ *                   transposed operand is stored K x M / N x K; lower_only as in Gemm
+ *   "gemm_batched"  the same for batch * outer problems z: A at (z % batch) sA + (z / batch) sA2,
+ *                   B likewise, C at z sC
+ *   "mat_copy"      c (M x N, contiguous) = alpha a, or alpha a^T with trans_a (a stored N x M); lda
+ *   "add_diag"      c (M x M, ldc): c_ii += alpha d_i, or += alpha when d is NULL
+ *   "symmetrize"    c (M x M, ldc): the strict upper triangle becomes the mirror of the lower one
+ *   "col_abs_sums"  out: the N column sums of |a| (a: M x N, lda), device doubles in every dtype
+ *   "kron"          c = kron(a, b), a M x N and b K x batch (!), all three contiguous
+ * a, b, c and d are copied verbatim - padding rows and the gaps between batch members included,
+ * filled by the caller - into larger allocations, *_off + EPS_DENSE_OP_GUARD elements in (offset
+ * 0 is 16-byte aligned, an odd offset is not).  out receives the whole result allocation from
+ * c_off on: guard + c_len + guard values (guard + N + guard for col_abs_sums), the guards
+ * EPS_DENSE_OP_SENTINEL unless something stored there.  route (at least 16 characters) receives
+ * the branch Gemm / GemmBatched took (csrc/kernels.h GemmLastRoute), "" for the other ops.
+ * The argument checks - an unknown or null op, a null operand or result, a negative size, offset
+ * or stride, a leading dimension below the rows it holds, a buffer whose length is not
+ * (cols - 1) ld + rows (plus the strides to the last batch member), results that overlap,
+ * lower_only with M != N - fail before any device work and name the argument. */
+typedef struct eps_gemm_op {
+  const char* op;
+  int trans_a, trans_b;
+  int64_t M, N, K;
+  double alpha, beta;
+  int64_t lda, ldb, ldc;
+  int64_t a_off, b_off, c_off;
+  int64_t batch, outer, sA, sB, sC, sA2, sB2;
+  int lower_only;
+  const double* a; int64_t a_len;
+  const double* b; int64_t b_len;
+  const double* c; int64_t c_len;
+  const double* d; int64_t d_len;
+} eps_gemm_op;
+int eps_test_gemm_op(const eps_gemm_op* args, double* out, char* route, size_t route_cap);
+
 /* Microbenchmark: average milliseconds of one launch of a standalone elementwise prox kernel on
  * n synthetic elements of the configured dtype - kind 0 scaled-zone (NORM_1) with scalar
  * parameters, 1 with a per-element threshold vector, 2 projection onto R+ (reference
