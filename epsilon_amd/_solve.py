@@ -631,6 +631,42 @@ def gemm_op(op, M=0, N=0, K=0, trans_a=False, trans_b=False, alpha=1.0, beta=0.0
     return out, route.value.decode()
 
 
+class _FactorOp(ctypes.Structure):
+    _fields_ = [("op", ctypes.c_char_p), ("n", ctypes.c_int64), ("form", ctypes.c_int),
+                ("a", ctypes.c_void_p), ("a_len", ctypes.c_int64), ("a_off", ctypes.c_int64),
+                ("lo", ctypes.c_int64), ("cnt", ctypes.c_int64), ("out_cols", ctypes.c_int64)]
+
+
+def factor_op(op, n=0, a=None, a_off=0, form=-1, lo=0, cnt=0, out_cols=None, want_out2=False):
+    """Test entry for the dense factor layer (include/epsilon_hip.h eps_test_factor_op): one call of
+    SpdInverseInPlace ("spd_inverse") or SpdInverseColumns ("spd_inverse_columns") on the n x n
+    float64 matrix a (column-major, copied as given, upper triangle included), placed a_off
+    elements into a larger device allocation, with the Cholesky step in `form`.
+
+    Returns (out, out2).  out is the result between its DENSE_OP_GUARD guard elements
+    (DENSE_OP_SENTINEL unless something stored there): the n * n inverse, or the n * out_cols slab
+    (out_cols defaults to cnt) whose columns cnt .. out_cols must come back as the sentinel.  out2
+    is None unless want_out2: X = L^-1 for "spd_inverse", W after the call - the Cholesky factor in
+    its lower triangle - for "spd_inverse_columns"; n * n values."""
+    L = lib()
+    L.eps_test_factor_op.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    g = _FactorOp()
+    g.op = op.encode("utf-8") if op is not None else None
+    g.n, g.form, g.a_off, g.lo, g.cnt = n, form, a_off, lo, cnt
+    g.out_cols = (cnt if op == "spd_inverse_columns" else 0) if out_cols is None else out_cols
+    if a is not None:
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+        g.a = a.ctypes.data_as(ctypes.c_void_p)
+        g.a_len = a.size
+    nn = max(n, 0) ** 2
+    body = max(n, 0) * max(g.out_cols, 0) if op == "spd_inverse_columns" else nn
+    out = np.full(body + 2 * DENSE_OP_GUARD, np.nan)
+    out2 = np.full(nn, np.nan) if want_out2 else None
+    _check(L.eps_test_factor_op(ctypes.byref(g), out.ctypes.data_as(ctypes.c_void_p),
+                                out2.ctypes.data_as(ctypes.c_void_p) if out2 is not None else None))
+    return out, out2
+
+
 def tv1d(v, lam):
     v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
     x = np.empty_like(v)

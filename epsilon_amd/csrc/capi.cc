@@ -498,6 +498,46 @@ GemmOpArgs CheckGemmOpArgs(const eps_gemm_op* g, const double* out, const char* 
   return a;
 }
 
+// ---- eps_test_factor_op ----------------------------------------------------------------------------
+
+// The argument checks of eps_test_factor_op, host only.
+struct FactorOpArgs {
+  enum Op { SPD_INVERSE, SPD_INVERSE_COLUMNS } op;
+};
+
+FactorOpArgs CheckFactorOpArgs(const eps_factor_op* g, const double* out) {
+  const char* const fn = "eps_test_factor_op: ";
+  FactorOpArgs a;
+  EPS_CHECK_MSG(g != nullptr, fn << "args is null");
+  EPS_CHECK_MSG(g->op != nullptr, fn << "op is null");
+  const std::string op(g->op);
+  if (op == "spd_inverse") a.op = FactorOpArgs::SPD_INVERSE;
+  else if (op == "spd_inverse_columns") a.op = FactorOpArgs::SPD_INVERSE_COLUMNS;
+  else EPS_FATAL(fn << "op must be spd_inverse or spd_inverse_columns, got " << op);
+  EPS_CHECK_MSG(out != nullptr, fn << "out is null");
+  const int64_t n = g->n;
+  EPS_CHECK_MSG(n >= 0, fn << "n is negative: " << n);
+  EPS_CHECK_MSG(n < (int64_t(1) << 20), fn << "n must be below 2^20");
+  EPS_CHECK_MSG(g->a_len >= 0, fn << "a_len is negative: " << g->a_len);
+  EPS_CHECK_MSG(g->a_off >= 0, fn << "a_off is negative: " << g->a_off);
+  EPS_CHECK_MSG(n == 0 || g->a != nullptr, fn << "a is null");
+  EPS_CHECK_MSG(g->a_len == n * n, fn << "a has " << g->a_len << " entries, the dimensions need " << n * n);
+  EPS_CHECK_MSG(g->form >= -1 && g->form <= 1, fn << "form must be -1, 0 or 1, got " << g->form);
+  if (a.op == FactorOpArgs::SPD_INVERSE) {
+    // both ops have a second result today; what an op has no use for must not be given
+    EPS_CHECK_MSG(g->lo == 0, fn << "lo is given (" << g->lo << "), spd_inverse has no column slab");
+    EPS_CHECK_MSG(g->cnt == 0, fn << "cnt is given (" << g->cnt << "), spd_inverse has no column slab");
+    EPS_CHECK_MSG(g->out_cols == 0, fn << "out_cols is given (" << g->out_cols << "), spd_inverse has no column slab");
+  } else {
+    EPS_CHECK_MSG(g->lo >= 0, fn << "lo is negative: " << g->lo);
+    EPS_CHECK_MSG(g->cnt >= 0, fn << "cnt is negative: " << g->cnt);
+    EPS_CHECK_MSG(g->lo <= n && g->cnt <= n - g->lo, fn << "lo + cnt > n: " << g->lo << " + " << g->cnt << " > " << n);
+    EPS_CHECK_MSG(g->out_cols >= g->cnt, fn << "out_cols " << g->out_cols << " < cnt " << g->cnt);
+    EPS_CHECK_MSG(g->out_cols < (int64_t(1) << 20), fn << "out_cols must be below 2^20");
+  }
+  return a;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1327,6 +1367,36 @@ int eps_test_gemm_op(const eps_gemm_op* g, double* out, char* route, size_t rout
     EPS_HIP(hipGetLastError());
     std::snprintf(route, route_cap, "%s", k::GemmLastRoute());
     c_all.Slice(g->c_off, g->c_len + 2 * G).ToHost(out);
+  });
+}
+
+int eps_test_factor_op(const eps_factor_op* g, double* out, double* out2) {
+  return Guard([&] {
+    const FactorOpArgs args = CheckFactorOpArgs(g, out);
+    const DType dt = ConfiguredDType();
+    constexpr int64_t G = EPS_DENSE_OP_GUARD;
+    const int64_t n = g->n;
+    DVec w_all;
+    DVec W = PlaceOperand(g->a, g->a_len, g->a_off, G, dt, &w_all);
+    struct Restore { ~Restore() { k::SetPotrfForm(-1); } } restore;
+    k::SetPotrfForm(g->form);
+    if (args.op == FactorOpArgs::SPD_INVERSE) {
+      DVec X;
+      k::SpdInverseInPlace(W, n, out2 != nullptr ? &X : nullptr);
+      EPS_HIP(hipGetLastError());
+      w_all.Slice(g->a_off, n * n + 2 * G).ToHost(out);
+      if (out2 != nullptr && n > 0) X.Slice(0, n * n).ToHost(out2);
+      return;
+    }
+    // the slab as InverseDistributed pads it: n * out_cols, of which the launcher owns n * cnt; it
+    // sits a_off elements in as well, so that an odd offset moves both operands off alignment
+    const int64_t len = n * g->out_cols;
+    std::vector<double> h(static_cast<size_t>(g->a_off + 2 * G + len), EPS_DENSE_OP_SENTINEL);
+    DVec o_all = DVec::FromHost(h.data(), static_cast<int64_t>(h.size()), dt);
+    k::SpdInverseColumns(W, n, g->lo, g->cnt, o_all.Slice(g->a_off + G, len));
+    EPS_HIP(hipGetLastError());
+    o_all.Slice(g->a_off, len + 2 * G).ToHost(out);
+    if (out2 != nullptr && n > 0) W.ToHost(out2);
   });
 }
 

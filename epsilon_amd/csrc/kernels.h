@@ -341,12 +341,14 @@ void KronDense(const DVec& dst, const DVec& A, int64_t mA, int64_t nA, const DVe
 // W (n x n, ld = n, symmetric positive definite, full storage) -> W^{-1} in place.
 // Blocked Cholesky + triangular inverse + X^T X, all on device.  Throws if a pivot is <= 0.
 // `factor_inverse` (optional) receives X = L^-1 (n x n, ld n, zeros above the diagonal).
+// Only the lower triangle of W (i >= j) is read: no result depends on what lies above the diagonal.
 void SpdInverseInPlace(const DVec& W, int64_t n, DVec* factor_inverse = nullptr);
 // Cholesky step form of the next factorisations: -1 by environment (default), 0 the fused f32 step,
 // 1 the diagonal + panel launches (tests hold the two forms to each other)
 void SetPotrfForm(int form);
 // Columns [lo, lo + cnt) of W^-1 into Out (n x cnt, ld n); W is overwritten by its Cholesky
 // factor.  Cholesky + two blocked triangular solves on the cnt unit columns.
+// Only the lower triangle of W (i >= j) is read; its strict upper triangle is scratch afterwards.
 void SpdInverseColumns(const DVec& W, int64_t n, int64_t lo, int64_t cnt, const DVec& Out);
 
 // ---- K6 / K12: elementwise and group prox kernels ------------------------------------------

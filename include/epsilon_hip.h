@@ -462,6 +462,38 @@ typedef struct eps_gemm_op {
 } eps_gemm_op;
 int eps_test_gemm_op(const eps_gemm_op* args, double* out, char* route, size_t route_cap);
 
+/* Test entry: ONE call of a public launcher of the dense factor layer (csrc/kernels.h:
+ * SpdInverseInPlace, SpdInverseColumns; csrc/kernels_factor.hip) on a caller-given column-major
+ * n x n matrix a (ld n), in the configured dtype.  `op` and what the results mean:
+ *   "spd_inverse"          SpdInverseInPlace(W, n, out2 ? &X : NULL): out receives guard + n^2 +
+ *                          guard values of W (the inverse, both triangles); out2 (optional) the n^2
+ *                          values of X = L^-1, the factor_inverse the whitened route streams
+ *   "spd_inverse_columns"  SpdInverseColumns(W, n, lo, cnt, Out) with Out allocated n * out_cols,
+ *                          out_cols >= cnt (the padded slab of InverseDistributed): out receives
+ *                          guard + n * out_cols + guard values; out2 (optional) the n^2 values of W
+ *                          afterwards, whose lower triangle is the Cholesky factor (the strict upper
+ *                          triangle is scratch).  cnt == 0 returns right after the factorisation:
+ *                          the pure-Cholesky entry.
+ * a is uploaded as given, upper triangle included, a_off + EPS_DENSE_OP_GUARD elements into a larger
+ * allocation (offset 0 is 16-byte aligned, an odd offset is not); the elements around it and every
+ * element of Out start as EPS_DENSE_OP_SENTINEL, so a store outside a result shows in the guards
+ * and in the padded columns cnt .. out_cols.  form (-1, 0 or 1, as in eps_test_spd_inverse_repeat)
+ * goes through SetPotrfForm for the one call and is back at -1 on every exit path.
+ * The argument checks - an unknown or null op, a null a or out, n < 0, a_len != n * n, a negative
+ * offset, form outside -1..1, lo < 0, cnt < 0, lo + cnt > n, out_cols < cnt, a result or a slab
+ * argument given to an op that has none (today: lo, cnt or out_cols with "spd_inverse"; both ops
+ * have an out2) - fail before any device work and name the argument.  A non-positive
+ * pivot is the launcher's own error, "dense inverse: matrix is not positive definite", returned as
+ * any other error. */
+typedef struct eps_factor_op {
+  const char* op;
+  int64_t n;
+  int form;
+  const double* a; int64_t a_len, a_off;
+  int64_t lo, cnt, out_cols;
+} eps_factor_op;
+int eps_test_factor_op(const eps_factor_op* args, double* out, double* out2);
+
 /* Microbenchmark: average milliseconds of one launch of a standalone elementwise prox kernel on
  * n synthetic elements of the configured dtype - kind 0 scaled-zone (NORM_1) with scalar
  * parameters, 1 with a per-element threshold vector, 2 projection onto R+ (reference
