@@ -125,7 +125,8 @@ int BatchWideMin();  // (with the batched solves below)
 
 // The indices of the options' words (options.cc).  "fused" (off with a leading 0), "fused_zero",
 // "fused_zero_tall", "fused_zero_tall_smooth", "fused_matrix" and "fused_resident" are read at
-// every Init, "batch_wide" per batch ("1" sends eligible groups to the wide route).
+// every Init, "batch_wide" and "batch_zero_tall" per batch ("1" sends eligible groups to the wide
+// route / lets the tall ZERO-term members of a batch form groups).
 enum ZeroTallMode { kZeroTallOff, kZeroTallOn, kZeroTallAuto };  // of either tall option
 enum MatrixRoute { kMatrixOff, kMatrixPass, kMatrixWide, kMatrixAuto };
 
@@ -257,7 +258,8 @@ struct WideSweep {
 // can run as members of a group (RunFusedBatches), and the launches of a sweep of such members.
 struct BatchRoute : FusedRoute {
   DType dt = F32;
-  int64_t m = 0, n = 0;  // the data matrix
+  int64_t m = 0, n = 0;  // the data matrix (the pass's own dimensions are pass.m, pass.n: a tall
+                         // ZERO-term route streams the transposed copy, and its dense pivot has order n)
   int grid = 0;
   DVec w, p, tpart;
   InverseApply inv;          // (unused when whitened or wide)
@@ -266,10 +268,14 @@ struct BatchRoute : FusedRoute {
   k::FusedResidency res;     // the matrix's share that stays in the Infinity Cache
 
   // The key of the group a fresh solve on this route can join; false: it is solved by itself.
-  virtual bool BatchKey(const pb::SolverParams& params, std::vector<uint64_t>* key) const = 0;
-  // The record of the row kernel (a ZERO-term member with a z block); null: the partials go
-  // through the reduction.
+  // `tall_groups`: the option "batch_zero_tall" of this batch.
+  virtual bool BatchKey(const pb::SolverParams& params, bool tall_groups, std::vector<uint64_t>* key) const = 0;
+  // The record of the row kernel (a ZERO-term member with a z block; tall: its x side); null: the
+  // partials go through the reduction.
   virtual const k::ZeroRowsArgs* Rows() const { return nullptr; }
+  // The record of the sample kernel (a tall ZERO-term member with a smooth z term): the pass then
+  // runs in two halves, `pass.chain` and chain 5, around it.
+  virtual const k::ZeroTallSamplesArgs* Samples() const { return nullptr; }
   // The resident share of a sweep of `count` members on this route's matrix.
   virtual k::FusedResidency Residency(int64_t count) const { return res; }
 
@@ -285,23 +291,35 @@ struct BatchRoute : FusedRoute {
             static_cast<uint64_t>(params.max_iterations), static_cast<uint64_t>(params.epoch_iterations)};
   }
 
-  // One sweep of the `count` members of `table` (k::LassoBatchUpload) on this route's matrix: the
-  // batched pass per `width` members; the row kernel on `row_table` (k::ZeroRowsBatchUpload) for
-  // ZERO-term members with a z block, else the batched reduction of the partials; then - unless
-  // whitened: the reduction wrote every member's w_hat - one batched apply of the packed inverse
-  // (`work`: count * k::SymvWorkspace(m)), or `own_applies` without a packed copy (D.Apply / Symv:
-  // per member).
+  // One sweep of the `count` members of `table` (k::LassoBatchUpload) on this route's matrix, in
+  // the pass's own dimensions pm x pn (pm: the register-held one, the order of the dense pivot): the
+  // batched pass per `width` members - with a sample kernel (Samples()): the dot pass per width(4)
+  // members, one sample launch on `sample_table` (k::ZeroTallSamplesBatchUpload), the accumulate
+  // pass per width(5) members; the row kernel on `row_table` (k::ZeroRowsBatchUpload) for ZERO-term
+  // members with a z block, else the batched reduction of the partials; then - unless whitened: the
+  // reduction wrote every member's w_hat - one batched apply of the packed inverse (`work`:
+  // count * k::SymvWorkspace(pm)), or `own_applies` without a packed copy (D.Apply / Symv: per
+  // member).
   template <class Applies>
-  void BatchSweep(const DVec& table, const DVec& row_table, int count, const double* group_lam,
-                  const k::FusedResidency& share, bool rhs_aligned, const DVec& work, Applies own_applies) const {
-    const int width = k::LassoBatchWidth(m, n, dt, pass.chain);
-    for (int first = 0; first < count; first += width)
-      k::LassoBatchPass(m, n, pass.lda, pass.A, table, first, std::min(width, count - first), group_lam, share,
-                        pass.chain);
-    if (Rows() != nullptr) k::ZeroFusedRowsBatch(m, grid, Rows()->smooth, dt, row_table, count);
-    else k::ReducePartialsBatch(m, grid, table, count, dt, rhs_aligned);
+  void BatchSweep(const DVec& table, const DVec& row_table, const DVec& sample_table, int count,
+                  const double* group_lam, const k::FusedResidency& share, bool rhs_aligned, const DVec& work,
+                  Applies own_applies) const {
+    const int64_t pm = pass.m, pn = pass.n;
+    auto passes = [&](int chain) {
+      const int width = k::LassoBatchWidth(pm, pn, dt, chain);
+      for (int first = 0; first < count; first += width)
+        k::LassoBatchPass(pm, pn, pass.lda, pass.A, table, first, std::min(width, count - first), group_lam, share,
+                          chain);
+    };
+    passes(pass.chain);
+    if (Samples() != nullptr) {
+      k::ZeroTallSamplesBatch(pn, dt, sample_table, count);
+      passes(5);
+    }
+    if (Rows() != nullptr) k::ZeroFusedRowsBatch(pm, grid, Rows()->smooth, dt, row_table, count, Rows()->tall);
+    else k::ReducePartialsBatch(pm, grid, table, count, dt, rhs_aligned);
     if (whiten) return;
-    if (inv.packed.n > 0) k::SymvPackedBatch(m, inv.D->scale(), inv.packed, table, count, work);
+    if (inv.packed.n > 0) k::SymvPackedBatch(pm, inv.D->scale(), inv.packed, table, count, work);
     else own_applies();
   }
 };
@@ -669,7 +687,7 @@ struct LassoRoute final : BatchRoute {
       }
       return;
     }
-    BatchSweep(table, DVec(), K, group_lam, res, rhs_aligned, inv.work, [&] {
+    BatchSweep(table, DVec(), DVec(), K, group_lam, res, rhs_aligned, inv.work, [&] {
       for (int64_t c = 0; c < cols; ++c) inv.Column(c).Apply();
     });
   }
@@ -739,7 +757,7 @@ struct LassoRoute final : BatchRoute {
   // ---- batched solves (RunFusedBatches) ---------------------------------------------------------
   // The key of the group a fresh solve on this route can join (same data matrix, inverse, dtype,
   // shape and schedule); false: its pass is none the batched one mirrors.
-  bool BatchKey(const pb::SolverParams& params, std::vector<uint64_t>* key) const override {
+  bool BatchKey(const pb::SolverParams& params, bool, std::vector<uint64_t>* key) const override {
     if (use_peer || ShardSpec::Get().active()) return false;
     if (cols > 1) return false;  // a matrix variable is a batch of its own: it runs alone
     const DenseMatrixImpl& L = *ls.L_arg_var;
@@ -771,8 +789,9 @@ struct LassoRoute final : BatchRoute {
 // partials' sum, the chain on x, f_x) and the apply of Dinv(x').  A smooth z term (`samples_smooth`:
 // SUM_LOGISTIC, under the option "fused_zero_tall_smooth") has its Newton in a kernel of its own over
 // the samples, between the two halves of the pass: the dot products C x' (chain 4), the sample kernel
-// with the carried head, the forward product (chain 5).  No batched form: a member of a batch on this
-// route is solved by itself.
+// with the carried head, the forward product (chain 5).  Under the option "batch_zero_tall" the tall
+// members of a batch that share C run as one group ("Tall members"); without it each is
+// solved by itself.
 struct ZeroRoute final : BatchRoute {
   // u, var, copy, y of the separable term, y of the ZERO term, their previous values: the state of
   // one consensus constraint
@@ -934,6 +953,7 @@ struct ZeroRoute final : BatchRoute {
     }
     if (CT.n == 0) {
       CT = DVec::Empty(m * n, dt);
+      ProfScope prof("transpose_copy", n, m);  // (a setup step: the members of a batch share one copy)
       k::MatCopy(true, n, m, 1.0, L.data(), L.rows(), CT);
       if (key) shared->Put(key, std::make_shared<DenseMatrixImpl>(CT, n, m, false, 1.0, key));
     }
@@ -1008,6 +1028,12 @@ struct ZeroRoute final : BatchRoute {
     pass.zrhs = zp.rhs_arg;
     pass.ke = -zp.e;
     pass.dinv = zp.dinv_arg;
+    // (a batched member carries them in its record)
+    k::LassoInstance& rec = pass.inst;
+    rec.zg = pass.zg;
+    rec.zrhs = pass.zrhs;
+    rec.ke = pass.ke;
+    rec.dinv = pass.dinv;
     RowsSide(sn, sx, ax);
     rows.tall = true;
     if (!samples_smooth) return;
@@ -1016,8 +1042,8 @@ struct ZeroRoute final : BatchRoute {
     pass.chain = 4;
     head = DVec::Zeros(3 * m, dt);
     dfarg = DVec::Zeros(2 * m, dt);
-    pass.zd = dfarg.Slice(0, m);
-    pass.zfarg = dfarg.Slice(m, m);
+    pass.zd = rec.zd = dfarg.Slice(0, m);
+    pass.zfarg = rec.zfarg = dfarg.Slice(m, m);
     k::ZeroTallSamplesArgs& t = samples;
     const k::LassoInstance& i = pass.inst;
     t.m = m;
@@ -1086,15 +1112,28 @@ struct ZeroRoute final : BatchRoute {
 
   // ---- batched solves (RunFusedBatches) ---------------------------------------------------------
   const k::ZeroRowsArgs* Rows() const override { return has_z ? &rows : nullptr; }
+  const k::ZeroTallSamplesArgs* Samples() const override { return samples_smooth ? &samples : nullptr; }
   // The key of the group a fresh solve on this route can join: the same data matrix, the same
   // inverse (and packed copy), the same e and z block, the same form of the row kernel and the
   // same schedule.  Everything else - the zones' parameters and vectors, the offset g, the rhs -
-  // is per member, so a hinge and a deadzone member on one matrix share a group.  false: tall, or
-  // the single pass takes a form the batched one does not mirror (512-thread workgroups).
-  bool BatchKey(const pb::SolverParams& params, std::vector<uint64_t>* key) const override {
-    if (tall || k::LassoBatchWidth(m, n, dt, 2) == 0) return false;
+  // is per member, so a hinge and a deadzone member on one matrix share a group.  false: the single
+  // pass takes a form the batched one does not mirror (512-thread workgroups), or tall without
+  // `tall_groups`.
+  // Tall: the key also has the transposed copy (the members find one through the solve's cache),
+  // the form (the pass whole, or in halves around the sample kernel: a logistic member never joins
+  // a scaled-zone group) and the scalar pivot.
+  bool BatchKey(const pb::SolverParams& params, bool tall_groups, std::vector<uint64_t>* key) const override {
+    if (tall) {
+      if (!tall_groups || !has_z || k::LassoBatchWidth(pass.m, pass.n, dt, pass.chain) == 0) return false;
+      if (samples_smooth && k::LassoBatchWidth(pass.m, pass.n, dt, acc.chain) == 0) return false;
+    } else if (k::LassoBatchWidth(m, n, dt, 2) == 0) {
+      return false;
+    }
     *key = KeyHead(*zp.L, *zp.Dinv, params);
     key->insert(key->end(), {Bits(zp.e), has_z ? 1u : 0u, rows.smooth ? 1u : 0u});
+    if (tall)
+      key->insert(key->end(), {reinterpret_cast<uintptr_t>(CT.data()), 1u, samples_smooth ? 1u : 0u,
+                               Bits(zp.dinv_arg)});
     return true;
   }
 };
@@ -1268,6 +1307,8 @@ void RunGroupSchedule(const Group& g, double t0, std::vector<int>* active, Sweep
 // own apply; whitened: none).  Each launch does per member what the member's own sweep does, so
 // its iterates are the single solve's bit for bit; a ZERO-term member's residual check is the
 // driver's generic one, at the sweeps of the member's own Run().
+// Tall ZERO-term members: every launch in the pass's own dimensions (pass.m = n, the order of the
+// dense pivot), and for a smooth z term the pass in halves around one sample launch (BatchSweep).
 void RunPassGroup(const Group& g) {
   const double t0 = Now();
   const BatchRoute& lead = *g[0].route;
@@ -1276,27 +1317,35 @@ void RunPassGroup(const Group& g) {
   std::vector<const k::LassoInstance*> all;
   for (const BatchMember& b : g) all.push_back(&b.route->pass.inst);
   const bool rhs_aligned = RhsAligned(all);
-  DVec symv_work = lead.inv.packed.n > 0 ? DVec::Empty(K * k::SymvWorkspace(lead.m), lead.dt) : DVec();
+  // (the pass's own dimensions: a tall lead's pass.m is n, the order of its dense pivot)
+  DVec symv_work = lead.inv.packed.n > 0 ? DVec::Empty(K * k::SymvWorkspace(lead.pass.m), lead.dt) : DVec();
   const k::FusedResidency res = lead.Residency(K);  // (a ZERO-term lead's own: none under "auto")
 
   std::vector<int> active(K);
   for (int i = 0; i < K; ++i) active[i] = i;
-  DVec table, row_table;
+  DVec table, row_table, sample_table;
   auto upload = [&] {
     std::vector<const k::LassoInstance*> v;
     std::vector<const k::ZeroRowsArgs*> r;
+    std::vector<const k::ZeroTallSamplesArgs*> t;
     for (int i : active) {
       const BatchRoute& mb = *g[i].route;
-      EPS_CHECK(mb.pass.chain == 0 || mb.pass.inst.e0.n == lead.n);  // the ZERO chain stores through it
+      EPS_CHECK(mb.pass.m == lead.pass.m && mb.pass.n == lead.pass.n && mb.pass.chain == lead.pass.chain);
+      EPS_CHECK(mb.pass.chain == 0 || mb.pass.inst.e0.n == lead.pass.n);  // the ZERO chains store through it
+      if (mb.pass.chain == 4)  // the halves of the tall pass store and load through them
+        EPS_CHECK(mb.pass.inst.zd.n == lead.pass.n && mb.pass.inst.zfarg.n == lead.pass.n);
       v.push_back(&mb.pass.inst);
       if (mb.Rows() != nullptr) r.push_back(mb.Rows());
+      if (mb.Samples() != nullptr) t.push_back(mb.Samples());
     }
     k::LassoBatchUpload(v, lead.dt, &table);
     if (lead.Rows() != nullptr) k::ZeroRowsBatchUpload(r, &row_table);
+    if (lead.Samples() != nullptr) k::ZeroTallSamplesBatchUpload(t, &sample_table);
   };
   upload();
   auto sweep = [&] {
-    lead.BatchSweep(table, row_table, static_cast<int>(active.size()), nullptr, res, rhs_aligned, symv_work, [&] {
+    lead.BatchSweep(table, row_table, sample_table, static_cast<int>(active.size()), nullptr, res, rhs_aligned,
+                    symv_work, [&] {
       for (int i : active) g[i].route->inv.Apply();
     });
   };
@@ -1377,13 +1426,14 @@ void RunWideGroup(const Group& g) {
 std::vector<bool> RunFusedBatches(const std::vector<Solver*>& solvers) {
   std::vector<bool> ran(solvers.size(), false);
   const bool wide = opt::Word(opt::kBatchWide) != 0;
+  const bool tall_groups = opt::Word(opt::kBatchZeroTall) != 0;  // (read first: a bad value is an error whatever the batch)
   std::map<std::vector<uint64_t>, std::vector<size_t>> groups;
   std::vector<BatchRoute*> routes(solvers.size(), nullptr);
   std::vector<std::vector<uint64_t>> order;  // groups in order of their first instance
   for (size_t i = 0; i < solvers.size(); ++i) {
     routes[i] = dynamic_cast<BatchRoute*>(solvers[i]->batch_route());
     std::vector<uint64_t> key;
-    if (routes[i] == nullptr || !routes[i]->BatchKey(solvers[i]->params(), &key)) continue;
+    if (routes[i] == nullptr || !routes[i]->BatchKey(solvers[i]->params(), tall_groups, &key)) continue;
     auto& members = groups[key];
     if (members.empty()) order.push_back(key);
     members.push_back(i);

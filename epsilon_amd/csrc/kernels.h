@@ -72,6 +72,11 @@ struct LassoInstance {
   double Bs = 0, Cs = 0, a1 = 0;    // prox-1 pre / post scaling, y1 = a1 * x1
   double lam = 0, alpha = 1, beta = 1, M = 0;
   double pkappa = 0;                // scale of the summed partials in p (see LassoBatchInst)
+  // chains 3, 4, 5 alone, what LassoFusedArgs has under the same names, which a batched member
+  // carries here (n entries each, n the streamed dimension: the samples)
+  DVec zg, zrhs;                    // chain 3, optional
+  DVec zd, zfarg;                   // chain 4 writes zd, chain 5 reads zfarg
+  double ke = 0, dinv = 0;          // chain 3
 };
 struct LassoFusedArgs {
   int64_t m = 0, n = 0, lda = 0;
@@ -162,8 +167,17 @@ void ZeroSmoothHead(const ZeroRowsArgs& args);  // profile tag "zero_fused_head"
 // own launch bit for bit.  The members share m, nparts, the dtype and the form (zone or smooth).
 // ZeroRowsBatchUpload writes their records in order into `table` (device; grown as needed): as with
 // LassoBatchUpload, a member that stops is dropped by uploading the shorter list.
+// `tall` (all members or none; profile tag "batch_zero_tall_cols"): grid row b is member b's own
+// "zero_tall_cols" launch, the x side of a tall problem (ZeroRowsArgs::tall).
 void ZeroRowsBatchUpload(const std::vector<const ZeroRowsArgs*>& members, DVec* table);
-void ZeroFusedRowsBatch(int64_t m, int nparts, bool smooth, DType dt, const DVec& table, int count);
+void ZeroFusedRowsBatch(int64_t m, int nparts, bool smooth, DType dt, const DVec& table, int count,
+                        bool tall = false);
+// The sample side of `count` tall members with a smooth z term in ONE launch, profile tag
+// "batch_zero_tall_samples": grid row b is member b's own ZeroTallSamples launch, a thread per
+// sample, on its own record with the carried head in its own hs, hys, hv; no wait, no barrier, no
+// atomic.  The members share m and the dtype; the upload is ZeroRowsBatchUpload's.
+void ZeroTallSamplesBatchUpload(const std::vector<const ZeroTallSamplesArgs*>& members, DVec* table);
+void ZeroTallSamplesBatch(int64_t m, DType dt, const DVec& table, int count);
 bool LassoFusedSupported(int64_t m, int64_t n, const DVec& A, int64_t lda);
 int LassoFusedGrid(int64_t m, int64_t n, DType dt = F32);
 int LassoFusedBlock(int64_t m, int64_t n, DType dt);  // threads per workgroup of the pass
@@ -207,11 +221,19 @@ template <class T> struct LassoBatchInst {
   T kappa, Bs, Cs, a1, lam, alpha, beta, M;
   T pkappa;          // scale of the summed partials in p (kappa, but for the whitened route)
   T* e0;             // n: the ZERO chain's second "previous y" (nullptr on the lasso chain)
+  // the tall ZERO chains (3, 4, 5); nullptr / unused on chains 0 and 2
+  const T* zg;       // n: chain 3's offset of the z term (nullptr: none)
+  const T* zrhs;     // n: chain 3's constant on the arg row (nullptr: none)
+  T* zd;             // n: chain 4 stores the dot products here
+  const T* zfarg;    // n: chain 5 reads the forward weights here
+  T ke, dinv;        // chain 3: -L(arg, z'), Dinv(arg)'s scalar
 };
 // Instances one launch of the batched pass carries for (m, dtype) - set by the register budget
 // of its instantiation - or 0 where the single pass would take a form the batched one does not
 // mirror (512-thread workgroups): such instances are solved one by one.  `chain`: 0 the lasso
-// chain, 2 the ZERO-term column chain (LassoFusedArgs::chain), which has widths of its own.
+// chain, 2 the ZERO-term column chain (LassoFusedArgs::chain), which has widths of its own; 3, 4, 5
+// the tall ZERO-term chains, (m, n) the pass's own dimensions (features x samples), each with its
+// widths - 4 and 5 hold half of the per-member registers and are wider.
 int LassoBatchWidth(int64_t m, int64_t n, DType dt, int chain = 0);
 // The descriptors of `members` in order into `table` (device; grown as needed): the active set
 // of a batch is this array, so an instance that stops is dropped by uploading the shorter list.
@@ -224,6 +246,9 @@ void LassoBatchUpload(const std::vector<const LassoInstance*>& members, DType dt
 // `res`: the matrix's resident share, as in LassoFusedArgs.
 // `chain` = 2: the column side of ZERO-term members (every record carries e0; no group_lam; profile
 // tag "batch_zero_pass", count <= LassoBatchWidth(m, n, dt, 2)); 0: the lasso chain ("batch_fused_pass").
+// `chain` = 3, 4, 5: the sample side of tall ZERO-term members, A the transposed copy (tags
+// "batch_zero_tall_pass", "batch_zero_tall_dot", "batch_zero_tall_acc"; every record carries what
+// its chain reads of zg, zrhs, zd, zfarg, ke, dinv; count <= LassoBatchWidth(m, n, dt, chain)).
 void LassoBatchPass(int64_t m, int64_t n, int64_t lda, const DVec& A, const DVec& table, int first,
                     int count, const double* group_lam = nullptr, const FusedResidency& res = FusedResidency(),
                     int chain = 0);

@@ -277,34 +277,61 @@ void LaunchFusedT(const LassoFusedArgs& a, int grid, int block) {
 // in hs, hys, hv as on the fat route's row kernel: finishes the sweep from d_i = C[i,:] . x', stores
 // the boundary state as MODE 3 does, computes the next head once, leaves it in hs, hys, hv and
 // writes the next f_arg_i for the accumulate pass.  A thread reads and writes its own sample alone.
+//
+// One member's sample side as the kernels read it (compute type T): the single launch takes it as
+// its argument, the batched launch (tag "batch_zero_tall_samples") reads row blockIdx.y of a device
+// table of them.  The arrays of one member do not overlap.
+template <class T> struct ZeroTallSamplesInst {
+  FusedScalarsT<T> c;
+  double lam64;
+  T ke, dinv;
+  const T* g;    // nullptr: none
+  const T* rhs;  // nullptr: none
+  const T* d;
+  T* u; T* z; T* zq; T* yz; T* yq; T* yzprev; T* yqprev;
+  T* hs; T* hys; T* hv;
+  T* farg;
+};
+
+// Sample i of one member: the body of the single and of the batched kernel.
 template <class T, class Fn>
-__global__ __launch_bounds__(kBlock) void ZeroTallSamplesKernel(
-    int64_t m, FusedScalarsT<T> c, double lam64, T ke, T dinv, const T* __restrict__ g,
-    const T* __restrict__ rhs, const T* __restrict__ d, T* __restrict__ u, T* __restrict__ z,
-    T* __restrict__ zq, T* __restrict__ yz, T* __restrict__ yq, T* __restrict__ yzprev,
-    T* __restrict__ yqprev, T* __restrict__ hs, T* __restrict__ hys, T* __restrict__ hv,
-    T* __restrict__ farg) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+__device__ __forceinline__ void ZeroTallSamplesBody(int64_t m, const ZeroTallSamplesInst<T>& I, int64_t i) {
   if (i >= m) return;
-  const T gi = g != nullptr ? g[i] : T(0), ri = rhs != nullptr ? rhs[i] : T(0);
-  const T s = hs[i], ys = hys[i], v = hv[i];
+  const FusedScalarsT<T>& c = I.c;
+  const T ke = I.ke, dinv = I.dinv;
+  const T gi = I.g != nullptr ? I.g[i] : T(0), ri = I.rhs != nullptr ? I.rhs[i] : T(0);
+  const T s = I.hs[i], ys = I.hys[i], v = I.hv[i];
   const T fa = ZeroTallForwardT<T>(v, ri, ke);
   const T garg = dinv * fa;
-  const T arg = c.kappa * d[i] + garg;
+  const T arg = c.kappa * I.d[i] + garg;
   const T q = ke * arg + v;
   const T un = v - q;  // y_q = q (its constraint map is I); u -= y_q
-  yzprev[i] = yz[i];
-  yqprev[i] = yq[i];
-  z[i] = s;
-  zq[i] = q;
-  yz[i] = ys;
-  yq[i] = q;
-  u[i] = un;
-  const ZeroHeadT<T> hn = ZeroHeadOfT<T, Fn>(c, gi, un, ys, q, lam64);
-  hs[i] = hn.s;
-  hys[i] = hn.ys;
-  hv[i] = hn.v;
-  farg[i] = ZeroTallForwardT<T>(hn.v, ri, ke);
+  I.yzprev[i] = I.yz[i];
+  I.yqprev[i] = I.yq[i];
+  I.z[i] = s;
+  I.zq[i] = q;
+  I.yz[i] = ys;
+  I.yq[i] = q;
+  I.u[i] = un;
+  const ZeroHeadT<T> hn = ZeroHeadOfT<T, Fn>(c, gi, un, ys, q, I.lam64);
+  I.hs[i] = hn.s;
+  I.hys[i] = hn.ys;
+  I.hv[i] = hn.v;
+  I.farg[i] = ZeroTallForwardT<T>(hn.v, ri, ke);
+}
+
+template <class T, class Fn>
+__global__ __launch_bounds__(kBlock) void ZeroTallSamplesKernel(int64_t m, ZeroTallSamplesInst<T> I) {
+  ZeroTallSamplesBody<T, Fn>(m, I, static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x);
+}
+
+// The members of a batch: grid row b is member b's single launch, thread for thread.  A thread
+// touches its own member's sample alone; nothing waits on another thread.
+template <class T, class Fn>
+__global__ __launch_bounds__(kBlock) void ZeroTallSamplesBatchKernel(
+    int64_t m, const ZeroTallSamplesInst<T>* __restrict__ tab) {
+  const ZeroTallSamplesInst<T> I = tab[blockIdx.y];
+  ZeroTallSamplesBody<T, Fn>(m, I, static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x);
 }
 
 // ---- the row side of a ZERO-term sweep ------------------------------------------------------------
@@ -411,11 +438,12 @@ __global__ __launch_bounds__(ROWS * kZeroLanes) void ZeroFusedRowsKernel(int64_t
 
 // The members of a batch: grid row b is member b's single launch, workgroup for workgroup.  A
 // workgroup touches its own member's rows alone; nothing waits on another workgroup.
-template <class T, int ROWS, class Fn>
+// TALL (tag "batch_zero_tall_cols"): grid row b is member b's "zero_tall_cols" launch.
+template <class T, int ROWS, class Fn, bool TALL = false>
 __global__ __launch_bounds__(ROWS * kZeroLanes) void ZeroFusedRowsBatchKernel(
     int64_t m, int nparts, const ZeroRowsInst<T>* __restrict__ tab) {
   const ZeroRowsInst<T> I = tab[blockIdx.y];
-  ZeroRowsBody<T, ROWS, Fn>(m, nparts, I, blockIdx.x);
+  ZeroRowsBody<T, ROWS, Fn, TALL>(m, nparts, I, blockIdx.x);
 }
 
 // The first head of a smooth z term from the adopted boundary state, a thread per row.
@@ -468,12 +496,24 @@ void LaunchZeroRows(const ZeroRowsArgs& a) {
                      Runtime::Get().stream(), a.m, a.nparts, RowsInstOf<T>(a));
 }
 
-template <class T, int ROWS, class Fn>
+template <class T, int ROWS, class Fn, bool TALL = false>
 void LaunchZeroRowsBatch(int64_t m, int nparts, const DVec& table, int count) {
   const unsigned grid = static_cast<unsigned>((m + ROWS - 1) / ROWS);
-  hipLaunchKernelGGL((ZeroFusedRowsBatchKernel<T, ROWS, Fn>), dim3(grid, static_cast<unsigned>(count)),
+  hipLaunchKernelGGL((ZeroFusedRowsBatchKernel<T, ROWS, Fn, TALL>), dim3(grid, static_cast<unsigned>(count)),
                      dim3(ROWS * kZeroLanes), 0, Runtime::Get().stream(), m, nparts,
                      reinterpret_cast<const ZeroRowsInst<T>*>(table.as<char>()));
+}
+
+// The records of a batch's members in order into `table` (device; grown as needed).
+template <class Inst>
+void UploadRecords(const std::vector<Inst>& host, DVec* table) {
+  const size_t bytes = host.size() * sizeof(Inst);
+  const int64_t words = static_cast<int64_t>((bytes + 7) / 8);
+  if (table->n < words || table->dt != F64) *table = DVec::Empty(words < 1 ? 1 : words, F64);
+  if (bytes == 0) return;
+  Runtime& rt = Runtime::Get();
+  EPS_HIP(hipMemcpyAsync(table->data(), host.data(), bytes, hipMemcpyHostToDevice, rt.stream()));
+  rt.Sync();  // `host` goes out of scope with the caller
 }
 
 template <class T>
@@ -481,13 +521,7 @@ void UploadRowsT(const std::vector<const ZeroRowsArgs*>& members, DVec* table) {
   std::vector<ZeroRowsInst<T>> host;
   host.reserve(members.size());
   for (const ZeroRowsArgs* a : members) host.push_back(RowsInstOf<T>(*a));
-  const size_t bytes = host.size() * sizeof(ZeroRowsInst<T>);
-  const int64_t words = static_cast<int64_t>((bytes + 7) / 8);
-  if (table->n < words || table->dt != F64) *table = DVec::Empty(words < 1 ? 1 : words, F64);
-  if (bytes == 0) return;
-  Runtime& rt = Runtime::Get();
-  EPS_HIP(hipMemcpyAsync(table->data(), host.data(), bytes, hipMemcpyHostToDevice, rt.stream()));
-  rt.Sync();  // `host` goes out of scope
+  UploadRecords(host, table);
 }
 
 template <class T>
@@ -545,6 +579,12 @@ void CheckZeroTallSamples(const ZeroTallSamplesArgs& a) {
   EPS_CHECK_MSG(a.fn == SMOOTH_LOGISTIC, "the tall ZERO-term sample side takes SUM_LOGISTIC alone, got " << a.fn);
 }
 
+template <class T> ZeroTallSamplesInst<T> SamplesInstOf(const ZeroTallSamplesArgs& a) {
+  return {ZeroTallSampleScalars<T>(a), a.lam, static_cast<T>(a.ke), static_cast<T>(a.dinv), OptT<T>(a.g),
+          OptT<T>(a.rhs), a.d.as<T>(), a.u.as<T>(), a.z.as<T>(), a.zq.as<T>(), a.yz.as<T>(), a.yq.as<T>(),
+          a.yzprev.as<T>(), a.yqprev.as<T>(), a.hs.as<T>(), a.hys.as<T>(), a.hv.as<T>(), a.farg.as<T>()};
+}
+
 template <class T>
 void LaunchZeroTallSamples(const ZeroTallSamplesArgs& a, bool head_only) {
   const dim3 grid(static_cast<unsigned>((a.m + kBlock - 1) / kBlock));
@@ -554,10 +594,23 @@ void LaunchZeroTallSamples(const ZeroTallSamplesArgs& a, bool head_only) {
                        a.hs.as<T>(), a.hys.as<T>(), a.hv.as<T>());
   else
     hipLaunchKernelGGL((ZeroTallSamplesKernel<T, FnLogistic>), grid, dim3(kBlock), 0, Runtime::Get().stream(), a.m,
-                       ZeroTallSampleScalars<T>(a), a.lam, static_cast<T>(a.ke), static_cast<T>(a.dinv), OptT<T>(a.g),
-                       OptT<T>(a.rhs), a.d.as<T>(), a.u.as<T>(), a.z.as<T>(), a.zq.as<T>(), a.yz.as<T>(),
-                       a.yq.as<T>(), a.yzprev.as<T>(), a.yqprev.as<T>(), a.hs.as<T>(), a.hys.as<T>(), a.hv.as<T>(),
-                       a.farg.as<T>());
+                       SamplesInstOf<T>(a));
+}
+
+template <class T>
+void UploadSamplesT(const std::vector<const ZeroTallSamplesArgs*>& members, DVec* table) {
+  std::vector<ZeroTallSamplesInst<T>> host;
+  host.reserve(members.size());
+  for (const ZeroTallSamplesArgs* a : members) host.push_back(SamplesInstOf<T>(*a));
+  UploadRecords(host, table);
+}
+
+template <class T>
+void LaunchZeroTallSamplesBatch(int64_t m, const DVec& table, int count) {
+  hipLaunchKernelGGL((ZeroTallSamplesBatchKernel<T, FnLogistic>),
+                     dim3(static_cast<unsigned>((m + kBlock - 1) / kBlock), static_cast<unsigned>(count)),
+                     dim3(kBlock), 0, Runtime::Get().stream(), m,
+                     reinterpret_cast<const ZeroTallSamplesInst<T>*>(table.as<char>()));
 }
 
 }  // namespace
@@ -584,24 +637,49 @@ void ZeroRowsBatchUpload(const std::vector<const ZeroRowsArgs*>& members, DVec* 
   for (const ZeroRowsArgs* a : members) {
     CheckZeroRows(*a);
     EPS_CHECK(a->m == lead.m && a->nparts == lead.nparts && a->smooth == lead.smooth && a->w.dt == lead.w.dt);
-    EPS_CHECK(!a->tall);  // a tall member is solved by itself
+    EPS_CHECK(a->tall == lead.tall);
   }
   if (lead.w.dt == F32) UploadRowsT<float>(members, table);
   else UploadRowsT<double>(members, table);
 }
 
-void ZeroFusedRowsBatch(int64_t m, int nparts, bool smooth, DType dt, const DVec& table, int count) {
+void ZeroFusedRowsBatch(int64_t m, int nparts, bool smooth, DType dt, const DVec& table, int count, bool tall) {
   const int64_t record = dt == F32 ? sizeof(ZeroRowsInst<float>) : sizeof(ZeroRowsInst<double>);
   EPS_CHECK(m >= 1 && nparts >= 1 && count >= 1 && count <= 65535);
   EPS_CHECK(table.dt == F64 && table.n * 8 >= count * record);
-  ProfScope prof("batch_zero_rows", m, count);
-  if (smooth) {
+  EPS_CHECK_MSG(!(tall && smooth), "the tall ZERO-term x side has no smooth form");
+  ProfScope prof(tall ? "batch_zero_tall_cols" : "batch_zero_rows", m, count);
+  if (tall) {
+    if (dt == F32) LaunchZeroRowsBatch<float, kZeroRows, void, true>(m, nparts, table, count);
+    else LaunchZeroRowsBatch<double, kZeroRows, void, true>(m, nparts, table, count);
+  } else if (smooth) {
     if (dt == F32) LaunchZeroRowsBatch<float, kZeroSmoothRows, FnLogistic>(m, nparts, table, count);
     else LaunchZeroRowsBatch<double, kZeroSmoothRows, FnLogistic>(m, nparts, table, count);
   } else {
     if (dt == F32) LaunchZeroRowsBatch<float, kZeroRows, void>(m, nparts, table, count);
     else LaunchZeroRowsBatch<double, kZeroRows, void>(m, nparts, table, count);
   }
+  EPS_HIP(hipGetLastError());
+}
+
+void ZeroTallSamplesBatchUpload(const std::vector<const ZeroTallSamplesArgs*>& members, DVec* table) {
+  EPS_CHECK(!members.empty());
+  const ZeroTallSamplesArgs& lead = *members[0];
+  for (const ZeroTallSamplesArgs* a : members) {
+    CheckZeroTallSamples(*a);
+    EPS_CHECK(a->m == lead.m && a->d.dt == lead.d.dt);
+  }
+  if (lead.d.dt == F32) UploadSamplesT<float>(members, table);
+  else UploadSamplesT<double>(members, table);
+}
+
+void ZeroTallSamplesBatch(int64_t m, DType dt, const DVec& table, int count) {
+  const int64_t record = dt == F32 ? sizeof(ZeroTallSamplesInst<float>) : sizeof(ZeroTallSamplesInst<double>);
+  EPS_CHECK(m >= 1 && count >= 1 && count <= 65535);
+  EPS_CHECK(table.dt == F64 && table.n * 8 >= count * record);
+  ProfScope prof("batch_zero_tall_samples", m, count);
+  if (dt == F32) LaunchZeroTallSamplesBatch<float>(m, table, count);
+  else LaunchZeroTallSamplesBatch<double>(m, table, count);
   EPS_HIP(hipGetLastError());
 }
 

@@ -19,6 +19,13 @@
 // CHAIN 2: the instances are ZERO-term problems and a column runs the single
 // pass's MODE 2 - ZeroChainT and its stores, e0 among them - in place of ChainOneT; everything
 // around the chain is the same code.
+//
+// CHAIN 3, 4, 5: the instances are TALL ZERO-term problems (DESIGN.md 3.11 "Tall C") and a column -
+// a sample of the transposed copy - runs the single pass's MODE 3, 4 or 5.  3: ZeroTallChainT with
+// the member's own offset, rhs, ke and dinv, and MODE 3's stores.  4: the dot products alone, stored
+// by thread 0 to the member's zd; no t' registers.  5: the member's zfarg of the sample and the
+// forward update alone; no w registers, no reduction, no barrier.  In 3 and 5 the members' values of
+// a sample (state, offset, rhs; zfarg) are fetched by one lane per member and read from its register.
 #include <hip/hip_runtime.h>
 
 #include <vector>
@@ -32,6 +39,15 @@ namespace k {
 namespace {
 
 constexpr int kBlock = 256;
+
+// Lane `l` (uniform) of v in every lane of the wave: a register read, no memory.
+__device__ inline float LaneValue(float v, int l) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+__device__ inline double LaneValue(double v, int l) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l),
+                          __builtin_amdgcn_readlane(__double2loint(v), l));
+}
 
 // GROUP: the nk instances are the columns of ONE matrix variable and the threshold is the group
 // shrinkage of its rows (NORM_2 along axis 1, weight glam): row j's nk threshold inputs are what
@@ -57,8 +73,9 @@ __global__ __launch_bounds__(kBlock) void LassoBatchStreamKernel(int64_t m, int6
   for (int i = 0; i < KB; ++i) {
 #pragma unroll
     for (int q = 0; q < NR; ++q) {
-      wv[i][q] = (i < nk && row[q] < m) ? *reinterpret_cast<const V*>(tab[i].w + row[q]) : zero;
-      tp[i][q] = zero;
+      if constexpr (CHAIN != 5)
+        wv[i][q] = (i < nk && row[q] < m) ? *reinterpret_cast<const V*>(tab[i].w + row[q]) : zero;
+      if constexpr (CHAIN != 4) tp[i][q] = zero;
     }
   }
   // this workgroup's columns: exactly those of LassoFusedStreamKernelT, in its order
@@ -78,6 +95,27 @@ __global__ __launch_bounds__(kBlock) void LassoBatchStreamKernel(int64_t m, int6
       else a[q] = zero;
     }
   };
+  // CHAIN 3 and 5: lane i of every wave fetches member i's values of a sample - one vector load
+  // per array for all members, in flight together - and the member's step reads them from that
+  // lane's register (LaneValue).  Member by member through the table they are KB dependent scalar
+  // loads, each waited for, which is what a sample then costs.  The values are the same.
+  [[maybe_unused]] const T *pu = nullptr, *py0 = nullptr, *py1 = nullptr, *pg = nullptr, *pr = nullptr,
+                           *pf = nullptr;
+  if constexpr (CHAIN == 3 || CHAIN == 5) {
+    static_assert(KB <= 64, "a lane per member");
+    if (lane < nk) {
+      const LassoBatchInst<T>& L = tab[lane];
+      if constexpr (CHAIN == 3) {
+        pu = L.u;
+        py0 = L.y0;
+        py1 = L.y1;
+        pg = L.zg;
+        pr = L.zrhs;
+      } else {
+        pf = L.zfarg;
+      }
+    }
+  }
   V cur[NR], nxt[NR];
   int64_t step = 0;
   int64_t j = column(0);
@@ -89,23 +127,67 @@ __global__ __launch_bounds__(kBlock) void LassoBatchStreamKernel(int64_t m, int6
     const int64_t step_n = (jn >= 0 && column(step + 1) < 0) ? step + 2 : step + 1;
     if (jn >= 0) load(nxt, jn);
     // every instance's column state is read before the barrier: thread 0 overwrites it after
-    T uj[KB], y0j[KB], y1j[KB];
+    [[maybe_unused]] T uj[KB], y0j[KB], y1j[KB];
+    [[maybe_unused]] T gj[KB], rj[KB];  // CHAIN 3: the member's offset and rhs of this sample
+    [[maybe_unused]] T su = T(0), sy0 = T(0), sy1 = T(0), sg = T(0), sr = T(0), sf = T(0);  // lane i: member i's
+    if constexpr (CHAIN == 3) {
+      if (lane < nk) {
+        su = pu[j];
+        sy0 = py0[j];
+        sy1 = py1[j];
+        if (pg != nullptr) sg = pg[j];
+        if (pr != nullptr) sr = pr[j];
+      }
+    }
+    if constexpr (CHAIN == 5) {
+      if (lane < nk) sf = pf[j];
+    }
 #pragma unroll
     for (int i = 0; i < KB; ++i) {
       if (i >= nk) continue;
-      uj[i] = tab[i].u[j];
-      y0j[i] = tab[i].y0[j];
-      y1j[i] = tab[i].y1[j];
-      T d = T(0);
+      if constexpr (CHAIN <= 2) {
+        uj[i] = tab[i].u[j];
+        y0j[i] = tab[i].y0[j];
+        y1j[i] = tab[i].y1[j];
+      }
+      if constexpr (CHAIN == 3) {
+        uj[i] = LaneValue(su, i);
+        y0j[i] = LaneValue(sy0, i);
+        y1j[i] = LaneValue(sy1, i);
+        gj[i] = LaneValue(sg, i);
+        rj[i] = LaneValue(sr, i);
+      }
+      if constexpr (CHAIN != 5) {
+        T d = T(0);
 #pragma unroll
-      for (int q = 0; q < NR; ++q)
+        for (int q = 0; q < NR; ++q)
 #pragma unroll
-        for (int r = 0; r < R; ++r) d += cur[q][r] * wv[i][q][r];
-      d = WaveSumT<T>(d);
-      if (lane == 0) red[par][i][wave] = d;
+          for (int r = 0; r < R; ++r) d += cur[q][r] * wv[i][q][r];
+        d = WaveSumT<T>(d);
+        if (lane == 0) red[par][i][wave] = d;
+      }
     }
-    __syncthreads();
-    if constexpr (GROUP) {
+    if constexpr (CHAIN != 5) __syncthreads();
+    if constexpr (CHAIN == 4) {
+#pragma unroll
+      for (int i = 0; i < KB; ++i) {
+        if (i >= nk) continue;
+        T d = red[par][i][0];
+#pragma unroll
+        for (int w2 = 1; w2 < kBlock / 64; ++w2) d += red[par][i][w2];
+        if (tid == 0) tab[i].zd[j] = d;
+      }
+    } else if constexpr (CHAIN == 5) {
+#pragma unroll
+      for (int i = 0; i < KB; ++i) {
+        if (i >= nk) continue;
+        const T v0n = LaneValue(sf, i);
+#pragma unroll
+        for (int q = 0; q < NR; ++q)
+#pragma unroll
+          for (int r = 0; r < R; ++r) tp[i][q][r] += cur[q][r] * v0n;
+      }
+    } else if constexpr (GROUP) {
       auto scalars = [&](int i) {
         const LassoBatchInst<T>& I = tab[i];
         FusedScalarsT<T> c;
@@ -167,7 +249,20 @@ __global__ __launch_bounds__(kBlock) void LassoBatchStreamKernel(int64_t m, int6
         c.beta = I.beta_v != nullptr ? I.beta_v[j] : I.beta;
         c.M = I.M;
         T v0n;
-        if constexpr (CHAIN == 2) {
+        if constexpr (CHAIN == 3) {
+          T ns, nq, nys, nyq, nu;
+          v0n = ZeroTallChainT<T>(d, c, I.ke, I.dinv, gj[i], rj[i], uj[i], y1j[i], y0j[i], &ns, &nq, &nys, &nyq,
+                                  &nu);
+          if (tid == 0) {
+            I.y1prev[j] = y1j[i];
+            I.e0[j] = y0j[i];
+            I.x1[j] = ns;
+            I.x0[j] = nq;
+            I.y1[j] = nys;
+            I.y0[j] = nyq;
+            I.u[j] = nu;
+          }
+        } else if constexpr (CHAIN == 2) {
           T ns, nq, nys, nyq, nu;
           v0n = ZeroChainT<T>(d, c, T(0), uj[i], y1j[i], y0j[i], &ns, &nq, &nys, &nyq, &nu);
           if (tid == 0) {
@@ -203,13 +298,15 @@ __global__ __launch_bounds__(kBlock) void LassoBatchStreamKernel(int64_t m, int6
     j = jn;
     step = step_n;
   }
+  if constexpr (CHAIN != 4) {
 #pragma unroll
-  for (int i = 0; i < KB; ++i) {
-    if (i >= nk) continue;
-    T* out = tab[i].tpart + static_cast<int64_t>(blockIdx.x) * m;
+    for (int i = 0; i < KB; ++i) {
+      if (i >= nk) continue;
+      T* out = tab[i].tpart + static_cast<int64_t>(blockIdx.x) * m;
 #pragma unroll
-    for (int q = 0; q < NR; ++q)
-      if (row[q] < m) *reinterpret_cast<V*>(out + row[q]) = tp[i][q];
+      for (int q = 0; q < NR; ++q)
+        if (row[q] < m) *reinterpret_cast<V*>(out + row[q]) = tp[i][q];
+    }
   }
 }
 
@@ -228,7 +325,17 @@ constexpr int WidthFor(int nr) { return nr <= 2 ? 8 : nr <= 4 ? 6 : nr <= 8 ? 5 
 // ("Registers"), so a form that would spill at the lasso's width takes a smaller
 // one here; the lasso's widths are not touched.
 constexpr int ZeroWidthFor(int nr) { return WidthFor(nr); }
-constexpr int WidthFor(int nr, int chain) { return chain == 2 ? ZeroWidthFor(nr) : WidthFor(nr); }
+// The tall ZERO chains.  CHAIN 3 keeps what CHAIN 2 keeps plus the sample's offset and rhs per
+// member.  CHAIN 4 holds no t' and CHAIN 5 no w - 4 NR registers per member instead of 8 NR - so
+// they carry more members per read of the matrix (DESIGN.md 3.6 has the registers of each form).
+constexpr int ZeroTallWidthFor(int nr) { return ZeroWidthFor(nr); }
+constexpr int ZeroTallHalfWidthFor(int nr) { return nr <= 2 ? 16 : nr <= 4 ? 12 : nr <= 8 ? 10 : 8; }
+constexpr int WidthFor(int nr, int chain) {
+  return chain == 2 ? ZeroWidthFor(nr)
+         : chain == 3 ? ZeroTallWidthFor(nr)
+         : chain >= 4 ? ZeroTallHalfWidthFor(nr)
+                      : WidthFor(nr);
+}
 
 template <class T, int NR>
 void LaunchBatch(int grid, int64_t m, int64_t n, const T* A, int64_t lda, const LassoBatchInst<T>* tab, int nk,
@@ -236,6 +343,15 @@ void LaunchBatch(int grid, int64_t m, int64_t n, const T* A, int64_t lda, const 
   if (chain == 2)
     hipLaunchKernelGGL((LassoBatchStreamKernel<T, NR, ZeroWidthFor(NR), false, 2>), dim3(grid), dim3(kBlock), 0,
                        Runtime::Get().stream(), m, n, A, lda, tab, nk, 0.0, res.qfull, res.jcut);
+  else if (chain == 3)
+    hipLaunchKernelGGL((LassoBatchStreamKernel<T, NR, ZeroTallWidthFor(NR), false, 3>), dim3(grid), dim3(kBlock), 0,
+                       Runtime::Get().stream(), m, n, A, lda, tab, nk, 0.0, res.qfull, res.jcut);
+  else if (chain == 4)
+    hipLaunchKernelGGL((LassoBatchStreamKernel<T, NR, ZeroTallHalfWidthFor(NR), false, 4>), dim3(grid), dim3(kBlock),
+                       0, Runtime::Get().stream(), m, n, A, lda, tab, nk, 0.0, res.qfull, res.jcut);
+  else if (chain == 5)
+    hipLaunchKernelGGL((LassoBatchStreamKernel<T, NR, ZeroTallHalfWidthFor(NR), false, 5>), dim3(grid), dim3(kBlock),
+                       0, Runtime::Get().stream(), m, n, A, lda, tab, nk, 0.0, res.qfull, res.jcut);
   else if (glam != nullptr)
     hipLaunchKernelGGL((LassoBatchStreamKernel<T, NR, WidthFor(NR), true, 0>), dim3(grid), dim3(kBlock), 0,
                        Runtime::Get().stream(), m, n, A, lda, tab, nk, *glam, res.qfull, res.jcut);
@@ -281,7 +397,9 @@ void LassoBatchUpload(const std::vector<const LassoInstance*>& members, DType dt
   for (const LassoInstance* s : members)
     for (const DVec* v : {&s->w, &s->tpart, &s->u, &s->x0, &s->x1, &s->y0, &s->y1, &s->y1prev, &s->p})
       EPS_CHECK(v->dt == dt && v->n > 0);
-  for (const LassoInstance* s : members) EPS_CHECK(s->e0.n == 0 || (s->e0.dt == dt && s->e0.n == s->u.n));
+  for (const LassoInstance* s : members)
+    for (const DVec* v : {&s->e0, &s->zg, &s->zrhs, &s->zd, &s->zfarg})
+      EPS_CHECK(v->n == 0 || (v->dt == dt && v->n == s->u.n));
   if (dt == F32) UploadT<float>(members, table);
   else UploadT<double>(members, table);
 }
@@ -289,7 +407,8 @@ void LassoBatchUpload(const std::vector<const LassoInstance*>& members, DType dt
 void LassoBatchPass(int64_t m, int64_t n, int64_t lda, const DVec& A, const DVec& table, int first, int count,
                     const double* group_lam, const FusedResidency& res, int chain) {
   const DType dt = A.dt;
-  EPS_CHECK_MSG(chain == 0 || (chain == 2 && group_lam == nullptr), "batched fused pass: chain " << chain);
+  EPS_CHECK_MSG(chain == 0 || (chain >= 2 && chain <= 5 && group_lam == nullptr),
+                "batched fused pass: chain " << chain);
   EPS_CHECK(LassoFusedSupported(m, n, A, lda));
   EPS_CHECK(res.qfull >= 0 && res.jcut >= 0 && res.jcut <= n);
   const int width = LassoBatchWidth(m, n, dt, chain);
@@ -297,7 +416,9 @@ void LassoBatchPass(int64_t m, int64_t n, int64_t lda, const DVec& A, const DVec
                 "batched fused pass: " << count << " instances, width " << width);
   const int grid = LassoFusedGrid(m, n, dt);
   const int nr = ChunksPerThread(m, dt);
-  ProfScope prof(chain == 2 ? "batch_zero_pass" : "batch_fused_pass", m, n);
+  static const char* const kTags[] = {"batch_fused_pass",     "batch_fused_pass",    "batch_zero_pass",
+                                      "batch_zero_tall_pass", "batch_zero_tall_dot", "batch_zero_tall_acc"};
+  ProfScope prof(kTags[chain], m, n);
   NoteFusedResidency(res.qfull, res.jcut);
   if (dt == F32)
     LaunchBatchT<float>(nr, grid, m, n, A.as<float>(), lda,

@@ -78,6 +78,12 @@ template <class T> LassoBatchInst<T> Narrow(const LassoInstance& s) {
   d.beta = static_cast<T>(s.beta);
   d.M = static_cast<T>(s.M);
   d.e0 = s.e0.n > 0 ? s.e0.as<T>() : nullptr;
+  d.zg = s.zg.n > 0 ? s.zg.as<T>() : nullptr;
+  d.zrhs = s.zrhs.n > 0 ? s.zrhs.as<T>() : nullptr;
+  d.zd = s.zd.n > 0 ? s.zd.as<T>() : nullptr;
+  d.zfarg = s.zfarg.n > 0 ? s.zfarg.as<T>() : nullptr;
+  d.ke = static_cast<T>(s.ke);
+  d.dinv = static_cast<T>(s.dinv);
   return d;
 }
 

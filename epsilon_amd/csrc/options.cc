@@ -21,6 +21,7 @@ const struct Option {
 } kOptions[] = {
     {kBatchWide, "EPSILON_HIP_BATCH_WIDE", "batch_wide", {"0", "1"}, "0"},
     {kBatchWideMin, "EPSILON_HIP_BATCH_WIDE_MIN"},
+    {kBatchZeroTall, "EPSILON_HIP_BATCH_ZERO_TALL", "batch_zero_tall", {"0", "1"}, "0"},
     {kBenchRandom, "EPSILON_HIP_BENCH_RANDOM"},
     {kDevice, "EPSILON_HIP_DEVICE", "device"},
     {kDistInverse, "EPSILON_HIP_DIST_INVERSE"},

@@ -14,6 +14,7 @@ namespace opt {
 enum Id {
   kBatchWide,
   kBatchWideMin,
+  kBatchZeroTall,
   kBenchRandom,
   kDevice,
   kDistInverse,

@@ -88,6 +88,14 @@ const char* eps_version(void);
  * instruction, up to 64 instances per read of the matrix); such groups match eps_solve to f32
  * rounding, not bit for bit - see eps_solve_batch.  Any other value is an error that names it
  * (env EPSILON_HIP_BATCH_WIDE).
+ * "batch_zero_tall" = "0" (default) | "1"  eps_solve_batch runs the instances on the tall ZERO-term
+ * route ("fused_zero_tall", "fused_zero_tall_smooth") that share the data matrix as one group: per
+ * sweep one pass over the transposed copy for up to KB of them (the logistic loss: two, around one
+ * launch over the samples of all), one launch for the x side of all and one inverse apply for all,
+ * each instance bit for bit its own eps_solve.  "0": each such instance is solved alone.
+ * "fused_zero_tall" = "0", "fused_zero" = "0" and "fused" = "0" switch the group off with the route.
+ * Read at every eps_solve_batch.  Any other value is an error that names it
+ * (env EPSILON_HIP_BATCH_ZERO_TALL).
  * "fused_matrix" = "auto" (default) | "0" | "pass" | "wide"  least squares on a matrix variable
  * X (n x k, data map I_k (x) A, at least 256 rows; multi-block driver, one GPU) with an l1 or a
  * row-group (multi-task group lasso) penalty: the k columns run as k members of the batched fused
@@ -165,7 +173,9 @@ int eps_solve(const void* problem, size_t problem_len, const void* solver_params
  * one Gram product and one inverse for all, then per sweep one pass over the matrix for up to KB
  * of them, one launch for the row side of all and one inverse apply for all; lambda, the loss's
  * parameters and vectors, the offset and the right-hand side may differ per instance, so hinge and
- * deadzone instances on one matrix run together.  Every other instance - tall data, the two-block
+ * deadzone instances on one matrix run together.  With the option "batch_zero_tall" = "1" so do the
+ * instances with tall data on the tall ZERO-term route (hinge and deadzone together, logistic among
+ * themselves).  Every other instance - tall data without that option, the two-block
  * driver, shapes above 10240 rows in f32 or 5120 in f64, sharded solves, and a fused one with no
  * partner - is solved alone by eps_solve's code.  Per-iteration log lines (verbose) are not printed for instances solved together.
  * With the option "batch_wide" = "1" the contract above is relaxed for the members of a WIDE
