@@ -4,7 +4,6 @@
 #include "fused_route.h"
 
 #include <algorithm>
-#include <array>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -21,19 +20,20 @@ namespace {
 // What the routes share
 // ---------------------------------------------------------------------------------------------------
 
-// The scaled-zone fields of a kernel record (k::LassoInstance, k::ZeroRowsArgs) from the
-// operator's description; a1: the scalar of the term's variable in its consensus constraint.
-template <class Record>
-void SetThreshold(Record* s, const ScaledZoneDesc& z, double a1) {
-  s->alpha_vec = z.alpha_vec;
-  s->beta_vec = z.beta_vec;
-  s->Bs = z.Bs;
-  s->Cs = z.Cs;
-  s->a1 = a1;
-  s->lam = z.lam;
-  s->alpha = z.alpha;
-  s->beta = z.beta;
-  s->M = z.M;
+// The zone of a kernel record from the operator's description; a1: the scalar of the term's
+// variable in its consensus constraint.
+k::ZoneParams ZoneOf(const ScaledZoneDesc& z, double a1) {
+  k::ZoneParams s;
+  s.alpha_vec = z.alpha_vec;
+  s.beta_vec = z.beta_vec;
+  s.Bs = z.Bs;
+  s.Cs = z.Cs;
+  s.a1 = a1;
+  s.lam = z.lam;
+  s.alpha = z.alpha;
+  s.beta = z.beta;
+  s.M = z.M;
+  return s;
 }
 
 // The consensus tie a0 copy + a1 var = 0: row `ck` of A holds scalar maps of length `len` on
@@ -416,9 +416,9 @@ struct LassoRoute final : BatchRoute {
                                      {&a.y[1], ck},         {&a.u, ck},            {&a.y_prev[1], ck}};
     views[5].take = false;
     for (size_t q = 0; q < views.size(); ++q) views[q].v = state_all.Slice(static_cast<int64_t>(q) * npad, nx);
-    k::LassoInstance& s = pass.inst;
-    s.x0 = views[0].v, s.x1 = views[1].v, s.y0 = views[2].v, s.y1 = views[3].v, s.u = views[4].v;
-    s.y1prev = views[5].v;
+    k::ConsensusState& s = pass.inst.state;
+    s.copy = views[0].v, s.var = views[1].v, s.y_zero = views[2].v, s.y_term = views[3].v, s.u = views[4].v;
+    s.y_term_prev = views[5].v;
     grid = k::LassoFusedGrid(m, n, dt);
     // a matrix variable: column c's p and w at c * m (the wide route's instance-major panels,
     // whole panels of 64), its partials at c * grid * m
@@ -542,11 +542,11 @@ struct LassoRoute final : BatchRoute {
   // (whitened: w_hat = X p).
   void ForwardFromState() {
     const DenseMatrixImpl& L = *ls.L_arg_var;
-    const k::LassoInstance& s = pass.inst;
+    const k::ConsensusState& s = pass.inst.state;
     DVec v0 = s.u.Clone();
-    k::Axpby(v0, -1.0, s.y0, 1.0);
-    k::Axpby(v0, -1.0, s.y1, 1.0);
-    k::Axpby(v0, 1.0, s.y0, 1.0);
+    k::Axpby(v0, -1.0, s.y_zero, 1.0);
+    k::Axpby(v0, -1.0, s.y_term, 1.0);
+    k::Axpby(v0, 1.0, s.y_zero, 1.0);
     if (cols == 1 && !whiten) {
       L.Apply(-1.0, v0, 0.0, p);
       ForwardTail(/*reduced=*/false);
@@ -648,23 +648,23 @@ struct LassoRoute final : BatchRoute {
     // x0 = v0 + kappa A^T w (whitened: c A_hat^T w_hat)
     s.kappa = -L.scale() * (whiten ? wscale : 1.0);
     s.pkappa = -L.scale();
-    SetThreshold(&s, sz, a1);
+    s.zone = ZoneOf(sz, a1);
     if (cols == 1) return;
     // a matrix variable: column c is member c, the slices of `inst` at its offsets; the table is
     // uploaded here, so that a sweep makes no upload and no host synchronisation
     members.assign(static_cast<size_t>(cols), s);
     for (int64_t c = 0; c < cols; ++c) {
-      k::LassoInstance& mb = members[static_cast<size_t>(c)];
+      k::LassoInstance& mb = members[static_cast<size_t>(c)];  // (a copy of `inst`: sliced in place)
       auto col = [&](const DVec& v, int64_t len) { return v.n > 0 ? v.Slice(c * len, len) : v; };
       mb.w = col(s.w, m);
       mb.p = col(s.p, m);
       mb.rhs = col(s.rhs, m);
       if (!wide) mb.tpart = col(s.tpart, static_cast<int64_t>(grid) * m);
       else mb.tpart = mb.w;  // (not read on the wide route: its partials are panels of WideSweep)
-      for (DVec k::LassoInstance::*v : {&k::LassoInstance::u, &k::LassoInstance::x0, &k::LassoInstance::x1,
-                                       &k::LassoInstance::y0, &k::LassoInstance::y1, &k::LassoInstance::y1prev,
-                                       &k::LassoInstance::alpha_vec, &k::LassoInstance::beta_vec})
-        mb.*v = col(s.*v, n);
+      k::ConsensusState& ms = mb.state;
+      for (DVec* v : {&ms.u, &ms.var, &ms.copy, &ms.y_term, &ms.y_zero, &ms.y_term_prev, &mb.zone.alpha_vec,
+                      &mb.zone.beta_vec})
+        *v = col(*v, n);
     }
     std::vector<const k::LassoInstance*> v;
     for (const auto& mb : members) v.push_back(&mb);
@@ -719,8 +719,9 @@ struct LassoRoute final : BatchRoute {
     Runtime& rt = Runtime::Get();
     norm_slot = rt.NewSlot();
     for (int q = 1; q < 6; ++q) rt.NewSlot();
-    const k::LassoInstance& s = pass.inst;
-    k::LassoFusedNorms(s.u, s.y0, s.y1, s.y1prev, sharded ? rt.ShardSlotPtr(norm_slot) : rt.SlotPtr(norm_slot), norm_work,
+    const k::ConsensusState& s = pass.inst.state;
+    k::LassoFusedNorms(s.u, s.y_zero, s.y_term, s.y_term_prev,
+                       sharded ? rt.ShardSlotPtr(norm_slot) : rt.SlotPtr(norm_slot), norm_work,
                        use_peer ? rt.peer()->device_error_word() : nullptr);
   }
   Check FinishCheck() override {
@@ -793,9 +794,7 @@ struct LassoRoute final : BatchRoute {
 // members of a batch that share C run as one group ("Tall members"); without it each is
 // solved by itself.
 struct ZeroRoute final : BatchRoute {
-  // u, var, copy, y of the separable term, y of the ZERO term, their previous values: the state of
-  // one consensus constraint
-  using Side = std::array<DVec, 7>;
+  using Side = k::ConsensusState;  // of the x constraint, of the z constraint
 
   ZeroProjectionDesc zp;
   ScaledZoneDesc sx, sz;  // the separable terms on x and on z
@@ -900,19 +899,19 @@ struct ZeroRoute final : BatchRoute {
                     DVec* all) {
       const int64_t pad = (len + 63) / 64 * 64;
       *all = DVec::Zeros(7 * pad, dt);
-      const std::vector<StateSlice> seven = {{&a.u, ck},
-                                             {&a.x[term], var},
-                                             {&a.x[N - 1], copy},
-                                             {&a.y[term], ck},
-                                             {&a.y[N - 1], ck},
-                                             {&a.y_prev[term], ck, DVec(), false},
-                                             {&a.y_prev[N - 1], ck, DVec(), false}};
       Side s;
-      for (int q = 0; q < 7; ++q) {
-        s[q] = all->Slice(q * pad, len);
-        views.push_back(seven[q]);
-        views.back().v = s[q];
-      }
+      int64_t q = 0;  // the next slice of `all`
+      auto slice = [&](DVec* v, BlockVector* home, const std::string& key, bool take = true) {
+        *v = all->Slice(q++ * pad, len);
+        views.push_back({home, key, *v, take});
+      };
+      slice(&s.u, &a.u, ck);
+      slice(&s.var, &a.x[term], var);
+      slice(&s.copy, &a.x[N - 1], copy);
+      slice(&s.y_term, &a.y[term], ck);
+      slice(&s.y_zero, &a.y[N - 1], ck);
+      slice(&s.y_term_prev, &a.y_prev[term], ck, false);
+      slice(&s.y_zero_prev, &a.y_prev[N - 1], ck, false);
       return s;
     };
     // (tall: the pass's register-held dimension is n, its streamed columns are the m samples)
@@ -964,20 +963,13 @@ struct ZeroRoute final : BatchRoute {
   // k::LassoFusedArgs), the row kernel's record from the other side.
   void PassSide(int chain, const Side& s, const ScaledZoneDesc& zone, double a1) {
     pass.chain = chain;
-    pass.e0 = s[6];
     k::LassoInstance& i = pass.inst;
     i.w = w;
     i.tpart = tpart;
     i.p = p;
-    i.u = s[0];
-    i.x1 = s[1];
-    i.x0 = s[2];
-    i.y1 = s[3];
-    i.y0 = s[4];
-    i.y1prev = s[5];
-    i.e0 = s[6];  // (a batched member carries it in its record)
+    i.state = s;
+    i.zone = ZoneOf(zone, a1);
     i.kappa = i.pkappa = -zp.L->scale();
-    SetThreshold(&i, zone, a1);
   }
   void RowsSide(const Side& s, const ScaledZoneDesc& zone, double a1) {
     rows.m = w.n;
@@ -985,15 +977,9 @@ struct ZeroRoute final : BatchRoute {
     rows.w = w;
     rows.tpart = tpart;
     rows.r = p;
-    rows.u = s[0];
-    rows.z = s[1];
-    rows.zq = s[2];
-    rows.yz = s[3];
-    rows.yq = s[4];
-    rows.yzprev = s[5];
-    rows.yqprev = s[6];
+    rows.state = s;
+    rows.zone = ZoneOf(zone, a1);
     rows.pkappa = -zp.L->scale();
-    SetThreshold(&rows, zone, a1);
   }
 
   // Fat: the x side into the pass (chain 2), the z side into the rows.
@@ -1024,50 +1010,35 @@ struct ZeroRoute final : BatchRoute {
     pass.lda = n;
     pass.A = CT;
     PassSide(3, sm, sz, az);
-    pass.zg = sz.g;
-    pass.zrhs = zp.rhs_arg;
-    pass.ke = -zp.e;
-    pass.dinv = zp.dinv_arg;
-    // (a batched member carries them in its record)
-    k::LassoInstance& rec = pass.inst;
-    rec.zg = pass.zg;
-    rec.zrhs = pass.zrhs;
-    rec.ke = pass.ke;
-    rec.dinv = pass.dinv;
+    k::LassoInstance& i = pass.inst;
+    i.zg = sz.g;
+    i.zrhs = zp.rhs_arg;
+    i.ke = -zp.e;
+    i.dinv = zp.dinv_arg;
     RowsSide(sn, sx, ax);
     rows.tall = true;
     if (!samples_smooth) return;
     // the pass in two halves (chains 4 and 5) around the sample kernel, which takes the z side's
-    // state, offset, rhs and pivots from the pass's record
+    // state, zone, offset, rhs and pivots from the pass's record
     pass.chain = 4;
     head = DVec::Zeros(3 * m, dt);
     dfarg = DVec::Zeros(2 * m, dt);
-    pass.zd = rec.zd = dfarg.Slice(0, m);
-    pass.zfarg = rec.zfarg = dfarg.Slice(m, m);
+    i.zd = dfarg.Slice(0, m);
+    i.zfarg = dfarg.Slice(m, m);
     k::ZeroTallSamplesArgs& t = samples;
-    const k::LassoInstance& i = pass.inst;
     t.m = m;
-    t.d = pass.zd;
-    t.farg = pass.zfarg;
-    t.rhs = pass.zrhs;
-    t.g = pass.zg;
-    t.u = i.u;
-    t.z = i.x1;
-    t.zq = i.x0;
-    t.yz = i.y1;
-    t.yq = i.y0;
-    t.yzprev = i.y1prev;
-    t.yqprev = i.e0;
+    t.d = i.zd;
+    t.farg = i.zfarg;
+    t.rhs = i.zrhs;
+    t.g = i.zg;
+    t.state = i.state;
+    t.zone = i.zone;
     t.hs = head.Slice(0, m);
     t.hys = head.Slice(m, m);
     t.hv = head.Slice(2 * m, m);
     t.kappa = i.kappa;
-    t.ke = pass.ke;
-    t.dinv = pass.dinv;
-    t.Bs = i.Bs;
-    t.Cs = i.Cs;
-    t.a1 = i.a1;
-    t.lam = i.lam;
+    t.ke = i.ke;
+    t.dinv = i.dinv;
   }
 
   // The dense pivot's vector of the first sweep from the current state, with the generic
@@ -1186,8 +1157,7 @@ struct TwoBlockRoute final : FusedRoute {
     w = DVec::Zeros(m, dt);
     grid = k::LassoFusedGrid(m, n, dt);
     tpart = DVec::Empty(static_cast<int64_t>(grid) * m, dt);
-    // the pass's arguments, once per Init; chain 1 reads the state arrays as
-    // u -> u0, y0 -> z0, y1 -> z1, y1prev -> z0_prev, e0 -> u1, e1 -> z1_prev
+    // the pass's arguments, once per Init; what chain 1 reads in each state array: k::LassoFusedArgs
     pass.m = m;
     pass.n = n;
     pass.lda = L.rows();
@@ -1196,21 +1166,21 @@ struct TwoBlockRoute final : FusedRoute {
     pass.a0 = a0;
     // beside the matrix: the partials, eight state vectors, p, w, and the inverse
     ResidentShare(m, n, dt, static_cast<int64_t>(grid) * m + 8 * n + 2 * m + m * m, /*auto_on=*/false, &pass);
-    pass.e0 = u1;
     pass.e1 = z1p;
     k::LassoInstance& s = pass.inst;
     s.w = w;
     s.tpart = tpart;
-    s.u = u0;
-    s.x0 = x0;
-    s.x1 = x1;
-    s.y0 = z0;
-    s.y1 = z1;
-    s.y1prev = z0p;
+    s.state.u = u0;
+    s.state.copy = x0;
+    s.state.var = x1;
+    s.state.y_zero = z0;
+    s.state.y_term = z1;
+    s.state.y_term_prev = z0p;
+    s.state.y_zero_prev = u1;
     s.p = p;
     s.rhs = ls.rhs_arg;
     s.kappa = s.pkappa = -L.scale();
-    SetThreshold(&s, sz, a1);
+    s.zone = ZoneOf(sz, a1);
     AdoptState(views, {&a.x, &a.z, &a.u, &a.z_prev});
     // p = rhs_arg - L(arg, var) (z0 - u0) of the current state, w = Dinv_arg p
     DVec v0 = z0.Clone();
@@ -1331,9 +1301,9 @@ void RunPassGroup(const Group& g) {
     for (int i : active) {
       const BatchRoute& mb = *g[i].route;
       EPS_CHECK(mb.pass.m == lead.pass.m && mb.pass.n == lead.pass.n && mb.pass.chain == lead.pass.chain);
-      EPS_CHECK(mb.pass.chain == 0 || mb.pass.inst.e0.n == lead.pass.n);  // the ZERO chains store through it
-      if (mb.pass.chain == 4)  // the halves of the tall pass store and load through them
-        EPS_CHECK(mb.pass.inst.zd.n == lead.pass.n && mb.pass.inst.zfarg.n == lead.pass.n);
+      // present where the chain stores or loads through them (the upload checks what is there)
+      EPS_CHECK(mb.pass.chain == 0 || mb.pass.inst.state.y_zero_prev.n == lead.pass.n);
+      if (mb.pass.chain == 4) EPS_CHECK(mb.pass.inst.zd.n == lead.pass.n && mb.pass.inst.zfarg.n == lead.pass.n);
       v.push_back(&mb.pass.inst);
       if (mb.Rows() != nullptr) r.push_back(mb.Rows());
       if (mb.Samples() != nullptr) t.push_back(mb.Samples());
@@ -1386,7 +1356,8 @@ void RunWideGroup(const Group& g) {
   DVec Pall = whiten ? DVec() : DVec::Zeros(npanels * panel_len, F32);
   for (int i = 0; i < K; ++i) {
     mem.push_back(g[i].route->pass.inst);
-    for (const DVec* v : {&mem[i].u, &mem[i].x0, &mem[i].x1, &mem[i].y0, &mem[i].y1, &mem[i].y1prev})
+    const k::ConsensusState& s = mem[i].state;
+    for (const DVec* v : {&s.u, &s.var, &s.copy, &s.y_term, &s.y_zero, &s.y_term_prev})
       EPS_CHECK_MSG(reinterpret_cast<uintptr_t>(v->data()) % 16 == 0, "wide batch: unaligned state vector");
     DVec slot = Wall.Slice(static_cast<int64_t>(i) * m, m);
     k::Copy(slot, mem[i].w);  // ForwardFromState's result at Init

@@ -58,22 +58,30 @@ void ReducePartials(int64_t rows, int nparts, const DVec& partial, double alpha,
                     const DVec& y, const DVec* add = nullptr);
 
 // ---- fused lasso sweep: one pass over A per ADMM sweep (kernels_fused.hip) ------------------
+// The state of one consensus constraint copy + a1 var = 0 (vectors of one length, updated in place):
+// `var` is the separable term's variable, `copy` the other term's (least squares; ZERO) own.
+struct ConsensusState {
+  DVec u, var, copy;
+  DVec y_term, y_zero;             // y of the separable term, y of the copy's term
+  DVec y_term_prev, y_zero_prev;   // their previous values (the lasso chain keeps no y_zero_prev)
+};
+// The separable term as a scaled zone, Cs zone(Bs v); a1 scales `var` in the constraint.
+struct ZoneParams {
+  DVec alpha_vec, beta_vec;        // optional per-entry alpha / beta
+  double Bs = 0, Cs = 0, a1 = 0, lam = 0, alpha = 1, beta = 1, M = 0;
+};
 // One instance of the sweep as the kernels read it (host view: scalars as double, narrowed to
 // the compute type in one place, kernels_fused_chain.h): the multi-block driver's fused state
 // plus its forward vectors.  Built once per Init by the drivers; a batch uploads its members'.
 struct LassoInstance {
   DVec w;        // m: the block-diagonal-scaled forward-substitution result of this sweep
   DVec tpart;    // LassoFusedGrid(m, n) * m: per-workgroup partials of A v0'
-  DVec u, x0, x1, y0, y1, y1prev;   // n each, updated in place
-  DVec alpha_vec, beta_vec;         // optional per-column alpha / beta of the scaled zone (n entries)
+  ConsensusState state;             // n each; what they mean per chain: LassoFusedArgs
+  ZoneParams zone;                  // (vectors: n entries)
   DVec p, rhs;   // m: the reduced partials (+ rhs), input of the inverse apply; its constant part
-  DVec e0;       // chain 2 alone (LassoFusedArgs::e0, which a batched member carries here): n
-  double kappa = 0;                 // x0 = v0 + kappa * (A^T w)
-  double Bs = 0, Cs = 0, a1 = 0;    // prox-1 pre / post scaling, y1 = a1 * x1
-  double lam = 0, alpha = 1, beta = 1, M = 0;
+  double kappa = 0;                 // copy = v0 + kappa * (A^T w)
   double pkappa = 0;                // scale of the summed partials in p (see LassoBatchInst)
-  // chains 3, 4, 5 alone, what LassoFusedArgs has under the same names, which a batched member
-  // carries here (n entries each, n the streamed dimension: the samples)
+  // chains 3, 4, 5 alone (n entries each, n the streamed dimension: the samples)
   DVec zg, zrhs;                    // chain 3, optional
   DVec zd, zfarg;                   // chain 4 writes zd, chain 5 reads zfarg
   double ke = 0, dinv = 0;          // chain 3
@@ -83,29 +91,23 @@ struct LassoFusedArgs {
   DVec A;        // m x n column-major
   LassoInstance inst;
   unsigned* epoch = nullptr;        // optional device counter, incremented once per launch
-  // chain = 1: the two-block driver's sweep (prox_admm_two_block.cc:97-112); the arrays then mean
-  // u -> u0, y0 -> z0, y1 -> z1, y1prev -> z0_prev, e0 -> u1, e1 -> z1_prev; a0, a1: the consensus
-  // constraint a0 x0 + a1 x1 = 0 the z-update projects onto.  f32 and f64.
+  // chain = 0: the lasso sweep; inst.state has copy -> x0, var -> x1, y_zero -> y0, y_term -> y1.
+  // chain = 1: the two-block driver's sweep (prox_admm_two_block.cc:97-112); copy -> x0, var -> x1,
+  // u -> u0, y_zero -> z0, y_term -> z1, y_term_prev -> z0_prev, y_zero_prev -> u1, e1 -> z1_prev;
+  // a0, a1: the consensus constraint a0 x0 + a1 x1 = 0 the z-update projects onto.  f32 and f64.
   // chain = 2: the sweep of a ZERO-term problem (scaled-zone term on x first, the
-  // projection's copy x' = v_x + kappa A^T w last); the arrays then mean u -> u on the x constraint,
-  // x0 -> x', x1 -> x, y0 -> y of the ZERO term, y1 -> y of the x term, y1prev -> the x term's
-  // previous y, e0 -> the ZERO term's previous y.  Profile tag "zero_fused".  f32 and f64.
+  // projection's copy x' = v_x + kappa A^T w last) on the x constraint.  Tag "zero_fused".  f32, f64.
   // chain = 3: the sample side of a TALL ZERO-term problem ("Tall C"): A is C^T
-  // (features x samples), w the copy x' of this sweep, the arrays are chain 2's on the z constraint
-  // (x0 -> z', x1 -> z, y0 -> y of the ZERO term, y1 -> y of the z term, y1prev / e0 -> their
-  // previous values); zg, zrhs: the z term's offset and the constant of the arg row per sample
-  // (optional), ke = -L(arg, z'), dinv = Dinv(arg)'s scalar; inst.kappa scales the product.  The
-  // partials are those of C^T f_arg of the next sweep.  Profile tag "zero_tall".  f32 and f64.
+  // (features x samples), w the copy x' of this sweep, the state is the z constraint's; inst.zg, zrhs:
+  // the z term's offset and the constant of the arg row per sample (optional), inst.ke = -L(arg, z'),
+  // dinv = Dinv(arg)'s scalar.  The partials are C^T f_arg's of the next sweep.  Tag "zero_tall".  f32, f64.
   // chain = 4, 5: chain 3 in two launches around ZeroTallSamples, for a smooth z term (256-thread
   // shapes alone).  4 (profile tag "zero_tall_dot"): zd[j] = A[:,j] . w per sample, nothing else is
   // read or written.  5 (profile tag "zero_tall_acc"): the partials of sum_j A[:,j] zfarg[j]; w and
-  // the state are not read.  zd, zfarg: n each.
+  // the state are not read.  inst.zd, zfarg: n each.
   int chain = 0;
   double a0 = 1;
-  DVec e0, e1;
-  DVec zg, zrhs;
-  double ke = 0, dinv = 0;
-  DVec zd, zfarg;
+  DVec e1;       // chain 1 alone
   // the matrix's share that is loaded to stay in the Infinity Cache (LassoFusedResidency); 0, 0:
   // every load non-temporal
   int qfull = 0;
@@ -127,11 +129,9 @@ struct ZeroRowsArgs {
   int64_t m = 0;
   int nparts = 0;
   DVec w, tpart, r, rhs, g;            // rhs, g: optional (empty: zero)
-  DVec u, z, zq, yz, yq, yzprev, yqprev;  // m each, in place: u on the z constraint, z, z', y of the
-                                          // z term and of the ZERO term, their previous values
-  DVec alpha_vec, beta_vec;            // optional per-row alpha / beta of the scaled zone
+  ConsensusState state;                // m each: the z constraint's (var -> z, copy -> z')
+  ZoneParams zone;                     // smooth: Bs, Cs, a1, lam alone are read
   double e = 0, pkappa = 0;
-  double Bs = 0, Cs = 0, a1 = 0, lam = 0, alpha = 1, beta = 1, M = 0;
   bool smooth = false;
   SmoothFn fn = SMOOTH_LOGISTIC;
   DVec hs, hys, hv;                    // smooth: m each, private to the caller
@@ -152,10 +152,10 @@ struct ZeroTallSamplesArgs {
   int64_t m = 0;
   DVec d, farg;                           // m each: in, out
   DVec rhs, g;                            // optional (empty: zero)
-  DVec u, z, zq, yz, yq, yzprev, yqprev;  // m each, in place (ZeroRowsArgs' meaning)
+  ConsensusState state;                   // m each: the z constraint's, as the pass's record has it
+  ZoneParams zone;                        // Bs, Cs, a1, lam alone are read
   DVec hs, hys, hv;                       // m each, private to the caller
   double kappa = 0, ke = 0, dinv = 0;     // scale of d; -L(arg, z'); Dinv(arg)'s scalar
-  double Bs = 0, Cs = 0, a1 = 0, lam = 0;
   SmoothFn fn = SMOOTH_LOGISTIC;
 };
 void ZeroTallSamples(const ZeroTallSamplesArgs& args);
@@ -244,11 +244,10 @@ void LassoBatchUpload(const std::vector<const LassoInstance*>& members, DType dt
 // threshold step is the group shrinkage of its rows with this weight (NORM_2 along axis 1)
 // instead of each instance's scaled zone.
 // `res`: the matrix's resident share, as in LassoFusedArgs.
-// `chain` = 2: the column side of ZERO-term members (every record carries e0; no group_lam; profile
-// tag "batch_zero_pass", count <= LassoBatchWidth(m, n, dt, 2)); 0: the lasso chain ("batch_fused_pass").
-// `chain` = 3, 4, 5: the sample side of tall ZERO-term members, A the transposed copy (tags
-// "batch_zero_tall_pass", "batch_zero_tall_dot", "batch_zero_tall_acc"; every record carries what
-// its chain reads of zg, zrhs, zd, zfarg, ke, dinv; count <= LassoBatchWidth(m, n, dt, chain)).
+// `chain`, as LassoFusedArgs::chain, every record holding what that chain reads and writes, count <=
+// LassoBatchWidth(m, n, dt, chain).  0: the lasso chain (profile tag "batch_fused_pass"); 2: the column
+// side of ZERO-term members ("batch_zero_pass"); 3, 4, 5: the sample side of tall ones, A the transposed
+// copy ("batch_zero_tall_pass", "batch_zero_tall_dot", "batch_zero_tall_acc").  2 to 5: no group_lam.
 void LassoBatchPass(int64_t m, int64_t n, int64_t lda, const DVec& A, const DVec& table, int first,
                     int count, const double* group_lam = nullptr, const FusedResidency& res = FusedResidency(),
                     int chain = 0);

@@ -221,17 +221,15 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
   }
 }
 
-template <class T> const T* OptT(const DVec& v) { return v.n > 0 ? v.as<T>() : nullptr; }
-
 template <class T, int NR, int BS>
 void LaunchFused(const LassoFusedArgs& a, int grid) {
   const LassoBatchInst<T> i = Narrow<T>(a.inst);
-  T* e0 = a.chain != 0 ? a.e0.as<T>() : nullptr;
+  const ZoneParams& z = a.inst.zone;
+  T* e0 = a.chain == 4 ? i.zd : i.e0;  // MODE 4 stores d through it
   T* e1 = a.chain == 1 ? a.e1.as<T>() : nullptr;
   ZeroTallScalarsT<T> zt = {nullptr, nullptr, T(0), T(0)};
-  if (a.chain == 3) zt = {OptT<T>(a.zg), OptT<T>(a.zrhs), static_cast<T>(a.ke), static_cast<T>(a.dinv)};
-  if (a.chain == 4) e0 = a.zd.as<T>();        // MODE 4 stores d through it
-  if (a.chain == 5) zt.rhs = a.zfarg.as<T>();  // MODE 5 reads f_arg through it
+  if (a.chain == 3) zt = {i.zg, i.zrhs, i.ke, i.dinv};
+  if (a.chain == 5) zt.rhs = i.zfarg;  // MODE 5 reads f_arg through it
   auto kernel = LassoFusedStreamKernelT<T, NR, BS, 0>;
   if (a.chain == 1) kernel = LassoFusedStreamKernelT<T, NR, BS, 1>;
   if (a.chain == 2) kernel = LassoFusedStreamKernelT<T, NR, BS, 2>;
@@ -244,8 +242,8 @@ void LaunchFused(const LassoFusedArgs& a, int grid) {
   hipLaunchKernelGGL(
       kernel,
       dim3(grid), dim3(BS), 0, Runtime::Get().stream(), a.m, a.n, a.A.as<T>(), a.lda, i.w,
-      ScalarsOf<T>(i, a.a0, a.inst.a1), i.u, i.x0, i.x1, i.y0, i.y1, i.y1prev, i.tpart, a.epoch, e0, e1,
-      a.qfull, a.jcut, zt);
+      ScalarsOf<T>(z, a.inst.kappa, a.a0, 1.0 / (a.a0 * a.a0 + z.a1 * z.a1)), i.u, i.x0, i.x1, i.y0, i.y1,
+      i.y1prev, i.tpart, a.epoch, e0, e1, a.qfull, a.jcut, zt);
 }
 
 // The instantiation for (type, threads, 16-byte row chunks a thread needs).  512 threads: the
@@ -460,32 +458,20 @@ __global__ __launch_bounds__(kBlock) void ZeroSmoothHeadKernel(
   hv[i] = h.v;
 }
 
-template <class T> FusedScalarsT<T> ZeroRowScalars(const ZeroRowsArgs& a) {
-  return {static_cast<T>(-a.e), static_cast<T>(a.Bs), static_cast<T>(a.Cs), static_cast<T>(a.a1),
-          static_cast<T>(a.lam), static_cast<T>(a.alpha), static_cast<T>(a.beta), static_cast<T>(a.M),
-          T(1), T(1), OptT<T>(a.alpha_vec), OptT<T>(a.beta_vec)};
-}
-
 template <class T> ZeroRowsInst<T> RowsInstOf(const ZeroRowsArgs& a) {
   ZeroRowsInst<T> d;
   d.tpart = a.tpart.as<T>();
   d.w = a.w.as<T>();
   d.rhs = OptT<T>(a.rhs);
   d.g = OptT<T>(a.g);
-  d.u = a.u.as<T>();
-  d.z = a.z.as<T>();
-  d.zq = a.zq.as<T>();
-  d.yz = a.yz.as<T>();
-  d.yq = a.yq.as<T>();
-  d.yzprev = a.yzprev.as<T>();
-  d.yqprev = a.yqprev.as<T>();
+  NarrowState<T>(a.state, &d.u, &d.z, &d.zq, &d.yz, &d.yq, &d.yzprev, &d.yqprev);
   d.r = a.r.as<T>();
   d.hs = a.smooth ? a.hs.as<T>() : nullptr;
   d.hys = a.smooth ? a.hys.as<T>() : nullptr;
   d.hv = a.smooth ? a.hv.as<T>() : nullptr;
-  d.c = ZeroRowScalars<T>(a);
+  d.c = ScalarsOf<T>(a.zone, -a.e, 1, 1);
   d.pkappa = static_cast<T>(a.pkappa);
-  d.lam64 = a.lam;
+  d.lam64 = a.zone.lam;
   return d;
 }
 
@@ -526,17 +512,25 @@ void UploadRowsT(const std::vector<const ZeroRowsArgs*>& members, DVec* table) {
 
 template <class T>
 void LaunchZeroSmoothHead(const ZeroRowsArgs& a) {
+  const ZeroRowsInst<T> I = RowsInstOf<T>(a);
   hipLaunchKernelGGL((ZeroSmoothHeadKernel<T, FnLogistic>), dim3(static_cast<unsigned>((a.m + kBlock - 1) / kBlock)),
-                     dim3(kBlock), 0, Runtime::Get().stream(), a.m, ZeroRowScalars<T>(a), a.lam, OptT<T>(a.g),
-                     a.u.as<T>(), a.yz.as<T>(), a.yq.as<T>(), a.hs.as<T>(), a.hys.as<T>(), a.hv.as<T>());
+                     dim3(kBlock), 0, Runtime::Get().stream(), a.m, I.c, I.lam64, I.g, I.u, I.yz, I.yq, I.hs, I.hys,
+                     I.hv);
+}
+
+// Every array of a constraint's state has n entries of type dt (`zero_prev`: y_zero_prev too).
+void CheckState(const ConsensusState& s, int64_t n, DType dt, bool zero_prev = true) {
+  for (const DVec* v : {&s.u, &s.var, &s.copy, &s.y_term, &s.y_zero, &s.y_term_prev})
+    EPS_CHECK(v->n == n && v->dt == dt);
+  if (zero_prev) EPS_CHECK(s.y_zero_prev.n == n && s.y_zero_prev.dt == dt);
 }
 
 void CheckZeroRows(const ZeroRowsArgs& a) {
   const DType dt = a.w.dt;
   EPS_CHECK(a.m >= 1 && a.nparts >= 1 && a.tpart.dt == dt && a.tpart.n >= static_cast<int64_t>(a.nparts) * a.m);
-  for (const DVec* v : {&a.w, &a.r, &a.u, &a.z, &a.zq, &a.yz, &a.yq, &a.yzprev, &a.yqprev})
-    EPS_CHECK(v->n == a.m && v->dt == dt);
-  for (const DVec* v : {&a.rhs, &a.g, &a.alpha_vec, &a.beta_vec})
+  EPS_CHECK(a.w.n == a.m && a.r.n == a.m && a.r.dt == dt);
+  CheckState(a.state, a.m, dt);
+  for (const DVec* v : {&a.rhs, &a.g, &a.zone.alpha_vec, &a.zone.beta_vec})
     if (v->n > 0) EPS_CHECK(v->n == a.m && v->dt == dt);
   EPS_CHECK_MSG(!(a.tall && a.smooth), "the tall ZERO-term x side has no smooth form");
   if (!a.smooth) return;
@@ -564,37 +558,39 @@ void ZeroFusedRows(const ZeroRowsArgs& a) {
 
 namespace {
 
-template <class T> FusedScalarsT<T> ZeroTallSampleScalars(const ZeroTallSamplesArgs& a) {
-  return {static_cast<T>(a.kappa), static_cast<T>(a.Bs), static_cast<T>(a.Cs), static_cast<T>(a.a1),
-          static_cast<T>(a.lam), T(1), T(1), T(0), T(1), T(1), nullptr, nullptr};
-}
-
 void CheckZeroTallSamples(const ZeroTallSamplesArgs& a) {
   const DType dt = a.d.dt;
   EPS_CHECK(a.m >= 1);
-  for (const DVec* v : {&a.d, &a.farg, &a.u, &a.z, &a.zq, &a.yz, &a.yq, &a.yzprev, &a.yqprev, &a.hs, &a.hys, &a.hv})
-    EPS_CHECK(v->n == a.m && v->dt == dt);
+  for (const DVec* v : {&a.d, &a.farg, &a.hs, &a.hys, &a.hv}) EPS_CHECK(v->n == a.m && v->dt == dt);
+  CheckState(a.state, a.m, dt);
   for (const DVec* v : {&a.rhs, &a.g})
     if (v->n > 0) EPS_CHECK(v->n == a.m && v->dt == dt);
   EPS_CHECK_MSG(a.fn == SMOOTH_LOGISTIC, "the tall ZERO-term sample side takes SUM_LOGISTIC alone, got " << a.fn);
 }
 
 template <class T> ZeroTallSamplesInst<T> SamplesInstOf(const ZeroTallSamplesArgs& a) {
-  return {ZeroTallSampleScalars<T>(a), a.lam, static_cast<T>(a.ke), static_cast<T>(a.dinv), OptT<T>(a.g),
-          OptT<T>(a.rhs), a.d.as<T>(), a.u.as<T>(), a.z.as<T>(), a.zq.as<T>(), a.yz.as<T>(), a.yq.as<T>(),
-          a.yzprev.as<T>(), a.yqprev.as<T>(), a.hs.as<T>(), a.hys.as<T>(), a.hv.as<T>(), a.farg.as<T>()};
+  ZeroTallSamplesInst<T> d = {ScalarsOf<T>(a.zone, a.kappa, 1, 1), a.zone.lam, static_cast<T>(a.ke),
+                              static_cast<T>(a.dinv), OptT<T>(a.g), OptT<T>(a.rhs), a.d.as<T>()};
+  d.c.alpha = d.c.beta = T(1);  // the smooth term has no zone, whatever the description holds
+  d.c.M = T(0);
+  d.c.alpha_v = d.c.beta_v = nullptr;
+  NarrowState<T>(a.state, &d.u, &d.z, &d.zq, &d.yz, &d.yq, &d.yzprev, &d.yqprev);
+  d.hs = a.hs.as<T>();
+  d.hys = a.hys.as<T>();
+  d.hv = a.hv.as<T>();
+  d.farg = a.farg.as<T>();
+  return d;
 }
 
 template <class T>
 void LaunchZeroTallSamples(const ZeroTallSamplesArgs& a, bool head_only) {
   const dim3 grid(static_cast<unsigned>((a.m + kBlock - 1) / kBlock));
+  const ZeroTallSamplesInst<T> I = SamplesInstOf<T>(a);
   if (head_only)
     hipLaunchKernelGGL((ZeroSmoothHeadKernel<T, FnLogistic>), grid, dim3(kBlock), 0, Runtime::Get().stream(), a.m,
-                       ZeroTallSampleScalars<T>(a), a.lam, OptT<T>(a.g), a.u.as<T>(), a.yz.as<T>(), a.yq.as<T>(),
-                       a.hs.as<T>(), a.hys.as<T>(), a.hv.as<T>());
+                       I.c, I.lam64, I.g, I.u, I.yz, I.yq, I.hs, I.hys, I.hv);
   else
-    hipLaunchKernelGGL((ZeroTallSamplesKernel<T, FnLogistic>), grid, dim3(kBlock), 0, Runtime::Get().stream(), a.m,
-                       SamplesInstOf<T>(a));
+    hipLaunchKernelGGL((ZeroTallSamplesKernel<T, FnLogistic>), grid, dim3(kBlock), 0, Runtime::Get().stream(), a.m, I);
 }
 
 template <class T>
@@ -860,17 +856,15 @@ void LassoFusedPass(const LassoFusedArgs& a) {
   const DType dt = a.A.dt;
   const LassoInstance& s = a.inst;
   EPS_CHECK(s.w.n == a.m && s.w.dt == dt);
-  for (const DVec* v : {&s.u, &s.x0, &s.x1, &s.y0, &s.y1, &s.y1prev})
-    EPS_CHECK(v->n == a.n && v->dt == dt);
-  for (const DVec* v : {&s.alpha_vec, &s.beta_vec})
+  CheckState(s.state, a.n, dt, /*zero_prev=*/a.chain >= 1 && a.chain <= 3);
+  for (const DVec* v : {&s.zone.alpha_vec, &s.zone.beta_vec})
     if (v->n > 0) EPS_CHECK(v->n == a.n && v->dt == dt);
-  if (a.chain == 1) EPS_CHECK(a.e0.n == a.n && a.e1.n == a.n && a.e0.dt == dt && a.e1.dt == dt);
-  if (a.chain == 2 || a.chain == 3) EPS_CHECK(a.e0.n == a.n && a.e0.dt == dt);
+  if (a.chain == 1) EPS_CHECK(a.e1.n == a.n && a.e1.dt == dt);
   EPS_CHECK(a.chain >= 0 && a.chain <= 5);
-  if (a.chain == 4) EPS_CHECK(a.zd.n == a.n && a.zd.dt == dt);
-  if (a.chain == 5) EPS_CHECK(a.zfarg.n == a.n && a.zfarg.dt == dt);
+  if (a.chain == 4) EPS_CHECK(s.zd.n == a.n && s.zd.dt == dt);
+  if (a.chain == 5) EPS_CHECK(s.zfarg.n == a.n && s.zfarg.dt == dt);
   if (a.chain == 3)
-    for (const DVec* v : {&a.zg, &a.zrhs})
+    for (const DVec* v : {&s.zg, &s.zrhs})
       if (v->n > 0) EPS_CHECK(v->n == a.n && v->dt == dt);
   const int grid = LassoFusedGrid(a.m, a.n, dt);
   const int block = LassoFusedBlock(a.m, a.n, dt);

@@ -394,12 +394,13 @@ int LassoBatchWidth(int64_t m, int64_t n, DType dt, int chain) {
 }
 
 void LassoBatchUpload(const std::vector<const LassoInstance*>& members, DType dt, DVec* table) {
-  for (const LassoInstance* s : members)
-    for (const DVec* v : {&s->w, &s->tpart, &s->u, &s->x0, &s->x1, &s->y0, &s->y1, &s->y1prev, &s->p})
+  for (const LassoInstance* s : members) {
+    const ConsensusState& c = s->state;
+    for (const DVec* v : {&s->w, &s->tpart, &c.u, &c.var, &c.copy, &c.y_term, &c.y_zero, &c.y_term_prev, &s->p})
       EPS_CHECK(v->dt == dt && v->n > 0);
-  for (const LassoInstance* s : members)
-    for (const DVec* v : {&s->e0, &s->zg, &s->zrhs, &s->zd, &s->zfarg})
-      EPS_CHECK(v->n == 0 || (v->dt == dt && v->n == s->u.n));
+    for (const DVec* v : {&c.y_zero_prev, &s->zg, &s->zrhs, &s->zd, &s->zfarg})
+      EPS_CHECK(v->n == 0 || (v->dt == dt && v->n == c.u.n));
+  }
   if (dt == F32) UploadT<float>(members, table);
   else UploadT<double>(members, table);
 }

@@ -51,45 +51,57 @@ template <class T> struct FusedScalarsT {
   const T* beta_v;
 };
 
-// One instance in the compute type T, as the kernels read it: the only place where the host's
-// record (scalars as double) is narrowed.  The single pass takes its scalars from it
-// (ScalarsOf), the batched passes upload it as it is.
+// The host's records (scalars as double) are narrowed to the compute type T here alone.
+template <class T> T* OptT(const DVec& v) { return v.n > 0 ? v.as<T>() : nullptr; }
+
+// The zone of a record as the chains read it, with the caller's kappa and two-block scalars.
+template <class T> FusedScalarsT<T> ScalarsOf(const ZoneParams& z, double kappa, double a0, double inv_aa) {
+  return {static_cast<T>(kappa), static_cast<T>(z.Bs), static_cast<T>(z.Cs), static_cast<T>(z.a1),
+          static_cast<T>(z.lam), static_cast<T>(z.alpha), static_cast<T>(z.beta), static_cast<T>(z.M),
+          static_cast<T>(a0), static_cast<T>(inv_aa), OptT<T>(z.alpha_vec), OptT<T>(z.beta_vec)};
+}
+
+// The seven state pointers into a device record's own fields (y_zero_prev: nullptr if empty).
+template <class T>
+void NarrowState(const ConsensusState& s, T** u, T** var, T** copy, T** y_term, T** y_zero, T** y_term_prev,
+                 T** y_zero_prev) {
+  *u = s.u.as<T>();
+  *var = s.var.as<T>();
+  *copy = s.copy.as<T>();
+  *y_term = s.y_term.as<T>();
+  *y_zero = s.y_zero.as<T>();
+  *y_term_prev = s.y_term_prev.as<T>();
+  *y_zero_prev = OptT<T>(s.y_zero_prev);
+}
+
+// One instance in the compute type T, as the kernels read it: the single pass takes its
+// arguments from it, the batched passes upload it as it is.
 template <class T> LassoBatchInst<T> Narrow(const LassoInstance& s) {
   LassoBatchInst<T> d;
   d.w = s.w.as<T>();
   d.tpart = s.tpart.as<T>();
-  d.u = s.u.as<T>();
-  d.x0 = s.x0.as<T>();
-  d.x1 = s.x1.as<T>();
-  d.y0 = s.y0.as<T>();
-  d.y1 = s.y1.as<T>();
-  d.y1prev = s.y1prev.as<T>();
-  d.alpha_v = s.alpha_vec.n > 0 ? s.alpha_vec.as<T>() : nullptr;
-  d.beta_v = s.beta_vec.n > 0 ? s.beta_vec.as<T>() : nullptr;
+  NarrowState<T>(s.state, &d.u, &d.x1, &d.x0, &d.y1, &d.y0, &d.y1prev, &d.e0);
+  const ZoneParams& z = s.zone;
+  d.alpha_v = OptT<T>(z.alpha_vec);
+  d.beta_v = OptT<T>(z.beta_vec);
   d.p = s.p.as<T>();
-  d.rhs = s.rhs.n > 0 ? s.rhs.as<T>() : nullptr;
+  d.rhs = OptT<T>(s.rhs);
   d.kappa = static_cast<T>(s.kappa);
   d.pkappa = static_cast<T>(s.pkappa);
-  d.Bs = static_cast<T>(s.Bs);
-  d.Cs = static_cast<T>(s.Cs);
-  d.a1 = static_cast<T>(s.a1);
-  d.lam = static_cast<T>(s.lam);
-  d.alpha = static_cast<T>(s.alpha);
-  d.beta = static_cast<T>(s.beta);
-  d.M = static_cast<T>(s.M);
-  d.e0 = s.e0.n > 0 ? s.e0.as<T>() : nullptr;
-  d.zg = s.zg.n > 0 ? s.zg.as<T>() : nullptr;
-  d.zrhs = s.zrhs.n > 0 ? s.zrhs.as<T>() : nullptr;
-  d.zd = s.zd.n > 0 ? s.zd.as<T>() : nullptr;
-  d.zfarg = s.zfarg.n > 0 ? s.zfarg.as<T>() : nullptr;
+  d.Bs = static_cast<T>(z.Bs);
+  d.Cs = static_cast<T>(z.Cs);
+  d.a1 = static_cast<T>(z.a1);
+  d.lam = static_cast<T>(z.lam);
+  d.alpha = static_cast<T>(z.alpha);
+  d.beta = static_cast<T>(z.beta);
+  d.M = static_cast<T>(z.M);
+  d.zg = OptT<T>(s.zg);
+  d.zrhs = OptT<T>(s.zrhs);
+  d.zd = OptT<T>(s.zd);
+  d.zfarg = OptT<T>(s.zfarg);
   d.ke = static_cast<T>(s.ke);
   d.dinv = static_cast<T>(s.dinv);
   return d;
-}
-
-template <class T> FusedScalarsT<T> ScalarsOf(const LassoBatchInst<T>& i, double a0, double a1) {
-  return {i.kappa, i.Bs, i.Cs, i.a1, i.lam, i.alpha, i.beta, i.M,
-          static_cast<T>(a0), static_cast<T>(1.0 / (a0 * a0 + a1 * a1)), i.alpha_v, i.beta_v};
 }
 
 template <class T> __device__ inline T WaveSumT(T v) {
