@@ -626,3 +626,163 @@ def test_long_slices_norm2_soc_zone_epigraph(solve_mod, dtype):
                     (ProxFunction.SUM_DEADZONE, dict(scaled_zone_params=wire.ProxScaledZoneParams(m=0.3)))):
         ez = ir.prox(typ, Y, tv, epigraph=True, has_axis=True, axis=0, **kw)
         run(solve_mod, ez, 1.0, {"var:Y": rng.randn(n * m), "var:t": [100.0, 1e7]}, tol_for(dtype))
+
+
+# Slice shapes that reach every group size of the segment kernels (GroupFor: 1, 8, 64 or 256
+# lanes per slice) and its boundaries.  (rows, columns, axis) of the column-major argument:
+# axis 0 gives contiguous slices of `rows` entries, axis 1 strided ones of `columns` entries.
+GROUP_SHAPES = {
+    "1x7": (1, 7, 0),                # one lane per slice
+    "5x37": (5, 37, 0),              # 8 lanes; 32 slices per workgroup, the second one ragged
+    "8x3": (8, 3, 0),
+    "9x3": (9, 3, 0),                # 64 lanes
+    "256x5": (256, 5, 0),            # 64 lanes; 4 slices per workgroup, the second one ragged
+    "257x3": (257, 3, 0),            # the whole workgroup
+    "strided_1027x3": (1027, 3, 1),  # >= 1024 strided slices: one lane each, 3 entries per lane
+    "strided_37x5": (37, 5, 1),      # strided, 8 lanes
+}
+GROUP_PROX = {
+    "max": (ProxFunction.MAX, {}),
+    "sum_largest_1": VECTOR_PROX["sum_largest_1"],
+    "sum_largest_4": VECTOR_PROX["sum_largest_4"],
+    "log_sum_exp": (ProxFunction.LOG_SUM_EXP, {}),
+    "norm_2": (ProxFunction.NORM_2, {}),
+}
+# epigraphs: the function value of one slice, which places the scalar input of that slice on
+# either side of it
+GROUP_EPI_F = {
+    "max": np.max,
+    "sum_largest_4": lambda z: np.sort(z)[::-1][:4].sum(),
+    "log_sum_exp": lambda z: z.max() + np.log(np.exp(z - z.max()).sum()),
+    "sum_exp": lambda z: np.exp(z).sum(),
+    "sum_logistic": lambda z: np.logaddexp(0, z).sum(),
+    "sum_neg_entr": lambda z: (z * np.log(z)).sum(),
+}
+GROUP_ZONE = {"hinge": (ProxFunction.SUM_HINGE, {}),
+              "deadzone": (ProxFunction.SUM_DEADZONE, dict(scaled_zone_params=wire.ProxScaledZoneParams(m=0.3)))}
+GROUP_OPS = (["prox_" + k for k in sorted(GROUP_PROX)] + ["epi_" + k for k in sorted(GROUP_EPI_F)] +
+             ["zone_" + k for k in sorted(GROUP_ZONE)] + ["soc"])
+
+
+def scalars_either_side(fvals, rng):
+    """Two scalar inputs per slice around its function value: the first infeasible on the even
+    slices and feasible on the odd ones, the second the other way round."""
+    gap = 0.5 + np.abs(rng.randn(len(fvals)))
+    sign = np.where(np.arange(len(fvals)) % 2 == 0, -1.0, 1.0)
+    return fvals + sign * gap, fvals - sign * gap
+
+
+def sum_largest_prox_rows(A, lam, k):
+    """Exact prox of lam * sum_largest(., k) of every row of A (one lam per row, or one for all):
+    x = v - clip(v - q, 0, lam) with sum_i clip(v_i - q, 0, lam) = min(k, len) lam, q by bisection."""
+    lam = np.broadcast_to(np.asarray(lam, dtype=float), A.shape[:1])[:, None]
+    kk = min(k, A.shape[1])
+    lo, hi = A.min(axis=1, keepdims=True) - lam, A.max(axis=1, keepdims=True)
+    for _ in range(100):
+        q = 0.5 * (lo + hi)
+        above = np.clip(A - q, 0, lam).sum(axis=1, keepdims=True) > kk * lam
+        lo, hi = np.where(above, q, lo), np.where(above, hi, q)
+    return A - np.clip(A - 0.5 * (lo + hi), 0, lam)
+
+
+def sum_largest_epigraph_rows(A, s, k):
+    """Exact projection of every (row of A, s_i) onto {sum_largest(x, k) <= t}: (prox_{lam f}(v),
+    s + lam) with lam >= 0 the root of the decreasing f(prox_{lam f}(v)) - lam - s, by bisection
+    on [0, f(v) - s]."""
+    f = lambda Z: np.sort(Z, axis=1)[:, ::-1][:, :k].sum(axis=1)
+    lo, hi = np.zeros(len(s)), np.maximum(f(A) - s, 0.0)
+    for _ in range(60):
+        lam = 0.5 * (lo + hi)
+        above = f(sum_largest_prox_rows(A, lam, k)) - lam - s > 0
+        lo, hi = np.where(above, lam, lo), np.where(above, hi, lam)
+    lam = 0.5 * (lo + hi)
+    return sum_largest_prox_rows(A, lam, k), s + lam
+
+
+def compare_where_reference_exact(got, want, exact, tol):
+    """Rows of device results against an exact answer, and against the oracle on the rows where
+    the oracle is exact itself.  The reference's sorted sweep (sum_largest.cc:36-55) leaves its
+    loop when every entry has entered the window, before sum_i clip(v_i - q, 0, lam) = k lam
+    holds; slices of 3 and 5 entries with k = 4 meet that on most inputs."""
+    np.testing.assert_allclose(got, exact, **tol)
+    ok = np.max(np.abs(want - exact), axis=1) <= 1e-4
+    np.testing.assert_allclose(got[ok], want[ok], **tol)
+
+
+@pytest.mark.parametrize("op", GROUP_OPS)
+@pytest.mark.parametrize("shape", sorted(GROUP_SHAPES))
+def test_segment_ops_every_group_size(solve_mod, dtype, shape, op):
+    """Every sliced operator at every group size the launch helper chooses, with ragged last
+    workgroups and strided slices, against the oracle.  Each epigraph sees, for every slice, one
+    scalar input outside the epigraph and one inside it, mixed within a launch so that neighbouring
+    groups of one wavefront stop at different iterations."""
+    m, n, axis = GROUP_SHAPES[shape]
+    count = n if axis == 0 else m
+    rng = np.random.RandomState(31)
+    V = rng.randn(m, n)
+    rows = lambda A: A.T if axis == 0 else A  # one slice per row
+    flat = lambda A: A.reshape(-1, order="F")
+    unflat = lambda b: rows(b.reshape((m, n), order="F"))
+    X = ir.variable(m, n, "var:X")
+    t = ir.variable(1, n, "var:t") if axis == 0 else ir.variable(m, 1, "var:t")
+    kind, _, name = op.partition("_")
+    if kind == "prox":
+        typ, kw = GROUP_PROX[name]
+        e = ir.prox(typ, X, has_axis=True, axis=axis, **kw)
+        if typ != ProxFunction.SUM_LARGEST:
+            run(solve_mod, e, 0.7, {"var:X": flat(V)}, tol_for(dtype))
+            return
+        got, want = both(solve_mod, e, 0.7, {"var:X": flat(V)})
+        exact = sum_largest_prox_rows(rows(V), 0.7, kw["sum_largest_params"].k)
+        compare_where_reference_exact(unflat(got["var:X"]), unflat(want["var:X"]), exact, tol_for(dtype))
+    elif kind == "epi":
+        if name == "sum_neg_entr":
+            V = np.abs(V) + 0.2  # inside the domain
+        typ, kw = EPIGRAPHS[name]
+        e = ir.prox(typ, X, t, epigraph=True, has_axis=True, axis=axis, **kw)
+        fvals = np.array([GROUP_EPI_F[name](z) for z in rows(V)])
+        for s in scalars_either_side(fvals, rng):
+            got, want = both(solve_mod, e, 1.0, {"var:X": flat(V), "var:t": s})
+            GX, WX = unflat(got["var:X"]), unflat(want["var:X"])
+            if name == "sum_largest_4":  # bisection to |g| <= 1e-5 in the reference (newton.cc:252)
+                tol = dict(rtol=5e-5, atol=5e-5) if dtype == "f64" else dict(rtol=1e-3, atol=1e-3)
+                ex, et = sum_largest_epigraph_rows(rows(V), s, 4)
+                compare_where_reference_exact(np.column_stack([GX, got["var:t"]]),
+                                              np.column_stack([WX, want["var:t"]]),
+                                              np.column_stack([ex, et]), tol)
+                continue
+            for i in range(count):
+                if name in SMOOTH_F and s[i] < fvals[i]:
+                    # The reference's joint Newton can end far from the projection, even below s
+                    # (check_epigraph then takes the point for a feasible one): where its own KKT
+                    # residual says so, the KKT conditions alone decide, to check_epigraph's bound.
+                    f, vi = SMOOTH_F[name](), rows(V)[i]
+                    interior = name != "sum_neg_entr" or np.all(GX[i] > 1.5e-6)
+                    if interior and kkt_norm(f, WX[i], want["var:t"][i], vi, s[i])[0] > 1e-4:
+                        r_gpu, lam = kkt_norm(f, GX[i], got["var:t"][i], vi, s[i])
+                        assert lam > 0
+                        assert r_gpu <= (1e-9 if dtype == "f64" else 2e-4) * max(1.0, np.linalg.norm(vi)), r_gpu
+                        continue
+                check_epigraph(dtype, name, {"x": GX[i], "t": got["var:t"][i:i + 1]},
+                               {"x": WX[i], "t": want["var:t"][i:i + 1]}, rows(V)[i], s[i], "x", "t")
+    elif kind == "zone":
+        typ, kw = GROUP_ZONE[name]
+        e = ir.prox(typ, X, t, epigraph=True, has_axis=True, axis=axis, **kw)
+        # The oracle's sorted search has no answer when the multiplier exceeds every key (a slice
+        # with no active entry, or a scalar input far below zero): the first entry of every slice is
+        # put above the zone, so that f > 0, and the infeasible scalar inputs lie in (0, f).
+        rows(V)[:, 0] = np.abs(rows(V)[:, 0]) + 0.5
+        zone_f = {"hinge": lambda Z: np.maximum(Z, 0).sum(axis=1),
+                  "deadzone": lambda Z: np.maximum(np.abs(Z) - 0.3, 0).sum(axis=1)}[name]
+        fvals = zone_f(rows(V))
+        outside, inside = fvals * (0.1 + 0.8 * rng.rand(count)), fvals + 0.5 + np.abs(rng.randn(count))
+        even = np.arange(count) % 2 == 0
+        for s in (np.where(even, outside, inside), np.where(even, inside, outside)):
+            run(solve_mod, e, 1.0, {"var:X": flat(V), "var:t": s}, tol_for(dtype))
+    else:  # one cone per row of the matrix: `count` slices of the shape's length, strided
+        ln = m if axis == 0 else n
+        Xr, tv = ir.variable(count, ln, "var:X"), ir.variable(count, 1, "var:t")
+        e = ir.prox(ProxFunction.SECOND_ORDER_CONE, tv, Xr, arg_size=[(count, 1), (count, ln)])
+        R = rng.randn(count, ln)
+        for s in scalars_either_side(np.linalg.norm(R, axis=1), rng):
+            run(solve_mod, e, 1.0, {"var:X": flat(R), "var:t": s}, tol_for(dtype, f64=1e-12, f32=1e-5))
