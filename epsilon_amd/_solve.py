@@ -544,6 +544,19 @@ DENSE_OP_SENTINEL = -777.25   # EPS_DENSE_OP_SENTINEL
 DENSE_OP_REDUCTIONS = ("sumsq", "sumsq_diff", "dot")
 
 
+def _set_operands(g, operands):
+    """Point the fields `name` and `name`_len of the struct g at each given (name, value) as
+    contiguous float64; returns the arrays, which must outlive the call that reads g."""
+    keep = []
+    for name, v in operands:
+        if v is not None:
+            v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+            keep.append(v)
+            setattr(g, name, v.ctypes.data_as(ctypes.c_void_p))
+            setattr(g, name + "_len", v.size)
+    return keep
+
+
 def dense_op(op, rows=0, cols=0, lda=None, nparts=1, alpha=1.0, beta=0.0, a=None, x=None, y=None,
              add=None, a_off=0, x_off=0, y_off=0, add_off=0, accumulate=False, use_work=False,
              with_add=None, alias_xy=False, preset=0.0):
@@ -562,13 +575,7 @@ def dense_op(op, rows=0, cols=0, lda=None, nparts=1, alpha=1.0, beta=0.0, a=None
     g.rows, g.cols, g.nparts = rows, cols, nparts
     g.lda = rows if lda is None else lda
     g.alpha, g.beta, g.preset = alpha, beta, preset
-    keep = []
-    for name, v in (("a", a), ("x", x), ("y", y), ("add", add)):
-        if v is not None:
-            v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
-            keep.append(v)
-            setattr(g, name, v.ctypes.data_as(ctypes.c_void_p))
-            setattr(g, name + "_len", v.size)
+    keep = _set_operands(g, (("a", a), ("x", x), ("y", y), ("add", add)))
     g.a_off, g.x_off, g.y_off, g.add_off = a_off, x_off, y_off, add_off
     g.accumulate, g.use_work, g.alias_xy = int(accumulate), int(use_work), int(alias_xy)
     g.with_add = int(add is not None if with_add is None else with_add)
@@ -617,13 +624,7 @@ def gemm_op(op, M=0, N=0, K=0, trans_a=False, trans_b=False, alpha=1.0, beta=0.0
     g.ldc = M if ldc is None else ldc
     g.a_off, g.b_off, g.c_off = a_off, b_off, c_off
     g.batch, g.outer, g.sA, g.sB, g.sC, g.sA2, g.sB2 = batch, outer, sA, sB, sC, sA2, sB2
-    keep = []
-    for name, v in (("a", a), ("b", b), ("c", c), ("d", d)):
-        if v is not None:
-            v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
-            keep.append(v)
-            setattr(g, name, v.ctypes.data_as(ctypes.c_void_p))
-            setattr(g, name + "_len", v.size)
+    keep = _set_operands(g, (("a", a), ("b", b), ("c", c), ("d", d)))
     n_out = (max(N, 0) if op == "col_abs_sums" else g.c_len) + 2 * DENSE_OP_GUARD
     out = np.full(n_out, np.nan)
     route = ctypes.create_string_buffer(32)
@@ -654,10 +655,7 @@ def factor_op(op, n=0, a=None, a_off=0, form=-1, lo=0, cnt=0, out_cols=None, wan
     g.op = op.encode("utf-8") if op is not None else None
     g.n, g.form, g.a_off, g.lo, g.cnt = n, form, a_off, lo, cnt
     g.out_cols = (cnt if op == "spd_inverse_columns" else 0) if out_cols is None else out_cols
-    if a is not None:
-        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
-        g.a = a.ctypes.data_as(ctypes.c_void_p)
-        g.a_len = a.size
+    keep = _set_operands(g, (("a", a),))
     nn = max(n, 0) ** 2
     body = max(n, 0) * max(g.out_cols, 0) if op == "spd_inverse_columns" else nn
     out = np.full(body + 2 * DENSE_OP_GUARD, np.nan)
