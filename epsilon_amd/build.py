@@ -16,7 +16,7 @@ OBJ = os.path.join(CSRC, "_build")
 LIB = os.path.join(HERE, "libepsilon_hip.so")
 
 HOST_SOURCES = ["options.cc", "wire.cc", "device.cc", "comm.cc", "linear_map.cc", "sparse.cc", "block.cc", "affine.cc", "prox.cc", "prox_more.cc",
-                "fused_route.cc", "admm.cc", "capi.cc", "capi_test.cc", "capi_bench.cc"]
+                "prox_matrix.cc", "fused_route.cc", "admm.cc", "capi.cc", "capi_test.cc", "capi_bench.cc"]
 # -ffp-contract=off for the elementwise / prox kernels: thresholds and projections must pick
 # the same branch and produce the same bits as a plain IEEE evaluation.
 DEVICE_SOURCES = [("kernels_vec.hip", ["-ffp-contract=off"]),

@@ -1104,7 +1104,7 @@ __global__ __launch_bounds__(kBlock) void GatherColsKernel(T* __restrict__ dst, 
 }
 
 // keep_v = false (matrix-core path only): the rotations are applied to W alone - V is neither read
-// nor written - for callers that rebuild the right factor from W afterwards (prox_more.cc): a
+// nor written - for callers that rebuild the right factor from W afterwards (prox_matrix.cc): a
 // step then streams W once more instead of W and V, 1.2 GB instead of 2.0 GB at n = 1e4.
 template <class T, bool kMfma = std::is_same<T, float>::value>
 int BlockJacobiImpl(const DVec& W, int64_t m, int64_t n, const DVec& V, int max_sweeps, bool warm,

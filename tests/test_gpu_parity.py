@@ -1127,6 +1127,36 @@ def test_robust_pca_problem(solve_mod, dtype, n):
         np.testing.assert_allclose(np.frombuffer(xg[k]), np.frombuffer(xo[k]), err_msg=k, **tol)
 
 
+@pytest.fixture(params=["1", "0"], ids=["partial", "no_partial"])
+def partial_route(request):
+    """EPSILON_HIP_SVD_PARTIAL on / off (the operator reads it when a solve initialises it)."""
+    import os
+    old = os.environ.get("EPSILON_HIP_SVD_PARTIAL")
+    os.environ["EPSILON_HIP_SVD_PARTIAL"] = request.param
+    yield request.param
+    if old is None:
+        os.environ.pop("EPSILON_HIP_SVD_PARTIAL", None)
+    else:
+        os.environ["EPSILON_HIP_SVD_PARTIAL"] = old
+
+
+def test_robust_pca_block_route_warm_starts(solve_mod, dtype, partial_route):
+    """Robust PCA at n = 520, 12 sweeps: the size from which the nuclear-norm prox keeps state
+    across applications on its large-matrix routes - partial route on: the rank of the last
+    success sizes the next block, failures back off; off: the block Jacobi continues from the
+    previous basis (alternating sides in fp32, the right factor in fp64).  Iterate parity with the
+    oracle at the tolerances of test_robust_pca_problem."""
+    prob, info = problems.robust_pca(520, r=2, seed=0)
+    sg, xg, so, xo = solve_both(solve_mod, prob, wire.SolverParams(max_iterations=12))
+    assert sg.num_iterations == so.num_iterations and sg.state == so.state
+    tol = dict(rtol=1e-6, atol=1e-7) if dtype == "f64" else dict(rtol=5e-3, atol=5e-3)
+    for k in xo:
+        g, o = np.frombuffer(xg[k]), np.frombuffer(xo[k])
+        print("%s %s partial=%s: max |gpu - oracle| = %.3e, max |oracle| = %.3e"
+              % (k, dtype, partial_route, np.abs(g - o).max(), np.abs(o).max()))
+        np.testing.assert_allclose(g, o, err_msg=k, **tol)
+
+
 @pytest.mark.parametrize("case", ["noise", "walk", "ties", "steps", "big", "tiny"])
 def test_tv1d_parallel_kernel(solve_mod, dtype, case):
     """Exact parallel TV-1D prox (level-set divide and conquer, kernels_tv3.hip) vs the DP

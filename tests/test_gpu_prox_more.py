@@ -504,7 +504,7 @@ def test_nuclear_norm_polar_route(solve_mod, dtype, case):
     on GEMMs only - polar factor Q of Y by Newton-Schulz, X = Q (H - tau I)_+ with the positive part
     from the matrix sign function, the dominant outliers taken out first by a randomized block -
     and is held to the optimality condition of the prox before it is returned
-    (prox_more.cc: PolarNuclearProx; reference prox/ortho_invariant.cc:36-105).  Against numpy's SVD:
+    (prox_matrix.cc: PolarNuclearProx; reference prox/ortho_invariant.cc:36-105).  Against numpy's SVD:
     the reference's robust-PCA matrix, a pure noise bulk, a tall matrix, and a spectrum with many
     values within a per cent of the threshold (where the sign iteration is NOT converged and must
     not matter)."""
