@@ -9,47 +9,14 @@ import numpy as np
 import pytest
 
 from epsilon_amd import ir, problems, wire
-from epsilon_amd.wire import ProxFunction
 from oracle import epsilon_oracle as orc
+from tests import route_support as rs
 
 pytestmark = pytest.mark.gpu
 
 PATH = (0.5, 0.35, 0.25, 0.18, 0.12)  # fractions of lambda_max of the lambda paths below
-STATUS_FIELDS = ("r_norm", "s_norm", "epsilon_primal", "epsilon_dual")
-
-
-@pytest.fixture(params=["f32", "f64"])
-def dtype(request, solve_mod):
-    solve_mod.set_option("dtype", request.param)
-    yield request.param
-    solve_mod.set_option("dtype", "f32")
-
-
-def status(st):
-    return wire.SolverStatus.FromString(st)
-
-
-def fused_problem(A, b_expr, lam, kind="lasso", qvec=None):
-    """sum_square(A x' - b) + lam * g(x)  s.t.  x' - x = 0 with g a scaled-zone function."""
-    m, n = A.shape
-    x = ir.variable(n, 1, problems.LASSO_COPY)
-    y = ir.variable(n, 1, problems.LASSO_VAR)
-    f0 = ir.prox(ProxFunction.SUM_SQUARE, ir.add(ir.linear_map(ir.dense_matrix(A), x),
-                                                 ir.linear_map(ir.scalar(-1, m), b_expr)), alpha=1.0)
-    if kind == "lasso":
-        f1 = ir.prox(ProxFunction.NORM_1, y, alpha=lam)
-    elif kind == "deadzone":
-        f1 = ir.prox(ProxFunction.SUM_DEADZONE, ir.linear_map(ir.scalar(2.0, n), y), alpha=lam,
-                     scaled_zone_params=wire.ProxScaledZoneParams(m=0.05))
-    elif kind == "hinge":
-        f1 = ir.prox(ProxFunction.SUM_HINGE, y, alpha=lam)
-    else:  # quantile with per-column alpha / beta from data vectors
-        qa, qb = ir.constant(qvec[0]), ir.constant(qvec[1])
-        qd = dict(qa.data)
-        qd.update(qb.data)
-        f1 = ir.prox(ProxFunction.SUM_QUANTILE, y, alpha=lam, data=qd,
-                     scaled_zone_params=wire.ProxScaledZoneParams(alpha_expr=qa.proto, beta_expr=qb.proto))
-    return ir.Problem([f0, f1], [ir.zero(ir.add(x, ir.linear_map(ir.scalar(-1, n), y)))])
+SETUP = ("gemm", "syrk", "spd_inverse")  # what setup_counts counts here: Gram products, explicit inverses
+dtype = rs.dtype_fixture(("f32", "f64"))
 
 
 def lambda_path(m, n, seed, fracs=PATH):
@@ -59,40 +26,15 @@ def lambda_path(m, n, seed, fracs=PATH):
     return probs, A, b
 
 
-def union_data(probs):
-    data = {}
-    for p in probs:
-        data.update(p.expression_data())
-    return data
-
-
 def singles(solve_mod, pbs, params, sb, data):
     return [solve_mod.solve(pb, ps, sb, data) for pb, ps in zip(pbs, params)]
-
-
-def assert_identical(batch, single):
-    assert len(batch) == len(single)
-    for k, ((stb, xb), (sts, xs)) in enumerate(zip(batch, single)):
-        a, s = status(stb), status(sts)
-        assert a.state == s.state and a.num_iterations == s.num_iterations, (k, a, s)
-        for f in STATUS_FIELDS:
-            assert getattr(a.residuals, f) == getattr(s.residuals, f), (k, f)
-        assert sorted(xb) == sorted(xs)
-        for v in xs:
-            assert np.array_equal(np.frombuffer(xb[v]), np.frombuffer(xs[v])), (k, v)
-
-
-def sweeps(st):
-    """sweeps a solve ran: a check at iteration i follows sweep i (0-based)"""
-    s = status(st)
-    return s.num_iterations + 1 if s.state == wire.SolverStatus.OPTIMAL else s.num_iterations
 
 
 def max_iterations_splitting(solve_mod, pbs, data, **kw):
     """A max_iterations that some instances reach OPTIMAL within (at different sweeps) and the
     slowest does not."""
     sb = wire.SolverParams(max_iterations=3000, **kw).SerializeToString()
-    its = sorted(status(st).num_iterations for st, _ in singles(solve_mod, pbs, [[]] * len(pbs), sb, data))
+    its = sorted(rs.status(st).num_iterations for st, _ in singles(solve_mod, pbs, [[]] * len(pbs), sb, data))
     assert its[-1] > its[0], its
     return its[-1] - 1
 
@@ -100,39 +42,30 @@ def max_iterations_splitting(solve_mod, pbs, data, **kw):
 @pytest.mark.parametrize("shape", [(200, 500), (1024, 3000)])
 def test_lambda_path_bit_identical(solve_mod, dtype, shape):
     probs, A, b = lambda_path(*shape, seed=3)
-    pbs, data = [p.SerializeToString() for p in probs], union_data(probs)
+    pbs, data = [p.SerializeToString() for p in probs], rs.union_data(probs)
     tight = dict(epoch_iterations=1, rel_tol=1e-4, abs_tol=1e-6)  # a check after every sweep
     max_it = max_iterations_splitting(solve_mod, pbs, data, **tight)
     sb = wire.SolverParams(max_iterations=max_it, **tight).SerializeToString()
     single = singles(solve_mod, pbs, [[]] * len(pbs), sb, data)
-    states = [status(st).state for st, _ in single]
+    states = [rs.status(st).state for st, _ in single]
     assert wire.SolverStatus.MAX_ITERATIONS_REACHED in states
-    assert len({status(st).num_iterations for st, _ in single}) >= 3  # stops at different checks
+    assert len({rs.status(st).num_iterations for st, _ in single}) >= 3  # stops at different checks
     batch = solve_mod.solve_batch(pbs, None, sb, data)
-    assert_identical(batch, single)
+    rs.assert_identical(batch, single)
 
 
 def test_lambda_path_matches_oracle_f64(solve_mod):
-    solve_mod.set_option("dtype", "f64")
-    try:
+    with rs.options(solve_mod, dtype="f64"):
         probs, A, b = lambda_path(200, 500, seed=4, fracs=PATH[:4])
-        pbs, data = [p.SerializeToString() for p in probs], union_data(probs)
+        pbs, data = [p.SerializeToString() for p in probs], rs.union_data(probs)
         sb = wire.SolverParams(max_iterations=400).SerializeToString()
         batch = solve_mod.solve_batch(pbs, None, sb, data)
-    finally:
-        solve_mod.set_option("dtype", "f32")
     for pb, (stb, xb) in zip(pbs, batch):
         sto, xo = orc.solve(pb, [], sb, data)
-        a, o = status(stb), status(sto)
+        a, o = rs.status(stb), rs.status(sto)
         assert a.state == o.state and a.num_iterations == o.num_iterations
         for v in xo:
             np.testing.assert_allclose(np.frombuffer(xb[v]), np.frombuffer(xo[v]), rtol=1e-7, atol=1e-9)
-
-
-def bind_b(b):
-    data = {}
-    c = ir.store(np.asarray(b, dtype=np.float64).reshape(-1, 1), data)
-    return [("param:b", c.SerializeToString())], data
 
 
 def test_parameters_and_scaled_zone_kinds(solve_mod, dtype):
@@ -145,46 +78,24 @@ def test_parameters_and_scaled_zone_kinds(solve_mod, dtype):
     # per-instance bindings of param:b, with lambda varying too
     for i, (bi, f) in enumerate(zip(bs, (0.3, 0.3, 0.2))):
         probs.append(problems.lasso_ir(ir.dense_matrix(A), ir.parameter(m, 1, "param:b"), f * lmax, n))
-        p, d = bind_b(bi)
+        p, d = rs.bind_b(bi)
         params.append(p)
         data.update(d)
     qvec = (0.2 + rng.rand(n), 0.2 + rng.rand(n))
     for kind in ("deadzone", "hinge", "quantile", "quantile"):
-        probs.append(fused_problem(A, ir.constant(b), (0.3 if len(probs) % 2 else 0.2) * lmax, kind, qvec))
+        lam = (0.3 if len(probs) % 2 else 0.2) * lmax
+        probs.append(rs.fused_problem(ir.dense_matrix(A), m, n, ir.constant(b), lam, kind, qvec))
         params.append([])
-    data.update(union_data(probs))
+    data.update(rs.union_data(probs))
     pbs = [p.SerializeToString() for p in probs]
     sb = wire.SolverParams(max_iterations=300).SerializeToString()
     single = singles(solve_mod, pbs, params, sb, data)
     batch = solve_mod.solve_batch(pbs, params, sb, data)
-    assert_identical(batch, single)
-
-
-def tags_of(solve_mod, fn):
-    solve_mod.profile_reset()
-    solve_mod.profile_enable(True)
-    try:
-        out = fn()
-        return out, solve_mod.profile_dump()
-    finally:
-        solve_mod.profile_enable(False)
-
-
-def setup_counts(tags):
-    """Gram products and explicit inverses of an Init"""
-    return {t: c for t, (c, _) in tags.items() if "gemm" in t or "syrk" in t or "spd_inverse" in t}
-
-
-def base_counts(tags):
-    """launch counts by tag name (the profile appends the shape: "name:AxB")"""
-    out = {}
-    for t, (c, _) in tags.items():
-        out[t.split(":")[0]] = out.get(t.split(":")[0], 0) + c
-    return out
+    rs.assert_identical(batch, single)
 
 
 def expected_passes(results, width):
-    sw = [sweeps(st) for st, _ in results]
+    sw = [rs.sweeps(st) for st, _ in results]
     return sum(math.ceil(sum(1 for s in sw if s > i) / width) for i in range(max(sw)))
 
 
@@ -193,22 +104,20 @@ def expected_passes(results, width):
 def test_shared_setup_and_pass_counts(solve_mod, dt, shape, k, width):
     """Widths per (m, dtype): DESIGN.md 3.6 (f32 and f64 at m = 1024 run two 16-byte chunks per
     thread, 8 instances per pass)."""
-    solve_mod.set_option("dtype", dt)
-    try:
+    with rs.options(solve_mod, dtype=dt):
         fracs = [0.5 * 0.9 ** i for i in range(k)]
         probs, A, b = lambda_path(*shape, seed=5, fracs=fracs)
-        pbs, data = [p.SerializeToString() for p in probs], union_data(probs)
+        pbs, data = [p.SerializeToString() for p in probs], rs.union_data(probs)
         sb = wire.SolverParams(max_iterations=250).SerializeToString()
-        one, tags1 = tags_of(solve_mod, lambda: solve_mod.solve(pbs[0], [], sb, data))
-        batch, tagsb = tags_of(solve_mod, lambda: solve_mod.solve_batch(pbs, None, sb, data))
+        one, tags1 = rs.profiled(solve_mod, lambda: solve_mod.solve(pbs[0], [], sb, data))
+        batch, tagsb = rs.profiled(solve_mod, lambda: solve_mod.solve_batch(pbs, None, sb, data))
         single = singles(solve_mod, pbs, [[]] * k, sb, data)
-    finally:
-        solve_mod.set_option("dtype", "f32")
-    assert_identical(batch, single)
-    assert setup_counts(tags1) and setup_counts(tagsb) == setup_counts(tags1), (tags1, tagsb)
-    c1, cb = base_counts(tags1), base_counts(tagsb)
+    rs.assert_identical(batch, single)
+    s1, sb_ = rs.setup_counts(tags1, SETUP), rs.setup_counts(tagsb, SETUP)
+    assert s1 and sb_ == s1, (tags1, tagsb)
+    c1, cb = rs.base_counts(tags1), rs.base_counts(tagsb)
     assert "lasso_fused" in c1 and "lasso_fused" not in cb, sorted(tagsb)
-    assert cb["batch_fused_pass"] == expected_passes(batch, width), (cb, [sweeps(s) for s, _ in batch])
+    assert cb["batch_fused_pass"] == expected_passes(batch, width), (cb, [rs.sweeps(s) for s, _ in batch])
     assert cb["batch_symv_packed"] > 0 and cb["batch_reduce_partials"] == cb["batch_fused_pass"] // math.ceil(k / width) or k > width
 
 
@@ -223,23 +132,23 @@ def test_fallbacks_are_exact(solve_mod, dtype):
     hinge, _ = problems.hinge_l1(80, 40, seed=1)
     logreg, _ = problems.logreg_l1(80, 40, seed=2)
     probs = [fused[0], sparse, hinge, fused[1], other_A[0], logreg]
-    pbs, data = [p.SerializeToString() for p in probs], union_data(probs)
+    pbs, data = [p.SerializeToString() for p in probs], rs.union_data(probs)
     sb = wire.SolverParams(max_iterations=200).SerializeToString()
-    assert_identical(solve_mod.solve_batch(pbs, None, sb, data), singles(solve_mod, pbs, [[]] * 6, sb, data))
+    rs.assert_identical(solve_mod.solve_batch(pbs, None, sb, data), singles(solve_mod, pbs, [[]] * 6, sb, data))
     # the two-block driver: solved one by one, the same bits
     sb2 = wire.SolverParams(max_iterations=200, solver=1).SerializeToString()
     pbs2 = [p.SerializeToString() for p in fused]
-    assert_identical(solve_mod.solve_batch(pbs2, None, sb2, data), singles(solve_mod, pbs2, [[]] * 2, sb2, data))
+    rs.assert_identical(solve_mod.solve_batch(pbs2, None, sb2, data), singles(solve_mod, pbs2, [[]] * 2, sb2, data))
 
 
 def test_errors_leave_the_library_usable(solve_mod):
     probs, A, b = lambda_path(100, 300, seed=1, fracs=(0.5, 0.3))
-    pbs, data = [p.SerializeToString() for p in probs], union_data(probs)
+    pbs, data = [p.SerializeToString() for p in probs], rs.union_data(probs)
     sb = wire.SolverParams(max_iterations=100).SerializeToString()
     good = solve_mod.solve_batch(pbs, None, sb, data)
 
     def check_ok():
-        assert_identical(solve_mod.solve_batch(pbs, None, sb, data), good)
+        rs.assert_identical(solve_mod.solve_batch(pbs, None, sb, data), good)
 
     with pytest.raises(solve_mod.error, match="count is 0"):
         solve_mod.solve_batch([], None, sb, data)
@@ -258,12 +167,12 @@ def test_errors_leave_the_library_usable(solve_mod):
 
 def test_full_size_lambda_path(solve_mod):
     """config 2 (10^4 x 5 * 10^4, fp32), a lambda path of 4."""
-    solve_mod.set_option("dtype", "f32")
     probs, A, b = lambda_path(10000, 50000, seed=0, fracs=(0.5, 0.35, 0.25, 0.18))
     del A, b
-    pbs, data = [p.SerializeToString() for p in probs], union_data(probs)
+    pbs, data = [p.SerializeToString() for p in probs], rs.union_data(probs)
     sb = wire.SolverParams().SerializeToString()
-    batch = solve_mod.solve_batch(pbs, None, sb, data)
-    single = singles(solve_mod, pbs, [[]] * 4, sb, data)
-    assert_identical(batch, single)
-    assert all(status(st).state == wire.SolverStatus.OPTIMAL for st, _ in batch)
+    with rs.options(solve_mod, dtype="f32"):
+        batch = solve_mod.solve_batch(pbs, None, sb, data)
+        single = singles(solve_mod, pbs, [[]] * 4, sb, data)
+    rs.assert_identical(batch, single)
+    assert all(rs.status(st).state == wire.SolverStatus.OPTIMAL for st, _ in batch)

@@ -22,12 +22,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from epsilon_amd import _solve, ir, problems, wire  # noqa: E402
-from epsilon_amd.wire import ProxFunction  # noqa: E402
 from oracle import epsilon_oracle as orc  # noqa: E402
+from tests import route_support as rs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-STATUS_FIELDS = ("r_norm", "s_norm", "epsilon_primal", "epsilon_dual")
 RESIDUAL_NORMS = ("r_norm", "s_norm")
 SMALL = (256, 768)  # the oracle is the reference here
 FIXED = wire.SolverParams(max_iterations=100, ignore_stopping_criteria=True).SerializeToString()
@@ -35,17 +34,6 @@ FIXED = wire.SolverParams(max_iterations=100, ignore_stopping_criteria=True).Ser
 ORACLE_FIXED = wire.SolverParams(max_iterations=100, abs_tol=0.0, rel_tol=0.0).SerializeToString()
 DEFAULT = wire.SolverParams().SerializeToString()
 EPOCH = wire.SolverParams().epoch_iterations
-
-
-def status(st):
-    return wire.SolverStatus.FromString(st)
-
-
-def union_data(probs):
-    data = {}
-    for p in probs:
-        data.update(p.expression_data())
-    return data
 
 
 def fracs_of(k):
@@ -62,12 +50,12 @@ def lasso_path(m, n, seed, fracs):
     """(serialized problems, data) of a lambda path on regression_data(m, n, seed)"""
     A, b, lmax, Aexpr, bexpr = regression(m, n, seed)
     probs = [problems.lasso_ir(Aexpr, bexpr, f * lmax, n) for f in fracs]
-    return [p.SerializeToString() for p in probs], union_data(probs)
+    return [p.SerializeToString() for p in probs], rs.union_data(probs)
 
 
 def f32_singles(pbs, params, sb, data):
-    _solve.set_option("dtype", "f32")
-    return [_solve.solve(pb, ps, sb, data) for pb, ps in zip(pbs, params)]
+    with rs.options(_solve, dtype="f32"):
+        return [_solve.solve(pb, ps, sb, data) for pb, ps in zip(pbs, params)]
 
 
 def f64_reference(shape, pbs, params, sb, data):
@@ -75,26 +63,19 @@ def f64_reference(shape, pbs, params, sb, data):
     if tuple(shape) == SMALL:
         sb = ORACLE_FIXED if sb == FIXED else sb
         return [orc.solve(pb, ps, sb, data) for pb, ps in zip(pbs, params)]
-    _solve.set_option("dtype", "f64")
-    try:
+    with rs.options(_solve, dtype="f64"):
         return [_solve.solve(pb, ps, sb, data) for pb, ps in zip(pbs, params)]
-    finally:
-        _solve.set_option("dtype", "f32")
 
 
 def wide_batch(pbs, params, sb, data):
-    _solve.set_option("dtype", "f32")
-    return _solve.solve_batch(pbs, params, sb, data, wide=True)
+    with rs.options(_solve, dtype="f32"):
+        return _solve.solve_batch(pbs, params, sb, data, wide=True)
 
 
 def tags_of(fn):
-    _solve.profile_reset()
-    _solve.profile_enable(True)
-    try:
-        out = fn()
-        return out, {t.split(":")[0] for t in _solve.profile_dump()}
-    finally:
-        _solve.profile_enable(False)
+    """(fn(), the set of tag names it launched)"""
+    out, tags = rs.profiled(_solve, fn)
+    return out, set(rs.base_counts(tags))
 
 
 def assert_values_within_bound(label, wide, single, ref, residuals=True):
@@ -117,7 +98,7 @@ def assert_values_within_bound(label, wide, single, ref, residuals=True):
             if not ew <= bound:
                 failures.append((k, v, ew, es, scale))
         if residuals:
-            a, s, o = status(stw), status(sts), status(str_)
+            a, s, o = rs.status(stw), rs.status(sts), rs.status(str_)
             assert a.num_iterations == s.num_iterations == o.num_iterations == 100
             for f in RESIDUAL_NORMS:
                 gw, gs, go = (getattr(z.residuals, f) for z in (a, s, o))
@@ -127,23 +108,12 @@ def assert_values_within_bound(label, wide, single, ref, residuals=True):
     assert not failures, failures
 
 
-def assert_same_bytes(a, b, what):
-    (sta, xa), (stb, xb) = a, b
-    p, q = status(sta), status(stb)
-    assert p.state == q.state and p.num_iterations == q.num_iterations, (what, p, q)
-    for f in STATUS_FIELDS:
-        assert getattr(p.residuals, f) == getattr(q.residuals, f), (what, f)
-    assert sorted(xa) == sorted(xb)
-    for v in xa:
-        assert xa[v] == xb[v], (what, v)
-
-
 # ---- 1. route taken ------------------------------------------------------------------------------
 def test_route_taken(solve_mod):
     pbs, data = lasso_path(*SMALL, 21, fracs_of(24))
-    solve_mod.set_option("dtype", "f32")
-    _, on = tags_of(lambda: solve_mod.solve_batch(pbs, None, FIXED, data, wide=True))
-    _, off = tags_of(lambda: solve_mod.solve_batch(pbs, None, FIXED, data, wide=False))
+    with rs.options(solve_mod, dtype="f32"):
+        _, on = tags_of(lambda: solve_mod.solve_batch(pbs, None, FIXED, data, wide=True))
+        _, off = tags_of(lambda: solve_mod.solve_batch(pbs, None, FIXED, data, wide=False))
     assert {"wide_back", "wide_forward", "wide_reduce"} <= on and "batch_fused_pass" not in on, sorted(on)
     assert "batch_fused_pass" in off and not {"wide_back", "wide_forward", "wide_reduce"} & off, sorted(off)
 
@@ -158,13 +128,13 @@ def test_fixed_sweeps_within_bound(solve_mod, shape, seed, k):
     wide = wide_batch(pbs, None, FIXED, data)
     single = f32_singles(pbs, none, FIXED, data)
     ref = f64_reference(shape, pbs, none, FIXED, data)
-    assert all(status(st).num_iterations == 100 for st, _ in wide)
+    assert all(rs.status(st).num_iterations == 100 for st, _ in wide)
     assert_values_within_bound("fixed %dx%d" % shape, wide, single, ref)
 
 
 # ---- 3. stopping ---------------------------------------------------------------------------------
 def ratio(st):
-    r = status(st).residuals
+    r = rs.status(st).residuals
     return max(r.r_norm / r.epsilon_primal, r.s_norm / r.epsilon_dual)
 
 
@@ -175,7 +145,7 @@ def reference_stops(shape, pbs, data):
     full = f64_reference(shape, pbs, [[]] * k, DEFAULT, data)
     out = []
     for pb, (st, _) in zip(pbs, full):
-        s = status(st)
+        s = rs.status(st)
         assert s.state == wire.SolverStatus.OPTIMAL
         stop = s.num_iterations
         close = ratio(st) > 0.95
@@ -184,7 +154,7 @@ def reference_stops(shape, pbs, data):
             # residuals of exactly that iterate
             sb = wire.SolverParams(max_iterations=stop - EPOCH + 1).SerializeToString()
             (stp, _), = f64_reference(shape, [pb], [[]], sb, data)
-            assert status(stp).state == wire.SolverStatus.MAX_ITERATIONS_REACHED
+            assert rs.status(stp).state == wire.SolverStatus.MAX_ITERATIONS_REACHED
             close = close or ratio(stp) < 1.05
         out.append((stop, close))
     return out
@@ -199,7 +169,7 @@ def test_stopping_matches_reference(solve_mod, shape, seed, k):
     assert nclose <= k // 4, "inconclusive: %d of %d instances within rounding of a threshold" % (nclose, k)
     assert len({s for s, _ in stops}) >= 2  # members leave their panel at different checks
     wide = wide_batch(pbs, None, DEFAULT, data)
-    got = [status(st) for st, _ in wide]
+    got = [rs.status(st) for st, _ in wide]
     print("wide stops", [s.num_iterations for s in got])
     assert all(s.state == wire.SolverStatus.OPTIMAL for s in got)
     for i, (s, (stop, close)) in enumerate(zip(got, stops)):
@@ -211,7 +181,7 @@ def test_stopping_matches_reference(solve_mod, shape, seed, k):
     slowest = max(s for s, _ in stops)
     cap = slowest - EPOCH + 1
     sb = wire.SolverParams(max_iterations=cap).SerializeToString()
-    capped = [status(st) for st, _ in wide_batch(pbs, None, sb, data)]
+    capped = [rs.status(st) for st, _ in wide_batch(pbs, None, sb, data)]
     states = {s.state for s in capped}
     assert states == {wire.SolverStatus.OPTIMAL, wire.SolverStatus.MAX_ITERATIONS_REACHED}, states
     for i, (s, (stop, close)) in enumerate(zip(capped, stops)):
@@ -224,36 +194,10 @@ def test_stopping_matches_reference(solve_mod, shape, seed, k):
 
 
 # ---- 4. what may differ per instance ---------------------------------------------------------------
-def fused_problem(Aexpr, m, n, b_expr, lam, kind, qvec=None):
-    """sum_square(A x' - b) + lam * g(x)  s.t.  x' - x = 0 with g a scaled-zone function."""
-    x = ir.variable(n, 1, problems.LASSO_COPY)
-    y = ir.variable(n, 1, problems.LASSO_VAR)
-    f0 = ir.prox(ProxFunction.SUM_SQUARE, ir.add(ir.linear_map(Aexpr, x),
-                                                 ir.linear_map(ir.scalar(-1, m), b_expr)), alpha=1.0)
-    if kind == "deadzone":
-        f1 = ir.prox(ProxFunction.SUM_DEADZONE, ir.linear_map(ir.scalar(2.0, n), y), alpha=lam,
-                     scaled_zone_params=wire.ProxScaledZoneParams(m=0.05))
-    elif kind == "hinge":
-        f1 = ir.prox(ProxFunction.SUM_HINGE, y, alpha=lam)
-    else:  # quantile with per-column alpha / beta from data vectors
-        qa, qb = ir.constant(qvec[0]), ir.constant(qvec[1])
-        qd = dict(qa.data)
-        qd.update(qb.data)
-        f1 = ir.prox(ProxFunction.SUM_QUANTILE, y, alpha=lam, data=qd,
-                     scaled_zone_params=wire.ProxScaledZoneParams(alpha_expr=qa.proto, beta_expr=qb.proto))
-    return ir.Problem([f0, f1], [ir.zero(ir.add(x, ir.linear_map(ir.scalar(-1, n), y)))])
-
-
-def bind_b(b):
-    data = {}
-    c = ir.store(np.asarray(b, dtype=np.float64).reshape(-1, 1), data)
-    return [("param:b", c.SerializeToString())], data
-
-
 def check_wide_group(label, shape, probs, params, data):
     pbs = [p.SerializeToString() for p in probs]
     data = dict(data)
-    data.update(union_data(probs))
+    data.update(rs.union_data(probs))
     wide, tags = tags_of(lambda: wide_batch(pbs, params, FIXED, data))
     assert "wide_back" in tags and not {"batch_fused_pass", "lasso_fused"} & tags, sorted(tags)
     single = f32_singles(pbs, params, FIXED, data)
@@ -269,7 +213,7 @@ def test_rhs_bindings_with_different_lambda(solve_mod):
     probs, params, data = [], [], {}
     for i, f in enumerate(fracs_of(18)):
         probs.append(problems.lasso_ir(Aexpr, ir.parameter(m, 1, "param:b"), f * lmax, n))
-        p, d = bind_b(bs[i % 3])
+        p, d = rs.bind_b(bs[i % 3])
         params.append(p)
         data.update(d)
     check_wide_group("param:b", (m, n), probs, params, data)
@@ -283,7 +227,7 @@ def test_scaled_zone_kinds(solve_mod, kind):
     probs = []
     for f in fracs_of(16):
         qvec = (0.2 + rng.rand(n), 0.2 + rng.rand(n))  # per-column alpha / beta, per instance
-        probs.append(fused_problem(Aexpr, m, n, bexpr, f * lmax, kind, qvec))
+        probs.append(rs.fused_problem(Aexpr, m, n, bexpr, f * lmax, kind, qvec))
     check_wide_group(kind, (m, n), probs, [[]] * 16, {})
 
 
@@ -293,16 +237,16 @@ def test_bits_do_not_depend_on_run_partners_or_position(solve_mod, shape, seed):
     path = fracs_of(24)
     pbs, data = lasso_path(*shape, seed, path)
     first = wide_batch(pbs, None, DEFAULT, data)
-    assert len({status(st).num_iterations for st, _ in first}) >= 2
+    assert len({rs.status(st).num_iterations for st, _ in first}) >= 2
     again = wide_batch(pbs, None, DEFAULT, data)
     for i in range(24):
-        assert_same_bytes(again[i], first[i], ("again", i))
+        rs.assert_same_bytes_and_residuals(again[i], first[i], ("again", i))
     rev = wide_batch(pbs[::-1], None, DEFAULT, data)
     for i in range(24):
-        assert_same_bytes(rev[23 - i], first[i], ("reversed", i))
+        rs.assert_same_bytes_and_residuals(rev[23 - i], first[i], ("reversed", i))
     head = wide_batch(pbs[:17], None, DEFAULT, data)
     for i in range(17):
-        assert_same_bytes(head[i], first[i], ("first 17", i))
+        rs.assert_same_bytes_and_residuals(head[i], first[i], ("first 17", i))
     # 70 members, two panels: the path's first half in panel 0, its second half across the boundary
     others = [float(f) for f in np.geomspace(0.55, 0.05, 46)]
     opbs, odata = lasso_path(*shape, seed, others)
@@ -314,38 +258,34 @@ def test_bits_do_not_depend_on_run_partners_or_position(solve_mod, shape, seed):
     assert "wide_back" in tags and "batch_fused_pass" not in tags
     for i, w in enumerate(where):
         assert big[w] is pbs[i]
-        assert_same_bytes(out[w], first[i], ("of 70", i))
+        rs.assert_same_bytes_and_residuals(out[w], first[i], ("of 70", i))
 
 
 # ---- 6. nothing else moves -------------------------------------------------------------------------
 def assert_identical_to_single(batch, single):
     assert len(batch) == len(single)
     for k, (a, b) in enumerate(zip(batch, single)):
-        assert_same_bytes(a, b, k)
+        rs.assert_same_bytes_and_residuals(a, b, k)
 
 
 def test_f64_batch_keeps_its_route(solve_mod):
     pbs, data = lasso_path(*SMALL, 21, fracs_of(24))
     sb = wire.SolverParams(max_iterations=300).SerializeToString()
-    solve_mod.set_option("dtype", "f64")
-    try:
+    with rs.options(solve_mod, dtype="f64"):
         batch, tags = tags_of(lambda: solve_mod.solve_batch(pbs, None, sb, data, wide=True))
         single = [solve_mod.solve(pb, [], sb, data) for pb in pbs]
-    finally:
-        solve_mod.set_option("dtype", "f32")
     assert "batch_fused_pass" in tags and "wide_back" not in tags, sorted(tags)
     assert_identical_to_single(batch, single)
 
 
 def test_two_block_batch_and_small_group_keep_their_routes(solve_mod):
     pbs, data = lasso_path(*SMALL, 21, fracs_of(24))
-    solve_mod.set_option("dtype", "f32")
     sb2 = wire.SolverParams(max_iterations=200, solver=1).SerializeToString()
-    batch, tags = tags_of(lambda: solve_mod.solve_batch(pbs, None, sb2, data, wide=True))
+    batch, tags = tags_of(lambda: wide_batch(pbs, None, sb2, data))
     assert "wide_back" not in tags, sorted(tags)
     assert_identical_to_single(batch, f32_singles(pbs, [[]] * 24, sb2, data))
     sb = wire.SolverParams(max_iterations=300).SerializeToString()
-    batch, tags = tags_of(lambda: solve_mod.solve_batch(pbs[:3], None, sb, data, wide=True))
+    batch, tags = tags_of(lambda: wide_batch(pbs[:3], None, sb, data))
     assert "batch_fused_pass" in tags and "wide_back" not in tags, sorted(tags)
     assert_identical_to_single(batch, f32_singles(pbs[:3], [[]] * 3, sb, data))
 
@@ -368,13 +308,13 @@ def test_mixed_batch(solve_mod):
     wide_at = list(range(8)) + list(range(10, 18))
     data = dict(wdata)
     data.update(odata)
-    data.update(union_data(extra))
+    data.update(rs.union_data(extra))
     batch, tags = tags_of(lambda: wide_batch(pbs, None, FIXED, data))
     assert {"wide_back", "batch_fused_pass"} <= tags, sorted(tags)
     single = f32_singles(pbs, [[]] * len(pbs), FIXED, data)
     for i in range(len(pbs)):
         if i not in wide_at:
-            assert_same_bytes(batch[i], single[i], i)
+            rs.assert_same_bytes_and_residuals(batch[i], single[i], i)
     wp = [pbs[i] for i in wide_at]
     ref = f64_reference(SMALL, wp, [[]] * 16, FIXED, data)
     assert_values_within_bound("mixed", [batch[i] for i in wide_at], [single[i] for i in wide_at], ref)
@@ -386,21 +326,20 @@ def test_full_size_path_of_32(solve_mod):
     atol = 2e-4 * scale of its single whitened solve, the tolerance of the full-size checks
     (test_gpu_full_size.py, test_gpu_fused_whiten.py)."""
     import bench
-    solve_mod.set_option("dtype", "f32")
     At, b, lam = bench.make_instance(10000, 50000, torch.device("cuda", 0))
     try:
         lmax = 2.0 * lam  # make_instance returns 0.5 lambda_max
         probs = [bench.build_problem(At, b, f * lmax) for f in fracs_of(32)]
-        pbs, data = [p.SerializeToString() for p in probs], union_data(probs)
+        pbs, data = [p.SerializeToString() for p in probs], rs.union_data(probs)
         sb = wire.SolverParams(max_iterations=30, ignore_stopping_criteria=True).SerializeToString()
-        wide, tags = tags_of(lambda: solve_mod.solve_batch(pbs, None, sb, data, wide=True))
-        single = [solve_mod.solve(pb, [], sb, data) for pb in pbs]
+        wide, tags = tags_of(lambda: wide_batch(pbs, None, sb, data))
+        single = f32_singles(pbs, [[]] * 32, sb, data)
     finally:
         del At
         torch.cuda.empty_cache()
     assert "wide_back" in tags and "batch_fused_pass" not in tags, sorted(tags)
     for k, ((stw, xw), (sts, xs)) in enumerate(zip(wide, single)):
-        assert status(stw).num_iterations == status(sts).num_iterations == 30
+        assert rs.status(stw).num_iterations == rs.status(sts).num_iterations == 30
         for v in xs:
             s = np.frombuffer(xs[v])
             scale = np.abs(s).max()

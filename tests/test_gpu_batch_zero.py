@@ -17,115 +17,13 @@ import pytest
 
 from epsilon_amd import ir, problems, wire
 from oracle import epsilon_oracle as orc
+from tests import route_support as rs
 
 pytestmark = pytest.mark.gpu
 
-FRACS = (0.5, 0.2, 0.1, 0.05, 0.02)  # of the generators' own lambda scale (their default: 0.1)
-DEADZONE_FRACS = (0.5, 0.3, 0.15)
-STATUS_FIELDS = ("r_norm", "s_norm", "epsilon_primal", "epsilon_dual")
 FIXED = dict(abs_tol=0.0, rel_tol=0.0)
-
-
-def status(st):
-    return wire.SolverStatus.FromString(st)
-
-
-def sweeps(st):
-    s = status(st)
-    return s.num_iterations + 1 if s.state == wire.SolverStatus.OPTIMAL else s.num_iterations
-
-
-def union_data(probs):
-    data = {}
-    for p in probs:
-        data.update(p.expression_data())
-    return data
-
-
-def assert_identical(batch, single):
-    assert len(batch) == len(single)
-    for k, ((stb, xb), (sts, xs)) in enumerate(zip(batch, single)):
-        a, s = status(stb), status(sts)
-        assert a.state == s.state and a.num_iterations == s.num_iterations, (k, a, s)
-        for f in STATUS_FIELDS:
-            assert getattr(a.residuals, f) == getattr(s.residuals, f), (k, f)
-        assert sorted(xb) == sorted(xs)
-        for v in xs:
-            assert np.array_equal(np.frombuffer(xb[v]), np.frombuffer(xs[v])), (k, v)
-
-
-def tags_of(solve_mod, fn):
-    solve_mod.profile_reset()
-    solve_mod.profile_enable(True)
-    try:
-        out = fn()
-        return out, solve_mod.profile_dump()
-    finally:
-        solve_mod.profile_enable(False)
-
-
-def base_counts(tags):
-    """launch counts by tag name (the profile appends the shape: "name:AxB")"""
-    out = {}
-    for t, (c, _) in tags.items():
-        out[t.split(":")[0]] = out.get(t.split(":")[0], 0) + c
-    return out
-
-
-def setup_counts(tags):
-    """Gram products, factorisations / explicit inverses and packed copies of an Init"""
-    return {t: c for t, (c, _) in tags.items()
-            if any(w in t for w in ("gemm", "syrk", "spd_inverse", "pack_inverse"))}
-
-
-_scale = {}
-
-
-def lam_scale(kind, m, n):
-    """what the generator multiplies by 0.1 for its default lambda"""
-    if (kind, m, n) not in _scale:
-        C = getattr(problems, kind)(m, n)[1]["C"]
-        _scale[kind, m, n] = (np.abs(C.sum(axis=0)).max() if kind == "hinge_l1" else
-                              np.abs(C.T.dot(np.full(m, 0.5))).max())
-    return _scale[kind, m, n]
-
-
-_members = {}
-
-
-def members(kind, shape, count=None):
-    """a path of one kind on one matrix (seed 0); `count`: that many members, lambda falling by 0.8
-    from half the scale"""
-    key = (kind, shape, count)
-    if key not in _members:
-        m, n = shape
-        if kind == "deadzone":
-            fr = DEADZONE_FRACS if count is None else [0.5 * 0.8 ** i for i in range(count)]
-            _members[key] = [problems.deadzone_l1(m, n, frac=f)[0] for f in fr]
-        elif kind == "bp":
-            A, b = [problems.basis_pursuit(m, n)[1][k] for k in ("A", "b")]
-            rng = np.random.RandomState(11)
-            bs = [b] + [A.dot(rng.randn(n) * (rng.rand(n) < 0.2)) for _ in range((count or 4) - 1)]
-            _members[key] = [problems.basis_pursuit(m, n, b=bi)[0] for bi in bs]
-        else:
-            gen = "hinge_l1" if kind == "hinge" else "logreg_l1"
-            fr = FRACS if count is None else [0.5 * 0.8 ** i for i in range(count)]
-            _members[key] = [getattr(problems, gen)(m, n, lam=f * lam_scale(gen, m, n))[0] for f in fr]
-    return _members[key]
-
-
-def run_both(solve_mod, probs, dtype, **params):
-    """(batch, its tags, singles, the first single's tags)"""
-    pbs, data = [p.SerializeToString() for p in probs], union_data(probs)
-    sb = wire.SolverParams(**params).SerializeToString()
-    solve_mod.set_option("dtype", dtype)
-    try:
-        batch, tagsb = tags_of(solve_mod, lambda: solve_mod.solve_batch(pbs, None, sb, data))
-        first, tags1 = tags_of(solve_mod, lambda: solve_mod.solve(pbs[0], [], sb, data))
-        single = [first] + [solve_mod.solve(pb, [], sb, data) for pb in pbs[1:]]
-    finally:
-        solve_mod.set_option("dtype", "f32")
-    return batch, tagsb, single, tags1
+SETUP = ("gemm", "syrk", "spd_inverse", "pack_inverse")  # what setup_counts counts here
+ON = {}  # options of a call here beside "dtype": none, the group is the library's default
 
 
 # ---- 1. lambda paths, members stopping at different checks ---------------------------------------
@@ -137,25 +35,25 @@ def test_paths_are_bit_identical_with_mixed_stopping(solve_mod, kind, shape, dty
     130 / 60, logreg 430 / 120 / 60 / 40 / 80, deadzone 470 / 530 / 380: under the cap members stop
     at distinct checks and (hinge, logreg) some reach it."""
     max_it = 500 if kind == "deadzone" else 300
-    batch, tagsb, single, _ = run_both(solve_mod, members(kind, shape), dtype, max_iterations=max_it)
-    st = [status(s) for s, _ in single]
+    batch, tagsb, single, _ = rs.run_both(solve_mod, rs.members(kind, shape), dtype, ON, max_iterations=max_it)
+    st = [rs.status(s) for s, _ in single]
     print(kind, shape, dtype, [(s.state, s.num_iterations) for s in st])
     assert len({s.num_iterations for s in st}) >= 2
     if kind != "deadzone":
         assert wire.SolverStatus.MAX_ITERATIONS_REACHED in [s.state for s in st]
-    cb = base_counts(tagsb)
+    cb = rs.base_counts(tagsb)
     assert cb.get("batch_zero_pass", 0) > 0 and cb.get("batch_zero_rows", 0) > 0 and "zero_fused" not in cb, sorted(cb)
-    assert_identical(batch, single)
+    rs.assert_identical(batch, single)
 
 
 # ---- 2. basis pursuit, several right-hand sides ---------------------------------------------------
 @pytest.mark.parametrize("dtype", ["f32", "f64"])
 def test_basis_pursuit_with_several_right_hand_sides(solve_mod, dtype):
-    batch, tagsb, single, _ = run_both(solve_mod, members("bp", (256, 601)), dtype, max_iterations=200)
-    cb = base_counts(tagsb)
+    batch, tagsb, single, _ = rs.run_both(solve_mod, rs.members("bp", (256, 601)), dtype, ON, max_iterations=200)
+    cb = rs.base_counts(tagsb)
     assert cb.get("batch_zero_pass", 0) > 0 and cb.get("batch_reduce_partials", 0) > 0, sorted(cb)
     assert "batch_zero_rows" not in cb and "zero_fused" not in cb, sorted(cb)
-    assert_identical(batch, single)
+    rs.assert_identical(batch, single)
 
 
 # ---- 3. launch counts and the shared setup --------------------------------------------------------
@@ -165,63 +63,51 @@ def test_launch_counts_and_shared_setup(solve_mod, dt, kind, k, width):
     """Widths of the ZERO chain per (chunks per thread, dtype): DESIGN.md 3.6 (m = 1028 is two
     16-byte chunks per thread in f32, width 8, and three, run as four, in f64, width 6)."""
     shape, n_sweeps = (1028, 2051), 60
-    batch, tagsb, single, tags1 = run_both(solve_mod, members(kind, shape, k), dt, max_iterations=n_sweeps, **FIXED)
-    assert all(sweeps(st) == n_sweeps for st, _ in batch)
-    c1, cb = base_counts(tags1), base_counts(tagsb)
+    batch, tagsb, single, tags1 = rs.run_both(solve_mod, rs.members(kind, shape, k), dt, ON, max_iterations=n_sweeps,
+                                              **FIXED)
+    assert all(rs.sweeps(st) == n_sweeps for st, _ in batch)
+    c1, cb = rs.base_counts(tags1), rs.base_counts(tagsb)
     assert c1.get("zero_fused") == n_sweeps and "zero_fused" not in cb, (sorted(c1), sorted(cb))
     assert cb.get("batch_zero_pass") == n_sweeps * math.ceil(k / width), cb
     assert cb.get("batch_zero_rows") == n_sweeps and cb.get("batch_symv_packed") == n_sweeps, cb
     assert "zero_fused_rows" not in cb, sorted(cb)
-    s1, sb = setup_counts(tags1), setup_counts(tagsb)
+    s1, sb = rs.setup_counts(tags1, SETUP), rs.setup_counts(tagsb, SETUP)
     assert any("pack_inverse" in t for t in s1) and any("spd_inverse" in t for t in s1), sorted(tags1)
     assert sb == s1, (s1, sb)
-    assert_identical(batch, single)
+    rs.assert_identical(batch, single)
 
 
 # ---- 4. more members than one launch holds --------------------------------------------------------
 def test_more_members_than_one_launch_holds(solve_mod):
     """f32 at one chunk per thread: width 8, so 9 members are launches of 8 and 1"""
     k, n_sweeps = 9, 30
-    batch, tagsb, single, _ = run_both(solve_mod, members("hinge", (256, 601), k), "f32", max_iterations=n_sweeps,
-                                       **FIXED)
-    cb = base_counts(tagsb)
+    batch, tagsb, single, _ = rs.run_both(solve_mod, rs.members("hinge", (256, 601), k), "f32", ON,
+                                          max_iterations=n_sweeps, **FIXED)
+    cb = rs.base_counts(tagsb)
     assert cb.get("batch_zero_pass") == 2 * n_sweeps and cb.get("batch_zero_rows") == n_sweeps, cb
-    assert_identical(batch, single)
+    rs.assert_identical(batch, single)
 
 
 # ---- 5. against the CPU oracle ---------------------------------------------------------------------
 @pytest.mark.parametrize("kind", ["hinge", "logreg", "bp"])
 def test_batch_matches_the_oracle_f64(solve_mod, kind):
-    probs = members(kind, (256, 601))[:3]
-    pbs, data = [p.SerializeToString() for p in probs], union_data(probs)
+    probs = rs.members(kind, (256, 601))[:3]
+    pbs, data = [p.SerializeToString() for p in probs], rs.union_data(probs)
     sb = wire.SolverParams(max_iterations=60, **FIXED).SerializeToString()
-    solve_mod.set_option("dtype", "f64")
-    try:
-        batch, tagsb = tags_of(solve_mod, lambda: solve_mod.solve_batch(pbs, None, sb, data))
-    finally:
-        solve_mod.set_option("dtype", "f32")
-    assert base_counts(tagsb).get("batch_zero_pass") == 60, sorted(tagsb)
+    with rs.options(solve_mod, dtype="f64"):
+        batch, tagsb = rs.profiled(solve_mod, lambda: solve_mod.solve_batch(pbs, None, sb, data))
+    assert rs.base_counts(tagsb).get("batch_zero_pass") == 60, sorted(tagsb)
     for pb, (stb, xb) in zip(pbs, batch):
         sto, xo = orc.solve(pb, [], sb, data)
-        a, o = status(stb), status(sto)
-        assert a.state == o.state and a.num_iterations == o.num_iterations
-        assert sorted(xb) == sorted(xo)
-        for v in xo:
-            np.testing.assert_allclose(np.frombuffer(xb[v]), np.frombuffer(xo[v]), rtol=1e-6, atol=1e-8, err_msg=v)
+        rs.assert_matches_oracle(stb, rs.arrays(xb), rs.status(sto), rs.arrays(xo), "f64")
 
 
 # ---- 6. a mixed batch, and the route switched off ---------------------------------------------------
-def lasso_pair(m, n, seed):
-    A, b = problems.regression_data(m, n, seed=seed)
-    lmax = np.abs(A.T.dot(b)).max()
-    return [problems.lasso_ir(ir.dense_matrix(A), ir.constant(b), f * lmax, n) for f in (0.4, 0.2)]
-
-
 @pytest.mark.parametrize("dtype", ["f32", "f64"])
 def test_mixed_batch_and_fallbacks(solve_mod, dtype):
     shape = (256, 601)
     m, n = shape
-    on_c1 = members("hinge", shape)[1:3]
+    on_c1 = rs.members("hinge", shape)[1:3]
     # a deadzone member on the hinge members' matrix: C of hinge_l1, the rows' offset from a vector b
     C = problems.hinge_l1(m, n)[1]["C"]
     b = np.random.RandomState(3).randn(m)
@@ -231,22 +117,18 @@ def test_mixed_batch_and_fallbacks(solve_mod, dtype):
                       ir.prox(wire.ProxFunction.NORM_1, x, alpha=lam)], C, -b)
     other = problems.hinge_l1(m, n, seed=1)[0]
     small = problems.hinge_l1(80, 40, seed=1)[0]
-    lasso = lasso_pair(300, 700, seed=6)
+    lasso = rs.lasso_pair(300, 700, seed=6)
     probs = [on_c1[0], lasso[0], other, deadzone, small, on_c1[1], lasso[1]]
     zero_only = [on_c1[0], other, deadzone, small, on_c1[1]]
-    batch, tagsb, single, _ = run_both(solve_mod, probs, dtype, max_iterations=120)
-    cb = base_counts(tagsb)
+    batch, tagsb, single, _ = rs.run_both(solve_mod, probs, dtype, ON, max_iterations=120)
+    cb = rs.base_counts(tagsb)
     assert cb.get("batch_fused_pass", 0) > 0 and cb.get("batch_zero_pass", 0) > 0, sorted(cb)
     # the member on another matrix runs alone on the single route, and it is the only one that does:
     # the deadzone member shares the hinge members' group (one row launch per sweep for the three)
-    assert cb.get("zero_fused") == sweeps(single[2][0]), (cb, sweeps(single[2][0]))
-    assert cb["batch_zero_rows"] == cb["batch_zero_pass"] == max(sweeps(single[i][0]) for i in (0, 3, 5)), cb
-    assert_identical(batch, single)
+    assert cb.get("zero_fused") == rs.sweeps(single[2][0]), (cb, rs.sweeps(single[2][0]))
+    assert cb["batch_zero_rows"] == cb["batch_zero_pass"] == max(rs.sweeps(single[i][0]) for i in (0, 3, 5)), cb
+    rs.assert_identical(batch, single)
 
-    solve_mod.set_option("fused_zero", "0")
-    try:
-        batch0, tags0, single0, _ = run_both(solve_mod, zero_only, dtype, max_iterations=120)
-    finally:
-        solve_mod.set_option("fused_zero", "auto")
-    assert not [t for t in base_counts(tags0) if t.startswith(("batch_zero", "zero_fused"))], sorted(tags0)
-    assert_identical(batch0, single0)
+    batch0, tags0, single0, _ = rs.run_both(solve_mod, zero_only, dtype, dict(fused_zero="0"), max_iterations=120)
+    assert not [t for t in rs.base_counts(tags0) if t.startswith(("batch_zero", "zero_fused"))], sorted(tags0)
+    rs.assert_identical(batch0, single0)

@@ -22,6 +22,7 @@ import scipy.sparse as sp
 from epsilon_amd import ir
 from oracle import epsilon_oracle as orc
 from oracle.epsilon_oracle import LM
+from tests import route_support as rs
 
 pytestmark = pytest.mark.gpu
 
@@ -29,15 +30,7 @@ GOLDEN = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)),
                                      "reference_known_answers.json")))
 TOL = {"f64": 1e-9, "f32": 2e-3}
 MAX = "MAX"  # a key without a diagonal block
-
-
-@pytest.fixture(params=["f64", "f32"])
-def dtype(request, solve_mod):
-    solve_mod.set_option("dtype", request.param)
-    solve_mod.set_option("refine", "auto")
-    yield request.param
-    solve_mod.set_option("dtype", "f32")
-    solve_mod.set_option("refine", "auto")
+dtype = rs.dtype_fixture(("f64", "f32"), refine="auto")
 
 
 # ---- one description of a block, two representations ------------------------------------------------

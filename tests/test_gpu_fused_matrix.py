@@ -16,29 +16,16 @@ import numpy as np
 import pytest
 
 from epsilon_amd import ir, problems, wire
-from oracle import epsilon_oracle as orc
+from tests import route_support as rs
 
 pytestmark = pytest.mark.gpu
 
 BATCH_TAGS = {"batch_fused_pass", "batch_reduce_partials", "batch_symv_packed"}
 WIDE_TAGS = {"wide_back", "wide_forward", "wide_reduce"}
 X, XP = "var:X", "separate:var:X:sum_square"
-
-
-def status(st):
-    return wire.SolverStatus.FromString(st)
-
-
-def sweeps(st):
-    s = status(st)
-    return s.num_iterations + 1 if s.state == wire.SolverStatus.OPTIMAL else s.num_iterations
-
-
-def base_counts(tags):
-    out = {}
-    for t, (c, _) in tags.items():
-        out[t.split(":")[0]] = out.get(t.split(":")[0], 0) + c
-    return out
+SETUP = ("gemm", "syrk", "spd_inverse")  # what setup_counts counts here
+# routes.solve(prob, dtype, route, fused, **solver params): the options of a solve here
+ROUTE_OPTIONS = (("route", "fused_matrix", "auto"), ("fused", "fused", "1"))
 
 
 def assert_launches(c, tag, st, per_sweep):
@@ -46,56 +33,12 @@ def assert_launches(c, tag, st, per_sweep):
     tolerances has the next epoch's sweeps enqueued behind it (Solver::Run); when that check says
     OPTIMAL they are discarded and not counted, so up to one epoch of 10 sweeps more was launched."""
     n = c.get(tag, 0)
-    assert n % per_sweep == 0 and n // per_sweep in (sweeps(st), sweeps(st) + 10), (tag, n, sweeps(st), per_sweep)
-
-
-def setup_counts(tags):
-    return {t: c for t, (c, _) in tags.items() if "gemm" in t or "syrk" in t or "spd_inverse" in t}
-
-
-class Routes(object):
-    """solves with the options set for one call and put back after it"""
-
-    def __init__(self, mod):
-        self.mod = mod
-
-    def solve(self, prob, dtype="f32", route="auto", fused="1", **params):
-        pb, data = prob.SerializeToString(), prob.expression_data()
-        sb = wire.SolverParams(**params).SerializeToString()
-        mod = self.mod
-        mod.set_option("dtype", dtype)
-        mod.set_option("fused_matrix", route)
-        mod.set_option("fused", fused)
-        mod.profile_reset()
-        mod.profile_enable(True)
-        try:
-            st, x = mod.solve(pb, [], sb, data)
-            tags = mod.profile_dump()
-        finally:
-            mod.profile_enable(False)
-            mod.set_option("fused", "1")
-            mod.set_option("fused_matrix", "auto")
-            mod.set_option("dtype", "f32")
-        return st, {k: np.frombuffer(v).copy() for k, v in x.items()}, tags
+    assert n % per_sweep == 0 and n // per_sweep in (rs.sweeps(st), rs.sweeps(st) + 10), (tag, n, rs.sweeps(st), per_sweep)
 
 
 @pytest.fixture
 def routes(solve_mod):
-    return Routes(solve_mod)
-
-
-_oracle = {}
-
-
-def oracle(kind, shape, **params):
-    """the CPU oracle's solve of one problem, computed once per module"""
-    key = (kind, shape, tuple(sorted(params.items())))
-    if key not in _oracle:
-        prob = make(kind, shape)
-        st, x = orc.solve(prob.SerializeToString(), [], wire.SolverParams(**params).SerializeToString(),
-                          prob.expression_data())
-        _oracle[key] = (status(st), {k: np.frombuffer(v).copy() for k, v in x.items()})
-    return _oracle[key]
+    return rs.Routes(solve_mod, ROUTE_OPTIONS, raw_tags=True)
 
 
 def make(kind, shape):
@@ -110,17 +53,7 @@ def make(kind, shape):
     return problems.group_lasso(m, n, k, lam=frac * lam)[0]
 
 
-def assert_matches_oracle(st, x, so, xo, dtype):
-    sg = status(st)
-    print("gpu: state %d at %d, r %.6g eps %.6g | oracle: state %d at %d, r %.6g eps %.6g" % (
-        sg.state, sg.num_iterations, sg.residuals.r_norm, sg.residuals.epsilon_primal,
-        so.state, so.num_iterations, so.residuals.r_norm, so.residuals.epsilon_primal))
-    assert sg.state == so.state and sg.num_iterations == so.num_iterations
-    tol = dict(rtol=1e-6, atol=1e-8) if dtype == "f64" else dict(rtol=5e-3, atol=5e-3)
-    assert sorted(x) == sorted(xo)
-    for k in xo:
-        print(k, "max |gpu - oracle| %.3g, max |oracle| %.3g" % (np.abs(x[k] - xo[k]).max(), np.abs(xo[k]).max()))
-        np.testing.assert_allclose(x[k], xo[k], err_msg=k, **tol)
+oracle = rs.oracle_of(make)
 
 
 # ---- 1. mv lasso, pass route, against the oracle -----------------------------------------------------
@@ -131,10 +64,10 @@ def test_mv_pass_route_matches_oracle(routes, dtype, shape, stop):
     so, xo = oracle("mv", shape)
     assert so.state == wire.SolverStatus.OPTIMAL and so.num_iterations == stop
     st, x, tags = routes.solve(make("mv", shape), dtype, "pass")
-    c = base_counts(tags)
+    c = rs.base_counts(tags)
     assert_launches(c, "batch_fused_pass", st, math.ceil(shape[2] / 8))
     assert not WIDE_TAGS & set(c) and "lasso_fused" not in c, sorted(c)
-    assert_matches_oracle(st, x, so, xo, dtype)
+    rs.assert_matches_oracle(st, x, so, xo, dtype)
 
 
 # ---- 2. mv lasso, wide route, f32, against the oracle ------------------------------------------------
@@ -144,11 +77,11 @@ def test_mv_wide_route_matches_oracle(routes, shape, route):
     so, xo = oracle("mv", shape)
     assert so.state == wire.SolverStatus.OPTIMAL and so.num_iterations == 30
     st, x, tags = routes.solve(make("mv", shape), "f32", route)
-    c = base_counts(tags)
+    c = rs.base_counts(tags)
     assert_launches(c, "wide_back", st, 1)
     assert WIDE_TAGS <= set(c), sorted(c)
     assert "batch_fused_pass" not in c and "lasso_fused" not in c, sorted(c)
-    assert_matches_oracle(st, x, so, xo, "f32")
+    rs.assert_matches_oracle(st, x, so, xo, "f32")
 
 
 # ---- 3. the forms of the inverse apply, against the generic path in the same process -----------------
@@ -162,7 +95,7 @@ def test_inverse_apply_forms_match_generic_path(routes, shape, dtype, route, for
     prob = make("mv", shape)
     st, x, tags = routes.solve(prob, dtype, route)
     sg, xg, tg = routes.solve(prob, dtype, route, fused="0")
-    c, cg = base_counts(tags), base_counts(tg)
+    c, cg = rs.base_counts(tags), rs.base_counts(tg)
     assert not (BATCH_TAGS | WIDE_TAGS) & set(cg), sorted(cg)
     if route == "pass":
         width = 6 if shape[0] == 2052 else 8  # four 16-byte chunks per thread from m = 2049 on
@@ -173,7 +106,7 @@ def test_inverse_apply_forms_match_generic_path(routes, shape, dtype, route, for
         assert not any(t.startswith(("symv", "batch_symv")) for t in c), sorted(c)
     else:
         assert c.get(form, 0) > 0, sorted(c)
-    a, g = status(st), status(sg)
+    a, g = rs.status(st), rs.status(sg)
     print("fused: state %d at %d | generic: state %d at %d" % (a.state, a.num_iterations, g.state, g.num_iterations))
     assert a.state == g.state
     assert sorted(x) == sorted(xg)
@@ -203,12 +136,12 @@ def check_group(routes, kind, shape, dtype, route, tag):
     so, xo = oracle(kind, shape, max_iterations=60)
     assert so.state == wire.SolverStatus.MAX_ITERATIONS_REACHED
     st, x, tags = routes.solve(make(kind, shape), dtype, route, max_iterations=60)
-    c = base_counts(tags)
+    c = rs.base_counts(tags)
     if tag is None:
         assert not (BATCH_TAGS | WIDE_TAGS) & set(c), sorted(c)
     else:
         assert c.get(tag) == 60 and "lasso_fused" not in c, c
-    assert_matches_oracle(st, x, so, xo, dtype)
+    rs.assert_matches_oracle(st, x, so, xo, dtype)
     k = shape[2]
     zero_g, zero_o = row_norms(x[X], k) == 0, row_norms(xo[X], k) == 0
     print("rows exactly zero: gpu %d, oracle %d of %d" % (zero_g.sum(), zero_o.sum(), zero_o.size))
@@ -248,55 +181,54 @@ def test_route_and_setup_tags(routes, shape, route):
     fixed = dict(max_iterations=25, ignore_stopping_criteria=True)
     prob, info = problems.mv_lasso(m, n, k, rho=rho)
     st, x, tags = routes.solve(prob, "f32", route, **fixed)
-    assert sweeps(st) == 25
-    c = base_counts(tags)
+    assert rs.sweeps(st) == 25
+    c = rs.base_counts(tags)
     assert "lasso_fused" not in c, sorted(c)
     if route == "pass":
-        assert c.get("batch_fused_pass") == sweeps(st) * math.ceil(k / 8), c
-        assert c.get("batch_reduce_partials") == sweeps(st) and not WIDE_TAGS & set(c), c
+        assert c.get("batch_fused_pass") == rs.sweeps(st) * math.ceil(k / 8), c
+        assert c.get("batch_reduce_partials") == rs.sweeps(st) and not WIDE_TAGS & set(c), c
     else:
-        assert c.get("wide_back") == c.get("wide_forward") == c.get("wide_reduce") == sweeps(st), c
+        assert c.get("wide_back") == c.get("wide_forward") == c.get("wide_reduce") == rs.sweeps(st), c
         assert not BATCH_TAGS & set(c), sorted(c)
     # the Gram product and the inverse are formed once for all k columns: the setup of ONE vector lasso
     vec = problems.lasso_ir(ir.dense_matrix(info["A"]), ir.constant(info["B"][:, 0]), info["lam"], n)
     _, _, tv = routes.solve(vec, "f32", **fixed)
-    assert "lasso_fused" in base_counts(tv)
-    setup = setup_counts(tags)
+    assert "lasso_fused" in rs.base_counts(tv)
+    setup = rs.setup_counts(tags, SETUP)
     if route == "wide":
         # the wide sweep's own product, the cached inverse times the panel of 64 members (once at
         # Init, once per sweep and contraction range), carries the gemm tag too: not setup
-        panel = [t for t in setup if t not in setup_counts(tv)]
+        panel = [t for t in setup if t not in rs.setup_counts(tv, SETUP)]
         assert panel and all(t.startswith("gemm:%dx" % (64 * m)) for t in panel), panel
-        assert all(setup.pop(t) % (sweeps(st) + 1) == 0 for t in panel), setup_counts(tags)
-    assert setup_counts(tv) and setup == setup_counts(tv), (setup, setup_counts(tv))
+        assert all(setup.pop(t) % (rs.sweeps(st) + 1) == 0 for t in panel), rs.setup_counts(tags, SETUP)
+    assert rs.setup_counts(tv, SETUP) and setup == rs.setup_counts(tv, SETUP), (setup, rs.setup_counts(tv, SETUP))
     _, x0, t0 = routes.solve(prob, "f32", "0", **fixed)
-    assert not (BATCH_TAGS | WIDE_TAGS | {"lasso_fused"}) & set(base_counts(t0)), sorted(base_counts(t0))
+    assert not (BATCH_TAGS | WIDE_TAGS | {"lasso_fused"}) & set(rs.base_counts(t0)), sorted(rs.base_counts(t0))
 
 
 # ---- 6. below the floor of 256 rows -----------------------------------------------------------------------
 @pytest.mark.parametrize("kind,shape", [("mv", (30, 40, 3, 0.1)), ("group", (30, 20, 3))])
 def test_small_problems_keep_the_generic_path(routes, kind, shape):
     st, x, tags = routes.solve(make(kind, shape), "f64", max_iterations=60)
-    c = base_counts(tags)
+    c = rs.base_counts(tags)
     assert c and not (BATCH_TAGS | WIDE_TAGS | {"lasso_fused"}) & set(c), sorted(c)
     # ... and the routes themselves are taken from 256 rows on (what fails without the fused sweep)
     big = {"mv": (256, 301, 3, 0.1), "group": (256, 301, 3)}[kind]
     _, _, tb = routes.solve(make(kind, big), "f64", max_iterations=20)
-    assert "batch_fused_pass" in base_counts(tb), sorted(base_counts(tb))
+    assert "batch_fused_pass" in rs.base_counts(tb), sorted(rs.base_counts(tb))
 
 
 # ---- 7. handles: two runs continue where one would ---------------------------------------------------------
 def handle_run(mod, prob, route, chunks):
-    mod.set_option("fused_matrix", route)
-    try:
+    with rs.options(mod, fused_matrix=route):
         s = mod.Solver(prob.SerializeToString(), wire.SolverParams().SerializeToString(), prob.expression_data())
-        s.init()
-        for n in chunks:
-            assert s.run(n) == n
-        st, x = s.result()
-        s.close()
-    finally:
-        mod.set_option("fused_matrix", "auto")
+        try:
+            s.init()
+            for n in chunks:
+                assert s.run(n) == n
+            st, x = s.result()
+        finally:
+            s.close()
     return st, x
 
 
@@ -306,8 +238,7 @@ def test_two_runs_continue_where_one_would(solve_mod, route):
     _, two = handle_run(solve_mod, prob, route, [5, 5])
     _, one = handle_run(solve_mod, prob, route, [10])
     assert sorted(one) == sorted(two) == sorted([X, XP])
-    for k in one:
-        assert one[k] == two[k], k
+    rs.assert_same_arrays(one, two)
 
 
 # ---- 8. the same solve twice ----------------------------------------------------------------------------------
@@ -316,9 +247,8 @@ def test_same_solve_twice_same_bytes(routes, route):
     prob = make("mv", (256, 301, 10, 0.1))
     sa, xa, _ = routes.solve(prob, "f32", route)
     sb, xb, _ = routes.solve(prob, "f32", route)
-    assert status(sa).num_iterations == status(sb).num_iterations
-    for k in xa:
-        assert xa[k].tobytes() == xb[k].tobytes(), k
+    assert rs.status(sa).num_iterations == rs.status(sb).num_iterations
+    rs.assert_same_arrays(xa, xb)
 
 
 # ---- 9. inside a batch the matrix-variable problem runs alone ---------------------------------------------------
@@ -328,19 +258,12 @@ def test_in_a_batch_the_mv_problem_runs_alone(solve_mod):
     A, B, lam = info["A"], info["B"], info["lam"]
     lassos = [problems.lasso_ir(ir.dense_matrix(A), ir.constant(B[:, c]), f * lam, n) for c, f in ((0, 1.0), (1, 0.7))]
     probs = [mv] + lassos
-    data = {}
-    for p in probs:
-        data.update(p.expression_data())
+    data = rs.union_data(probs)
     sb = wire.SolverParams().SerializeToString()
     pbs = [p.SerializeToString() for p in probs]
     batch = solve_mod.solve_batch(pbs, None, sb, data)
     st, x = solve_mod.solve(pbs[0], [], sb, data)
-    a, s = status(batch[0][0]), status(st)
-    assert a.state == s.state and a.num_iterations == s.num_iterations
-    assert sorted(batch[0][1]) == sorted(x)
-    for v in x:
-        assert batch[0][1][v] == x[v], v
+    rs.assert_same_bytes(batch[0][0], batch[0][1], st, x)
     for i in (1, 2):  # the two vector problems still form their group
         sti, xi = solve_mod.solve(pbs[i], [], sb, data)
-        for v in xi:
-            assert batch[i][1][v] == xi[v], (i, v)
+        rs.assert_same_arrays(batch[i][1], xi, i)

@@ -18,15 +18,12 @@ import numpy as np
 import pytest
 
 from epsilon_amd import problems, wire
+from tests import route_support as rs
 
 pytestmark = pytest.mark.gpu
 
 RESIDUALS = ("r_norm", "s_norm", "epsilon_primal", "epsilon_dual")
 SWEEPS = 25
-
-
-def status(st):
-    return wire.SolverStatus.FromString(st)
 
 
 def rule(mod, m, n, dtype, budget_bytes):
@@ -88,14 +85,14 @@ def runs(mod, prob, dtype, budgets, tag, shares=None, **params):
             tags = tag_counts(mod)
             mod.profile_enable(False)
             st, x = s.result()
-            assert status(st).num_iterations == SWEEPS
+            assert rs.status(st).num_iterations == SWEEPS
             if tag is not None:
                 assert tags.get(tag, 0) >= SWEEPS, (budget, tags)  # the fused pass ran every sweep
                 if shares is not None:
                     assert last_share(mod) == shares[len(out)], (budget, last_share(mod), shares)
             else:
                 assert not any(t.endswith("_fused") for t in tags), (budget, tags)
-            out.append((tuple(getattr(status(st).residuals, f) for f in RESIDUALS), {k: bytes(v) for k, v in x.items()}))
+            out.append((tuple(getattr(rs.status(st).residuals, f) for f in RESIDUALS), {k: bytes(v) for k, v in x.items()}))
     finally:
         mod.profile_enable(False)
         s.close()
@@ -172,7 +169,7 @@ def test_batch_members_equal_their_single_solves_under_every_budget(solve_mod):
     kib, cuts = budgets_kib(solve_mod, m, n, "f32")
 
     def result(st, x):
-        s = status(st)
+        s = rs.status(st)
         assert s.num_iterations == SWEEPS
         return tuple(getattr(s.residuals, f) for f in RESIDUALS), {k: bytes(v) for k, v in x.items()}
 

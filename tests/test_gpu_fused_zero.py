@@ -21,130 +21,46 @@ import pytest
 
 from epsilon_amd import problems, wire
 from oracle import epsilon_oracle as orc
+from tests import route_support as rs
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(256, 601), (260, 601), (1028, 2051)]
 FIXED = dict(max_iterations=60, abs_tol=0.0, rel_tol=0.0)
-
-
-def status(st):
-    return wire.SolverStatus.FromString(st)
-
-
-def sweeps(st):
-    s = status(st)
-    return s.num_iterations + 1 if s.state == wire.SolverStatus.OPTIMAL else s.num_iterations
-
-
-def base_counts(tags):
-    out = {}
-    for t, (c, _) in tags.items():
-        out[t.split(":")[0]] = out.get(t.split(":")[0], 0) + c
-    return out
+# routes.solve(prob, dtype, route, fused, **solver params): the options of a solve here
+ROUTE_OPTIONS = (("route", "fused_zero", "auto"), ("fused", "fused", "1"))
+ON = rs.switched_on(ROUTE_OPTIONS)  # nothing: the route is the library's default
 
 
 def zero_tags(c):
     return sorted(t for t in c if t.startswith("zero_fused"))
 
 
-class Routes(object):
-    """solves with the options set for one call and put back after it"""
-
-    def __init__(self, mod):
-        self.mod = mod
-
-    def solve(self, prob, dtype="f32", route="auto", fused="1", **params):
-        pb, data = prob.SerializeToString(), prob.expression_data()
-        sb = wire.SolverParams(**params).SerializeToString()
-        mod = self.mod
-        mod.set_option("dtype", dtype)
-        mod.set_option("fused_zero", route)
-        mod.set_option("fused", fused)
-        mod.profile_reset()
-        mod.profile_enable(True)
-        try:
-            st, x = mod.solve(pb, [], sb, data)
-            tags = mod.profile_dump()
-        finally:
-            mod.profile_enable(False)
-            mod.set_option("fused", "1")
-            mod.set_option("fused_zero", "auto")
-            mod.set_option("dtype", "f32")
-        return st, {k: np.frombuffer(v).copy() for k, v in x.items()}, base_counts(tags)
-
-
 @pytest.fixture
 def routes(solve_mod):
-    return Routes(solve_mod)
+    return rs.Routes(solve_mod, ROUTE_OPTIONS)
 
 
-_made = {}
-
-
-def make(kind, shape):
-    key = (kind, shape)
-    if key not in _made:
-        m, n = shape
-        if kind == "bp":
-            _made[key] = problems.basis_pursuit(m, n)[0]
-        elif kind == "deadzone":
-            _made[key] = problems.deadzone_l1(m, n)[0]
-        elif kind == "hinge_default":
-            _made[key] = problems.hinge_l1(m, n)[0]
-        elif kind == "hinge":
-            C = problems.hinge_l1(m, n)[1]["C"]
-            _made[key] = problems.hinge_l1(m, n, lam=0.01 * np.abs(C.sum(axis=0)).max())[0]
-        elif kind == "hinge_tall":
-            _made[key] = problems.hinge_l1(m, n)[0]
-        elif kind == "lp":
-            _made[key] = problems.lp(m, n)[0]
-        else:
-            assert kind == "lad"
-            _made[key] = problems.least_abs_dev(m, n)[0]
-    return _made[key]
-
-
-_oracle = {}
-
-
-def oracle(kind, shape, **params):
-    """the CPU oracle's solve of one problem, computed once per module"""
-    key = (kind, shape, tuple(sorted(params.items())))
-    if key not in _oracle:
-        prob = make(kind, shape)
-        st, x = orc.solve(prob.SerializeToString(), [], wire.SolverParams(**params).SerializeToString(),
-                          prob.expression_data())
-        _oracle[key] = (status(st), {k: np.frombuffer(v).copy() for k, v in x.items()})
-    return _oracle[key]
-
-
-def assert_close(x, xo, dtype):
-    tol = dict(rtol=1e-6, atol=1e-8) if dtype == "f64" else dict(rtol=5e-3, atol=5e-3)
-    assert sorted(x) == sorted(xo)
-    for k in xo:
-        print(k, "max |gpu - oracle| %.3g, max |oracle| %.3g" % (np.abs(x[k] - xo[k]).max(), np.abs(xo[k]).max()))
-    for k in xo:
-        np.testing.assert_allclose(x[k], xo[k], err_msg=k, **tol)
-
-
-def assert_matches_oracle(st, x, so, xo, dtype):
-    sg = status(st)
-    print("gpu: state %d at %d, r %.6g eps %.6g | oracle: state %d at %d, r %.6g eps %.6g" % (
-        sg.state, sg.num_iterations, sg.residuals.r_norm, sg.residuals.epsilon_primal,
-        so.state, so.num_iterations, so.residuals.r_norm, so.residuals.epsilon_primal))
-    assert sg.state == so.state and sg.num_iterations == so.num_iterations
-    assert_close(x, xo, dtype)
+make = rs.memoised({
+    "bp": lambda m, n: problems.basis_pursuit(m, n)[0],
+    "deadzone": lambda m, n: problems.deadzone_l1(m, n)[0],
+    "hinge_default": lambda m, n: problems.hinge_l1(m, n)[0],
+    "hinge": lambda m, n: problems.hinge_l1(m, n, lam=0.01 * rs.lam_scale("hinge_l1", m, n))[0],
+    "hinge_tall": lambda m, n: problems.hinge_l1(m, n)[0],
+    "lp": lambda m, n: problems.lp(m, n)[0],
+    "lad": lambda m, n: problems.least_abs_dev(m, n)[0],
+})
+oracle = rs.oracle_of(make)
 
 
 def assert_route(c, st, rows, shape):
     """one pass per sweep (the checks are not pipelined: nothing is discarded), the row kernel
     with it where the problem has a z block, the packed symmetric apply from 1024 rows"""
-    assert c.get("zero_fused", 0) == sweeps(st), (zero_tags(c), c.get("zero_fused"), sweeps(st))
-    assert c.get("zero_fused_rows", 0) == (sweeps(st) if rows else 0), (c.get("zero_fused_rows"), sweeps(st))
+    assert c.get("zero_fused", 0) == rs.sweeps(st), (zero_tags(c), c.get("zero_fused"), rs.sweeps(st))
+    assert c.get("zero_fused_rows", 0) == (rs.sweeps(st) if rows else 0), (c.get("zero_fused_rows"), rs.sweeps(st))
     assert "lasso_fused" not in c
     if shape[0] >= 1024:
-        assert c.get("symv_packed", 0) >= sweeps(st), sorted(c)
+        assert c.get("symv_packed", 0) >= rs.sweeps(st), sorted(c)
 
 
 # ---- 1. basis pursuit, default stopping rule -------------------------------------------------------
@@ -154,7 +70,7 @@ def test_basis_pursuit_stops_with_the_oracle(routes, dtype, shape, stop):
     so, xo = oracle("bp", shape)
     assert so.state == wire.SolverStatus.OPTIMAL and so.num_iterations == stop
     st, x, c = routes.solve(make("bp", shape), dtype)
-    assert_matches_oracle(st, x, so, xo, dtype)
+    rs.assert_matches_oracle(st, x, so, xo, dtype)
     assert_route(c, st, False, shape)
 
 
@@ -187,7 +103,7 @@ def test_sixty_sweeps_match_the_oracle(routes, kind, shape, dtype):
     assert_both_sides(kind, xo)
     st, x, c = routes.solve(make(kind, shape), dtype, **FIXED)
     assert_route(c, st, kind != "bp", shape)
-    assert_matches_oracle(st, x, so, xo, dtype)
+    rs.assert_matches_oracle(st, x, so, xo, dtype)
 
 
 # ---- 3. hinge, default stopping rule, f64 -----------------------------------------------------------
@@ -197,7 +113,7 @@ def test_hinge_stops_with_the_oracle_f64(routes):
     assert so.state == wire.SolverStatus.OPTIMAL and so.num_iterations == 270
     st, x, c = routes.solve(make("hinge_default", shape), "f64")
     assert_route(c, st, True, shape)
-    assert_matches_oracle(st, x, so, xo, "f64")
+    rs.assert_matches_oracle(st, x, so, xo, "f64")
 
 
 # ---- 4. fused against generic, f64 --------------------------------------------------------------------
@@ -209,7 +125,7 @@ def test_fused_equals_generic_to_rounding_f64(routes, kind):
     st0, x0, c0 = routes.solve(prob, "f64", "0", **FIXED)
     assert_route(c, st, kind != "bp", shape)
     assert not zero_tags(c0)
-    assert status(st).num_iterations == status(st0).num_iterations == 60
+    assert rs.status(st).num_iterations == rs.status(st0).num_iterations == 60
     for k in x0:
         diff, ref = np.abs(x[k] - x0[k]).max(), np.abs(x0[k]).max()
         print(k, "max |fused - generic| %.3g, max |generic| %.3g" % (diff, ref))
@@ -232,10 +148,7 @@ def test_fall_backs_are_the_generic_path(routes, kind, shape, dtype, params, fus
     st, x, c = routes.solve(prob, dtype, "auto", fused, **params)
     st0, x0, c0 = routes.solve(prob, dtype, "0", fused, **params)
     assert not zero_tags(c) and not zero_tags(c0)
-    assert (status(st).state, status(st).num_iterations) == (status(st0).state, status(st0).num_iterations)
-    assert sorted(x) == sorted(x0)
-    for k in x0:
-        assert x[k].tobytes() == x0[k].tobytes(), k
+    rs.assert_same_bytes(st, x, st0, x0)
 
 
 def test_rows_multiple_of_two_take_the_route_in_f64(routes):
@@ -244,36 +157,16 @@ def test_rows_multiple_of_two_take_the_route_in_f64(routes):
 
 
 # ---- 6. sweep boundaries and warm start -------------------------------------------------------------
-def run_handle(mod, prob, dtype, splits, **params):
-    mod.set_option("dtype", dtype)
-    s = mod.Solver(prob.SerializeToString(), wire.SolverParams(**params).SerializeToString(),
-                   prob.expression_data())
-    mod.profile_reset()
-    mod.profile_enable(True)
-    try:
-        s.init()
-        for part in splits:
-            assert s.run(part) == part
-        c = base_counts(mod.profile_dump())
-        st, x = s.result()
-    finally:
-        mod.profile_enable(False)
-        s.close()
-        mod.set_option("dtype", "f32")
-    return st, {k: np.frombuffer(v).copy() for k, v in x.items()}, c
-
-
 @pytest.mark.parametrize("dtype", ["f32", "f64"])
 def test_a_solve_can_stop_after_any_sweep(solve_mod, dtype):
     prob = make("hinge_default", (256, 601))
     params = dict(max_iterations=1000, abs_tol=0.0, rel_tol=0.0)
-    st_a, xa, ca = run_handle(solve_mod, prob, dtype, [30], **params)
-    st_b, xb, cb = run_handle(solve_mod, prob, dtype, [1, 9, 20], **params)
+    st_a, xa, ca = rs.run_handle(solve_mod, prob, dtype, [30], ON, **params)
+    st_b, xb, cb = rs.run_handle(solve_mod, prob, dtype, [1, 9, 20], ON, **params)
     assert ca.get("zero_fused") == cb.get("zero_fused") == 30
     assert ca.get("zero_fused_rows") == cb.get("zero_fused_rows") == 30
-    assert sorted(xa) == sorted(xb) and len(xa) == 4
-    for k in xa:
-        assert xa[k].tobytes() == xb[k].tobytes(), k
+    assert len(xa) == 4
+    rs.assert_same_arrays(xa, xb)
 
 
 @pytest.mark.parametrize("dtype", ["f32", "f64"])
@@ -283,28 +176,20 @@ def test_warm_start_takes_the_state_over(solve_mod, dtype):
     prob = make("hinge_default", (256, 601))
     sp = wire.SolverParams(warm_start=True, max_iterations=30, abs_tol=0.0, rel_tol=0.0)
     pb, data = prob.SerializeToString(), prob.expression_data()
-    solve_mod.set_option("dtype", dtype)
-    s = solve_mod.Solver(pb, sp.SerializeToString(), data)
-    solve_mod.profile_reset()
-    solve_mod.profile_enable(True)
-    try:
+    with rs.handle(solve_mod, prob, dtype, sp, **ON) as s:
         s.init()
         s.run(-1)
         s.init()
         s.run(-1)
-        c = base_counts(solve_mod.profile_dump())
+        c = rs.base_counts(solve_mod.profile_dump())
         st, x = s.result()
-    finally:
-        solve_mod.profile_enable(False)
-        s.close()
-        solve_mod.set_option("dtype", "f32")
     assert c.get("zero_fused") == c.get("zero_fused_rows") == 60
     osolver = orc.create_solver(wire.Problem.FromString(pb), dict(data), sp)
     osolver.solve()
     xo = osolver.solve()
-    assert status(st).num_iterations == osolver.status.num_iterations == 30
-    x = {k: np.frombuffer(v) for k, v in x.items()}
-    assert_close(x, {k: np.asarray(xo(k), dtype=np.float64).ravel() for k in x}, dtype)
+    assert rs.status(st).num_iterations == osolver.status.num_iterations == 30
+    x = rs.arrays(x)
+    rs.assert_close(x, {k: np.asarray(xo(k), dtype=np.float64).ravel() for k in x}, dtype)
     # the second solve went on from the first: it is not the cold solve's iterate (in the oracle
     # the two differ by 0.94 in z, far above the tolerances)
     cold = oracle("hinge_default", (256, 601), max_iterations=30, abs_tol=0.0, rel_tol=0.0)[1]
@@ -318,5 +203,4 @@ def test_two_solves_return_the_same_bytes(routes):
     st2, x2, c2 = routes.solve(prob, "f32", **FIXED)
     assert_route(c1, st1, True, (1028, 2051))
     assert c1.get("zero_fused") == c2.get("zero_fused")
-    for k in x1:
-        assert x1[k].tobytes() == x2[k].tobytes(), k
+    rs.assert_same_arrays(x1, x2)

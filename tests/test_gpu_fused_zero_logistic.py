@@ -20,122 +20,43 @@ import pytest
 
 from epsilon_amd import problems, wire
 from oracle import epsilon_oracle as orc
+from tests import route_support as rs
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(256, 601), (260, 601), (1028, 2051)]
 FIXED = dict(max_iterations=60, abs_tol=0.0, rel_tol=0.0)
 KEYS = ["separate:var:x:zero", "separate:var:z:zero", "var:x", "var:z"]
-
-
-def status(st):
-    return wire.SolverStatus.FromString(st)
-
-
-def sweeps(st):
-    s = status(st)
-    return s.num_iterations + 1 if s.state == wire.SolverStatus.OPTIMAL else s.num_iterations
-
-
-def base_counts(tags):
-    out = {}
-    for t, (c, _) in tags.items():
-        out[t.split(":")[0]] = out.get(t.split(":")[0], 0) + c
-    return out
+# routes.solve(prob, dtype, route, fused, **solver params): the options of a solve here
+ROUTE_OPTIONS = (("route", "fused_zero", "auto"), ("fused", "fused", "1"))
+ON = rs.switched_on(ROUTE_OPTIONS)  # nothing: the route is the library's default
 
 
 def zero_tags(c):
     return sorted(t for t in c if t.startswith("zero_fused"))
 
 
-class Routes(object):
-    """solves with the options set for one call and put back after it"""
-
-    def __init__(self, mod):
-        self.mod = mod
-
-    def solve(self, prob, dtype="f32", route="auto", fused="1", **params):
-        pb, data = prob.SerializeToString(), prob.expression_data()
-        sb = wire.SolverParams(**params).SerializeToString()
-        mod = self.mod
-        mod.set_option("dtype", dtype)
-        mod.set_option("fused_zero", route)
-        mod.set_option("fused", fused)
-        mod.profile_reset()
-        mod.profile_enable(True)
-        try:
-            st, x = mod.solve(pb, [], sb, data)
-            tags = mod.profile_dump()
-        finally:
-            mod.profile_enable(False)
-            mod.set_option("fused", "1")
-            mod.set_option("fused_zero", "auto")
-            mod.set_option("dtype", "f32")
-        return st, {k: np.frombuffer(v).copy() for k, v in x.items()}, base_counts(tags)
-
-
 @pytest.fixture
 def routes(solve_mod):
-    return Routes(solve_mod)
+    return rs.Routes(solve_mod, ROUTE_OPTIONS)
 
 
-_made = {}
-
-
-def make(kind, shape):
-    """kind "default": the default lambda, 0.1 max|C^T 1/2|; "small": a tenth of it"""
-    key = (kind, shape)
-    if key not in _made:
-        m, n = shape
-        if kind == "default":
-            _made[key] = problems.logreg_l1(m, n)[0]
-        else:
-            assert kind == "small"
-            C = problems.logreg_l1(m, n)[1]["C"]
-            _made[key] = problems.logreg_l1(m, n, lam=0.01 * np.abs(C.T.dot(np.full(m, 0.5))).max())[0]
-    return _made[key]
-
-
-_oracle = {}
-
-
-def oracle(kind, shape, **params):
-    """the CPU oracle's solve of one problem, computed once per module"""
-    key = (kind, shape, tuple(sorted(params.items())))
-    if key not in _oracle:
-        prob = make(kind, shape)
-        st, x = orc.solve(prob.SerializeToString(), [], wire.SolverParams(**params).SerializeToString(),
-                          prob.expression_data())
-        _oracle[key] = (status(st), {k: np.frombuffer(v).copy() for k, v in x.items()})
-    return _oracle[key]
-
-
-def assert_close(x, xo, dtype):
-    tol = dict(rtol=1e-6, atol=1e-8) if dtype == "f64" else dict(rtol=5e-3, atol=5e-3)
-    assert sorted(x) == sorted(xo)
-    for k in xo:
-        print(k, "max |gpu - oracle| %.3g, max |oracle| %.3g" % (np.abs(x[k] - xo[k]).max(), np.abs(xo[k]).max()))
-    for k in xo:
-        np.testing.assert_allclose(x[k], xo[k], err_msg=k, **tol)
-
-
-def assert_matches_oracle(st, x, so, xo, dtype):
-    sg = status(st)
-    print("gpu: state %d at %d, r %.6g eps %.6g | oracle: state %d at %d, r %.6g eps %.6g" % (
-        sg.state, sg.num_iterations, sg.residuals.r_norm, sg.residuals.epsilon_primal,
-        so.state, so.num_iterations, so.residuals.r_norm, so.residuals.epsilon_primal))
-    assert sg.state == so.state and sg.num_iterations == so.num_iterations
-    assert_close(x, xo, dtype)
+# kind "default": the default lambda, 0.1 max|C^T 1/2|; "small": a tenth of it
+make = rs.memoised({
+    "default": lambda m, n: problems.logreg_l1(m, n)[0],
+    "small": lambda m, n: problems.logreg_l1(m, n, lam=0.01 * rs.lam_scale("logreg_l1", m, n))[0],
+})
+oracle = rs.oracle_of(make)
 
 
 def assert_route(c, st, shape):
     """one pass and one row kernel per sweep (the checks are not pipelined: nothing is discarded),
     the packed symmetric apply from 1024 rows"""
-    assert c.get("zero_fused", 0) == sweeps(st), (zero_tags(c), c.get("zero_fused"), sweeps(st))
-    assert c.get("zero_fused_rows", 0) == sweeps(st), (c.get("zero_fused_rows"), sweeps(st))
+    assert c.get("zero_fused", 0) == rs.sweeps(st), (zero_tags(c), c.get("zero_fused"), rs.sweeps(st))
+    assert c.get("zero_fused_rows", 0) == rs.sweeps(st), (c.get("zero_fused_rows"), rs.sweeps(st))
     assert "lasso_fused" not in c
     if shape[0] >= 1024:
-        assert c.get("symv_packed", 0) >= sweeps(st), sorted(c)
+        assert c.get("symv_packed", 0) >= rs.sweeps(st), sorted(c)
 
 
 # ---- 1. fixed 60 sweeps, every variable against the oracle -----------------------------------------
@@ -153,7 +74,7 @@ def test_sixty_sweeps_match_the_oracle(routes, kind, shape, dtype):
     assert z.min() < 3 and z.max() > 4.5  # rows on the bend of the logistic loss and far out in its tails
     st, x, c = routes.solve(make(kind, shape), dtype, **FIXED)
     assert_route(c, st, shape)
-    assert_matches_oracle(st, x, so, xo, dtype)
+    rs.assert_matches_oracle(st, x, so, xo, dtype)
 
 
 # ---- 2. default stopping rule -------------------------------------------------------------------------
@@ -171,7 +92,7 @@ def test_stops_with_the_oracle(routes, shape, dtype, stop, ratio):
     assert so.residuals.s_norm <= 0.5 * so.residuals.epsilon_dual
     st, x, c = routes.solve(make("default", shape), dtype)
     assert_route(c, st, shape)
-    assert_matches_oracle(st, x, so, xo, dtype)
+    rs.assert_matches_oracle(st, x, so, xo, dtype)
 
 
 # ---- 3. fused against generic, f64 --------------------------------------------------------------------
@@ -184,7 +105,7 @@ def test_fused_equals_generic_to_rounding_f64(routes):
     st0, x0, c0 = routes.solve(prob, "f64", "0", **FIXED)
     assert_route(c, st, shape)
     assert not zero_tags(c0)
-    assert status(st).num_iterations == status(st0).num_iterations == 60
+    assert rs.status(st).num_iterations == rs.status(st0).num_iterations == 60
     assert sorted(x) == sorted(x0) == KEYS
     for k in x0:
         diff, ref = np.abs(x[k] - x0[k]).max(), np.abs(x0[k]).max()
@@ -194,37 +115,17 @@ def test_fused_equals_generic_to_rounding_f64(routes):
 
 
 # ---- 4. sweep boundaries and warm start -------------------------------------------------------------
-def run_handle(mod, prob, dtype, splits, **params):
-    mod.set_option("dtype", dtype)
-    s = mod.Solver(prob.SerializeToString(), wire.SolverParams(**params).SerializeToString(),
-                   prob.expression_data())
-    mod.profile_reset()
-    mod.profile_enable(True)
-    try:
-        s.init()
-        for part in splits:
-            assert s.run(part) == part
-        c = base_counts(mod.profile_dump())
-        st, x = s.result()
-    finally:
-        mod.profile_enable(False)
-        s.close()
-        mod.set_option("dtype", "f32")
-    return st, {k: np.frombuffer(v).copy() for k, v in x.items()}, c
-
-
 @pytest.mark.parametrize("dtype", ["f32", "f64"])
 def test_a_solve_can_stop_after_any_sweep(solve_mod, dtype):
     """the head the row kernel carries from one sweep to the next survives the end of a run call"""
     prob = make("default", (256, 601))
     params = dict(max_iterations=1000, abs_tol=0.0, rel_tol=0.0)
-    st_a, xa, ca = run_handle(solve_mod, prob, dtype, [30], **params)
-    st_b, xb, cb = run_handle(solve_mod, prob, dtype, [1, 7, 22], **params)
+    st_a, xa, ca = rs.run_handle(solve_mod, prob, dtype, [30], ON, **params)
+    st_b, xb, cb = rs.run_handle(solve_mod, prob, dtype, [1, 7, 22], ON, **params)
     assert ca.get("zero_fused") == cb.get("zero_fused") == 30
     assert ca.get("zero_fused_rows") == cb.get("zero_fused_rows") == 30
     assert sorted(xa) == sorted(xb) == KEYS
-    for k in xa:
-        assert xa[k].tobytes() == xb[k].tobytes(), k
+    rs.assert_same_arrays(xa, xb)
 
 
 @pytest.mark.parametrize("dtype", ["f32", "f64"])
@@ -234,34 +135,26 @@ def test_warm_start_takes_the_state_over(solve_mod, dtype):
     prob = make("default", (256, 601))
     sp = wire.SolverParams(warm_start=True, max_iterations=30, abs_tol=0.0, rel_tol=0.0)
     pb, data = prob.SerializeToString(), prob.expression_data()
-    solve_mod.set_option("dtype", dtype)
-    s = solve_mod.Solver(pb, sp.SerializeToString(), data)
-    solve_mod.profile_reset()
-    solve_mod.profile_enable(True)
-    try:
+    with rs.handle(solve_mod, prob, dtype, sp, **ON) as s:
         s.init()
         s.run(-1)
         s.init()
         s.run(-1)
-        c = base_counts(solve_mod.profile_dump())
+        c = rs.base_counts(solve_mod.profile_dump())
         st, x = s.result()
-    finally:
-        solve_mod.profile_enable(False)
-        s.close()
-        solve_mod.set_option("dtype", "f32")
     assert c.get("zero_fused") == c.get("zero_fused_rows") == 60
     osolver = orc.create_solver(wire.Problem.FromString(pb), dict(data), sp)
     osolver.solve()
     xo = osolver.solve()
-    assert status(st).num_iterations == osolver.status.num_iterations == 30
-    x = {k: np.frombuffer(v) for k, v in x.items()}
+    assert rs.status(st).num_iterations == osolver.status.num_iterations == 30
+    x = rs.arrays(x)
     xo = {k: np.asarray(xo(k), dtype=np.float64).ravel() for k in x}
     # the second solve went on from the first: in the oracle it is not the cold solve's iterate,
     # by far more than the tolerances
     cold = oracle("default", (256, 601), max_iterations=30, abs_tol=0.0, rel_tol=0.0)[1]
     print("oracle: max |warm - cold| in z %.3g" % np.abs(xo["var:z"] - cold["var:z"]).max())
     assert np.abs(xo["var:z"] - cold["var:z"]).max() > 0.1
-    assert_close(x, xo, dtype)
+    rs.assert_close(x, xo, dtype)
 
 
 # ---- 5. determinism ------------------------------------------------------------------------------------
@@ -274,8 +167,7 @@ def test_two_solves_return_the_same_bytes(routes, dtype):
     assert_route(c1, st1, shape)
     assert_route(c2, st2, shape)
     assert sorted(x1) == sorted(x2) == KEYS
-    for k in x1:
-        assert x1[k].tobytes() == x2[k].tobytes(), k
+    rs.assert_same_arrays(x1, x2)
 
 
 # ---- 6. what keeps the generic path ---------------------------------------------------------------------
@@ -291,7 +183,5 @@ def test_fall_backs_are_the_generic_path(routes, shape, dtype, params, fused):
     st, x, c = routes.solve(prob, dtype, "auto", fused, **params)
     st0, x0, c0 = routes.solve(prob, dtype, "0", fused, **params)
     assert not zero_tags(c) and not zero_tags(c0)
-    assert (status(st).state, status(st).num_iterations) == (status(st0).state, status(st0).num_iterations)
     assert sorted(x) == sorted(x0) == KEYS
-    for k in x0:
-        assert x[k].tobytes() == x0[k].tobytes(), k
+    rs.assert_same_bytes(st, x, st0, x0)

@@ -26,6 +26,7 @@ import pytest
 
 from epsilon_amd import problems, wire
 from oracle import epsilon_oracle as orc
+from tests import route_support as rs
 
 pytestmark = pytest.mark.gpu
 
@@ -33,114 +34,29 @@ SHAPES = [(601, 256), (603, 260), (2051, 1028)]
 FIXED = dict(max_iterations=60, abs_tol=0.0, rel_tol=0.0)
 KEYS = ["separate:var:x:zero", "separate:var:z:zero", "var:x", "var:z"]
 SMOOTH_TAGS = ["zero_tall_dot", "zero_tall_samples", "zero_tall_acc", "zero_tall_cols"]
-
-
-def status(st):
-    return wire.SolverStatus.FromString(st)
-
-
-def sweeps(st):
-    s = status(st)
-    return s.num_iterations + 1 if s.state == wire.SolverStatus.OPTIMAL else s.num_iterations
-
-
-def base_counts(tags):
-    out = {}
-    for t, (c, _) in tags.items():
-        out[t.split(":")[0]] = out.get(t.split(":")[0], 0) + c
-    return out
+# routes.solve(prob, dtype, smooth, tall, fused, fused_zero, **solver params): the options of a solve
+ROUTE_OPTIONS = (("smooth", "fused_zero_tall_smooth", "1"), ("tall", "fused_zero_tall", "1"),
+                 ("fused", "fused", "1"), ("fused_zero", "fused_zero", "auto"))
+ON = rs.switched_on(ROUTE_OPTIONS)  # the two tall options = "1": what the handles and the batch set
 
 
 def route_tags(c):
     return sorted(t for t in c if t.startswith("zero_tall") or t.startswith("zero_fused"))
 
 
-class Routes(object):
-    """solves with the options set for one call and put back after it"""
-
-    def __init__(self, mod):
-        self.mod = mod
-
-    def solve(self, prob, dtype="f32", smooth="1", tall="1", fused="1", fused_zero="auto", **params):
-        pb, data = prob.SerializeToString(), prob.expression_data()
-        sb = wire.SolverParams(**params).SerializeToString()
-        mod = self.mod
-        mod.set_option("dtype", dtype)
-        mod.set_option("fused_zero_tall_smooth", smooth)
-        mod.set_option("fused_zero_tall", tall)
-        mod.set_option("fused_zero", fused_zero)
-        mod.set_option("fused", fused)
-        mod.profile_reset()
-        mod.profile_enable(True)
-        try:
-            st, x = mod.solve(pb, [], sb, data)
-            tags = mod.profile_dump()
-        finally:
-            mod.profile_enable(False)
-            mod.set_option("fused", "1")
-            mod.set_option("fused_zero", "auto")
-            mod.set_option("fused_zero_tall", "auto")
-            mod.set_option("fused_zero_tall_smooth", "auto")
-            mod.set_option("dtype", "f32")
-        return st, {k: np.frombuffer(v).copy() for k, v in x.items()}, base_counts(tags)
-
-
 @pytest.fixture
 def routes(solve_mod):
-    return Routes(solve_mod)
+    return rs.Routes(solve_mod, ROUTE_OPTIONS)
 
 
-_made = {}
-
-
-def make(kind, shape):
-    """kind "default": the default lambda, 0.1 max|C^T 1/2|; "small": a tenth of it; "hinge":
-    problems.hinge_l1 with lambda = 0.01 max|sum_i C_i|"""
-    key = (kind, shape)
-    if key not in _made:
-        m, n = shape
-        if kind == "default":
-            _made[key] = problems.logreg_l1(m, n)[0]
-        elif kind == "small":
-            C = problems.logreg_l1(m, n)[1]["C"]
-            _made[key] = problems.logreg_l1(m, n, lam=0.01 * np.abs(C.T.dot(np.full(m, 0.5))).max())[0]
-        else:
-            assert kind == "hinge"
-            C = problems.hinge_l1(m, n)[1]["C"]
-            _made[key] = problems.hinge_l1(m, n, lam=0.01 * np.abs(C.sum(axis=0)).max())[0]
-    return _made[key]
-
-
-_oracle = {}
-
-
-def oracle(kind, shape, **params):
-    """the CPU oracle's solve of one problem, computed once per module"""
-    key = (kind, shape, tuple(sorted(params.items())))
-    if key not in _oracle:
-        prob = make(kind, shape)
-        st, x = orc.solve(prob.SerializeToString(), [], wire.SolverParams(**params).SerializeToString(),
-                          prob.expression_data())
-        _oracle[key] = (status(st), {k: np.frombuffer(v).copy() for k, v in x.items()})
-    return _oracle[key]
-
-
-def assert_close(x, xo, dtype):
-    tol = dict(rtol=1e-6, atol=1e-8) if dtype == "f64" else dict(rtol=5e-3, atol=5e-3)
-    assert sorted(x) == sorted(xo)
-    for k in xo:
-        print(k, "max |gpu - oracle| %.3g, max |oracle| %.3g" % (np.abs(x[k] - xo[k]).max(), np.abs(xo[k]).max()))
-    for k in xo:
-        np.testing.assert_allclose(x[k], xo[k], err_msg=k, **tol)
-
-
-def assert_matches_oracle(st, x, so, xo, dtype):
-    sg = status(st)
-    print("gpu: state %d at %d, r %.6g eps %.6g | oracle: state %d at %d, r %.6g eps %.6g" % (
-        sg.state, sg.num_iterations, sg.residuals.r_norm, sg.residuals.epsilon_primal,
-        so.state, so.num_iterations, so.residuals.r_norm, so.residuals.epsilon_primal))
-    assert sg.state == so.state and sg.num_iterations == so.num_iterations
-    assert_close(x, xo, dtype)
+# kind "default": the default lambda, 0.1 max|C^T 1/2|; "small": a tenth of it; "hinge":
+# problems.hinge_l1 with lambda = 0.01 max|sum_i C_i|
+make = rs.memoised({
+    "default": lambda m, n: problems.logreg_l1(m, n)[0],
+    "small": lambda m, n: problems.logreg_l1(m, n, lam=0.01 * rs.lam_scale("logreg_l1", m, n))[0],
+    "hinge": lambda m, n: problems.hinge_l1(m, n, lam=0.01 * rs.lam_scale("hinge_l1", m, n))[0],
+})
+oracle = rs.oracle_of(make)
 
 
 def assert_route_counts(c, count, shape):
@@ -157,18 +73,11 @@ def assert_route_counts(c, count, shape):
 
 
 def assert_route(c, st, shape):
-    assert_route_counts(c, sweeps(st), shape)
+    assert_route_counts(c, rs.sweeps(st), shape)
 
 
 def assert_generic(c):
     assert not route_tags(c), route_tags(c)
-
-
-def assert_same_bytes(st, x, st0, x0):
-    assert (status(st).state, status(st).num_iterations) == (status(st0).state, status(st0).num_iterations)
-    assert sorted(x) == sorted(x0)
-    for k in x0:
-        assert x[k].tobytes() == x0[k].tobytes(), k
 
 
 # ---- 1. fixed 60 sweeps, every variable against the oracle -----------------------------------------
@@ -200,7 +109,7 @@ def test_sixty_sweeps_match_the_oracle(routes, kind, shape, dtype):
     assert abs(z.min() - zlo) <= 0.1 * zlo + 0.005 and abs(z.max() - zhi) <= 0.01 * zhi
     st, x, c = routes.solve(make(kind, shape), dtype, **FIXED)
     assert_route(c, st, shape)
-    assert_matches_oracle(st, x, so, xo, dtype)
+    rs.assert_matches_oracle(st, x, so, xo, dtype)
 
 
 # ---- 2. default stopping rule -------------------------------------------------------------------------
@@ -217,7 +126,7 @@ def test_stops_with_the_oracle(routes, shape, dtype, stop, ratio):
     assert so.residuals.s_norm <= 0.5 * so.residuals.epsilon_dual
     st, x, c = routes.solve(make("default", shape), dtype)
     assert_route(c, st, shape)
-    assert_matches_oracle(st, x, so, xo, dtype)
+    rs.assert_matches_oracle(st, x, so, xo, dtype)
 
 
 # ---- 3. fused against generic, f64 --------------------------------------------------------------------
@@ -230,7 +139,7 @@ def test_fused_equals_generic_to_rounding_f64(routes):
     st0, x0, c0 = routes.solve(prob, "f64", "0", **FIXED)
     assert_route(c, st, shape)
     assert_generic(c0)
-    assert status(st).num_iterations == status(st0).num_iterations == 60
+    assert rs.status(st).num_iterations == rs.status(st0).num_iterations == 60
     assert sorted(x) == sorted(x0) == KEYS
     for k in x0:
         diff, ref = np.abs(x[k] - x0[k]).max(), np.abs(x0[k]).max()
@@ -240,54 +149,18 @@ def test_fused_equals_generic_to_rounding_f64(routes):
 
 
 # ---- 4. sweep boundaries and warm start -------------------------------------------------------------
-class Handle(object):
-    """a solver handle on the route, profiled, with the options put back at the end"""
-
-    def __init__(self, mod, prob, dtype, sp):
-        self.mod, self.prob, self.dtype, self.sp = mod, prob, dtype, sp
-
-    def __enter__(self):
-        mod = self.mod
-        mod.set_option("dtype", self.dtype)
-        mod.set_option("fused_zero_tall", "1")
-        mod.set_option("fused_zero_tall_smooth", "1")
-        self.s = mod.Solver(self.prob.SerializeToString(), self.sp.SerializeToString(), self.prob.expression_data())
-        mod.profile_reset()
-        mod.profile_enable(True)
-        return self.s
-
-    def __exit__(self, *exc):
-        mod = self.mod
-        mod.profile_enable(False)
-        self.s.close()
-        mod.set_option("fused_zero_tall_smooth", "auto")
-        mod.set_option("fused_zero_tall", "auto")
-        mod.set_option("dtype", "f32")
-
-
-def run_handle(mod, prob, dtype, splits, **params):
-    with Handle(mod, prob, dtype, wire.SolverParams(**params)) as s:
-        s.init()
-        for part in splits:
-            assert s.run(part) == part
-        c = base_counts(mod.profile_dump())
-        st, x = s.result()
-    return st, {k: np.frombuffer(v).copy() for k, v in x.items()}, c
-
-
 @pytest.mark.parametrize("dtype", ["f32", "f64"])
 def test_a_solve_can_stop_after_any_sweep(solve_mod, dtype):
     """the head the sample kernel carries from one sweep to the next survives the end of a run call"""
     shape = (601, 256)
     prob = make("default", shape)
     params = dict(max_iterations=1000, abs_tol=0.0, rel_tol=0.0)
-    st_a, xa, ca = run_handle(solve_mod, prob, dtype, [30], **params)
-    st_b, xb, cb = run_handle(solve_mod, prob, dtype, [1, 7, 22], **params)
+    st_a, xa, ca = rs.run_handle(solve_mod, prob, dtype, [30], ON, **params)
+    st_b, xb, cb = rs.run_handle(solve_mod, prob, dtype, [1, 7, 22], ON, **params)
     assert_route_counts(ca, 30, shape)
     assert_route_counts(cb, 30, shape)
     assert sorted(xa) == sorted(xb) == KEYS
-    for k in xa:
-        assert xa[k].tobytes() == xb[k].tobytes(), k
+    rs.assert_same_arrays(xa, xb)
 
 
 @pytest.mark.parametrize("dtype", ["f32", "f64"])
@@ -297,26 +170,26 @@ def test_warm_start_takes_the_state_over(solve_mod, dtype):
     shape = (601, 256)
     prob = make("default", shape)
     sp = wire.SolverParams(warm_start=True, max_iterations=30, abs_tol=0.0, rel_tol=0.0)
-    with Handle(solve_mod, prob, dtype, sp) as s:
+    with rs.handle(solve_mod, prob, dtype, sp, **ON) as s:
         s.init()
         s.run(-1)
         s.init()
         s.run(-1)
-        c = base_counts(solve_mod.profile_dump())
+        c = rs.base_counts(solve_mod.profile_dump())
         st, x = s.result()
     assert_route_counts(c, 60, shape)
     osolver = orc.create_solver(wire.Problem.FromString(prob.SerializeToString()), dict(prob.expression_data()), sp)
     osolver.solve()
     xo = osolver.solve()
-    assert status(st).num_iterations == osolver.status.num_iterations == 30
-    x = {k: np.frombuffer(v) for k, v in x.items()}
+    assert rs.status(st).num_iterations == osolver.status.num_iterations == 30
+    x = rs.arrays(x)
     xo = {k: np.asarray(xo(k), dtype=np.float64).ravel() for k in x}
     # the second solve went on from the first: in the oracle it is not the cold solve's iterate,
     # by far more than the tolerances (1.84 in z)
     cold = oracle("default", shape, max_iterations=30, abs_tol=0.0, rel_tol=0.0)[1]
     print("oracle: max |warm - cold| in z %.3g" % np.abs(xo["var:z"] - cold["var:z"]).max())
     assert np.abs(xo["var:z"] - cold["var:z"]).max() > 0.1
-    assert_close(x, xo, dtype)
+    rs.assert_close(x, xo, dtype)
 
 
 # ---- 5. determinism ------------------------------------------------------------------------------------
@@ -329,8 +202,7 @@ def test_two_solves_return_the_same_bytes(routes, dtype):
     assert_route(c1, st1, shape)
     assert_route(c2, st2, shape)
     assert sorted(x1) == sorted(x2) == KEYS
-    for k in x1:
-        assert x1[k].tobytes() == x2[k].tobytes(), k
+    rs.assert_same_arrays(x1, x2)
 
 
 # ---- 6. what keeps the generic path ---------------------------------------------------------------------
@@ -351,7 +223,7 @@ def test_fall_backs_are_the_generic_path(routes, shape, smooth, tall, fused, fus
     st0, x0, c0 = routes.solve(prob, "f32", "0", "1", "1", "auto", **params)
     assert_generic(c)
     assert_generic(c0)
-    assert_same_bytes(st, x, st0, x0)
+    rs.assert_same_bytes(st, x, st0, x0)
 
 
 def test_the_option_leaves_tall_hinge_alone(routes):
@@ -360,9 +232,9 @@ def test_the_option_leaves_tall_hinge_alone(routes):
     st1, x1, c1 = routes.solve(prob, "f32", "1", max_iterations=30)
     st0, x0, c0 = routes.solve(prob, "f32", "0", max_iterations=30)
     for c, st in ((c1, st1), (c0, st0)):
-        assert c.get("zero_tall", 0) == c.get("zero_tall_cols", 0) == sweeps(st), route_tags(c)
+        assert c.get("zero_tall", 0) == c.get("zero_tall_cols", 0) == rs.sweeps(st), route_tags(c)
         assert route_tags(c) == ["zero_tall", "zero_tall_cols"]
-    assert_same_bytes(st1, x1, st0, x0)
+    rs.assert_same_bytes(st1, x1, st0, x0)
 
 
 def test_auto_takes_the_route_from_the_measured_floor(routes):
@@ -373,7 +245,7 @@ def test_auto_takes_the_route_from_the_measured_floor(routes):
     st1, x1, c1 = routes.solve(make("default", shape), "f32", "1", max_iterations=30)
     assert_route(c, st, shape)
     assert_route(c1, st1, shape)
-    assert_same_bytes(st, x, st1, x1)
+    rs.assert_same_bytes(st, x, st1, x1)
 
 
 # ---- 7. batch ---------------------------------------------------------------------------------------
@@ -383,37 +255,18 @@ def test_batch_members_are_their_own_solves(solve_mod):
     m, n = 601, 256
     scale = np.abs(problems.logreg_l1(m, n)[1]["C"].T.dot(np.full(m, 0.5))).max()
     probs = [problems.logreg_l1(m, n, lam=f * scale)[0] for f in (0.1, 0.05, 0.02)]
-    data = {}
-    for p in probs:
-        data.update(p.expression_data())
-    pbs = [p.SerializeToString() for p in probs]
+    pbs, data = [p.SerializeToString() for p in probs], rs.union_data(probs)
     sb = wire.SolverParams(max_iterations=60).SerializeToString()
     # in the oracle the second member stops by the rule at 40, the other two run into the cap
-    ost = [status(orc.solve(pb, [], sb, data)[0]) for pb in pbs]
+    ost = [rs.status(orc.solve(pb, [], sb, data)[0]) for pb in pbs]
     assert [(s.state, s.num_iterations) for s in ost] == [
         (wire.SolverStatus.MAX_ITERATIONS_REACHED, 60), (wire.SolverStatus.OPTIMAL, 40),
         (wire.SolverStatus.MAX_ITERATIONS_REACHED, 60)]
-    solve_mod.set_option("fused_zero_tall", "1")
-    solve_mod.set_option("fused_zero_tall_smooth", "1")
-    solve_mod.profile_reset()
-    solve_mod.profile_enable(True)
-    try:
-        batch = solve_mod.solve_batch(pbs, None, sb, data)
-        cb = base_counts(solve_mod.profile_dump())
-        solve_mod.profile_enable(False)
+    with rs.options(solve_mod, **ON):
+        batch, tags = rs.profiled(solve_mod, lambda: solve_mod.solve_batch(pbs, None, sb, data))
         single = [solve_mod.solve(pb, [], sb, data) for pb in pbs]
-    finally:
-        solve_mod.profile_enable(False)
-        solve_mod.set_option("fused_zero_tall_smooth", "auto")
-        solve_mod.set_option("fused_zero_tall", "auto")
-    assert_route_counts(cb, sum(sweeps(st) for st, _ in batch), (m, n))
+    cb = rs.base_counts(tags)
+    assert_route_counts(cb, sum(rs.sweeps(st) for st, _ in batch), (m, n))
     assert not [t for t in cb if t.startswith("batch_zero")], sorted(cb)
     assert len(batch) == len(single) == 3
-    for k, ((stb, xb), (sts, xs)) in enumerate(zip(batch, single)):
-        a, s = status(stb), status(sts)
-        assert a.state == s.state and a.num_iterations == s.num_iterations, (k, a, s)
-        for f in ("r_norm", "s_norm", "epsilon_primal", "epsilon_dual"):
-            assert getattr(a.residuals, f) == getattr(s.residuals, f), (k, f)
-        assert sorted(xb) == sorted(xs)
-        for v in xs:
-            assert np.array_equal(np.frombuffer(xb[v]), np.frombuffer(xs[v])), (k, v)
+    rs.assert_identical(batch, single)

@@ -16,17 +16,12 @@ import scipy.sparse as sp
 from epsilon_amd import ir, problems, wire
 from epsilon_amd.wire import ProxFunction
 from oracle import epsilon_oracle as orc
+from tests import route_support as rs
 
 pytestmark = pytest.mark.gpu
 
 TOL = {"f64": dict(rtol=1e-10, atol=1e-11), "f32": dict(rtol=2e-4, atol=2e-5)}
-
-
-@pytest.fixture(params=["f64", "f32"])
-def dtype(request, solve_mod):
-    solve_mod.set_option("dtype", request.param)
-    yield request.param
-    solve_mod.set_option("dtype", "f32")
+dtype = rs.dtype_fixture(("f64", "f32"))
 
 
 def oracle_map(lmap):

@@ -13,18 +13,13 @@ import pytest
 from epsilon_amd import ir, wire
 from epsilon_amd.wire import ProxFunction
 from oracle import epsilon_oracle as orc
+from . import route_support as rs
 from .test_oracle_prox_more import project_sum_largest_epigraph
 
 pytestmark = pytest.mark.gpu
 
 N = 10
-
-
-@pytest.fixture(params=["f64", "f32"])
-def dtype(request, solve_mod):
-    solve_mod.set_option("dtype", request.param)
-    yield request.param
-    solve_mod.set_option("dtype", "f32")
+dtype = rs.dtype_fixture(("f64", "f32"))
 
 
 def tol_for(dtype, f64=1e-8, f32=5e-4):

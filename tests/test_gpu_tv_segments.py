@@ -18,16 +18,11 @@ torch = pytest.importorskip("torch")
 from epsilon_amd import ir, problems, wire  # noqa: E402
 from epsilon_amd.wire import ProxFunction  # noqa: E402
 from oracle import epsilon_oracle as orc  # noqa: E402
+from tests import route_support as rs  # noqa: E402
 from tests.test_tv_segments_args import dykstra_tv2d, tv_slices  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(params=["f64", "f32"])
-def dtype(request, solve_mod):
-    solve_mod.set_option("dtype", request.param)
-    yield request.param
-    solve_mod.set_option("dtype", "f32")
+dtype = rs.dtype_fixture(("f64", "f32"))
 
 
 def as_dtype(V, dtype):
