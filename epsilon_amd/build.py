@@ -24,6 +24,7 @@ DEVICE_SOURCES = [("kernels_vec.hip", ["-ffp-contract=off"]),
                   ("kernels_fused.hip", ["-ffp-contract=off"]),
                   ("kernels_fused_batch.hip", ["-ffp-contract=off"]),
                   ("kernels_fused_wide.hip", ["-ffp-contract=off"]),
+                  ("kernels_fused_tall.hip", ["-ffp-contract=off"]),
                   ("kernels_peer.hip", ["-ffp-contract=off"]),
                   ("kernels_gemv.hip", []),
                   ("kernels_gemv_multi.hip", []),

@@ -1,5 +1,5 @@
 // The fused routes (fused_route.h): the lasso structure with its sharded / peer, whitened,
-// matrix-variable and wide forms and the batched solves that run on it, the ZERO-term structure,
+// matrix-variable, wide and tall forms and the batched solves that run on it, the ZERO-term structure,
 // and the lasso structure in two-block form.
 #include "fused_route.h"
 
@@ -124,10 +124,10 @@ std::vector<BlockVector*> Homes(const MultiBlockParts& a) {
 int BatchWideMin();  // (with the batched solves below)
 
 // The indices of the options' words (options.cc).  "fused" (off with a leading 0), "fused_zero",
-// "fused_zero_tall", "fused_zero_tall_smooth", "fused_matrix" and "fused_resident" are read at
-// every Init, "batch_wide" and "batch_zero_tall" per batch ("1" sends eligible groups to the wide
+// "fused_zero_tall", "fused_zero_tall_smooth", "fused_tall", "fused_matrix" and "fused_resident" are
+// read at every Init, "batch_wide" and "batch_zero_tall" per batch ("1" sends eligible groups to the wide
 // route / lets the tall ZERO-term members of a batch form groups).
-enum ZeroTallMode { kZeroTallOff, kZeroTallOn, kZeroTallAuto };  // of either tall option
+enum ZeroTallMode { kZeroTallOff, kZeroTallOn, kZeroTallAuto };  // of every tall option
 enum MatrixRoute { kMatrixOff, kMatrixPass, kMatrixWide, kMatrixAuto };
 
 // What the Infinity Cache holds of lines loaded with the default policy before re-reads start to
@@ -177,6 +177,19 @@ constexpr int64_t kZeroTallAutoMinCols = 256;
 // is "0".
 // Measured: 3.5 x at n = 512, the first cell, and no cell above it below 2.4 x.
 constexpr int64_t kZeroTallSmoothAutoMinCols = 512;
+
+// Tall lasso (more rows than columns: the order of the least-squares prox's block LDL^T ends in the
+// variable) on the fused sweep (LassoRoute with `tall`).  Below this many columns
+// the solve keeps the generic operator path whatever the option says (a constant: no crossover was
+// measured below it).
+constexpr int64_t kLassoTallMinCols = 256;
+// The floor of "auto" ("fused_tall"): the smallest n of the 4n x n ladder of bench_tall.py from
+// which every cell measured at least 1.05 x the generic path of the same build (the rule of
+// kZeroTallAutoMinCols; DESIGN.md 4: 5.0 x at n = 256, the first cell, and no cell above it below
+// 4.7 x); 0 would mean that no cell got there and "auto" is "0".
+constexpr int64_t kLassoTallAutoMinCols = 256;
+// The first word of a tall lasso member's batch key (the others begin with the pass's chain, 0 to 5).
+constexpr uint64_t kTallLassoKey = 0x7a111a550;
 
 // The bits of a scalar, as a word of a batch key.
 uint64_t Bits(double v) {
@@ -266,6 +279,8 @@ struct BatchRoute : FusedRoute {
   bool whiten = false;       // the lasso route alone: the pass streams Ahat = X A, w holds X p (EnableWhiten)
   k::LassoFusedArgs pass;    // the state vectors, and what the pass and a batch read of the rest
   k::FusedResidency res;     // the matrix's share that stays in the Infinity Cache
+  bool tall_cols = false;    // the tall lasso route: no pass; w, p, inv are n-long / of order n, pass.inst
+                             // is LassoTallCols' record, and a group runs on RunTallGroup
 
   // The key of the group a fresh solve on this route can join; false: it is solved by itself.
   // `tall_groups`: the option "batch_zero_tall" of this batch.
@@ -332,6 +347,12 @@ struct BatchRoute : FusedRoute {
 // with a0 = 1 and no constant.  The sweep is then: one fused pass over A (back substitution of
 // this sweep, elementwise chain, forward substitution of the next sweep), a partial-sum
 // reduction (+ the all-reduce when sharded) and the apply of the cached inverse.
+//
+// Tall A (`tall`): the same terms and tie with the least-squares prox's block LDL^T
+// in the order [constraint, arg, var].  The prox is then x0 = Dinv(var) (v0 - c) with the constant
+// c = L(var, arg) rhs_arg, so a sweep never reads A: the tile launch of the packed inverse on
+// r = v0 - c and the cols kernel (the tiles' sum, the chain from x0 on, the next r) from n = 1024,
+// the dense apply and the cols kernel below.  One GPU, vector variables, f32 and f64.
 struct LassoRoute final : BatchRoute {
   LeastSquaresDesc ls;
   ScaledZoneDesc sz;
@@ -356,6 +377,8 @@ struct LassoRoute final : BatchRoute {
   std::vector<k::LassoInstance> members;
   DVec table;              // their descriptors on the device (LassoBatchUpload)
   WideSweep ws;
+  bool tall = false;       // no pass, m > n
+  DVec crhs;               // tall: c = L(var, arg) rhs_arg (empty: no rhs)
 
   // The matrix's resident share for a sweep of `count` members on it (`into`: the pass's record,
   // BuildPass): each has its partials (written and re-read: the same lines), six state vectors, p
@@ -363,18 +386,20 @@ struct LassoRoute final : BatchRoute {
   // stream everything; so does "auto" for more than one member (a batch, a matrix variable): the
   // batched pass has not been timed with a share.
   k::FusedResidency Residency(int64_t count, k::LassoFusedArgs* into) const {
-    if (sharded || use_peer || wide || ShardSpec::Get().active()) return k::FusedResidency();
+    if (sharded || use_peer || wide || tall || ShardSpec::Get().active()) return k::FusedResidency();
     return ResidentShare(m, n, dt, count * (static_cast<int64_t>(grid) * m + 6 * n + 2 * m) + (whiten ? 0 : m * m),
                          /*auto_on=*/count == 1 && cols == 1, into);
   }
   k::FusedResidency Residency(int64_t count) const override { return Residency(count, nullptr); }
 
-  bool Enable(const MultiBlockParts& a) {
+  // `tall_mode`: the option "fused_tall"; under "auto" the measured floor applies
+  bool Enable(const MultiBlockParts& a, int tall_mode) {
     if (opt::Is0(opt::kFused) || a.prox.size() != 2 || a.num_constraints != 1 || !a.b.data().empty()) return false;
     const ShardSpec& sh = ShardSpec::Get();
     // consensus form: the threshold step averages over the ranks, which the fused pass does not
     if (sh.active() && sh.consensus_terms()) return false;
     if (!a.prox[0]->DescribeLeastSquares(&ls)) return false;
+    if (ls.tall && tall_mode == kZeroTallOff) return false;
     cols = ls.cols;
     const int matrix_mode = cols > 1 ? opt::Word(opt::kFusedMatrix) : kMatrixAuto;
     if (cols > 1 && (matrix_mode == kMatrixOff || sh.active())) return false;
@@ -395,30 +420,18 @@ struct LassoRoute final : BatchRoute {
     if ((sz.alpha_vec.n > 0 && sz.alpha_vec.dt != dt) || (sz.beta_vec.n > 0 && sz.beta_vec.dt != dt)) return false;
     const std::string ck = affine::constraint_key(0);
     if (ls.constraint_key != ck || sz.constraint_key != ck || a.A.data().size() != 2) return false;
-    const DenseMatrixImpl& L = *ls.L_arg_var;
-    if (L.trans()) return false;
+    const DenseMatrixImpl& L = *ls.L_arg_var;  // (tall: L(var, arg), trans() set: its buffer is A, m x n)
+    if (L.trans() != ls.tall) return false;
     m = L.rows();
     n = L.cols();
     const int64_t nx = n * cols;  // entries of the variable (a matrix variable: column c at c * n)
     double a0 = 0;
     if (!ConsensusTie(a.A, ck, ls.var_key, sz.var_key, nx, &a0, &a1) || a0 != 1.0) return false;
+    if (ls.tall) return EnableTall(a, tall_mode, ck);
     if (!k::LassoFusedSupported(m, n, L.data(), L.rows())) return false;
     if (ls.rhs_arg.n != 0 && ls.rhs_arg.n != m * cols) return false;
     if (cols > 1 && !ChooseMatrixRoute(matrix_mode)) return false;
-    // the six state vectors are slices of ONE buffer, so that a residual check can snapshot the
-    // iterates with a single copy (pipelined checks, Solver::Run)
-    const int64_t npad = (nx + 63) / 64 * 64;
-    state_all = DVec::Zeros(6 * npad, dt);
-    snapshot = DVec::Empty(6 * npad, dt);
-    norm_work = DVec::Zeros(64 * 5 + 1, F64);
-    a.y_prev.resize(2);
-    std::vector<StateSlice> views = {{&a.x[0], ls.var_key}, {&a.x[1], sz.var_key}, {&a.y[0], ck},
-                                     {&a.y[1], ck},         {&a.u, ck},            {&a.y_prev[1], ck}};
-    views[5].take = false;
-    for (size_t q = 0; q < views.size(); ++q) views[q].v = state_all.Slice(static_cast<int64_t>(q) * npad, nx);
-    k::ConsensusState& s = pass.inst.state;
-    s.copy = views[0].v, s.var = views[1].v, s.y_zero = views[2].v, s.y_term = views[3].v, s.u = views[4].v;
-    s.y_term_prev = views[5].v;
+    const std::vector<StateSlice> views = StateViews(a, ck, nx);
     grid = k::LassoFusedGrid(m, n, dt);
     // a matrix variable: column c's p and w at c * m (the wide route's instance-major panels,
     // whole panels of 64), its partials at c * grid * m
@@ -462,6 +475,64 @@ struct LassoRoute final : BatchRoute {
     BuildPass();
     AdoptState(views, Homes(a));
     ForwardFromState();
+    return true;
+  }
+
+  // The six state vectors (x0, x1, y0, y1, u, y1prev; `nx` entries each) as slices of ONE buffer, so
+  // that a residual check can snapshot the iterates with a single copy (pipelined checks,
+  // Solver::Run), in the pass's record and as the table AdoptState takes.
+  std::vector<StateSlice> StateViews(const MultiBlockParts& a, const std::string& ck, int64_t nx) {
+    const int64_t npad = (nx + 63) / 64 * 64;
+    state_all = DVec::Zeros(6 * npad, dt);
+    snapshot = DVec::Empty(6 * npad, dt);
+    norm_work = DVec::Zeros(64 * 5 + 1, F64);
+    a.y_prev.resize(2);
+    std::vector<StateSlice> views = {{&a.x[0], ls.var_key}, {&a.x[1], sz.var_key}, {&a.y[0], ck},
+                                     {&a.y[1], ck},         {&a.u, ck},            {&a.y_prev[1], ck}};
+    views[5].take = false;
+    for (size_t q = 0; q < views.size(); ++q) views[q].v = state_all.Slice(static_cast<int64_t>(q) * npad, nx);
+    k::ConsensusState& s = pass.inst.state;
+    s.copy = views[0].v, s.var = views[1].v, s.y_zero = views[2].v, s.y_term = views[3].v, s.u = views[4].v;
+    s.y_term_prev = views[5].v;
+    return views;
+  }
+
+  // The tall form, after the gates that both forms share (Enable).  Any m > n and any n from the
+  // floor up, odd ones included: the sweep never streams A, so LassoFusedSupported does not apply.
+  bool EnableTall(const MultiBlockParts& a, int mode, const std::string& ck) {
+    const DenseMatrixImpl& L = *ls.L_arg_var;
+    const DenseMatrixImpl& D = *ls.Dinv_arg;
+    if (ShardSpec::Get().active() || n < kLassoTallMinCols || m <= n) return false;
+    if (mode == kZeroTallAuto && (kLassoTallAutoMinCols == 0 || n < kLassoTallAutoMinCols)) return false;
+    if (L.dtype() != dt || D.dtype() != dt || D.rows() != n || D.cols() != n) return false;
+    auto fits = [&](const DVec& v, int64_t len) { return v.n == 0 || (v.n == len && v.dt == dt); };
+    if (!fits(ls.rhs_arg, m) || !fits(sz.alpha_vec, n) || !fits(sz.beta_vec, n)) return false;
+    tall = tall_cols = true;
+    const std::vector<StateSlice> views = StateViews(a, ck, n);
+    p = DVec::Zeros(n, dt);  // r, the apply's input
+    w = DVec::Zeros(n, dt);  // the dense apply's output (below the packed floor)
+    inv.Init(ls.Dinv_arg, n, p, w, a.shared_cache);
+    // c at every Init: parameters re-bind the rhs (nothing here is keyed on A)
+    if (ls.rhs_arg.n != 0) {
+      crhs = DVec::Empty(n, dt);
+      ProfScope prof("lasso_tall_rhs", m, n);
+      L.Apply(1.0, ls.rhs_arg, 0.0, crhs);
+    }
+    k::LassoInstance& s = pass.inst;
+    s.w = w;
+    s.p = p;
+    s.tpart = inv.work;  // the tile partials (empty below the packed floor)
+    s.rhs = crhs;
+    s.kappa = s.pkappa = D.scale();  // x0 = scale * (tiles' sum), SymvPacked's alpha
+    s.zone = ZoneOf(sz, a1);
+    AdoptState(views, Homes(a));
+    // r of the first sweep from the adopted state: v0 - c
+    const k::ConsensusState& st = s.state;
+    k::Copy(p, st.u);
+    k::Axpby(p, -1.0, st.y_zero, 1.0);
+    k::Axpby(p, -1.0, st.y_term, 1.0);
+    k::Axpby(p, 1.0, st.y_zero, 1.0);
+    if (crhs.n != 0) k::Axpby(p, -1.0, crhs, 1.0);
     return true;
   }
 
@@ -693,7 +764,12 @@ struct LassoRoute final : BatchRoute {
   }
 
   void Sweep() override {
-    if (cols > 1) {
+    if (tall) {
+      const bool tiles = inv.packed.n > 0;  // two launches: the tiles, then their sum and the chain
+      if (tiles) k::SymvPackedTiles(n, inv.packed, p, inv.work);
+      else inv.Apply();
+      k::LassoTallCols(n, pass.inst, tiles);
+    } else if (cols > 1) {
       MatrixSweep();
     } else if (use_peer) {
       pass.epoch = Runtime::Get().peer()->view().epoch;
@@ -722,7 +798,8 @@ struct LassoRoute final : BatchRoute {
     const k::ConsensusState& s = pass.inst.state;
     k::LassoFusedNorms(s.u, s.y_zero, s.y_term, s.y_term_prev,
                        sharded ? rt.ShardSlotPtr(norm_slot) : rt.SlotPtr(norm_slot), norm_work,
-                       use_peer ? rt.peer()->device_error_word() : nullptr);
+                       use_peer ? rt.peer()->device_error_word() : nullptr,
+                       tall ? "lasso_tall_norms" : "lasso_fused_norms");
   }
   Check FinishCheck() override {
     Runtime& rt = Runtime::Get();
@@ -758,8 +835,17 @@ struct LassoRoute final : BatchRoute {
   // ---- batched solves (RunFusedBatches) ---------------------------------------------------------
   // The key of the group a fresh solve on this route can join (same data matrix, inverse, dtype,
   // shape and schedule); false: its pass is none the batched one mirrors.
+  // Tall: the same inverse with its packed copy (n >= 1024), n, the dtype and the schedule; lambda,
+  // the zone's parameters and b are per member.
   bool BatchKey(const pb::SolverParams& params, bool, std::vector<uint64_t>* key) const override {
     if (use_peer || ShardSpec::Get().active()) return false;
+    if (tall) {
+      if (inv.packed.n == 0) return false;
+      *key = {kTallLassoKey, reinterpret_cast<uintptr_t>(inv.D->data().data()), Bits(inv.D->scale()),
+              reinterpret_cast<uintptr_t>(inv.packed.data()), static_cast<uint64_t>(n), static_cast<uint64_t>(dt),
+              static_cast<uint64_t>(params.max_iterations), static_cast<uint64_t>(params.epoch_iterations)};
+      return true;
+    }
     if (cols > 1) return false;  // a matrix variable is a batch of its own: it runs alone
     const DenseMatrixImpl& L = *ls.L_arg_var;
     if (L.dtype() != dt || k::LassoBatchWidth(m, n, dt) == 0) return false;
@@ -1211,7 +1297,8 @@ std::unique_ptr<FusedRoute> RecogniseMultiBlockRoute(const MultiBlockParts& part
   const bool zero = opt::Word(opt::kFusedZero) != 0;  // (read first: a bad value is an error whatever the problem)
   const int tall = opt::Word(opt::kFusedZeroTall);
   const int tall_smooth = opt::Word(opt::kFusedZeroTallSmooth);
-  if (auto r = Recognise<LassoRoute>(parts)) return r;
+  const int lasso_tall = opt::Word(opt::kFusedTall);
+  if (auto r = Recognise<LassoRoute>(parts, lasso_tall)) return r;  // fat, then tall
   if (!zero) return nullptr;
   return Recognise<ZeroRoute>(parts, tall, tall_smooth);  // fat, then tall
 }
@@ -1325,6 +1412,39 @@ void RunPassGroup(const Group& g) {
   });
 }
 
+// A group on the tall lasso route: per sweep ONE tile launch of the packed inverse
+// for all active members (the tile is read once) and ONE cols launch whose grid row b is member b's
+// own launch on its own record, so its iterates are the single solve's bit for bit.
+void RunTallGroup(const Group& g) {
+  const double t0 = Now();
+  const BatchRoute& lead = *g[0].route;
+  SetCurrentDType(lead.dt);
+  const int K = static_cast<int>(g.size());
+  const int64_t n = lead.n;
+  DVec work = DVec::Empty(K * k::SymvWorkspace(n), lead.dt);
+  std::vector<int> active(K);
+  for (int i = 0; i < K; ++i) active[i] = i;
+  DVec table;
+  auto upload = [&] {
+    std::vector<const k::LassoInstance*> v;
+    for (int i : active) {
+      EPS_CHECK(g[i].route->tall_cols && g[i].route->n == n && g[i].route->inv.packed.data() == lead.inv.packed.data());
+      v.push_back(&g[i].route->pass.inst);
+    }
+    k::LassoBatchUpload(v, lead.dt, &table);
+  };
+  upload();
+  auto sweep = [&] {
+    const int count = static_cast<int>(active.size());
+    k::SymvPackedTilesBatch(n, lead.inv.packed, table, count, work);
+    k::LassoTallColsBatch(n, lead.dt, table, count, work);
+  };
+  // the stopped ones are frozen: drop their descriptors
+  RunGroupSchedule(g, t0, &active, sweep, [&](const std::vector<int>&) {
+    if (!active.empty()) upload();
+  });
+}
+
 // Smallest group the wide route takes.  Measured crossovers against the batched pass on MI355X
 // (DESIGN.md 3.8), rounded up to a multiple of 8.
 constexpr int kWideMin = 8;
@@ -1415,8 +1535,10 @@ std::vector<bool> RunFusedBatches(const std::vector<Solver*>& solvers) {
     Group g;
     for (size_t i : idx) g.push_back({solvers[i], routes[i]});
     const BatchRoute& lead = *g[0].route;
-    // the wide kernels run the lasso chain alone
-    if (wide && lead.pass.chain == 0 && static_cast<int>(g.size()) >= BatchWideMin() && lead.dt == F32 &&
+    // a tall lasso group has its own two launches; the wide kernels run the lasso chain alone
+    if (lead.tall_cols)
+      RunTallGroup(g);
+    else if (wide && lead.pass.chain == 0 && static_cast<int>(g.size()) >= BatchWideMin() && lead.dt == F32 &&
         k::LassoWideSupported(lead.m, lead.n, lead.pass.A, lead.pass.lda))
       RunWideGroup(g);
     else

@@ -52,6 +52,11 @@ DVec SymvPack(int64_t n, const DVec& S, int64_t lds);
 void SymvPacked(int64_t n, double alpha, const DVec& P, const DVec& x, double beta, const DVec& y,
                 const DVec* work = nullptr);
 
+// The tile launch of SymvPacked alone: the per-tile partials of P x into `work`
+// (SymvWorkspace(n) values), for a caller whose own kernel sums them in SymvPacked's order
+// (kernels_symv_reduce.h).  Profile tag "symv_packed_tiles".
+void SymvPackedTiles(int64_t n, const DVec& P, const DVec& x, const DVec& work);
+
 // y[r] = alpha * sum_{k < nparts} partial[k*rows + r] + beta*y[r], fixed summation order.
 // `add` (optional) is added to the result afterwards: y = (alpha*sum + beta*y) + add.
 void ReducePartials(int64_t rows, int nparts, const DVec& partial, double alpha, double beta,
@@ -202,8 +207,9 @@ void LassoFusedPass(const LassoFusedArgs& args);
 // out6 = {||y0||^2, ||y1||^2, ||y0 + y1||^2, ||y1 - y1prev||^2, ||u||^2, peer_err ? 1 : 0} (device
 // doubles), one launch; `work`: 64 * 5 + 1 doubles, zero-initialised once (the last double is a
 // ticket counter); `peer_err` (optional): the device-side error word of the peer exchange.
+// `tag`: the launch's profile tag (the tall lasso route's is "lasso_tall_norms").
 void LassoFusedNorms(const DVec& u, const DVec& y0, const DVec& y1, const DVec& y1prev, double* out6,
-                     const DVec& work, const unsigned* peer_err = nullptr);
+                     const DVec& work, const unsigned* peer_err = nullptr, const char* tag = "lasso_fused_norms");
 
 // ---- batched fused pass: instances sharing one data matrix (kernels_fused_batch.hip) ---------
 // One instance of a batched sweep as the kernels read it (device array, compute type T): the
@@ -261,6 +267,25 @@ void ReducePartialsBatch(int64_t m, int nparts, const DVec& table, int count, DT
 // count * SymvWorkspace(m) values.
 void SymvPackedBatch(int64_t m, double alpha, const DVec& P, const DVec& table, int count,
                      const DVec& work);
+// The tile launch of SymvPackedBatch alone (profile tag "batch_symv_packed_tiles"): member b's
+// partials of P p_b at work + b * SymvWorkspace(m).
+void SymvPackedTilesBatch(int64_t m, const DVec& P, const DVec& table, int count, const DVec& work);
+
+// ---- tall lasso sweep: no pass over A (kernels_fused_tall.hip) ------------------
+// The element-wise side of a sweep of the lasso structure whose block LDL^T ends in the dense
+// n x n pivot of the variable (more rows than columns): x0 = Dinv r is all of the least-squares
+// prox that depends on the iterate.  One launch, profile tag "lasso_tall_cols", one workgroup of
+// 256 threads per 128 entries; a thread touches its own entry alone.  Per entry j: x0_j - from
+// `partials`, the tile partials of SymvPackedTiles(n, P, inst.p, inst.tpart) summed in SymvPacked's
+// order and scaled by inst.kappa (bit for bit SymvPacked's output); else read from inst.w, the
+// finished apply - then the lasso chain from x0 on (kernels_fused_chain.h), the six state stores and
+// the next sweep's input inst.p[j] = v0'_j - inst.rhs[j] (rhs: c = L(var, arg) rhs_arg; empty: zero).
+// inst.pkappa and the z fields are not read.
+void LassoTallCols(int64_t n, const LassoInstance& inst, bool partials);
+// `count` members (LassoBatchUpload) in ONE launch, profile tag "batch_lasso_tall_cols": grid row b
+// is member b's own LassoTallCols launch on its own record with its partials at
+// work + b * SymvWorkspace(n) (SymvPackedTilesBatch), so its result is that of its own solve bit for bit.
+void LassoTallColsBatch(int64_t n, DType dt, const DVec& table, int count, const DVec& work);
 
 // ---- wide batched sweep on the f32 matrix instruction (kernels_fused_wide.hip) -----------------
 // A panel is up to kLassoWidePanel f32 instances of one `table` (LassoBatchUpload), slots

@@ -757,7 +757,7 @@ __global__ __launch_bounds__(kBlock) void LassoFusedNormsKernel(
 }  // namespace
 
 void LassoFusedNorms(const DVec& u, const DVec& y0, const DVec& y1, const DVec& y1prev, double* out6,
-                     const DVec& work, const unsigned* peer_err) {
+                     const DVec& work, const unsigned* peer_err, const char* tag) {
   const int64_t n = u.n;
   EPS_CHECK(y0.n == n && y1.n == n && y1prev.n == n && y0.dt == u.dt && y1.dt == u.dt && y1prev.dt == u.dt);
   EPS_CHECK(work.dt == F64 && work.n >= kNormBlocks * 5 + 1);
@@ -766,7 +766,7 @@ void LassoFusedNorms(const DVec& u, const DVec& y0, const DVec& y1, const DVec& 
   if (grid < 1) grid = 1;
   double* partial = work.as<double>();
   unsigned* ticket = reinterpret_cast<unsigned*>(partial + kNormBlocks * 5);  // zero between launches
-  ProfScope prof("lasso_fused_norms", n);
+  ProfScope prof(tag, n);
   if (u.dt == F32)
     hipLaunchKernelGGL(LassoFusedNormsKernel<float>, dim3(static_cast<unsigned>(grid)), dim3(kBlock), 0,
                        Runtime::Get().stream(), n, u.as<float>(), y0.as<float>(), y1.as<float>(),

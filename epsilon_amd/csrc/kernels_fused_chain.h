@@ -124,16 +124,22 @@ template <class T> __device__ inline T ScaledZoneOneT(T xi, T lam, T alpha, T be
 template <class T> struct ChainHeadT {
   T x0, u2, vin;  // x0 = y0; u after "term 1: u += y_1"; the threshold's input B v
 };
-template <class T>
-__device__ inline ChainHeadT<T> ChainHeadOfT(T d, const FusedScalarsT<T>& c, T u, T y0p, T y1p) {
-  // sweep start: u -= y0; u -= y1; then term 0: u += y0       (prox_admm.cc:137-142)
-  const T v0 = ((u - y0p) - y1p) + y0p;
-  const T x0 = c.kappa * d + v0;  // back substitution epilogue: alpha*acc + 1*y
+// sweep start: u -= y0; u -= y1; then term 0: u += y0         (prox_admm.cc:137-142)
+template <class T> __device__ inline T ChainStartT(T u, T y0p, T y1p) { return ((u - y0p) - y1p) + y0p; }
+// From term 0's result x0 on (the tall lasso sweep has it from the inverse apply as it is,
+// kernels_fused_tall.hip).
+template <class T> __device__ inline ChainHeadT<T> ChainHeadFromT(T v0, T x0, const FusedScalarsT<T>& c, T y1p) {
   const T y0 = x0;                // y_0 = A_ x_0 with A_(c0,x) = I
   const T u1 = v0 - y0;           // u -= y_0
   const T u2 = u1 + y1p;          // term 1: u += y_1
   const T vin = c.Bs * u2;        // VectorProx: B v (+ g = 0)      (vector_prox.cc:141)
   return {x0, u2, vin};
+}
+template <class T>
+__device__ inline ChainHeadT<T> ChainHeadOfT(T d, const FusedScalarsT<T>& c, T u, T y0p, T y1p) {
+  const T v0 = ChainStartT<T>(u, y0p, y1p);
+  const T x0 = c.kappa * d + v0;  // back substitution epilogue: alpha*acc + 1*y
+  return ChainHeadFromT<T>(v0, x0, c, y1p);
 }
 // From the threshold's result xz on.  Returns v0' (input of the next sweep's forward pass).
 template <class T>

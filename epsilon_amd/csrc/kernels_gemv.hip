@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "kernels_symv_reduce.h"
 
 namespace eps {
 namespace k {
@@ -408,8 +409,6 @@ void LaunchGemvT(int64_t rows, int64_t cols, double alpha, const T* A, int64_t l
 // row groups with three shuffle steps).  Both land in per-tile partial
 // vectors that SymvReduceKernel adds in a fixed order, so the result is deterministic.
 // ------------------------------------------------------------------------------------------
-constexpr int kSB = 128;
-
 // PACKED: S is the tile-packed copy made by SymvPack - tile `lin` is 128 x 128 values, column-major,
 // contiguous (64 KB in f32), zero-padded at the matrix edge: a workgroup's 64 KB then come out of
 // a few DRAM pages instead of 128 column pieces of 512 bytes each 4 lds bytes apart.
@@ -502,38 +501,8 @@ __global__ __launch_bounds__(kBlock) void SymvTileKernel(int64_t n, const T* __r
   }
 }
 
-// y[r] = alpha * (sum_{J <= I} prow[(I,J)][r] + sum_{I' > I} pcol[(I',I)][r]) + beta * y[r].
-// One workgroup per block of 128 rows; the nb partial vectors of a block are dealt to two
-// half-workgroups (even / odd position in the list), loaded eight at a time, and the two halves
-// are added in a fixed order.
-template <class T>
-__device__ inline void SymvReduceBody(int64_t n, int64_t nb, const T* __restrict__ prow,
-                                      const T* __restrict__ pcol, T alpha, T beta, T* y, int64_t I) {
-  __shared__ T half[kSB];
-  const int off = threadIdx.x & (kSB - 1), grp = threadIdx.x >> 7;  // kSB == 128
-  const int64_t base = I * (I + 1) / 2;
-  auto part = [&](int64_t p) -> const T* {  // p-th partial vector of this block, p < nb
-    return p <= I ? prow + (base + p) * kSB : pcol + (p * (p + 1) / 2 + I) * kSB;
-  };
-  T s = T(0);
-  int64_t p = grp;
-  for (; p + 14 < nb; p += 16) {
-    T v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = part(p + 2 * u)[off];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) s += v[u];
-  }
-  for (; p < nb; p += 2) s += part(p)[off];
-  if (grp == 1) half[off] = s;
-  __syncthreads();
-  const int64_t r = I * kSB + off;
-  if (grp == 0 && r < n) {
-    const T tot = s + half[off];
-    y[r] = (beta == T(0)) ? alpha * tot : alpha * tot + beta * y[r];
-  }
-}
-
+// y[r] = alpha * (sum_{J <= I} prow[(I,J)][r] + sum_{I' > I} pcol[(I',I)][r]) + beta * y[r]:
+// SymvReduceBody (kernels_symv_reduce.h), one workgroup per block of 128 rows.
 template <class T>
 __global__ __launch_bounds__(kBlock) void SymvReduceKernel(int64_t n, int64_t nb,
                                                            const T* __restrict__ prow,
@@ -574,6 +543,7 @@ void LaunchSymv(int64_t n, double alpha, const T* S, int64_t lds, const T* x, do
   hipLaunchKernelGGL((SymvTileKernel<T, PACKED>), dim3(static_cast<unsigned>(ntiles)), dim3(kBlock), 0, s,
                      n, S, lds, x, prow, pcol);
   static_assert(kSB == 128 && kBlock == 256, "SymvReduceKernel geometry");
+  if (y == nullptr) return;  // the tile launch alone: the caller's own kernel sums the partials
   hipLaunchKernelGGL((SymvReduceKernel<T>), dim3(static_cast<unsigned>(nb)), dim3(kBlock), 0, s, n,
                      nb, prow, pcol, T(alpha), T(beta), y);
 }
@@ -629,6 +599,16 @@ void SymvPacked(int64_t n, double alpha, const DVec& P, const DVec& x, double be
   void* wp = work ? work->data() : nullptr;
   if (P.dt == F32) LaunchSymv<float, true>(n, alpha, P.as<float>(), kSB, x.as<float>(), beta, y.as<float>(), wp);
   else LaunchSymv<double, true>(n, alpha, P.as<double>(), kSB, x.as<double>(), beta, y.as<double>(), wp);
+  EPS_HIP(hipGetLastError());
+}
+
+void SymvPackedTiles(int64_t n, const DVec& P, const DVec& x, const DVec& work) {
+  EPS_CHECK(P.dt == x.dt && x.n == n && P.n >= SymvPackedSize(n));
+  EPS_CHECK(work.dt == P.dt && work.n >= SymvWorkspace(n));
+  if (n == 0) return;
+  ProfScope prof("symv_packed_tiles", n);
+  if (P.dt == F32) LaunchSymv<float, true>(n, 0.0, P.as<float>(), kSB, x.as<float>(), 0.0, nullptr, work.data());
+  else LaunchSymv<double, true>(n, 0.0, P.as<double>(), kSB, x.as<double>(), 0.0, nullptr, work.data());
   EPS_HIP(hipGetLastError());
 }
 
@@ -869,13 +849,15 @@ __global__ __launch_bounds__(kBlock) void SymvReduceBatchKernel(int64_t n, int64
 }
 
 template <class T>
-void LaunchSymvPackedBatch(int64_t n, double alpha, const T* P, const LassoBatchInst<T>* tab, int count, T* work) {
+void LaunchSymvPackedBatch(int64_t n, double alpha, const T* P, const LassoBatchInst<T>* tab, int count, T* work,
+                           bool reduce = true) {
   hipStream_t s = Runtime::Get().stream();
   const int64_t nb = (n + kSB - 1) / kSB;
   const int64_t ntiles = nb * (nb + 1) / 2;
   const int64_t ws = SymvWorkspace(n);
   hipLaunchKernelGGL((SymvTileBatchKernel<T>), dim3(static_cast<unsigned>(ntiles)), dim3(kBlock), 0, s, n, P, tab,
                      count, work, ws, ntiles);
+  if (!reduce) return;  // the tile launch alone
   hipLaunchKernelGGL((SymvReduceBatchKernel<T>), dim3(static_cast<unsigned>(nb), static_cast<unsigned>(count)),
                      dim3(kBlock), 0, s, n, nb, work, ws, ntiles, T(alpha), tab);
 }
@@ -911,6 +893,20 @@ void SymvPackedBatch(int64_t m, double alpha, const DVec& P, const DVec& table, 
     LaunchSymvPackedBatch<double>(m, alpha, P.as<double>(),
                                   reinterpret_cast<const LassoBatchInst<double>*>(table.as<char>()), count,
                                   work.as<double>());
+  EPS_HIP(hipGetLastError());
+}
+
+void SymvPackedTilesBatch(int64_t n, const DVec& P, const DVec& table, int count, const DVec& work) {
+  if (n == 0 || count == 0) return;
+  EPS_CHECK(P.n >= SymvPackedSize(n) && work.dt == P.dt && work.n >= count * SymvWorkspace(n));
+  ProfScope prof("batch_symv_packed_tiles", n, count);
+  if (P.dt == F32)
+    LaunchSymvPackedBatch<float>(n, 0.0, P.as<float>(), reinterpret_cast<const LassoBatchInst<float>*>(table.as<char>()),
+                                 count, work.as<float>(), /*reduce=*/false);
+  else
+    LaunchSymvPackedBatch<double>(n, 0.0, P.as<double>(),
+                                  reinterpret_cast<const LassoBatchInst<double>*>(table.as<char>()), count,
+                                  work.as<double>(), /*reduce=*/false);
   EPS_HIP(hipGetLastError());
 }
 

@@ -32,6 +32,7 @@ const struct Option {
     {kFusedGrid, "EPSILON_HIP_FUSED_GRID"},
     {kFusedMatrix, "EPSILON_HIP_FUSED_MATRIX", "fused_matrix", {"0", "pass", "wide", "auto"}, "auto"},
     {kFusedResident, "EPSILON_HIP_FUSED_RESIDENT_KB", "fused_resident"},
+    {kFusedTall, "EPSILON_HIP_FUSED_TALL", "fused_tall", {"0", "1", "auto"}, "auto"},
     {kFusedWhiten, "EPSILON_HIP_FUSED_WHITEN"},
     {kFusedZero, "EPSILON_HIP_FUSED_ZERO", "fused_zero", {"0", "auto"}, "auto"},
     {kFusedZeroTall, "EPSILON_HIP_FUSED_ZERO_TALL", "fused_zero_tall", {"0", "1", "auto"}, "auto"},

@@ -25,6 +25,7 @@ enum Id {
   kFusedGrid,
   kFusedMatrix,
   kFusedResident,
+  kFusedTall,
   kFusedWhiten,
   kFusedZero,
   kFusedZeroTall,

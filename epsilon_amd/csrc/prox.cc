@@ -547,6 +547,7 @@ class SumSquareProx final : public ProxOperator {
       return true;
     }
     if (p.size() != 3 || var_keys_.size() != 1) return false;
+    if (p[2] == *var_keys_.begin()) return DescribeTall(d);
     const std::string &ck = p[0], &vk = p[1], &ak = p[2];
     if (vk != *var_keys_.begin()) return false;
     const BlockMatrix& L = chol_.L();
@@ -565,6 +566,37 @@ class SumSquareProx final : public ProxOperator {
     d->var_key = vk;
     d->arg_key = ak;
     d->cols = cols;
+    d->rhs_arg = b_.has_key(ak) ? b_(ak) : DVec();
+    return true;
+  }
+
+  // The same term with more rows than columns: the fill model eliminates [constraint, arg, var], so
+  // arg is a scalar pivot and var carries the dense one, Dinv(var) = (I + alpha^2 H^T H)^-1, with
+  // L(var, arg) = -alpha H^T (transposed, lazily scaled).  Forward: b_var = v_c - L(var,arg) b_arg
+  // with b_arg = rhs_arg alone (v has no entry on the arg row); the back substitution writes rows
+  // that Apply drops.  So Solve(b_ + v)[var] = Dinv(var) (v_c - L(var,arg) rhs_arg).
+  // Vector variables alone: a Kronecker block (matrix variable) is not this form.
+  bool DescribeTall(LeastSquaresDesc* d) const {
+    const std::vector<std::string>& p = chol_.order();
+    const std::string &ck = p[0], &ak = p[1], &vk = p[2];
+    const BlockMatrix& L = chol_.L();
+    const BlockMatrix& Di = chol_.D_inv();
+    if (!L.has_key(vk, ck) || !L.has_key(vk, ak) || L.has_key(ak, ck)) return false;
+    if (!Di.has_key(ck, ck) || !Di.has_key(ak, ak) || !Di.has_key(vk, vk)) return false;
+    if (!is_scalar(L(vk, ck), -1.0) || !is_scalar(Di(ck, ck), -1.0)) return false;
+    if (Di(ak, ak).impl().type() != SCALAR_MATRIX) return false;
+    if (L(vk, ak).impl().type() != DENSE_MATRIX || Di(vk, vk).impl().type() != DENSE_MATRIX) return false;
+    for (const auto& kv : b_.data())
+      if (kv.first != ak) return false;
+    d->L_arg_var = std::static_pointer_cast<const DenseMatrixImpl>(L(vk, ak).ptr());
+    d->Dinv_arg = std::static_pointer_cast<const DenseMatrixImpl>(Di(vk, vk).ptr());
+    if (!d->L_arg_var->trans() || !d->Dinv_arg->symmetric()) return false;
+    d->tall = true;
+    d->dinv_arg = GetScalar(Di(ak, ak));
+    d->constraint_key = ck;
+    d->var_key = vk;
+    d->arg_key = ak;
+    d->cols = 1;
     d->rhs_arg = b_.has_key(ak) ? b_(ak) : DVec();
     return true;
   }

@@ -46,6 +46,12 @@ struct LeastSquaresDesc {  // SumSquareProx after block elimination [constraint,
   // I_cols (x) Dinv_arg; the descriptors above are the dense factors with the scalar factor of the
   // Kronecker product folded into their scale, rhs_arg has m * cols entries (column c at c * m).
   int64_t cols = 1;
+  // The tall form (more rows than columns): the order is [constraint, arg, variable], arg a scalar
+  // pivot.  L_arg_var then holds L(var, arg) (transposed: its buffer is the data matrix, rows x
+  // cols), Dinv_arg the dense symmetric Dinv(var), dinv_arg Dinv(arg)'s scalar, and
+  // Solve(b_ + v)[var] = Dinv(var) (v_c - L(var,arg) rhs_arg).  Vector variables alone (cols == 1).
+  bool tall = false;
+  double dinv_arg = 0;
 };
 struct ScaledZoneDesc {  // ScaledZoneProx with scalar H, A and uniform parameters
   std::string var_key, constraint_key;

@@ -61,6 +61,9 @@ def lasso_ir(A_map, b_expr, lam, n):
 
 
 def lasso(m, n, rho=1.0, seed=0):
+    """The reference's lasso (problems/lasso.py): regression_data with lam = 0.5 max|A^T b|.  Fat A
+    (m < n) runs on the fused pass over A; tall A (m > n, at least 256 columns) on the
+    sweep that never reads A (option "fused_tall": "auto" takes it from 256 columns)."""
     A, b = regression_data(m, n, rho=rho, seed=seed)
     lam = 0.5 * np.abs(A.T.dot(b)).max()
     prob = lasso_ir(ir.dense_matrix(A), ir.constant(b), lam, n)

@@ -128,6 +128,17 @@ const char* eps_version(void);
  * "fused_zero_tall" = "0", "fused_zero" = "0" and "fused" = "0" switch it off as well.  It touches
  * nothing but tall problems with a smooth term on z.  Read at every Init.  Any other value is an
  * error that names it (env EPSILON_HIP_FUSED_ZERO_TALL_SMOOTH).
+ * "fused_tall" = "auto" (default) | "0" | "1"  least squares with a separable scaled-zone penalty
+ * (lasso; deadzone or quantile penalty) whose data matrix has more rows than columns: the prox of
+ * the least-squares term is then the cached n x n inverse applied to the iterate minus a constant,
+ * and the sweep never reads the matrix - from 1024 columns two launches (the tiles of the packed
+ * inverse; their sum with the element-wise chain), below that the dense apply and the chain.
+ * "1": wherever the route is supported - vector variable, at least 256 columns, any number of rows
+ * above that, multi-block driver, one GPU, f32 and f64; "0": never; "auto": from the measured floor
+ * on the number of columns (256, so "auto" is "1" at present).  "fused" = "0" switches
+ * it off as well.  In eps_solve_batch the instances on the route that share the inverse (one data
+ * matrix, from 1024 columns) run as one group, each bit for bit its own eps_solve.  Read at every
+ * Init.  Any other value is an error that names it (env EPSILON_HIP_FUSED_TALL).
  * "fused_resident" = "auto" (default) | "<KiB>"  bytes of the data matrix that the fused pass
  * (single and batched; one GPU) loads with the default cache policy, so that they stay in the
  * 256 MiB Infinity Cache from sweep to sweep, while the rest is streamed with non-temporal loads.
