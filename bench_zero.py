@@ -58,6 +58,17 @@ handle (default auto); the line carries it.
 
     python bench_zero.py --shapes logreg_tall,logreg_tall64,logreg_ladder512,logreg_ladder1024,logreg_ladder2048
     python bench_zero.py --shapes logreg_tall --resident 29297
+
+Ridge cells (a ridge term on x in place of the l1 term: problems.hinge_l2 / svr_l2 / logreg_l2 with
+their default lambda; DESIGN.md 3.11 "A ridge term on x"): the routes are those of the option
+"fused_zero_ridge" - "0" the generic operator path, which is what these problems took before the
+option existed, and "1" - with "fused_zero_tall" = "fused_zero_tall_smooth" = "1", so that "1" is on
+wherever the routes take the shape.  Per KIND in hinge_l2, svr_l2, logreg_l2: the 4n x n ladder
+KIND_ladder256 / 512 / 1024 / 2048, KIND_tall = 5000 x 1500 (KIND_tall64 in f64), and the fat cells of
+hinge + l1 above, KIND_floor = 256 x 601, KIND_fat = 1500 x 5000, KIND_fat_big = 4096 x 16384.  They
+set the floors of that option's "auto", one per route.  --shapes ridge is all of them.
+
+    python bench_zero.py --shapes ridge
 """
 
 import argparse
@@ -99,6 +110,13 @@ SHAPES = {
     "logreg_ladder2048": ("logreg_l1", 8192, 2048, "f32"),
     "logreg_mnist_shape": ("logreg_l1", 60000, 784, "f32"),
 }
+RIDGE_KINDS = ("hinge_l2", "svr_l2", "logreg_l2")
+RIDGE_CELLS = (("ladder256", 1024, 256, "f32"), ("ladder512", 2048, 512, "f32"), ("ladder1024", 4096, 1024, "f32"),
+               ("ladder2048", 8192, 2048, "f32"), ("tall", 5000, 1500, "f32"), ("tall64", 5000, 1500, "f64"),
+               ("floor", 256, 601, "f32"), ("fat", 1500, 5000, "f32"), ("fat_big", 4096, 16384, "f32"))
+for _kind in RIDGE_KINDS:
+    for _cell, _m, _n, _dtype in RIDGE_CELLS:
+        SHAPES["%s_%s" % (_kind, _cell)] = (_kind, _m, _n, _dtype)
 ROUTES = ("0", "auto")
 TALL_ROUTES = ("0", "1")  # of "fused_zero_tall", for the cells with more rows than columns
 
@@ -230,20 +248,29 @@ def main():
         for line in path_lines(a):
             print(json.dumps(line), flush=True)
         return
-    for name in a.shapes.split(","):
+    names = a.shapes.split(",")
+    if "ridge" in names:
+        at = names.index("ridge")
+        names[at:at + 1] = ["%s_%s" % (k, c[0]) for k in RIDGE_KINDS for c in RIDGE_CELLS]
+    for name in names:
         kind, m, n, dtype = SHAPES[name]
         tall = m > n
+        ridge = kind in RIDGE_KINDS
         option, routes, tag = (("fused_zero_tall_smooth", TALL_ROUTES, "zero_tall_samples")
-                               if tall and kind == "logreg_l1" else
+                               if tall and kind.startswith("logreg") else
                                ("fused_zero_tall", TALL_ROUTES, "zero_tall") if tall else
                                ("fused_zero", ROUTES, "zero_fused"))
+        if ridge:  # the same tags show the route; the option that is switched is the ridge term's
+            option, routes = "fused_zero_ridge", TALL_ROUTES
         prob = getattr(problems, kind)(m, n)[0]
         pb, data = prob.SerializeToString(), prob.expression_data()
         sb = wire.SolverParams(max_iterations=10 ** 9, ignore_stopping_criteria=True).SerializeToString()
         _solve.set_option("dtype", dtype)
         _solve.set_option("fused_resident", a.resident)
-        if option == "fused_zero_tall_smooth":
+        if option == "fused_zero_tall_smooth" or ridge:
             _solve.set_option("fused_zero_tall", "1")
+        if ridge:
+            _solve.set_option("fused_zero_tall_smooth", "1")
         handles = {}
         try:
             for route in routes:
@@ -268,6 +295,7 @@ def main():
                 s.close()
             _solve.set_option(option, "auto")
             _solve.set_option("fused_zero_tall", "auto")
+            _solve.set_option("fused_zero_tall_smooth", "auto")
             _solve.set_option("fused_resident", "auto")
             _solve.set_option("dtype", "f32")
         ms = {r: (1e3 * statistics.median(times[r]) if r in times else None) for r in routes}
@@ -278,6 +306,8 @@ def main():
                     speedup=(ms["0"] / ms[routes[1]] if ms[routes[1]] else None))
         if a.resident != "auto":
             line["fused_resident_kb"] = int(a.resident)
+        if ridge:
+            line["option"] = option
         if tall:
             line["sweeps_per_s"] = {r: (1e3 / ms[r] if ms[r] else None) for r in routes}
         print(json.dumps(line), flush=True)

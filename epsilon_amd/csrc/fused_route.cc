@@ -124,10 +124,10 @@ std::vector<BlockVector*> Homes(const MultiBlockParts& a) {
 int BatchWideMin();  // (with the batched solves below)
 
 // The indices of the options' words (options.cc).  "fused" (off with a leading 0), "fused_zero",
-// "fused_zero_tall", "fused_zero_tall_smooth", "fused_tall", "fused_matrix" and "fused_resident" are
+// "fused_zero_ridge", "fused_zero_tall", "fused_zero_tall_smooth", "fused_tall", "fused_matrix" and "fused_resident" are
 // read at every Init, "batch_wide" and "batch_zero_tall" per batch ("1" sends eligible groups to the wide
 // route / lets the tall ZERO-term members of a batch form groups).
-enum ZeroTallMode { kZeroTallOff, kZeroTallOn, kZeroTallAuto };  // of every tall option
+enum ZeroTallMode { kZeroTallOff, kZeroTallOn, kZeroTallAuto };  // of every tall option, and of "fused_zero_ridge"
 enum MatrixRoute { kMatrixOff, kMatrixPass, kMatrixWide, kMatrixAuto };
 
 // What the Infinity Cache holds of lines loaded with the default policy before re-reads start to
@@ -177,6 +177,21 @@ constexpr int64_t kZeroTallAutoMinCols = 256;
 // is "0".
 // Measured: 3.5 x at n = 512, the first cell, and no cell above it below 2.4 x.
 constexpr int64_t kZeroTallSmoothAutoMinCols = 512;
+
+// A ridge term on x in place of the scaled zone (hinge_l2, svr_l2, logreg_l2; option "fused_zero_ridge",
+// DESIGN.md 3.11 "A ridge term on x").  The floors of its "auto", one per route by the rule of
+// kZeroTallAutoMinCols on the *_l2 cells of bench_zero.py: the smallest m of the fat ladder, the
+// smallest n of the 4n x n ladder for the hinge / deadzone losses (one pass) and for the logistic loss
+// (the pass in halves), from which every measured cell is ahead of the generic path by more than the
+// spread of its runs; 0 means that no cell got there, or that the cells were not run, and "auto" is "0"
+// on that route.
+// Measured (profiles/r19_zero_ridge.jsonl): every cell is ahead, the spreads at most 0.13.
+// Fat: 4.4 to 4.7 x at m = 256, the first cell, and no cell above it below 2.5 x.  Tall, hinge and
+// deadzone: 5.6 and 4.5 x at n = 256, no cell above it below 2.7 x.  Tall, logistic: 3.7 x at n = 256,
+// no cell above it below 2.2 x.  So each floor is the route's own and "auto" is "1" at present.
+constexpr int64_t kZeroRidgeAutoMinRows = 256;
+constexpr int64_t kZeroRidgeTallAutoMinCols = 256;
+constexpr int64_t kZeroRidgeTallSmoothAutoMinCols = 256;
 
 // Tall lasso (more rows than columns: the order of the least-squares prox's block LDL^T ends in the
 // variable) on the fused sweep (LassoRoute with `tall`).  Below this many columns
@@ -879,11 +894,18 @@ struct LassoRoute final : BatchRoute {
 // with the carried head, the forward product (chain 5).  Under the option "batch_zero_tall" the tall
 // members of a batch that share C run as one group ("Tall members"); without it each is
 // solved by itself.
+//
+// A ridge term on x (`x_ridge`, option "fused_zero_ridge"; DESIGN.md 3.11 "A ridge term on x"): the
+// term on x may be SUM_SQUARE with a scalar argument map instead of a scaled zone
+// (ScalarLeastSquaresDesc).  The side that owns x - the pass on fat C, the x-side kernel on tall C -
+// then takes the block solve's two multiplies in the threshold's place; everything else is as above.
+// Single solves on the multi-block driver alone: such a member of a batch is solved by itself.
 struct ZeroRoute final : BatchRoute {
   using Side = k::ConsensusState;  // of the x constraint, of the z constraint
 
   ZeroProjectionDesc zp;
   ScaledZoneDesc sx, sz;  // the separable terms on x and on z
+  bool x_ridge = false;   // the x term is a ridge term: sx.Bs, sx.Cs are the two factors of its block solve
   bool tall = false;
   bool has_z = false;
   // m, n: C is m x n.  w, p, tpart: the dense pivot's vectors (tall: x' of the coming sweep, f_x and
@@ -899,9 +921,9 @@ struct ZeroRoute final : BatchRoute {
   DVec dfarg;
   k::LassoFusedArgs acc;
 
-  // `tall_mode`, `tall_smooth_mode`: the options "fused_zero_tall" and "fused_zero_tall_smooth";
-  // under "auto" the measured floors apply
-  bool Enable(const MultiBlockParts& a, int tall_mode, int tall_smooth_mode) {
+  // `tall_mode`, `tall_smooth_mode`, `ridge_mode`: the options "fused_zero_tall",
+  // "fused_zero_tall_smooth" and "fused_zero_ridge"; under "auto" the measured floors apply
+  bool Enable(const MultiBlockParts& a, int tall_mode, int tall_smooth_mode, int ridge_mode) {
     if (opt::Is0(opt::kFused) || ShardSpec::Get().active() || !a.b.data().empty()) return false;
     const int nc = a.num_constraints, N = static_cast<int>(a.prox.size());
     if (nc < 1 || nc > 2 || N != nc + 1) return false;
@@ -914,6 +936,18 @@ struct ZeroRoute final : BatchRoute {
     for (int i = 0; i + 1 < N; ++i) {
       ScaledZoneDesc d;
       SmoothSeparableDesc sm;
+      ScalarLeastSquaresDesc ls;
+      if (a.prox[i]->DescribeScalarLeastSquares(&ls)) {  // a ridge term: on x alone, in the zone's place
+        if (ridge_mode == kZeroTallOff || ix >= 0 || ls.constraint_key != zp.x_constraint_key) return false;
+        sx = ScaledZoneDesc();
+        sx.var_key = ls.var_key;
+        sx.constraint_key = ls.constraint_key;
+        sx.Bs = -1.0 * ls.l_var_con;  // the factors as the scalar maps' Apply forms them: alpha * scalar
+        sx.Cs = 1.0 * ls.dinv_var;
+        x_ridge = true;
+        ix = i;
+        continue;
+      }
       const bool smooth = !a.prox[i]->DescribeScaledZoneOffset(&d);
       if (smooth) {  // the scalar form is the zone's; its parameters are not read
         if (!a.prox[i]->DescribeSmoothSeparable(&sm)) return false;
@@ -959,8 +993,12 @@ struct ZeroRoute final : BatchRoute {
         // the halves of the pass exist in the 256-thread shapes alone
         if (k::LassoFusedBlock(n, m, dt) != 256) return false;
       }
+      const int64_t ridge_floor = samples_smooth ? kZeroRidgeTallSmoothAutoMinCols : kZeroRidgeTallAutoMinCols;
+      if (x_ridge && ridge_mode == kZeroTallAuto && (ridge_floor == 0 || n < ridge_floor)) return false;
     } else {
       if (m < kZeroFusedMinRows || !k::LassoFusedSupported(m, n, L.data(), L.rows())) return false;
+      if (x_ridge && ridge_mode == kZeroTallAuto && (kZeroRidgeAutoMinRows == 0 || m < kZeroRidgeAutoMinRows))
+        return false;
     }
     // the consensus constraints: copy + a var = 0, nothing else in their rows or columns
     if (static_cast<int>(a.A.data().size()) != 2 * nc) return false;
@@ -1075,6 +1113,7 @@ struct ZeroRoute final : BatchRoute {
     pass.lda = zp.L->rows();
     pass.A = zp.L->data();
     PassSide(2, sn, sx, ax);
+    pass.inst.zone.ridge = x_ridge;
     pass.inst.rhs = zp.rhs_arg;
     if (!has_z) return;
     RowsSide(sm, sz, az);
@@ -1102,6 +1141,7 @@ struct ZeroRoute final : BatchRoute {
     i.ke = -zp.e;
     i.dinv = zp.dinv_arg;
     RowsSide(sn, sx, ax);
+    rows.zone.ridge = x_ridge;
     rows.tall = true;
     if (!samples_smooth) return;
     // the pass in two halves (chains 4 and 5) around the sample kernel, which takes the z side's
@@ -1180,6 +1220,7 @@ struct ZeroRoute final : BatchRoute {
   // the form (the pass whole, or in halves around the sample kernel: a logistic member never joins
   // a scaled-zone group) and the scalar pivot.
   bool BatchKey(const pb::SolverParams& params, bool tall_groups, std::vector<uint64_t>* key) const override {
+    if (x_ridge) return false;  // the batched kernels have no ridge head: such a member is solved by itself
     if (tall) {
       if (!tall_groups || !has_z || k::LassoBatchWidth(pass.m, pass.n, dt, pass.chain) == 0) return false;
       if (samples_smooth && k::LassoBatchWidth(pass.m, pass.n, dt, acc.chain) == 0) return false;
@@ -1298,9 +1339,10 @@ std::unique_ptr<FusedRoute> RecogniseMultiBlockRoute(const MultiBlockParts& part
   const int tall = opt::Word(opt::kFusedZeroTall);
   const int tall_smooth = opt::Word(opt::kFusedZeroTallSmooth);
   const int lasso_tall = opt::Word(opt::kFusedTall);
+  const int ridge = opt::Word(opt::kFusedZeroRidge);
   if (auto r = Recognise<LassoRoute>(parts, lasso_tall)) return r;  // fat, then tall
   if (!zero) return nullptr;
-  return Recognise<ZeroRoute>(parts, tall, tall_smooth);  // fat, then tall
+  return Recognise<ZeroRoute>(parts, tall, tall_smooth, ridge);  // fat, then tall
 }
 
 std::unique_ptr<FusedRoute> RecogniseTwoBlockRoute(const TwoBlockParts& parts) {

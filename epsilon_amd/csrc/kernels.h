@@ -71,9 +71,13 @@ struct ConsensusState {
   DVec y_term_prev, y_zero_prev;   // their previous values (the lasso chain keeps no y_zero_prev)
 };
 // The separable term as a scaled zone, Cs zone(Bs v); a1 scales `var` in the constraint.
+// `ridge` (the x side of a ZERO-term sweep alone: LassoFusedArgs chain 2, ZeroRowsArgs::tall): the
+// term is a scalar least-squares prox instead, var = Cs (Bs v) with Bs and Cs the two factors of its
+// block solve (-L(var, constraint) and Dinv(var)); the zone's parameters are not read.
 struct ZoneParams {
   DVec alpha_vec, beta_vec;        // optional per-entry alpha / beta
   double Bs = 0, Cs = 0, a1 = 0, lam = 0, alpha = 1, beta = 1, M = 0;
+  bool ridge = false;
 };
 // One instance of the sweep as the kernels read it (host view: scalars as double, narrowed to
 // the compute type in one place, kernels_fused_chain.h): the multi-block driver's fused state

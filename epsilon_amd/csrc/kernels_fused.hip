@@ -62,6 +62,8 @@ constexpr int kBlock = 256;
 // "zero_tall_acc") is the forward product alone: per sample a broadcast load of f_arg_j from `zt.rhs`,
 // here the m-long vector the sample kernel wrote, then t' += C[j,:]^T f_arg_j; no dot product, no
 // reduction, no barrier.
+// MODE 6: MODE 2 with a ridge term on x (ZoneParams::ridge: the RidgeStep head in place of the
+// threshold); the same arrays, the same tag.
 template <class T, int NR, int BS, int MODE>
 __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
     int64_t m, int64_t n, const T* __restrict__ A, int64_t lda, const T* __restrict__ w,
@@ -119,7 +121,7 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
     if (jn >= 0) load(nxt, jn);
     // per-column state (same address in every lane: broadcast loads)
     T uj = T(0), y0j = T(0), y1j = T(0);
-    if constexpr (MODE <= 3) {
+    if constexpr (MODE <= 3 || MODE == 6) {
       uj = u[j];
       y0j = y0[j];
       y1j = y1[j];
@@ -164,9 +166,10 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
         y1[j] = ny1;
         u[j] = nu;
       }
-    } else if (MODE == 2) {
+    } else if (MODE == 2 || MODE == 6) {
       T ns, nq, nys, nyq, nu;
-      v0n = ZeroChainT<T>(d, cj, T(0), uj, y1j, y0j, &ns, &nq, &nys, &nyq, &nu);
+      if constexpr (MODE == 6) v0n = ZeroChainT<T, RidgeStep>(d, cj, T(0), uj, y1j, y0j, &ns, &nq, &nys, &nyq, &nu);
+      else v0n = ZeroChainT<T>(d, cj, T(0), uj, y1j, y0j, &ns, &nq, &nys, &nyq, &nu);
       if (tid == 0) {
         y1prev[j] = y1j;
         e0[j] = y0j;
@@ -233,6 +236,7 @@ void LaunchFused(const LassoFusedArgs& a, int grid) {
   auto kernel = LassoFusedStreamKernelT<T, NR, BS, 0>;
   if (a.chain == 1) kernel = LassoFusedStreamKernelT<T, NR, BS, 1>;
   if (a.chain == 2) kernel = LassoFusedStreamKernelT<T, NR, BS, 2>;
+  if (a.chain == 2 && z.ridge) kernel = LassoFusedStreamKernelT<T, NR, BS, 6>;
   if (a.chain == 3) kernel = LassoFusedStreamKernelT<T, NR, BS, 3>;
   // the halves of the tall pass exist in the 256-thread shapes alone (ZeroRoute takes no other)
   if constexpr (BS == 256) {
@@ -364,7 +368,8 @@ template <class T> struct ZeroRowsInst {
 // Workgroup `block` of one member's row side: the body of the single and of the batched kernel.
 // TALL (tag "zero_tall_cols"): the x side of a tall problem over the n entries of x.  The same
 // summation of the partials; the chain takes q = x'_j as the inverse apply left it in w
-// (ZeroTallColsChainT) and r_j = f_x = v_x' + pkappa sum: no rhs on this side.
+// (ZeroTallColsChainT) and r_j = f_x = v_x' + pkappa sum: no rhs on this side.  Fn = void: the x term
+// is a scaled zone; Fn = RidgeStep: a ridge term (ZoneParams::ridge).
 template <class T, int ROWS, class Fn, bool TALL = false>
 __device__ __forceinline__ void ZeroRowsBody(int64_t m, int nparts, const ZeroRowsInst<T>& I, unsigned block) {
   __shared__ T part[kZeroLanes][ROWS];
@@ -398,7 +403,7 @@ __device__ __forceinline__ void ZeroRowsBody(int64_t m, int nparts, const ZeroRo
   T ns, nq, nys, nyq, nu, vn;
   if constexpr (TALL) {
     nq = nyq = I.w[i];
-    vn = ZeroTallColsChainT<T>(nq, ci, gi, I.u[i], yzi, yqi, &ns, &nys, &nu);
+    vn = ZeroTallColsChainT<T, Fn>(nq, ci, gi, I.u[i], yzi, yqi, &ns, &nys, &nu);
   } else if constexpr (std::is_void<Fn>::value) {
     vn = ZeroChainT<T>(I.w[i], ci, gi, I.u[i], yzi, yqi, &ns, &nq, &nys, &nyq, &nu);
   } else {
@@ -533,6 +538,7 @@ void CheckZeroRows(const ZeroRowsArgs& a) {
   for (const DVec* v : {&a.rhs, &a.g, &a.zone.alpha_vec, &a.zone.beta_vec})
     if (v->n > 0) EPS_CHECK(v->n == a.m && v->dt == dt);
   EPS_CHECK_MSG(!(a.tall && a.smooth), "the tall ZERO-term x side has no smooth form");
+  EPS_CHECK_MSG(!a.zone.ridge || a.tall, "a ridge term is on the x side: the rows take it in the tall form alone");
   if (!a.smooth) return;
   EPS_CHECK_MSG(a.fn == SMOOTH_LOGISTIC, "the fused ZERO-term rows take SUM_LOGISTIC alone, got " << a.fn);
   for (const DVec* v : {&a.hs, &a.hys, &a.hv}) EPS_CHECK(v->n == a.m && v->dt == dt);
@@ -543,7 +549,10 @@ void CheckZeroRows(const ZeroRowsArgs& a) {
 void ZeroFusedRows(const ZeroRowsArgs& a) {
   CheckZeroRows(a);
   ProfScope prof(a.tall ? "zero_tall_cols" : "zero_fused_rows", a.m, a.nparts);
-  if (a.tall) {
+  if (a.tall && a.zone.ridge) {
+    if (a.w.dt == F32) LaunchZeroRows<float, kZeroRows, RidgeStep, true>(a);
+    else LaunchZeroRows<double, kZeroRows, RidgeStep, true>(a);
+  } else if (a.tall) {
     if (a.w.dt == F32) LaunchZeroRows<float, kZeroRows, void, true>(a);
     else LaunchZeroRows<double, kZeroRows, void, true>(a);
   } else if (a.smooth) {
@@ -634,6 +643,7 @@ void ZeroRowsBatchUpload(const std::vector<const ZeroRowsArgs*>& members, DVec* 
     CheckZeroRows(*a);
     EPS_CHECK(a->m == lead.m && a->nparts == lead.nparts && a->smooth == lead.smooth && a->w.dt == lead.w.dt);
     EPS_CHECK(a->tall == lead.tall);
+    EPS_CHECK_MSG(!a->zone.ridge, "the batched rows have no ridge form");
   }
   if (lead.w.dt == F32) UploadRowsT<float>(members, table);
   else UploadRowsT<double>(members, table);
@@ -861,6 +871,7 @@ void LassoFusedPass(const LassoFusedArgs& a) {
     if (v->n > 0) EPS_CHECK(v->n == a.n && v->dt == dt);
   if (a.chain == 1) EPS_CHECK(a.e1.n == a.n && a.e1.dt == dt);
   EPS_CHECK(a.chain >= 0 && a.chain <= 5);
+  EPS_CHECK_MSG(!s.zone.ridge || a.chain == 2, "a ridge term is on the x side: the pass takes it in chain 2 alone");
   if (a.chain == 4) EPS_CHECK(s.zd.n == a.n && s.zd.dt == dt);
   if (a.chain == 5) EPS_CHECK(s.zfarg.n == a.n && s.zfarg.dt == dt);
   if (a.chain == 3)

@@ -174,27 +174,37 @@ __device__ inline T ChainOneT(T d, const FusedScalarsT<T>& c, T u, T y0p, T y1p,
 // needs the boundary state alone; the tail needs this sweep's w.
 // Fn (kernels_smooth_fn.h): a smooth separable term in place of the zone, its prox the fp64 Newton
 // of SmoothProxKernel on the rounded input with the operator's own weight `lam64`.
+// RidgeStep in the Fn slot (the x side alone): the term is a scalar least-squares prox
+// (ScalarLeastSquaresDesc, ZoneParams::ridge) and its variable the block solve's two scalar-map
+// applies on the prox input, s = Cs (Bs ub): no offset, no zone, one rounding per multiply.
+struct RidgeStep {};
 template <class T> struct ZeroHeadT {
   T s, ys, v;  // the separable term's variable and y; the ZERO prox's input on this row
 };
 template <class T, class Fn = void>
 __device__ inline ZeroHeadT<T> ZeroHeadOfT(const FusedScalarsT<T>& c, T g, T u, T ysp, T yqp, double lam64 = 0) {
   const T ub = ((u - ysp) - yqp) + ysp;  // sweep start, then the separable term's u += y_s
-  const T vin = c.Bs * ub + g;           // VectorProx: B v + g            (vector_prox.cc:141)
-  T xz;
-  if constexpr (std::is_void<Fn>::value) xz = ScaledZoneOneT<T>(vin, c.lam, c.alpha, c.beta, c.M);
-  else xz = static_cast<T>(ProxElem<Fn>(static_cast<double>(vin), lam64));
-  const T s = c.Cs * (xz - g);           // C (x - g)                      (vector_prox.cc:145)
+  T s;
+  if constexpr (std::is_same<Fn, RidgeStep>::value) {
+    const T t = c.Bs * ub;               // forward substitution: -L(var, constraint) v   (block.cc Substitute)
+    s = c.Cs * t;                        // the pivot: Dinv(var) t
+  } else {
+    const T vin = c.Bs * ub + g;         // VectorProx: B v + g            (vector_prox.cc:141)
+    T xz;
+    if constexpr (std::is_void<Fn>::value) xz = ScaledZoneOneT<T>(vin, c.lam, c.alpha, c.beta, c.M);
+    else xz = static_cast<T>(ProxElem<Fn>(static_cast<double>(vin), lam64));
+    s = c.Cs * (xz - g);                 // C (x - g)                      (vector_prox.cc:145)
+  }
   const T ys = c.a1 * s;                 // y_s = A_ s
   const T uc = ub - ys;                  // u -= y_s
   return {s, ys, uc + yqp};              // ZERO term: u += y_q
 }
 // Finishes the sweep from the product `d` with this sweep's w (q = kappa d + v), writes the
 // boundary state and returns the NEXT sweep's v, computed in registers from that state.
-template <class T>
+template <class T, class Fn = void>
 __device__ inline T ZeroChainT(T d, const FusedScalarsT<T>& c, T g, T u, T ysp, T yqp, T* so, T* qo, T* yso,
                                T* yqo, T* uo) {
-  const ZeroHeadT<T> h = ZeroHeadOfT<T>(c, g, u, ysp, yqp);
+  const ZeroHeadT<T> h = ZeroHeadOfT<T, Fn>(c, g, u, ysp, yqp);
   const T q = c.kappa * d + h.v;  // back substitution epilogue: alpha*acc + 1*y
   const T un = h.v - q;           // y_q = q (its constraint map is I); u -= y_q
   *so = h.s;
@@ -202,7 +212,7 @@ __device__ inline T ZeroChainT(T d, const FusedScalarsT<T>& c, T g, T u, T ysp, 
   *yso = h.ys;
   *yqo = q;
   *uo = un;
-  return ZeroHeadOfT<T>(c, g, un, h.ys, q).v;
+  return ZeroHeadOfT<T, Fn>(c, g, un, h.ys, q).v;
 }
 
 // ---- tall ZERO-term problems ("Tall C"): the block LDL^T eliminates
@@ -242,15 +252,15 @@ __device__ inline T ZeroTallChainT(T d, const FusedScalarsT<T>& c, T ke, T dinv,
 }
 // The x side of the same sweep: x'_j comes from the apply of Dinv(x') as it is (q = x'_j, no
 // product on top), y_q = q, u = v - q; returns the NEXT sweep's v_x.
-template <class T>
+template <class T, class Fn = void>
 __device__ inline T ZeroTallColsChainT(T q, const FusedScalarsT<T>& c, T g, T u, T ysp, T yqp, T* so, T* yso,
                                        T* uo) {
-  const ZeroHeadT<T> h = ZeroHeadOfT<T>(c, g, u, ysp, yqp);
+  const ZeroHeadT<T> h = ZeroHeadOfT<T, Fn>(c, g, u, ysp, yqp);
   const T un = h.v - q;
   *so = h.s;
   *yso = h.ys;
   *uo = un;
-  return ZeroHeadOfT<T>(c, g, un, h.ys, q).v;
+  return ZeroHeadOfT<T, Fn>(c, g, un, h.ys, q).v;
 }
 
 // The group threshold of one row of a matrix variable (NORM_2 with axis = 1): SegNorm2Kernel's

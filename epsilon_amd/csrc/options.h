@@ -28,6 +28,7 @@ enum Id {
   kFusedTall,
   kFusedWhiten,
   kFusedZero,
+  kFusedZeroRidge,
   kFusedZeroTall,
   kFusedZeroTallSmooth,
   kGemm,

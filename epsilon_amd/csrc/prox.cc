@@ -512,9 +512,43 @@ class SumSquareProx final : public ProxOperator {
     chol_.Compute(M);
     b_ = (-alpha) * g;
     var_keys_ = H.col_keys();
+    arg_keys_ = H.row_keys();
+    h_scalar_ = true;
+    for (const auto& col : H.data())
+      for (const auto& blk : col.second) h_scalar_ = h_scalar_ && blk.second.impl().type() == SCALAR_MATRIX;
   }
   BlockVector Apply(const BlockVector& v) override {
     return chol_.Solve(b_ + v).Select(var_keys_);
+  }
+
+  // A ridge term ("A ridge term on x"): H a scalar map on one variable, no offset,
+  // the order [arg, constraint, var] - what the fill model gives this system, arg and constraint
+  // tying on the bound and taken in key order - and L(var, arg), L(var, constraint), the three
+  // pivots the only blocks, all scalar matrices.  The prox input has no entry on the arg row, so the
+  // forward substitution reaches var from the constraint row alone and Solve(v)[var] =
+  // Dinv(var) (-L(var, constraint) v_c).  Every other order keeps the generic path.
+  bool DescribeScalarLeastSquares(ScalarLeastSquaresDesc* d) const override {
+    const std::vector<std::string>& p = chol_.order();
+    if (chol_.refine_steps() > 0 || !h_scalar_ || !b_.data().empty()) return false;
+    if (p.size() != 3 || var_keys_.size() != 1 || arg_keys_.size() != 1) return false;
+    const std::string &ak = p[0], &ck = p[1], &vk = p[2];
+    if (vk != *var_keys_.begin() || ak != *arg_keys_.begin() || ck == ak || ck == vk) return false;
+    const BlockMatrix& L = chol_.L();
+    const BlockMatrix& Di = chol_.D_inv();
+    size_t blocks = 0;
+    for (const BlockMatrix* M : {&L, &Di})
+      for (const auto& col : M->data())
+        for (const auto& blk : col.second) {
+          if (blk.second.impl().type() != SCALAR_MATRIX) return false;
+          ++blocks;
+        }
+    if (blocks != 5 || !L.has_key(vk, ak) || !L.has_key(vk, ck)) return false;
+    if (!Di.has_key(ak, ak) || !Di.has_key(ck, ck) || !Di.has_key(vk, vk)) return false;
+    d->var_key = vk;
+    d->constraint_key = ck;
+    d->l_var_con = GetScalar(L(vk, ck));
+    d->dinv_var = GetScalar(Di(vk, vk));
+    return true;
   }
 
   // Pattern of the compiled lasso: elimination order [constraint, var, arg],
@@ -621,7 +655,8 @@ class SumSquareProx final : public ProxOperator {
  private:
   BlockCholesky chol_;
   BlockVector b_;
-  std::set<std::string> var_keys_;
+  std::set<std::string> var_keys_, arg_keys_;
+  bool h_scalar_ = false;  // every block of the argument map is a scalar matrix
 };
 REGISTER_PROX_OPERATOR(SUM_SQUARE, SumSquareProx);
 

@@ -53,6 +53,18 @@ struct LeastSquaresDesc {  // SumSquareProx after block elimination [constraint,
   bool tall = false;
   double dinv_arg = 0;
 };
+// SumSquareProx with a scalar argument map, no offset and one variable, in the order the fill model
+// gives this system, [arg, constraint, var], every block of the factorisation a scalar matrix.
+// Nothing reaches the var row in the forward substitution but the constraint row, and the back
+// substitution starts from it, so Solve(v)[var] is two scalar-map applies on the prox input,
+//   t = (-1 * l_var_con) v_c ;  x = (1 * dinv_var) t
+// (block.cc Substitute, then D_inv *): each factor the product a scalar map's Apply narrows to the
+// compute type, one rounding per multiply.  In exact arithmetic x = a v / (a^2 + 2 alpha).
+struct ScalarLeastSquaresDesc {
+  std::string var_key, constraint_key;
+  double l_var_con = 0;  // L(var, constraint)'s scalar, as the factorisation holds it
+  double dinv_var = 0;   // Dinv(var)'s scalar, as the factorisation holds it
+};
 struct ScaledZoneDesc {  // ScaledZoneProx with scalar H, A and uniform parameters
   std::string var_key, constraint_key;
   double Bs = 0, Cs = 0;  // v' = Bs*v ; x = Cs*x'
@@ -106,6 +118,7 @@ class ProxOperator {  // reference prox/prox.h:37-43
   virtual void Init(const ProxOperatorArg& arg) {}
   virtual BlockVector Apply(const BlockVector& v) = 0;
   virtual bool DescribeLeastSquares(LeastSquaresDesc* d) const { return false; }
+  virtual bool DescribeScalarLeastSquares(ScalarLeastSquaresDesc* d) const { return false; }
   virtual bool DescribeScaledZone(ScaledZoneDesc* d) const { return false; }
   virtual bool DescribeGroupNorm2(GroupNorm2Desc* d) const { return false; }
   // DescribeScaledZone for an argument that may carry a constant offset (d->g; empty: none)

@@ -552,6 +552,74 @@ def deadzone_l1(m, n, frac=0.3, M=0.5, seed=0):
     return _graph_form(terms, A, -b), dict(A=A, b=b, lam=lam, M=M)
 
 
+# ---- the same losses with a ridge penalty on x (reference python/epopt/problems/hinge_l2.py) ------
+# The x term is sum_square(x)[lam], a scalar least-squares prox: the fused ZERO-term routes take it
+# under the option "fused_zero_ridge" ("A ridge term on x").
+
+def _ridge_data(m, n, seed):
+    """A with unit columns, then x0 and the noise e, drawn in this order (the reference's
+    problem_util.create_classification / create_regression, dense)."""
+    rng = np.random.RandomState(seed)
+    A = rng.randn(m, n)
+    A /= np.sqrt(np.sum(A ** 2, 0))
+    x0 = rng.randn(n)
+    e = rng.randn(m)
+    return A, x0, e
+
+
+def _ridge(x, lam):
+    return ir.prox(ProxFunction.SUM_SQUARE, x, alpha=lam)
+
+
+def hinge_l2(m, n, lam=1.0, seed=0):
+    """The standard SVM, sum_i max(0, 1 - y_i a_i^T x) + lam ||x||_2^2: sum_hinge(1 - z) with
+    z = diag(y) A x, y = sign(A x0 + 0.05 e)."""
+    A, x0, e = _ridge_data(m, n, seed)
+    y = np.sign(A.dot(x0) + 0.05 * e)
+    C = y[:, None] * A
+
+    def terms(x, z):
+        arg = ir.add(ir.linear_map(ir.scalar(-1, m), z), ir.scalar_constant(1.0, (m, 1)))
+        return [ir.prox(ProxFunction.SUM_HINGE, arg), _ridge(x, lam)]
+    return _graph_form(terms, C, None), dict(C=C, A=A, b=y, lam=lam)
+
+
+def hinge_l2_objective(C, lam, x):
+    return float(np.maximum(1.0 - C.dot(x), 0).sum() + lam * np.sum(x ** 2))
+
+
+def svr_l2(m, n, lam=1.0, M=0.5, seed=0):
+    """eps-insensitive support-vector regression sum_i max(|a_i^T x - b_i| - M, 0) + lam ||x||_2^2:
+    sum_deadzone(z) with z = A x - b, b = A x0 + e."""
+    A, x0, e = _ridge_data(m, n, seed)
+    b = A.dot(x0) + e
+
+    def terms(x, z):
+        return [ir.prox(ProxFunction.SUM_DEADZONE, z, scaled_zone_params=wire.ProxScaledZoneParams(m=M)),
+                _ridge(x, lam)]
+    return _graph_form(terms, A, -b), dict(C=A, A=A, b=b, lam=lam, M=M)
+
+
+def svr_l2_objective(A, b, lam, M, x):
+    return float(np.maximum(np.abs(A.dot(x) - b) - M, 0).sum() + lam * np.sum(x ** 2))
+
+
+def logreg_l2(m, n, lam=1.0, seed=0):
+    """Ridge-regularised logistic regression sum_i logistic(-y_i a_i^T x) + lam ||x||_2^2:
+    sum_logistic(z) with z = -diag(y) A x, y = sign(A x0 + 0.05 e)."""
+    A, x0, e = _ridge_data(m, n, seed)
+    y = np.sign(A.dot(x0) + 0.05 * e)
+    C = -y[:, None] * A
+
+    def terms(x, z):
+        return [ir.prox(ProxFunction.SUM_LOGISTIC, z, alpha=1.0), _ridge(x, lam)]
+    return _graph_form(terms, C, None), dict(C=C, A=A, b=y, lam=lam)
+
+
+def logreg_l2_objective(C, lam, x):
+    return float(np.sum(np.logaddexp(0, C.dot(x))) + lam * np.sum(x ** 2))
+
+
 def quantile(m, n, tau=0.3, seed=0):
     """Quantile regression sum_i rho_tau(b_i - a_i^T x): sum_quantile(z), z = A x - b, with
     alpha = 1 - tau on the positive and beta = tau on the negative part of z."""

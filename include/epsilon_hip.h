@@ -128,6 +128,16 @@ const char* eps_version(void);
  * "fused_zero_tall" = "0", "fused_zero" = "0" and "fused" = "0" switch it off as well.  It touches
  * nothing but tall problems with a smooth term on z.  Read at every Init.  Any other value is an
  * error that names it (env EPSILON_HIP_FUSED_ZERO_TALL_SMOOTH).
+ * "fused_zero_ridge" = "auto" (default) | "0" | "1"  the ZERO-term problems of the three options
+ * above with a ridge penalty lam ||x||_2^2 on x in the l1 term's place (the standard SVM,
+ * eps-insensitive regression, ridge-regularised logistic regression): on the same routes, fat and
+ * tall, the ridge prox as the two multiplies of its scalar block solve in the threshold's place.
+ * "1": wherever those routes take the shape; "0": never; "auto": from the measured floors, one per
+ * route (a route without one stays generic).  "fused_zero" = "0", "fused_zero_tall" =
+ * "0", "fused_zero_tall_smooth" = "0" and "fused" = "0" switch it off with their routes.  Single
+ * solves on the multi-block driver; in eps_solve_batch such an instance is solved by itself.  It
+ * touches nothing but problems with a ridge term on x.  Read at every Init.  Any other value is an
+ * error that names it (env EPSILON_HIP_FUSED_ZERO_RIDGE).
  * "fused_tall" = "auto" (default) | "0" | "1"  least squares with a separable scaled-zone penalty
  * (lasso; deadzone or quantile penalty) whose data matrix has more rows than columns: the prox of
  * the least-squares term is then the cached n x n inverse applied to the iterate minus a constant,
