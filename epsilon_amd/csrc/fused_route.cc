@@ -21,8 +21,10 @@ namespace {
 // ---------------------------------------------------------------------------------------------------
 
 // The zone of a kernel record from the operator's description; a1: the scalar of the term's
-// variable in its consensus constraint.
-k::ZoneParams ZoneOf(const ScaledZoneDesc& z, double a1) {
+// variable in its consensus constraint.  A ridge term takes the record with Bs, Cs the two factors of
+// its block solve; smooth terms and row groups read the scalar form alone (the zone's parameters are
+// the defaults).
+k::ZoneParams ZoneOf(const SeparableDesc& z, double a1) {
   k::ZoneParams s;
   s.alpha_vec = z.alpha_vec;
   s.beta_vec = z.beta_vec;
@@ -33,7 +35,20 @@ k::ZoneParams ZoneOf(const ScaledZoneDesc& z, double a1) {
   s.alpha = z.alpha;
   s.beta = z.beta;
   s.M = z.M;
+  s.ridge = z.kind == SeparableDesc::kRidge;
   return s;
+}
+
+// Empty, or `len` values of the compute type `dt`.
+bool Fits(const DVec& v, int64_t len, DType dt) { return v.n == 0 || (v.n == len && v.dt == dt); }
+
+// The prox input of the first sweep from an adopted state, into `v0`:
+// v0 = ((u - y_zero) - y_term) + y_zero, in this order.
+void FirstInput(const k::ConsensusState& s, const DVec& v0) {
+  k::Copy(v0, s.u);
+  k::Axpby(v0, -1.0, s.y_zero, 1.0);
+  k::Axpby(v0, -1.0, s.y_term, 1.0);
+  k::Axpby(v0, 1.0, s.y_zero, 1.0);
 }
 
 // The consensus tie a0 copy + a1 var = 0: row `ck` of A holds scalar maps of length `len` on
@@ -127,8 +142,16 @@ int BatchWideMin();  // (with the batched solves below)
 // "fused_zero_ridge", "fused_zero_tall", "fused_zero_tall_smooth", "fused_tall", "fused_matrix" and "fused_resident" are
 // read at every Init, "batch_wide" and "batch_zero_tall" per batch ("1" sends eligible groups to the wide
 // route / lets the tall ZERO-term members of a batch form groups).
-enum ZeroTallMode { kZeroTallOff, kZeroTallOn, kZeroTallAuto };  // of every tall option, and of "fused_zero_ridge"
+// "0", "1", "auto" of "fused_tall", "fused_zero_tall", "fused_zero_tall_smooth" and "fused_zero_ridge"
+enum RouteMode { kRouteOff, kRouteOn, kRouteAuto };
 enum MatrixRoute { kMatrixOff, kMatrixPass, kMatrixWide, kMatrixAuto };
+
+// Whether such an option lets a problem of `size` onto its route: "0" no, "1" yes, "auto" from the
+// route's measured floor up (a floor of 0: no measured cell got there, "auto" is "0").
+bool Allowed(int mode, int64_t size, int64_t auto_floor) {
+  if (mode == kRouteAuto) return auto_floor != 0 && size >= auto_floor;
+  return mode == kRouteOn;
+}
 
 // What the Infinity Cache holds of lines loaded with the default policy before re-reads start to
 // miss: the upper end of the plateau of the budget sweep on the pass ("A resident
@@ -370,7 +393,7 @@ struct BatchRoute : FusedRoute {
 // the dense apply and the cols kernel below.  One GPU, vector variables, f32 and f64.
 struct LassoRoute final : BatchRoute {
   LeastSquaresDesc ls;
-  ScaledZoneDesc sz;
+  SeparableDesc sz;  // the threshold: a zone, or - a matrix variable - the group shrinkage of the rows (weight sz.lam)
   double a1 = 0;
   int64_t slab = 0;  // rows of the cached inverse applied per rank (sharded runs)
   bool sharded = false;    // the least-squares variable is split over the ranks
@@ -385,8 +408,6 @@ struct LassoRoute final : BatchRoute {
   DVec X, Ahat, rhat;        // L^-1 of the inverse, X A (ld m), X rhs_arg (empty: no rhs)
   // matrix variable (n x cols under I_cols (x) A): its columns are members of the batched kernels
   int64_t cols = 1;
-  bool group = false;      // the threshold is the group shrinkage of the rows (weight sz.lam)
-  int64_t group_rows = 0;
   bool wide = false;       // the wide route (f32): w and p are whole panels of 64 members
   bool rhs_aligned = true;
   std::vector<k::LassoInstance> members;
@@ -414,23 +435,14 @@ struct LassoRoute final : BatchRoute {
     // consensus form: the threshold step averages over the ranks, which the fused pass does not
     if (sh.active() && sh.consensus_terms()) return false;
     if (!a.prox[0]->DescribeLeastSquares(&ls)) return false;
-    if (ls.tall && tall_mode == kZeroTallOff) return false;
     cols = ls.cols;
     const int matrix_mode = cols > 1 ? opt::Word(opt::kFusedMatrix) : kMatrixAuto;
     if (cols > 1 && (matrix_mode == kMatrixOff || sh.active())) return false;
-    if (!a.prox[1]->DescribeScaledZone(&sz)) {
-      // group lasso: one group per row of the n x cols variable
-      GroupNorm2Desc gn;
-      if (cols == 1 || !a.prox[1]->DescribeGroupNorm2(&gn) || gn.cols != cols) return false;
-      group = true;
-      group_rows = gn.rows;
-      sz = ScaledZoneDesc();
-      sz.var_key = gn.var_key;
-      sz.constraint_key = gn.constraint_key;
-      sz.Bs = gn.Bs;
-      sz.Cs = gn.Cs;
-      sz.lam = gn.lam;
-    }
+    // accepted: a zone without offset; or row groups, one per row of the n x cols variable (group lasso)
+    if (!a.prox[1]->DescribeSeparable(&sz)) return false;
+    if (!(sz.kind == SeparableDesc::kZone && sz.g.n == 0) &&
+        !(sz.kind == SeparableDesc::kRowGroups && cols > 1 && sz.cols == cols))
+      return false;
     dt = a.data->dtype();
     if ((sz.alpha_vec.n > 0 && sz.alpha_vec.dt != dt) || (sz.beta_vec.n > 0 && sz.beta_vec.dt != dt)) return false;
     const std::string ck = affine::constraint_key(0);
@@ -518,10 +530,9 @@ struct LassoRoute final : BatchRoute {
     const DenseMatrixImpl& L = *ls.L_arg_var;
     const DenseMatrixImpl& D = *ls.Dinv_arg;
     if (ShardSpec::Get().active() || n < kLassoTallMinCols || m <= n) return false;
-    if (mode == kZeroTallAuto && (kLassoTallAutoMinCols == 0 || n < kLassoTallAutoMinCols)) return false;
+    if (!Allowed(mode, n, kLassoTallAutoMinCols)) return false;
     if (L.dtype() != dt || D.dtype() != dt || D.rows() != n || D.cols() != n) return false;
-    auto fits = [&](const DVec& v, int64_t len) { return v.n == 0 || (v.n == len && v.dt == dt); };
-    if (!fits(ls.rhs_arg, m) || !fits(sz.alpha_vec, n) || !fits(sz.beta_vec, n)) return false;
+    if (!Fits(ls.rhs_arg, m, dt) || !Fits(sz.alpha_vec, n, dt) || !Fits(sz.beta_vec, n, dt)) return false;
     tall = tall_cols = true;
     const std::vector<StateSlice> views = StateViews(a, ck, n);
     p = DVec::Zeros(n, dt);  // r, the apply's input
@@ -542,11 +553,7 @@ struct LassoRoute final : BatchRoute {
     s.zone = ZoneOf(sz, a1);
     AdoptState(views, Homes(a));
     // r of the first sweep from the adopted state: v0 - c
-    const k::ConsensusState& st = s.state;
-    k::Copy(p, st.u);
-    k::Axpby(p, -1.0, st.y_zero, 1.0);
-    k::Axpby(p, -1.0, st.y_term, 1.0);
-    k::Axpby(p, 1.0, st.y_zero, 1.0);
+    FirstInput(s.state, p);
     if (crhs.n != 0) k::Axpby(p, -1.0, crhs, 1.0);
     return true;
   }
@@ -556,8 +563,9 @@ struct LassoRoute final : BatchRoute {
   bool ChooseMatrixRoute(int mode) {
     const DenseMatrixImpl& L = *ls.L_arg_var;
     const DenseMatrixImpl& D = *ls.Dinv_arg;
+    const bool group = sz.kind == SeparableDesc::kRowGroups;
     if (m < kMatrixFusedMinRows || L.dtype() != dt || D.dtype() != dt) return false;
-    if (group && group_rows != n) return false;
+    if (group && sz.rows != n) return false;
     if (sz.alpha_vec.n > 0 && sz.alpha_vec.n != n * cols) return false;
     if (sz.beta_vec.n > 0 && sz.beta_vec.n != n * cols) return false;
     if (D.rows() != m || D.cols() != m) return false;
@@ -629,10 +637,8 @@ struct LassoRoute final : BatchRoute {
   void ForwardFromState() {
     const DenseMatrixImpl& L = *ls.L_arg_var;
     const k::ConsensusState& s = pass.inst.state;
-    DVec v0 = s.u.Clone();
-    k::Axpby(v0, -1.0, s.y_zero, 1.0);
-    k::Axpby(v0, -1.0, s.y_term, 1.0);
-    k::Axpby(v0, 1.0, s.y_zero, 1.0);
+    DVec v0 = DVec::Empty(s.u.n, s.u.dt);
+    FirstInput(s, v0);
     if (cols == 1 && !whiten) {
       L.Apply(-1.0, v0, 0.0, p);
       ForwardTail(/*reduced=*/false);
@@ -761,7 +767,7 @@ struct LassoRoute final : BatchRoute {
   // A matrix variable's sweep: its columns through the batched or the wide kernels.
   void MatrixSweep() {
     const int K = static_cast<int>(cols);
-    const double* group_lam = group ? &sz.lam : nullptr;
+    const double* group_lam = sz.kind == SeparableDesc::kRowGroups ? &sz.lam : nullptr;
     if (wide) {
       constexpr int PW = WideSweep::PW;
       for (int first = 0; first < K; first += PW) {
@@ -895,17 +901,17 @@ struct LassoRoute final : BatchRoute {
 // members of a batch that share C run as one group ("Tall members"); without it each is
 // solved by itself.
 //
-// A ridge term on x (`x_ridge`, option "fused_zero_ridge"; DESIGN.md 3.11 "A ridge term on x"): the
-// term on x may be SUM_SQUARE with a scalar argument map instead of a scaled zone
-// (ScalarLeastSquaresDesc).  The side that owns x - the pass on fat C, the x-side kernel on tall C -
-// then takes the block solve's two multiplies in the threshold's place; everything else is as above.
+// A ridge term on x (`sx` of kind kRidge, option "fused_zero_ridge"; DESIGN.md 3.11 "A ridge term on
+// x"): the term on x may be SUM_SQUARE with a scalar argument map instead of a scaled zone; sx.Bs,
+// sx.Cs are then the two factors of its block solve (SeparableDesc).  The side that owns x - the pass
+// on fat C, the x-side kernel on tall C - then takes the block solve's two multiplies in the
+// threshold's place; everything else is as above.
 // Single solves on the multi-block driver alone: such a member of a batch is solved by itself.
 struct ZeroRoute final : BatchRoute {
   using Side = k::ConsensusState;  // of the x constraint, of the z constraint
 
   ZeroProjectionDesc zp;
-  ScaledZoneDesc sx, sz;  // the separable terms on x and on z
-  bool x_ridge = false;   // the x term is a ridge term: sx.Bs, sx.Cs are the two factors of its block solve
+  SeparableDesc sx, sz;  // the separable terms on x (a zone, or a ridge term) and on z (a zone, or smooth)
   bool tall = false;
   bool has_z = false;
   // m, n: C is m x n.  w, p, tpart: the dense pivot's vectors (tall: x' of the coming sweep, f_x and
@@ -929,50 +935,33 @@ struct ZeroRoute final : BatchRoute {
     if (nc < 1 || nc > 2 || N != nc + 1) return false;
     if (!a.prox[N - 1]->DescribeZeroProjection(&zp)) return false;
     tall = zp.tall;
-    if (tall && tall_mode == kZeroTallOff) return false;
     has_z = !zp.z_key.empty();
     if (has_z != (nc == 2)) return false;
     int ix = -1, iz = -1;  // positions of the separable terms among the objective terms
     for (int i = 0; i + 1 < N; ++i) {
-      ScaledZoneDesc d;
-      SmoothSeparableDesc sm;
-      ScalarLeastSquaresDesc ls;
-      if (a.prox[i]->DescribeScalarLeastSquares(&ls)) {  // a ridge term: on x alone, in the zone's place
-        if (ridge_mode == kZeroTallOff || ix >= 0 || ls.constraint_key != zp.x_constraint_key) return false;
-        sx = ScaledZoneDesc();
-        sx.var_key = ls.var_key;
-        sx.constraint_key = ls.constraint_key;
-        sx.Bs = -1.0 * ls.l_var_con;  // the factors as the scalar maps' Apply forms them: alpha * scalar
-        sx.Cs = 1.0 * ls.dinv_var;
-        x_ridge = true;
-        ix = i;
-        continue;
-      }
-      const bool smooth = !a.prox[i]->DescribeScaledZoneOffset(&d);
-      if (smooth) {  // the scalar form is the zone's; its parameters are not read
-        if (!a.prox[i]->DescribeSmoothSeparable(&sm)) return false;
-        if (tall && (tall_smooth_mode == kZeroTallOff || sm.fn != k::SMOOTH_LOGISTIC)) return false;
-        d.var_key = sm.var_key;
-        d.constraint_key = sm.constraint_key;
-        d.Bs = sm.Bs;
-        d.Cs = sm.Cs;
-        d.lam = sm.lam;
-        d.g = sm.g;
-      }
-      if (!smooth && ix < 0 && d.constraint_key == zp.x_constraint_key && d.g.n == 0) {
+      SeparableDesc d;
+      if (!a.prox[i]->DescribeSeparable(&d)) return false;
+      // accepted on x: a zone without offset, or a ridge term; on z: a zone (its offset with it), or a
+      // smooth term (tall: SUM_LOGISTIC alone) - each once, on its own constraint row
+      const bool zone = d.kind == SeparableDesc::kZone, smooth = d.kind == SeparableDesc::kSmooth;
+      const bool on_x = (zone && d.g.n == 0) || d.kind == SeparableDesc::kRidge;
+      const bool on_z = zone || (smooth && (!tall || d.fn == k::SMOOTH_LOGISTIC));
+      if (on_x && ix < 0 && d.constraint_key == zp.x_constraint_key) {
         sx = d;
         ix = i;
-      } else if (has_z && iz < 0 && d.constraint_key == zp.z_constraint_key) {
+      } else if (on_z && has_z && iz < 0 && d.constraint_key == zp.z_constraint_key) {
         sz = d;
         iz = i;
-        // (the smooth form belongs to the z side: tall, that is the sample kernel, not the rows)
-        (tall ? samples_smooth : rows.smooth) = smooth;
-        (tall ? samples.fn : rows.fn) = sm.fn;
       } else {
         return false;
       }
     }
     if (ix < 0 || (has_z && iz < 0)) return false;
+    const bool x_ridge = sx.kind == SeparableDesc::kRidge;
+    // (the smooth form belongs to the z side: tall, that is the sample kernel, not the rows)
+    samples_smooth = tall && sz.kind == SeparableDesc::kSmooth;
+    rows.smooth = !tall && sz.kind == SeparableDesc::kSmooth;
+    (tall ? samples.fn : rows.fn) = sz.fn;
     const DenseMatrixImpl& L = *zp.L;  // (tall: trans() set: its buffer is C, m x n)
     const DenseMatrixImpl& D = *zp.Dinv;
     dt = a.data->dtype();
@@ -981,24 +970,20 @@ struct ZeroRoute final : BatchRoute {
     const int64_t nw = tall ? n : m;  // the order of the dense pivot
     if (L.dtype() != dt || D.dtype() != dt || D.rows() != nw || D.cols() != nw) return false;
     if (tall) {
-      if (n < kZeroTallMinCols || m <= n) return false;
-      if (tall_mode == kZeroTallAuto && (kZeroTallAutoMinCols == 0 || n < kZeroTallAutoMinCols)) return false;
+      if (n < kZeroTallMinCols || m <= n || !Allowed(tall_mode, n, kZeroTallAutoMinCols)) return false;
       // the pass's shape conditions, on the copy's geometry, before the copy is made
       const int64_t chunk = dt == F32 ? 4 : 2;
       if (n % chunk != 0 || n > (dt == F32 ? 20 : 10) * 1024) return false;
       if (samples_smooth) {
-        if (tall_smooth_mode == kZeroTallAuto &&
-            (kZeroTallSmoothAutoMinCols == 0 || n < kZeroTallSmoothAutoMinCols))
-          return false;
+        if (!Allowed(tall_smooth_mode, n, kZeroTallSmoothAutoMinCols)) return false;
         // the halves of the pass exist in the 256-thread shapes alone
         if (k::LassoFusedBlock(n, m, dt) != 256) return false;
       }
       const int64_t ridge_floor = samples_smooth ? kZeroRidgeTallSmoothAutoMinCols : kZeroRidgeTallAutoMinCols;
-      if (x_ridge && ridge_mode == kZeroTallAuto && (ridge_floor == 0 || n < ridge_floor)) return false;
+      if (x_ridge && !Allowed(ridge_mode, n, ridge_floor)) return false;
     } else {
       if (m < kZeroFusedMinRows || !k::LassoFusedSupported(m, n, L.data(), L.rows())) return false;
-      if (x_ridge && ridge_mode == kZeroTallAuto && (kZeroRidgeAutoMinRows == 0 || m < kZeroRidgeAutoMinRows))
-        return false;
+      if (x_ridge && !Allowed(ridge_mode, m, kZeroRidgeAutoMinRows)) return false;
     }
     // the consensus constraints: copy + a var = 0, nothing else in their rows or columns
     if (static_cast<int>(a.A.data().size()) != 2 * nc) return false;
@@ -1010,9 +995,8 @@ struct ZeroRoute final : BatchRoute {
     };
     if (!tie(zp.x_constraint_key, zp.x_key, sx.var_key, n, &ax)) return false;
     if (has_z && !tie(zp.z_constraint_key, zp.z_key, sz.var_key, m, &az)) return false;
-    auto fits = [&](const DVec& v, int64_t len) { return v.n == 0 || (v.n == len && v.dt == dt); };
-    if (!fits(zp.rhs_arg, m) || !fits(sx.alpha_vec, n) || !fits(sx.beta_vec, n)) return false;
-    if (!fits(sz.alpha_vec, m) || !fits(sz.beta_vec, m) || !fits(sz.g, m)) return false;
+    if (!Fits(zp.rhs_arg, m, dt) || !Fits(sx.alpha_vec, n, dt) || !Fits(sx.beta_vec, n, dt)) return false;
+    if (!Fits(sz.alpha_vec, m, dt) || !Fits(sz.beta_vec, m, dt) || !Fits(sz.g, m, dt)) return false;
     if (tall && !TransposedCopy(a.shared_cache)) return false;
 
     // state: u, var, copy, y of the separable term, y of the ZERO term, their previous values -
@@ -1085,7 +1069,7 @@ struct ZeroRoute final : BatchRoute {
 
   // The pass's instance from the side it runs (chains 2 and 3 read the arrays alike,
   // k::LassoFusedArgs), the row kernel's record from the other side.
-  void PassSide(int chain, const Side& s, const ScaledZoneDesc& zone, double a1) {
+  void PassSide(int chain, const Side& s, const SeparableDesc& zone, double a1) {
     pass.chain = chain;
     k::LassoInstance& i = pass.inst;
     i.w = w;
@@ -1095,7 +1079,7 @@ struct ZeroRoute final : BatchRoute {
     i.zone = ZoneOf(zone, a1);
     i.kappa = i.pkappa = -zp.L->scale();
   }
-  void RowsSide(const Side& s, const ScaledZoneDesc& zone, double a1) {
+  void RowsSide(const Side& s, const SeparableDesc& zone, double a1) {
     rows.m = w.n;
     rows.nparts = grid;
     rows.w = w;
@@ -1113,7 +1097,6 @@ struct ZeroRoute final : BatchRoute {
     pass.lda = zp.L->rows();
     pass.A = zp.L->data();
     PassSide(2, sn, sx, ax);
-    pass.inst.zone.ridge = x_ridge;
     pass.inst.rhs = zp.rhs_arg;
     if (!has_z) return;
     RowsSide(sm, sz, az);
@@ -1141,7 +1124,6 @@ struct ZeroRoute final : BatchRoute {
     i.ke = -zp.e;
     i.dinv = zp.dinv_arg;
     RowsSide(sn, sx, ax);
-    rows.zone.ridge = x_ridge;
     rows.tall = true;
     if (!samples_smooth) return;
     // the pass in two halves (chains 4 and 5) around the sample kernel, which takes the z side's
@@ -1220,7 +1202,8 @@ struct ZeroRoute final : BatchRoute {
   // the form (the pass whole, or in halves around the sample kernel: a logistic member never joins
   // a scaled-zone group) and the scalar pivot.
   bool BatchKey(const pb::SolverParams& params, bool tall_groups, std::vector<uint64_t>* key) const override {
-    if (x_ridge) return false;  // the batched kernels have no ridge head: such a member is solved by itself
+    // the batched kernels have no ridge head: such a member is solved by itself
+    if (sx.kind == SeparableDesc::kRidge) return false;
     if (tall) {
       if (!tall_groups || !has_z || k::LassoBatchWidth(pass.m, pass.n, dt, pass.chain) == 0) return false;
       if (samples_smooth && k::LassoBatchWidth(pass.m, pass.n, dt, acc.chain) == 0) return false;
@@ -1246,7 +1229,7 @@ struct ZeroRoute final : BatchRoute {
 // is the driver's generic one on views of the state.
 struct TwoBlockRoute final : FusedRoute {
   LeastSquaresDesc ls;
-  ScaledZoneDesc sz;
+  SeparableDesc sz;
   int64_t m = 0, n = 0;
   int grid = 0;
   DVec p, w, tpart;
@@ -1255,7 +1238,8 @@ struct TwoBlockRoute final : FusedRoute {
   bool Enable(const TwoBlockParts& a) {
     if (opt::Is0(opt::kFused) || a.prox.size() != 2 || a.num_constraints != 1) return false;
     if (ShardSpec::Get().active() || !a.constr_H.b.data().empty()) return false;
-    if (!a.prox[0]->DescribeLeastSquares(&ls) || !a.prox[1]->DescribeScaledZone(&sz)) return false;
+    if (!a.prox[0]->DescribeLeastSquares(&ls) || !a.prox[1]->DescribeSeparable(&sz)) return false;
+    if (sz.kind != SeparableDesc::kZone || sz.g.n != 0) return false;  // accepted: a zone without offset
     if (ls.cols != 1) return false;  // matrix variables: the multi-block driver only
     const DenseMatrixImpl& L = *ls.L_arg_var;
     if (L.trans()) return false;

@@ -34,9 +34,6 @@ std::unique_ptr<ProxOperator> CreateProxOperator(int type, bool epigraph) {
 
 namespace {
 
-// A scalar map with exactly this value (the describers' test of a block of L or Dinv).
-bool is_scalar(const LinearMap& m, double a) { return m.impl().type() == SCALAR_MATRIX && GetScalar(m) == a; }
-
 // What the argument map H and the constraint row A look like to an elementwise prox: the
 // diagonals of H^T H and of H A^T A H^T, provided both are block diagonal with one and the same
 // diagonal on every block (the test of reference vector_prox.cc:4-49).  `uniform` = every block
@@ -183,10 +180,9 @@ BlockVector VectorProx::Apply(const BlockVector& v) {  // vector_prox.cc:140-183
   return r;
 }
 
-bool VectorProx::ScalarForm(std::string* var_key, std::string* constraint_key, double* Bs,
-                            double* Cs, double* lam, DVec* g) const {
+bool VectorProx::ScalarForm(SeparableDesc* d, bool offset) const {
   if (input_.elementwise_ || !D_.data().empty()) return false;
-  if (g == nullptr ? !g_.data().empty() : g_.data().size() > 1) return false;
+  if (offset ? g_.data().size() > 1 : !g_.data().empty()) return false;
   if (B_.data().size() != 1 || B_.data().begin()->second.size() != 1) return false;
   if (C_.data().size() != 1 || C_.data().begin()->second.size() != 1) return false;
   const auto& bcol = *B_.data().begin();  // (arg:0, constraint)
@@ -195,17 +191,15 @@ bool VectorProx::ScalarForm(std::string* var_key, std::string* constraint_key, d
   const LinearMap& Cm = ccol.second.begin()->second;
   if (Bm.impl().type() != SCALAR_MATRIX || Cm.impl().type() != SCALAR_MATRIX) return false;
   if (bcol.second.begin()->first != ccol.first) return false;  // both through arg:0
-  *constraint_key = bcol.first;
-  *var_key = ccol.second.begin()->first;
-  *Bs = GetScalar(Bm);
-  *Cs = GetScalar(Cm);
-  *lam = input_.lambda_;
-  if (g != nullptr) {
-    *g = DVec();
-    if (!g_.data().empty()) {
-      if (g_.data().begin()->first != ccol.first) return false;  // the offset of arg:0
-      *g = g_.data().begin()->second;
-    }
+  d->constraint_key = bcol.first;
+  d->var_key = ccol.second.begin()->first;
+  d->Bs = GetScalar(Bm);
+  d->Cs = GetScalar(Cm);
+  d->lam = input_.lambda_;
+  d->g = DVec();
+  if (!g_.data().empty()) {
+    if (g_.data().begin()->first != ccol.first) return false;  // the offset of arg:0
+    d->g = g_.data().begin()->second;
   }
   return true;
 }
@@ -300,15 +294,11 @@ class ScaledZoneProx final : public VectorProx {
   }
 
  public:
-  bool DescribeScaledZone(ScaledZoneDesc* d) const override { return Describe(d, false); }
-  bool DescribeScaledZoneOffset(ScaledZoneDesc* d) const override { return Describe(d, true); }
-
- private:
-  bool Describe(ScaledZoneDesc* d, bool offset) const {
-    if (has_axis_) return false;
-    d->g = DVec();
-    if (!ScalarForm(&d->var_key, &d->constraint_key, &d->Bs, &d->Cs, &d->lam, offset ? &d->g : nullptr))
-      return false;
+  // The zone, with the offset of its argument when there is one (d->g): a route that cannot take an
+  // offset refuses g.n != 0 itself.
+  bool DescribeSeparable(SeparableDesc* d) const override {
+    if (has_axis_ || !ScalarForm(d, /*offset=*/true)) return false;
+    d->kind = SeparableDesc::kZone;
     d->alpha = alpha_.value;
     d->beta = beta_.value;
     d->alpha_vec = alpha_.is_vec ? alpha_.vec : DVec();
@@ -431,9 +421,10 @@ class Norm2Prox final : public VectorProx {
   }
 
   // Group lasso: one group per row of the n x k argument, scalar maps.
-  bool DescribeGroupNorm2(GroupNorm2Desc* d) const override {
+  bool DescribeSeparable(SeparableDesc* d) const override {
     if (!has_axis_ || axis_ != 1 || rows_ < 1 || cols_ < 1) return false;
-    if (!ScalarForm(&d->var_key, &d->constraint_key, &d->Bs, &d->Cs, &d->lam)) return false;
+    if (!ScalarForm(d, /*offset=*/false)) return false;
+    d->kind = SeparableDesc::kRowGroups;
     d->rows = rows_;
     d->cols = cols_;
     return true;
@@ -493,6 +484,56 @@ class TotalVariation1DProx final : public VectorProx {
 };
 REGISTER_PROX_OPERATOR(TOTAL_VARIATION_1D, TotalVariation1DProx);
 
+// ---- what the describers ask of a block LDL^T -----------------------------------------------------------
+// The checks the pattern matchers of SumSquareProx and ZeroProx share, over an operator's
+// factorisation and the constant part `b` of its right-hand side.  Which of them a pattern imposes,
+// and on which keys, is the matcher's own statement.
+using Key = std::string;
+
+// The number of blocks M holds.
+size_t Blocks(const BlockMatrix& M) {
+  size_t count = 0;
+  for (const auto& col : M.data()) count += col.second.size();
+  return count;
+}
+// The scalar block at (r, c), its value in *a when asked for.  False: no block there, or not a
+// scalar matrix.
+bool ScalarAt(const BlockMatrix& M, const Key& r, const Key& c, double* a = nullptr) {
+  if (!M.has_key(r, c) || M(r, c).impl().type() != SCALAR_MATRIX) return false;
+  if (a != nullptr) *a = GetScalar(M(r, c));
+  return true;
+}
+// ... with exactly the value a.
+bool ScalarIs(const BlockMatrix& M, const Key& r, const Key& c, double a) {
+  double s = 0;
+  return ScalarAt(M, r, c, &s) && s == a;
+}
+// The dense block at (r, c), or null.
+std::shared_ptr<const DenseMatrixImpl> DenseAt(const BlockMatrix& M, const Key& r, const Key& c) {
+  if (!M.has_key(r, c) || M(r, c).impl().type() != DENSE_MATRIX) return nullptr;
+  return std::static_pointer_cast<const DenseMatrixImpl>(M(r, c).ptr());
+}
+
+struct Factored {
+  const BlockCholesky& chol;
+  const BlockVector& b;
+
+  const BlockMatrix& L() const { return chol.L(); }
+  const BlockMatrix& Di() const { return chol.D_inv(); }
+  // No refinement steps: a refined solve is not a closed form in L and Dinv (fp32 on
+  // ill-conditioned data: block.cc).
+  bool Exact() const { return chol.refine_steps() == 0; }
+  // The copy `vk` is tied to the constraint row `ck`: L(vk, ck) = -1, Dinv(ck) = -1.
+  bool Tied(const Key& vk, const Key& ck) const { return ScalarIs(L(), vk, ck, -1.0) && ScalarIs(Di(), ck, ck, -1.0); }
+  // The constant lies on the row `ak` alone (or there is none).
+  bool ConstantOn(const Key& ak) const {
+    for (const auto& kv : b.data())
+      if (kv.first != ak) return false;
+    return true;
+  }
+  DVec Constant(const Key& ak) const { return b.has_key(ak) ? b(ak) : DVec(); }
+};
+
 // ---- SumSquareProx: ||H(x)||_2^2 (reference prox/sum_square.cc:10-40) ---------------------------------
 
 class SumSquareProx final : public ProxOperator {
@@ -527,27 +568,24 @@ class SumSquareProx final : public ProxOperator {
   // pivots the only blocks, all scalar matrices.  The prox input has no entry on the arg row, so the
   // forward substitution reaches var from the constraint row alone and Solve(v)[var] =
   // Dinv(var) (-L(var, constraint) v_c).  Every other order keeps the generic path.
-  bool DescribeScalarLeastSquares(ScalarLeastSquaresDesc* d) const override {
-    const std::vector<std::string>& p = chol_.order();
-    if (chol_.refine_steps() > 0 || !h_scalar_ || !b_.data().empty()) return false;
+  // Bs and Cs are the two factors as the scalar maps' Apply forms them: alpha * scalar.
+  bool DescribeSeparable(SeparableDesc* d) const override {
+    const Factored f{chol_, b_};
+    const std::vector<Key>& p = chol_.order();
+    if (!f.Exact() || !h_scalar_ || !b_.data().empty()) return false;
     if (p.size() != 3 || var_keys_.size() != 1 || arg_keys_.size() != 1) return false;
-    const std::string &ak = p[0], &ck = p[1], &vk = p[2];
+    const Key &ak = p[0], &ck = p[1], &vk = p[2];
     if (vk != *var_keys_.begin() || ak != *arg_keys_.begin() || ck == ak || ck == vk) return false;
-    const BlockMatrix& L = chol_.L();
-    const BlockMatrix& Di = chol_.D_inv();
-    size_t blocks = 0;
-    for (const BlockMatrix* M : {&L, &Di})
-      for (const auto& col : M->data())
-        for (const auto& blk : col.second) {
-          if (blk.second.impl().type() != SCALAR_MATRIX) return false;
-          ++blocks;
-        }
-    if (blocks != 5 || !L.has_key(vk, ak) || !L.has_key(vk, ck)) return false;
-    if (!Di.has_key(ak, ak) || !Di.has_key(ck, ck) || !Di.has_key(vk, vk)) return false;
+    // five scalar blocks and no other
+    double l_var_con = 0, dinv_var = 0;  // the scalars as the factorisation holds them
+    if (Blocks(f.L()) + Blocks(f.Di()) != 5) return false;
+    if (!ScalarAt(f.L(), vk, ak) || !ScalarAt(f.L(), vk, ck, &l_var_con)) return false;
+    if (!ScalarAt(f.Di(), ak, ak) || !ScalarAt(f.Di(), ck, ck) || !ScalarAt(f.Di(), vk, vk, &dinv_var)) return false;
+    d->kind = SeparableDesc::kRidge;
     d->var_key = vk;
     d->constraint_key = ck;
-    d->l_var_con = GetScalar(L(vk, ck));
-    d->dinv_var = GetScalar(Di(vk, vk));
+    d->Bs = -1.0 * l_var_con;
+    d->Cs = 1.0 * dinv_var;
     return true;
   }
 
@@ -555,52 +593,39 @@ class SumSquareProx final : public ProxOperator {
   // L(var, constraint) = -1, Dinv(constraint) = -1, Dinv(var) = 1, L(arg, var) and Dinv(arg)
   // dense.  Then Solve(b_ + v)[var] = v_c + kappa * A^T (Dinv_arg (rhs_arg + kappa * A v_c)).
   bool DescribeLeastSquares(LeastSquaresDesc* d) const override {
-    const std::vector<std::string>& p = chol_.order();
-    // a refined solve is not the closed form below (fp32 on ill-conditioned data: block.cc)
-    if (chol_.refine_steps() > 0) return false;
-    if (p.size() == 2 && var_keys_.size() == 1) {
+    const Factored f{chol_, b_};
+    const std::vector<Key>& p = chol_.order();
+    if (!f.Exact() || var_keys_.size() != 1) return false;
+    if (p.size() == 2) {
       // Two-block driver: A = I on the term's own variable, whose id is then both a column and a
       // row key (prox_admm_two_block.cc:70-75), so the KKT matrix has the two keys [var, arg],
       // M(var, var) = I, and Solve(b_ + v)[var] = v + kappa A^T (Dinv_arg (rhs_arg + kappa A v)) again.
-      const std::string &vk = p[0], &ak = p[1];
-      if (vk != *var_keys_.begin()) return false;
-      const BlockMatrix& L = chol_.L();
-      const BlockMatrix& Di = chol_.D_inv();
-      if (!L.has_key(ak, vk) || !Di.has_key(vk, vk) || !Di.has_key(ak, ak)) return false;
-      if (Di(vk, vk).impl().type() != SCALAR_MATRIX || GetScalar(Di(vk, vk)) != 1.0) return false;
-      if (L(ak, vk).impl().type() != DENSE_MATRIX || Di(ak, ak).impl().type() != DENSE_MATRIX)
-        return false;
-      for (const auto& kv : b_.data())
-        if (kv.first != ak) return false;
+      const Key &vk = p[0], &ak = p[1];
+      if (vk != *var_keys_.begin() || !ScalarIs(f.Di(), vk, vk, 1.0) || !f.ConstantOn(ak)) return false;
+      d->L_arg_var = DenseAt(f.L(), ak, vk);
+      d->Dinv_arg = DenseAt(f.Di(), ak, ak);
+      if (!d->L_arg_var || !d->Dinv_arg) return false;
       d->constraint_key = vk;
       d->var_key = vk;
       d->arg_key = ak;
-      d->L_arg_var = std::static_pointer_cast<const DenseMatrixImpl>(L(ak, vk).ptr());
-      d->Dinv_arg = std::static_pointer_cast<const DenseMatrixImpl>(Di(ak, ak).ptr());
-      if (b_.has_key(ak)) d->rhs_arg = b_(ak);
+      d->rhs_arg = f.Constant(ak);
       return true;
     }
-    if (p.size() != 3 || var_keys_.size() != 1) return false;
-    if (p[2] == *var_keys_.begin()) return DescribeTall(d);
-    const std::string &ck = p[0], &vk = p[1], &ak = p[2];
+    if (p.size() != 3) return false;
+    if (p[2] == *var_keys_.begin()) return DescribeTall(f, d);
+    const Key &ck = p[0], &vk = p[1], &ak = p[2];
     if (vk != *var_keys_.begin()) return false;
-    const BlockMatrix& L = chol_.L();
-    const BlockMatrix& Di = chol_.D_inv();
-    if (!L.has_key(vk, ck) || !L.has_key(ak, vk) || L.has_key(ak, ck)) return false;
-    if (!Di.has_key(ck, ck) || !Di.has_key(vk, vk) || !Di.has_key(ak, ak)) return false;
-    if (!is_scalar(L(vk, ck), -1.0) || !is_scalar(Di(ck, ck), -1.0) || !is_scalar(Di(vk, vk), 1.0))
-      return false;
-    for (const auto& kv : b_.data())
-      if (kv.first != ak) return false;
+    if (!f.Tied(vk, ck) || !ScalarIs(f.Di(), vk, vk, 1.0) || f.L().has_key(ak, ck) || !f.ConstantOn(ak)) return false;
+    if (!f.L().has_key(ak, vk) || !f.Di().has_key(ak, ak)) return false;
     int64_t cols = 1, dcols = 1;
-    d->L_arg_var = DenseFactor(L(ak, vk), &cols);
-    d->Dinv_arg = DenseFactor(Di(ak, ak), &dcols);
+    d->L_arg_var = DenseFactor(f.L()(ak, vk), &cols);
+    d->Dinv_arg = DenseFactor(f.Di()(ak, ak), &dcols);
     if (!d->L_arg_var || !d->Dinv_arg || cols != dcols) return false;
     d->constraint_key = ck;
     d->var_key = vk;
     d->arg_key = ak;
     d->cols = cols;
-    d->rhs_arg = b_.has_key(ak) ? b_(ak) : DVec();
+    d->rhs_arg = f.Constant(ak);
     return true;
   }
 
@@ -610,28 +635,21 @@ class SumSquareProx final : public ProxOperator {
   // with b_arg = rhs_arg alone (v has no entry on the arg row); the back substitution writes rows
   // that Apply drops.  So Solve(b_ + v)[var] = Dinv(var) (v_c - L(var,arg) rhs_arg).
   // Vector variables alone: a Kronecker block (matrix variable) is not this form.
-  bool DescribeTall(LeastSquaresDesc* d) const {
-    const std::vector<std::string>& p = chol_.order();
-    const std::string &ck = p[0], &ak = p[1], &vk = p[2];
-    const BlockMatrix& L = chol_.L();
-    const BlockMatrix& Di = chol_.D_inv();
-    if (!L.has_key(vk, ck) || !L.has_key(vk, ak) || L.has_key(ak, ck)) return false;
-    if (!Di.has_key(ck, ck) || !Di.has_key(ak, ak) || !Di.has_key(vk, vk)) return false;
-    if (!is_scalar(L(vk, ck), -1.0) || !is_scalar(Di(ck, ck), -1.0)) return false;
-    if (Di(ak, ak).impl().type() != SCALAR_MATRIX) return false;
-    if (L(vk, ak).impl().type() != DENSE_MATRIX || Di(vk, vk).impl().type() != DENSE_MATRIX) return false;
-    for (const auto& kv : b_.data())
-      if (kv.first != ak) return false;
-    d->L_arg_var = std::static_pointer_cast<const DenseMatrixImpl>(L(vk, ak).ptr());
-    d->Dinv_arg = std::static_pointer_cast<const DenseMatrixImpl>(Di(vk, vk).ptr());
-    if (!d->L_arg_var->trans() || !d->Dinv_arg->symmetric()) return false;
+  // (Dinv(var) = 1 is not asked here: var carries the dense pivot.)
+  bool DescribeTall(const Factored& f, LeastSquaresDesc* d) const {
+    const std::vector<Key>& p = chol_.order();
+    const Key &ck = p[0], &ak = p[1], &vk = p[2];
+    if (!f.Tied(vk, ck) || f.L().has_key(ak, ck) || !f.ConstantOn(ak)) return false;
+    if (!ScalarAt(f.Di(), ak, ak, &d->dinv_arg)) return false;
+    d->L_arg_var = DenseAt(f.L(), vk, ak);
+    d->Dinv_arg = DenseAt(f.Di(), vk, vk);
+    if (!d->L_arg_var || !d->Dinv_arg || !d->L_arg_var->trans() || !d->Dinv_arg->symmetric()) return false;
     d->tall = true;
-    d->dinv_arg = GetScalar(Di(ak, ak));
     d->constraint_key = ck;
     d->var_key = vk;
     d->arg_key = ak;
     d->cols = 1;
-    d->rhs_arg = b_.has_key(ak) ? b_(ak) : DVec();
+    d->rhs_arg = f.Constant(ak);
     return true;
   }
 
@@ -714,51 +732,44 @@ class ZeroProx final : public ProxOperator {
   //   Solve(b_ + v)[x'] = v_x - L(arg,x')^T w,  [z'] = v_z - e w,
   //   w = Dinv_arg ((rhs_arg - e v_z) - L(arg,x') v_x).
   bool DescribeFat(ZeroProjectionDesc* d) const {
-    const std::vector<std::string>& p = chol_.order();
-    if (chol_.refine_steps() > 0) return false;
+    const Factored f{chol_, b_};
+    const std::vector<Key>& p = chol_.order();
+    if (!f.Exact()) return false;
     const size_t nv = var_keys_.size();
     if ((nv != 1 && nv != 2) || p.size() != 2 * nv + 1) return false;
-    const std::string& ak = p.back();
+    const Key& ak = p.back();
     if (var_keys_.count(ak) != 0) return false;
-    const BlockMatrix& L = chol_.L();
-    const BlockMatrix& Di = chol_.D_inv();
-    if (!Di.has_key(ak, ak) || Di(ak, ak).impl().type() != DENSE_MATRIX) return false;
+    const BlockMatrix& L = f.L();
     *d = ZeroProjectionDesc();
-    for (const std::string& vk : var_keys_) {
+    d->Dinv = DenseAt(f.Di(), ak, ak);
+    if (!d->Dinv) return false;
+    for (const Key& vk : var_keys_) {
       // its constraint row: the one key before the arg pivot whose column reaches vk
-      std::string ck;
+      Key ck;
       for (size_t i = 0; i + 1 < p.size(); ++i) {
         if (var_keys_.count(p[i]) != 0 || !L.has_key(vk, p[i])) continue;
         if (!ck.empty()) return false;
         ck = p[i];
       }
       if (ck.empty() || L.has_key(ak, ck) || !L.has_key(ak, vk)) return false;
-      if (!Di.has_key(ck, ck) || !Di.has_key(vk, vk)) return false;
-      if (!is_scalar(L(vk, ck), -1.0) || !is_scalar(Di(ck, ck), -1.0) || !is_scalar(Di(vk, vk), 1.0))
-        return false;
-      for (const std::string& other : var_keys_)
+      if (!f.Tied(vk, ck) || !ScalarIs(f.Di(), vk, vk, 1.0)) return false;
+      for (const Key& other : var_keys_)
         if (other != vk && (L.has_key(other, vk) || L.has_key(vk, other) || L.has_key(other, ck))) return false;
-      const LinearMap& Lav = L(ak, vk);
-      if (Lav.impl().type() == DENSE_MATRIX) {
+      if (auto dense = DenseAt(L, ak, vk)) {
         if (d->L) return false;
-        d->L = std::static_pointer_cast<const DenseMatrixImpl>(Lav.ptr());
+        d->L = dense;
         d->x_key = vk;
         d->x_constraint_key = ck;
-      } else if (Lav.impl().type() == SCALAR_MATRIX) {
-        if (!d->z_key.empty()) return false;
-        d->e = GetScalar(Lav);
+      } else if (d->z_key.empty() && ScalarAt(L, ak, vk, &d->e)) {
         d->z_key = vk;
         d->z_constraint_key = ck;
       } else {
         return false;
       }
     }
-    if (!d->L || d->L->trans() || (nv == 2 && d->z_key.empty())) return false;
-    for (const auto& kv : b_.data())
-      if (kv.first != ak) return false;
+    if (!d->L || d->L->trans() || (nv == 2 && d->z_key.empty()) || !f.ConstantOn(ak)) return false;
     d->arg_key = ak;
-    d->Dinv = std::static_pointer_cast<const DenseMatrixImpl>(Di(ak, ak).ptr());
-    d->rhs_arg = b_.has_key(ak) ? b_(ak) : DVec();
+    d->rhs_arg = f.Constant(ak);
     return true;
   }
 
@@ -769,48 +780,34 @@ class ZeroProx final : public ProxOperator {
   //   f_arg = rhs_arg - e v_z,  Solve(b_ + v)[x'] = Dinv(x') (v_x - L(x',arg) f_arg),
   //   arg = Dinv(arg) f_arg - L(x',arg)^T x',  [z'] = v_z - e arg.
   bool DescribeTall(ZeroProjectionDesc* d) const {
-    const std::vector<std::string>& p = chol_.order();
-    if (chol_.refine_steps() > 0) return false;
-    if (var_keys_.size() != 2 || p.size() != 5) return false;
-    const std::string &zk = p[2], &ak = p[3], &xk = p[4];
+    const Factored f{chol_, b_};
+    const std::vector<Key>& p = chol_.order();
+    if (!f.Exact() || var_keys_.size() != 2 || p.size() != 5) return false;
+    const Key &zk = p[2], &ak = p[3], &xk = p[4];
     if (var_keys_.count(zk) == 0 || var_keys_.count(xk) == 0 || var_keys_.count(ak) != 0) return false;
     if (var_keys_.count(p[0]) != 0 || var_keys_.count(p[1]) != 0) return false;
-    const BlockMatrix& L = chol_.L();
-    const BlockMatrix& Di = chol_.D_inv();
     // the constraint row of each copy: the one of the first two keys whose column reaches it
-    auto row_of = [&](const std::string& vk, std::string* ck) {
-      const bool r0 = L.has_key(vk, p[0]), r1 = L.has_key(vk, p[1]);
+    auto row_of = [&](const Key& vk, Key* ck) {
+      const bool r0 = f.L().has_key(vk, p[0]), r1 = f.L().has_key(vk, p[1]);
       if (r0 == r1) return false;
       *ck = r0 ? p[0] : p[1];
-      return Di.has_key(*ck, *ck) && is_scalar(L(vk, *ck), -1.0) && is_scalar(Di(*ck, *ck), -1.0);
+      return f.Tied(vk, *ck);
     };
-    std::string cx, cz;
-    if (!row_of(xk, &cx) || !row_of(zk, &cz) || cx == cz) return false;
-    // L holds these four blocks and no other
-    size_t blocks = 0;
-    for (const auto& col : L.data()) blocks += col.second.size();
-    if (blocks != 4 || !L.has_key(ak, zk) || !L.has_key(xk, ak)) return false;
-    if (!Di.has_key(zk, zk) || !Di.has_key(ak, ak) || !Di.has_key(xk, xk)) return false;
-    if (!is_scalar(Di(zk, zk), 1.0)) return false;
-    if (Di(ak, ak).impl().type() != SCALAR_MATRIX || L(ak, zk).impl().type() != SCALAR_MATRIX) return false;
-    if (L(xk, ak).impl().type() != DENSE_MATRIX || Di(xk, xk).impl().type() != DENSE_MATRIX) return false;
-    auto Lxa = std::static_pointer_cast<const DenseMatrixImpl>(L(xk, ak).ptr());
-    auto Dx = std::static_pointer_cast<const DenseMatrixImpl>(Di(xk, xk).ptr());
-    if (!Lxa->trans() || Dx->rows() != Lxa->m() || Dx->cols() != Lxa->m()) return false;
-    for (const auto& kv : b_.data())
-      if (kv.first != ak) return false;
     *d = ZeroProjectionDesc();
+    if (!row_of(xk, &d->x_constraint_key) || !row_of(zk, &d->z_constraint_key)) return false;
+    if (d->x_constraint_key == d->z_constraint_key) return false;
+    // L holds these four blocks and no other
+    if (Blocks(f.L()) != 4 || !ScalarAt(f.L(), ak, zk, &d->e)) return false;
+    if (!ScalarIs(f.Di(), zk, zk, 1.0) || !ScalarAt(f.Di(), ak, ak, &d->dinv_arg)) return false;
+    d->L = DenseAt(f.L(), xk, ak);
+    d->Dinv = DenseAt(f.Di(), xk, xk);
+    if (!d->L || !d->Dinv || !d->L->trans()) return false;
+    if (d->Dinv->rows() != d->L->m() || d->Dinv->cols() != d->L->m() || !f.ConstantOn(ak)) return false;
     d->tall = true;
     d->x_key = xk;
     d->z_key = zk;
     d->arg_key = ak;
-    d->x_constraint_key = cx;
-    d->z_constraint_key = cz;
-    d->L = Lxa;
-    d->Dinv = Dx;
-    d->dinv_arg = GetScalar(Di(ak, ak));
-    d->e = GetScalar(L(ak, zk));
-    d->rhs_arg = b_.has_key(ak) ? b_(ak) : DVec();
+    d->rhs_arg = f.Constant(ak);
     return true;
   }
 

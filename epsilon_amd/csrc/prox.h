@@ -53,41 +53,36 @@ struct LeastSquaresDesc {  // SumSquareProx after block elimination [constraint,
   bool tall = false;
   double dinv_arg = 0;
 };
-// SumSquareProx with a scalar argument map, no offset and one variable, in the order the fill model
-// gives this system, [arg, constraint, var], every block of the factorisation a scalar matrix.
+// A separable term in scalar form (scalar H and A, one weight for every element): with v the prox
+// input of the term's constraint row,
+//   x = Cs * (f(Bs*v + g) - g),
+// f by `kind`.  Each operator answers one kind; which kinds a route takes on which side, and whether
+// it takes an offset g, is the route's decision (fused_route.cc).
+struct SeparableDesc {
+  enum Kind {
+    kZone,       // ScaledZoneProx with uniform or per-element alpha / beta: f the scaled zone's prox
+    kSmooth,     // SmoothProxOp (SUM_LOGISTIC alone answers): f = prox_{lam fn}
+    kRowGroups,  // Norm2Prox with axis = 1 on a rows x cols argument: f the group shrinkage of each row
+    kRidge,      // SumSquareProx with a scalar argument map: f the identity, x = Cs * (Bs*v) (below)
+  };
+  Kind kind = kZone;
+  std::string var_key, constraint_key;
+  double Bs = 0, Cs = 0;  // v' = Bs*v ; x = Cs*x'
+  double lam = 0;         // (kRidge: not set, the weight is in Bs and Cs)
+  double alpha = 1, beta = 1, M = 0;       // kZone
+  DVec alpha_vec, beta_vec;                // kZone: per-element alpha / beta (SUM_QUANTILE with data vectors); empty: uniform
+  DVec g;                                  // kZone, kSmooth: constant offset of the argument (empty: none)
+  k::SmoothFn fn = k::SMOOTH_LOGISTIC;     // kSmooth
+  int64_t rows = 0, cols = 0;              // kRowGroups
+};
+// kRidge: SumSquareProx with a scalar argument map, no offset and one variable, in the order the fill
+// model gives this system, [arg, constraint, var], every block of the factorisation a scalar matrix.
 // Nothing reaches the var row in the forward substitution but the constraint row, and the back
 // substitution starts from it, so Solve(v)[var] is two scalar-map applies on the prox input,
-//   t = (-1 * l_var_con) v_c ;  x = (1 * dinv_var) t
+//   t = (-1 * L(var, constraint)) v_c ;  x = (1 * Dinv(var)) t
 // (block.cc Substitute, then D_inv *): each factor the product a scalar map's Apply narrows to the
-// compute type, one rounding per multiply.  In exact arithmetic x = a v / (a^2 + 2 alpha).
-struct ScalarLeastSquaresDesc {
-  std::string var_key, constraint_key;
-  double l_var_con = 0;  // L(var, constraint)'s scalar, as the factorisation holds it
-  double dinv_var = 0;   // Dinv(var)'s scalar, as the factorisation holds it
-};
-struct ScaledZoneDesc {  // ScaledZoneProx with scalar H, A and uniform parameters
-  std::string var_key, constraint_key;
-  double Bs = 0, Cs = 0;  // v' = Bs*v ; x = Cs*x'
-  double lam = 0, alpha = 1, beta = 1, M = 0;
-  DVec alpha_vec, beta_vec;  // per-element alpha / beta (SUM_QUANTILE with data vectors); empty: uniform
-  DVec g;  // constant offset of the argument, x = Cs * (zone(Bs*v + g) - g): DescribeScaledZoneOffset only
-};
-// A smooth separable term of the Newton family in the same scalar form,
-// x = Cs * (prox_{lam fn}(Bs*v + g) - g) with one weight for every element (SmoothProxOp;
-// SUM_LOGISTIC alone answers).
-struct SmoothSeparableDesc {
-  k::SmoothFn fn = k::SMOOTH_LOGISTIC;
-  std::string var_key, constraint_key;
-  double Bs = 0, Cs = 0, lam = 0;
-  DVec g;  // constant offset of the argument (empty: none)
-};
-
-struct GroupNorm2Desc {  // Norm2Prox with axis = 1 on an n x cols argument: one group per row
-  std::string var_key, constraint_key;
-  double Bs = 0, Cs = 0;  // v' = Bs*v ; x = Cs*x'
-  double lam = 0;
-  int64_t rows = 0, cols = 0;
-};
+// compute type, one rounding per multiply; Bs and Cs are these two factors, the scalars as the
+// factorisation holds them.  In exact arithmetic x = a v / (a^2 + 2 alpha).
 
 // ZeroProx after block elimination: the projection onto {C x' + e z' + d = 0} of the graph-form
 // problems, in one of two orders; v is the prox input.
@@ -118,12 +113,7 @@ class ProxOperator {  // reference prox/prox.h:37-43
   virtual void Init(const ProxOperatorArg& arg) {}
   virtual BlockVector Apply(const BlockVector& v) = 0;
   virtual bool DescribeLeastSquares(LeastSquaresDesc* d) const { return false; }
-  virtual bool DescribeScalarLeastSquares(ScalarLeastSquaresDesc* d) const { return false; }
-  virtual bool DescribeScaledZone(ScaledZoneDesc* d) const { return false; }
-  virtual bool DescribeGroupNorm2(GroupNorm2Desc* d) const { return false; }
-  // DescribeScaledZone for an argument that may carry a constant offset (d->g; empty: none)
-  virtual bool DescribeScaledZoneOffset(ScaledZoneDesc* d) const { return false; }
-  virtual bool DescribeSmoothSeparable(SmoothSeparableDesc* d) const { return false; }
+  virtual bool DescribeSeparable(SeparableDesc* d) const { return false; }
   virtual bool DescribeZeroProjection(ZeroProjectionDesc* d) const { return false; }
 };
 
@@ -187,11 +177,10 @@ class VectorProx : public ProxOperator {
   // and handles the axis itself; elementwise operators are axis-agnostic.
   virtual void ApplyVector(const VectorProxInput& input, VectorProxOutput* output) = 0;
 
-  // For DescribeScaledZone / DescribeSmoothSeparable: true iff B_, C_ are single scalar blocks,
-  // no offset, scalar lambda.
-  // With `g` an offset on the argument row is accepted and handed out (empty: there is none).
-  bool ScalarForm(std::string* var_key, std::string* constraint_key, double* Bs, double* Cs,
-                  double* lam, DVec* g = nullptr) const;
+  // For DescribeSeparable: true iff B_, C_ are single scalar blocks and lambda is a scalar; fills the
+  // keys, Bs, Cs, lam and g.  `offset`: a constant on the argument row is accepted and handed out in
+  // d->g (empty: there is none); without it any constant is refused.
+  bool ScalarForm(SeparableDesc* d, bool offset) const;
 
  private:
   BlockMatrix B_, C_, D_;

@@ -85,10 +85,11 @@ template <k::SmoothFn FN> class SmoothProxOp final : public VectorProx {
  public:
   // SUM_LOGISTIC alone: the domain projections of the others and the closed form of SUM_NEG_LOG
   // have no fused row chain.
-  bool DescribeSmoothSeparable(SmoothSeparableDesc* d) const override {
+  bool DescribeSeparable(SeparableDesc* d) const override {
     if (FN != k::SMOOTH_LOGISTIC) return false;
+    d->kind = SeparableDesc::kSmooth;
     d->fn = FN;
-    return ScalarForm(&d->var_key, &d->constraint_key, &d->Bs, &d->Cs, &d->lam, &d->g);
+    return ScalarForm(d, /*offset=*/true);
   }
 
  protected:
