@@ -665,6 +665,168 @@ def factor_op(op, n=0, a=None, a_off=0, form=-1, lo=0, cnt=0, out_cols=None, wan
     return out, out2
 
 
+class _SparseOp(ctypes.Structure):
+    _fields_ = [("op", ctypes.c_char_p),
+                ("rows", ctypes.c_int64), ("cols", ctypes.c_int64), ("nnz", ctypes.c_int64),
+                ("ptr", ctypes.c_void_p), ("ptr_len", ctypes.c_int64),
+                ("idx", ctypes.c_void_p), ("idx_len", ctypes.c_int64),
+                ("val", ctypes.c_void_p), ("val_len", ctypes.c_int64),
+                ("alpha", ctypes.c_double), ("beta", ctypes.c_double),
+                ("d", ctypes.c_void_p), ("d_len", ctypes.c_int64), ("ld", ctypes.c_int64), ("n", ctypes.c_int64),
+                ("y", ctypes.c_void_p), ("y_len", ctypes.c_int64)]
+
+
+def _set_indices(g, operands):
+    """As _set_operands for int32 arrays."""
+    keep = []
+    for name, v in operands:
+        if v is not None:
+            v = np.ascontiguousarray(v, dtype=np.int32).reshape(-1)
+            keep.append(v)
+            setattr(g, name, v.ctypes.data_as(ctypes.c_void_p))
+            setattr(g, name + "_len", v.size)
+    return keep
+
+
+def sparse_op(op, rows=0, cols=0, ptr=None, idx=None, val=None, nnz=None, alpha=1.0, beta=0.0, d=None,
+              ld=0, n=0, y=None):
+    """Test entry for the sparse layer (include/epsilon_hip.h eps_test_sparse_op): one call of the
+    launcher `op` names ("spmv", "spmm_csr_dense", "dense_spmm_csc", "scatter_add_csc") on the CSR
+    operand (ptr, idx, val), rows x cols, the dense operand d (copied verbatim, leading dimension
+    ld, n columns of B / rows of A) and the initial output y.  nnz defaults to the length of val.
+
+    Returns the output with its DENSE_OP_GUARD guard elements on each side (DENSE_OP_SENTINEL if
+    nothing stored outside the output)."""
+    L = lib()
+    L.eps_test_sparse_op.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    g = _SparseOp()
+    g.op = op.encode("utf-8") if op is not None else None
+    g.rows, g.cols, g.alpha, g.beta, g.ld, g.n = rows, cols, alpha, beta, ld, n
+    keep = _set_indices(g, (("ptr", ptr), ("idx", idx))) + _set_operands(g, (("val", val), ("d", d), ("y", y)))
+    g.nnz = g.val_len if nnz is None else nnz
+    out = np.full(g.y_len + 2 * DENSE_OP_GUARD, np.nan)
+    _check(L.eps_test_sparse_op(ctypes.byref(g), out.ctypes.data_as(ctypes.c_void_p)))
+    del keep
+    return out
+
+
+class _Csc(ctypes.Structure):
+    _fields_ = [("m", ctypes.c_int64), ("n", ctypes.c_int64), ("nnz", ctypes.c_int64),
+                ("colptr", ctypes.c_void_p), ("colptr_len", ctypes.c_int64),
+                ("rowidx", ctypes.c_void_p), ("rowidx_len", ctypes.c_int64),
+                ("val", ctypes.c_void_p), ("val_len", ctypes.c_int64)]
+
+
+class _CscOp(ctypes.Structure):
+    _fields_ = [("op", ctypes.c_char_p), ("a", _Csc), ("b", _Csc),
+                ("d", ctypes.c_void_p), ("d_len", ctypes.c_int64),
+                ("blob", ctypes.c_void_p), ("blob_len", ctypes.c_size_t),
+                ("colptr", ctypes.c_void_p), ("colptr_cap", ctypes.c_int64),
+                ("rowidx", ctypes.c_void_p), ("val", ctypes.c_void_p), ("nnz_cap", ctypes.c_int64)]
+
+
+def _set_csc(c, operand, keep):
+    """operand: (m, n, colptr, rowidx, val) or (m, n, colptr, rowidx, val, nnz); None entries stay null."""
+    if operand is None:
+        return 0
+    c.m, c.n = operand[0], operand[1]
+    keep += _set_indices(c, (("colptr", operand[2]), ("rowidx", operand[3])))
+    keep += _set_operands(c, (("val", operand[4]),))
+    c.nnz = operand[5] if len(operand) > 5 else c.val_len
+    return c.nnz
+
+
+def csc_op(op, a=None, b=None, d=None, blob=None, m=0, n=0, nnz=0, colptr_cap=None, nnz_cap=None):
+    """Test entry for the host CSC algebra (include/epsilon_hip.h eps_test_csc_op; no device):
+    "transpose", "add", "multiply", "kron", "scale_rows", "scale_cols" on the operands a and b, each
+    (m, n, colptr, rowidx, val); "from_dense" on the column-major m x n values d; "from_blob" on
+    the wire bytes `blob` of an m x n matrix with nnz entries.  The capacities of the result
+    buffers default to what the op can produce at most.
+
+    Returns (m, n, colptr, rowidx, val) of the result."""
+    L = lib()
+    L.eps_test_csc_op.argtypes = [ctypes.c_void_p] * 4
+    g = _CscOp()
+    g.op = op.encode("utf-8") if op is not None else None
+    keep = []
+    na, nb = _set_csc(g.a, a, keep), _set_csc(g.b, b, keep)
+    if a is None:
+        g.a.m, g.a.n, g.a.nnz = m, n, nnz
+    keep += _set_operands(g, (("d", d),))
+    if blob is not None:
+        blob = bytes(blob)
+        buf = ctypes.create_string_buffer(blob, max(len(blob), 1))
+        keep.append(buf)
+        g.blob, g.blob_len = ctypes.cast(buf, ctypes.c_void_p), len(blob)
+    if colptr_cap is None:
+        colptr_cap = max({"transpose": g.a.m, "add": g.a.n, "multiply": g.b.n, "kron": g.a.n * g.b.n}.get(op, g.a.n), 0) + 1
+    if nnz_cap is None:
+        nnz_cap = max({"add": na + nb, "multiply": g.a.m * g.b.n, "kron": na * nb, "from_dense": g.d_len,
+                       "from_blob": nnz}.get(op, na), 0)
+    colptr = np.zeros(max(colptr_cap, 1), dtype=np.int32)
+    rowidx = np.zeros(max(nnz_cap, 1), dtype=np.int32)
+    val = np.zeros(max(nnz_cap, 1), dtype=np.float64)
+    g.colptr, g.colptr_cap = colptr.ctypes.data_as(ctypes.c_void_p), colptr_cap
+    g.rowidx, g.val, g.nnz_cap = rowidx.ctypes.data_as(ctypes.c_void_p), val.ctypes.data_as(ctypes.c_void_p), nnz_cap
+    rm, rn, rnnz = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    _check(L.eps_test_csc_op(ctypes.byref(g), ctypes.byref(rm), ctypes.byref(rn), ctypes.byref(rnnz)))
+    del keep
+    return rm.value, rn.value, colptr[:rn.value + 1].copy(), rowidx[:rnnz.value].copy(), val[:rnnz.value].copy()
+
+
+class _SparseHandleOp(ctypes.Structure):
+    _fields_ = [("op", ctypes.c_char_p), ("sparse_map", ctypes.c_void_p), ("len", ctypes.c_size_t),
+                ("data", ctypes.c_void_p), ("ndata", ctypes.c_size_t),
+                ("transpose", ctypes.c_int), ("scaled", ctypes.c_int), ("scale", ctypes.c_double),
+                ("p", ctypes.c_void_p), ("p_len", ctypes.c_int64),
+                ("d", ctypes.c_void_p), ("d_rows", ctypes.c_int64), ("d_cols", ctypes.c_int64)]
+
+
+def sparse_handle_op(op, S, d, transpose=False, scale=None, p=None):
+    """Test entry for a sparse map handle as an operand (include/epsilon_hip.h
+    eps_test_sparse_handle_op): the handle is the sparse ir.LMap S, transposed with `transpose`,
+    then multiplied by the scalar map scale * I unless scale is None; `op` ("apply", "adjoint",
+    "sparse_dense", "dense_sparse", "sparse_plus_dense", "dense_plus_sparse") combines it with the
+    dense operand d (1-D for "apply" / "adjoint").  With p the map as built is applied to p first.
+
+    Returns the result (2-D for the products and sums), or (result, S p) with p."""
+    L = lib()
+    L.eps_test_sparse_handle_op.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+    g = _SparseHandleOp()
+    g.op = op.encode("utf-8") if op is not None else None
+    keep = []
+    sm, sn = 0, 0
+    if S is not None:
+        payload = S if isinstance(S, (bytes, bytearray)) else S.proto.SerializeToString()
+        buf = ctypes.create_string_buffer(bytes(payload), max(len(payload), 1))
+        keep.append(buf)
+        g.sparse_map, g.len = ctypes.cast(buf, ctypes.c_void_p), len(payload)
+        if not isinstance(S, (bytes, bytearray)):
+            blobs, nb = _blobs(S.data, keep)
+            keep.append(blobs)
+            g.data, g.ndata = ctypes.cast(blobs, ctypes.c_void_p), nb
+            sm, sn = (S.n, S.m) if transpose else (S.m, S.n)
+    g.transpose, g.scaled, g.scale = int(transpose), int(scale is not None), 1.0 if scale is None else scale
+    if d is not None:
+        d = np.asarray(d, dtype=np.float64)
+        g.d_rows, g.d_cols = d.shape[0], (1 if d.ndim == 1 else d.shape[1])
+        d = np.asfortranarray(d)
+        keep.append(d)
+        g.d = d.ctypes.data_as(ctypes.c_void_p)
+    keep += _set_operands(g, (("p", p),))
+    shape = {"apply": (sm, 1), "adjoint": (sn, 1), "sparse_dense": (sm, g.d_cols), "dense_sparse": (g.d_rows, sn)}.get(
+        op, (sm, sn))
+    out = np.full(max(shape[0] * shape[1], 1), np.nan)
+    out2 = np.full(max(S.m, 1), np.nan) if p is not None and S is not None and not isinstance(S, (bytes, bytearray)) else None
+    _check(L.eps_test_sparse_handle_op(ctypes.byref(g), out.ctypes.data_as(ctypes.c_void_p),
+                                       ctypes.c_int64(shape[0] * shape[1]),
+                                       out2.ctypes.data_as(ctypes.c_void_p) if out2 is not None else None))
+    del keep
+    res = out[:shape[0] * shape[1]]
+    res = res if op in ("apply", "adjoint") else res.reshape(shape, order="F")
+    return res if p is None else (res, out2[:S.m])
+
+
 def tv1d(v, lam):
     v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
     x = np.empty_like(v)

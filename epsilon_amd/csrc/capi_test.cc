@@ -1,5 +1,6 @@
 // extern "C" boundary, the per-operator test entries: eps_linear_map_*, eps_test_*, eps_fused_residency*
-// of include/epsilon_hip.h.  Each checks its arguments on the host before any device work starts.
+// of include/epsilon_hip.h.  Each checks its arguments on the host before any device work starts
+// (eps_test_csc_op, the host CSC algebra, starts none at all).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -10,6 +11,7 @@
 
 #include "block.h"
 #include "capi_util.h"
+#include "sparse.h"
 
 using namespace eps;
 using namespace eps::capi;
@@ -402,6 +404,194 @@ FactorOpArgs CheckFactorOpArgs(const eps_factor_op* g, const double* out) {
   return a;
 }
 
+// ---- eps_test_sparse_op, eps_test_csc_op -------------------------------------------------------------
+
+// A compressed structure as an entry was given it: `outer` compressed rows (CSR) or columns (CSC)
+// whose indices lie in [0, inner).  ptr_name / idx_name are the argument names in the messages.
+struct Compressed {
+  const char *ptr_name, *idx_name, *outer_name, *inner_name;
+  int64_t outer, inner, nnz;
+  const int32_t* ptr; int64_t ptr_len;
+  const int32_t* idx; int64_t idx_len;
+  const double* val;  int64_t val_len;
+};
+
+// Everything that lets the structure be indexed safely: sizes, pointer array, index range; with
+// `ascending` also the HostCsc invariant (indices strictly ascending within each outer slice).
+void CheckCompressed(const char* fn, const Compressed& s, bool ascending) {
+  const int64_t lim = int64_t(1) << 31;  // int32 structure
+  EPS_CHECK_MSG(s.outer >= 0, fn << s.outer_name << " is negative: " << s.outer);
+  EPS_CHECK_MSG(s.inner >= 0, fn << s.inner_name << " is negative: " << s.inner);
+  EPS_CHECK_MSG(s.nnz >= 0, fn << "nnz is negative: " << s.nnz);
+  EPS_CHECK_MSG(s.outer < lim - 1 && s.inner < lim && s.nnz < lim,
+                fn << s.outer_name << ", " << s.inner_name << " and nnz must be below 2^31");
+  EPS_CHECK_MSG(s.ptr != nullptr, fn << s.ptr_name << " is null");
+  EPS_CHECK_MSG(s.nnz == 0 || s.idx != nullptr, fn << s.idx_name << " is null");
+  EPS_CHECK_MSG(s.nnz == 0 || s.val != nullptr, fn << "val is null");
+  EPS_CHECK_MSG(s.ptr_len == s.outer + 1, fn << s.ptr_name << " has " << s.ptr_len << " entries, " << s.outer_name
+                                             << " + 1 is " << s.outer + 1);
+  EPS_CHECK_MSG(s.idx_len == s.nnz, fn << s.idx_name << " has " << s.idx_len << " entries, nnz is " << s.nnz);
+  EPS_CHECK_MSG(s.val_len == s.nnz, fn << "val has " << s.val_len << " entries, nnz is " << s.nnz);
+  EPS_CHECK_MSG(s.ptr[0] == 0, fn << s.ptr_name << "[0] is " << s.ptr[0] << ", not 0");
+  for (int64_t i = 0; i < s.outer; ++i)
+    EPS_CHECK_MSG(s.ptr[i] <= s.ptr[i + 1], fn << s.ptr_name << " is not monotone at " << i << ": " << s.ptr[i]
+                                               << " > " << s.ptr[i + 1]);
+  EPS_CHECK_MSG(s.ptr[s.outer] == s.nnz, fn << s.ptr_name << " ends at " << s.ptr[s.outer] << ", nnz is " << s.nnz);
+  for (int64_t i = 0; i < s.outer; ++i)
+    for (int32_t p = s.ptr[i]; p < s.ptr[i + 1]; ++p) {
+      EPS_CHECK_MSG(s.idx[p] >= 0 && s.idx[p] < s.inner, fn << s.idx_name << "[" << p << "] = " << s.idx[p]
+                                                            << " is outside [0, " << s.inner << ")");
+      EPS_CHECK_MSG(!ascending || p == s.ptr[i] || s.idx[p] > s.idx[p - 1],
+                    fn << s.idx_name << " is not strictly ascending at " << p);
+    }
+}
+
+// the structure as the host matrix whose columns are its outer slices
+HostCsc HostCscOf(const Compressed& s) {
+  HostCsc A;
+  A.m = s.inner;
+  A.n = s.outer;
+  A.colptr.assign(s.ptr, s.ptr + s.ptr_len);
+  if (s.nnz > 0) {
+    A.rowidx.assign(s.idx, s.idx + s.nnz);
+    A.val.assign(s.val, s.val + s.nnz);
+  }
+  return A;
+}
+
+// The argument checks of eps_test_sparse_op, host only: nothing malformed reaches a kernel.
+struct SparseOpArgs {
+  enum Op { SPMV, SPMM_CSR_DENSE, DENSE_SPMM_CSC, SCATTER_ADD_CSC } op;
+  Compressed csr;
+};
+
+SparseOpArgs CheckSparseOpArgs(const eps_sparse_op* g, const double* out) {
+  const char* const fn = "eps_test_sparse_op: ";
+  SparseOpArgs a;
+  EPS_CHECK_MSG(g != nullptr, fn << "args is null");
+  EPS_CHECK_MSG(g->op != nullptr, fn << "op is null");
+  const std::string op(g->op);
+  if (op == "spmv") a.op = SparseOpArgs::SPMV;
+  else if (op == "spmm_csr_dense") a.op = SparseOpArgs::SPMM_CSR_DENSE;
+  else if (op == "dense_spmm_csc") a.op = SparseOpArgs::DENSE_SPMM_CSC;
+  else if (op == "scatter_add_csc") a.op = SparseOpArgs::SCATTER_ADD_CSC;
+  else EPS_FATAL(fn << "op must be spmv, spmm_csr_dense, dense_spmm_csc or scatter_add_csc, got " << op);
+  EPS_CHECK_MSG(out != nullptr, fn << "out is null");
+  a.csr = {"ptr", "idx", "rows", "cols", g->rows, g->cols, g->nnz, g->ptr, g->ptr_len,
+           g->idx, g->idx_len, g->val, g->val_len};
+  CheckCompressed(fn, a.csr, false);
+  const int64_t rows = g->rows, cols = g->cols, n = g->n, ld = g->ld;
+  const Operand D = {"d", g->d, g->d_len, 0}, Y = {"y", g->y, g->y_len, 0};
+  CheckOperandSigns(fn, {D, Y});
+  const bool product = a.op == SparseOpArgs::SPMM_CSR_DENSE || a.op == SparseOpArgs::DENSE_SPMM_CSC;
+  if (a.op != SparseOpArgs::SPMV)
+    EPS_CHECK_MSG(g->beta == 0.0, fn << "beta is given (" << g->beta << "), " << op << " has none");
+  if (product) {
+    EPS_CHECK_MSG(n >= 0, fn << "n is negative: " << n);
+    EPS_CHECK_MSG(n < (int64_t(1) << 31), fn << "n must be below 2^31");
+    // d: `held` rows per column, `count` columns
+    const int64_t held = a.op == SparseOpArgs::SPMM_CSR_DENSE ? cols : n;
+    const int64_t count = a.op == SparseOpArgs::SPMM_CSR_DENSE ? n : cols;
+    EPS_CHECK_MSG(ld >= held, fn << "ld " << ld << " < rows " << held);
+    EPS_CHECK_MSG(ld < (int64_t(1) << 31), fn << "ld must be below 2^31");
+    // as the launchers ask: (count - 1) ld + held, whatever is empty
+    NeedOperand(fn, D, std::max<int64_t>((count - 1) * ld + held, 0));
+    NeedOperand(fn, Y, rows * n);
+  } else {
+    EPS_CHECK_MSG(n == 0, fn << "n is given (" << n << "), " << op << " has none");
+    EPS_CHECK_MSG(ld == 0, fn << "ld is given (" << ld << "), " << op << " has none");
+    if (a.op == SparseOpArgs::SPMV) {
+      NeedOperand(fn, D, cols);
+      NeedOperand(fn, Y, rows);
+    } else {
+      EPS_CHECK_MSG(g->d == nullptr && g->d_len == 0, fn << "d is given, " << op << " has none");
+      NeedOperand(fn, Y, rows * cols);
+    }
+  }
+  return a;
+}
+
+// The argument checks of eps_test_csc_op.
+struct CscOpArgs {
+  enum Op { TRANSPOSE, ADD, MULTIPLY, KRON, SCALE_ROWS, SCALE_COLS, FROM_DENSE, FROM_BLOB } op;
+  bool use_a = false, use_b = false;
+};
+
+Compressed CompressedOf(const char* ptr_name, const char* idx_name, const char* m_name, const char* n_name,
+                        const eps_csc& c) {
+  return {ptr_name, idx_name, n_name, m_name, c.n, c.m, c.nnz, c.colptr, c.colptr_len,
+          c.rowidx, c.rowidx_len, c.val, c.val_len};
+}
+
+CscOpArgs CheckCscOpArgs(const eps_csc_op* g, const int64_t* m, const int64_t* n, const int64_t* nnz) {
+  const char* const fn = "eps_test_csc_op: ";
+  CscOpArgs a;
+  EPS_CHECK_MSG(g != nullptr, fn << "args is null");
+  EPS_CHECK_MSG(g->op != nullptr, fn << "op is null");
+  const std::string op(g->op);
+  if (op == "transpose") a.op = CscOpArgs::TRANSPOSE;
+  else if (op == "add") a.op = CscOpArgs::ADD;
+  else if (op == "multiply") a.op = CscOpArgs::MULTIPLY;
+  else if (op == "kron") a.op = CscOpArgs::KRON;
+  else if (op == "scale_rows") a.op = CscOpArgs::SCALE_ROWS;
+  else if (op == "scale_cols") a.op = CscOpArgs::SCALE_COLS;
+  else if (op == "from_dense") a.op = CscOpArgs::FROM_DENSE;
+  else if (op == "from_blob") a.op = CscOpArgs::FROM_BLOB;
+  else
+    EPS_FATAL(fn << "op must be transpose, add, multiply, kron, scale_rows, scale_cols, from_dense or from_blob, "
+                    "got " << op);
+  EPS_CHECK_MSG(m != nullptr && n != nullptr && nnz != nullptr, fn << "m, n or nnz is null");
+  EPS_CHECK_MSG(g->colptr != nullptr, fn << "colptr is null");
+  EPS_CHECK_MSG(g->colptr_cap >= 0, fn << "colptr_cap is negative: " << g->colptr_cap);
+  EPS_CHECK_MSG(g->nnz_cap >= 0, fn << "nnz_cap is negative: " << g->nnz_cap);
+  EPS_CHECK_MSG(g->nnz_cap == 0 || (g->rowidx != nullptr && g->val != nullptr), fn << "rowidx or val is null");
+  EPS_CHECK_MSG(g->d_len >= 0, fn << "d_len is negative: " << g->d_len);
+  const bool sized_only = a.op == CscOpArgs::FROM_DENSE || a.op == CscOpArgs::FROM_BLOB;
+  a.use_a = !sized_only;
+  a.use_b = a.op == CscOpArgs::ADD || a.op == CscOpArgs::MULTIPLY || a.op == CscOpArgs::KRON;
+  if (a.use_a) CheckCompressed(fn, CompressedOf("a.colptr", "a.rowidx", "a.m", "a.n", g->a), true);
+  if (a.use_b) CheckCompressed(fn, CompressedOf("b.colptr", "b.rowidx", "b.m", "b.n", g->b), true);
+  const Operand D = {"d", g->d, g->d_len, 0};
+  const int64_t lim = int64_t(1) << 31;
+  switch (a.op) {
+    case CscOpArgs::ADD:
+      EPS_CHECK_MSG(g->a.m == g->b.m && g->a.n == g->b.n, fn << "add: a is " << g->a.m << " x " << g->a.n << ", b is "
+                                                             << g->b.m << " x " << g->b.n);
+      break;
+    case CscOpArgs::MULTIPLY:
+      EPS_CHECK_MSG(g->a.n == g->b.m, fn << "multiply: a has " << g->a.n << " columns, b has " << g->b.m << " rows");
+      break;
+    case CscOpArgs::SCALE_ROWS:
+    case CscOpArgs::SCALE_COLS: {
+      const int64_t need = a.op == CscOpArgs::SCALE_ROWS ? g->a.m : g->a.n;
+      EPS_CHECK_MSG(g->d != nullptr, fn << "d is null");
+      EPS_CHECK_MSG(g->d_len == 1 || g->d_len == need, fn << "d has " << g->d_len << " entries, " << op
+                                                          << " needs 1 or " << need);
+      break;
+    }
+    case CscOpArgs::FROM_DENSE:
+    case CscOpArgs::FROM_BLOB:
+      EPS_CHECK_MSG(g->a.m >= 0, fn << "a.m is negative: " << g->a.m);
+      EPS_CHECK_MSG(g->a.n >= 0, fn << "a.n is negative: " << g->a.n);
+      EPS_CHECK_MSG(g->a.m < lim && g->a.n < lim - 1, fn << "a.m and a.n must be below 2^31");
+      if (a.op == CscOpArgs::FROM_DENSE) {
+        EPS_CHECK_MSG(g->a.n == 0 || g->a.m <= (lim - 1) / g->a.n, fn << "a.m * a.n must be below 2^31");
+        NeedOperand(fn, D, g->a.m * g->a.n);
+      } else {
+        EPS_CHECK_MSG(g->a.nnz >= 0, fn << "nnz is negative: " << g->a.nnz);
+        EPS_CHECK_MSG(g->a.nnz < lim, fn << "nnz must be below 2^31");
+        EPS_CHECK_MSG(g->blob != nullptr, fn << "blob is null");
+      }
+      break;
+    default: break;
+  }
+  return a;
+}
+
+HostCsc HostCscOf(const char* ptr_name, const eps_csc& c) {
+  return HostCscOf(CompressedOf(ptr_name, "", "", "", c));
+}
+
 }  // namespace
 
 extern "C" {
@@ -721,6 +911,150 @@ int eps_test_factor_op(const eps_factor_op* g, double* out, double* out2) {
     EPS_HIP(hipGetLastError());
     o_all.Slice(g->a_off, len + 2 * G).ToHost(out);
     if (out2 != nullptr && n > 0) W.ToHost(out2);
+  });
+}
+
+int eps_test_sparse_op(const eps_sparse_op* g, double* out) {
+  return Guard([&] {
+    const SparseOpArgs args = CheckSparseOpArgs(g, out);
+    const DType dt = ConfiguredDType();
+    constexpr int64_t G = EPS_DENSE_OP_GUARD;
+    // the CSR arrays of S are the CSC arrays of S^T
+    const std::shared_ptr<DeviceCsr> S = UploadAsCsrOfTranspose(HostCscOf(args.csr), dt);
+    DVec d_all, y_all, d;
+    if (args.op != SparseOpArgs::SCATTER_ADD_CSC) d = PlaceOperand(g->d, g->d_len, 0, 0, dt, &d_all);
+    const DVec y = PlaceOperand(g->y, g->y_len, 0, G, dt, &y_all);
+    switch (args.op) {
+      case SparseOpArgs::SPMV: k::SpmvCsr(*S, g->alpha, d, g->beta, y); break;
+      case SparseOpArgs::SPMM_CSR_DENSE: k::SpmmCsrDense(*S, g->alpha, d, g->ld, g->n, y); break;
+      case SparseOpArgs::DENSE_SPMM_CSC: k::DenseSpmmCsc(*S, g->alpha, d, g->ld, g->n, y); break;
+      case SparseOpArgs::SCATTER_ADD_CSC: k::ScatterAddCsc(*S, g->alpha, y); break;
+    }
+    EPS_HIP(hipGetLastError());
+    y_all.ToHost(out);
+  });
+}
+
+int eps_test_csc_op(const eps_csc_op* g, int64_t* m, int64_t* n, int64_t* nnz) {
+  return Guard([&] {
+    const char* const fn = "eps_test_csc_op: ";
+    const CscOpArgs args = CheckCscOpArgs(g, m, n, nnz);
+    HostCsc A, B, C;
+    if (args.use_a) A = HostCscOf("a.colptr", g->a);
+    if (args.use_b) B = HostCscOf("b.colptr", g->b);
+    const std::vector<double> d(g->d, g->d + (g->d != nullptr ? g->d_len : 0));
+    switch (args.op) {
+      case CscOpArgs::TRANSPOSE: C = CscTranspose(A); break;
+      case CscOpArgs::ADD: C = CscAdd(A, B); break;
+      case CscOpArgs::MULTIPLY: C = CscMultiply(A, B); break;
+      case CscOpArgs::KRON: C = CscKron(A, B); break;
+      case CscOpArgs::SCALE_ROWS: C = CscScaleRows(A, d); break;
+      case CscOpArgs::SCALE_COLS: C = CscScaleCols(A, d); break;
+      case CscOpArgs::FROM_DENSE: C = CscFromDense(d, g->a.m, g->a.n); break;
+      case CscOpArgs::FROM_BLOB: {
+        pb::Constant c;
+        c.constant_type = pb::Constant::SPARSE_MATRIX;
+        c.m = static_cast<int32_t>(g->a.m);
+        c.n = static_cast<int32_t>(g->a.n);
+        c.nnz = static_cast<int32_t>(g->a.nnz);
+        c.data_location = "blob";
+        C = CscFromBlob(c, g->blob, g->blob_len);
+        break;
+      }
+    }
+    EPS_CHECK_MSG(static_cast<int64_t>(C.colptr.size()) == C.n + 1 && C.rowidx.size() == C.val.size(),
+                  fn << "the result's arrays do not fit its size");
+    EPS_CHECK_MSG(g->colptr_cap >= C.n + 1, fn << "colptr_cap " << g->colptr_cap << " < n + 1 = " << C.n + 1);
+    EPS_CHECK_MSG(g->nnz_cap >= C.nnz(), fn << "nnz_cap " << g->nnz_cap << " < nnz = " << C.nnz());
+    std::memcpy(g->colptr, C.colptr.data(), C.colptr.size() * sizeof(int32_t));
+    if (C.nnz() > 0) {
+      std::memcpy(g->rowidx, C.rowidx.data(), C.rowidx.size() * sizeof(int32_t));
+      std::memcpy(g->val, C.val.data(), C.val.size() * sizeof(double));
+    }
+    *m = C.m;
+    *n = C.n;
+    *nnz = C.nnz();
+  });
+}
+
+int eps_test_sparse_handle_op(const eps_sparse_handle_op* g, double* out, int64_t out_cap, double* out2) {
+  return Guard([&] {
+    const char* const fn = "eps_test_sparse_handle_op: ";
+    EPS_CHECK_MSG(g != nullptr, fn << "args is null");
+    EPS_CHECK_MSG(g->op != nullptr, fn << "op is null");
+    const std::string op(g->op);
+    enum { APPLY, ADJOINT, SD, DS, SPD, DPS } what;
+    if (op == "apply") what = APPLY;
+    else if (op == "adjoint") what = ADJOINT;
+    else if (op == "sparse_dense") what = SD;
+    else if (op == "dense_sparse") what = DS;
+    else if (op == "sparse_plus_dense") what = SPD;
+    else if (op == "dense_plus_sparse") what = DPS;
+    else
+      EPS_FATAL(fn << "op must be apply, adjoint, sparse_dense, dense_sparse, sparse_plus_dense or "
+                      "dense_plus_sparse, got " << op);
+    EPS_CHECK_MSG(g->sparse_map != nullptr && g->len > 0, fn << "sparse_map is null or empty");
+    EPS_CHECK_MSG(g->ndata == 0 || g->data != nullptr, fn << "data is null with ndata " << g->ndata);
+    EPS_CHECK_MSG(out != nullptr, fn << "out is null");
+    EPS_CHECK_MSG(g->d != nullptr, fn << "d is null");
+    EPS_CHECK_MSG(g->d_rows >= 0 && g->d_cols >= 0 && g->d_rows < (int64_t(1) << 31) && g->d_cols < (int64_t(1) << 31),
+                  fn << "d_rows and d_cols must be 0..2^31, got " << g->d_rows << " x " << g->d_cols);
+    EPS_CHECK_MSG(g->p == nullptr || out2 != nullptr, fn << "out2 is null with p given");
+    pb::LinearMap proto;
+    try {
+      proto = pb::ParseLinearMap(g->sparse_map, g->len);
+    } catch (const std::exception& e) {
+      EPS_FATAL(fn << "malformed LinearMap: " << e.what());
+    }
+    EPS_CHECK_MSG(proto.linear_map_type == pb::LinearMap::SPARSE_MATRIX,
+                  fn << "sparse_map is not a sparse matrix: type " << proto.linear_map_type);
+    // the handle's size from the payload alone, so that the sizes are checked before any device work
+    const int64_t hm = g->transpose ? proto.n : proto.m, hn = g->transpose ? proto.m : proto.n;
+    int64_t need_rows = 0, need_cols = g->d_cols, rm = 0, rn = 0;
+    switch (what) {
+      case APPLY: need_rows = hn, need_cols = 1, rm = hm, rn = 1; break;
+      case ADJOINT: need_rows = hm, need_cols = 1, rm = hn, rn = 1; break;
+      case SD: need_rows = hn, rm = hm, rn = g->d_cols; break;
+      case DS: need_rows = g->d_rows, need_cols = hm, rm = g->d_rows, rn = hn; break;
+      case SPD:
+      case DPS: need_rows = hm, need_cols = hn, rm = hm, rn = hn; break;
+    }
+    EPS_CHECK_MSG(g->d_rows == need_rows && g->d_cols == need_cols,
+                  fn << "d is " << g->d_rows << " x " << g->d_cols << ", " << op << " with a " << hm << " x " << hn
+                     << " handle needs " << need_rows << " x " << need_cols);
+    EPS_CHECK_MSG(out_cap >= rm * rn, fn << "out_cap " << out_cap << " < the " << rm * rn << " entries of the result");
+    EPS_CHECK_MSG(g->p == nullptr || g->p_len == proto.n, fn << "p has " << g->p_len << " entries, the map has "
+                                                             << proto.n << " columns");
+    const DType dt = ConfiguredDType();
+    SetCurrentDType(dt);
+    auto dm = MakeDataMap(g->data, g->ndata, dt);
+    const LinearMap S = BuildLinearMap(proto, dm.get());
+    EPS_CHECK_MSG(S.impl().m() == proto.m && S.impl().n() == proto.n, fn << "the constant is " << S.impl().m() << " x "
+                                                                         << S.impl().n() << ", the LinearMap says "
+                                                                         << proto.m << " x " << proto.n);
+    if (g->p != nullptr) {
+      DVec pd = DVec::FromHost(g->p, g->p_len, dt);
+      DVec qd = DVec::Empty(proto.m, dt);
+      S.impl().Apply(1.0, pd, 0.0, qd);
+      qd.ToHost(out2);
+    }
+    LinearMap H = g->transpose ? S.Transpose() : S;
+    if (g->scaled) H = LinearMap::Scalar(g->scale, H.impl().m()) * H;
+    EPS_CHECK_MSG(H.impl().type() == SPARSE_MATRIX, fn << "the handle became " << H.impl().DebugString());
+    DVec dd = DVec::FromHost(g->d, g->d_rows * g->d_cols, dt);
+    if (what == APPLY || what == ADJOINT) {
+      const LinearMap M = what == APPLY ? H : H.Transpose();
+      DVec yd = DVec::Empty(rm, dt);
+      M.impl().Apply(1.0, dd, 0.0, yd);
+      yd.ToHost(out);
+      return;
+    }
+    const LinearMap D = LinearMap::Dense(dd, g->d_rows, g->d_cols);
+    const LinearMap C = what == SD ? H * D : what == DS ? D * H : what == SPD ? H + D : D + H;
+    EPS_CHECK_MSG(C.impl().type() == DENSE_MATRIX && C.impl().m() == rm && C.impl().n() == rn,
+                  fn << "the result is " << C.impl().DebugString());
+    const std::vector<double> R = C.impl().AsDenseHost();
+    std::memcpy(out, R.data(), R.size() * sizeof(double));
   });
 }
 

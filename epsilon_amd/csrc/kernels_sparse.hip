@@ -12,6 +12,8 @@
 // combinations of dense columns (coalesced), output rows of S*B are gathered per column of B.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "sparse.h"
 
 namespace eps {
@@ -20,6 +22,7 @@ namespace k {
 namespace {
 
 constexpr int kBlock = 256;
+constexpr int64_t kMaxGridY = 65535;  // the largest gridDim.y of a launch
 
 template <class T, int LANES>
 __global__ __launch_bounds__(kBlock) void SpmvCsrKernel(int64_t rows,
@@ -172,13 +175,16 @@ void SpmmCsrDense(const DeviceCsr& S, double alpha, const DVec& B, int64_t ldb, 
   EPS_CHECK(ldb >= S.cols && B.n >= (N - 1) * ldb + S.cols && C.n == S.rows * N && B.dt == C.dt);
   CheckVals(S, B);
   if (S.rows == 0 || N == 0) return;
-  EPS_CHECK_MSG(N <= 65535, "SpmmCsrDense: too many columns");
   ProfScope prof("spmm_csr_dense", S.rows, N);
-  dim3 grid(static_cast<unsigned>((S.rows + kBlock - 1) / kBlock), static_cast<unsigned>(N));
-  EPS_DISPATCH(B.dt, hipLaunchKernelGGL((SpmmCsrDenseKernel<T>), grid, dim3(kBlock), 0,
-                                        Runtime::Get().stream(), S.rows, S.rowptr(), S.colidx(),
-                                        S.val.as<T>(), B.as<T>(), ldb, static_cast<T>(alpha),
-                                        C.as<T>()));
+  // blockIdx.y is the column of B: slabs of at most kMaxGridY columns, B and C advanced per slab
+  for (int64_t j0 = 0; j0 < N; j0 += kMaxGridY) {
+    dim3 grid(static_cast<unsigned>((S.rows + kBlock - 1) / kBlock),
+              static_cast<unsigned>(std::min(N - j0, kMaxGridY)));
+    EPS_DISPATCH(B.dt, hipLaunchKernelGGL((SpmmCsrDenseKernel<T>), grid, dim3(kBlock), 0,
+                                          Runtime::Get().stream(), S.rows, S.rowptr(), S.colidx(),
+                                          S.val.as<T>(), B.as<T>() + j0 * ldb, ldb,
+                                          static_cast<T>(alpha), C.as<T>() + j0 * S.rows));
+  }
   EPS_HIP(hipGetLastError());
 }
 
@@ -188,13 +194,17 @@ void DenseSpmmCsc(const DeviceCsr& St, double alpha, const DVec& A, int64_t lda,
   EPS_CHECK(lda >= M && A.n >= (St.cols - 1) * lda + M && C.n == M * St.rows && A.dt == C.dt);
   CheckVals(St, A);
   if (M == 0 || St.rows == 0) return;
-  EPS_CHECK_MSG(St.rows <= 65535, "DenseSpmmCsc: too many columns");
   ProfScope prof("dense_spmm_csc", M, St.rows);
-  dim3 grid(static_cast<unsigned>((M + kBlock - 1) / kBlock), static_cast<unsigned>(St.rows));
-  EPS_DISPATCH(A.dt, hipLaunchKernelGGL((DenseSpmmCscKernel<T>), grid, dim3(kBlock), 0,
-                                        Runtime::Get().stream(), M, St.rowptr(), St.colidx(),
-                                        St.val.as<T>(), A.as<T>(), lda, static_cast<T>(alpha),
-                                        C.as<T>()));
+  // blockIdx.y is the column of S: slabs of at most kMaxGridY columns; the column pointers hold
+  // positions in the whole index / value arrays, so only colptr and C advance per slab
+  for (int64_t j0 = 0; j0 < St.rows; j0 += kMaxGridY) {
+    dim3 grid(static_cast<unsigned>((M + kBlock - 1) / kBlock),
+              static_cast<unsigned>(std::min(St.rows - j0, kMaxGridY)));
+    EPS_DISPATCH(A.dt, hipLaunchKernelGGL((DenseSpmmCscKernel<T>), grid, dim3(kBlock), 0,
+                                          Runtime::Get().stream(), M, St.rowptr() + j0, St.colidx(),
+                                          St.val.as<T>(), A.as<T>(), lda, static_cast<T>(alpha),
+                                          C.as<T>() + j0 * M));
+  }
   EPS_HIP(hipGetLastError());
 }
 

@@ -294,8 +294,10 @@ HostCsc CscFromBlob(const pb::Constant& c, const void* bytes, size_t len) {
   A.val.resize(nnz);
   const char* p = static_cast<const char*>(bytes);
   std::memcpy(A.colptr.data(), p, (n + 1) * sizeof(int32_t));
-  std::memcpy(A.rowidx.data(), p + (n + 1) * sizeof(int32_t), nnz * sizeof(int32_t));
-  std::memcpy(A.val.data(), p + (n + 1 + nnz) * sizeof(int32_t), nnz * sizeof(double));
+  if (nnz > 0) {  // (an empty vector's data() may be null, which memcpy must not be given)
+    std::memcpy(A.rowidx.data(), p + (n + 1) * sizeof(int32_t), nnz * sizeof(int32_t));
+    std::memcpy(A.val.data(), p + (n + 1 + nnz) * sizeof(int32_t), nnz * sizeof(double));
+  }
   EPS_CHECK_MSG(A.colptr[0] == 0 && A.colptr[n] == nnz, "sparse blob: bad column pointers");
   // validation on the host threads (23 ms on one for 7.5e6 entries); every column pointer is
   // checked against [0, nnz] before anything is indexed with it
@@ -390,6 +392,7 @@ std::shared_ptr<Buffer> UploadI32(const std::vector<int32_t>& v) {
   }
   return buf;
 }
+}  // namespace
 
 // the CSC arrays of a matrix are the CSR arrays of its transpose
 std::shared_ptr<DeviceCsr> UploadAsCsrOfTranspose(const HostCsc& A, DType dt) {
@@ -404,6 +407,7 @@ std::shared_ptr<DeviceCsr> UploadAsCsrOfTranspose(const HostCsc& A, DType dt) {
   return d;
 }
 
+namespace {
 const DeviceCsr& CoreCsrOfA(const SparseCore& c, DType dt) {
   if (!c.csr_a) c.csr_a = UploadAsCsrOfTranspose(c.Transposed(), dt);
   return *c.csr_a;

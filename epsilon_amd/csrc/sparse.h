@@ -52,6 +52,10 @@ struct DeviceCsr {
   const int32_t* colidx() const { return static_cast<const int32_t*>(idx->p); }
 };
 
+// The CSC arrays of A are the CSR arrays of A^T: the device CSR of A^T (rows = A.n, cols = A.m),
+// values in dt.
+std::shared_ptr<DeviceCsr> UploadAsCsrOfTranspose(const HostCsc& A, DType dt);
+
 // What every handle on one sparse matrix shares: the host CSC arrays as they arrived, their
 // transpose (built on first use, once), and the device CSR forms of both.
 struct SparseCore {

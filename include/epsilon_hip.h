@@ -525,6 +525,97 @@ typedef struct eps_factor_op {
 } eps_factor_op;
 int eps_test_factor_op(const eps_factor_op* args, double* out, double* out2);
 
+/* Test entry: ONE call of one launcher of the sparse layer (csrc/sparse.h: SpmvCsr, SpmmCsrDense,
+ * DenseSpmmCsc, ScatterAddCsc; csrc/kernels_sparse.hip) on caller-given operands, in the
+ * configured dtype.  The sparse operand is the CSR matrix (ptr, idx, val), rows x cols with nnz
+ * stored entries, exactly as the launcher receives it; `op` and what the other operands mean:
+ *   "spmv"             y (rows) = alpha S x + beta y; d: x, cols entries; beta == 0 never reads y
+ *   "spmm_csr_dense"   C (rows x n, ld rows) = alpha S B; d: B, cols x n column-major with leading
+ *                      dimension ld, (n - 1) ld + cols entries
+ *   "dense_spmm_csc"   C (n x rows, ld n) = alpha A F, where the CSR operand is that of the
+ *                      TRANSPOSE of the sparse factor (F = S^T, cols x rows, i.e. F in CSC form);
+ *                      d: A, n x cols column-major with leading dimension ld,
+ *                      (cols - 1) ld + n entries
+ *   "scatter_add_csc"  W (cols x rows column-major, ld cols) += alpha F, F = S^T as above; y: W;
+ *                      entries within one row of the CSR operand must be unique
+ * d is uploaded verbatim, padding rows included.  The output starts as the caller's y_len values
+ * of y between EPS_DENSE_OP_GUARD guard elements on each side, all EPS_DENSE_OP_SENTINEL; out
+ * receives guard + y_len + guard values, so a store outside the output shows.
+ * The argument checks - an unknown or null op, a null array or result, a negative size, ptr not of
+ * rows + 1 entries, not starting at 0, not monotone or not ending at nnz, idx or val not of nnz
+ * entries, a column index outside [0, cols), ld below the rows it holds, d or y not of the length
+ * the dimensions need, d, ld, n or beta given to an op that has none - fail before any device
+ * work and name the argument: no malformed structure reaches a kernel. */
+typedef struct eps_sparse_op {
+  const char* op;
+  int64_t rows, cols, nnz;
+  const int32_t* ptr; int64_t ptr_len;
+  const int32_t* idx; int64_t idx_len;
+  const double* val;  int64_t val_len;
+  double alpha, beta;
+  const double* d;    int64_t d_len, ld, n;
+  const double* y;    int64_t y_len;
+} eps_sparse_op;
+int eps_test_sparse_op(const eps_sparse_op* args, double* out);
+
+/* Test entry: the host CSC algebra of csrc/sparse.h (CscTranspose, CscAdd, CscMultiply, CscKron,
+ * CscScaleRows, CscScaleCols, CscFromDense, CscFromBlob).  It touches no device.  `op`:
+ *   "transpose"                  a^T
+ *   "add" "multiply" "kron"      a + b, a b, kron(a, b)
+ *   "scale_rows" "scale_cols"    diag(d) a, a diag(d); d of one entry is a scalar
+ *   "from_dense"                 the a.m x a.n column-major matrix d without its exact zeros
+ *   "from_blob"                  the wire blob (int32 col_ptr[n + 1] | int32 row_index[nnz] |
+ *                                float64 values[nnz]) of an a.m x a.n matrix with a.nnz entries
+ * An operand is m x n with nnz stored entries in column-compressed form, row indices strictly
+ * ascending within each column ("from_dense" and "from_blob" read only a.m, a.n and a.nnz).  The
+ * result goes to colptr (colptr_cap entries, at least its n + 1), rowidx and val (nnz_cap entries
+ * each); *m, *n and *nnz receive its size.
+ * The argument checks - an unknown or null op, a null array or result, a negative size, column
+ * pointers not of n + 1 entries, not starting at 0, not monotone or not ending at nnz, rowidx or
+ * val not of nnz entries, a row index outside [0, m) or not ascending within its column, operand
+ * sizes that do not fit each other, d not of the length the op needs, a result larger than the
+ * capacities - name the argument; a malformed blob is CscFromBlob's own error ("sparse blob ..."). */
+typedef struct eps_csc {
+  int64_t m, n, nnz;
+  const int32_t* colptr; int64_t colptr_len;
+  const int32_t* rowidx; int64_t rowidx_len;
+  const double* val;     int64_t val_len;
+} eps_csc;
+typedef struct eps_csc_op {
+  const char* op;
+  eps_csc a, b;
+  const double* d;  int64_t d_len;
+  const void* blob; size_t blob_len;
+  int32_t* colptr;  int64_t colptr_cap;
+  int32_t* rowidx;  double* val; int64_t nnz_cap;
+} eps_csc_op;
+int eps_test_csc_op(const eps_csc_op* args, int64_t* m, int64_t* n, int64_t* nnz);
+
+/* Test entry: a sparse map HANDLE as an operand.  The wire format has no product node, so
+ * eps_linear_map_binary cannot be given a sparse map that carries a lazy scalar factor; this
+ * entry builds one.  sparse_map: wire bytes of a SPARSE_MATRIX `LinearMap` S with its data blobs.
+ * The handle is H = S, transposed with `transpose`, then - with `scaled` - the scalar map product
+ * Scalar(scale) * H (SparseMatrixImpl::Scaled: same core, a factor the callers fold into alpha).
+ * With p (S.n entries) the map as built is applied to p FIRST and the S.m values go to out2: the
+ * core has then cached the CSR copy of the plain direction before the handle asks for its own.
+ * `op` and the dense operand d (d_rows x d_cols, column-major, contiguous):
+ *   "apply"    out = H d        (d_cols == 1)     "adjoint"  out = H^T d  (d_cols == 1)
+ *   "sparse_dense"  out = H * D     "dense_sparse"  out = D * H      (Dense results)
+ *   "sparse_plus_dense"  out = H + D     "dense_plus_sparse"  out = D + H
+ * out receives the result (column-major) and needs out_cap >= its size.  The argument checks - an
+ * unknown or null op, a null payload, operand or result, a map that is not a sparse matrix,
+ * a dense operand whose size does not fit, out_cap too small - name the argument. */
+typedef struct eps_sparse_handle_op {
+  const char* op;
+  const void* sparse_map; size_t len;
+  const eps_blob* data;   size_t ndata;
+  int transpose, scaled;
+  double scale;
+  const double* p; int64_t p_len;
+  const double* d; int64_t d_rows, d_cols;
+} eps_sparse_handle_op;
+int eps_test_sparse_handle_op(const eps_sparse_handle_op* args, double* out, int64_t out_cap, double* out2);
+
 /* Microbenchmark: average milliseconds of one launch of a standalone elementwise prox kernel on
  * n synthetic elements of the configured dtype - kind 0 scaled-zone (NORM_1) with scalar
  * parameters, 1 with a per-element threshold vector, 2 projection onto R+ (reference
