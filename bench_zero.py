@@ -69,6 +69,20 @@ hinge + l1 above, KIND_floor = 256 x 601, KIND_fat = 1500 x 5000, KIND_fat_big =
 set the floors of that option's "auto", one per route.  --shapes ridge is all of them.
 
     python bench_zero.py --shapes ridge
+
+Free-x cells (no penalty on x, so x lives in the ZERO term alone: problems.least_abs_dev and
+problems.quantile with tau = 0.3; DESIGN.md 3.11 "x in the ZERO term alone"): the routes are those of
+the option "fused_zero_xfree" - "0", its default, the generic operator path, which is what these
+problems took before the option existed, and "1" the fused sweep - with "fused_zero_tall" = "1".  Per
+KIND in lad, quantile: the 4n x n ladder KIND_ladder256 / 512 / 1024 / 2048 and KIND_tall = 5000 x 1500
+(KIND_tall64 in f64).  --shapes xfree is all of them.  With --path K1,K2,... the cells are the quantile
+ones and a member count K is a tau path (tau from 0.1 to 0.9 in K steps) on one matrix under
+"fused_zero_xfree" = "1": the batch as one group ("batch_zero_tall" = "1") against the same solves run
+one by one ("batch_zero_tall" = "0"), the two alternated --runs times; one JSON line per (shape, K)
+with ms_per_sweep, spread and tags per side and the speedup of the group.
+
+    python bench_zero.py --shapes xfree
+    python bench_zero.py --shapes xfree --path 2,4,8 [--steps 100] [--runs 3]
 """
 
 import argparse
@@ -117,6 +131,11 @@ RIDGE_CELLS = (("ladder256", 1024, 256, "f32"), ("ladder512", 2048, 512, "f32"),
 for _kind in RIDGE_KINDS:
     for _cell, _m, _n, _dtype in RIDGE_CELLS:
         SHAPES["%s_%s" % (_kind, _cell)] = (_kind, _m, _n, _dtype)
+XFREE_KINDS = {"lad": "least_abs_dev", "quantile": "quantile"}
+XFREE_CELLS = RIDGE_CELLS[:6]  # the ladder and the two 5000 x 1500 cells: no fat ones (C^T C is singular there)
+for _name, _kind in XFREE_KINDS.items():
+    for _cell, _m, _n, _dtype in XFREE_CELLS:
+        SHAPES["%s_%s" % (_name, _cell)] = (_kind, _m, _n, _dtype)
 ROUTES = ("0", "auto")
 TALL_ROUTES = ("0", "1")  # of "fused_zero_tall", for the cells with more rows than columns
 
@@ -204,6 +223,63 @@ def path_lines(a):
             _solve.set_option("dtype", "f32")
 
 
+def xfree_path_lines(a, names):
+    """the --path cells of the free-x group: a tau path as one group against its members one by one"""
+    ks = sorted(int(k) for k in a.path.split(","))
+    assert 2 <= ks[0], "--path takes member counts from 2"
+    sb = wire.SolverParams(max_iterations=a.steps, abs_tol=0.0, rel_tol=0.0).SerializeToString()
+    short = wire.SolverParams(max_iterations=10, abs_tol=0.0, rel_tol=0.0).SerializeToString()
+    sides = (("group", "1"), ("one_by_one", "0"))  # of "batch_zero_tall"
+    for name in names:
+        kind, m, n, dtype = SHAPES[name]
+        if kind != "quantile":
+            continue  # (least absolute deviations has no parameter to make a path of)
+        _solve.set_option("dtype", dtype)
+        _solve.set_option("fused_zero_tall", "1")
+        _solve.set_option("fused_zero_xfree", "1")
+        try:
+            for K in ks:
+                probs = [problems.quantile(m, n, tau=float(t))[0] for t in np.linspace(0.1, 0.9, K)]
+                data = {}
+                for p in probs:
+                    data.update(p.expression_data())
+                pbs = [p.SerializeToString() for p in probs]
+                tags, times = {}, {side: [] for side, _ in sides}
+                for side, word in sides:  # warm-up, and the launches per sweep
+                    _solve.set_option("batch_zero_tall", word)
+                    _solve.profile_reset()
+                    _solve.profile_enable(True)
+                    try:
+                        _solve.solve_batch(pbs, None, short, data)
+                        tags[side] = {}
+                        for t, (c, _) in _solve.profile_dump().items():
+                            if t.startswith(("batch_zero", "zero_tall")):
+                                tags[side][t.split(":")[0]] = tags[side].get(t.split(":")[0], 0) + c / 10.0
+                    finally:
+                        _solve.profile_enable(False)
+                assert "batch_zero_tall_free_cols" in tags["group"] and "zero_tall_free_cols" in tags["one_by_one"], tags
+                for _ in range(a.runs):
+                    for side, word in sides:
+                        _solve.set_option("batch_zero_tall", word)
+                        res = _solve.solve_batch(pbs, None, sb, data)
+                        sts = [wire.SolverStatus.FromString(st) for st, _ in res]
+                        assert all(s.num_iterations == a.steps for s in sts)
+                        # a group's members all carry the group's loop time; members solved one by
+                        # one carry their own
+                        loops = [s.timing.total_time - s.timing.init_time for s in sts]
+                        times[side].append((loops[0] if side == "group" else sum(loops)) / a.steps)
+                med = {side: statistics.median(v) for side, v in times.items()}
+                yield dict(bench="zero_xfree_path", shape=name, problem=kind, m=m, n=n, dtype=dtype, gpus=1, K=K,
+                           steps=a.steps, runs=a.runs, ms_per_sweep={side: 1e3 * v for side, v in med.items()},
+                           spread={side: (max(v) - min(v)) / med[side] for side, v in times.items()},
+                           speedup=med["one_by_one"] / med["group"], tags=tags)
+        finally:
+            _solve.set_option("batch_zero_tall", "0")
+            _solve.set_option("fused_zero_xfree", "0")
+            _solve.set_option("fused_zero_tall", "auto")
+            _solve.set_option("dtype", "f32")
+
+
 def path_against(a):
     """this tree's library and --against, alternated in child processes"""
     cells = {}
@@ -242,13 +318,20 @@ def main():
     a = parse()
     if a.lib:
         _solve.LIB_PATH = os.path.abspath(a.lib)  # (before the first call loads the library)
+    names = a.shapes.split(",")
+    if "xfree" in names:
+        at = names.index("xfree")
+        names[at:at + 1] = ["%s_%s" % (k, c[0]) for k in XFREE_KINDS for c in XFREE_CELLS]
+    if a.path and all(SHAPES[name][0] in XFREE_KINDS.values() for name in names):
+        for line in xfree_path_lines(a, names):
+            print(json.dumps(line), flush=True)
+        return
     if a.path:
         if a.against:
             return path_against(a)
         for line in path_lines(a):
             print(json.dumps(line), flush=True)
         return
-    names = a.shapes.split(",")
     if "ridge" in names:
         at = names.index("ridge")
         names[at:at + 1] = ["%s_%s" % (k, c[0]) for k in RIDGE_KINDS for c in RIDGE_CELLS]
@@ -256,18 +339,21 @@ def main():
         kind, m, n, dtype = SHAPES[name]
         tall = m > n
         ridge = kind in RIDGE_KINDS
+        xfree = kind in XFREE_KINDS.values()
         option, routes, tag = (("fused_zero_tall_smooth", TALL_ROUTES, "zero_tall_samples")
                                if tall and kind.startswith("logreg") else
                                ("fused_zero_tall", TALL_ROUTES, "zero_tall") if tall else
                                ("fused_zero", ROUTES, "zero_fused"))
         if ridge:  # the same tags show the route; the option that is switched is the ridge term's
             option, routes = "fused_zero_ridge", TALL_ROUTES
+        if xfree:  # the x side's own launch shows the route
+            option, routes, tag = "fused_zero_xfree", TALL_ROUTES, "zero_tall_free_cols"
         prob = getattr(problems, kind)(m, n)[0]
         pb, data = prob.SerializeToString(), prob.expression_data()
         sb = wire.SolverParams(max_iterations=10 ** 9, ignore_stopping_criteria=True).SerializeToString()
         _solve.set_option("dtype", dtype)
         _solve.set_option("fused_resident", a.resident)
-        if option == "fused_zero_tall_smooth" or ridge:
+        if option == "fused_zero_tall_smooth" or ridge or xfree:
             _solve.set_option("fused_zero_tall", "1")
         if ridge:
             _solve.set_option("fused_zero_tall_smooth", "1")
@@ -293,7 +379,7 @@ def main():
         finally:
             for s in handles.values():
                 s.close()
-            _solve.set_option(option, "auto")
+            _solve.set_option(option, "0" if xfree else "auto")
             _solve.set_option("fused_zero_tall", "auto")
             _solve.set_option("fused_zero_tall_smooth", "auto")
             _solve.set_option("fused_resident", "auto")
@@ -306,7 +392,7 @@ def main():
                     speedup=(ms["0"] / ms[routes[1]] if ms[routes[1]] else None))
         if a.resident != "auto":
             line["fused_resident_kb"] = int(a.resident)
-        if ridge:
+        if ridge or xfree:
             line["option"] = option
         if tall:
             line["sweeps_per_s"] = {r: (1e3 / ms[r] if ms[r] else None) for r in routes}

@@ -139,8 +139,8 @@ std::vector<BlockVector*> Homes(const MultiBlockParts& a) {
 int BatchWideMin();  // (with the batched solves below)
 
 // The indices of the options' words (options.cc).  "fused" (off with a leading 0), "fused_zero",
-// "fused_zero_ridge", "fused_zero_tall", "fused_zero_tall_smooth", "fused_tall", "fused_matrix" and "fused_resident" are
-// read at every Init, "batch_wide" and "batch_zero_tall" per batch ("1" sends eligible groups to the wide
+// "fused_zero_ridge", "fused_zero_tall", "fused_zero_tall_smooth", "fused_zero_xfree", "fused_tall", "fused_matrix" and
+// "fused_resident" are read at every Init, "batch_wide" and "batch_zero_tall" per batch ("1" sends eligible groups to the wide
 // route / lets the tall ZERO-term members of a batch form groups).
 // "0", "1", "auto" of "fused_tall", "fused_zero_tall", "fused_zero_tall_smooth" and "fused_zero_ridge"
 enum RouteMode { kRouteOff, kRouteOn, kRouteAuto };
@@ -369,7 +369,8 @@ struct BatchRoute : FusedRoute {
       k::ZeroTallSamplesBatch(pn, dt, sample_table, count);
       passes(5);
     }
-    if (Rows() != nullptr) k::ZeroFusedRowsBatch(pm, grid, Rows()->smooth, dt, row_table, count, Rows()->tall);
+    if (Rows() != nullptr)
+      k::ZeroFusedRowsBatch(pm, grid, Rows()->smooth, dt, row_table, count, Rows()->tall, Rows()->x_free);
     else k::ReducePartialsBatch(pm, grid, table, count, dt, rhs_aligned);
     if (whiten) return;
     if (inv.packed.n > 0) k::SymvPackedBatch(pm, inv.D->scale(), inv.packed, table, count, work);
@@ -907,6 +908,14 @@ struct LassoRoute final : BatchRoute {
 // on fat C, the x-side kernel on tall C - then takes the block solve's two multiplies in the
 // threshold's place; everything else is as above.
 // Single solves on the multi-block driver alone: such a member of a batch is solved by itself.
+//
+// Free x (`zp.x_free`, option "fused_zero_xfree" = "1"; DESIGN.md 3.11 "x in the ZERO term alone"): no
+// term on x, so x is no copy - it lives in the ZERO term alone and has no constraint row
+// (least_abs_dev, quantile).  The tall form with one constraint and one separable term, a zone on z:
+// the pass with chain 3 as it is, an x side that is the partials' sum alone (rows.x_free: x kept in
+// `xcur`, f_x = pkappa sum, no state and no chain) and the apply of Dinv(x) = (C^T C / e^2)^-1, which
+// exists for m > n alone - asked for here, since the factorisation has the same order for fat C.
+// Under "batch_zero_tall" such members that share C form groups of their own.
 struct ZeroRoute final : BatchRoute {
   using Side = k::ConsensusState;  // of the x constraint, of the z constraint
 
@@ -917,6 +926,7 @@ struct ZeroRoute final : BatchRoute {
   // m, n: C is m x n.  w, p, tpart: the dense pivot's vectors (tall: x' of the coming sweep, f_x and
   // the pass's partials, n-long)
   DVec state_n, state_m;  // the slices of a side's state in one buffer (n: the x constraint's rows)
+  DVec xcur;  // free x: the whole x side - x as the pass of the last sweep read it (no u, no y)
   DVec CT;    // tall: C^T, n x m, ld n: shared through the solve's cache
   DVec head;  // a smooth z term: the carried head (s, y_s, v of the coming sweep)
   k::ZeroRowsArgs rows;  // the side that is not in the pass: z (tall: x)
@@ -928,15 +938,19 @@ struct ZeroRoute final : BatchRoute {
   k::LassoFusedArgs acc;
 
   // `tall_mode`, `tall_smooth_mode`, `ridge_mode`: the options "fused_zero_tall",
-  // "fused_zero_tall_smooth" and "fused_zero_ridge"; under "auto" the measured floors apply
-  bool Enable(const MultiBlockParts& a, int tall_mode, int tall_smooth_mode, int ridge_mode) {
+  // "fused_zero_tall_smooth" and "fused_zero_ridge"; under "auto" the measured floors apply.
+  // `xfree_on`: the option "fused_zero_xfree" is "1"
+  bool Enable(const MultiBlockParts& a, int tall_mode, int tall_smooth_mode, int ridge_mode, bool xfree_on) {
     if (opt::Is0(opt::kFused) || ShardSpec::Get().active() || !a.b.data().empty()) return false;
     const int nc = a.num_constraints, N = static_cast<int>(a.prox.size());
     if (nc < 1 || nc > 2 || N != nc + 1) return false;
     if (!a.prox[N - 1]->DescribeZeroProjection(&zp)) return false;
     tall = zp.tall;
     has_z = !zp.z_key.empty();
-    if (has_z != (nc == 2)) return false;
+    // free x: the tall form with one constraint, the z tie, and one separable term, the one on z
+    const bool xfree = zp.x_free;
+    if (xfree && (!xfree_on || !tall || !has_z || nc != 1)) return false;
+    if (!xfree && has_z != (nc == 2)) return false;
     int ix = -1, iz = -1;  // positions of the separable terms among the objective terms
     for (int i = 0; i + 1 < N; ++i) {
       SeparableDesc d;
@@ -944,8 +958,9 @@ struct ZeroRoute final : BatchRoute {
       // accepted on x: a zone without offset, or a ridge term; on z: a zone (its offset with it), or a
       // smooth term (tall: SUM_LOGISTIC alone) - each once, on its own constraint row
       const bool zone = d.kind == SeparableDesc::kZone, smooth = d.kind == SeparableDesc::kSmooth;
-      const bool on_x = (zone && d.g.n == 0) || d.kind == SeparableDesc::kRidge;
-      const bool on_z = zone || (smooth && (!tall || d.fn == k::SMOOTH_LOGISTIC));
+      // free x: no term on x, and on z a zone alone (a smooth z term keeps the generic path)
+      const bool on_x = !xfree && ((zone && d.g.n == 0) || d.kind == SeparableDesc::kRidge);
+      const bool on_z = zone || (smooth && !xfree && (!tall || d.fn == k::SMOOTH_LOGISTIC));
       if (on_x && ix < 0 && d.constraint_key == zp.x_constraint_key) {
         sx = d;
         ix = i;
@@ -956,8 +971,8 @@ struct ZeroRoute final : BatchRoute {
         return false;
       }
     }
-    if (ix < 0 || (has_z && iz < 0)) return false;
-    const bool x_ridge = sx.kind == SeparableDesc::kRidge;
+    if ((!xfree && ix < 0) || (has_z && iz < 0)) return false;
+    const bool x_ridge = !xfree && sx.kind == SeparableDesc::kRidge;
     // (the smooth form belongs to the z side: tall, that is the sample kernel, not the rows)
     samples_smooth = tall && sz.kind == SeparableDesc::kSmooth;
     rows.smooth = !tall && sz.kind == SeparableDesc::kSmooth;
@@ -986,14 +1001,15 @@ struct ZeroRoute final : BatchRoute {
       if (x_ridge && !Allowed(ridge_mode, m, kZeroRidgeAutoMinRows)) return false;
     }
     // the consensus constraints: copy + a var = 0, nothing else in their rows or columns
-    if (static_cast<int>(a.A.data().size()) != 2 * nc) return false;
+    // (free x: the one tie is all there is, so no column of A is x's)
+    if (static_cast<int>(a.A.data().size()) != 2 * nc || (xfree && a.A.data().count(zp.x_key) != 0)) return false;
     double ax = 0, az = 0;  // constraint maps of x and z (their copies': 1)
     auto tie = [&](const std::string& ck, const std::string& copy, const std::string& var, int64_t len, double* av) {
       double a0 = 0;
       return ConsensusTie(a.A, ck, copy, var, len, &a0, av) && a0 == 1.0 && a.A.col(copy).size() == 1 &&
              a.A.col(var).size() == 1;
     };
-    if (!tie(zp.x_constraint_key, zp.x_key, sx.var_key, n, &ax)) return false;
+    if (!xfree && !tie(zp.x_constraint_key, zp.x_key, sx.var_key, n, &ax)) return false;
     if (has_z && !tie(zp.z_constraint_key, zp.z_key, sz.var_key, m, &az)) return false;
     if (!Fits(zp.rhs_arg, m, dt) || !Fits(sx.alpha_vec, n, dt) || !Fits(sx.beta_vec, n, dt)) return false;
     if (!Fits(sz.alpha_vec, m, dt) || !Fits(sz.beta_vec, m, dt) || !Fits(sz.g, m, dt)) return false;
@@ -1028,14 +1044,23 @@ struct ZeroRoute final : BatchRoute {
     p = DVec::Zeros(nw, dt);
     tpart = DVec::Empty(static_cast<int64_t>(grid) * nw, dt);
     inv.Init(zp.Dinv, nw, p, w, a.shared_cache);
-    const Side sn = side(n, zp.x_constraint_key, ix, sx.var_key, zp.x_key, &state_n);
+    // (free x: x itself is the x side, a view of the ZERO term's own variable like a copy is)
+    Side sn;
+    if (xfree) {
+      xcur = DVec::Zeros(n, dt);
+      views.push_back({&a.x[N - 1], zp.x_key, xcur, true});
+    } else {
+      sn = side(n, zp.x_constraint_key, ix, sx.var_key, zp.x_key, &state_n);
+    }
     const Side sm = has_z ? side(m, zp.z_constraint_key, iz, sz.var_key, zp.z_key, &state_m) : Side();
     if (tall) FillTall(sn, ax, sm, az);
     else FillFat(sn, ax, sm, az);
     // beside the matrix the sweep touches the partials (the rows kernel re-reads them), the seven
-    // state vectors of either side, p, w, the inverse, and the sample kernel's head, d and f_arg
+    // state vectors of either side (free x: x alone on its side), p, w, the inverse, and the sample
+    // kernel's head, d and f_arg
     res = ResidentShare(pass.m, pass.n, dt,
-                        static_cast<int64_t>(grid) * nw + 7 * (n + m) + 2 * nw + nw * nw + head.n + dfarg.n,
+                        static_cast<int64_t>(grid) * nw + (xfree ? 7 * m + n : 7 * (n + m)) + 2 * nw + nw * nw +
+                            head.n + dfarg.n,
                         /*auto_on=*/false, &pass);
     if (samples_smooth) {  // the share holds for both halves: the matrix is read twice per sweep
       acc = pass;
@@ -1125,6 +1150,10 @@ struct ZeroRoute final : BatchRoute {
     i.dinv = zp.dinv_arg;
     RowsSide(sn, sx, ax);
     rows.tall = true;
+    if (zp.x_free) {  // no state and no term on this side: x alone (RowsSide's are empty defaults)
+      rows.x_free = true;
+      rows.xcur = xcur;
+    }
     if (!samples_smooth) return;
     // the pass in two halves (chains 4 and 5) around the sample kernel, which takes the z side's
     // state, zone, offset, rhs and pivots from the pass's record
@@ -1152,7 +1181,7 @@ struct ZeroRoute final : BatchRoute {
   // The dense pivot's vector of the first sweep from the current state, with the generic
   // operators: the sweep up to the ZERO prox's input v (on copies: the state is not touched), then
   // the forward substitution and the inverse apply.  Fat: r = (rhs - e v_z) - L(arg, x') v_x.
-  // Tall: f_arg = rhs - e v_z, f_x = v_x - L(x', arg) f_arg.
+  // Tall: f_arg = rhs - e v_z, f_x = v_x - L(x', arg) f_arg; free x: f_x = -L(x, arg) f_arg, no v_x.
   void ForwardFromState(const MultiBlockParts& a) {
     const size_t N = a.prox.size();
     BlockVector v = a.u;
@@ -1165,8 +1194,8 @@ struct ZeroRoute final : BatchRoute {
     if (tall) {
       DVec farg = zp.rhs_arg.n != 0 ? zp.rhs_arg.Clone() : DVec::Zeros(m, dt);
       k::Axpby(farg, -zp.e, v(zp.z_constraint_key), 1.0);
-      k::Copy(p, v(zp.x_constraint_key));
-      zp.L->Apply(-1.0, farg, 1.0, p);
+      if (!zp.x_free) k::Copy(p, v(zp.x_constraint_key));
+      zp.L->Apply(-1.0, farg, zp.x_free ? 0.0 : 1.0, p);
     } else {
       if (zp.rhs_arg.n != 0) k::Copy(p, zp.rhs_arg);
       else k::Fill(p, 0.0);
@@ -1200,7 +1229,8 @@ struct ZeroRoute final : BatchRoute {
   // `tall_groups`.
   // Tall: the key also has the transposed copy (the members find one through the solve's cache),
   // the form (the pass whole, or in halves around the sample kernel: a logistic member never joins
-  // a scaled-zone group) and the scalar pivot.
+  // a scaled-zone group), the scalar pivot, and whether x is free (such a member has another x-side
+  // launch: it never joins a hinge or deadzone group).
   bool BatchKey(const pb::SolverParams& params, bool tall_groups, std::vector<uint64_t>* key) const override {
     // the batched kernels have no ridge head: such a member is solved by itself
     if (sx.kind == SeparableDesc::kRidge) return false;
@@ -1214,7 +1244,7 @@ struct ZeroRoute final : BatchRoute {
     key->insert(key->end(), {Bits(zp.e), has_z ? 1u : 0u, rows.smooth ? 1u : 0u});
     if (tall)
       key->insert(key->end(), {reinterpret_cast<uintptr_t>(CT.data()), 1u, samples_smooth ? 1u : 0u,
-                               Bits(zp.dinv_arg)});
+                               Bits(zp.dinv_arg), zp.x_free ? 1u : 0u});
     return true;
   }
 };
@@ -1324,9 +1354,10 @@ std::unique_ptr<FusedRoute> RecogniseMultiBlockRoute(const MultiBlockParts& part
   const int tall_smooth = opt::Word(opt::kFusedZeroTallSmooth);
   const int lasso_tall = opt::Word(opt::kFusedTall);
   const int ridge = opt::Word(opt::kFusedZeroRidge);
+  const bool xfree = opt::Word(opt::kFusedZeroXfree) != 0;
   if (auto r = Recognise<LassoRoute>(parts, lasso_tall)) return r;  // fat, then tall
   if (!zero) return nullptr;
-  return Recognise<ZeroRoute>(parts, tall, tall_smooth, ridge);  // fat, then tall
+  return Recognise<ZeroRoute>(parts, tall, tall_smooth, ridge, xfree);  // fat, then tall, then tall with free x
 }
 
 std::unique_ptr<FusedRoute> RecogniseTwoBlockRoute(const TwoBlockParts& parts) {

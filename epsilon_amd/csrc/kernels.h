@@ -148,6 +148,13 @@ struct ZeroRowsArgs {
   // the copy x' as the inverse apply left it (q = w, no product on top), the term is the one on x
   // and r = v_x' + pkappa sum(tpart) is the next f_x; rhs, g and e are not read.  Scaled zone alone.
   bool tall = false;
+  // Free x (with tall; profile tag "zero_tall_free_cols"; DESIGN.md 3.11 "x in the ZERO term alone"):
+  // x has no constraint row, so there is no state, no term and no chain.  Per entry j the launch
+  // sums the partials in the same order, keeps xcur[j] = w[j] - x of the sweep the pass just used,
+  // the iterate at this boundary - and writes r[j] = pkappa sum(tpart), the next f_x.  `state`, the
+  // zone, rhs, g and e are not read; xcur: m entries.
+  bool x_free = false;
+  DVec xcur;
 };
 // The sample side of a tall ZERO-term sweep whose z term is smooth (SMOOTH_LOGISTIC alone), between
 // the two halves of the pass (LassoFusedArgs::chain 4 and 5), one launch, a thread per sample,
@@ -178,9 +185,11 @@ void ZeroSmoothHead(const ZeroRowsArgs& args);  // profile tag "zero_fused_head"
 // LassoBatchUpload, a member that stops is dropped by uploading the shorter list.
 // `tall` (all members or none; profile tag "batch_zero_tall_cols"): grid row b is member b's own
 // "zero_tall_cols" launch, the x side of a tall problem (ZeroRowsArgs::tall).
+// `x_free` (with `tall`, all members or none; profile tag "batch_zero_tall_free_cols"): grid row b is
+// member b's own "zero_tall_free_cols" launch (ZeroRowsArgs::x_free).
 void ZeroRowsBatchUpload(const std::vector<const ZeroRowsArgs*>& members, DVec* table);
 void ZeroFusedRowsBatch(int64_t m, int nparts, bool smooth, DType dt, const DVec& table, int count,
-                        bool tall = false);
+                        bool tall = false, bool x_free = false);
 // The sample side of `count` tall members with a smooth z term in ONE launch, profile tag
 // "batch_zero_tall_samples": grid row b is member b's own ZeroTallSamples launch, a thread per
 // sample, on its own record with the carried head in its own hs, hys, hv; no wait, no barrier, no

@@ -370,7 +370,11 @@ template <class T> struct ZeroRowsInst {
 // summation of the partials; the chain takes q = x'_j as the inverse apply left it in w
 // (ZeroTallColsChainT) and r_j = f_x = v_x' + pkappa sum: no rhs on this side.  Fn = void: the x term
 // is a scaled zone; Fn = RidgeStep: a ridge term (ZoneParams::ridge).
-template <class T, int ROWS, class Fn, bool TALL = false>
+// FREE (with TALL, Fn = void; tag "zero_tall_free_cols"): x lives in the ZERO term alone, so the side
+// has no state, no term and no chain.  The same summation of the partials; then lane 0 keeps
+// x_j = w_j of the sweep the pass just used in I.zq (the ZERO term's own variable of this side: here x
+// itself) and writes r_j = f_x = pkappa sum.  Of the record it reads tpart, w, zq, r and pkappa alone.
+template <class T, int ROWS, class Fn, bool TALL = false, bool FREE = false>
 __device__ __forceinline__ void ZeroRowsBody(int64_t m, int nparts, const ZeroRowsInst<T>& I, unsigned block) {
   __shared__ T part[kZeroLanes][ROWS];
   const FusedScalarsT<T>& c = I.c;
@@ -395,6 +399,12 @@ __device__ __forceinline__ void ZeroRowsBody(int64_t m, int nparts, const ZeroRo
   T sum = part[0][rl];
 #pragma unroll
   for (int q = 1; q < kZeroLanes; ++q) sum += part[q][rl];
+  if constexpr (FREE) {
+    static_assert(TALL && std::is_void<Fn>::value, "free x: the tall form, no term on this side");
+    I.zq[i] = I.w[i];         // the boundary iterate: x as the pass of this sweep read it
+    I.r[i] = I.pkappa * sum;  // f_x = -L(x, arg) f_arg: no v_x (block.cc Substitute / the GEMV epilogue)
+    return;
+  }
   FusedScalarsT<T> ci = c;
   if (c.alpha_v != nullptr) ci.alpha = c.alpha_v[i];
   if (c.beta_v != nullptr) ci.beta = c.beta_v[i];
@@ -438,6 +448,11 @@ template <class T, int ROWS, class Fn, bool TALL = false>
 __global__ __launch_bounds__(ROWS * kZeroLanes) void ZeroFusedRowsKernel(int64_t m, int nparts, ZeroRowsInst<T> I) {
   ZeroRowsBody<T, ROWS, Fn, TALL>(m, nparts, I, blockIdx.x);
 }
+// Free x (tag "zero_tall_free_cols"): the body's FREE form, 16 entries of x per workgroup.
+template <class T>
+__global__ __launch_bounds__(kZeroRows * kZeroLanes) void ZeroFreeColsKernel(int64_t m, int nparts, ZeroRowsInst<T> I) {
+  ZeroRowsBody<T, kZeroRows, void, true, true>(m, nparts, I, blockIdx.x);
+}
 
 // The members of a batch: grid row b is member b's single launch, workgroup for workgroup.  A
 // workgroup touches its own member's rows alone; nothing waits on another workgroup.
@@ -447,6 +462,13 @@ __global__ __launch_bounds__(ROWS * kZeroLanes) void ZeroFusedRowsBatchKernel(
     int64_t m, int nparts, const ZeroRowsInst<T>* __restrict__ tab) {
   const ZeroRowsInst<T> I = tab[blockIdx.y];
   ZeroRowsBody<T, ROWS, Fn, TALL>(m, nparts, I, blockIdx.x);
+}
+// Free x (tag "batch_zero_tall_free_cols"): grid row b is member b's "zero_tall_free_cols" launch.
+template <class T>
+__global__ __launch_bounds__(kZeroRows * kZeroLanes) void ZeroFreeColsBatchKernel(
+    int64_t m, int nparts, const ZeroRowsInst<T>* __restrict__ tab) {
+  const ZeroRowsInst<T> I = tab[blockIdx.y];
+  ZeroRowsBody<T, kZeroRows, void, true, true>(m, nparts, I, blockIdx.x);
 }
 
 // The first head of a smooth z term from the adopted boundary state, a thread per row.
@@ -464,6 +486,15 @@ __global__ __launch_bounds__(kBlock) void ZeroSmoothHeadKernel(
 }
 
 template <class T> ZeroRowsInst<T> RowsInstOf(const ZeroRowsArgs& a) {
+  if (a.x_free) {  // no state and no term: the partials, w, x (in the copy's place), r and pkappa
+    ZeroRowsInst<T> f = {};
+    f.tpart = a.tpart.as<T>();
+    f.w = a.w.as<T>();
+    f.zq = a.xcur.as<T>();
+    f.r = a.r.as<T>();
+    f.pkappa = static_cast<T>(a.pkappa);
+    return f;
+  }
   ZeroRowsInst<T> d;
   d.tpart = a.tpart.as<T>();
   d.w = a.w.as<T>();
@@ -486,12 +517,25 @@ void LaunchZeroRows(const ZeroRowsArgs& a) {
   hipLaunchKernelGGL((ZeroFusedRowsKernel<T, ROWS, Fn, TALL>), dim3(grid), dim3(ROWS * kZeroLanes), 0,
                      Runtime::Get().stream(), a.m, a.nparts, RowsInstOf<T>(a));
 }
+template <class T>
+void LaunchZeroFreeCols(const ZeroRowsArgs& a) {
+  const unsigned grid = static_cast<unsigned>((a.m + kZeroRows - 1) / kZeroRows);
+  hipLaunchKernelGGL((ZeroFreeColsKernel<T>), dim3(grid), dim3(kZeroRows * kZeroLanes), 0, Runtime::Get().stream(),
+                     a.m, a.nparts, RowsInstOf<T>(a));
+}
 
 template <class T, int ROWS, class Fn, bool TALL = false>
 void LaunchZeroRowsBatch(int64_t m, int nparts, const DVec& table, int count) {
   const unsigned grid = static_cast<unsigned>((m + ROWS - 1) / ROWS);
   hipLaunchKernelGGL((ZeroFusedRowsBatchKernel<T, ROWS, Fn, TALL>), dim3(grid, static_cast<unsigned>(count)),
                      dim3(ROWS * kZeroLanes), 0, Runtime::Get().stream(), m, nparts,
+                     reinterpret_cast<const ZeroRowsInst<T>*>(table.as<char>()));
+}
+template <class T>
+void LaunchZeroFreeColsBatch(int64_t m, int nparts, const DVec& table, int count) {
+  const unsigned grid = static_cast<unsigned>((m + kZeroRows - 1) / kZeroRows);
+  hipLaunchKernelGGL((ZeroFreeColsBatchKernel<T>), dim3(grid, static_cast<unsigned>(count)),
+                     dim3(kZeroRows * kZeroLanes), 0, Runtime::Get().stream(), m, nparts,
                      reinterpret_cast<const ZeroRowsInst<T>*>(table.as<char>()));
 }
 
@@ -534,6 +578,11 @@ void CheckZeroRows(const ZeroRowsArgs& a) {
   const DType dt = a.w.dt;
   EPS_CHECK(a.m >= 1 && a.nparts >= 1 && a.tpart.dt == dt && a.tpart.n >= static_cast<int64_t>(a.nparts) * a.m);
   EPS_CHECK(a.w.n == a.m && a.r.n == a.m && a.r.dt == dt);
+  if (a.x_free) {  // x alone in the state's place; no term, so nothing else of the record is read
+    EPS_CHECK_MSG(a.tall && !a.smooth && !a.zone.ridge, "free x is the tall form without a term on x");
+    EPS_CHECK(a.xcur.n == a.m && a.xcur.dt == dt);
+    return;
+  }
   CheckState(a.state, a.m, dt);
   for (const DVec* v : {&a.rhs, &a.g, &a.zone.alpha_vec, &a.zone.beta_vec})
     if (v->n > 0) EPS_CHECK(v->n == a.m && v->dt == dt);
@@ -548,8 +597,11 @@ void CheckZeroRows(const ZeroRowsArgs& a) {
 
 void ZeroFusedRows(const ZeroRowsArgs& a) {
   CheckZeroRows(a);
-  ProfScope prof(a.tall ? "zero_tall_cols" : "zero_fused_rows", a.m, a.nparts);
-  if (a.tall && a.zone.ridge) {
+  ProfScope prof(a.x_free ? "zero_tall_free_cols" : a.tall ? "zero_tall_cols" : "zero_fused_rows", a.m, a.nparts);
+  if (a.x_free) {
+    if (a.w.dt == F32) LaunchZeroFreeCols<float>(a);
+    else LaunchZeroFreeCols<double>(a);
+  } else if (a.tall && a.zone.ridge) {
     if (a.w.dt == F32) LaunchZeroRows<float, kZeroRows, RidgeStep, true>(a);
     else LaunchZeroRows<double, kZeroRows, RidgeStep, true>(a);
   } else if (a.tall) {
@@ -642,20 +694,25 @@ void ZeroRowsBatchUpload(const std::vector<const ZeroRowsArgs*>& members, DVec* 
   for (const ZeroRowsArgs* a : members) {
     CheckZeroRows(*a);
     EPS_CHECK(a->m == lead.m && a->nparts == lead.nparts && a->smooth == lead.smooth && a->w.dt == lead.w.dt);
-    EPS_CHECK(a->tall == lead.tall);
+    EPS_CHECK(a->tall == lead.tall && a->x_free == lead.x_free);
     EPS_CHECK_MSG(!a->zone.ridge, "the batched rows have no ridge form");
   }
   if (lead.w.dt == F32) UploadRowsT<float>(members, table);
   else UploadRowsT<double>(members, table);
 }
 
-void ZeroFusedRowsBatch(int64_t m, int nparts, bool smooth, DType dt, const DVec& table, int count, bool tall) {
+void ZeroFusedRowsBatch(int64_t m, int nparts, bool smooth, DType dt, const DVec& table, int count, bool tall,
+                        bool x_free) {
   const int64_t record = dt == F32 ? sizeof(ZeroRowsInst<float>) : sizeof(ZeroRowsInst<double>);
   EPS_CHECK(m >= 1 && nparts >= 1 && count >= 1 && count <= 65535);
   EPS_CHECK(table.dt == F64 && table.n * 8 >= count * record);
   EPS_CHECK_MSG(!(tall && smooth), "the tall ZERO-term x side has no smooth form");
-  ProfScope prof(tall ? "batch_zero_tall_cols" : "batch_zero_rows", m, count);
-  if (tall) {
+  EPS_CHECK_MSG(!x_free || tall, "free x is the tall form");
+  ProfScope prof(x_free ? "batch_zero_tall_free_cols" : tall ? "batch_zero_tall_cols" : "batch_zero_rows", m, count);
+  if (x_free) {
+    if (dt == F32) LaunchZeroFreeColsBatch<float>(m, nparts, table, count);
+    else LaunchZeroFreeColsBatch<double>(m, nparts, table, count);
+  } else if (tall) {
     if (dt == F32) LaunchZeroRowsBatch<float, kZeroRows, void, true>(m, nparts, table, count);
     else LaunchZeroRowsBatch<double, kZeroRows, void, true>(m, nparts, table, count);
   } else if (smooth) {

@@ -38,6 +38,7 @@ const struct Option {
     {kFusedZeroRidge, "EPSILON_HIP_FUSED_ZERO_RIDGE", "fused_zero_ridge", {"0", "1", "auto"}, "auto"},
     {kFusedZeroTall, "EPSILON_HIP_FUSED_ZERO_TALL", "fused_zero_tall", {"0", "1", "auto"}, "auto"},
     {kFusedZeroTallSmooth, "EPSILON_HIP_FUSED_ZERO_TALL_SMOOTH", "fused_zero_tall_smooth", {"0", "1", "auto"}, "auto"},
+    {kFusedZeroXfree, "EPSILON_HIP_FUSED_ZERO_XFREE", "fused_zero_xfree", {"0", "1"}, "0"},
     {kGemm, "EPSILON_HIP_GEMM", "gemm"},
     {kGemmOrder, "EPSILON_HIP_GEMM_ORDER"},
     {kGemmSmall, "EPSILON_HIP_GEMM_SMALL"},

@@ -31,6 +31,7 @@ enum Id {
   kFusedZeroRidge,
   kFusedZeroTall,
   kFusedZeroTallSmooth,
+  kFusedZeroXfree,
   kGemm,
   kGemmOrder,
   kGemmSmall,

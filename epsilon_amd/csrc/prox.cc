@@ -718,10 +718,10 @@ class ZeroProx final : public ProxOperator {
     return chol_.Solve(b_ + v).Select(var_keys_);
   }
 
-  // The fat order, then the tall one (no factorisation has both patterns: the fat order ends in
-  // the arg pivot, the tall one in a copy).
+  // The fat order, then the tall one, then the tall one with free x (no factorisation has two of the
+  // patterns: the fat order ends in the arg pivot, the tall ones in x, over 5 keys and over 4).
   bool DescribeZeroProjection(ZeroProjectionDesc* d) const override {
-    return DescribeFat(d) || DescribeTall(d);
+    return DescribeFat(d) || DescribeTall(d) || DescribeTallFree(d);
   }
 
  private:
@@ -806,6 +806,42 @@ class ZeroProx final : public ProxOperator {
     d->tall = true;
     d->x_key = xk;
     d->z_key = zk;
+    d->arg_key = ak;
+    d->rhs_arg = f.Constant(ak);
+    return true;
+  }
+
+  // The graph forms without a penalty on x (least absolute deviations, quantile regression): x is
+  // no copy, it lives in this term alone and has no constraint row.  The order is [constraint, z',
+  // arg, x]: z' tied to its constraint row as above (Dinv(z') = 1), the arg pivot a scalar matrix,
+  // L(arg, z') a scalar, L(x, arg) the dense transposed data matrix and Dinv(x) the only dense pivot;
+  // these three blocks and no other in L, so nothing of x meets the constraint.  Then with v the
+  // prox input (v has no entry on x's row)
+  //   f_arg = rhs_arg - e v_z,  Solve(b_ + v)[x] = Dinv(x) (-L(x,arg) f_arg),
+  //   arg = Dinv(arg) f_arg - L(x,arg)^T x,  [z'] = v_z - e arg.
+  // The fill model gives a fat matrix the same order, where Dinv(x) inverts a singular C^T C: the
+  // shape is the route's to ask for.
+  bool DescribeTallFree(ZeroProjectionDesc* d) const {
+    const Factored f{chol_, b_};
+    const std::vector<Key>& p = chol_.order();
+    if (!f.Exact() || var_keys_.size() != 2 || p.size() != 4) return false;
+    const Key &ck = p[0], &zk = p[1], &ak = p[2], &xk = p[3];
+    if (var_keys_.count(ck) != 0 || var_keys_.count(zk) == 0 || var_keys_.count(ak) != 0 || var_keys_.count(xk) == 0)
+      return false;
+    *d = ZeroProjectionDesc();
+    if (!f.Tied(zk, ck) || !ScalarIs(f.Di(), zk, zk, 1.0)) return false;
+    // L holds these three blocks and no other: none of them joins x to the constraint row or to z'
+    if (Blocks(f.L()) != 3 || !ScalarAt(f.L(), ak, zk, &d->e)) return false;
+    if (!ScalarAt(f.Di(), ak, ak, &d->dinv_arg)) return false;
+    d->L = DenseAt(f.L(), xk, ak);
+    d->Dinv = DenseAt(f.Di(), xk, xk);
+    if (!d->L || !d->Dinv || !d->L->trans()) return false;
+    if (d->Dinv->rows() != d->L->m() || d->Dinv->cols() != d->L->m() || !f.ConstantOn(ak)) return false;
+    d->tall = true;
+    d->x_free = true;
+    d->x_key = xk;
+    d->z_key = zk;
+    d->z_constraint_key = ck;
     d->arg_key = ak;
     d->rhs_arg = f.Constant(ak);
     return true;

@@ -96,8 +96,16 @@ struct SeparableDesc {
 //   x' = Dinv (v_x - L f_arg),  arg = dinv_arg f_arg - L^T x',  z' = v_z - e arg
 // with L = L(x', arg) = -C^T / e^2 as the factorisation holds it (transposed, lazily scaled) and
 // Dinv = Dinv(x') = (I + C^T C / e^2)^-1.
+// Free x (x_free, with tall; DESIGN.md 3.11 "x in the ZERO term alone"): x is no copy - it lives in
+// the ZERO term alone, with no constraint row - and the order is [constraint, z', arg, x].  With
+// f_arg as above:
+//   x = Dinv (-L f_arg),  arg = dinv_arg f_arg - L^T x,  z' = v_z - e arg
+// with L = L(x, arg) as above and Dinv = Dinv(x) = (C^T C / e^2)^-1: no "+ I", so C must have full
+// column rank (the factorisation has the same order for fat C: the route asks for m > n itself).
+// x_constraint_key is empty.
 struct ZeroProjectionDesc {
   bool tall = false;
+  bool x_free = false;
   std::string x_key, z_key, arg_key;             // z_key empty: no z block (basis pursuit)
   std::string x_constraint_key, z_constraint_key;
   std::shared_ptr<const DenseMatrixImpl> L;     // the dense map: lazily scaled data matrix (tall: trans() set)

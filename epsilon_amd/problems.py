@@ -523,6 +523,10 @@ def least_abs_dev(m, n, seed=0):
     return prob, dict(A=A, b=b)
 
 
+def least_abs_dev_objective(A, b, x):
+    return float(np.abs(A.dot(x) - b).sum())
+
+
 def hinge_l1(m, n, lam=None, seed=0):
     """sum_i max(0, 1 - y_i a_i^T x) + lam ||x||_1: sum_hinge(1 - z) with z = diag(y) A x."""
     rng = np.random.RandomState(seed)
@@ -633,6 +637,13 @@ def quantile(m, n, tau=0.3, seed=0):
                         scaled_zone_params=wire.ProxScaledZoneParams(alpha_expr=qa.proto,
                                                                      beta_expr=qb.proto))]
     return _graph_form(terms, A, -b, x_in_terms=False), dict(A=A, b=b, tau=tau)
+
+
+def quantile_objective(A, b, tau, x):
+    """sum_i rho_tau(b_i - a_i^T x) as quantile() states it: 1 - tau on the positive part of
+    z = A x - b, tau on the negative part"""
+    z = A.dot(x) - b
+    return float((1.0 - tau) * np.maximum(z, 0).sum() + tau * np.maximum(-z, 0).sum())
 
 
 def lp(m, n, seed=0):

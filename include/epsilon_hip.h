@@ -138,6 +138,19 @@ const char* eps_version(void);
  * solves on the multi-block driver; in eps_solve_batch such an instance is solved by itself.  It
  * touches nothing but problems with a ridge term on x.  Read at every Init.  Any other value is an
  * error that names it (env EPSILON_HIP_FUSED_ZERO_RIDGE).
+ * "fused_zero_xfree" = "0" (default, and what unset means) | "1"  the same graph forms without a
+ * penalty on x, so that x is no copy and lives in the ZERO term alone (least absolute deviations,
+ * quantile regression) with tall C: on the route of "fused_zero_tall" in three launches per sweep -
+ * the pass over the transposed copy of C, one kernel on the x side that sums the pass's partials and
+ * keeps x (no state, no term: x has no constraint row), and the apply of the cached n x n inverse
+ * (C^T C / e^2)^-1.  "1": wherever that route is supported and C has more rows than columns (with
+ * fewer the inverse does not exist: the generic path); "0": never.  A smooth loss with free x, the
+ * two-block driver and sharded solves keep the generic path.  "fused_zero_tall" = "0", "fused_zero"
+ * = "0" and "fused" = "0" switch it off as well.  In eps_solve_batch under "batch_zero_tall" = "1"
+ * such instances that share C (a path over the quantile) run as one group, each bit for bit its own
+ * eps_solve; without it each is solved by itself on the route.  It touches nothing but these
+ * problems.  Read at every Init.  Any other value is an error that names it (env
+ * EPSILON_HIP_FUSED_ZERO_XFREE).
  * "fused_tall" = "auto" (default) | "0" | "1"  least squares with a separable scaled-zone penalty
  * (lasso; deadzone or quantile penalty) whose data matrix has more rows than columns: the prox of
  * the least-squares term is then the cached n x n inverse applied to the iterate minus a constant,
