@@ -83,6 +83,29 @@ with ms_per_sweep, spread and tags per side and the speedup of the group.
 
     python bench_zero.py --shapes xfree
     python bench_zero.py --shapes xfree --path 2,4,8 [--steps 100] [--runs 3]
+
+--check: the residual check of the fused ZERO-term routes (DESIGN.md 3.11 "The residual check"): the
+two sides are those of the option "fused_zero_check" - "0", its default, the driver's generic check,
+waited for, and "1" the route's one launch with the next epoch's sweeps enqueued behind it - with
+every route option on, so that each cell is on its fused sweep on both sides.  Each side runs --steps
+sweeps (a multiple of 10) from a live handle with epoch_iterations at its default, 10, and
+ignore_stopping_criteria set: every tenth sweep is followed by a check and no solve stops early.  The
+sides are alternated --runs times in one process.  One JSON line per shape:
+  ms_per_sweep        {side: median loop time / steps}, the checks included; spread as above
+  speedup             ms_per_sweep["0"] / ms_per_sweep["1"]
+  verdict             "win" / "loss" where the medians differ by more than the two spreads combined
+                      (ZERO paragraph), else "tie"
+  launches_per_check  {side: {tag: count}} of one profiled check: the profile of one sweep with its
+                      check less that of a sweep without one.  The generic check's vector kernels
+                      carry no profile tag, so side "0" shows none of its launches.
+  time_to_optimal_s   {side: median loop time of --runs solves at the default tolerances}, with
+                      stop = {side: [state, stopping sweep]}
+With --path K1,K2,... the same for a K-member group (the members of --path above) through
+_solve.solve_batch under "batch_zero_tall" = "1": ms_per_sweep from solves of --steps sweeps, stop a
+list over the members.
+
+    python bench_zero.py --check --shapes hinge_tall,hinge_tall64,logreg_tall,lad_tall,hinge,logreg,bp,ladder256,floor
+    python bench_zero.py --check --shapes hinge_tall --path 2,8
 """
 
 import argparse
@@ -151,6 +174,7 @@ def parse():
     p.add_argument("--lib", default="")
     p.add_argument("--against", default="")
     p.add_argument("--resident", default="auto", help="the option fused_resident: auto or a number of KiB")
+    p.add_argument("--check", action="store_true", help="the sides of the option fused_zero_check")
     return p.parse_args()
 
 
@@ -304,6 +328,135 @@ def path_against(a):
             flush=True)
 
 
+CHECK_SIDES = ("0", "1")  # of "fused_zero_check"
+CHECK_ROUTES_ON = (("fused_zero_tall", "1", "auto"), ("fused_zero_tall_smooth", "1", "auto"),
+                   ("fused_zero_ridge", "1", "auto"), ("fused_zero_xfree", "1", "0"))  # (option, on, default)
+
+
+def profiled_counts(fn):
+    """{tag without its shape: launches} of fn()"""
+    _solve.profile_reset()
+    _solve.profile_enable(True)
+    try:
+        fn()
+        out = {}
+        for t, (c, _) in _solve.profile_dump().items():
+            out[t.split(":")[0]] = out.get(t.split(":")[0], 0) + c
+        return out
+    finally:
+        _solve.profile_enable(False)
+
+
+def less(a, b, times=1):
+    """{tag: a[tag] - b[tag] / times} where that is not zero"""
+    out = {t: a.get(t, 0) - b.get(t, 0) / float(times) for t in set(a) | set(b)}
+    return {t: v for t, v in sorted(out.items()) if v != 0}
+
+
+def check_line(a, name, side_times, **more):
+    kind, m, n, dtype = SHAPES[name]
+    med = {side: statistics.median(v) for side, v in side_times.items()}
+    spread = {side: (max(v) - min(v)) / med[side] for side, v in side_times.items()}
+    gap, room = med["0"] - med["1"], spread["0"] * med["0"] + spread["1"] * med["1"]
+    return dict(bench="zero_check", shape=name, problem=kind, m=m, n=n, dtype=dtype, gpus=1, steps=a.steps,
+                warmup=a.warmup, runs=a.runs, epoch_iterations=10,
+                ms_per_sweep={side: 1e3 * v for side, v in med.items()}, spread=spread, speedup=med["0"] / med["1"],
+                verdict="win" if gap > room else "loss" if -gap > room else "tie", **more)
+
+
+def check_lines(a, names):
+    """the --check cells: single solves, or with --path groups"""
+    assert a.steps % 10 == 0 and a.warmup % 10 == 0, "--check takes --steps and --warmup in whole epochs"
+    ks = sorted(int(k) for k in a.path.split(",")) if a.path else [0]
+    loop = lambda st: st.timing.total_time - st.timing.init_time
+    for name in names:
+        kind, m, n, dtype = SHAPES[name]
+        _solve.set_option("dtype", dtype)
+        for option, on, _ in CHECK_ROUTES_ON:
+            _solve.set_option(option, on)
+        _solve.set_option("batch_zero_tall", "1")
+        try:
+            for K in ks:
+                line = check_group(a, name, K, loop) if K else check_single(a, name, loop)
+                print(json.dumps(line), flush=True)
+        finally:
+            _solve.set_option("fused_zero_check", "0")
+            _solve.set_option("batch_zero_tall", "0")
+            for option, _, default in CHECK_ROUTES_ON:
+                _solve.set_option(option, default)
+            _solve.set_option("dtype", "f32")
+
+
+def check_single(a, name, loop):
+    kind, m, n, dtype = SHAPES[name]
+    prob = getattr(problems, kind)(m, n)[0]
+    pb, data = prob.SerializeToString(), prob.expression_data()
+    sb = wire.SolverParams(max_iterations=10 ** 9, ignore_stopping_criteria=True).SerializeToString()
+    default = wire.SolverParams().SerializeToString()
+    handles, launches = {}, {}
+    try:
+        for side in CHECK_SIDES:
+            _solve.set_option("fused_zero_check", side)  # read at Init
+            s = handles[side] = _solve.Solver(pb, sb, data)
+            s.init()
+            s.run(a.warmup)
+            with_check = profiled_counts(lambda: s.run(1))  # sweep `warmup`, a multiple of the epoch
+            nine = profiled_counts(lambda: s.run(9))
+            assert any(t.startswith("zero_") for t in nine), (name, sorted(nine))  # on its fused sweep
+            launches[side] = less(with_check, nine, 9)
+        times = {side: [] for side in CHECK_SIDES}
+        for _ in range(a.runs):
+            for side, s in handles.items():
+                before = s.timing()[1]
+                s.run(a.steps)
+                times[side].append((s.timing()[1] - before) / a.steps)
+    finally:
+        for s in handles.values():
+            s.close()
+    optimal, stop = {side: [] for side in CHECK_SIDES}, {}
+    for r in range(a.runs + 1):  # (the first round: a warm-up)
+        for side in CHECK_SIDES:
+            _solve.set_option("fused_zero_check", side)
+            st = wire.SolverStatus.FromString(_solve.solve(pb, [], default, data)[0])
+            stop[side] = [st.state, st.num_iterations]
+            if r > 0:
+                optimal[side].append(loop(st))
+    return check_line(a, name, times, launches_per_check=launches,
+                      time_to_optimal_s={side: statistics.median(v) for side, v in optimal.items()}, stop=stop)
+
+
+def check_group(a, name, K, loop):
+    kind, m, n, dtype = SHAPES[name]
+    probs = path_members(kind, m, n, K)
+    data = {}
+    for p in probs:
+        data.update(p.expression_data())
+    pbs = [p.SerializeToString() for p in probs]
+    fixed = lambda sweeps: wire.SolverParams(max_iterations=sweeps, ignore_stopping_criteria=True).SerializeToString()
+    default = wire.SolverParams().SerializeToString()
+    launches = {}
+    for side in CHECK_SIDES:
+        _solve.set_option("fused_zero_check", side)
+        # 20, 21 and 30 sweeps have 3, 4 and 4 checks: 21 less 20 is a sweep and a check, 30 less 21 nine sweeps
+        _solve.solve_batch(pbs, None, fixed(20), data)
+        c20, c21, c30 = (profiled_counts(lambda k=k: _solve.solve_batch(pbs, None, fixed(k), data)) for k in (20, 21, 30))
+        assert any(t.startswith("batch_zero") for t in c20), (name, K, sorted(c20))  # one group
+        launches[side] = less(less(c21, c20), less(c30, c21), 9)
+    times = {side: [] for side in CHECK_SIDES}
+    optimal, stop = {side: [] for side in CHECK_SIDES}, {}
+    for r in range(a.runs):
+        for side in CHECK_SIDES:
+            _solve.set_option("fused_zero_check", side)
+            sts = [wire.SolverStatus.FromString(st) for st, _ in _solve.solve_batch(pbs, None, fixed(a.steps), data)]
+            assert all(s.num_iterations == a.steps for s in sts)
+            times[side].append(loop(sts[0]) / a.steps)  # (a group's members all carry the group's loop time)
+            sts = [wire.SolverStatus.FromString(st) for st, _ in _solve.solve_batch(pbs, None, default, data)]
+            optimal[side].append(loop(sts[0]))
+            stop[side] = [[s.state, s.num_iterations] for s in sts]
+    return check_line(a, name, times, K=K, launches_per_check=launches,
+                      time_to_optimal_s={side: statistics.median(v) for side, v in optimal.items()}, stop=stop)
+
+
 def names_of_one_sweep(s):
     _solve.profile_reset()
     _solve.profile_enable(True)
@@ -322,6 +475,8 @@ def main():
     if "xfree" in names:
         at = names.index("xfree")
         names[at:at + 1] = ["%s_%s" % (k, c[0]) for k in XFREE_KINDS for c in XFREE_CELLS]
+    if a.check:
+        return check_lines(a, names)
     if a.path and all(SHAPES[name][0] in XFREE_KINDS.values() for name in names):
         for line in xfree_path_lines(a, names):
             print(json.dumps(line), flush=True)

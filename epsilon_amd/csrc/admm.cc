@@ -82,8 +82,9 @@ Solver::Solver(pb::Problem problem, std::shared_ptr<DataMap> data, pb::SolverPar
 Solver::~Solver() {}
 
 FusedRoute* Solver::batch_route() const { return initialized_ && !finished_ && iter_ == 0 ? route_.get() : nullptr; }
-// (a route without a check of its own - the ZERO-term route - launches nothing ahead: its member
-// runs the driver's generic check, waited for, when it is asked for the outcome)
+// (a route without a check of its own - the ZERO-term route unless "fused_zero_check" is "1" -
+// launches nothing ahead: its member runs the driver's generic check, waited for, when it is asked
+// for the outcome)
 void Solver::BatchLaunchCheck(int iter) {
   iter_ = iter;
   if (route_->HasCheck()) route_->LaunchNorms();

@@ -139,7 +139,7 @@ std::vector<BlockVector*> Homes(const MultiBlockParts& a) {
 int BatchWideMin();  // (with the batched solves below)
 
 // The indices of the options' words (options.cc).  "fused" (off with a leading 0), "fused_zero",
-// "fused_zero_ridge", "fused_zero_tall", "fused_zero_tall_smooth", "fused_zero_xfree", "fused_tall", "fused_matrix" and
+// "fused_zero_check", "fused_zero_ridge", "fused_zero_tall", "fused_zero_tall_smooth", "fused_zero_xfree", "fused_tall", "fused_matrix" and
 // "fused_resident" are read at every Init, "batch_wide" and "batch_zero_tall" per batch ("1" sends eligible groups to the wide
 // route / lets the tall ZERO-term members of a batch form groups).
 // "0", "1", "auto" of "fused_tall", "fused_zero_tall", "fused_zero_tall_smooth" and "fused_zero_ridge"
@@ -888,7 +888,8 @@ struct LassoRoute final : BatchRoute {
 // sweep is then: the pass over the data matrix (chain 2: back product, column chain, forward
 // product), the row kernel (row chain, the partials' sum, r) - basis pursuit: the partials'
 // reduction alone - and the apply of the cached inverse.  The residual check is the driver's
-// generic one on views of the state.  One GPU, every dtype the compute type.
+// generic one on views of the state, or - option "fused_zero_check" = "1" - one launch of the route's
+// own, pipelined with the sweeps.  One GPU, every dtype the compute type.
 //
 // Tall C (`tall`, DESIGN.md 3.11 "Tall C"): the same terms and ties with the ZERO term's block
 // LDL^T in the tall order: arg is a scalar pivot, x' the dense one.
@@ -936,11 +937,32 @@ struct ZeroRoute final : BatchRoute {
   k::ZeroTallSamplesArgs samples;
   DVec dfarg;
   k::LassoFusedArgs acc;
+  // The residual check of the route's own (option "fused_zero_check" = "1"; DESIGN.md 3.11 "The
+  // residual check"): everything a sweep hands to the next - w, either side's state, free x, the
+  // carried head - then lies in ONE buffer, so that a snapshot is one copy.  Off: none of this exists.
+  bool own_check = false;
+  DVec carried, snapshot;
+  int64_t carried_used = 0;
+  double ax = 0, az = 0;  // the constraint maps of x and z (their copies': 1)
+  Side check_x, check_z;  // the sides as the norms kernel reads them (absent: empty)
+  DVec norm_work;         // partials + ticket of the one-launch residual norms
+  int norm_slot = 0;
+
+  // `len` zeroed values of what a sweep hands to the next: a buffer of their own, or - with a check
+  // of the route's own - the next slice of `carried`, on a 64-value boundary.
+  DVec Carried(int64_t len) {
+    if (!own_check) return DVec::Zeros(len, dt);
+    EPS_CHECK(carried_used + len <= carried.n);
+    const DVec v = carried.Slice(carried_used, len);
+    carried_used += (len + 63) / 64 * 64;
+    return v;
+  }
 
   // `tall_mode`, `tall_smooth_mode`, `ridge_mode`: the options "fused_zero_tall",
   // "fused_zero_tall_smooth" and "fused_zero_ridge"; under "auto" the measured floors apply.
-  // `xfree_on`: the option "fused_zero_xfree" is "1"
-  bool Enable(const MultiBlockParts& a, int tall_mode, int tall_smooth_mode, int ridge_mode, bool xfree_on) {
+  // `xfree_on`, `check_on`: the options "fused_zero_xfree" and "fused_zero_check" are "1"
+  bool Enable(const MultiBlockParts& a, int tall_mode, int tall_smooth_mode, int ridge_mode, bool xfree_on,
+              bool check_on) {
     if (opt::Is0(opt::kFused) || ShardSpec::Get().active() || !a.b.data().empty()) return false;
     const int nc = a.num_constraints, N = static_cast<int>(a.prox.size());
     if (nc < 1 || nc > 2 || N != nc + 1) return false;
@@ -1003,7 +1025,6 @@ struct ZeroRoute final : BatchRoute {
     // the consensus constraints: copy + a var = 0, nothing else in their rows or columns
     // (free x: the one tie is all there is, so no column of A is x's)
     if (static_cast<int>(a.A.data().size()) != 2 * nc || (xfree && a.A.data().count(zp.x_key) != 0)) return false;
-    double ax = 0, az = 0;  // constraint maps of x and z (their copies': 1)
     auto tie = [&](const std::string& ck, const std::string& copy, const std::string& var, int64_t len, double* av) {
       double a0 = 0;
       return ConsensusTie(a.A, ck, copy, var, len, &a0, av) && a0 == 1.0 && a.A.col(copy).size() == 1 &&
@@ -1014,6 +1035,15 @@ struct ZeroRoute final : BatchRoute {
     if (!Fits(zp.rhs_arg, m, dt) || !Fits(sx.alpha_vec, n, dt) || !Fits(sx.beta_vec, n, dt)) return false;
     if (!Fits(sz.alpha_vec, m, dt) || !Fits(sz.beta_vec, m, dt) || !Fits(sz.g, m, dt)) return false;
     if (tall && !TransposedCopy(a.shared_cache)) return false;
+    own_check = check_on;
+    if (own_check) {
+      auto pad = [](int64_t len) { return (len + 63) / 64 * 64; };
+      const bool smooth = sz.kind == SeparableDesc::kSmooth;
+      const int64_t sides = (xfree ? pad(n) : 7 * pad(n)) + (has_z ? 7 * pad(m) : 0);
+      carried = DVec::Zeros(pad(nw) + sides + (smooth ? pad(3 * m) : 0), dt);
+      snapshot = DVec::Empty(carried.n, dt);
+      norm_work = DVec::Zeros(k::kZeroNormsWork, F64);
+    }
 
     // state: u, var, copy, y of the separable term, y of the ZERO term, their previous values -
     // per constraint row, taken over from the generic containers (warm start)
@@ -1022,7 +1052,7 @@ struct ZeroRoute final : BatchRoute {
     auto side = [&](int64_t len, const std::string& ck, int term, const std::string& var, const std::string& copy,
                     DVec* all) {
       const int64_t pad = (len + 63) / 64 * 64;
-      *all = DVec::Zeros(7 * pad, dt);
+      *all = Carried(7 * pad);
       Side s;
       int64_t q = 0;  // the next slice of `all`
       auto slice = [&](DVec* v, BlockVector* home, const std::string& key, bool take = true) {
@@ -1040,19 +1070,21 @@ struct ZeroRoute final : BatchRoute {
     };
     // (tall: the pass's register-held dimension is n, its streamed columns are the m samples)
     grid = tall ? k::LassoFusedGrid(n, m, dt) : k::LassoFusedGrid(m, n, dt);
-    w = DVec::Zeros(nw, dt);
+    w = Carried(nw);
     p = DVec::Zeros(nw, dt);
     tpart = DVec::Empty(static_cast<int64_t>(grid) * nw, dt);
     inv.Init(zp.Dinv, nw, p, w, a.shared_cache);
     // (free x: x itself is the x side, a view of the ZERO term's own variable like a copy is)
     Side sn;
     if (xfree) {
-      xcur = DVec::Zeros(n, dt);
+      xcur = Carried(n);
       views.push_back({&a.x[N - 1], zp.x_key, xcur, true});
     } else {
       sn = side(n, zp.x_constraint_key, ix, sx.var_key, zp.x_key, &state_n);
     }
     const Side sm = has_z ? side(m, zp.z_constraint_key, iz, sz.var_key, zp.z_key, &state_m) : Side();
+    check_x = sn;
+    check_z = sm;
     if (tall) FillTall(sn, ax, sm, az);
     else FillFat(sn, ax, sm, az);
     // beside the matrix the sweep touches the partials (the rows kernel re-reads them), the seven
@@ -1129,7 +1161,7 @@ struct ZeroRoute final : BatchRoute {
     rows.g = sz.g;
     rows.e = zp.e;
     if (rows.smooth) {
-      head = DVec::Zeros(3 * m, dt);
+      head = Carried(3 * m);
       rows.hs = head.Slice(0, m);
       rows.hys = head.Slice(m, m);
       rows.hv = head.Slice(2 * m, m);
@@ -1158,7 +1190,7 @@ struct ZeroRoute final : BatchRoute {
     // the pass in two halves (chains 4 and 5) around the sample kernel, which takes the z side's
     // state, zone, offset, rhs and pivots from the pass's record
     pass.chain = 4;
-    head = DVec::Zeros(3 * m, dt);
+    head = Carried(3 * m);
     dfarg = DVec::Zeros(2 * m, dt);
     i.zd = dfarg.Slice(0, m);
     i.zfarg = dfarg.Slice(m, m);
@@ -1216,6 +1248,52 @@ struct ZeroRoute final : BatchRoute {
     else
       k::ReducePartials(m, grid, tpart, pass.inst.pkappa, 0.0, p, zp.rhs_arg.n != 0 ? &zp.rhs_arg : nullptr);
     inv.Apply();
+  }
+
+  // ---- residual check (option "fused_zero_check"): one launch, splittable for pipelining ---------
+  // With b empty, the ZERO term last and each row c tying its copy (coefficient 1) to one term's
+  // variable (coefficient a_c), the quantities of prox_admm.cc:178-217 are, summed over the sides
+  // that are present,
+  //   ||A x_term,c|| = ||y_term,c||,  ||A x_ZERO||^2 = sum_c ||y_zero,c||^2,  r^2 = sum_c ||y_term,c + y_zero,c||^2,
+  //   s^2 = sum_c a_c^2 ||y_zero,c - y_zero_prev,c||^2  (A_i^T of term i reads its own row alone, and
+  //   on that row Ax_diff holds the ZERO term's difference and no other),
+  //   ||A^T u||^2 = sum_c (1 + a_c^2) ||u_c||^2.
+  bool HasCheck() const override { return own_check; }
+  bool PipelineChecks() const override {
+    static const bool off = opt::Is0(opt::kPipelineChecks);
+    return own_check && !off;
+  }
+  // the check's ten scalars into the next ten slots
+  void LaunchNorms() override {
+    EPS_CHECK(own_check);
+    Runtime& rt = Runtime::Get();
+    norm_slot = rt.NewSlot();
+    for (int q = 1; q < 10; ++q) rt.NewSlot();
+    k::ZeroFusedNorms(check_x, check_z, rt.SlotPtr(norm_slot), norm_work,
+                      tall ? "zero_tall_norms" : "zero_fused_norms");
+  }
+  Check FinishCheck() override {
+    Runtime& rt = Runtime::Get();
+    double x[5], z[5];
+    for (int q = 0; q < 5; ++q) {
+      x[q] = rt.SlotValue(norm_slot + q);
+      z[q] = rt.SlotValue(norm_slot + 5 + q);
+    }
+    Check c;
+    c.r = std::sqrt(x[2] + z[2]);
+    c.s = std::sqrt(ax * ax * x[3] + az * az * z[3]);
+    c.max_norm = std::fmax(std::fmax(std::sqrt(x[0]), std::sqrt(z[0])), std::sqrt(x[1] + z[1]));
+    c.atu = std::sqrt((1.0 + ax * ax) * x[4] + (1.0 + az * az) * z[4]);
+    return c;
+  }
+  // What a sweep hands to the next is `carried` and nothing else: the pass reads w and its side's
+  // state, the row kernel (the sample kernel) the other side's and the head, the free-x kernel keeps
+  // xcur; p, the partials, d and f_arg and the apply's workspace are written in every sweep before
+  // they are read.
+  void SaveSnapshot() override { k::Copy(snapshot, carried); }
+  void RestoreSnapshot() override {
+    Runtime::Get().Sync();  // let the discarded sweeps drain
+    k::Copy(carried, snapshot);
   }
 
   // ---- batched solves (RunFusedBatches) ---------------------------------------------------------
@@ -1355,9 +1433,10 @@ std::unique_ptr<FusedRoute> RecogniseMultiBlockRoute(const MultiBlockParts& part
   const int lasso_tall = opt::Word(opt::kFusedTall);
   const int ridge = opt::Word(opt::kFusedZeroRidge);
   const bool xfree = opt::Word(opt::kFusedZeroXfree) != 0;
+  const bool check = opt::Word(opt::kFusedZeroCheck) != 0;
   if (auto r = Recognise<LassoRoute>(parts, lasso_tall)) return r;  // fat, then tall
   if (!zero) return nullptr;
-  return Recognise<ZeroRoute>(parts, tall, tall_smooth, ridge, xfree);  // fat, then tall, then tall with free x
+  return Recognise<ZeroRoute>(parts, tall, tall_smooth, ridge, xfree, check);  // fat, then tall, then tall with free x
 }
 
 std::unique_ptr<FusedRoute> RecogniseTwoBlockRoute(const TwoBlockParts& parts) {
@@ -1420,7 +1499,8 @@ void RunGroupSchedule(const Group& g, double t0, std::vector<int>* active, Sweep
 // the rhs folded in) - and one batched apply of the packed inverse (below m = 1024: each member's
 // own apply; whitened: none).  Each launch does per member what the member's own sweep does, so
 // its iterates are the single solve's bit for bit; a ZERO-term member's residual check is the
-// driver's generic one, at the sweeps of the member's own Run().
+// driver's generic one - under "fused_zero_check" its own one launch, with one fetch for the group -
+// at the sweeps of the member's own Run().
 // Tall ZERO-term members: every launch in the pass's own dimensions (pass.m = n, the order of the
 // dense pivot), and for a smooth z term the pass in halves around one sample launch (BatchSweep).
 void RunPassGroup(const Group& g) {

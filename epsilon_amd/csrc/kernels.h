@@ -223,6 +223,21 @@ void LassoFusedPass(const LassoFusedArgs& args);
 // `tag`: the launch's profile tag (the tall lasso route's is "lasso_tall_norms").
 void LassoFusedNorms(const DVec& u, const DVec& y0, const DVec& y1, const DVec& y1prev, double* out6,
                      const DVec& work, const unsigned* peer_err = nullptr, const char* tag = "lasso_fused_norms");
+// The residual check of a ZERO-term route ("The residual check"), one launch: per
+// constraint side c, out10[5 c + ...] = {||y_term||^2, ||y_zero||^2, ||y_term + y_zero||^2,
+// ||y_zero - y_zero_prev||^2, ||u||^2} (device doubles; c = 0: `x`, c = 1: `z`), accumulated in double
+// from the state's own type.  A side whose u is empty is absent and its five values are 0; of a side
+// present u, y_term, y_zero and y_zero_prev are read, all of one length and of the dtype both sides
+// share.  At most 64 workgroups, split between the sides as ZeroFusedNormsGrid says; the summation
+// order is a function of the two lengths alone.  `work`: kZeroNormsWork doubles, zero-initialised once
+// and private to the caller (ten partials per workgroup; the last double is a ticket counter).
+// `tag`: "zero_fused_norms" on the fat route, "zero_tall_norms" on the tall ones.
+constexpr int64_t kZeroNormsWork = 64 * 10 + 1;
+void ZeroFusedNorms(const ConsensusState& x, const ConsensusState& z, double* out10, const DVec& work,
+                    const char* tag);
+// The workgroups of each side for lengths nx, nz (0: absent, none): one per 1024 entries, and from
+// 64 in all on in proportion to the lengths, a side that is present keeping at least one.
+void ZeroFusedNormsGrid(int64_t nx, int64_t nz, int* gx, int* gz);
 
 // ---- batched fused pass: instances sharing one data matrix (kernels_fused_batch.hip) ---------
 // One instance of a batched sweep as the kernels read it (device array, compute type T): the

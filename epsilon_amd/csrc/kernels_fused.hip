@@ -845,6 +845,124 @@ void LassoFusedNorms(const DVec& u, const DVec& y0, const DVec& y1, const DVec& 
   EPS_HIP(hipGetLastError());
 }
 
+namespace {
+
+// The residual check of a ZERO-term route in ONE launch: the five sums of squares ||y_term||^2,
+// ||y_zero||^2, ||y_term + y_zero||^2, ||y_zero - y_zero_prev||^2, ||u||^2 of the x constraint's
+// rows and of the z constraint's, accumulated in double from the state's own type.  Workgroups
+// [0, gx) reduce contiguous parts of the x side, [gx, gridDim.x) of the z side (a side that is
+// absent has none); each publishes ten partials, the five of the other side zero, and the
+// workgroup whose ticket comes last adds them in workgroup order.  The hand-off is
+// LassoFusedNormsKernel's as it stands.
+static_assert(kZeroNormsWork == kNormBlocks * 10 + 1, "ten partials per workgroup and the ticket");
+template <class T> struct ZeroNormsSideT {
+  int64_t len;
+  const T *u, *y_term, *y_zero, *y_zero_prev;
+};
+
+template <class T>
+__global__ __launch_bounds__(kBlock) void ZeroFusedNormsKernel(ZeroNormsSideT<T> sx, ZeroNormsSideT<T> sz,
+                                                               unsigned gx, double* partial, unsigned* ticket,
+                                                               double* out) {
+  __shared__ double red[kBlock / 64][5];
+  __shared__ bool last;
+  const bool on_x = blockIdx.x < gx;  // uniform over the workgroup
+  const ZeroNormsSideT<T> side = on_x ? sx : sz;
+  const int64_t parts = on_x ? gx : gridDim.x - gx, part = on_x ? blockIdx.x : blockIdx.x - gx;
+  const int64_t per = (side.len + parts - 1) / parts;
+  const int64_t lo = part * per;
+  int64_t hi = lo + per;
+  if (hi > side.len) hi = side.len;
+  double s[5] = {0, 0, 0, 0, 0};
+  for (int64_t i = lo + threadIdx.x; i < hi; i += kBlock) {
+    const double a = side.y_term[i], b = side.y_zero[i], c = side.y_zero_prev[i], d = side.u[i];
+    s[0] += a * a;
+    s[1] += b * b;
+    s[2] += (a + b) * (a + b);
+    s[3] += (b - c) * (b - c);
+    s[4] += d * d;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const double t = WaveSumT<double>(s[k]);
+    if (lane == 0) red[wave][k] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x < 10) {
+    const int k = threadIdx.x % 5;
+    const bool mine = (threadIdx.x < 5) == on_x;  // slots 0-4: the x side's, 5-9: the z side's
+    const double t = mine ? ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k] : 0.0;
+    __hip_atomic_store(partial + blockIdx.x * 10 + threadIdx.x, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned prev = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last = prev == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!last) return;
+  if (threadIdx.x < 10) {
+    const int k = threadIdx.x;
+    double t = 0;
+    for (unsigned b = 0; b < gridDim.x; ++b)
+      t += __hip_atomic_load(partial + b * 10 + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    out[k] = t;
+  }
+  if (threadIdx.x == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// A side of the check from the route's state; absent (len 0) when the state is empty.
+template <class T> ZeroNormsSideT<T> NormsSideOf(const ConsensusState& s) {
+  return {s.u.n, OptT<T>(s.u), OptT<T>(s.y_term), OptT<T>(s.y_zero), OptT<T>(s.y_zero_prev)};
+}
+
+template <class T>
+void LaunchZeroFusedNorms(const ConsensusState& x, const ConsensusState& z, unsigned gx, unsigned gz, double* partial,
+                          unsigned* ticket, double* out10) {
+  hipLaunchKernelGGL(ZeroFusedNormsKernel<T>, dim3(gx + gz), dim3(kBlock), 0, Runtime::Get().stream(),
+                     NormsSideOf<T>(x), NormsSideOf<T>(z), gx, partial, ticket, out10);
+}
+
+}  // namespace
+
+void ZeroFusedNormsGrid(int64_t nx, int64_t nz, int* gx, int* gz) {
+  auto want = [](int64_t len) { return (len + 4 * kBlock - 1) / (4 * kBlock); };
+  int64_t a = want(nx), b = want(nz);
+  if (a + b > kNormBlocks) {
+    // in proportion to the lengths, rounded to nearest, a side that is present keeping one
+    a = (kNormBlocks * nx + (nx + nz) / 2) / (nx + nz);
+    if (a < 1 && nx > 0) a = 1;
+    if (a > kNormBlocks - 1 && nz > 0) a = kNormBlocks - 1;
+    b = kNormBlocks - a;
+  }
+  *gx = static_cast<int>(a);
+  *gz = static_cast<int>(b);
+}
+
+void ZeroFusedNorms(const ConsensusState& x, const ConsensusState& z, double* out10, const DVec& work,
+                    const char* tag) {
+  const int64_t nx = x.u.n, nz = z.u.n;
+  EPS_CHECK_MSG(nx > 0 || nz > 0, "the ZERO-term check needs a side");
+  const DType dt = nx > 0 ? x.u.dt : z.u.dt;
+  for (const ConsensusState* s : {&x, &z})
+    for (const DVec* v : {&s->u, &s->y_term, &s->y_zero, &s->y_zero_prev})
+      EPS_CHECK(v->n == s->u.n && (v->n == 0 || v->dt == dt));
+  EPS_CHECK(out10 != nullptr && work.dt == F64 && work.n >= kZeroNormsWork);
+  int gx = 0, gz = 0;
+  ZeroFusedNormsGrid(nx, nz, &gx, &gz);
+  EPS_CHECK(gx + gz >= 1 && gx + gz <= kNormBlocks && (gx > 0) == (nx > 0) && (gz > 0) == (nz > 0));
+  double* partial = work.as<double>();
+  unsigned* ticket = reinterpret_cast<unsigned*>(partial + kNormBlocks * 10);  // zero between launches
+  ProfScope prof(tag, nx, nz);
+  if (dt == F32)
+    LaunchZeroFusedNorms<float>(x, z, static_cast<unsigned>(gx), static_cast<unsigned>(gz), partial, ticket, out10);
+  else
+    LaunchZeroFusedNorms<double>(x, z, static_cast<unsigned>(gx), static_cast<unsigned>(gz), partial, ticket, out10);
+  EPS_HIP(hipGetLastError());
+}
+
 bool LassoFusedSupported(int64_t m, int64_t n, const DVec& A, int64_t lda) {
   if (n < 1 || reinterpret_cast<uintptr_t>(A.data()) % 16 != 0) return false;
   if (A.dt == F32) return m >= 4 && m % 4 == 0 && lda % 4 == 0 && m <= 20 * 1024;

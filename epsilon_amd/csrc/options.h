@@ -28,6 +28,7 @@ enum Id {
   kFusedTall,
   kFusedWhiten,
   kFusedZero,
+  kFusedZeroCheck,
   kFusedZeroRidge,
   kFusedZeroTall,
   kFusedZeroTallSmooth,

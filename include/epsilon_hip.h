@@ -151,6 +151,17 @@ const char* eps_version(void);
  * eps_solve; without it each is solved by itself on the route.  It touches nothing but these
  * problems.  Read at every Init.  Any other value is an error that names it (env
  * EPSILON_HIP_FUSED_ZERO_XFREE).
+ * "fused_zero_check" = "0" (default, and what unset means) | "1"  the residual check of the fused
+ * ZERO-term routes above (fat and tall; zone, logistic and ridge terms; free x).  "0": the driver's
+ * generic check on views of the route's state - some thirty small vector launches and a fetch the
+ * host waits for before it enqueues the next sweep.  "1": one launch that sums the five squares of
+ * either constraint side in double, in a summation order fixed by the two lengths; the host finishes
+ * the closed form, the next epoch's sweeps are enqueued behind the check (EPSILON_HIP_PIPELINE_CHECKS=0:
+ * not), and if the check says OPTIMAL they are discarded and a snapshot of the iterate is restored.
+ * In eps_solve_batch a group's check is then one launch per active member and one fetch.  The
+ * iterates do not depend on it, bit for bit; r_norm, s_norm and the two tolerances agree with the
+ * generic check's to rounding.  It touches nothing but solves on those routes.  Read at every Init.
+ * Any other value is an error that names it (env EPSILON_HIP_FUSED_ZERO_CHECK).
  * "fused_tall" = "auto" (default) | "0" | "1"  least squares with a separable scaled-zone penalty
  * (lasso; deadzone or quantile penalty) whose data matrix has more rows than columns: the prox of
  * the least-squares term is then the cached n x n inverse applied to the iterate minus a constant,
