@@ -84,6 +84,16 @@ with ms_per_sweep, spread and tags per side and the speedup of the group.
     python bench_zero.py --shapes xfree
     python bench_zero.py --shapes xfree --path 2,4,8 [--steps 100] [--runs 3]
 
+LP cells (a linear term on x, the non-negative cone on z: problems.lp, and the cone with an l1 or ridge
+term on x: problems.polyhedron; DESIGN.md 3.11 "A linear term on x, a cone on z"): the routes are those
+of the option "fused_zero_lp" - "0", its default, the generic operator path, which is what these
+problems took before the option existed, and "1" the fused sweep - with "fused_zero_tall" = "1".
+lp_ladder256 / 512 / 1024 / 2048 = the 4n x n ladder, lp_tall = 5000 x 1500 (lp_tall64 in f64), and the
+fat cells lp_floor = 256 x 601, lp_fat = 1500 x 5000; poly_l1_tall, poly_l1_fat, poly_l2_tall,
+poly_l2_fat = the polyhedron problems at 5000 x 1500 and 1500 x 5000.  --shapes lp is all of them.
+
+    python bench_zero.py --shapes lp
+
 --check: the residual check of the fused ZERO-term routes (DESIGN.md 3.11 "The residual check"): the
 two sides are those of the option "fused_zero_check" - "0", its default, the driver's generic check,
 waited for, and "1" the route's one launch with the next epoch's sweeps enqueued behind it - with
@@ -159,6 +169,13 @@ XFREE_CELLS = RIDGE_CELLS[:6]  # the ladder and the two 5000 x 1500 cells: no fa
 for _name, _kind in XFREE_KINDS.items():
     for _cell, _m, _n, _dtype in XFREE_CELLS:
         SHAPES["%s_%s" % (_name, _cell)] = (_kind, _m, _n, _dtype)
+LP_KINDS = {"lp": problems.lp, "poly_l1": lambda m, n: problems.polyhedron(m, n, norm="l1"),
+            "poly_l2": lambda m, n: problems.polyhedron(m, n, norm="l2")}
+LP_CELLS = RIDGE_CELLS[:8]  # the ladder, the two 5000 x 1500 cells, and the fat cells 256 x 601 and 1500 x 5000
+LP_NAMES = ["lp_%s" % c[0] for c in LP_CELLS] + ["%s_%s" % (k, c) for k in ("poly_l1", "poly_l2") for c in ("tall", "fat")]
+for _name in LP_NAMES:
+    _kind, _cell = _name.rsplit("_", 1)
+    SHAPES[_name] = (_kind,) + [c[1:] for c in RIDGE_CELLS if c[0] == _cell][0]
 ROUTES = ("0", "auto")
 TALL_ROUTES = ("0", "1")  # of "fused_zero_tall", for the cells with more rows than columns
 
@@ -490,11 +507,15 @@ def main():
     if "ridge" in names:
         at = names.index("ridge")
         names[at:at + 1] = ["%s_%s" % (k, c[0]) for k in RIDGE_KINDS for c in RIDGE_CELLS]
+    if "lp" in names:
+        at = names.index("lp")
+        names[at:at + 1] = LP_NAMES
     for name in names:
         kind, m, n, dtype = SHAPES[name]
         tall = m > n
         ridge = kind in RIDGE_KINDS
         xfree = kind in XFREE_KINDS.values()
+        lp = kind in LP_KINDS
         option, routes, tag = (("fused_zero_tall_smooth", TALL_ROUTES, "zero_tall_samples")
                                if tall and kind.startswith("logreg") else
                                ("fused_zero_tall", TALL_ROUTES, "zero_tall") if tall else
@@ -503,12 +524,14 @@ def main():
             option, routes = "fused_zero_ridge", TALL_ROUTES
         if xfree:  # the x side's own launch shows the route
             option, routes, tag = "fused_zero_xfree", TALL_ROUTES, "zero_tall_free_cols"
-        prob = getattr(problems, kind)(m, n)[0]
+        if lp:  # the same tags show the route; the option that is switched is the two heads'
+            option, routes = "fused_zero_lp", TALL_ROUTES
+        prob = (LP_KINDS[kind] if lp else getattr(problems, kind))(m, n)[0]
         pb, data = prob.SerializeToString(), prob.expression_data()
         sb = wire.SolverParams(max_iterations=10 ** 9, ignore_stopping_criteria=True).SerializeToString()
         _solve.set_option("dtype", dtype)
         _solve.set_option("fused_resident", a.resident)
-        if option == "fused_zero_tall_smooth" or ridge or xfree:
+        if option == "fused_zero_tall_smooth" or ridge or xfree or lp:
             _solve.set_option("fused_zero_tall", "1")
         if ridge:
             _solve.set_option("fused_zero_tall_smooth", "1")
@@ -534,7 +557,7 @@ def main():
         finally:
             for s in handles.values():
                 s.close()
-            _solve.set_option(option, "0" if xfree else "auto")
+            _solve.set_option(option, "0" if xfree or lp else "auto")
             _solve.set_option("fused_zero_tall", "auto")
             _solve.set_option("fused_zero_tall_smooth", "auto")
             _solve.set_option("fused_resident", "auto")
@@ -547,7 +570,7 @@ def main():
                     speedup=(ms["0"] / ms[routes[1]] if ms[routes[1]] else None))
         if a.resident != "auto":
             line["fused_resident_kb"] = int(a.resident)
-        if ridge or xfree:
+        if ridge or xfree or lp:
             line["option"] = option
         if tall:
             line["sweeps_per_s"] = {r: (1e3 / ms[r] if ms[r] else None) for r in routes}

@@ -23,7 +23,7 @@ namespace {
 // The zone of a kernel record from the operator's description; a1: the scalar of the term's
 // variable in its consensus constraint.  A ridge term takes the record with Bs, Cs the two factors of
 // its block solve; smooth terms and row groups read the scalar form alone (the zone's parameters are
-// the defaults).
+// the defaults).  A linear term and the non-negative cone take it with their step in the zone's place.
 k::ZoneParams ZoneOf(const SeparableDesc& z, double a1) {
   k::ZoneParams s;
   s.alpha_vec = z.alpha_vec;
@@ -36,6 +36,8 @@ k::ZoneParams ZoneOf(const SeparableDesc& z, double a1) {
   s.beta = z.beta;
   s.M = z.M;
   s.ridge = z.kind == SeparableDesc::kRidge;
+  if (z.kind == SeparableDesc::kLinear) s.step = k::kStepLinear;
+  if (z.kind == SeparableDesc::kNonNegative) s.step = k::kStepNonNeg;
   return s;
 }
 
@@ -139,7 +141,7 @@ std::vector<BlockVector*> Homes(const MultiBlockParts& a) {
 int BatchWideMin();  // (with the batched solves below)
 
 // The indices of the options' words (options.cc).  "fused" (off with a leading 0), "fused_zero",
-// "fused_zero_check", "fused_zero_ridge", "fused_zero_tall", "fused_zero_tall_smooth", "fused_zero_xfree", "fused_tall", "fused_matrix" and
+// "fused_zero_check", "fused_zero_lp", "fused_zero_ridge", "fused_zero_tall", "fused_zero_tall_smooth", "fused_zero_xfree", "fused_tall", "fused_matrix" and
 // "fused_resident" are read at every Init, "batch_wide" and "batch_zero_tall" per batch ("1" sends eligible groups to the wide
 // route / lets the tall ZERO-term members of a batch form groups).
 // "0", "1", "auto" of "fused_tall", "fused_zero_tall", "fused_zero_tall_smooth" and "fused_zero_ridge"
@@ -910,6 +912,13 @@ struct LassoRoute final : BatchRoute {
 // threshold's place; everything else is as above.
 // Single solves on the multi-block driver alone: such a member of a batch is solved by itself.
 //
+// A linear term on x, the non-negative cone on z (`sx` of kind kLinear, `sz` of kind kNonNegative,
+// option "fused_zero_lp" = "1"; DESIGN.md 3.11 "A linear term on x, a cone on z"): the two heads that
+// problems.lp needs.  Each stands in its side's threshold's place - on fat C the linear step in the
+// pass and the cone in the rows, on tall C the cone in the pass and the linear step in the x-side
+// kernel - and the sides are independent, so either also runs with the other side's zone, ridge or
+// smooth term.  The 256-thread shapes and single solves alone; never with free x.
+//
 // Free x (`zp.x_free`, option "fused_zero_xfree" = "1"; DESIGN.md 3.11 "x in the ZERO term alone"): no
 // term on x, so x is no copy - it lives in the ZERO term alone and has no constraint row
 // (least_abs_dev, quantile).  The tall form with one constraint and one separable term, a zone on z:
@@ -921,7 +930,8 @@ struct ZeroRoute final : BatchRoute {
   using Side = k::ConsensusState;  // of the x constraint, of the z constraint
 
   ZeroProjectionDesc zp;
-  SeparableDesc sx, sz;  // the separable terms on x (a zone, or a ridge term) and on z (a zone, or smooth)
+  // the separable terms on x (a zone, a ridge term or a linear term) and on z (a zone, smooth or the cone)
+  SeparableDesc sx, sz;
   bool tall = false;
   bool has_z = false;
   // m, n: C is m x n.  w, p, tpart: the dense pivot's vectors (tall: x' of the coming sweep, f_x and
@@ -960,9 +970,10 @@ struct ZeroRoute final : BatchRoute {
 
   // `tall_mode`, `tall_smooth_mode`, `ridge_mode`: the options "fused_zero_tall",
   // "fused_zero_tall_smooth" and "fused_zero_ridge"; under "auto" the measured floors apply.
-  // `xfree_on`, `check_on`: the options "fused_zero_xfree" and "fused_zero_check" are "1"
+  // `xfree_on`, `lp_on`, `check_on`: the options "fused_zero_xfree", "fused_zero_lp" and
+  // "fused_zero_check" are "1"
   bool Enable(const MultiBlockParts& a, int tall_mode, int tall_smooth_mode, int ridge_mode, bool xfree_on,
-              bool check_on) {
+              bool lp_on, bool check_on) {
     if (opt::Is0(opt::kFused) || ShardSpec::Get().active() || !a.b.data().empty()) return false;
     const int nc = a.num_constraints, N = static_cast<int>(a.prox.size());
     if (nc < 1 || nc > 2 || N != nc + 1) return false;
@@ -977,12 +988,15 @@ struct ZeroRoute final : BatchRoute {
     for (int i = 0; i + 1 < N; ++i) {
       SeparableDesc d;
       if (!a.prox[i]->DescribeSeparable(&d)) return false;
-      // accepted on x: a zone without offset, or a ridge term; on z: a zone (its offset with it), or a
-      // smooth term (tall: SUM_LOGISTIC alone) - each once, on its own constraint row
+      // accepted on x: a zone without offset, a ridge term, or - "fused_zero_lp" - a linear term; on z: a
+      // zone (its offset with it), a smooth term (tall: SUM_LOGISTIC alone), or - "fused_zero_lp" - the
+      // non-negative cone (its offset with it) - each once, on its own constraint row
       const bool zone = d.kind == SeparableDesc::kZone, smooth = d.kind == SeparableDesc::kSmooth;
-      // free x: no term on x, and on z a zone alone (a smooth z term keeps the generic path)
-      const bool on_x = !xfree && ((zone && d.g.n == 0) || d.kind == SeparableDesc::kRidge);
-      const bool on_z = zone || (smooth && !xfree && (!tall || d.fn == k::SMOOTH_LOGISTIC));
+      const bool linear = lp_on && d.kind == SeparableDesc::kLinear;
+      const bool nonneg = lp_on && d.kind == SeparableDesc::kNonNegative;
+      // free x: no term on x, and on z a zone alone (a smooth z term and the cone keep the generic path)
+      const bool on_x = !xfree && ((zone && d.g.n == 0) || d.kind == SeparableDesc::kRidge || linear);
+      const bool on_z = zone || ((smooth || nonneg) && !xfree && (!tall || !smooth || d.fn == k::SMOOTH_LOGISTIC));
       if (on_x && ix < 0 && d.constraint_key == zp.x_constraint_key) {
         sx = d;
         ix = i;
@@ -995,6 +1009,8 @@ struct ZeroRoute final : BatchRoute {
     }
     if ((!xfree && ix < 0) || (has_z && iz < 0)) return false;
     const bool x_ridge = !xfree && sx.kind == SeparableDesc::kRidge;
+    const bool x_linear = !xfree && sx.kind == SeparableDesc::kLinear;
+    const bool lp_head = x_linear || (has_z && sz.kind == SeparableDesc::kNonNegative);
     // (the smooth form belongs to the z side: tall, that is the sample kernel, not the rows)
     samples_smooth = tall && sz.kind == SeparableDesc::kSmooth;
     rows.smooth = !tall && sz.kind == SeparableDesc::kSmooth;
@@ -1018,9 +1034,12 @@ struct ZeroRoute final : BatchRoute {
       }
       const int64_t ridge_floor = samples_smooth ? kZeroRidgeTallSmoothAutoMinCols : kZeroRidgeTallAutoMinCols;
       if (x_ridge && !Allowed(ridge_mode, n, ridge_floor)) return false;
+      // the linear and the non-negative head exist in the 256-thread shapes alone
+      if (lp_head && k::LassoFusedBlock(n, m, dt) != 256) return false;
     } else {
       if (m < kZeroFusedMinRows || !k::LassoFusedSupported(m, n, L.data(), L.rows())) return false;
       if (x_ridge && !Allowed(ridge_mode, m, kZeroRidgeAutoMinRows)) return false;
+      if (lp_head && k::LassoFusedBlock(m, n, dt) != 256) return false;
     }
     // the consensus constraints: copy + a var = 0, nothing else in their rows or columns
     // (free x: the one tie is all there is, so no column of A is x's)
@@ -1034,6 +1053,7 @@ struct ZeroRoute final : BatchRoute {
     if (has_z && !tie(zp.z_constraint_key, zp.z_key, sz.var_key, m, &az)) return false;
     if (!Fits(zp.rhs_arg, m, dt) || !Fits(sx.alpha_vec, n, dt) || !Fits(sx.beta_vec, n, dt)) return false;
     if (!Fits(sz.alpha_vec, m, dt) || !Fits(sz.beta_vec, m, dt) || !Fits(sz.g, m, dt)) return false;
+    if (x_linear ? (sx.g.n != n || sx.g.dt != dt) : sx.g.n != 0) return false;  // the linear term's vector, and no other
     if (tall && !TransposedCopy(a.shared_cache)) return false;
     own_check = check_on;
     if (own_check) {
@@ -1155,6 +1175,7 @@ struct ZeroRoute final : BatchRoute {
     pass.A = zp.L->data();
     PassSide(2, sn, sx, ax);
     pass.inst.rhs = zp.rhs_arg;
+    if (sx.kind == SeparableDesc::kLinear) pass.inst.zg = sx.g;  // one value per streamed column
     if (!has_z) return;
     RowsSide(sm, sz, az);
     rows.rhs = zp.rhs_arg;
@@ -1182,6 +1203,7 @@ struct ZeroRoute final : BatchRoute {
     i.dinv = zp.dinv_arg;
     RowsSide(sn, sx, ax);
     rows.tall = true;
+    if (sx.kind == SeparableDesc::kLinear) rows.g = sx.g;
     if (zp.x_free) {  // no state and no term on this side: x alone (RowsSide's are empty defaults)
       rows.x_free = true;
       rows.xcur = xcur;
@@ -1310,8 +1332,9 @@ struct ZeroRoute final : BatchRoute {
   // a scaled-zone group), the scalar pivot, and whether x is free (such a member has another x-side
   // launch: it never joins a hinge or deadzone group).
   bool BatchKey(const pb::SolverParams& params, bool tall_groups, std::vector<uint64_t>* key) const override {
-    // the batched kernels have no ridge head: such a member is solved by itself
-    if (sx.kind == SeparableDesc::kRidge) return false;
+    // the batched kernels have no ridge, linear or non-negative head: such a member is solved by itself
+    if (sx.kind == SeparableDesc::kRidge || sx.kind == SeparableDesc::kLinear) return false;
+    if (has_z && sz.kind == SeparableDesc::kNonNegative) return false;
     if (tall) {
       if (!tall_groups || !has_z || k::LassoBatchWidth(pass.m, pass.n, dt, pass.chain) == 0) return false;
       if (samples_smooth && k::LassoBatchWidth(pass.m, pass.n, dt, acc.chain) == 0) return false;
@@ -1433,10 +1456,11 @@ std::unique_ptr<FusedRoute> RecogniseMultiBlockRoute(const MultiBlockParts& part
   const int lasso_tall = opt::Word(opt::kFusedTall);
   const int ridge = opt::Word(opt::kFusedZeroRidge);
   const bool xfree = opt::Word(opt::kFusedZeroXfree) != 0;
+  const bool lp = opt::Word(opt::kFusedZeroLp) != 0;
   const bool check = opt::Word(opt::kFusedZeroCheck) != 0;
   if (auto r = Recognise<LassoRoute>(parts, lasso_tall)) return r;  // fat, then tall
   if (!zero) return nullptr;
-  return Recognise<ZeroRoute>(parts, tall, tall_smooth, ridge, xfree, check);  // fat, then tall, then tall with free x
+  return Recognise<ZeroRoute>(parts, tall, tall_smooth, ridge, xfree, lp, check);  // fat, then tall, then tall with free x
 }
 
 std::unique_ptr<FusedRoute> RecogniseTwoBlockRoute(const TwoBlockParts& parts) {

@@ -74,10 +74,19 @@ struct ConsensusState {
 // `ridge` (the x side of a ZERO-term sweep alone: LassoFusedArgs chain 2, ZeroRowsArgs::tall): the
 // term is a scalar least-squares prox instead, var = Cs (Bs v) with Bs and Cs the two factors of its
 // block solve (-L(var, constraint) and Dinv(var)); the zone's parameters are not read.
+// `step` (single launches alone; DESIGN.md 3.11 "A linear term on x, a cone on z"): what stands in the
+// zone's place when it is not kStepZone; the zone's parameters are then not read either.
+//   kStepLinear, the x side alone (chain 2 in the 256-thread shapes, ZeroRowsArgs::tall): a linear
+//     term, var = Cs (Bs v + g_j) with Bs and Cs as for `ridge` and g the n-vector the side carries
+//     (LassoInstance::zg in the pass, ZeroRowsArgs::g in the rows).
+//   kStepNonNeg, the z side alone (the fat rows, chain 3 in the 256-thread shapes): the non-negative
+//     cone, var = Cs (max(Bs v + g, 0) - g) with the side's optional offset g.
+enum ZoneStep { kStepZone, kStepLinear, kStepNonNeg };
 struct ZoneParams {
   DVec alpha_vec, beta_vec;        // optional per-entry alpha / beta
   double Bs = 0, Cs = 0, a1 = 0, lam = 0, alpha = 1, beta = 1, M = 0;
   bool ridge = false;
+  ZoneStep step = kStepZone;
 };
 // One instance of the sweep as the kernels read it (host view: scalars as double, narrowed to
 // the compute type in one place, kernels_fused_chain.h): the multi-block driver's fused state
@@ -91,7 +100,7 @@ struct LassoInstance {
   double kappa = 0;                 // copy = v0 + kappa * (A^T w)
   double pkappa = 0;                // scale of the summed partials in p (see LassoBatchInst)
   // chains 3, 4, 5 alone (n entries each, n the streamed dimension: the samples)
-  DVec zg, zrhs;                    // chain 3, optional
+  DVec zg, zrhs;                    // chain 3, optional; chain 2 with a linear term (zone.step): zg = g
   DVec zd, zfarg;                   // chain 4 writes zd, chain 5 reads zfarg
   double ke = 0, dinv = 0;          // chain 3
 };
@@ -146,7 +155,9 @@ struct ZeroRowsArgs {
   DVec hs, hys, hv;                    // smooth: m each, private to the caller
   // The x side of a tall problem (profile tag "zero_tall_cols"): the m entries are those of x, w is
   // the copy x' as the inverse apply left it (q = w, no product on top), the term is the one on x
-  // and r = v_x' + pkappa sum(tpart) is the next f_x; rhs, g and e are not read.  Scaled zone alone.
+  // and r = v_x' + pkappa sum(tpart) is the next f_x; rhs and e are not read.  A scaled zone, a ridge
+  // term (zone.ridge) or a linear term (zone.step = kStepLinear, `g` its vector of m entries).
+  // Fat (tall unset): zone.step = kStepNonNeg puts the non-negative cone in the zone's place.
   bool tall = false;
   // Free x (with tall; profile tag "zero_tall_free_cols"; DESIGN.md 3.11 "x in the ZERO term alone"):
   // x has no constraint row, so there is no state, no term and no chain.  Per entry j the launch

@@ -64,6 +64,10 @@ constexpr int kBlock = 256;
 // reduction, no barrier.
 // MODE 6: MODE 2 with a ridge term on x (ZoneParams::ridge: the RidgeStep head in place of the
 // threshold); the same arrays, the same tag.
+// MODE 7: MODE 2 with a linear term on x (ZoneParams::step: the LinearStep head); the same arrays, the
+// same tag, and one broadcast load of g_j from `zt.g` per streamed column.  MODE 8: MODE 3 with the
+// non-negative cone on z (the NonNegStep head); the same arrays, the same tag.  Both in the
+// 256-thread shapes alone.
 template <class T, int NR, int BS, int MODE>
 __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
     int64_t m, int64_t n, const T* __restrict__ A, int64_t lda, const T* __restrict__ w,
@@ -121,7 +125,7 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
     if (jn >= 0) load(nxt, jn);
     // per-column state (same address in every lane: broadcast loads)
     T uj = T(0), y0j = T(0), y1j = T(0);
-    if constexpr (MODE <= 3 || MODE == 6) {
+    if constexpr (MODE <= 3 || MODE >= 6) {
       uj = u[j];
       y0j = y0[j];
       y1j = y1[j];
@@ -129,10 +133,11 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
     T u1j = T(0);
     if (MODE == 1) u1j = e0[j];
     T gj = T(0), rj = T(0);
-    if (MODE == 3) {
+    if (MODE == 3 || MODE == 8) {
       if (zt.g != nullptr) gj = zt.g[j];
       if (zt.rhs != nullptr) rj = zt.rhs[j];
     }
+    if constexpr (MODE == 7) gj = zt.g[j];
     T d = T(0);
     if constexpr (MODE != 5) {
 #pragma unroll
@@ -166,9 +171,10 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
         y1[j] = ny1;
         u[j] = nu;
       }
-    } else if (MODE == 2 || MODE == 6) {
+    } else if (MODE == 2 || MODE == 6 || MODE == 7) {
       T ns, nq, nys, nyq, nu;
       if constexpr (MODE == 6) v0n = ZeroChainT<T, RidgeStep>(d, cj, T(0), uj, y1j, y0j, &ns, &nq, &nys, &nyq, &nu);
+      else if constexpr (MODE == 7) v0n = ZeroChainT<T, LinearStep>(d, cj, gj, uj, y1j, y0j, &ns, &nq, &nys, &nyq, &nu);
       else v0n = ZeroChainT<T>(d, cj, T(0), uj, y1j, y0j, &ns, &nq, &nys, &nyq, &nu);
       if (tid == 0) {
         y1prev[j] = y1j;
@@ -179,9 +185,12 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
         y0[j] = nyq;
         u[j] = nu;
       }
-    } else if (MODE == 3) {
+    } else if (MODE == 3 || MODE == 8) {
       T ns, nq, nys, nyq, nu;
-      v0n = ZeroTallChainT<T>(d, cj, zt.ke, zt.dinv, gj, rj, uj, y1j, y0j, &ns, &nq, &nys, &nyq, &nu);
+      if constexpr (MODE == 8)
+        v0n = ZeroTallChainT<T, NonNegStep>(d, cj, zt.ke, zt.dinv, gj, rj, uj, y1j, y0j, &ns, &nq, &nys, &nyq, &nu);
+      else
+        v0n = ZeroTallChainT<T>(d, cj, zt.ke, zt.dinv, gj, rj, uj, y1j, y0j, &ns, &nq, &nys, &nyq, &nu);
       if (tid == 0) {
         y1prev[j] = y1j;
         e0[j] = y0j;
@@ -238,10 +247,16 @@ void LaunchFused(const LassoFusedArgs& a, int grid) {
   if (a.chain == 2) kernel = LassoFusedStreamKernelT<T, NR, BS, 2>;
   if (a.chain == 2 && z.ridge) kernel = LassoFusedStreamKernelT<T, NR, BS, 6>;
   if (a.chain == 3) kernel = LassoFusedStreamKernelT<T, NR, BS, 3>;
-  // the halves of the tall pass exist in the 256-thread shapes alone (ZeroRoute takes no other)
+  // the halves of the tall pass, the linear and the non-negative head exist in the 256-thread shapes
+  // alone (ZeroRoute takes no other)
   if constexpr (BS == 256) {
     if (a.chain == 4) kernel = LassoFusedStreamKernelT<T, NR, BS, 4>;
     if (a.chain == 5) kernel = LassoFusedStreamKernelT<T, NR, BS, 5>;
+    if (a.chain == 2 && z.step == kStepLinear) {
+      kernel = LassoFusedStreamKernelT<T, NR, BS, 7>;
+      zt.g = i.zg;
+    }
+    if (a.chain == 3 && z.step == kStepNonNeg) kernel = LassoFusedStreamKernelT<T, NR, BS, 8>;
   }
   hipLaunchKernelGGL(
       kernel,
@@ -342,7 +357,8 @@ __global__ __launch_bounds__(kBlock) void ZeroTallSamplesBatchKernel(
 // through LDS - a fixed summation order, a function of (m, nparts) alone - and lane 0 runs the
 // row's chain (d = w_i, kappa = -e) and writes r.  A workgroup reads and writes the state of its
 // own rows only.
-// Fn = void, 16 rows: the z term is a scaled zone (ZeroChainT; a threshold on 16 lanes).
+// Fn = void, 16 rows: the z term is a scaled zone (ZeroChainT; a threshold on 16 lanes).  Fn =
+// NonNegStep: the same with the non-negative cone in the zone's place (ZoneParams::step).
 // Fn a smooth function, 64 rows: the lanes pl = 0 are one whole wave, so the fp64 Newton runs on
 // every lane of the only wave that is still alive; consecutive lanes load consecutive rows of a
 // partial vector.  The head of this sweep (s, y_s, v) comes from the previous launch in hs, hys,
@@ -369,7 +385,8 @@ template <class T> struct ZeroRowsInst {
 // TALL (tag "zero_tall_cols"): the x side of a tall problem over the n entries of x.  The same
 // summation of the partials; the chain takes q = x'_j as the inverse apply left it in w
 // (ZeroTallColsChainT) and r_j = f_x = v_x' + pkappa sum: no rhs on this side.  Fn = void: the x term
-// is a scaled zone; Fn = RidgeStep: a ridge term (ZoneParams::ridge).
+// is a scaled zone; Fn = RidgeStep: a ridge term (ZoneParams::ridge); Fn = LinearStep: a linear term
+// (ZoneParams::step), its per-entry constant in I.g.
 // FREE (with TALL, Fn = void; tag "zero_tall_free_cols"): x lives in the ZERO term alone, so the side
 // has no state, no term and no chain.  The same summation of the partials; then lane 0 keeps
 // x_j = w_j of the sweep the pass just used in I.zq (the ZERO term's own variable of this side: here x
@@ -414,8 +431,8 @@ __device__ __forceinline__ void ZeroRowsBody(int64_t m, int nparts, const ZeroRo
   if constexpr (TALL) {
     nq = nyq = I.w[i];
     vn = ZeroTallColsChainT<T, Fn>(nq, ci, gi, I.u[i], yzi, yqi, &ns, &nys, &nu);
-  } else if constexpr (std::is_void<Fn>::value) {
-    vn = ZeroChainT<T>(I.w[i], ci, gi, I.u[i], yzi, yqi, &ns, &nq, &nys, &nyq, &nu);
+  } else if constexpr (std::is_void<Fn>::value || std::is_same<Fn, NonNegStep>::value) {
+    vn = ZeroChainT<T, Fn>(I.w[i], ci, gi, I.u[i], yzi, yqi, &ns, &nq, &nys, &nyq, &nu);
   } else {
     // ZeroChainT from the carried head on: q = kappa d + v, y_q = q, u -= y_q
     ns = I.hs[i];
@@ -579,7 +596,8 @@ void CheckZeroRows(const ZeroRowsArgs& a) {
   EPS_CHECK(a.m >= 1 && a.nparts >= 1 && a.tpart.dt == dt && a.tpart.n >= static_cast<int64_t>(a.nparts) * a.m);
   EPS_CHECK(a.w.n == a.m && a.r.n == a.m && a.r.dt == dt);
   if (a.x_free) {  // x alone in the state's place; no term, so nothing else of the record is read
-    EPS_CHECK_MSG(a.tall && !a.smooth && !a.zone.ridge, "free x is the tall form without a term on x");
+    EPS_CHECK_MSG(a.tall && !a.smooth && !a.zone.ridge && a.zone.step == kStepZone,
+                  "free x is the tall form without a term on x");
     EPS_CHECK(a.xcur.n == a.m && a.xcur.dt == dt);
     return;
   }
@@ -588,6 +606,11 @@ void CheckZeroRows(const ZeroRowsArgs& a) {
     if (v->n > 0) EPS_CHECK(v->n == a.m && v->dt == dt);
   EPS_CHECK_MSG(!(a.tall && a.smooth), "the tall ZERO-term x side has no smooth form");
   EPS_CHECK_MSG(!a.zone.ridge || a.tall, "a ridge term is on the x side: the rows take it in the tall form alone");
+  const ZoneStep step = a.zone.step;
+  EPS_CHECK_MSG(step != kStepLinear || a.tall, "a linear term is on the x side: the rows take it in the tall form alone");
+  EPS_CHECK_MSG(step != kStepLinear || a.g.n == a.m, "a linear term carries its vector g, one value per entry of x");
+  EPS_CHECK_MSG(step != kStepNonNeg || !a.tall, "the non-negative cone is on the z side: the rows take it in the fat form alone");
+  EPS_CHECK_MSG(step == kStepZone || (!a.zone.ridge && !a.smooth), "one head per side: a step, a ridge term or a smooth term");
   if (!a.smooth) return;
   EPS_CHECK_MSG(a.fn == SMOOTH_LOGISTIC, "the fused ZERO-term rows take SUM_LOGISTIC alone, got " << a.fn);
   for (const DVec* v : {&a.hs, &a.hys, &a.hv}) EPS_CHECK(v->n == a.m && v->dt == dt);
@@ -604,9 +627,15 @@ void ZeroFusedRows(const ZeroRowsArgs& a) {
   } else if (a.tall && a.zone.ridge) {
     if (a.w.dt == F32) LaunchZeroRows<float, kZeroRows, RidgeStep, true>(a);
     else LaunchZeroRows<double, kZeroRows, RidgeStep, true>(a);
+  } else if (a.tall && a.zone.step == kStepLinear) {
+    if (a.w.dt == F32) LaunchZeroRows<float, kZeroRows, LinearStep, true>(a);
+    else LaunchZeroRows<double, kZeroRows, LinearStep, true>(a);
   } else if (a.tall) {
     if (a.w.dt == F32) LaunchZeroRows<float, kZeroRows, void, true>(a);
     else LaunchZeroRows<double, kZeroRows, void, true>(a);
+  } else if (a.zone.step == kStepNonNeg) {
+    if (a.w.dt == F32) LaunchZeroRows<float, kZeroRows, NonNegStep, false>(a);
+    else LaunchZeroRows<double, kZeroRows, NonNegStep, false>(a);
   } else if (a.smooth) {
     if (a.w.dt == F32) LaunchZeroRows<float, kZeroSmoothRows, FnLogistic>(a);
     else LaunchZeroRows<double, kZeroSmoothRows, FnLogistic>(a);
@@ -696,6 +725,7 @@ void ZeroRowsBatchUpload(const std::vector<const ZeroRowsArgs*>& members, DVec* 
     EPS_CHECK(a->m == lead.m && a->nparts == lead.nparts && a->smooth == lead.smooth && a->w.dt == lead.w.dt);
     EPS_CHECK(a->tall == lead.tall && a->x_free == lead.x_free);
     EPS_CHECK_MSG(!a->zone.ridge, "the batched rows have no ridge form");
+    EPS_CHECK_MSG(a->zone.step == kStepZone, "the batched rows have no linear and no non-negative form");
   }
   if (lead.w.dt == F32) UploadRowsT<float>(members, table);
   else UploadRowsT<double>(members, table);
@@ -1047,6 +1077,13 @@ void LassoFusedPass(const LassoFusedArgs& a) {
   if (a.chain == 1) EPS_CHECK(a.e1.n == a.n && a.e1.dt == dt);
   EPS_CHECK(a.chain >= 0 && a.chain <= 5);
   EPS_CHECK_MSG(!s.zone.ridge || a.chain == 2, "a ridge term is on the x side: the pass takes it in chain 2 alone");
+  const ZoneStep step = s.zone.step;
+  EPS_CHECK_MSG(step != kStepLinear || a.chain == 2, "a linear term is on the x side: the pass takes it in chain 2 alone");
+  EPS_CHECK_MSG(step != kStepLinear || (s.zg.n == a.n && s.zg.dt == dt),
+                "a linear term carries its vector g, one value per column");
+  EPS_CHECK_MSG(step != kStepNonNeg || a.chain == 3,
+                "the non-negative cone is on the z side: the pass takes it in chain 3 alone");
+  EPS_CHECK_MSG(step == kStepZone || !s.zone.ridge, "one head per side: a step or a ridge term");
   if (a.chain == 4) EPS_CHECK(s.zd.n == a.n && s.zd.dt == dt);
   if (a.chain == 5) EPS_CHECK(s.zfarg.n == a.n && s.zfarg.dt == dt);
   if (a.chain == 3)
@@ -1058,6 +1095,7 @@ void LassoFusedPass(const LassoFusedArgs& a) {
   EPS_CHECK(reinterpret_cast<uintptr_t>(s.w.data()) % 16 == 0 &&
             reinterpret_cast<uintptr_t>(s.tpart.data()) % 16 == 0);
   EPS_CHECK_MSG(a.chain < 4 || block == 256, "the halves of the tall pass take 256-thread shapes alone");
+  EPS_CHECK_MSG(step == kStepZone || block == 256, "the linear and the non-negative head take 256-thread shapes alone");
   static const char* const kTags[] = {"lasso_fused", "lasso_fused", "zero_fused", "zero_tall", "zero_tall_dot",
                                       "zero_tall_acc"};
   ProfScope prof(kTags[a.chain], a.m, a.n);

@@ -401,6 +401,7 @@ void LassoBatchUpload(const std::vector<const LassoInstance*>& members, DType dt
     for (const DVec* v : {&c.y_zero_prev, &s->zg, &s->zrhs, &s->zd, &s->zfarg})
       EPS_CHECK(v->n == 0 || (v->dt == dt && v->n == c.u.n));
     EPS_CHECK_MSG(!s->zone.ridge, "the batched pass has no ridge form");
+    EPS_CHECK_MSG(s->zone.step == kStepZone, "the batched pass has no linear and no non-negative form");
   }
   if (dt == F32) UploadT<float>(members, table);
   else UploadT<double>(members, table);

@@ -177,7 +177,14 @@ __device__ inline T ChainOneT(T d, const FusedScalarsT<T>& c, T u, T y0p, T y1p,
 // RidgeStep in the Fn slot (the x side alone): the term is a scalar least-squares prox
 // (ScalarLeastSquaresDesc, ZoneParams::ridge) and its variable the block solve's two scalar-map
 // applies on the prox input, s = Cs (Bs ub): no offset, no zone, one rounding per multiply.
+// LinearStep in the Fn slot (the x side alone): the term is linear (SeparableDesc::kLinear,
+// ZoneParams::step) and its variable the block solve's forward step on the row that holds the
+// constant and the pivot, s = Cs (Bs ub + g): `g` is the per-element constant -alpha c_j, passed where
+// the offset goes.  NonNegStep (the z side alone): the non-negative cone in the zone's place,
+// max(vin, 0) as MaxZeroKernel computes it (kernels_prox.hip), with the zone's offset handling.
 struct RidgeStep {};
+struct LinearStep {};
+struct NonNegStep {};
 template <class T> struct ZeroHeadT {
   T s, ys, v;  // the separable term's variable and y; the ZERO prox's input on this row
 };
@@ -188,10 +195,14 @@ __device__ inline ZeroHeadT<T> ZeroHeadOfT(const FusedScalarsT<T>& c, T g, T u, 
   if constexpr (std::is_same<Fn, RidgeStep>::value) {
     const T t = c.Bs * ub;               // forward substitution: -L(var, constraint) v   (block.cc Substitute)
     s = c.Cs * t;                        // the pivot: Dinv(var) t
+  } else if constexpr (std::is_same<Fn, LinearStep>::value) {
+    const T t = c.Bs * ub + g;           // forward substitution onto the row of g_: -L(var, constraint) v + g_j
+    s = c.Cs * t;                        // the pivot: Dinv(var) t
   } else {
     const T vin = c.Bs * ub + g;         // VectorProx: B v + g            (vector_prox.cc:141)
     T xz;
     if constexpr (std::is_void<Fn>::value) xz = ScaledZoneOneT<T>(vin, c.lam, c.alpha, c.beta, c.M);
+    else if constexpr (std::is_same<Fn, NonNegStep>::value) xz = vin > T(0) ? vin : T(0);  // non_negative.cc:8
     else xz = static_cast<T>(ProxElem<Fn>(static_cast<double>(vin), lam64));
     s = c.Cs * (xz - g);                 // C (x - g)                      (vector_prox.cc:145)
   }
@@ -234,10 +245,10 @@ template <class T> struct ZeroTallScalarsT {
 template <class T> __device__ inline T ZeroTallForwardT(T v, T rhs, T ke) { return ke * v + rhs; }
 // Finishes the sample's sweep from the product `d`, writes the boundary state and returns the
 // NEXT sweep's f_arg, computed in registers from that state.
-template <class T>
+template <class T, class Fn = void>
 __device__ inline T ZeroTallChainT(T d, const FusedScalarsT<T>& c, T ke, T dinv, T g, T rhs, T u, T ysp, T yqp,
                                    T* so, T* qo, T* yso, T* yqo, T* uo) {
-  const ZeroHeadT<T> h = ZeroHeadOfT<T>(c, g, u, ysp, yqp);
+  const ZeroHeadT<T> h = ZeroHeadOfT<T, Fn>(c, g, u, ysp, yqp);
   const T farg = ZeroTallForwardT<T>(h.v, rhs, ke);
   const T garg = dinv * farg;
   const T arg = c.kappa * d + garg;
@@ -248,7 +259,7 @@ __device__ inline T ZeroTallChainT(T d, const FusedScalarsT<T>& c, T ke, T dinv,
   *yso = h.ys;
   *yqo = q;
   *uo = un;
-  return ZeroTallForwardT<T>(ZeroHeadOfT<T>(c, g, un, h.ys, q).v, rhs, ke);
+  return ZeroTallForwardT<T>(ZeroHeadOfT<T, Fn>(c, g, un, h.ys, q).v, rhs, ke);
 }
 // The x side of the same sweep: x'_j comes from the apply of Dinv(x') as it is (q = x'_j, no
 // product on top), y_q = q, u = v - q; returns the NEXT sweep's v_x.

@@ -36,6 +36,7 @@ const struct Option {
     {kFusedWhiten, "EPSILON_HIP_FUSED_WHITEN"},
     {kFusedZero, "EPSILON_HIP_FUSED_ZERO", "fused_zero", {"0", "auto"}, "auto"},
     {kFusedZeroCheck, "EPSILON_HIP_FUSED_ZERO_CHECK", "fused_zero_check", {"0", "1"}, "0"},
+    {kFusedZeroLp, "EPSILON_HIP_FUSED_ZERO_LP", "fused_zero_lp", {"0", "1"}, "0"},
     {kFusedZeroRidge, "EPSILON_HIP_FUSED_ZERO_RIDGE", "fused_zero_ridge", {"0", "1", "auto"}, "auto"},
     {kFusedZeroTall, "EPSILON_HIP_FUSED_ZERO_TALL", "fused_zero_tall", {"0", "1", "auto"}, "auto"},
     {kFusedZeroTallSmooth, "EPSILON_HIP_FUSED_ZERO_TALL_SMOOTH", "fused_zero_tall_smooth", {"0", "1", "auto"}, "auto"},

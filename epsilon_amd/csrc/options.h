@@ -29,6 +29,7 @@ enum Id {
   kFusedWhiten,
   kFusedZero,
   kFusedZeroCheck,
+  kFusedZeroLp,
   kFusedZeroRidge,
   kFusedZeroTall,
   kFusedZeroTallSmooth,

@@ -467,6 +467,15 @@ class NonNegativeProx final : public VectorProx {
     k::MaxZero(x, v);
     output->set_value(0, x);
   }
+
+ public:
+  // The cone, with the offset of its argument when there is one (d->g), under ScaledZoneProx's
+  // conditions: scalar maps, one weight (which the projection does not read).
+  bool DescribeSeparable(SeparableDesc* d) const override {
+    if (!ScalarForm(d, /*offset=*/true)) return false;
+    d->kind = SeparableDesc::kNonNegative;
+    return true;
+  }
 };
 REGISTER_PROX_OPERATOR(NON_NEGATIVE, NonNegativeProx);
 
@@ -864,27 +873,65 @@ class AffineProx final : public ProxOperator {
     const BlockVector& b = arg.affine_constraint().b;
     const double alpha = arg.prox_function().alpha;
     BlockVector c;
+    one_dense_row_ = false;
     if (arg.prox_function().prox_function_type == pb::ProxFunction::AFFINE) {
       // GetLinear (affine.cc:8-17): the 1 x n maps of H as vectors
       const DType dt = arg.data_map()->dtype();
+      int maps = 0, dense = 0;
       for (const auto& col : arg.affine_arg().A.data()) {
         for (const auto& row : col.second) {
           EPS_CHECK_MSG(row.second.impl().m() == 1, "AFFINE prox expects 1 x n argument maps");
           auto D = ToDense(row.second.impl(), dt);
           c.Set(col.first, D->Materialize(false));  // 1 x n contiguous == the transposed row
+          ++maps;
+          if (row.second.impl().type() == DENSE_MATRIX) ++dense;
         }
       }
       c = alpha * c;
+      one_dense_row_ = maps == 1 && dense == 1;
     }
     BlockMatrix M = A + A.Transpose() - A.LeftIdentity();
     chol_.Compute(M);
     g_ = (-1.0) * b - c;
+    var_keys_ = arg.affine_arg().A.col_keys();
+    constant_ = !b.data().empty();
   }
   BlockVector Apply(const BlockVector& v) override { return chol_.Solve(g_ + v); }
+
+  // A linear term ("A linear term on x, a cone on z"; SeparableDesc::kLinear): AFFINE
+  // with one dense 1 x n argument map on one variable, one constraint row with a scalar map and no
+  // constant.  The order is [constraint, var] - var has no diagonal block before the constraint is
+  // eliminated, so the fill model can give no other - with L(var, constraint) and the two pivots the
+  // only blocks, all scalar matrices; the forward substitution adds -L(var, constraint) v_c to the var
+  // row of g_ and Solve(g_ + v)[var] = Dinv(var) (-L(var, constraint) v_c + g_var).  Anything else
+  // keeps the generic path.
+  // Bs and Cs are the two factors as the scalar maps' Apply forms them: alpha * scalar.
+  bool DescribeSeparable(SeparableDesc* d) const override {
+    const Factored f{chol_, g_};
+    const std::vector<Key>& p = chol_.order();
+    if (!f.Exact() || !one_dense_row_ || constant_ || var_keys_.size() != 1 || p.size() != 2) return false;
+    const Key &ck = p[0], &vk = p[1];
+    if (vk != *var_keys_.begin() || ck == vk || !f.ConstantOn(vk) || !g_.has_key(vk)) return false;
+    // three scalar blocks and no other
+    double l_var_con = 0, dinv_var = 0;  // the scalars as the factorisation holds them
+    if (Blocks(f.L()) + Blocks(f.Di()) != 3) return false;
+    if (!ScalarAt(f.L(), vk, ck, &l_var_con)) return false;
+    if (!ScalarAt(f.Di(), ck, ck) || !ScalarAt(f.Di(), vk, vk, &dinv_var)) return false;
+    d->kind = SeparableDesc::kLinear;
+    d->var_key = vk;
+    d->constraint_key = ck;
+    d->Bs = -1.0 * l_var_con;
+    d->Cs = 1.0 * dinv_var;
+    d->g = g_(vk);
+    return true;
+  }
 
  private:
   BlockCholesky chol_;
   BlockVector g_;
+  std::set<std::string> var_keys_;
+  bool one_dense_row_ = false;  // AFFINE with one argument map, a dense 1 x n matrix
+  bool constant_ = false;       // the constraint rows carry a constant
 };
 REGISTER_PROX_OPERATOR(AFFINE, AffineProx);
 REGISTER_PROX_OPERATOR(CONSTANT, AffineProx);

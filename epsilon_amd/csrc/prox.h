@@ -64,6 +64,8 @@ struct SeparableDesc {
     kSmooth,     // SmoothProxOp (SUM_LOGISTIC alone answers): f = prox_{lam fn}
     kRowGroups,  // Norm2Prox with axis = 1 on a rows x cols argument: f the group shrinkage of each row
     kRidge,      // SumSquareProx with a scalar argument map: f the identity, x = Cs * (Bs*v) (below)
+    kLinear,     // AffineProx with one dense 1 x n argument map: f the identity, x = Cs * (Bs*v + g) (below)
+    kNonNegative,  // NonNegativeProx: f = max(., 0) as k::MaxZero computes it
   };
   Kind kind = kZone;
   std::string var_key, constraint_key;
@@ -71,7 +73,8 @@ struct SeparableDesc {
   double lam = 0;         // (kRidge: not set, the weight is in Bs and Cs)
   double alpha = 1, beta = 1, M = 0;       // kZone
   DVec alpha_vec, beta_vec;                // kZone: per-element alpha / beta (SUM_QUANTILE with data vectors); empty: uniform
-  DVec g;                                  // kZone, kSmooth: constant offset of the argument (empty: none)
+  DVec g;                                  // kZone, kSmooth, kNonNegative: constant offset of the argument (empty: none)
+                                           // kLinear: the var row of the solve's constant, -alpha c (n entries)
   k::SmoothFn fn = k::SMOOTH_LOGISTIC;     // kSmooth
   int64_t rows = 0, cols = 0;              // kRowGroups
 };
@@ -83,6 +86,17 @@ struct SeparableDesc {
 // (block.cc Substitute, then D_inv *): each factor the product a scalar map's Apply narrows to the
 // compute type, one rounding per multiply; Bs and Cs are these two factors, the scalars as the
 // factorisation holds them.  In exact arithmetic x = a v / (a^2 + 2 alpha).
+// kLinear: AffineProx of an AFFINE function c^T x with one dense 1 x n argument map on one variable
+// and one constraint row with a scalar map a and no constant.  The KKT matrix [[0, a], [a, -I]] has no
+// diagonal block on var, so the fill model (BlockCholesky: a key without a pivot has no bound) can
+// only give the order [constraint, var], both blocks of the factorisation and both pivots scalar
+// matrices.  The right-hand side is g_ + v with g_ = -alpha c on the var row and v on the constraint
+// row, so Solve(g_ + v)[var] is
+//   t = (-1 * L(var, constraint)) v_c + g_j ;  x = (1 * Dinv(var)) t
+// (block.cc Substitute: the scalar map's Apply adds its product to the row that holds g, then D_inv *;
+// the back substitution writes the constraint row, which no constraint map reads): one rounding per
+// multiply and per add.  Bs and Cs are these two factors, the scalars as the factorisation holds them,
+// g the var row of g_ in the compute type.  In exact arithmetic x = (a v - alpha c) / a^2.
 
 // ZeroProx after block elimination: the projection onto {C x' + e z' + d = 0} of the graph-form
 // problems, in one of two orders; v is the prox input.

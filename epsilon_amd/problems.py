@@ -661,6 +661,28 @@ def lp(m, n, seed=0):
     return _graph_form(terms, -A, b, z_key="var:s"), dict(A=A, b=b, c=c)
 
 
+def lp_objective(c, x):
+    return float(np.dot(c, x))
+
+
+def polyhedron(m, n, norm="l1", lam=1.0, seed=0):
+    """The smallest point of the polyhedron of lp(m, n, seed), min ||x||_1 (`norm` = "l1": the sparsest
+    point) or min lam ||x||_2^2 ("l2": the least-norm point)  s.t.  A x <= b:  norm_1(x) or
+    sum_square(x)[lam] + non_negative(s) with s = b - A x, on lp's own A and b."""
+    info = lp(m, n, seed)[1]
+    A, b = info["A"], info["b"]
+    assert norm in ("l1", "l2"), norm
+
+    def terms(x, s):
+        fx = ir.prox(ProxFunction.NORM_1, x) if norm == "l1" else _ridge(x, lam)
+        return [fx, ir.prox(ProxFunction.NON_NEGATIVE, s)]
+    return _graph_form(terms, -A, b, z_key="var:s"), dict(A=A, b=b, lam=lam, norm=norm)
+
+
+def polyhedron_objective(norm, lam, x):
+    return float(np.abs(x).sum()) if norm == "l1" else float(lam * np.sum(x ** 2))
+
+
 # ---- the reference's solver-level known answers (python/epopt/constant_atoms_test.py) ------------
 
 def constant_atom(prox_name, arg_columns, k=None, alpha=None, beta=None, arg_scale=None, linear=None, axis=None):

@@ -151,6 +151,19 @@ const char* eps_version(void);
  * eps_solve; without it each is solved by itself on the route.  It touches nothing but these
  * problems.  Read at every Init.  Any other value is an error that names it (env
  * EPSILON_HIP_FUSED_ZERO_XFREE).
+ * "fused_zero_lp" = "0" (default, and what unset means) | "1"  the same graph forms with a linear
+ * term c^T x on x (AFFINE with one dense 1 x n argument map) or the non-negative cone on z
+ * (NON_NEGATIVE, its offset with it) in a threshold's place: linear programs min c^T x s.t. A x <= b,
+ * and every mix of the two with the l1, ridge, zone and logistic terms of the options above (the
+ * sparsest or least-norm point of a polyhedron; a linear cost with a hinge loss).  On the same
+ * routes, fat and tall, with the same launches: the linear term is the two steps of its scalar block
+ * solve, x = Dinv (-L v + g) with g = -alpha c, the cone max(., 0).  "1": wherever those routes take
+ * the shape in their 256-thread forms; "0": never.  Free x with the cone, the two-block driver and
+ * sharded solves keep the generic path; the options of the routes switch it off with them (a ridge
+ * term beside the cone needs "fused_zero_ridge").  Single solves on the multi-block driver; in
+ * eps_solve_batch such an instance is solved by itself.  It touches nothing but problems with one of
+ * the two terms.  Read at every Init.  Any other value is an error that names it (env
+ * EPSILON_HIP_FUSED_ZERO_LP).
  * "fused_zero_check" = "0" (default, and what unset means) | "1"  the residual check of the fused
  * ZERO-term routes above (fat and tall; zone, logistic and ridge terms; free x).  "0": the driver's
  * generic check on views of the route's state - some thirty small vector launches and a fetch the
