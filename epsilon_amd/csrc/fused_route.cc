@@ -20,10 +20,24 @@ namespace {
 // What the routes share
 // ---------------------------------------------------------------------------------------------------
 
+// What stands in the threshold's place for a term of this kind.  Row groups keep the zone head: their
+// threshold goes through the pass's group_lam.
+k::Head HeadOf(SeparableDesc::Kind kind) {
+  switch (kind) {
+    case SeparableDesc::kZone:
+    case SeparableDesc::kRowGroups: return k::kHeadZone;
+    case SeparableDesc::kRidge: return k::kHeadRidge;
+    case SeparableDesc::kLinear: return k::kHeadLinear;
+    case SeparableDesc::kNonNegative: return k::kHeadNonNeg;
+    case SeparableDesc::kSmooth: return k::kHeadSmooth;
+  }
+  return k::kHeadZone;
+}
+
 // The zone of a kernel record from the operator's description; a1: the scalar of the term's
-// variable in its consensus constraint.  A ridge term takes the record with Bs, Cs the two factors of
-// its block solve; smooth terms and row groups read the scalar form alone (the zone's parameters are
-// the defaults).  A linear term and the non-negative cone take it with their step in the zone's place.
+// variable in its consensus constraint.  A ridge and a linear term take the record with Bs, Cs the
+// two factors of their block solve; smooth terms and row groups read the scalar form alone (the
+// zone's parameters are the defaults).
 k::ZoneParams ZoneOf(const SeparableDesc& z, double a1) {
   k::ZoneParams s;
   s.alpha_vec = z.alpha_vec;
@@ -35,9 +49,7 @@ k::ZoneParams ZoneOf(const SeparableDesc& z, double a1) {
   s.alpha = z.alpha;
   s.beta = z.beta;
   s.M = z.M;
-  s.ridge = z.kind == SeparableDesc::kRidge;
-  if (z.kind == SeparableDesc::kLinear) s.step = k::kStepLinear;
-  if (z.kind == SeparableDesc::kNonNegative) s.step = k::kStepNonNeg;
+  s.head = HeadOf(z.kind);
   return s;
 }
 
@@ -228,7 +240,7 @@ constexpr int64_t kLassoTallMinCols = 256;
 // kZeroTallAutoMinCols; DESIGN.md 4: 5.0 x at n = 256, the first cell, and no cell above it below
 // 4.7 x); 0 would mean that no cell got there and "auto" is "0".
 constexpr int64_t kLassoTallAutoMinCols = 256;
-// The first word of a tall lasso member's batch key (the others begin with the pass's chain, 0 to 5).
+// The first word of a tall lasso member's batch key (the others begin with the pass's k::Chain).
 constexpr uint64_t kTallLassoKey = 0x7a111a550;
 
 // The bits of a scalar, as a word of a batch key.
@@ -329,7 +341,7 @@ struct BatchRoute : FusedRoute {
   // partials go through the reduction.
   virtual const k::ZeroRowsArgs* Rows() const { return nullptr; }
   // The record of the sample kernel (a tall ZERO-term member with a smooth z term): the pass then
-  // runs in two halves, `pass.chain` and chain 5, around it.
+  // runs in two halves, `pass.chain` and k::kChainZeroTallAcc, around it.
   virtual const k::ZeroTallSamplesArgs* Samples() const { return nullptr; }
   // The resident share of a sweep of `count` members on this route's matrix.
   virtual k::FusedResidency Residency(int64_t count) const { return res; }
@@ -348,9 +360,9 @@ struct BatchRoute : FusedRoute {
 
   // One sweep of the `count` members of `table` (k::LassoBatchUpload) on this route's matrix, in
   // the pass's own dimensions pm x pn (pm: the register-held one, the order of the dense pivot): the
-  // batched pass per `width` members - with a sample kernel (Samples()): the dot pass per width(4)
-  // members, one sample launch on `sample_table` (k::ZeroTallSamplesBatchUpload), the accumulate
-  // pass per width(5) members; the row kernel on `row_table` (k::ZeroRowsBatchUpload) for ZERO-term
+  // batched pass per `width` members - with a sample kernel (Samples()): the dot pass per its width
+  // of members, one sample launch on `sample_table` (k::ZeroTallSamplesBatchUpload), the accumulate
+  // pass per its own; the row kernel on `row_table` (k::ZeroRowsBatchUpload) for ZERO-term
   // members with a z block, else the batched reduction of the partials; then - unless whitened: the
   // reduction wrote every member's w_hat - one batched apply of the packed inverse (`work`:
   // count * k::SymvWorkspace(pm)), or `own_applies` without a packed copy (D.Apply / Symv: per
@@ -360,7 +372,7 @@ struct BatchRoute : FusedRoute {
                   const double* group_lam, const k::FusedResidency& share, bool rhs_aligned, const DVec& work,
                   Applies own_applies) const {
     const int64_t pm = pass.m, pn = pass.n;
-    auto passes = [&](int chain) {
+    auto passes = [&](k::Chain chain) {
       const int width = k::LassoBatchWidth(pm, pn, dt, chain);
       for (int first = 0; first < count; first += width)
         k::LassoBatchPass(pm, pn, pass.lda, pass.A, table, first, std::min(width, count - first), group_lam, share,
@@ -369,10 +381,10 @@ struct BatchRoute : FusedRoute {
     passes(pass.chain);
     if (Samples() != nullptr) {
       k::ZeroTallSamplesBatch(pn, dt, sample_table, count);
-      passes(5);
+      passes(k::kChainZeroTallAcc);
     }
     if (Rows() != nullptr)
-      k::ZeroFusedRowsBatch(pm, grid, Rows()->smooth, dt, row_table, count, Rows()->tall, Rows()->x_free);
+      k::ZeroFusedRowsBatch(pm, grid, Rows()->side, Rows()->zone.head, dt, row_table, count);
     else k::ReducePartialsBatch(pm, grid, table, count, dt, rhs_aligned);
     if (whiten) return;
     if (inv.packed.n > 0) k::SymvPackedBatch(pm, inv.D->scale(), inv.packed, table, count, work);
@@ -887,7 +899,7 @@ struct LassoRoute final : BatchRoute {
 // other terms are one scaled-zone term on x and at most one on z (which may carry an offset, and
 // may be SUM_LOGISTIC, a smooth separable term, instead of a scaled zone),
 // each tied to its copy by a consensus constraint copy + a var = 0 without a constant.  The
-// sweep is then: the pass over the data matrix (chain 2: back product, column chain, forward
+// sweep is then: the pass over the data matrix (k::kChainZeroCols: back product, column chain, forward
 // product), the row kernel (row chain, the partials' sum, r) - basis pursuit: the partials'
 // reduction alone - and the apply of the cached inverse.  The residual check is the driver's
 // generic one on views of the state, or - option "fused_zero_check" = "1" - one launch of the route's
@@ -897,11 +909,11 @@ struct LassoRoute final : BatchRoute {
 // LDL^T in the tall order: arg is a scalar pivot, x' the dense one.
 // Everything between C x' of sweep k and C^T f_arg of sweep k+1 is element-wise in the sample, so
 // the pass streams C^T (features x samples, one contiguous copy made at Init): per sample the
-// product with x', the z-side chain and the forward product (chain 3); then the x-side kernel (the
+// product with x', the z-side chain and the forward product (k::kChainZeroTall); then the x-side kernel (the
 // partials' sum, the chain on x, f_x) and the apply of Dinv(x').  A smooth z term (`samples_smooth`:
 // SUM_LOGISTIC, under the option "fused_zero_tall_smooth") has its Newton in a kernel of its own over
-// the samples, between the two halves of the pass: the dot products C x' (chain 4), the sample kernel
-// with the carried head, the forward product (chain 5).  Under the option "batch_zero_tall" the tall
+// the samples, between the two halves of the pass: the dot products C x' (k::kChainZeroTallDot), the sample kernel
+// with the carried head, the forward product (k::kChainZeroTallAcc).  Under the option "batch_zero_tall" the tall
 // members of a batch that share C run as one group ("Tall members"); without it each is
 // solved by itself.
 //
@@ -922,7 +934,7 @@ struct LassoRoute final : BatchRoute {
 // Free x (`zp.x_free`, option "fused_zero_xfree" = "1"; DESIGN.md 3.11 "x in the ZERO term alone"): no
 // term on x, so x is no copy - it lives in the ZERO term alone and has no constraint row
 // (least_abs_dev, quantile).  The tall form with one constraint and one separable term, a zone on z:
-// the pass with chain 3 as it is, an x side that is the partials' sum alone (rows.x_free: x kept in
+// the pass with k::kChainZeroTall as it is, an x side that is the partials' sum alone (k::kRowsXFree: x kept in
 // `xcur`, f_x = pkappa sum, no state and no chain) and the apply of Dinv(x) = (C^T C / e^2)^-1, which
 // exists for m > n alone - asked for here, since the factorisation has the same order for fat C.
 // Under "batch_zero_tall" such members that share C form groups of their own.
@@ -1008,13 +1020,17 @@ struct ZeroRoute final : BatchRoute {
       }
     }
     if ((!xfree && ix < 0) || (has_z && iz < 0)) return false;
-    const bool x_ridge = !xfree && sx.kind == SeparableDesc::kRidge;
-    const bool x_linear = !xfree && sx.kind == SeparableDesc::kLinear;
-    const bool lp_head = x_linear || (has_z && sz.kind == SeparableDesc::kNonNegative);
+    // the two sides' heads (a side without a term - free x, no z - has the default, the zone)
+    const k::Head hx = HeadOf(sx.kind), hz = HeadOf(sz.kind);
+    const bool x_ridge = hx == k::kHeadRidge;
+    const bool lp_head = hx == k::kHeadLinear || hz == k::kHeadNonNeg;
     // (the smooth form belongs to the z side: tall, that is the sample kernel, not the rows)
-    samples_smooth = tall && sz.kind == SeparableDesc::kSmooth;
-    rows.smooth = !tall && sz.kind == SeparableDesc::kSmooth;
+    samples_smooth = tall && hz == k::kHeadSmooth;
     (tall ? samples.fn : rows.fn) = sz.fn;
+    // the pass as FillTall / FillFat set it up: the z side over the transposed copy (in halves
+    // around the sample kernel, which then has the head), or the x side
+    const k::Chain chain = !tall ? k::kChainZeroCols : samples_smooth ? k::kChainZeroTallDot : k::kChainZeroTall;
+    const k::Head pass_head = !tall ? hx : samples_smooth ? k::kHeadZone : hz;
     const DenseMatrixImpl& L = *zp.L;  // (tall: trans() set: its buffer is C, m x n)
     const DenseMatrixImpl& D = *zp.Dinv;
     dt = a.data->dtype();
@@ -1027,20 +1043,17 @@ struct ZeroRoute final : BatchRoute {
       // the pass's shape conditions, on the copy's geometry, before the copy is made
       const int64_t chunk = dt == F32 ? 4 : 2;
       if (n % chunk != 0 || n > (dt == F32 ? 20 : 10) * 1024) return false;
-      if (samples_smooth) {
-        if (!Allowed(tall_smooth_mode, n, kZeroTallSmoothAutoMinCols)) return false;
-        // the halves of the pass exist in the 256-thread shapes alone
-        if (k::LassoFusedBlock(n, m, dt) != 256) return false;
-      }
+      if (samples_smooth && !Allowed(tall_smooth_mode, n, kZeroTallSmoothAutoMinCols)) return false;
       const int64_t ridge_floor = samples_smooth ? kZeroRidgeTallSmoothAutoMinCols : kZeroRidgeTallAutoMinCols;
       if (x_ridge && !Allowed(ridge_mode, n, ridge_floor)) return false;
-      // the linear and the non-negative head exist in the 256-thread shapes alone
-      if (lp_head && k::LassoFusedBlock(n, m, dt) != 256) return false;
     } else {
       if (m < kZeroFusedMinRows || !k::LassoFusedSupported(m, n, L.data(), L.rows())) return false;
       if (x_ridge && !Allowed(ridge_mode, m, kZeroRidgeAutoMinRows)) return false;
-      if (lp_head && k::LassoFusedBlock(m, n, dt) != 256) return false;
     }
+    // the pass's form exists in this thread shape (the halves, the linear and the non-negative head:
+    // 256 threads alone); "fused_zero_lp" takes the 256-thread shapes alone on whichever side its head is
+    const int block = tall ? k::LassoFusedBlock(n, m, dt) : k::LassoFusedBlock(m, n, dt);
+    if (!k::FusedPassExists(chain, pass_head, block) || (lp_head && block != 256)) return false;
     // the consensus constraints: copy + a var = 0, nothing else in their rows or columns
     // (free x: the one tie is all there is, so no column of A is x's)
     if (static_cast<int>(a.A.data().size()) != 2 * nc || (xfree && a.A.data().count(zp.x_key) != 0)) return false;
@@ -1053,12 +1066,12 @@ struct ZeroRoute final : BatchRoute {
     if (has_z && !tie(zp.z_constraint_key, zp.z_key, sz.var_key, m, &az)) return false;
     if (!Fits(zp.rhs_arg, m, dt) || !Fits(sx.alpha_vec, n, dt) || !Fits(sx.beta_vec, n, dt)) return false;
     if (!Fits(sz.alpha_vec, m, dt) || !Fits(sz.beta_vec, m, dt) || !Fits(sz.g, m, dt)) return false;
-    if (x_linear ? (sx.g.n != n || sx.g.dt != dt) : sx.g.n != 0) return false;  // the linear term's vector, and no other
+    if (hx == k::kHeadLinear ? (sx.g.n != n || sx.g.dt != dt) : sx.g.n != 0) return false;  // the linear term's vector, and no other
     if (tall && !TransposedCopy(a.shared_cache)) return false;
     own_check = check_on;
     if (own_check) {
       auto pad = [](int64_t len) { return (len + 63) / 64 * 64; };
-      const bool smooth = sz.kind == SeparableDesc::kSmooth;
+      const bool smooth = hz == k::kHeadSmooth;
       const int64_t sides = (xfree ? pad(n) : 7 * pad(n)) + (has_z ? 7 * pad(m) : 0);
       carried = DVec::Zeros(pad(nw) + sides + (smooth ? pad(3 * m) : 0), dt);
       snapshot = DVec::Empty(carried.n, dt);
@@ -1116,10 +1129,11 @@ struct ZeroRoute final : BatchRoute {
                         /*auto_on=*/false, &pass);
     if (samples_smooth) {  // the share holds for both halves: the matrix is read twice per sweep
       acc = pass;
-      acc.chain = 5;
+      acc.chain = k::kChainZeroTallAcc;
     }
+    EPS_CHECK(pass.chain == chain && pass.inst.zone.head == pass_head);
     AdoptState(views, Homes(a));
-    if (rows.smooth) k::ZeroSmoothHead(rows);
+    if (rows.zone.head == k::kHeadSmooth) k::ZeroSmoothHead(rows);
     if (samples_smooth) k::ZeroTallSamplesHead(samples);
     ForwardFromState(a);
     return true;
@@ -1144,9 +1158,9 @@ struct ZeroRoute final : BatchRoute {
     return k::LassoFusedSupported(n, m, CT, n);
   }
 
-  // The pass's instance from the side it runs (chains 2 and 3 read the arrays alike,
-  // k::LassoFusedArgs), the row kernel's record from the other side.
-  void PassSide(int chain, const Side& s, const SeparableDesc& zone, double a1) {
+  // The pass's instance from the side it runs (the two ZERO chains read the arrays alike, k::Chain),
+  // the row kernel's record from the other side.
+  void PassSide(k::Chain chain, const Side& s, const SeparableDesc& zone, double a1) {
     pass.chain = chain;
     k::LassoInstance& i = pass.inst;
     i.w = w;
@@ -1167,21 +1181,21 @@ struct ZeroRoute final : BatchRoute {
     rows.pkappa = -zp.L->scale();
   }
 
-  // Fat: the x side into the pass (chain 2), the z side into the rows.
+  // Fat: the x side into the pass (k::kChainZeroCols), the z side into the rows.
   void FillFat(const Side& sn, double ax, const Side& sm, double az) {
     pass.m = m;
     pass.n = n;
     pass.lda = zp.L->rows();
     pass.A = zp.L->data();
-    PassSide(2, sn, sx, ax);
+    PassSide(k::kChainZeroCols, sn, sx, ax);
     pass.inst.rhs = zp.rhs_arg;
-    if (sx.kind == SeparableDesc::kLinear) pass.inst.zg = sx.g;  // one value per streamed column
+    if (pass.inst.zone.head == k::kHeadLinear) pass.inst.zg = sx.g;  // one value per streamed column
     if (!has_z) return;
     RowsSide(sm, sz, az);
     rows.rhs = zp.rhs_arg;
     rows.g = sz.g;
     rows.e = zp.e;
-    if (rows.smooth) {
+    if (rows.zone.head == k::kHeadSmooth) {
       head = Carried(3 * m);
       rows.hs = head.Slice(0, m);
       rows.hys = head.Slice(m, m);
@@ -1189,29 +1203,30 @@ struct ZeroRoute final : BatchRoute {
     }
   }
 
-  // Tall: the z side into the pass (chain 3) over the transposed copy, the x side into the rows.
+  // Tall: the z side into the pass (k::kChainZeroTall) over the transposed copy, the x side into the rows.
   void FillTall(const Side& sn, double ax, const Side& sm, double az) {
     pass.m = n;
     pass.n = m;
     pass.lda = n;
     pass.A = CT;
-    PassSide(3, sm, sz, az);
+    PassSide(k::kChainZeroTall, sm, sz, az);
     k::LassoInstance& i = pass.inst;
     i.zg = sz.g;
     i.zrhs = zp.rhs_arg;
     i.ke = -zp.e;
     i.dinv = zp.dinv_arg;
     RowsSide(sn, sx, ax);
-    rows.tall = true;
-    if (sx.kind == SeparableDesc::kLinear) rows.g = sx.g;
+    rows.side = k::kRowsX;
+    if (rows.zone.head == k::kHeadLinear) rows.g = sx.g;
     if (zp.x_free) {  // no state and no term on this side: x alone (RowsSide's are empty defaults)
-      rows.x_free = true;
+      rows.side = k::kRowsXFree;
       rows.xcur = xcur;
     }
     if (!samples_smooth) return;
-    // the pass in two halves (chains 4 and 5) around the sample kernel, which takes the z side's
-    // state, zone, offset, rhs and pivots from the pass's record
-    pass.chain = 4;
+    // the pass in two halves (the dot pass here, the accumulate pass in `acc`) around the sample kernel,
+    // which takes the z side's state, zone with its head, offset, rhs and pivots from the pass's
+    // record; the halves themselves run no head
+    pass.chain = k::kChainZeroTallDot;
     head = Carried(3 * m);
     dfarg = DVec::Zeros(2 * m, dt);
     i.zd = dfarg.Slice(0, m);
@@ -1224,6 +1239,7 @@ struct ZeroRoute final : BatchRoute {
     t.g = i.zg;
     t.state = i.state;
     t.zone = i.zone;
+    i.zone.head = k::kHeadZone;
     t.hs = head.Slice(0, m);
     t.hys = head.Slice(m, m);
     t.hv = head.Slice(2 * m, m);
@@ -1332,17 +1348,14 @@ struct ZeroRoute final : BatchRoute {
   // a scaled-zone group), the scalar pivot, and whether x is free (such a member has another x-side
   // launch: it never joins a hinge or deadzone group).
   bool BatchKey(const pb::SolverParams& params, bool tall_groups, std::vector<uint64_t>* key) const override {
-    // the batched kernels have no ridge, linear or non-negative head: such a member is solved by itself
-    if (sx.kind == SeparableDesc::kRidge || sx.kind == SeparableDesc::kLinear) return false;
-    if (has_z && sz.kind == SeparableDesc::kNonNegative) return false;
-    if (tall) {
-      if (!tall_groups || !has_z || k::LassoBatchWidth(pass.m, pass.n, dt, pass.chain) == 0) return false;
-      if (samples_smooth && k::LassoBatchWidth(pass.m, pass.n, dt, acc.chain) == 0) return false;
-    } else if (k::LassoBatchWidth(m, n, dt, 2) == 0) {
-      return false;
-    }
+    // a head without a batched form (ridge, linear, the cone): such a member is solved by itself
+    if (!k::BatchPassExists(pass.chain, pass.inst.zone.head)) return false;
+    if (Rows() != nullptr && !k::BatchRowsExist(rows.side, rows.zone.head)) return false;
+    if (tall && (!tall_groups || !has_z)) return false;
+    if (k::LassoBatchWidth(pass.m, pass.n, dt, pass.chain) == 0) return false;
+    if (samples_smooth && k::LassoBatchWidth(pass.m, pass.n, dt, acc.chain) == 0) return false;
     *key = KeyHead(*zp.L, *zp.Dinv, params);
-    key->insert(key->end(), {Bits(zp.e), has_z ? 1u : 0u, rows.smooth ? 1u : 0u});
+    key->insert(key->end(), {Bits(zp.e), has_z ? 1u : 0u, rows.zone.head == k::kHeadSmooth ? 1u : 0u});
     if (tall)
       key->insert(key->end(), {reinterpret_cast<uintptr_t>(CT.data()), 1u, samples_smooth ? 1u : 0u,
                                Bits(zp.dinv_arg), zp.x_free ? 1u : 0u});
@@ -1356,7 +1369,7 @@ struct ZeroRoute final : BatchRoute {
 // [SUM_SQUARE with a dense argument map, scaled-zone prox], one constraint a0 x0 + a1 x1 = 0
 // without a constant: the x-updates are the same two operators as in the multi-block driver, the
 // z-update is the closed-form projection onto the constraint, so one pass over the data matrix
-// does a whole sweep (kernels_fused.hip, chain 1).  f32 and f64, single GPU.  The residual check
+// does a whole sweep (kernels_fused.hip, k::kChainTwoBlock).  f32 and f64, single GPU.  The residual check
 // is the driver's generic one on views of the state.
 struct TwoBlockRoute final : FusedRoute {
   LeastSquaresDesc ls;
@@ -1399,12 +1412,12 @@ struct TwoBlockRoute final : FusedRoute {
     w = DVec::Zeros(m, dt);
     grid = k::LassoFusedGrid(m, n, dt);
     tpart = DVec::Empty(static_cast<int64_t>(grid) * m, dt);
-    // the pass's arguments, once per Init; what chain 1 reads in each state array: k::LassoFusedArgs
+    // the pass's arguments, once per Init; what the chain reads in each state array: k::Chain
     pass.m = m;
     pass.n = n;
     pass.lda = L.rows();
     pass.A = L.data();
-    pass.chain = 1;
+    pass.chain = k::kChainTwoBlock;
     pass.a0 = a0;
     // beside the matrix: the partials, eight state vectors, p, w, and the inverse
     ResidentShare(m, n, dt, static_cast<int64_t>(grid) * m + 8 * n + 2 * m + m * m, /*auto_on=*/false, &pass);
@@ -1550,8 +1563,8 @@ void RunPassGroup(const Group& g) {
       const BatchRoute& mb = *g[i].route;
       EPS_CHECK(mb.pass.m == lead.pass.m && mb.pass.n == lead.pass.n && mb.pass.chain == lead.pass.chain);
       // present where the chain stores or loads through them (the upload checks what is there)
-      EPS_CHECK(mb.pass.chain == 0 || mb.pass.inst.state.y_zero_prev.n == lead.pass.n);
-      if (mb.pass.chain == 4) EPS_CHECK(mb.pass.inst.zd.n == lead.pass.n && mb.pass.inst.zfarg.n == lead.pass.n);
+      EPS_CHECK(mb.pass.chain == k::kChainLasso || mb.pass.inst.state.y_zero_prev.n == lead.pass.n);
+      if (mb.pass.chain == k::kChainZeroTallDot) EPS_CHECK(mb.pass.inst.zd.n == lead.pass.n && mb.pass.inst.zfarg.n == lead.pass.n);
       v.push_back(&mb.pass.inst);
       if (mb.Rows() != nullptr) r.push_back(mb.Rows());
       if (mb.Samples() != nullptr) t.push_back(mb.Samples());
@@ -1699,7 +1712,7 @@ std::vector<bool> RunFusedBatches(const std::vector<Solver*>& solvers) {
     // a tall lasso group has its own two launches; the wide kernels run the lasso chain alone
     if (lead.tall_cols)
       RunTallGroup(g);
-    else if (wide && lead.pass.chain == 0 && static_cast<int>(g.size()) >= BatchWideMin() && lead.dt == F32 &&
+    else if (wide && lead.pass.chain == k::kChainLasso && static_cast<int>(g.size()) >= BatchWideMin() && lead.dt == F32 &&
         k::LassoWideSupported(lead.m, lead.n, lead.pass.A, lead.pass.lda))
       RunWideGroup(g);
     else

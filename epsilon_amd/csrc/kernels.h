@@ -70,62 +70,114 @@ struct ConsensusState {
   DVec y_term, y_zero;             // y of the separable term, y of the copy's term
   DVec y_term_prev, y_zero_prev;   // their previous values (the lasso chain keeps no y_zero_prev)
 };
-// The separable term as a scaled zone, Cs zone(Bs v); a1 scales `var` in the constraint.
-// `ridge` (the x side of a ZERO-term sweep alone: LassoFusedArgs chain 2, ZeroRowsArgs::tall): the
-// term is a scalar least-squares prox instead, var = Cs (Bs v) with Bs and Cs the two factors of its
-// block solve (-L(var, constraint) and Dinv(var)); the zone's parameters are not read.
-// `step` (single launches alone; DESIGN.md 3.11 "A linear term on x, a cone on z"): what stands in the
-// zone's place when it is not kStepZone; the zone's parameters are then not read either.
-//   kStepLinear, the x side alone (chain 2 in the 256-thread shapes, ZeroRowsArgs::tall): a linear
-//     term, var = Cs (Bs v + g_j) with Bs and Cs as for `ridge` and g the n-vector the side carries
-//     (LassoInstance::zg in the pass, ZeroRowsArgs::g in the rows).
-//   kStepNonNeg, the z side alone (the fat rows, chain 3 in the 256-thread shapes): the non-negative
-//     cone, var = Cs (max(Bs v + g, 0) - g) with the side's optional offset g.
-enum ZoneStep { kStepZone, kStepLinear, kStepNonNeg };
+// The chain of a fused pass (LassoFusedArgs::chain, LassoBatchPass): what a streamed column j does
+// between its dot product d_j = A[:,j] . w and its forward update t' += A[:,j] v_j.  The values are
+// fixed: the batch keys begin with them.  Per chain: what the arrays of LassoInstance::state mean, what
+// else of the instance is read, the profile tag (single; batched) and the thread shapes.  f32 and f64.
+enum Chain {
+  // The lasso sweep of the multi-block driver (ChainOneT): copy -> x0, var -> x1, y_zero -> y0, y_term
+  // -> y1, y_term_prev -> y1prev; no y_zero_prev.  "lasso_fused"; "batch_fused_pass".  256 and 512
+  // threads; batched: 256 alone, optionally with the group threshold (group_lam).
+  kChainLasso = 0,
+  // The two-block driver's sweep (prox_admm_two_block.cc:97-112; ChainTwoBlockT): copy -> x0, var -> x1,
+  // u -> u0, y_zero -> z0, y_term -> z1, y_term_prev -> z0_prev, y_zero_prev -> u1, LassoFusedArgs::e1
+  // -> z1_prev; a0, a1: the constraint a0 x0 + a1 x1 = 0 the z-update projects onto.  "lasso_fused"; no
+  // batched form.  256 and 512 threads.
+  kChainTwoBlock = 1,
+  // The column side of a ZERO-term problem (ZeroChainT) on the x constraint: the term
+  // on x first, the projection's copy x' = v_x + kappa A^T w last.  copy -> x', var -> x, y_zero -> the
+  // ZERO term's y, y_term -> the x term's y, y_term_prev / y_zero_prev -> their previous values; a
+  // linear head reads its vector g in zg.  "zero_fused"; "batch_zero_pass".  256 and 512 threads.
+  kChainZeroCols = 2,
+  // The sample side of a TALL ZERO-term problem (DESIGN.md 3.11 "Tall C"; ZeroTallChainT): A is C^T
+  // (features x samples), w the copy x' of this sweep, the state is the z constraint's with
+  // kChainZeroCols' meaning (copy -> z', var -> z); zg, zrhs: the z term's offset and the constant of
+  // the arg row per sample (optional), ke = -L(arg, z'), dinv = Dinv(arg)'s scalar.  The partials are
+  // C^T f_arg's of the next sweep.  "zero_tall"; "batch_zero_tall_pass".  256 and 512 threads.
+  kChainZeroTall = 3,
+  // kChainZeroTall in two launches around ZeroTallSamples, for a z term whose prox does not fit the
+  // column step (a smooth term); they stream C^T as it does and run no head.  Dot: zd[j] = A[:,j] . w
+  // per sample, nothing else is read or written.  "zero_tall_dot"; "batch_zero_tall_dot".  Acc: the
+  // partials of sum_j A[:,j] zfarg[j]; w and the state are not read; no reduction, no barrier.
+  // "zero_tall_acc"; "batch_zero_tall_acc".  256 threads alone.
+  kChainZeroTallDot = 4,
+  kChainZeroTallAcc = 5,
+};
+constexpr bool ChainIsTallHalf(Chain c) { return c == kChainZeroTallDot || c == kChainZeroTallAcc; }
+// The chain keeps the previous y of the copy's term (ConsensusState::y_zero_prev).
+constexpr bool ChainKeepsZeroPrev(Chain c) {
+  return c == kChainTwoBlock || c == kChainZeroCols || c == kChainZeroTall;
+}
+// The profile tag of a launch, by chain: {single, batched}.
+constexpr const char* kChainTags[6][2] = {
+    {"lasso_fused", "batch_fused_pass"},      {"lasso_fused", "batch_fused_pass"},
+    {"zero_fused", "batch_zero_pass"},        {"zero_tall", "batch_zero_tall_pass"},
+    {"zero_tall_dot", "batch_zero_tall_dot"}, {"zero_tall_acc", "batch_zero_tall_acc"}};
+
+// What stands in the threshold's place on a side, var = Cs f(Bs v); a1 scales `var`
+// in the constraint.  One head per side.
+enum Head {
+  kHeadZone,    // the scaled zone, Cs (zone(Bs v + g) - g): every chain and side
+  kHeadRidge,   // the x side of a ZERO-term sweep: a scalar least-squares prox, var = Cs (Bs v) with Bs
+                // and Cs the two factors of its block solve (-L(var, constraint) and Dinv(var))
+  kHeadLinear,  // the x side: a linear term, var = Cs (Bs v + g_j), Bs and Cs as for the ridge term, g
+                // the vector the side carries (LassoInstance::zg in the pass, ZeroRowsArgs::g in the rows)
+  kHeadNonNeg,  // the z side: the non-negative cone, var = Cs (max(Bs v + g, 0) - g), g optional
+  kHeadSmooth,  // the z side: a smooth separable function (ZeroRowsArgs::fn), prox_{lam fn}(Bs v + g) by
+                // the fp64 Newton of SmoothProx; Bs, Cs, a1, lam alone are read
+};
 struct ZoneParams {
   DVec alpha_vec, beta_vec;        // optional per-entry alpha / beta
-  double Bs = 0, Cs = 0, a1 = 0, lam = 0, alpha = 1, beta = 1, M = 0;
-  bool ridge = false;
-  ZoneStep step = kStepZone;
+  double Bs = 0, Cs = 0, a1 = 0, lam = 0, alpha = 1, beta = 1, M = 0;  // kHeadZone alone: lam ... M
+  Head head = kHeadZone;
 };
+// Which side of a ZERO-term sweep the row kernel runs (ZeroRowsArgs::side).
+enum RowsSide {
+  kRowsZ,      // fat C: the z constraint's rows
+  kRowsX,      // tall C: the entries of x
+  kRowsXFree,  // tall C with x in the ZERO term alone: no state, no term, no head
+};
+// The forms that are instantiated; a launcher, an upload and a route's gate all read these.  `block`:
+// LassoFusedBlock.  The halves of the tall pass run no head: their record says kHeadZone.
+constexpr bool FusedPassExists(Chain c, Head h, int block) {
+  if (h == kHeadZone) return !ChainIsTallHalf(c) || block == 256;
+  if (c == kChainZeroCols) return h == kHeadRidge || (h == kHeadLinear && block == 256);
+  return c == kChainZeroTall && h == kHeadNonNeg && block == 256;
+}
+constexpr bool ZeroRowsExist(RowsSide s, Head h) {
+  if (h == kHeadZone) return true;
+  if (s == kRowsZ) return h == kHeadNonNeg || h == kHeadSmooth;
+  return s == kRowsX && (h == kHeadRidge || h == kHeadLinear);
+}
+constexpr bool BatchPassExists(Chain c, Head h) { return c != kChainTwoBlock && h == kHeadZone; }
+constexpr bool BatchRowsExist(RowsSide s, Head h) { return h == kHeadZone || (s == kRowsZ && h == kHeadSmooth); }
+// For the message of a check that one of these fails.
+constexpr const char* kHeadNames[] = {"zone", "ridge", "linear", "non-negative", "smooth"};
+constexpr const char* kRowsSideNames[] = {"z", "x", "free x"};
 // One instance of the sweep as the kernels read it (host view: scalars as double, narrowed to
 // the compute type in one place, kernels_fused_chain.h): the multi-block driver's fused state
 // plus its forward vectors.  Built once per Init by the drivers; a batch uploads its members'.
 struct LassoInstance {
   DVec w;        // m: the block-diagonal-scaled forward-substitution result of this sweep
   DVec tpart;    // LassoFusedGrid(m, n) * m: per-workgroup partials of A v0'
-  ConsensusState state;             // n each; what they mean per chain: LassoFusedArgs
+  ConsensusState state;             // n each; what they mean per chain: Chain
   ZoneParams zone;                  // (vectors: n entries)
   DVec p, rhs;   // m: the reduced partials (+ rhs), input of the inverse apply; its constant part
   double kappa = 0;                 // copy = v0 + kappa * (A^T w)
   double pkappa = 0;                // scale of the summed partials in p (see LassoBatchInst)
-  // chains 3, 4, 5 alone (n entries each, n the streamed dimension: the samples)
-  DVec zg, zrhs;                    // chain 3, optional; chain 2 with a linear term (zone.step): zg = g
-  DVec zd, zfarg;                   // chain 4 writes zd, chain 5 reads zfarg
-  double ke = 0, dinv = 0;          // chain 3
+  // the tall ZERO chains alone (n entries each, n the streamed dimension: the samples)
+  DVec zg, zrhs;                    // kChainZeroTall, optional; kChainZeroCols with kHeadLinear: zg = g
+  DVec zd, zfarg;                   // kChainZeroTallDot writes zd, kChainZeroTallAcc reads zfarg
+  double ke = 0, dinv = 0;          // kChainZeroTall
 };
 struct LassoFusedArgs {
   int64_t m = 0, n = 0, lda = 0;
   DVec A;        // m x n column-major
   LassoInstance inst;
   unsigned* epoch = nullptr;        // optional device counter, incremented once per launch
-  // chain = 0: the lasso sweep; inst.state has copy -> x0, var -> x1, y_zero -> y0, y_term -> y1.
-  // chain = 1: the two-block driver's sweep (prox_admm_two_block.cc:97-112); copy -> x0, var -> x1,
-  // u -> u0, y_zero -> z0, y_term -> z1, y_term_prev -> z0_prev, y_zero_prev -> u1, e1 -> z1_prev;
-  // a0, a1: the consensus constraint a0 x0 + a1 x1 = 0 the z-update projects onto.  f32 and f64.
-  // chain = 2: the sweep of a ZERO-term problem (scaled-zone term on x first, the
-  // projection's copy x' = v_x + kappa A^T w last) on the x constraint.  Tag "zero_fused".  f32, f64.
-  // chain = 3: the sample side of a TALL ZERO-term problem ("Tall C"): A is C^T
-  // (features x samples), w the copy x' of this sweep, the state is the z constraint's; inst.zg, zrhs:
-  // the z term's offset and the constant of the arg row per sample (optional), inst.ke = -L(arg, z'),
-  // dinv = Dinv(arg)'s scalar.  The partials are C^T f_arg's of the next sweep.  Tag "zero_tall".  f32, f64.
-  // chain = 4, 5: chain 3 in two launches around ZeroTallSamples, for a smooth z term (256-thread
-  // shapes alone).  4 (profile tag "zero_tall_dot"): zd[j] = A[:,j] . w per sample, nothing else is
-  // read or written.  5 (profile tag "zero_tall_acc"): the partials of sum_j A[:,j] zfarg[j]; w and
-  // the state are not read.  inst.zd, zfarg: n each.
-  int chain = 0;
+  Chain chain = kChainLasso;
   double a0 = 1;
-  DVec e1;       // chain 1 alone
+  DVec e1;       // kChainTwoBlock alone
   // the matrix's share that is loaded to stay in the Infinity Cache (LassoFusedResidency); 0, 0:
   // every load non-temporal
   int qfull = 0;
@@ -139,37 +191,33 @@ enum SmoothFn { SMOOTH_EXP, SMOOTH_LOGISTIC, SMOOTH_NEG_ENTR, SMOOTH_INV_POS, SM
 // "zero_fused_rows".  Per row: finishes sweep k with w (z' = v_z - e w, y and u on the z
 // constraint), runs the z term of sweep k + 1 (zone(Bs v + g) - g, scaled by Cs), forms the next
 // v_z, sums the pass's partials in a fixed order and writes r = (rhs - e v_z) + pkappa sum(tpart).
-// smooth: the z term is the smooth separable function `fn` (SMOOTH_LOGISTIC alone) in place of the
-// zone, prox_{lam fn}(Bs v + g) by the fp64 Newton of SmoothProx.  The z term of sweep k + 1 (s,
-// y_s, v_z) is then carried to the next launch in hs, hys, hv instead of being recomputed there:
-// ZeroSmoothHead fills them from the state before the first launch.
+// The head is zone.head (ZeroRowsExist says which a side takes).  kHeadSmooth: `fn` (SMOOTH_LOGISTIC
+// alone); the z term of sweep k + 1 (s, y_s, v_z) is then carried to the next launch in hs, hys, hv
+// instead of being recomputed there: ZeroSmoothHead fills them from the state before the first launch.
 struct ZeroRowsArgs {
   int64_t m = 0;
   int nparts = 0;
   DVec w, tpart, r, rhs, g;            // rhs, g: optional (empty: zero)
   ConsensusState state;                // m each: the z constraint's (var -> z, copy -> z')
-  ZoneParams zone;                     // smooth: Bs, Cs, a1, lam alone are read
+  ZoneParams zone;
   double e = 0, pkappa = 0;
-  bool smooth = false;
   SmoothFn fn = SMOOTH_LOGISTIC;
-  DVec hs, hys, hv;                    // smooth: m each, private to the caller
-  // The x side of a tall problem (profile tag "zero_tall_cols"): the m entries are those of x, w is
-  // the copy x' as the inverse apply left it (q = w, no product on top), the term is the one on x
-  // and r = v_x' + pkappa sum(tpart) is the next f_x; rhs and e are not read.  A scaled zone, a ridge
-  // term (zone.ridge) or a linear term (zone.step = kStepLinear, `g` its vector of m entries).
-  // Fat (tall unset): zone.step = kStepNonNeg puts the non-negative cone in the zone's place.
-  bool tall = false;
-  // Free x (with tall; profile tag "zero_tall_free_cols"; DESIGN.md 3.11 "x in the ZERO term alone"):
-  // x has no constraint row, so there is no state, no term and no chain.  Per entry j the launch
-  // sums the partials in the same order, keeps xcur[j] = w[j] - x of the sweep the pass just used,
-  // the iterate at this boundary - and writes r[j] = pkappa sum(tpart), the next f_x.  `state`, the
-  // zone, rhs, g and e are not read; xcur: m entries.
-  bool x_free = false;
+  DVec hs, hys, hv;                    // kHeadSmooth: m each, private to the caller
+  // kRowsX, the x side of a tall problem (profile tag "zero_tall_cols"): the m entries are those of x,
+  // w is the copy x' as the inverse apply left it (q = w, no product on top), the term is the one on
+  // x and r = v_x' + pkappa sum(tpart) is the next f_x; rhs and e are not read.  A linear head reads
+  // its vector in `g`, m entries.
+  // kRowsXFree (profile tag "zero_tall_free_cols"; DESIGN.md 3.11 "x in the ZERO term alone"): x has
+  // no constraint row, so there is no state, no term and no chain.  Per entry j the launch sums the
+  // partials in the same order, keeps xcur[j] = w[j] - x of the sweep the pass just used, the iterate
+  // at this boundary - and writes r[j] = pkappa sum(tpart), the next f_x.  `state`, the zone, rhs, g
+  // and e are not read; xcur: m entries.
+  RowsSide side = kRowsZ;
   DVec xcur;
 };
 // The sample side of a tall ZERO-term sweep whose z term is smooth (SMOOTH_LOGISTIC alone), between
-// the two halves of the pass (LassoFusedArgs::chain 4 and 5), one launch, a thread per sample,
-// profile tag "zero_tall_samples".  Per sample: finishes sweep k from d = C[i,:] . x' (chain 3's
+// the two halves of the pass (kChainZeroTallDot, kChainZeroTallAcc), one launch, a thread per sample,
+// profile tag "zero_tall_samples".  Per sample: finishes sweep k from d = C[i,:] . x' (kChainZeroTall's
 // arithmetic: f_arg, the scalar pivot, arg, z' = v + ke arg, y and u on the z constraint) with the z
 // term of this sweep taken from the carried head hs, hys, hv; runs the z term of sweep k + 1 -
 // prox_{lam fn}(Bs v + g) by the fp64 Newton of SmoothProx, once - leaves it in hs, hys, hv and
@@ -191,16 +239,13 @@ void ZeroFusedRows(const ZeroRowsArgs& args);
 void ZeroSmoothHead(const ZeroRowsArgs& args);  // profile tag "zero_fused_head"
 // The row side of `count` members of a batch in ONE launch, profile tag "batch_zero_rows": member b
 // (grid row b) runs ZeroFusedRows' own workgroups on its own record, so its result is that of its
-// own launch bit for bit.  The members share m, nparts, the dtype and the form (zone or smooth).
-// ZeroRowsBatchUpload writes their records in order into `table` (device; grown as needed): as with
-// LassoBatchUpload, a member that stops is dropped by uploading the shorter list.
-// `tall` (all members or none; profile tag "batch_zero_tall_cols"): grid row b is member b's own
-// "zero_tall_cols" launch, the x side of a tall problem (ZeroRowsArgs::tall).
-// `x_free` (with `tall`, all members or none; profile tag "batch_zero_tall_free_cols"): grid row b is
-// member b's own "zero_tall_free_cols" launch (ZeroRowsArgs::x_free).
+// own launch bit for bit.  The members share m, nparts, the dtype, the side and the head
+// (BatchRowsExist).  ZeroRowsBatchUpload writes their records in order into `table` (device; grown as
+// needed): as with LassoBatchUpload, a member that stops is dropped by uploading the shorter list.
+// kRowsX (profile tag "batch_zero_tall_cols"), kRowsXFree ("batch_zero_tall_free_cols"): grid row b is
+// member b's own "zero_tall_cols" / "zero_tall_free_cols" launch.
 void ZeroRowsBatchUpload(const std::vector<const ZeroRowsArgs*>& members, DVec* table);
-void ZeroFusedRowsBatch(int64_t m, int nparts, bool smooth, DType dt, const DVec& table, int count,
-                        bool tall = false, bool x_free = false);
+void ZeroFusedRowsBatch(int64_t m, int nparts, RowsSide side, Head head, DType dt, const DVec& table, int count);
 // The sample side of `count` tall members with a smooth z term in ONE launch, profile tag
 // "batch_zero_tall_samples": grid row b is member b's own ZeroTallSamples launch, a thread per
 // sample, on its own record with the carried head in its own hs, hys, hv; no wait, no barrier, no
@@ -266,20 +311,19 @@ template <class T> struct LassoBatchInst {
   T kappa, Bs, Cs, a1, lam, alpha, beta, M;
   T pkappa;          // scale of the summed partials in p (kappa, but for the whitened route)
   T* e0;             // n: the ZERO chain's second "previous y" (nullptr on the lasso chain)
-  // the tall ZERO chains (3, 4, 5); nullptr / unused on chains 0 and 2
-  const T* zg;       // n: chain 3's offset of the z term (nullptr: none)
-  const T* zrhs;     // n: chain 3's constant on the arg row (nullptr: none)
-  T* zd;             // n: chain 4 stores the dot products here
-  const T* zfarg;    // n: chain 5 reads the forward weights here
-  T ke, dinv;        // chain 3: -L(arg, z'), Dinv(arg)'s scalar
+  // the tall ZERO chains; nullptr / unused on kChainLasso and kChainZeroCols
+  const T* zg;       // n: kChainZeroTall's offset of the z term (nullptr: none)
+  const T* zrhs;     // n: kChainZeroTall's constant on the arg row (nullptr: none)
+  T* zd;             // n: kChainZeroTallDot stores the dot products here
+  const T* zfarg;    // n: kChainZeroTallAcc reads the forward weights here
+  T ke, dinv;        // kChainZeroTall: -L(arg, z'), Dinv(arg)'s scalar
 };
 // Instances one launch of the batched pass carries for (m, dtype) - set by the register budget
 // of its instantiation - or 0 where the single pass would take a form the batched one does not
-// mirror (512-thread workgroups): such instances are solved one by one.  `chain`: 0 the lasso
-// chain, 2 the ZERO-term column chain (LassoFusedArgs::chain), which has widths of its own; 3, 4, 5
-// the tall ZERO-term chains, (m, n) the pass's own dimensions (features x samples), each with its
-// widths - 4 and 5 hold half of the per-member registers and are wider.
-int LassoBatchWidth(int64_t m, int64_t n, DType dt, int chain = 0);
+// mirror (512-thread workgroups): such instances are solved one by one.  Every `chain` has widths of
+// its own, (m, n) the pass's own dimensions (the tall chains: features x samples); the halves of the
+// tall pass hold half of the per-member registers and are wider.
+int LassoBatchWidth(int64_t m, int64_t n, DType dt, Chain chain = kChainLasso);
 // The descriptors of `members` in order into `table` (device; grown as needed): the active set
 // of a batch is this array, so an instance that stops is dropped by uploading the shorter list.
 void LassoBatchUpload(const std::vector<const LassoInstance*>& members, DType dt, DVec* table);
@@ -289,13 +333,11 @@ void LassoBatchUpload(const std::vector<const LassoInstance*>& members, DType dt
 // threshold step is the group shrinkage of its rows with this weight (NORM_2 along axis 1)
 // instead of each instance's scaled zone.
 // `res`: the matrix's resident share, as in LassoFusedArgs.
-// `chain`, as LassoFusedArgs::chain, every record holding what that chain reads and writes, count <=
-// LassoBatchWidth(m, n, dt, chain).  0: the lasso chain (profile tag "batch_fused_pass"); 2: the column
-// side of ZERO-term members ("batch_zero_pass"); 3, 4, 5: the sample side of tall ones, A the transposed
-// copy ("batch_zero_tall_pass", "batch_zero_tall_dot", "batch_zero_tall_acc").  2 to 5: no group_lam.
+// `chain` (BatchPassExists), every record holding what that chain reads and writes, count <=
+// LassoBatchWidth(m, n, dt, chain).  group_lam: kChainLasso alone.
 void LassoBatchPass(int64_t m, int64_t n, int64_t lda, const DVec& A, const DVec& table, int first,
                     int count, const double* group_lam = nullptr, const FusedResidency& res = FusedResidency(),
-                    int chain = 0);
+                    Chain chain = kChainLasso);
 // p = pkappa * sum(tpart) (+ rhs) of `count` instances in one launch, each in the summation order
 // of ReducePartials(m, nparts, tpart, pkappa, 0, p, rhs).  `rhs_aligned`: every rhs present is
 // 16-byte aligned (picks the same kernel form as the single call).

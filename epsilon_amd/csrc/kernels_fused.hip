@@ -46,35 +46,21 @@ constexpr int kBlock = 256;
 // BS threads own the m rows: 256 (two workgroups per CU) up to m = 10240 in f32; 512 (one
 // workgroup of 8 waves per CU) up to m = 20480 (6.37 TB/s on 2e4 x 5e4).  In f64 a 16-byte load
 // holds two rows, so 512 threads x 10 chunks own up to 10240 rows.
-// MODE 0: the multi-block driver's chain (ChainOneT).  MODE 1: the two-block driver's (ChainTwoBlockT);
-// the state arrays then mean u -> u0, y0 -> z0, y1 -> z1, y1prev -> z0_prev, e0 -> u1, e1 -> z1_prev.
-// MODE 2: the column side of a ZERO-term problem (ZeroChainT); x0 -> x', x1 -> x, y0 -> the ZERO
-// term's y, y1 -> the x term's y, y1prev / e0 -> their previous values.
-// MODE 3: the sample side of a tall ZERO-term problem (ZeroTallChainT, tag "zero_tall").  The matrix
-// is C^T, so the register-held dimension is the feature index and a streamed column is a sample:
-// w -> x', the state arrays are the m-long ones of the z constraint with MODE 2's meaning (x0 -> z',
-// x1 -> z, y0 -> the ZERO term's y, y1 -> the z term's y), and `zt` has the per-sample offset and
-// rhs and the two scalar pivots.  The value returned into the forward product is the next f_arg.
-// MODE 4 and MODE 5: MODE 3 in two halves, for a z term whose prox does not fit the per-column step
-// (a smooth term: ZeroTallSamplesKernel runs between them).  They stream C^T exactly as MODE 3 does.
-// MODE 4 (tag "zero_tall_dot") is the dot product alone: per sample j thread 0 stores d_j =
-// C[j,:] . x' to `e0`, here the m-long vector d; no partials, no state access.  MODE 5 (tag
-// "zero_tall_acc") is the forward product alone: per sample a broadcast load of f_arg_j from `zt.rhs`,
-// here the m-long vector the sample kernel wrote, then t' += C[j,:]^T f_arg_j; no dot product, no
-// reduction, no barrier.
-// MODE 6: MODE 2 with a ridge term on x (ZoneParams::ridge: the RidgeStep head in place of the
-// threshold); the same arrays, the same tag.
-// MODE 7: MODE 2 with a linear term on x (ZoneParams::step: the LinearStep head); the same arrays, the
-// same tag, and one broadcast load of g_j from `zt.g` per streamed column.  MODE 8: MODE 3 with the
-// non-negative cone on z (the NonNegStep head); the same arrays, the same tag.  Both in the
-// 256-thread shapes alone.
-template <class T, int NR, int BS, int MODE>
+// CHAIN: what a column does between its dot product and its forward update, and what the state
+// arrays, e0, e1 and `zt` then hold (Chain, kernels.h; u, x0, x1, y0, y1, y1prev are the instance's u,
+// copy, var, y_zero, y_term, y_term_prev, e0 its y_zero_prev).  kChainZeroTallDot stores d_j through
+// `e0`, here the vector zd; kChainZeroTallAcc reads f_arg_j through `zt.rhs`, here zfarg.
+// Head: the tag of what stands in the threshold's place (kernels_fused_chain.h; void: the zone), for
+// the forms FusedPassExists lists; the same arrays, the same tag, and for LinearStep one broadcast
+// load of g_j from `zt.g` per streamed column.
+template <class T, int NR, int BS, int CHAIN, class Head = void>
 __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
     int64_t m, int64_t n, const T* __restrict__ A, int64_t lda, const T* __restrict__ w,
     FusedScalarsT<T> c, T* u, T* x0, T* x1, T* y0, T* y1, T* y1prev, T* __restrict__ tpart,
     unsigned* epoch, T* e0, T* e1, int qfull, int64_t jcut, ZeroTallScalarsT<T> zt) {
   typedef typename Chunk<T>::V V;
   constexpr int R = Chunk<T>::R;
+  constexpr bool kHalf = ChainIsTallHalf(static_cast<Chain>(CHAIN));  // no state, no head
   __shared__ T red[2][BS / 64];
   // sweep counter of the peer exchange (kernels_peer.hip): the two exchange kernels that follow
   // this pass in stream order tag their granules with it
@@ -88,8 +74,8 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
 #pragma unroll
   for (int q = 0; q < NR; ++q) {
     row[q] = (static_cast<int64_t>(q) * BS + tid) * R;
-    if constexpr (MODE != 5) wv[q] = row[q] < m ? *reinterpret_cast<const V*>(w + row[q]) : zero;
-    if constexpr (MODE != 4) tp[q] = zero;
+    if constexpr (CHAIN != kChainZeroTallAcc) wv[q] = row[q] < m ? *reinterpret_cast<const V*>(w + row[q]) : zero;
+    if constexpr (CHAIN != kChainZeroTallDot) tp[q] = zero;
   }
   // this workgroup's columns: pairs (2 jp, 2 jp + 1), jp = blockIdx.x + k gridDim.x, one column
   // at a time
@@ -125,21 +111,21 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
     if (jn >= 0) load(nxt, jn);
     // per-column state (same address in every lane: broadcast loads)
     T uj = T(0), y0j = T(0), y1j = T(0);
-    if constexpr (MODE <= 3 || MODE >= 6) {
+    if constexpr (!kHalf) {
       uj = u[j];
       y0j = y0[j];
       y1j = y1[j];
     }
     T u1j = T(0);
-    if (MODE == 1) u1j = e0[j];
+    if constexpr (CHAIN == kChainTwoBlock) u1j = e0[j];
     T gj = T(0), rj = T(0);
-    if (MODE == 3 || MODE == 8) {
+    if constexpr (CHAIN == kChainZeroTall) {
       if (zt.g != nullptr) gj = zt.g[j];
       if (zt.rhs != nullptr) rj = zt.rhs[j];
     }
-    if constexpr (MODE == 7) gj = zt.g[j];
+    if constexpr (std::is_same<Head, LinearStep>::value) gj = zt.g[j];
     T d = T(0);
-    if constexpr (MODE != 5) {
+    if constexpr (CHAIN != kChainZeroTallAcc) {
 #pragma unroll
       for (int q = 0; q < NR; ++q)
 #pragma unroll
@@ -156,11 +142,11 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
     if (c.alpha_v != nullptr) cj.alpha = c.alpha_v[j];
     if (c.beta_v != nullptr) cj.beta = c.beta_v[j];
     T v0n = T(0);
-    if constexpr (MODE == 4) {
+    if constexpr (CHAIN == kChainZeroTallDot) {
       if (tid == 0) e0[j] = d;
-    } else if constexpr (MODE == 5) {
+    } else if constexpr (CHAIN == kChainZeroTallAcc) {
       v0n = zt.rhs[j];
-    } else if (MODE == 0) {
+    } else if constexpr (CHAIN == kChainLasso) {
       T nx0, nx1, ny0, ny1, nu;
       v0n = ChainOneT<T>(d, cj, uj, y0j, y1j, &nx0, &nx1, &ny0, &ny1, &nu);
       if (tid == 0) {
@@ -171,26 +157,12 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
         y1[j] = ny1;
         u[j] = nu;
       }
-    } else if (MODE == 2 || MODE == 6 || MODE == 7) {
-      T ns, nq, nys, nyq, nu;
-      if constexpr (MODE == 6) v0n = ZeroChainT<T, RidgeStep>(d, cj, T(0), uj, y1j, y0j, &ns, &nq, &nys, &nyq, &nu);
-      else if constexpr (MODE == 7) v0n = ZeroChainT<T, LinearStep>(d, cj, gj, uj, y1j, y0j, &ns, &nq, &nys, &nyq, &nu);
-      else v0n = ZeroChainT<T>(d, cj, T(0), uj, y1j, y0j, &ns, &nq, &nys, &nyq, &nu);
-      if (tid == 0) {
-        y1prev[j] = y1j;
-        e0[j] = y0j;
-        x1[j] = ns;
-        x0[j] = nq;
-        y1[j] = nys;
-        y0[j] = nyq;
-        u[j] = nu;
-      }
-    } else if (MODE == 3 || MODE == 8) {
-      T ns, nq, nys, nyq, nu;
-      if constexpr (MODE == 8)
-        v0n = ZeroTallChainT<T, NonNegStep>(d, cj, zt.ke, zt.dinv, gj, rj, uj, y1j, y0j, &ns, &nq, &nys, &nyq, &nu);
+    } else if constexpr (CHAIN == kChainZeroCols || CHAIN == kChainZeroTall) {
+      T ns, nq, nys, nyq, nu;  // (gj: zero but for the linear head and kChainZeroTall's offset)
+      if constexpr (CHAIN == kChainZeroCols)
+        v0n = ZeroChainT<T, Head>(d, cj, gj, uj, y1j, y0j, &ns, &nq, &nys, &nyq, &nu);
       else
-        v0n = ZeroTallChainT<T>(d, cj, zt.ke, zt.dinv, gj, rj, uj, y1j, y0j, &ns, &nq, &nys, &nyq, &nu);
+        v0n = ZeroTallChainT<T, Head>(d, cj, zt.ke, zt.dinv, gj, rj, uj, y1j, y0j, &ns, &nq, &nys, &nyq, &nu);
       if (tid == 0) {
         y1prev[j] = y1j;
         e0[j] = y0j;
@@ -214,7 +186,7 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
         e0[j] = nu1;
       }
     }
-    if constexpr (MODE != 4) {
+    if constexpr (CHAIN != kChainZeroTallDot) {
 #pragma unroll
       for (int q = 0; q < NR; ++q)
 #pragma unroll
@@ -225,7 +197,7 @@ __global__ __launch_bounds__(BS, 2) void LassoFusedStreamKernelT(
     j = jn;
     step = step_n;
   }
-  if constexpr (MODE != 4) {
+  if constexpr (CHAIN != kChainZeroTallDot) {
     T* out = tpart + static_cast<int64_t>(blockIdx.x) * m;
 #pragma unroll
     for (int q = 0; q < NR; ++q)
@@ -237,27 +209,22 @@ template <class T, int NR, int BS>
 void LaunchFused(const LassoFusedArgs& a, int grid) {
   const LassoBatchInst<T> i = Narrow<T>(a.inst);
   const ZoneParams& z = a.inst.zone;
-  T* e0 = a.chain == 4 ? i.zd : i.e0;  // MODE 4 stores d through it
-  T* e1 = a.chain == 1 ? a.e1.as<T>() : nullptr;
+  T* e0 = a.chain == kChainZeroTallDot ? i.zd : i.e0;  // the dot half stores d through it
+  T* e1 = a.chain == kChainTwoBlock ? a.e1.as<T>() : nullptr;
   ZeroTallScalarsT<T> zt = {nullptr, nullptr, T(0), T(0)};
-  if (a.chain == 3) zt = {i.zg, i.zrhs, i.ke, i.dinv};
-  if (a.chain == 5) zt.rhs = i.zfarg;  // MODE 5 reads f_arg through it
-  auto kernel = LassoFusedStreamKernelT<T, NR, BS, 0>;
-  if (a.chain == 1) kernel = LassoFusedStreamKernelT<T, NR, BS, 1>;
-  if (a.chain == 2) kernel = LassoFusedStreamKernelT<T, NR, BS, 2>;
-  if (a.chain == 2 && z.ridge) kernel = LassoFusedStreamKernelT<T, NR, BS, 6>;
-  if (a.chain == 3) kernel = LassoFusedStreamKernelT<T, NR, BS, 3>;
-  // the halves of the tall pass, the linear and the non-negative head exist in the 256-thread shapes
-  // alone (ZeroRoute takes no other)
-  if constexpr (BS == 256) {
-    if (a.chain == 4) kernel = LassoFusedStreamKernelT<T, NR, BS, 4>;
-    if (a.chain == 5) kernel = LassoFusedStreamKernelT<T, NR, BS, 5>;
-    if (a.chain == 2 && z.step == kStepLinear) {
-      kernel = LassoFusedStreamKernelT<T, NR, BS, 7>;
-      zt.g = i.zg;
-    }
-    if (a.chain == 3 && z.step == kStepNonNeg) kernel = LassoFusedStreamKernelT<T, NR, BS, 8>;
-  }
+  if (a.chain == kChainZeroTall) zt = {i.zg, i.zrhs, i.ke, i.dinv};
+  if (a.chain == kChainZeroTallAcc) zt.rhs = i.zfarg;  // the accumulate half reads f_arg through it
+  if (z.head == kHeadLinear) zt.g = i.zg;
+  // the one instantiation of (chain, head) in this shape; LassoFusedPass has checked that it exists
+  decltype(&LassoFusedStreamKernelT<T, NR, BS, kChainLasso>) kernel = nullptr;
+  WithChain(a.chain, [&](auto chain) {
+    WithHead(z.head, [&](auto head) {
+      constexpr Chain kChain = decltype(chain)::value;
+      typedef typename decltype(head)::type H;
+      if constexpr (FusedPassExists(kChain, HeadOf<H>(), BS)) kernel = LassoFusedStreamKernelT<T, NR, BS, kChain, H>;
+    });
+  });
+  EPS_CHECK(kernel != nullptr);
   hipLaunchKernelGGL(
       kernel,
       dim3(grid), dim3(BS), 0, Runtime::Get().stream(), a.m, a.n, a.A.as<T>(), a.lda, i.w,
@@ -292,7 +259,7 @@ void LaunchFusedT(const LassoFusedArgs& a, int grid, int block) {
 // so the fp64 Newton of the z term runs once per sample and sweep, on whole waves.  ZeroTallChainT
 // from its second line on, with the head of this sweep (s, y_s, v) carried from the previous launch
 // in hs, hys, hv as on the fat route's row kernel: finishes the sweep from d_i = C[i,:] . x', stores
-// the boundary state as MODE 3 does, computes the next head once, leaves it in hs, hys, hv and
+// the boundary state as kChainZeroTall does, computes the next head once, leaves it in hs, hys, hv and
 // writes the next f_arg_i for the accumulate pass.  A thread reads and writes its own sample alone.
 //
 // One member's sample side as the kernels read it (compute type T): the single launch takes it as
@@ -358,7 +325,7 @@ __global__ __launch_bounds__(kBlock) void ZeroTallSamplesBatchKernel(
 // row's chain (d = w_i, kappa = -e) and writes r.  A workgroup reads and writes the state of its
 // own rows only.
 // Fn = void, 16 rows: the z term is a scaled zone (ZeroChainT; a threshold on 16 lanes).  Fn =
-// NonNegStep: the same with the non-negative cone in the zone's place (ZoneParams::step).
+// NonNegStep: the same with the non-negative cone in the zone's place.
 // Fn a smooth function, 64 rows: the lanes pl = 0 are one whole wave, so the fp64 Newton runs on
 // every lane of the only wave that is still alive; consecutive lanes load consecutive rows of a
 // partial vector.  The head of this sweep (s, y_s, v) comes from the previous launch in hs, hys,
@@ -385,8 +352,8 @@ template <class T> struct ZeroRowsInst {
 // TALL (tag "zero_tall_cols"): the x side of a tall problem over the n entries of x.  The same
 // summation of the partials; the chain takes q = x'_j as the inverse apply left it in w
 // (ZeroTallColsChainT) and r_j = f_x = v_x' + pkappa sum: no rhs on this side.  Fn = void: the x term
-// is a scaled zone; Fn = RidgeStep: a ridge term (ZoneParams::ridge); Fn = LinearStep: a linear term
-// (ZoneParams::step), its per-entry constant in I.g.
+// is a scaled zone; Fn = RidgeStep: a ridge term; Fn = LinearStep: a linear term, its per-entry
+// constant in I.g.
 // FREE (with TALL, Fn = void; tag "zero_tall_free_cols"): x lives in the ZERO term alone, so the side
 // has no state, no term and no chain.  The same summation of the partials; then lane 0 keeps
 // x_j = w_j of the sweep the pass just used in I.zq (the ZERO term's own variable of this side: here x
@@ -503,7 +470,7 @@ __global__ __launch_bounds__(kBlock) void ZeroSmoothHeadKernel(
 }
 
 template <class T> ZeroRowsInst<T> RowsInstOf(const ZeroRowsArgs& a) {
-  if (a.x_free) {  // no state and no term: the partials, w, x (in the copy's place), r and pkappa
+  if (a.side == kRowsXFree) {  // no state and no term: the partials, w, x (in the copy's place), r and pkappa
     ZeroRowsInst<T> f = {};
     f.tpart = a.tpart.as<T>();
     f.w = a.w.as<T>();
@@ -519,53 +486,54 @@ template <class T> ZeroRowsInst<T> RowsInstOf(const ZeroRowsArgs& a) {
   d.g = OptT<T>(a.g);
   NarrowState<T>(a.state, &d.u, &d.z, &d.zq, &d.yz, &d.yq, &d.yzprev, &d.yqprev);
   d.r = a.r.as<T>();
-  d.hs = a.smooth ? a.hs.as<T>() : nullptr;
-  d.hys = a.smooth ? a.hys.as<T>() : nullptr;
-  d.hv = a.smooth ? a.hv.as<T>() : nullptr;
+  const bool smooth = a.zone.head == kHeadSmooth;
+  d.hs = smooth ? a.hs.as<T>() : nullptr;
+  d.hys = smooth ? a.hys.as<T>() : nullptr;
+  d.hv = smooth ? a.hv.as<T>() : nullptr;
   d.c = ScalarsOf<T>(a.zone, -a.e, 1, 1);
   d.pkappa = static_cast<T>(a.pkappa);
   d.lam64 = a.zone.lam;
   return d;
 }
 
-template <class T, int ROWS, class Fn, bool TALL = false>
-void LaunchZeroRows(const ZeroRowsArgs& a) {
-  const unsigned grid = static_cast<unsigned>((a.m + ROWS - 1) / ROWS);
-  hipLaunchKernelGGL((ZeroFusedRowsKernel<T, ROWS, Fn, TALL>), dim3(grid), dim3(ROWS * kZeroLanes), 0,
+// The single and the batched kernel of (side, head) - null where ZeroRowsExist, BatchRowsExist list
+// none; the callers have checked - and the rows of their workgroups (the smooth head: a whole wave).
+template <class T> struct RowsForm {
+  void (*single)(int64_t, int, ZeroRowsInst<T>);
+  void (*batch)(int64_t, int, const ZeroRowsInst<T>*);
+  int rows;
+};
+template <class T> RowsForm<T> RowsFormOf(RowsSide side, Head h) {
+  if (side == kRowsXFree) return {ZeroFreeColsKernel<T>, ZeroFreeColsBatchKernel<T>, kZeroRows};
+  RowsForm<T> f = {nullptr, nullptr, h == kHeadSmooth ? kZeroSmoothRows : kZeroRows};
+  WithHead(h, [&](auto head) {
+    typedef typename decltype(head)::type Fn;
+    auto pick = [&](auto tall) {
+      constexpr bool kTall = decltype(tall)::value;
+      constexpr RowsSide kSide = kTall ? kRowsX : kRowsZ;
+      constexpr int kRows = HeadOf<Fn>() == kHeadSmooth ? kZeroSmoothRows : kZeroRows;
+      if constexpr (ZeroRowsExist(kSide, HeadOf<Fn>())) f.single = ZeroFusedRowsKernel<T, kRows, Fn, kTall>;
+      if constexpr (BatchRowsExist(kSide, HeadOf<Fn>())) f.batch = ZeroFusedRowsBatchKernel<T, kRows, Fn, kTall>;
+    };
+    if (side == kRowsX) pick(std::true_type());
+    else pick(std::false_type());
+  });
+  return f;
+}
+
+template <class T> void LaunchZeroRows(const ZeroRowsArgs& a) {
+  const RowsForm<T> f = RowsFormOf<T>(a.side, a.zone.head);
+  EPS_CHECK(f.single != nullptr);
+  hipLaunchKernelGGL(f.single, dim3(static_cast<unsigned>((a.m + f.rows - 1) / f.rows)), dim3(f.rows * kZeroLanes), 0,
                      Runtime::Get().stream(), a.m, a.nparts, RowsInstOf<T>(a));
 }
 template <class T>
-void LaunchZeroFreeCols(const ZeroRowsArgs& a) {
-  const unsigned grid = static_cast<unsigned>((a.m + kZeroRows - 1) / kZeroRows);
-  hipLaunchKernelGGL((ZeroFreeColsKernel<T>), dim3(grid), dim3(kZeroRows * kZeroLanes), 0, Runtime::Get().stream(),
-                     a.m, a.nparts, RowsInstOf<T>(a));
-}
-
-template <class T, int ROWS, class Fn, bool TALL = false>
-void LaunchZeroRowsBatch(int64_t m, int nparts, const DVec& table, int count) {
-  const unsigned grid = static_cast<unsigned>((m + ROWS - 1) / ROWS);
-  hipLaunchKernelGGL((ZeroFusedRowsBatchKernel<T, ROWS, Fn, TALL>), dim3(grid, static_cast<unsigned>(count)),
-                     dim3(ROWS * kZeroLanes), 0, Runtime::Get().stream(), m, nparts,
+void LaunchZeroRowsBatch(int64_t m, int nparts, RowsSide side, Head head, const DVec& table, int count) {
+  const RowsForm<T> f = RowsFormOf<T>(side, head);
+  EPS_CHECK(f.batch != nullptr);
+  hipLaunchKernelGGL(f.batch, dim3(static_cast<unsigned>((m + f.rows - 1) / f.rows), static_cast<unsigned>(count)),
+                     dim3(f.rows * kZeroLanes), 0, Runtime::Get().stream(), m, nparts,
                      reinterpret_cast<const ZeroRowsInst<T>*>(table.as<char>()));
-}
-template <class T>
-void LaunchZeroFreeColsBatch(int64_t m, int nparts, const DVec& table, int count) {
-  const unsigned grid = static_cast<unsigned>((m + kZeroRows - 1) / kZeroRows);
-  hipLaunchKernelGGL((ZeroFreeColsBatchKernel<T>), dim3(grid, static_cast<unsigned>(count)),
-                     dim3(kZeroRows * kZeroLanes), 0, Runtime::Get().stream(), m, nparts,
-                     reinterpret_cast<const ZeroRowsInst<T>*>(table.as<char>()));
-}
-
-// The records of a batch's members in order into `table` (device; grown as needed).
-template <class Inst>
-void UploadRecords(const std::vector<Inst>& host, DVec* table) {
-  const size_t bytes = host.size() * sizeof(Inst);
-  const int64_t words = static_cast<int64_t>((bytes + 7) / 8);
-  if (table->n < words || table->dt != F64) *table = DVec::Empty(words < 1 ? 1 : words, F64);
-  if (bytes == 0) return;
-  Runtime& rt = Runtime::Get();
-  EPS_HIP(hipMemcpyAsync(table->data(), host.data(), bytes, hipMemcpyHostToDevice, rt.stream()));
-  rt.Sync();  // `host` goes out of scope with the caller
 }
 
 template <class T>
@@ -591,58 +559,44 @@ void CheckState(const ConsensusState& s, int64_t n, DType dt, bool zero_prev = t
   if (zero_prev) EPS_CHECK(s.y_zero_prev.n == n && s.y_zero_prev.dt == dt);
 }
 
+// `exists`: ZeroRowsExist or BatchRowsExist (`what`: "" or "batched ") of (side, head).
+void CheckRowsForm(bool exists, const char* what, RowsSide side, Head head) {
+  EPS_CHECK_MSG(exists, "the " << what << "ZERO-term rows have no " << kHeadNames[head] << " head on the "
+                               << kRowsSideNames[side] << " side");
+}
+
 void CheckZeroRows(const ZeroRowsArgs& a) {
   const DType dt = a.w.dt;
   EPS_CHECK(a.m >= 1 && a.nparts >= 1 && a.tpart.dt == dt && a.tpart.n >= static_cast<int64_t>(a.nparts) * a.m);
   EPS_CHECK(a.w.n == a.m && a.r.n == a.m && a.r.dt == dt);
-  if (a.x_free) {  // x alone in the state's place; no term, so nothing else of the record is read
-    EPS_CHECK_MSG(a.tall && !a.smooth && !a.zone.ridge && a.zone.step == kStepZone,
-                  "free x is the tall form without a term on x");
+  const Head head = a.zone.head;
+  CheckRowsForm(ZeroRowsExist(a.side, head), "", a.side, head);
+  if (a.side == kRowsXFree) {  // x alone in the state's place; no term, so nothing else of the record is read
     EPS_CHECK(a.xcur.n == a.m && a.xcur.dt == dt);
     return;
   }
   CheckState(a.state, a.m, dt);
   for (const DVec* v : {&a.rhs, &a.g, &a.zone.alpha_vec, &a.zone.beta_vec})
     if (v->n > 0) EPS_CHECK(v->n == a.m && v->dt == dt);
-  EPS_CHECK_MSG(!(a.tall && a.smooth), "the tall ZERO-term x side has no smooth form");
-  EPS_CHECK_MSG(!a.zone.ridge || a.tall, "a ridge term is on the x side: the rows take it in the tall form alone");
-  const ZoneStep step = a.zone.step;
-  EPS_CHECK_MSG(step != kStepLinear || a.tall, "a linear term is on the x side: the rows take it in the tall form alone");
-  EPS_CHECK_MSG(step != kStepLinear || a.g.n == a.m, "a linear term carries its vector g, one value per entry of x");
-  EPS_CHECK_MSG(step != kStepNonNeg || !a.tall, "the non-negative cone is on the z side: the rows take it in the fat form alone");
-  EPS_CHECK_MSG(step == kStepZone || (!a.zone.ridge && !a.smooth), "one head per side: a step, a ridge term or a smooth term");
-  if (!a.smooth) return;
+  EPS_CHECK_MSG(head != kHeadLinear || a.g.n == a.m, "a linear term carries its vector g, one value per entry of x");
+  if (head != kHeadSmooth) return;
   EPS_CHECK_MSG(a.fn == SMOOTH_LOGISTIC, "the fused ZERO-term rows take SUM_LOGISTIC alone, got " << a.fn);
   for (const DVec* v : {&a.hs, &a.hys, &a.hv}) EPS_CHECK(v->n == a.m && v->dt == dt);
+}
+
+const char* RowsTag(RowsSide side, bool batched) {
+  if (side == kRowsXFree) return batched ? "batch_zero_tall_free_cols" : "zero_tall_free_cols";
+  if (side == kRowsX) return batched ? "batch_zero_tall_cols" : "zero_tall_cols";
+  return batched ? "batch_zero_rows" : "zero_fused_rows";
 }
 
 }  // namespace
 
 void ZeroFusedRows(const ZeroRowsArgs& a) {
   CheckZeroRows(a);
-  ProfScope prof(a.x_free ? "zero_tall_free_cols" : a.tall ? "zero_tall_cols" : "zero_fused_rows", a.m, a.nparts);
-  if (a.x_free) {
-    if (a.w.dt == F32) LaunchZeroFreeCols<float>(a);
-    else LaunchZeroFreeCols<double>(a);
-  } else if (a.tall && a.zone.ridge) {
-    if (a.w.dt == F32) LaunchZeroRows<float, kZeroRows, RidgeStep, true>(a);
-    else LaunchZeroRows<double, kZeroRows, RidgeStep, true>(a);
-  } else if (a.tall && a.zone.step == kStepLinear) {
-    if (a.w.dt == F32) LaunchZeroRows<float, kZeroRows, LinearStep, true>(a);
-    else LaunchZeroRows<double, kZeroRows, LinearStep, true>(a);
-  } else if (a.tall) {
-    if (a.w.dt == F32) LaunchZeroRows<float, kZeroRows, void, true>(a);
-    else LaunchZeroRows<double, kZeroRows, void, true>(a);
-  } else if (a.zone.step == kStepNonNeg) {
-    if (a.w.dt == F32) LaunchZeroRows<float, kZeroRows, NonNegStep, false>(a);
-    else LaunchZeroRows<double, kZeroRows, NonNegStep, false>(a);
-  } else if (a.smooth) {
-    if (a.w.dt == F32) LaunchZeroRows<float, kZeroSmoothRows, FnLogistic>(a);
-    else LaunchZeroRows<double, kZeroSmoothRows, FnLogistic>(a);
-  } else {
-    if (a.w.dt == F32) LaunchZeroRows<float, kZeroRows, void>(a);
-    else LaunchZeroRows<double, kZeroRows, void>(a);
-  }
+  ProfScope prof(RowsTag(a.side, false), a.m, a.nparts);
+  if (a.w.dt == F32) LaunchZeroRows<float>(a);
+  else LaunchZeroRows<double>(a);
   EPS_HIP(hipGetLastError());
 }
 
@@ -722,36 +676,22 @@ void ZeroRowsBatchUpload(const std::vector<const ZeroRowsArgs*>& members, DVec* 
   const ZeroRowsArgs& lead = *members[0];
   for (const ZeroRowsArgs* a : members) {
     CheckZeroRows(*a);
-    EPS_CHECK(a->m == lead.m && a->nparts == lead.nparts && a->smooth == lead.smooth && a->w.dt == lead.w.dt);
-    EPS_CHECK(a->tall == lead.tall && a->x_free == lead.x_free);
-    EPS_CHECK_MSG(!a->zone.ridge, "the batched rows have no ridge form");
-    EPS_CHECK_MSG(a->zone.step == kStepZone, "the batched rows have no linear and no non-negative form");
+    EPS_CHECK(a->m == lead.m && a->nparts == lead.nparts && a->w.dt == lead.w.dt);
+    EPS_CHECK(a->side == lead.side && a->zone.head == lead.zone.head);
+    CheckRowsForm(BatchRowsExist(a->side, a->zone.head), "batched ", a->side, a->zone.head);
   }
   if (lead.w.dt == F32) UploadRowsT<float>(members, table);
   else UploadRowsT<double>(members, table);
 }
 
-void ZeroFusedRowsBatch(int64_t m, int nparts, bool smooth, DType dt, const DVec& table, int count, bool tall,
-                        bool x_free) {
+void ZeroFusedRowsBatch(int64_t m, int nparts, RowsSide side, Head head, DType dt, const DVec& table, int count) {
   const int64_t record = dt == F32 ? sizeof(ZeroRowsInst<float>) : sizeof(ZeroRowsInst<double>);
   EPS_CHECK(m >= 1 && nparts >= 1 && count >= 1 && count <= 65535);
   EPS_CHECK(table.dt == F64 && table.n * 8 >= count * record);
-  EPS_CHECK_MSG(!(tall && smooth), "the tall ZERO-term x side has no smooth form");
-  EPS_CHECK_MSG(!x_free || tall, "free x is the tall form");
-  ProfScope prof(x_free ? "batch_zero_tall_free_cols" : tall ? "batch_zero_tall_cols" : "batch_zero_rows", m, count);
-  if (x_free) {
-    if (dt == F32) LaunchZeroFreeColsBatch<float>(m, nparts, table, count);
-    else LaunchZeroFreeColsBatch<double>(m, nparts, table, count);
-  } else if (tall) {
-    if (dt == F32) LaunchZeroRowsBatch<float, kZeroRows, void, true>(m, nparts, table, count);
-    else LaunchZeroRowsBatch<double, kZeroRows, void, true>(m, nparts, table, count);
-  } else if (smooth) {
-    if (dt == F32) LaunchZeroRowsBatch<float, kZeroSmoothRows, FnLogistic>(m, nparts, table, count);
-    else LaunchZeroRowsBatch<double, kZeroSmoothRows, FnLogistic>(m, nparts, table, count);
-  } else {
-    if (dt == F32) LaunchZeroRowsBatch<float, kZeroRows, void>(m, nparts, table, count);
-    else LaunchZeroRowsBatch<double, kZeroRows, void>(m, nparts, table, count);
-  }
+  CheckRowsForm(BatchRowsExist(side, head), "batched ", side, head);
+  ProfScope prof(RowsTag(side, true), m, count);
+  if (dt == F32) LaunchZeroRowsBatch<float>(m, nparts, side, head, table, count);
+  else LaunchZeroRowsBatch<double>(m, nparts, side, head, table, count);
   EPS_HIP(hipGetLastError());
 }
 
@@ -777,7 +717,7 @@ void ZeroTallSamplesBatch(int64_t m, DType dt, const DVec& table, int count) {
 }
 
 void ZeroSmoothHead(const ZeroRowsArgs& a) {
-  EPS_CHECK(a.smooth);
+  EPS_CHECK(a.zone.head == kHeadSmooth);
   CheckZeroRows(a);
   ProfScope prof("zero_fused_head", a.m);
   if (a.w.dt == F32) LaunchZeroSmoothHead<float>(a);
@@ -1071,22 +1011,17 @@ void LassoFusedPass(const LassoFusedArgs& a) {
   const DType dt = a.A.dt;
   const LassoInstance& s = a.inst;
   EPS_CHECK(s.w.n == a.m && s.w.dt == dt);
-  CheckState(s.state, a.n, dt, /*zero_prev=*/a.chain >= 1 && a.chain <= 3);
+  EPS_CHECK(a.chain >= kChainLasso && a.chain <= kChainZeroTallAcc);
+  CheckState(s.state, a.n, dt, /*zero_prev=*/ChainKeepsZeroPrev(a.chain));
   for (const DVec* v : {&s.zone.alpha_vec, &s.zone.beta_vec})
     if (v->n > 0) EPS_CHECK(v->n == a.n && v->dt == dt);
-  if (a.chain == 1) EPS_CHECK(a.e1.n == a.n && a.e1.dt == dt);
-  EPS_CHECK(a.chain >= 0 && a.chain <= 5);
-  EPS_CHECK_MSG(!s.zone.ridge || a.chain == 2, "a ridge term is on the x side: the pass takes it in chain 2 alone");
-  const ZoneStep step = s.zone.step;
-  EPS_CHECK_MSG(step != kStepLinear || a.chain == 2, "a linear term is on the x side: the pass takes it in chain 2 alone");
-  EPS_CHECK_MSG(step != kStepLinear || (s.zg.n == a.n && s.zg.dt == dt),
+  if (a.chain == kChainTwoBlock) EPS_CHECK(a.e1.n == a.n && a.e1.dt == dt);
+  const Head head = s.zone.head;
+  EPS_CHECK_MSG(head != kHeadLinear || (s.zg.n == a.n && s.zg.dt == dt),
                 "a linear term carries its vector g, one value per column");
-  EPS_CHECK_MSG(step != kStepNonNeg || a.chain == 3,
-                "the non-negative cone is on the z side: the pass takes it in chain 3 alone");
-  EPS_CHECK_MSG(step == kStepZone || !s.zone.ridge, "one head per side: a step or a ridge term");
-  if (a.chain == 4) EPS_CHECK(s.zd.n == a.n && s.zd.dt == dt);
-  if (a.chain == 5) EPS_CHECK(s.zfarg.n == a.n && s.zfarg.dt == dt);
-  if (a.chain == 3)
+  if (a.chain == kChainZeroTallDot) EPS_CHECK(s.zd.n == a.n && s.zd.dt == dt);
+  if (a.chain == kChainZeroTallAcc) EPS_CHECK(s.zfarg.n == a.n && s.zfarg.dt == dt);
+  if (a.chain == kChainZeroTall)
     for (const DVec* v : {&s.zg, &s.zrhs})
       if (v->n > 0) EPS_CHECK(v->n == a.n && v->dt == dt);
   const int grid = LassoFusedGrid(a.m, a.n, dt);
@@ -1094,11 +1029,10 @@ void LassoFusedPass(const LassoFusedArgs& a) {
   EPS_CHECK(s.tpart.n >= static_cast<int64_t>(grid) * a.m && s.tpart.dt == dt);
   EPS_CHECK(reinterpret_cast<uintptr_t>(s.w.data()) % 16 == 0 &&
             reinterpret_cast<uintptr_t>(s.tpart.data()) % 16 == 0);
-  EPS_CHECK_MSG(a.chain < 4 || block == 256, "the halves of the tall pass take 256-thread shapes alone");
-  EPS_CHECK_MSG(step == kStepZone || block == 256, "the linear and the non-negative head take 256-thread shapes alone");
-  static const char* const kTags[] = {"lasso_fused", "lasso_fused", "zero_fused", "zero_tall", "zero_tall_dot",
-                                      "zero_tall_acc"};
-  ProfScope prof(kTags[a.chain], a.m, a.n);
+  const char* tag = kChainTags[a.chain][0];
+  EPS_CHECK_MSG(FusedPassExists(a.chain, head, block),
+                "the fused pass \"" << tag << "\" has no " << kHeadNames[head] << " head with " << block << " threads");
+  ProfScope prof(tag, a.m, a.n);
   NoteFusedResidency(a.qfull, a.jcut);
   if (dt == F32) LaunchFusedT<float>(a, grid, block);
   else LaunchFusedT<double>(a, grid, block);

@@ -16,16 +16,11 @@
 // order of forward updates, and this file is compiled with -ffp-contract=off as kernels_fused.hip
 // is - so every instance's iterates are bit-identical to its own solve.
 //
-// CHAIN 2: the instances are ZERO-term problems and a column runs the single
-// pass's MODE 2 - ZeroChainT and its stores, e0 among them - in place of ChainOneT; everything
-// around the chain is the same code.
-//
-// CHAIN 3, 4, 5: the instances are TALL ZERO-term problems (DESIGN.md 3.11 "Tall C") and a column -
-// a sample of the transposed copy - runs the single pass's MODE 3, 4 or 5.  3: ZeroTallChainT with
-// the member's own offset, rhs, ke and dinv, and MODE 3's stores.  4: the dot products alone, stored
-// by thread 0 to the member's zd; no t' registers.  5: the member's zfarg of the sample and the
-// forward update alone; no w registers, no reduction, no barrier.  In 3 and 5 the members' values of
-// a sample (state, offset, rhs; zfarg) are fetched by one lane per member and read from its register.
+// CHAIN (Chain, kernels.h: the batched forms are those of BatchPassExists): a column runs the single
+// pass's step of that chain, its stores among them, on every member's own record; everything around
+// the chain is the same code.  kChainZeroTallDot holds no t' registers, kChainZeroTallAcc no w
+// registers.  In kChainZeroTall and kChainZeroTallAcc the members' values of a sample (state, offset,
+// rhs; zfarg) are fetched by one lane per member and read from its register.
 #include <hip/hip_runtime.h>
 
 #include <vector>
@@ -73,9 +68,9 @@ __global__ __launch_bounds__(kBlock) void LassoBatchStreamKernel(int64_t m, int6
   for (int i = 0; i < KB; ++i) {
 #pragma unroll
     for (int q = 0; q < NR; ++q) {
-      if constexpr (CHAIN != 5)
+      if constexpr (CHAIN != kChainZeroTallAcc)
         wv[i][q] = (i < nk && row[q] < m) ? *reinterpret_cast<const V*>(tab[i].w + row[q]) : zero;
-      if constexpr (CHAIN != 4) tp[i][q] = zero;
+      if constexpr (CHAIN != kChainZeroTallDot) tp[i][q] = zero;
     }
   }
   // this workgroup's columns: exactly those of LassoFusedStreamKernelT, in its order
@@ -95,17 +90,17 @@ __global__ __launch_bounds__(kBlock) void LassoBatchStreamKernel(int64_t m, int6
       else a[q] = zero;
     }
   };
-  // CHAIN 3 and 5: lane i of every wave fetches member i's values of a sample - one vector load
+  // kChainZeroTall and kChainZeroTallAcc: lane i of every wave fetches member i's values of a sample - one vector load
   // per array for all members, in flight together - and the member's step reads them from that
   // lane's register (LaneValue).  Member by member through the table they are KB dependent scalar
   // loads, each waited for, which is what a sample then costs.  The values are the same.
   [[maybe_unused]] const T *pu = nullptr, *py0 = nullptr, *py1 = nullptr, *pg = nullptr, *pr = nullptr,
                            *pf = nullptr;
-  if constexpr (CHAIN == 3 || CHAIN == 5) {
+  if constexpr (CHAIN == kChainZeroTall || CHAIN == kChainZeroTallAcc) {
     static_assert(KB <= 64, "a lane per member");
     if (lane < nk) {
       const LassoBatchInst<T>& L = tab[lane];
-      if constexpr (CHAIN == 3) {
+      if constexpr (CHAIN == kChainZeroTall) {
         pu = L.u;
         py0 = L.y0;
         py1 = L.y1;
@@ -128,9 +123,9 @@ __global__ __launch_bounds__(kBlock) void LassoBatchStreamKernel(int64_t m, int6
     if (jn >= 0) load(nxt, jn);
     // every instance's column state is read before the barrier: thread 0 overwrites it after
     [[maybe_unused]] T uj[KB], y0j[KB], y1j[KB];
-    [[maybe_unused]] T gj[KB], rj[KB];  // CHAIN 3: the member's offset and rhs of this sample
+    [[maybe_unused]] T gj[KB], rj[KB];  // kChainZeroTall: the member's offset and rhs of this sample
     [[maybe_unused]] T su = T(0), sy0 = T(0), sy1 = T(0), sg = T(0), sr = T(0), sf = T(0);  // lane i: member i's
-    if constexpr (CHAIN == 3) {
+    if constexpr (CHAIN == kChainZeroTall) {
       if (lane < nk) {
         su = pu[j];
         sy0 = py0[j];
@@ -139,25 +134,25 @@ __global__ __launch_bounds__(kBlock) void LassoBatchStreamKernel(int64_t m, int6
         if (pr != nullptr) sr = pr[j];
       }
     }
-    if constexpr (CHAIN == 5) {
+    if constexpr (CHAIN == kChainZeroTallAcc) {
       if (lane < nk) sf = pf[j];
     }
 #pragma unroll
     for (int i = 0; i < KB; ++i) {
       if (i >= nk) continue;
-      if constexpr (CHAIN <= 2) {
+      if constexpr (CHAIN == kChainLasso || CHAIN == kChainZeroCols) {
         uj[i] = tab[i].u[j];
         y0j[i] = tab[i].y0[j];
         y1j[i] = tab[i].y1[j];
       }
-      if constexpr (CHAIN == 3) {
+      if constexpr (CHAIN == kChainZeroTall) {
         uj[i] = LaneValue(su, i);
         y0j[i] = LaneValue(sy0, i);
         y1j[i] = LaneValue(sy1, i);
         gj[i] = LaneValue(sg, i);
         rj[i] = LaneValue(sr, i);
       }
-      if constexpr (CHAIN != 5) {
+      if constexpr (CHAIN != kChainZeroTallAcc) {
         T d = T(0);
 #pragma unroll
         for (int q = 0; q < NR; ++q)
@@ -167,8 +162,8 @@ __global__ __launch_bounds__(kBlock) void LassoBatchStreamKernel(int64_t m, int6
         if (lane == 0) red[par][i][wave] = d;
       }
     }
-    if constexpr (CHAIN != 5) __syncthreads();
-    if constexpr (CHAIN == 4) {
+    if constexpr (CHAIN != kChainZeroTallAcc) __syncthreads();
+    if constexpr (CHAIN == kChainZeroTallDot) {
 #pragma unroll
       for (int i = 0; i < KB; ++i) {
         if (i >= nk) continue;
@@ -177,7 +172,7 @@ __global__ __launch_bounds__(kBlock) void LassoBatchStreamKernel(int64_t m, int6
         for (int w2 = 1; w2 < kBlock / 64; ++w2) d += red[par][i][w2];
         if (tid == 0) tab[i].zd[j] = d;
       }
-    } else if constexpr (CHAIN == 5) {
+    } else if constexpr (CHAIN == kChainZeroTallAcc) {
 #pragma unroll
       for (int i = 0; i < KB; ++i) {
         if (i >= nk) continue;
@@ -249,22 +244,13 @@ __global__ __launch_bounds__(kBlock) void LassoBatchStreamKernel(int64_t m, int6
         c.beta = I.beta_v != nullptr ? I.beta_v[j] : I.beta;
         c.M = I.M;
         T v0n;
-        if constexpr (CHAIN == 3) {
+        if constexpr (CHAIN == kChainZeroCols || CHAIN == kChainZeroTall) {
           T ns, nq, nys, nyq, nu;
-          v0n = ZeroTallChainT<T>(d, c, I.ke, I.dinv, gj[i], rj[i], uj[i], y1j[i], y0j[i], &ns, &nq, &nys, &nyq,
-                                  &nu);
-          if (tid == 0) {
-            I.y1prev[j] = y1j[i];
-            I.e0[j] = y0j[i];
-            I.x1[j] = ns;
-            I.x0[j] = nq;
-            I.y1[j] = nys;
-            I.y0[j] = nyq;
-            I.u[j] = nu;
-          }
-        } else if constexpr (CHAIN == 2) {
-          T ns, nq, nys, nyq, nu;
-          v0n = ZeroChainT<T>(d, c, T(0), uj[i], y1j[i], y0j[i], &ns, &nq, &nys, &nyq, &nu);
+          if constexpr (CHAIN == kChainZeroCols)
+            v0n = ZeroChainT<T>(d, c, T(0), uj[i], y1j[i], y0j[i], &ns, &nq, &nys, &nyq, &nu);
+          else
+            v0n = ZeroTallChainT<T>(d, c, I.ke, I.dinv, gj[i], rj[i], uj[i], y1j[i], y0j[i], &ns, &nq, &nys, &nyq,
+                                    &nu);
           if (tid == 0) {
             I.y1prev[j] = y1j[i];
             I.e0[j] = y0j[i];
@@ -298,7 +284,7 @@ __global__ __launch_bounds__(kBlock) void LassoBatchStreamKernel(int64_t m, int6
     j = jn;
     step = step_n;
   }
-  if constexpr (CHAIN != 4) {
+  if constexpr (CHAIN != kChainZeroTallDot) {
 #pragma unroll
     for (int i = 0; i < KB; ++i) {
       if (i >= nk) continue;
@@ -321,48 +307,35 @@ int ChunksPerThread(int64_t m, DType dt) {
 // either type, the column and the next one in flight 8 NR more.  Chosen so that no
 // instantiation spills to scratch (hipcc -Rpass-analysis=kernel-resource-usage).
 constexpr int WidthFor(int nr) { return nr <= 2 ? 8 : nr <= 4 ? 6 : nr <= 8 ? 5 : 4; }
-// The ZERO chain's widths (CHAIN 2): its column step keeps a few more values live than the lasso's
-// ("Registers"), so a form that would spill at the lasso's width takes a smaller
-// one here; the lasso's widths are not touched.
-constexpr int ZeroWidthFor(int nr) { return WidthFor(nr); }
-// The tall ZERO chains.  CHAIN 3 keeps what CHAIN 2 keeps plus the sample's offset and rhs per
-// member.  CHAIN 4 holds no t' and CHAIN 5 no w - 4 NR registers per member instead of 8 NR - so
-// they carry more members per read of the matrix (DESIGN.md 3.6 has the registers of each form).
-constexpr int ZeroTallWidthFor(int nr) { return ZeroWidthFor(nr); }
-constexpr int ZeroTallHalfWidthFor(int nr) { return nr <= 2 ? 16 : nr <= 4 ? 12 : nr <= 8 ? 10 : 8; }
-constexpr int WidthFor(int nr, int chain) {
-  return chain == 2 ? ZeroWidthFor(nr)
-         : chain == 3 ? ZeroTallWidthFor(nr)
-         : chain >= 4 ? ZeroTallHalfWidthFor(nr)
-                      : WidthFor(nr);
+// Per chain.  The ZERO chains keep a few more values live per column step than the lasso's (DESIGN.md
+// 3.11, "Registers"; kChainZeroTall also the sample's offset and rhs per member): a form of theirs
+// that would spill at the lasso's width takes a smaller one without touching the lasso's.  The halves
+// of the tall pass hold no t' or no w - 4 NR registers per member instead of 8 NR - so they carry
+// more members per read of the matrix (DESIGN.md 3.6 has the registers of each form).
+constexpr int WidthFor(int nr, Chain chain) {
+  return ChainIsTallHalf(chain) ? (nr <= 2 ? 16 : nr <= 4 ? 12 : nr <= 8 ? 10 : 8) : WidthFor(nr);
 }
 
+// The one instantiation of the chain (BatchPassExists; LassoBatchPass has checked it), or the lasso
+// chain's group form.
 template <class T, int NR>
 void LaunchBatch(int grid, int64_t m, int64_t n, const T* A, int64_t lda, const LassoBatchInst<T>* tab, int nk,
-                 const double* glam, const FusedResidency& res, int chain) {
-  if (chain == 2)
-    hipLaunchKernelGGL((LassoBatchStreamKernel<T, NR, ZeroWidthFor(NR), false, 2>), dim3(grid), dim3(kBlock), 0,
-                       Runtime::Get().stream(), m, n, A, lda, tab, nk, 0.0, res.qfull, res.jcut);
-  else if (chain == 3)
-    hipLaunchKernelGGL((LassoBatchStreamKernel<T, NR, ZeroTallWidthFor(NR), false, 3>), dim3(grid), dim3(kBlock), 0,
-                       Runtime::Get().stream(), m, n, A, lda, tab, nk, 0.0, res.qfull, res.jcut);
-  else if (chain == 4)
-    hipLaunchKernelGGL((LassoBatchStreamKernel<T, NR, ZeroTallHalfWidthFor(NR), false, 4>), dim3(grid), dim3(kBlock),
-                       0, Runtime::Get().stream(), m, n, A, lda, tab, nk, 0.0, res.qfull, res.jcut);
-  else if (chain == 5)
-    hipLaunchKernelGGL((LassoBatchStreamKernel<T, NR, ZeroTallHalfWidthFor(NR), false, 5>), dim3(grid), dim3(kBlock),
-                       0, Runtime::Get().stream(), m, n, A, lda, tab, nk, 0.0, res.qfull, res.jcut);
-  else if (glam != nullptr)
-    hipLaunchKernelGGL((LassoBatchStreamKernel<T, NR, WidthFor(NR), true, 0>), dim3(grid), dim3(kBlock), 0,
-                       Runtime::Get().stream(), m, n, A, lda, tab, nk, *glam, res.qfull, res.jcut);
-  else
-    hipLaunchKernelGGL((LassoBatchStreamKernel<T, NR, WidthFor(NR), false, 0>), dim3(grid), dim3(kBlock), 0,
-                       Runtime::Get().stream(), m, n, A, lda, tab, nk, 0.0, res.qfull, res.jcut);
+                 const double* glam, const FusedResidency& res, Chain chain) {
+  decltype(&LassoBatchStreamKernel<T, NR, WidthFor(NR), false, kChainLasso>) kernel = nullptr;
+  WithChain(chain, [&](auto c) {
+    constexpr Chain kChain = decltype(c)::value;
+    if constexpr (BatchPassExists(kChain, kHeadZone))
+      kernel = LassoBatchStreamKernel<T, NR, WidthFor(NR, kChain), false, kChain>;
+  });
+  if (glam != nullptr) kernel = LassoBatchStreamKernel<T, NR, WidthFor(NR), true, kChainLasso>;
+  EPS_CHECK(kernel != nullptr);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, Runtime::Get().stream(), m, n, A, lda, tab, nk,
+                     glam != nullptr ? *glam : 0.0, res.qfull, res.jcut);
 }
 
 template <class T>
 void LaunchBatchT(int nr, int grid, int64_t m, int64_t n, const T* A, int64_t lda, const LassoBatchInst<T>* tab,
-                  int nk, const double* glam, const FusedResidency& res, int chain) {
+                  int nk, const double* glam, const FusedResidency& res, Chain chain) {
   switch (nr) {
     case 1: LaunchBatch<T, 1>(grid, m, n, A, lda, tab, nk, glam, res, chain); break;
     case 2: LaunchBatch<T, 2>(grid, m, n, A, lda, tab, nk, glam, res, chain); break;
@@ -377,18 +350,12 @@ void UploadT(const std::vector<const LassoInstance*>& members, DVec* table) {
   std::vector<LassoBatchInst<T>> host;
   host.reserve(members.size());
   for (const LassoInstance* s : members) host.push_back(Narrow<T>(*s));
-  const size_t bytes = host.size() * sizeof(LassoBatchInst<T>);
-  const int64_t words = static_cast<int64_t>((bytes + 7) / 8);
-  if (table->n < words || table->dt != F64) *table = DVec::Empty(words < 1 ? 1 : words, F64);
-  if (bytes == 0) return;
-  Runtime& rt = Runtime::Get();
-  EPS_HIP(hipMemcpyAsync(table->data(), host.data(), bytes, hipMemcpyHostToDevice, rt.stream()));
-  rt.Sync();  // `host` goes out of scope
+  UploadRecords(host, table);
 }
 
 }  // namespace
 
-int LassoBatchWidth(int64_t m, int64_t n, DType dt, int chain) {
+int LassoBatchWidth(int64_t m, int64_t n, DType dt, Chain chain) {
   if (LassoFusedBlock(m, n, dt) != kBlock) return 0;
   return WidthFor(ChunksPerThread(m, dt), chain);
 }
@@ -400,17 +367,17 @@ void LassoBatchUpload(const std::vector<const LassoInstance*>& members, DType dt
       EPS_CHECK(v->dt == dt && v->n > 0);
     for (const DVec* v : {&c.y_zero_prev, &s->zg, &s->zrhs, &s->zd, &s->zfarg})
       EPS_CHECK(v->n == 0 || (v->dt == dt && v->n == c.u.n));
-    EPS_CHECK_MSG(!s->zone.ridge, "the batched pass has no ridge form");
-    EPS_CHECK_MSG(s->zone.step == kStepZone, "the batched pass has no linear and no non-negative form");
+    EPS_CHECK_MSG(s->zone.head == kHeadZone, "the batched pass has no " << kHeadNames[s->zone.head] << " head");
   }
   if (dt == F32) UploadT<float>(members, table);
   else UploadT<double>(members, table);
 }
 
 void LassoBatchPass(int64_t m, int64_t n, int64_t lda, const DVec& A, const DVec& table, int first, int count,
-                    const double* group_lam, const FusedResidency& res, int chain) {
+                    const double* group_lam, const FusedResidency& res, Chain chain) {
   const DType dt = A.dt;
-  EPS_CHECK_MSG(chain == 0 || (chain >= 2 && chain <= 5 && group_lam == nullptr),
+  EPS_CHECK_MSG(chain >= kChainLasso && chain <= kChainZeroTallAcc && BatchPassExists(chain, kHeadZone) &&
+                    (chain == kChainLasso || group_lam == nullptr),
                 "batched fused pass: chain " << chain);
   EPS_CHECK(LassoFusedSupported(m, n, A, lda));
   EPS_CHECK(res.qfull >= 0 && res.jcut >= 0 && res.jcut <= n);
@@ -419,9 +386,7 @@ void LassoBatchPass(int64_t m, int64_t n, int64_t lda, const DVec& A, const DVec
                 "batched fused pass: " << count << " instances, width " << width);
   const int grid = LassoFusedGrid(m, n, dt);
   const int nr = ChunksPerThread(m, dt);
-  static const char* const kTags[] = {"batch_fused_pass",     "batch_fused_pass",    "batch_zero_pass",
-                                      "batch_zero_tall_pass", "batch_zero_tall_dot", "batch_zero_tall_acc"};
-  ProfScope prof(kTags[chain], m, n);
+  ProfScope prof(kChainTags[chain][1], m, n);
   NoteFusedResidency(res.qfull, res.jcut);
   if (dt == F32)
     LaunchBatchT<float>(nr, grid, m, n, A.as<float>(), lda,

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
+#include <vector>
 
 #include "kernels.h"
 #include "kernels_smooth_fn.h"
@@ -104,6 +105,17 @@ template <class T> LassoBatchInst<T> Narrow(const LassoInstance& s) {
   return d;
 }
 
+// The records of a batch's members in order into `table` (device; grown as needed).
+template <class Inst> void UploadRecords(const std::vector<Inst>& host, DVec* table) {
+  const size_t bytes = host.size() * sizeof(Inst);
+  const int64_t words = static_cast<int64_t>((bytes + 7) / 8);
+  if (table->n < words || table->dt != F64) *table = DVec::Empty(words < 1 ? 1 : words, F64);
+  if (bytes == 0) return;
+  Runtime& rt = Runtime::Get();
+  EPS_HIP(hipMemcpyAsync(table->data(), host.data(), bytes, hipMemcpyHostToDevice, rt.stream()));
+  rt.Sync();  // `host` goes out of scope with the caller
+}
+
 template <class T> __device__ inline T WaveSumT(T v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
@@ -174,17 +186,48 @@ __device__ inline T ChainOneT(T d, const FusedScalarsT<T>& c, T u, T y0p, T y1p,
 // needs the boundary state alone; the tail needs this sweep's w.
 // Fn (kernels_smooth_fn.h): a smooth separable term in place of the zone, its prox the fp64 Newton
 // of SmoothProxKernel on the rounded input with the operator's own weight `lam64`.
-// RidgeStep in the Fn slot (the x side alone): the term is a scalar least-squares prox
-// (ScalarLeastSquaresDesc, ZoneParams::ridge) and its variable the block solve's two scalar-map
+// RidgeStep in the Fn slot (kHeadRidge, the x side alone): the term is a scalar least-squares prox
+// (ScalarLeastSquaresDesc) and its variable the block solve's two scalar-map
 // applies on the prox input, s = Cs (Bs ub): no offset, no zone, one rounding per multiply.
-// LinearStep in the Fn slot (the x side alone): the term is linear (SeparableDesc::kLinear,
-// ZoneParams::step) and its variable the block solve's forward step on the row that holds the
+// LinearStep in the Fn slot (kHeadLinear, the x side alone): the term is linear (SeparableDesc::kLinear)
+// and its variable the block solve's forward step on the row that holds the
 // constant and the pivot, s = Cs (Bs ub + g): `g` is the per-element constant -alpha c_j, passed where
-// the offset goes.  NonNegStep (the z side alone): the non-negative cone in the zone's place,
-// max(vin, 0) as MaxZeroKernel computes it (kernels_prox.hip), with the zone's offset handling.
+// the offset goes.  NonNegStep (kHeadNonNeg, the z side alone): the non-negative cone in the zone's
+// place, max(vin, 0) as MaxZeroKernel computes it (kernels_prox.hip), with the zone's offset handling.
 struct RidgeStep {};
 struct LinearStep {};
 struct NonNegStep {};
+// A head as the type in the Fn slot: `void` the zone, FnLogistic the smooth term (the one smooth
+// function the fused kernels take).  WithHead calls f(HeadTag<Fn>()) for the head's type, so that a
+// launcher names its instantiation once, behind `if constexpr` on the tables of kernels.h.
+template <class Fn> struct HeadTag { typedef Fn type; };
+template <class Fn> constexpr Head HeadOf() {
+  return std::is_same<Fn, RidgeStep>::value    ? kHeadRidge
+         : std::is_same<Fn, LinearStep>::value ? kHeadLinear
+         : std::is_same<Fn, NonNegStep>::value ? kHeadNonNeg
+         : std::is_void<Fn>::value             ? kHeadZone
+                                               : kHeadSmooth;
+}
+template <class F> void WithHead(Head h, F f) {
+  switch (h) {
+    case kHeadZone: return f(HeadTag<void>());
+    case kHeadRidge: return f(HeadTag<RidgeStep>());
+    case kHeadLinear: return f(HeadTag<LinearStep>());
+    case kHeadNonNeg: return f(HeadTag<NonNegStep>());
+    case kHeadSmooth: return f(HeadTag<FnLogistic>());
+  }
+}
+// The same for a chain: f(std::integral_constant<Chain, c>()).
+template <class F> void WithChain(Chain c, F f) {
+  switch (c) {
+    case kChainLasso: return f(std::integral_constant<Chain, kChainLasso>());
+    case kChainTwoBlock: return f(std::integral_constant<Chain, kChainTwoBlock>());
+    case kChainZeroCols: return f(std::integral_constant<Chain, kChainZeroCols>());
+    case kChainZeroTall: return f(std::integral_constant<Chain, kChainZeroTall>());
+    case kChainZeroTallDot: return f(std::integral_constant<Chain, kChainZeroTallDot>());
+    case kChainZeroTallAcc: return f(std::integral_constant<Chain, kChainZeroTallAcc>());
+  }
+}
 template <class T> struct ZeroHeadT {
   T s, ys, v;  // the separable term's variable and y; the ZERO prox's input on this row
 };

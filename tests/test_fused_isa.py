@@ -47,3 +47,9 @@ def test_fused_stream_kernels_keep_nontemporal_loads_and_no_scratch(tmp_path):
     for name in sorted(nt_loads):
         assert scratch[name] == 0, "%s uses %d bytes of scratch" % (name, scratch[name])
         assert nt_loads[name] >= 1, "%s has no non-temporal 16-byte load" % name
+    # exactly the forms of FusedPassExists (kernels.h), not the product of chains and heads
+    assert len(nt_loads) == 120, (
+        "%d streaming kernels, expected 120: with 256 threads 5 chunk counts x 9 forms (six chains with the zone or "
+        "no head, the column chain with the ridge and the linear head, the tall chain with the cone) in f32 and in "
+        "f64 = 90; with 512 threads 4 chunk counts (f32) + 2 (f64) x 5 forms (the first four chains, the column "
+        "chain with the ridge head) = 30" % len(nt_loads))

@@ -69,8 +69,8 @@ def test_paths_are_bit_identical_with_mixed_stopping(solve_mod, kind, shape, dty
                                               ("f64", "logreg", 7, {"dot": 12, "acc": 12})])
 def test_launch_counts_and_shared_setup(solve_mod, dt, kind, k, widths):
     """Widths of the tall chains per (chunks per thread, dtype): DESIGN.md 3.6 (n = 1028 is two
-    16-byte chunks per thread in f32, chain 3: width 8; three, run as four, in f64, chains 4 and 5:
-    width 12)."""
+    16-byte chunks per thread in f32, kChainZeroTall: width 8; three, run as four, in f64, the two
+    halves of the tall pass: width 12)."""
     shape, n_sweeps = (2051, 1028), 60
     batch, tagsb, single, tags1 = rs.run_both(solve_mod, rs.members(kind, shape, k), dt, ON, max_iterations=n_sweeps,
                                               **FIXED)
@@ -92,7 +92,7 @@ def test_launch_counts_and_shared_setup(solve_mod, dt, kind, k, widths):
 
 # ---- 3. more members than one launch holds --------------------------------------------------------
 def test_more_members_than_one_launch_holds(solve_mod):
-    """f32 at one chunk per thread: chain 3 has width 8, so 9 members are launches
+    """f32 at one chunk per thread: kChainZeroTall has width 8, so 9 members are launches
     of 8 and 1"""
     k, n_sweeps = 9, 30
     batch, tagsb, single, _ = rs.run_both(solve_mod, rs.members("hinge", (601, 256), k), "f32", ON,

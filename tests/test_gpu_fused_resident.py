@@ -9,8 +9,8 @@ every variable and the same four residuals.
 A row chunk is what one load instruction of the workgroup covers: 4 KB of a column at 256 threads,
 8 KB at 512.  Rows 2560 (f32: 2.5 chunks, f64: 5) with an odd number of columns (a trailing unpaired
 column), 4 (one chunk, smaller than a workgroup), 10244 (the 512-thread form), the two-block driver
-and basis pursuit (chains 1 and 2) on small shapes, and a 3-member lambda path through solve_batch
-at 2048 x 4100 (the batched pass, on the whitened route)."""
+and basis pursuit (kChainTwoBlock and kChainZeroCols) on small shapes, and a 3-member lambda path
+through solve_batch at 2048 x 4100 (the batched pass, on the whitened route)."""
 
 import ctypes
 
@@ -129,8 +129,8 @@ CASES = [
     ("lasso", 2560, 2701, "f64", {}, "lasso_fused"),
     ("lasso", 4, 7, "f32", {}, "lasso_fused"),          # one chunk, smaller than a workgroup
     ("lasso", 10244, 10261, "f32", {}, "lasso_fused"),  # the 512-thread form
-    ("lasso", 1536, 1601, "f32", {"solver": 1}, "lasso_fused"),  # two-block driver: chain 1
-    ("bp", 1536, 2051, "f32", {}, "zero_fused"),                 # ZERO route: chain 2
+    ("lasso", 1536, 1601, "f32", {"solver": 1}, "lasso_fused"),  # two-block driver: kChainTwoBlock
+    ("bp", 1536, 2051, "f32", {}, "zero_fused"),                 # ZERO route: kChainZeroCols
 ]
 
 

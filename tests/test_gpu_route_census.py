@@ -33,7 +33,7 @@ SWEEPS = dict(max_iterations=5, epoch_iterations=5)
 # the sweep's launches by route; a tag of this universe that a row's route does not name must be absent
 ROUTES = {
     "generic": (),
-    "lasso": ("lasso_fused",),              # the pass over A (two-block driver: chain 1, the same tag)
+    "lasso": ("lasso_fused",),              # the pass over A (two-block driver: kChainTwoBlock, the same tag)
     "lasso_tall": ("lasso_tall_cols",),
     "matrix": ("batch_fused_pass",),        # the columns of a matrix variable as members of the batched pass
     "basis_pursuit": ("zero_fused",),       # no z block: the partials go through the reduction
